@@ -30,7 +30,10 @@ ranks; 0 on one GPU) and the spread of the ranks' own time per step (`ms_per_ste
         one step = mlhip_kmeans_step = assignment + exact update sums + all-reduce of counts/sums + new centroids
         (ML/KMeans.cpp:82-108).
     python bench.py --workload em-diag [...]               diagonal-covariance EM at N=1M, d=16, K=16 (BASELINE.json
-        configs[1]; an extension: the reference has full covariances only)."""
+        configs[1]; an extension: the reference has full covariances only).
+    python bench.py ... --dump-outputs DIR                 after the timed steps, writes what the primary workload's last timed
+        step returned (EM: log_likelihood, mixing, means, covariances / variances; K-means: inertia, counts, centroids) as
+        DIR/<name>.npy in float64. The inputs depend only on the arguments, so two builds can be compared output for output."""
 import argparse
 import json
 import os
@@ -305,14 +308,15 @@ class Job:
         self.dist.all_gather_object(box, obj)
         return box
 
-    def timed(self, run, steps, warmup, names=(), live=True):
+    def timed(self, run, steps, warmup, names=(), live=True, after=None):
         """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.
         run(k) executes k steps. Returns (seconds, {kernel family: average ms per launch}).
         live: the kernels of the timed steps themselves carry HIP event pairs on the stream they are launched on; the
         pairs are only recorded inside the region and read after its closing barrier, so the region runs without any
         extra synchronisation (cost: a few microseconds per pair -- 0.1 % of an EM iteration, 0.5 % of a K-means step).
         not live (iterations of ~0.1 ms, where those microseconds would be 10 % of the metric): the region runs without
-        events and the same K steps are replayed with them right afterwards."""
+        events and the same K steps are replayed with them right afterwards.
+        after(): called once the timed region has closed, before any replay -- it sees the state of the last timed step."""
         if warmup:
             run(warmup)
         self.ctx.timing_reset()
@@ -324,6 +328,8 @@ class Job:
         own = time.perf_counter() - t0               # this rank's own steps, before it waits for the others
         self.barrier()
         elapsed = self.max_over_ranks(time.perf_counter() - t0)
+        if after is not None:
+            after()
         if names and not live:
             self.ctx.timing_enable(True)
             run(steps)
@@ -385,7 +391,23 @@ def traffic_for(kernel, headline):
         return None, None
 
 
-def kmeans_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as dirname/<name>.npy in float64. Should the arrays exceed DUMP_LIMIT_BYTES together (large
+    user-chosen shapes), each one over its share is replaced by a fixed, seeded sample of its flattened entries."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    share = DUMP_LIMIT_BYTES // 8 // len(arrays)
+    for name, a in arrays.items():
+        if sum(x.size for x in arrays.values()) * 8 > DUMP_LIMIT_BYTES and a.size > share:
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def kmeans_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples, dump_dir=None):
     """K-means steps/sec, N row-sharded over the ranks, centroids replicated, one all-reduce of [inertia, n_changed,
     counts(K), sums(K*d)] per step. Returns the report dict on rank 0 (None elsewhere)."""
     import numpy as np
@@ -396,21 +418,28 @@ def kmeans_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples):
     X = sample_rows(mix, lo, hi)             # chunk-wise definition: the same rows for any number of ranks
     data = _lib.Data(job.ctx, X)
     del X
-    state = {"C": mix.means + 0.3 * np.random.default_rng(1).standard_normal((K, d)), "inertia": None}
+    state = {"C": mix.means + 0.3 * np.random.default_rng(1).standard_normal((K, d)), "inertia": None, "counts": None}
 
     def run(k):
         if job.args.per_step_calls:
             for _ in range(k):
-                state["inertia"], _, _, state["C"] = data.kmeans_step(state["C"])
+                state["inertia"], _, state["counts"], state["C"] = data.kmeans_step(state["C"])
             return
         # the reference's step loop (ML/KMeans.cpp:80-110) in one call, tolerance 0: it can only stop early on identical
         # labels; exactly k steps are executed either way -- a converged loop is entered again
         done = 0
         while done < k:
-            n_steps, _, state["inertia"], _, state["C"], _ = data.kmeans_iterate(state["C"], k - done, 0.0)
+            n_steps, _, state["inertia"], state["counts"], state["C"], _ = data.kmeans_iterate(state["C"], k - done, 0.0)
             done += n_steps
 
-    elapsed, ms = job.timed(run, steps, warmup, ["kmeans_assign"])
+    last = {}
+
+    def keep_last():
+        last.update(inertia=[state["inertia"]], counts=np.array(state["counts"]), centroids=np.array(state["C"]))
+
+    elapsed, ms = job.timed(run, steps, warmup, ["kmeans_assign"], after=keep_last)
+    if dump_dir and job.rank == 0:
+        dump_outputs(dump_dir, last)
     k_ms = ms["kmeans_assign"]
     n_locals = job.rows_per_unit(data, hi - lo)
     out = None
@@ -460,7 +489,7 @@ def elapsed_hint_ms(n, d, K, diagonal, world):
     return flops / ((20e12 if diagonal or d < 12 else 60e12)) * 1e3
 
 
-def em_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples, diagonal=False):
+def em_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples, diagonal=False, dump_dir=None):
     """EM iterations/sec (full covariances, or the diagonal extension), N row-sharded over the ranks."""
     import numpy as np
     from ml_amd import _lib, synth
@@ -490,7 +519,15 @@ def em_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples, diagonal=Fals
         assert done == k
 
     names = ["em_diag", "em_close"] if diagonal else ["em_estep", "em_mstats", "em_fused", "em_close", "em_resident"]
-    elapsed, ms = job.timed(run, steps, warmup, names, live=(elapsed_hint_ms(n, d, K, diagonal, job.units) >= 1.0))
+    last = {}
+
+    def keep_last():
+        last.update({"log_likelihood": [state["ll"]], "mixing": np.array(state["pi"]), "means": np.array(state["mu"]),
+                     ("variances" if diagonal else "covariances"): np.array(state["S"])})
+
+    elapsed, ms = job.timed(run, steps, warmup, names, live=(elapsed_hint_ms(n, d, K, diagonal, job.units) >= 1.0), after=keep_last)
+    if dump_dir and job.rank == 0:
+        dump_outputs(dump_dir, last)
     ms.setdefault("em_fused_wide", 0.0)
     n_locals = job.rows_per_unit(data, hi - lo)
     if job.rank != 0:
@@ -662,11 +699,15 @@ def main():
                     help="--gpus N from ONE process through the library's device group (mlhip_ctx_create_group: one host thread per "
                          "shard, RCCL between distinct GPUs, an in-process sum when shards share a GPU) instead of one process per "
                          "GPU: what ml::EM::fit / cppyml.clustering.EM.fit use when MLHIP_NUM_GPUS is set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of the primary workload returned as DIR/<name>.npy")
     ap.add_argument("--dry-launch", action="store_true",
                     help="(test) start the ranks, join a gloo group, report the launch environment; no GPU work")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.single_process:
         return launch_ranks(args)
@@ -715,13 +756,13 @@ def main():
     with_cpu = args.gpus == 1 and not args.no_cpu_baseline
     if args.workload == "kmeans":
         out = kmeans_measure(job, args.n or 100_000_000, args.dim or 8, args.components or 256, args.steps, args.warmup,
-                             with_cpu, args.cpu_samples)
+                             with_cpu, args.cpu_samples, dump_dir=args.dump_outputs)
     elif args.workload == "em-diag":
         out = em_measure(job, args.n or 1_000_000, args.dim or 16, args.components or 16, args.steps, args.warmup,
-                         with_cpu, args.cpu_samples, diagonal=True)
+                         with_cpu, args.cpu_samples, diagonal=True, dump_dir=args.dump_outputs)
     else:
         out = em_measure(job, args.n or N_TOTAL, args.dim or DIM, args.components or COMPONENTS, args.steps, args.warmup,
-                         with_cpu, args.cpu_samples)
+                         with_cpu, args.cpu_samples, dump_dir=args.dump_outputs)
         default_shape = (args.n, args.dim, args.components) == (None, None, None)
         if args.gpus == 1 and default_shape and not args.no_secondary:
             # In the same driver-timed run (the EM block has been freed above), as a LIST:

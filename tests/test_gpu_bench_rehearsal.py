@@ -49,3 +49,41 @@ def test_three_rank_kmeans_and_diag_lines():
     d3 = _bench("--gpus", "3", "--allreduce", "gloo", "--workload", "em-diag", "--samples", "300000", "--steps", "3", "--warmup", "1")
     a, b = d1["config"]["final_mean_log_likelihood"], d3["config"]["final_mean_log_likelihood"]
     assert abs(a - b) <= 1e-12 * abs(a)
+
+
+@pytest.mark.parametrize("workload,n", [("em", 400000), ("em-diag", 300000)])
+def test_dumped_outputs_are_the_last_timed_step(tmp_path, workload, n):
+    """--dump-outputs writes what the primary workload's last timed step returned: warmup + steps iterations of mlhip_em_iterate
+    from the benchmark's start, and the same bytes on a second run with the same arguments (em-diag: the kernel times come from a
+    replay of the steps after the timed region, which must not leak into the dump)."""
+    import numpy as np
+    from ml_amd import _lib, synth
+    sys.path.insert(0, ROOT)
+    import bench
+    diagonal = workload == "em-diag"
+    runs = []
+    for r in range(2):
+        out = tmp_path / f"run{r}"
+        line = _bench("--workload", workload, "--samples", str(n), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                      "--dump-outputs", str(out))
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        runs.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    cov_name = "variances" if diagonal else "covariances"
+    assert sorted(runs[0]) == sorted(["log_likelihood", "mixing", "means", cov_name])
+    assert all(a.dtype == np.float64 for a in runs[0].values())
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
+
+    d, K = (16, 16) if diagonal else (32, 64)
+    mix = synth.Mixture(d, K, diagonal=diagonal)
+    ctx = _lib.Context(0)
+    data = _lib.Data(ctx, bench.sample_rows(mix, 0, n))
+    _, cov = data.sample_covariance()
+    S0 = np.stack([np.diag(cov)] * K) if diagonal else np.stack([cov] * K)
+    steps, _, ll, pi, mu, S, _ = data.em_iterate(np.full(K, 1.0 / K), mix.initial_means(), S0, 4, 0.0, 0.0, diagonal)
+    data.close()
+    ctx.close()
+    got = runs[0]
+    assert steps == 4 and abs(got["log_likelihood"][0] - ll) <= 1e-12 * abs(ll)
+    for name, want in (("mixing", pi), ("means", mu), (cov_name, S)):
+        assert np.max(np.abs(got[name] - want)) <= 1e-11 * np.max(np.abs(want)), name
