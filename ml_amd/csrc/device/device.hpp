@@ -88,6 +88,7 @@ struct MstatsArgs {
     double* stats;                                           // out: device, K*F + 1 doubles
     double* ll_scratch;                                      // kFromLogRespSelfNorm: >= 1024 doubles for the ll partials
     double* lse_out; double* ll_out;                         // kFromLogRespSelfNorm: per-sample max (-> lse) and exp-sum (n_pad each)
+    unsigned long long* nz_count;                            // kFromLogRespSelfNorm (may be null): += nonzero responsibilities
 };
 int launch_em_mstats_generic(const MstatsArgs& a, hipStream_t stream);   // d > kMaxDim: writes ONE partial block [K][F]
 /// 128 < d <= 1024 on the matrix cores (big_dim.hip); the plain tier above it and with MLHIP_BIG_DIM=0.
@@ -98,6 +99,11 @@ int launch_em_estep_big(const EstepArgs& a, int num_cus, hipStream_t stream);
 int launch_em_mstats_big(const MstatsArgs& a, int num_cus, hipStream_t stream);   // writes big_dim_splits partial blocks [K][F]
 /// Whether the statistics kernel chosen for (d, K) can normalise log-responsibilities itself (mode kFromLogRespSelfNorm).
 bool em_mstats_self_norm_supported(int d, int K, int num_cus);
+/// The sparse self-normalising statistics kernel (em_mstats_sparse.hip): same inputs, partial blocks and per-sample outputs as the
+/// self-normalising wide kernel, but it accumulates only the nonzero responsibilities. Returns the grid (the partial blocks
+/// written) or <= 0.
+bool em_mstats_sparse_supported(int d, int K, int num_cus);
+int launch_em_mstats_sparse(const MstatsArgs& a, int num_cus, hipStream_t stream);
 /// Fused E-step + statistics for small shapes (em_fused_small.hip): params are the estep_param_stride(D) records.
 struct FusedArgs {
     const double* xt; size_t ldx; uint32_t n; int d;

@@ -1,0 +1,192 @@
+// M-step sufficient statistics, SPARSE self-normalising variant (d <= 32, K <= 64): the same statistics as the wide kernel's
+// EXP = 2 form (em_mstats_wide.hip) -- per component S_k = sum_i r_ik xt_i xt_i^T, xt_i = [x_i - shift ; 1], packed lower
+// triangle, one partial block [KP][FP] per workgroup in the same layout, and the per-sample (max, sum of exponentials) for
+// em_lse_finish_kernel -- but only the (sample, component) pairs with r != 0 are accumulated.
+//
+// Why: once the components of a mixture are well apart, all but a few of a sample's K responsibilities underflow to exactly 0.0
+// (headline, d = 32, K = 64, after the first iterations: ~4.8 nonzero per sample). The dense GEMM R^T Phi multiplies all 64; a term
+// whose r is exactly 0 adds exactly 0, so skipping them changes nothing but the summation order.
+//
+//   * staging: the wide kernel's roles and normalisation code (em_mstats_stage.hpp) -> (max, sum) bit-identical to it. The x~ row
+//     of a sample is stored with the extra "1" coordinate left out, zero-padded to 32 coordinates and with its first 12 repeated
+//     behind them (row stride XE = 45, odd): quad q of the row (4 coordinates) can then be read as quad q .. q + 2 (mod 8);
+//   * compaction: wave w owns components w, w + 8, ... (K <= 64: up to 8). Per component, lane s reads r_sc of tile sample s; a
+//     ballot gives the nonzero set, v_mbcnt its rank: lane s writes s to slot rank of the component's list -- the bucket in sample
+//     order, no atomics, the same order in every run. (Building all 8 buckets first, so that their LDS round trips overlap, measured
+//     slower: 5.83 against 5.48 ms at the headline shape, 24 registers spilled instead of 16);
+//   * accumulation on v_mfma_f64_4x4x4_4b (lane layout as in em_estep_mfma4.hip: A[b][i][k] <- lane 16k + 4b + i,
+//     B[b][k][j] <- lane 16k + 4b + j, D[b][i][j] -> lane 16i + 4b + j): four bucket entries per step, sample k = lane >> 4. The
+//     32 x 32 Gram matrix has 36 quad pairs {Q, P} with P = Q + delta (mod 8): delta = 0..3 for every Q, delta = 4 for Q < 4.
+//     Block b of instruction (g, delta) takes Q = 4g + b, so the A operand is the lane's row quad b + 4g + delta -- one
+//     ds_read off a per-lane base with an immediate offset (the repeated quads are what makes that possible) -- and the B
+//     operand r x~ quad (b + 4g): 9 instructions for the Gram matrix, 2 for sum r x (A = 1), 1 for sum r (A = 1, B = r).
+//     12 accumulator doubles per component, 192 registers for the wave's 8;
+//   * the wide kernel's software pipeline: next tile's loads in flight during the accumulation, double-buffered LDS, one barrier
+//     per tile.
+// Choice between this kernel and the dense one: runtime/em.cpp (run_mstats), from the nonzero count both kernels report.
+#include "em_mstats_common.hpp"
+#include "em_mstats_stage.hpp"
+
+namespace mlhip {
+namespace mstats {
+namespace {
+
+constexpr int SNW = 8;             // waves per workgroup
+constexpr int SCPW = 8;            // component slots per wave (K <= 64)
+constexpr int SNRV = 8;            // responsibilities staged per thread: 64 components x 64 samples / 512 threads
+constexpr int SRS = 65;            // odd row stride of the responsibility tile (64 components + 1)
+constexpr int SXE = 45;            // odd row stride of the extended sample row: 32 coordinates + the first 12 again
+constexpr int SNA = 12;            // accumulators per component: 9 Gram quad pairs, 2 sum r x quads, sum r
+
+template <int N, int I = 0, class F> __device__ __forceinline__ void static_for(F&& f)
+{
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<N, I + 1>(f);
+    }
+}
+
+__global__ __launch_bounds__(512, 2) void em_mstats_sparse_kernel(
+    const double* __restrict__ xt, size_t ldx, uint32_t n, int d, int D, const double* __restrict__ shift,
+    const double* __restrict__ lw, size_t ldr, int K, double* __restrict__ partials, int KP, int FP,
+    double* __restrict__ lse_out, double* __restrict__ esum_out, unsigned long long* __restrict__ nz_count)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int NXV = kRegDim / SNW;                // x rows staged per thread (4)
+    constexpr int tile_doubles = TS * SXE + TS * SRS;
+    int* lists = reinterpret_cast<int*>(smem + 2 * tile_doubles);   // [SNW][TS]: the current component's bucket per wave
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int* list = lists + wave * TS;
+
+    double acc[SCPW][SNA];
+#pragma unroll
+    for (int c = 0; c < SCPW; ++c)
+#pragma unroll
+        for (int t = 0; t < SNA; ++t) acc[c][t] = 0.0;
+
+    // staging roles as in em_mstats_wide.hip (EXP = 2, RBW = 4)
+    const int sS = lane;
+    const int sR = 8 * wave + (lane & 7);
+    const int cg = lane >> 3;
+    double xv[NXV], rv[SNRV];
+    uint32_t nonzero = 0;
+    auto prefetch = [&](uint32_t tile) {
+        const uint32_t i = tile * TS + sS;           // < n_pad: always inside the allocation
+#pragma unroll
+        for (int it = 0; it < NXV; ++it) xv[it] = xt[(size_t)min(wave + SNW * it, D - 1) * ldx + i];
+#pragma unroll
+        for (int it = 0; it < SNRV; ++it) rv[it] = lw[(size_t)min(cg * SNRV + it, K - 1) * ldr + tile * TS + sR];
+    };
+    auto stage = [&](double* Xe, double* Rb, uint32_t tile) {
+        const uint32_t i = tile * TS + sR;
+        nonzero += stage_self_norm<SNRV, SRS>(rv, cg, K, i, i < n, Rb, sR, true, lse_out, esum_out);
+#pragma unroll
+        for (int it = 0; it < NXV; ++it) {
+            const int j = wave + SNW * it;
+            const double v = j < d ? xv[it] - shift[min(j, d - 1)] : 0.0;
+            Xe[sS * SXE + j] = v;
+            if (j < 12) Xe[sS * SXE + 32 + j] = v;
+        }
+    };
+
+    // accumulation role: bucket entry k = lane >> 4 of a step of four, block b, row / column i = j = lane & 3
+    const int k4 = lane >> 4, bq = (lane >> 2) & 3, i4 = lane & 3;
+    const uint32_t n_tiles = (n + TS - 1) / TS;
+    int buf = 0;
+    if (blockIdx.x < n_tiles) prefetch(blockIdx.x);
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, buf ^= 1) {
+        double* Xe = smem + buf * tile_doubles;
+        double* Rb = Xe + TS * SXE;
+        stage(Xe, Rb, tile);
+        __syncthreads();
+        const uint32_t next = tile + gridDim.x;
+        prefetch(next < n_tiles ? next : tile);      // the last iteration re-reads its own tile (discarded)
+        __builtin_amdgcn_s_setprio(kMatrixPhasePriority);
+        static_for<SCPW>([&](auto sl_) {
+            constexpr int sl = sl_;
+            const int c = sl * SNW + wave;
+            if (c < K) {
+                // compaction: the nonzero responsibilities of component c, in sample order
+                const double r_own = Rb[lane * SRS + c];
+                const unsigned long long mask = __ballot(r_own != 0.0);
+                const uint32_t cnt = (uint32_t)__builtin_popcountll(mask);
+                if (r_own != 0.0)
+                    list[__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u))] = lane;
+                for (uint32_t e0 = 0; e0 < cnt; e0 += 4) {
+                    const uint32_t e = e0 + k4;
+                    const bool valid = e < cnt;
+                    const int s = valid ? list[e] : 0;
+                    const double r = valid ? Rb[s * SRS + c] : 0.0;   // (entries past the bucket: r = 0 on a real sample row)
+                    const double* xr = Xe + s * SXE + 4 * bq + i4;
+                    double y[8];
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) y[m] = xr[4 * m];
+                    const double ry0 = r * y[0], ry1 = r * y[4];
+#pragma unroll
+                    for (int dl = 0; dl < 4; ++dl) {
+                        acc[sl][dl] = __builtin_amdgcn_mfma_f64_4x4x4f64(y[dl], ry0, acc[sl][dl], 0, 0, 0);
+                        acc[sl][4 + dl] = __builtin_amdgcn_mfma_f64_4x4x4f64(y[4 + dl], ry1, acc[sl][4 + dl], 0, 0, 0);
+                    }
+                    acc[sl][8] = __builtin_amdgcn_mfma_f64_4x4x4f64(y[4], ry0, acc[sl][8], 0, 0, 0);
+                    acc[sl][9] = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, ry0, acc[sl][9], 0, 0, 0);
+                    acc[sl][10] = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, ry1, acc[sl][10], 0, 0, 0);
+                    acc[sl][11] = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, r, acc[sl][11], 0, 0, 0);
+                }
+            }
+        });
+        __builtin_amdgcn_s_setprio(0);
+    }
+    if (nz_count && lane == 0) atomicAdd(nz_count, (unsigned long long)nonzero);   // (an integer sum: order-free)
+
+    // ---- epilogue: partials[blockIdx.x][c][f]; D[b][i][j] of a step sits in lane 16i + 4b + j
+    const int ri = lane >> 4, rj = lane & 3;
+    const int f_lin = d * (d + 1) / 2;                // packed row d: sum r x (columns 0..d-1) and sum r (column d)
+#pragma unroll
+    for (int sl = 0; sl < SCPW; ++sl) {
+        const int c = sl * SNW + wave;
+        if (c >= K) continue;
+        double* out = partials + ((size_t)blockIdx.x * KP + c) * FP;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int g = t < 8 ? t / 4 : 0, dl = t < 8 ? t % 4 : 4;
+            const int Q = 4 * g + bq, P = (Q + dl) & 7;
+            const int a = 4 * P + ri, b = 4 * Q + rj;
+            if (a < d && b < d && (dl != 0 || a >= b)) {
+                const int hi = a > b ? a : b, lo = a > b ? b : a;
+                out[hi * (hi + 1) / 2 + lo] = acc[sl][t];
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int b = 4 * (bq + 4 * h) + rj;
+            if (ri == 0 && b < d) out[f_lin + b] = acc[sl][9 + h];
+        }
+        if (lane == 0) out[f_lin + d] = acc[sl][11];
+    }
+}
+
+}  // namespace
+}  // namespace mstats
+
+bool em_mstats_sparse_supported(int d, int K, int num_cus)
+{
+    return d <= kRegDim && K <= mstats::SCPW * mstats::SNW && em_mstats_self_norm_supported(d, K, num_cus);
+}
+
+int launch_em_mstats_sparse(const MstatsArgs& a, int num_cus, hipStream_t stream)
+{
+    using namespace mstats;
+    if (a.mode != kFromLogRespSelfNorm || !em_mstats_sparse_supported(a.d, a.K, num_cus)) return -3;
+    const Plan p = make_plan(a.d, a.K, num_cus);
+    const uint32_t n_tiles = (a.n + TS - 1) / TS;
+    int grid_x = num_cus < p.grid_x ? num_cus : p.grid_x;       // one workgroup per CU (the dense plan may have two)
+    if ((uint32_t)grid_x > n_tiles) grid_x = (int)(n_tiles ? n_tiles : 1);
+    if ((size_t)grid_x * p.KP * p.FP > a.partials_capacity || p.KP < a.K || p.FP < stats_count(a.d)) return -2;
+    const size_t smem = sizeof(double) * 2 * ((size_t)TS * SXE + (size_t)TS * SRS) + sizeof(int) * SNW * TS;
+    hipLaunchKernelGGL(em_mstats_sparse_kernel, dim3(grid_x), dim3(512), smem, stream, a.xt, a.ldx, a.n, a.d, padded_dim(a.d),
+                       a.shift, a.lw, a.ldr, a.K, a.partials, p.KP, p.FP, a.lse_out, a.ll_out, a.nz_count);
+    return grid_x;
+}
+
+}  // namespace mlhip

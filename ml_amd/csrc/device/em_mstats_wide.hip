@@ -22,7 +22,7 @@
 #include "parts.hpp"
 
 #include "em_mstats_common.hpp"
-#include "exp_nonpos.hpp"
+#include "em_mstats_stage.hpp"
 
 #ifndef MSTATS_UNROLL_GEN
 #define MSTATS_UNROLL_GEN 16   // the 16 sample groups of a tile, all of them (see the contraction loop)
@@ -34,50 +34,6 @@ namespace {
 
 constexpr int NW = 8;   // waves per workgroup
 typedef __attribute__((address_space(3))) const double lds_cdouble;
-
-/// Partner values for all-reductions over lane bits 3, 4, 5 without the LDS pipe (a __shfl_xor of a double is two
-/// ds_bpermute: ~100 cycles of latency each, six of them in a row in the staging phase where every wave of the CU waits):
-/// bit 3 by a DPP row rotation, bits 4 and 5 by v_permlane16_swap / v_permlane32_swap.
-__device__ __forceinline__ double partner_xor8(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x128, 0xf, 0xf, false);   // row_ror:8
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x128, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-template <bool BIT5> __device__ __forceinline__ void partners_swap(double v, double& a, double& b)
-{
-    // a = v, b = v; swap: afterwards (a, b) hold {own half-or-row value, partner's} such that op(a, b) is the pairwise result
-    const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-    if constexpr (BIT5) {
-        const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        a = __hiloint2double((int)h[0], (int)l[0]);
-        b = __hiloint2double((int)h[1], (int)l[1]);
-    } else {
-        const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        a = __hiloint2double((int)h[0], (int)l[0]);
-        b = __hiloint2double((int)h[1], (int)l[1]);
-    }
-}
-__device__ __forceinline__ double allreduce_max_bits345(double v)
-{
-    double a, b;
-    v = fmax(v, partner_xor8(v));
-    partners_swap<false>(v, a, b);
-    v = fmax(a, b);
-    partners_swap<true>(v, a, b);
-    return fmax(a, b);
-}
-__device__ __forceinline__ double allreduce_sum_bits345(double v)
-{
-    double a, b;
-    v += partner_xor8(v);
-    partners_swap<false>(v, a, b);
-    v = a + b;
-    partners_swap<true>(v, a, b);
-    return a + b;
-}
 
 template <int N, int I = 0, class F> __device__ __forceinline__ void static_for(F&& f)
 {
@@ -96,7 +52,8 @@ template <int RBW, int CBW, int EXP, int DM, int CBT = 0>
 __global__ __launch_bounds__(512, 2) void em_mstats_wide_kernel(
     const double* __restrict__ xt, size_t ldx, uint32_t n, int d, int D, const double* __restrict__ shift,
     const double* __restrict__ lw, size_t ldr, const double* __restrict__ lse, int K, int n_rbg, int CB_total,
-    double* __restrict__ partials, int KP, int FP, double* __restrict__ lse_out, double* __restrict__ ll_out)
+    double* __restrict__ partials, int KP, int FP, double* __restrict__ lse_out, double* __restrict__ ll_out,
+    unsigned long long* __restrict__ nz_count)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int RS = RBW * 16 + 1;     // odd row stride of the responsibility tile
@@ -156,6 +113,7 @@ __global__ __launch_bounds__(512, 2) void em_mstats_wide_kernel(
     const int sR = EXP == 2 ? 8 * wave + (lane & 7) : lane;
     const int cg = lane >> 3;
     double xv[NXV], rv[NRV], lv = 0.0;
+    uint32_t nonzero = 0;                // EXP == 2: nonzero responsibilities staged by this wave (the runtime's kernel choice)
     auto prefetch = [&](uint32_t tile) {
         const uint32_t i = tile * TS + sS;           // < n_pad: always inside the allocation
 #pragma unroll
@@ -172,31 +130,7 @@ __global__ __launch_bounds__(512, 2) void em_mstats_wide_kernel(
     auto stage = [&](double* Xb, double* Rb, uint32_t tile) {
         if constexpr (EXP == 2) {
             const uint32_t i = tile * TS + sR;
-            const bool live = i < n;
-            double m = -__builtin_inf();
-#pragma unroll
-            for (int it = 0; it < NRV; ++it) {
-                if (cg * NRV + it >= K) rv[it] = -__builtin_inf();          // components beyond K: exp(-inf) = 0
-                m = fmax(m, rv[it]);
-            }
-            m = allreduce_max_bits345(m);
-            double sum = 0.0;
-#pragma unroll
-            for (int it = 0; it < NRV; ++it) {
-                rv[it] = exp_nonpos(rv[it] - m);
-                sum += rv[it];
-                __builtin_amdgcn_sched_barrier(0);          // one exp at a time: interleaved they spill next to 160 accumulator registers
-            }
-            sum = allreduce_sum_bits345(sum);
-            const double inv = live ? 1.0 / sum : 0.0;                      // padding samples contribute nothing
-#pragma unroll
-            for (int it = 0; it < NRV; ++it) Rb[sR * RS + cg * NRV + it] = rv[it] * inv;
-            // lse = m + log(sum) is finished by a separate pass over these two N-vectors (em_lse_finish_kernel): a log in
-            // this loop, next to 160 accumulator registers, cost 0.8 ms at the headline shape in spills and scheduling
-            if (cg == 0 && blockIdx.y == 0) {
-                lse_out[i] = m;
-                ll_out[i] = sum;
-            }
+            nonzero += stage_self_norm<NRV, RS>(rv, cg, K, i, i < n, Rb, sR, blockIdx.y == 0, lse_out, ll_out);
         } else {
         const bool live = tile * TS + sS < n;
 #pragma unroll
@@ -342,6 +276,9 @@ __global__ __launch_bounds__(512, 2) void em_mstats_wide_kernel(
         __builtin_amdgcn_s_setprio(0);
     }
 
+    if constexpr (EXP == 2) {
+        if (nz_count && blockIdx.y == 0 && lane == 0) atomicAdd(nz_count, (unsigned long long)nonzero);   // (an integer sum: order-free)
+    }
     // ---- epilogue: partials[blockIdx.x][k][f]; C/D layout of v_mfma_f64_16x16x4: col = lane&15, row = (lane>>4) + 4*reg
     double* out = partials + (size_t)blockIdx.x * KP * FP;
     if constexpr (CBT > 0) {
@@ -606,15 +543,15 @@ void launch_t(const MstatsArgs& a, const Plan& p, int grid_x, hipStream_t stream
     if (a.mode == kFromLogRespSelfNorm)
         hipLaunchKernelGGL((em_mstats_wide_kernel<RBW, CBW, 2, DM, CBT>), grid, dim3(512), smem, stream, a.xt, a.ldx, a.n, a.d,
                            padded_dim(a.d), a.shift, a.lw, a.ldr, a.lse, a.K, p.n_rbg, p.CB, a.partials, p.KP, p.FP,
-                           a.lse_out, a.ll_out);
+                           a.lse_out, a.ll_out, a.nz_count);
     else if (a.mode == kFromLogResp)
         hipLaunchKernelGGL((em_mstats_wide_kernel<RBW, CBW, 1, DM, CBT>), grid, dim3(512), smem, stream, a.xt, a.ldx, a.n, a.d,
                            padded_dim(a.d), a.shift, a.lw, a.ldr, a.lse, a.K, p.n_rbg, p.CB, a.partials, p.KP, p.FP,
-                           nullptr, nullptr);
+                           nullptr, nullptr, nullptr);
     else
         hipLaunchKernelGGL((em_mstats_wide_kernel<RBW, CBW, 0, DM, CBT>), grid, dim3(512), smem, stream, a.xt, a.ldx, a.n, a.d,
                            padded_dim(a.d), a.shift, a.lw, a.ldr, a.lse, a.K, p.n_rbg, p.CB, a.partials, p.KP, p.FP,
-                           nullptr, nullptr);
+                           nullptr, nullptr, nullptr);
 }
 
 }  // namespace

@@ -265,7 +265,20 @@ void run_mstats(mlhip_data* dt, int K, int mode, const double* resp_dev, size_t 
     dt->stats_resp = a.lw;
     dt->stats_ld = a.ldr;
     int rc = 0;
-    ctx->timed("em_mstats", [&] { rc = launch_em_mstats(a, ctx->num_cus, ctx->stream); });
+    if (mode == kFromLogRespSelfNorm) {
+        const bool sparse = mstats_sparse_applies(dt, K);
+        const int slot = (int)(dt->sn_calls % 3);
+        dt->sn_calls++;
+        a.nz_count = dt->nz_dev.as<unsigned long long>();
+        HIP_CHECK(hipMemsetAsync(dt->nz_dev.p, 0, sizeof(unsigned long long), ctx->stream));
+        ctx->timed("em_mstats", [&] {
+            rc = sparse ? launch_em_mstats_sparse(a, ctx->num_cus, ctx->stream) : launch_em_mstats(a, ctx->num_cus, ctx->stream);
+        });
+        HIP_CHECK(hipMemcpyAsync(dt->nz_host.as<unsigned long long>() + slot, dt->nz_dev.p, sizeof(unsigned long long),
+                                 hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        ctx->timed("em_mstats", [&] { rc = launch_em_mstats(a, ctx->num_cus, ctx->stream); });
+    }
     if (rc <= 0) throw std::runtime_error("statistics kernel launch failed (plan/scratch)");
     launch_em_reduce(a, ctx->num_cus, rc, ctx->stream);
     HIP_CHECK(hipGetLastError());
@@ -416,6 +429,30 @@ bool self_norm_applies(const mlhip_data* dt, int K)
     static const bool allowed = [] { const char* e = std::getenv("MLHIP_SELF_NORM"); return !(e && e[0] == '0'); }();
     return allowed && estep_mfma4_supported(dt->D) && !std::getenv("MLHIP_ESTEP") &&
            em_mstats_self_norm_supported(dt->d, K, dt->ctx->num_cus);
+}
+
+
+/// Whether the next self-normalising statistics pass of `dt` runs the sparse kernel (em_mstats_sparse.hip) instead of the dense
+/// one. The sparse kernel's cost grows with the nonzero responsibilities, the dense kernel's does not: sparse while the pass two
+/// passes back (the last whose count every loop has in hand) had at most kSparseMaxPairs nonzero pairs per sample. The first two
+/// passes with a K are dense. The choice depends only on the handle's call history, so a loop of mlhip_em_step and
+/// mlhip_em_iterate take the same kernels in the same order. MLHIP_MSTATS_SPARSE=1 / 0 forces the sparse / dense kernel (A/B
+/// runs; where the sparse kernel exists).
+bool mstats_sparse_applies(mlhip_data* dt, int K)
+{
+    constexpr double kSparseMaxPairs = 16.0;
+    if (dt->sn_K != K) {
+        dt->sn_K = K;
+        dt->sn_calls = 0;
+    }
+    dt->nz_dev.reserve(sizeof(unsigned long long));
+    dt->nz_host.reserve(3 * sizeof(unsigned long long));
+    if (!em_mstats_sparse_supported(dt->d, K, dt->ctx->num_cus)) return false;
+    const char* e = std::getenv("MLHIP_MSTATS_SPARSE");
+    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+    if (dt->sn_calls < 2) return false;
+    const unsigned long long nz = dt->nz_host.as<unsigned long long>()[(dt->sn_calls - 2) % 3];
+    return (double)nz <= kSparseMaxPairs * (double)dt->n;
 }
 
 

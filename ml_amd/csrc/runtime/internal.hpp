@@ -390,6 +390,13 @@ struct mlhip_data {
     size_t stats_ld = 0;
     DevBuf refine_shift, refine_stats;
     uint64_t refined_components = 0;   // diagnostic counter
+    // self-normalising statistics passes (run_mstats): both kernels add the number of nonzero responsibilities to nz_dev, which
+    // is copied to slot sn_calls % 3 of nz_host; pass t chooses the sparse kernel from the count of pass t - 2 (in hand in every
+    // loop: mlhip_em_iterate has waited for iteration t - 2 before it launches t)
+    DevBuf nz_dev;
+    PinnedBuf nz_host;
+    uint64_t sn_calls = 0;
+    int sn_K = 0;
     // K-means workspace
     DevBuf km_labels[2], km_cent, km_cent_next, km_partials, km_out, km_mind, km_probe, km_scale, km_cnorm, km_xt_pad;
     PinnedBuf km_host;
@@ -404,9 +411,9 @@ struct mlhip_data {
     {
         for (DevBuf* b : {&xt, &shift_dev, &lw, &lse, &esum, &ll_partials, &params_dev, &partials, &stats_dev, &resp_dev,
                           &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr, &km_ticket,
-                          &refine_shift, &refine_stats, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
+                          &refine_shift, &refine_stats, &nz_dev, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
             b->pool = pool;
-        for (PinnedBuf* b : {&params_host, &stats_host, &km_host, &it_info_slot[0], &it_info_slot[1], &it_info_slot[2], &it_history}) b->pool = pool;
+        for (PinnedBuf* b : {&params_host, &stats_host, &nz_host, &km_host, &it_info_slot[0], &it_info_slot[1], &it_info_slot[2], &it_history}) b->pool = pool;
     }
 
     ~mlhip_data()
@@ -414,11 +421,11 @@ struct mlhip_data {
         for (mlhip_data* p : parts) mlhip_data_free(p);
         for (DevBuf* b : {&xt, &shift_dev, &lw, &lse, &esum, &ll_partials, &params_dev, &partials, &stats_dev, &resp_dev,
                           &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr, &km_ticket,
-                          &refine_shift, &refine_stats, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
+                          &refine_shift, &refine_stats, &nz_dev, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
             b->release();
         for (auto& sl : it_info_slot) sl.release();
         for (auto& e : it_event) if (e) (void)hipEventDestroy(e);
-        params_host.release(); stats_host.release(); km_host.release(); it_history.release();
+        params_host.release(); stats_host.release(); nz_host.release(); km_host.release(); it_history.release();
     }
 };
 
@@ -557,6 +564,7 @@ void km_iterate(mlhip_data* dt, int K, double* centroids, double* old_centroids,
 /// the statistics kernel normalises them (one exp per pair in the iteration); otherwise the E-step keeps its online
 /// log-sum-exp. MLHIP_SELF_NORM=0 forces the latter (A/B runs).
 bool self_norm_applies(const mlhip_data* dt, int K);
+bool mstats_sparse_applies(mlhip_data* dt, int K);
 
 /// One full-covariance EM iteration with the closing arithmetic on the HOST (the body of mlhip_em_step).
 void em_step_full(mlhip_data* data, int K, const double* mixing, const double* means, const double* covariances,
