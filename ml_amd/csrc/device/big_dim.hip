@@ -3,9 +3,9 @@
 // instructions) runs at 0.2 - 0.8 TFLOP/s. The reference has no limit on d (ML/EM.cpp:96-101), and at these dimensions both passes
 // of an EM iteration are plain matrix products:
 //   * E-step (EM::expectation_step, ML/EM.cpp:190-219): per component Y = W (X - mu) with W = L^-1 lower triangular, q_i = |y_i|^2.
-//     One wave per 16 samples: the centred tile Z (d x 16) sits in LDS, W streams through as the A operand of v_mfma_f64_16x16x4
-//     row block by row block (16 rows x the columns up to the diagonal), the squares of the 16 x 16 output block are folded into
-//     q on the spot -- Y never exists. Same whitening form as every other E-step here: no cancellation.
+//     A workgroup owns a 128 x 128 tile of Y, W and the centred samples stream through LDS in chunks as the operands of
+//     v_mfma_f64_16x16x4, the squares of a finished tile are folded into q on the spot -- Y never exists. Same whitening form as
+//     every other E-step here: no cancellation.
 //   * statistics (EM::maximisation_step, ML/EM.cpp:229-248): S_k = sum_i r_ik x~_i x~_i^T, x~ = [x - shift ; 1], lower triangle.
 //     A workgroup owns one 64 x 64 tile of one component's S over one range of samples: panels of 32 samples of the 64 + 64 rows
 //     go through LDS (the A panel scaled by r), four waves hold 2 x 2 output blocks each. The sample ranges of a tile are
@@ -23,7 +23,7 @@ namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-constexpr int kBigMaxDim = 1024;      // (the E-step's centred tile: 128 KB of the CU's 160 KB of LDS)
+constexpr int kBigMaxDim = 1024;      // (set by round 4's E-step, whose centred tile took 128 KB of the CU's 160 KB of LDS)
 
 /// Lanes l, l ^ 16, l ^ 32, l ^ 48 hold the partial sums of one sample: all four get the total (fixed order).
 __device__ __forceinline__ double quad_total(double v)
@@ -38,106 +38,9 @@ __device__ __forceinline__ double quad_total(double v)
     return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
 }
 
-/// Records: estep_param_stride(D) doubles per component, [ mean(D) | W packed lower triangle, row by row | coef ] (layout.hpp).
-/// A workgroup of four waves per 16 samples: ONE centred tile Z[D][16] in LDS serves all four, which share the row blocks of W
-/// (block rb needs rb + 1 column groups: dealt out in a snake, rounds of four, so that every wave gets the same number of
-/// products); the four partial sums of |y|^2 meet in LDS in wave order. (One wave per tile keeps a CU at four waves -- the tile
-/// is 32 KB at d = 256 -- and every product waits for its own gather of W: 7.7 ms at N = 100k, d = 256, K = 8 against 2.1 here.)
-__global__ __launch_bounds__(256) void em_estep_big_kernel(const double* __restrict__ xt, size_t ldx, uint32_t n, uint32_t n_pad, int D,
-                                                            const double* __restrict__ params, int K, double* __restrict__ lw_out,
-                                                            size_t ldr, double* __restrict__ lse_out, double* __restrict__ ll_partials)
-{
-    extern __shared__ __attribute__((aligned(16))) double zt[];       // [D][16], then the partial sums qs[4][16]
-    double* qs = zt + (size_t)D * 16;
-    const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, kq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const size_t PS = (size_t)D + (size_t)D * (D + 1) / 2 + 1;
-    const int RB = (D + 15) / 16;
-    double ll_acc = 0.0;
-    const uint32_t n_blocks = n_pad / 16;
-    for (uint32_t sb = blockIdx.x; sb < n_blocks; sb += gridDim.x) {
-        const uint32_t i0 = sb * 16;
-        double m = -__builtin_inf(), s = 0.0;
-        for (int k = 0; k < K; ++k) {
-            const double* __restrict__ p = params + (size_t)k * PS;
-            const double* __restrict__ w = p + D;
-            __syncthreads();                                           // the previous component's reads of the tile and of qs are done
-            for (int l = tid >> 4; l < D; l += 16) zt[l * 16 + j] = xt[(size_t)l * ldx + i0 + j] - p[l];
-            __syncthreads();
-            double q = 0.0;
-            for (int round = 0; round * 4 < RB; ++round) {
-                const int rb = round * 4 + ((round & 1) ? 3 - wave : wave);
-                if (rb >= RB) continue;                                // (wave-uniform)
-                const int row = rb * 16 + j;                           // (the A operand's row index is the lane's low four bits too)
-                const bool row_ok = row < D;
-                const double* __restrict__ wr = w + (size_t)row * (row + 1) / 2;
-                const int l_end = (rb * 16 + 16 < D ? rb * 16 + 16 : D);   // columns 0 .. l_end - 1 (a multiple of 4)
-                d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-                // The columns LEFT of the diagonal block need no triangle test, and only the last row block can hold rows >= D: the
-                // bulk of the products runs without predicates, the lane's row pointer and its LDS address advancing by constants
-                // (13 vector instructions per product before -- address arithmetic and selects --, counters in profiles/r04_pmc_new_kernels.txt).
-                const double* __restrict__ wp = wr + kq;
-                const double* zp = zt + kq * 16 + j;
-                const int l_full = rb * 16;                            // (a multiple of 16)
-                int l0 = 0;
-                if (rb * 16 + 16 <= D) {
-                    for (; l0 < l_full; l0 += 16) {                     // four gathers of W in flight
-                        const double a0 = wp[l0], a1 = wp[l0 + 4], a2 = wp[l0 + 8], a3 = wp[l0 + 12];
-                        const double b0 = zp[l0 * 16], b1 = zp[(l0 + 4) * 16], b2 = zp[(l0 + 8) * 16], b3 = zp[(l0 + 12) * 16];
-                        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc1, 0, 0, 0);
-                        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a3, b3, acc1, 0, 0, 0);
-                    }
-                }
-                for (; l0 + 8 <= l_end; l0 += 8) {                      // the diagonal block (and all of the last row block)
-                    const int c0 = l0 + kq, c1 = l0 + 4 + kq;
-                    const double a0 = (row_ok && c0 <= row) ? wr[c0] : 0.0;
-                    const double a1 = (row_ok && c1 <= row) ? wr[c1] : 0.0;
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, zt[c0 * 16 + j], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, zt[c1 * 16 + j], acc1, 0, 0, 0);
-                }
-                for (; l0 < l_end; l0 += 4) {
-                    const int c0 = l0 + kq;
-                    const double a0 = (row_ok && c0 <= row) ? wr[c0] : 0.0;
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, zt[c0 * 16 + j], acc0, 0, 0, 0);
-                }
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const double y = acc0[g] + acc1[g];                // rows kq + 4 g of the block, sample j
-                    q = __builtin_fma(y, y, q);
-                }
-            }
-            q = quad_total(q);
-            if (kq == 0) qs[wave * 16 + j] = q;
-            __syncthreads();
-            if (wave == 0) {
-                const double qt = ((qs[j] + qs[16 + j]) + qs[32 + j]) + qs[48 + j];
-                const double lw = __builtin_fma(-0.5, qt, p[PS - 1]);
-                if (kq == 0) lw_out[(size_t)k * ldr + i0 + j] = lw;
-                const double e = exp_nonpos(lw == -HUGE_VAL ? -HUGE_VAL : -fabs(lw - m));   // online log-sum-exp (em_estep.hip)
-                const bool up = lw > m;
-                s = up ? __builtin_fma(s, e, 1.0) : s + e;
-                m = up ? lw : m;
-            }
-        }
-        if (wave == 0) {
-            const double lse = m + log(s);
-            if (kq == 0) {
-                lse_out[i0 + j] = lse;
-                if (i0 + j < n) ll_acc += lse;
-            }
-        }
-    }
-    // lanes 0 .. 15 of wave 0 carry the sums of their sample column; fixed-order tree over them
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) ll_acc += __shfl_down(ll_acc, off, 64);
-    if (tid == 0) ll_partials[blockIdx.x] = ll_acc;
-}
-
 // ---- E-step, tiled as a matrix product (round 5) ------------------------------------------------------------------------
-// The kernel above keeps ONE centred tile of 16 samples per workgroup (all D rows of it: 128 KB at D = 1024) and streams the whole of W
-// past it: every element of W is fetched again for every 16 samples -- 4 flop per byte from L2, which is what it ran at (15.8 TFLOP/s
+// Round 4's kernel kept ONE centred tile of 16 samples per workgroup (all D rows of it: 128 KB at D = 1024) and streamed the whole of W
+// past it: every element of W was fetched again for every 16 samples -- 4 flop per byte from L2, which is what it ran at (15.8 TFLOP/s
 // at d = 1024: 52 GB through L2 per launch). Here a workgroup owns a tile of 128 rows of Y = W (X - mu) x 128 samples in registers (each
 // of four waves 64 x 64: 16 accumulator blocks -- its rows are every other 16-row block of the tile) and walks the columns l of W in chunks of 16: 128 x 16 of W and 16 x 128 of the centred
 // samples go through LDS, double-buffered, the next chunk in flight during the matrix phase: 16 flop per byte. Only chunks on or left
@@ -596,10 +499,6 @@ int big_dim_splits(int d, int K, int num_cus)
 int estep_parts(uint32_t units1, int D, int slots, size_t max_parts)
 {
     const int n_rb = (D + GR - 1) / GR;
-    if (const char* e = ab_env("MLHIP_ESTEP_PARTS")) {                          // (A/B runs: a given count where it is allowed)
-        const int want = std::atoi(e);
-        if (want >= 1 && want <= 8 && want <= n_rb && (want == 1 || (size_t)want <= max_parts)) return want;
-    }
     if (units1 == 0 || units1 >= 16u * (uint32_t)slots) return 1;              // many rounds: the tail is a few per cent at most
     int best_p = 1;
     double best_t = 0.0;
@@ -633,34 +532,18 @@ int estep_parts(uint32_t units1, int D, int slots, size_t max_parts)
 int launch_em_estep_big(const EstepArgs& a, int num_cus, hipStream_t stream)
 {
     const uint32_t n_pad = padded_samples(a.n);
-    static const bool tiled = [] { const char* e = ab_env("MLHIP_ESTEP_BIG"); return !(e && e[0] == 't'); }();   // "tile": round 4's kernel (A/B)
-    if (tiled) {
-        static_assert(kSampleTile % GS == 0, "a sample tile of the product must divide the padding granule of N");
-        const int P = estep_parts(n_pad / GS * (uint32_t)a.K, a.D, 2 * num_cus, a.scratch ? a.scratch_doubles / ((size_t)a.K * a.ldr) : 0);
-        const uint32_t units = n_pad / GS * (uint32_t)a.K * (uint32_t)P;
-        uint32_t grid = 2u * (uint32_t)num_cus;
-        if (grid > units) grid = units;
-        hipLaunchKernelGGL(em_estep_gemm_kernel, dim3(grid), dim3(256), 0, stream, a.xt, a.ldx, n_pad, a.D, a.params, a.K, a.lw, a.ldr, P, a.scratch);
-        uint32_t lgrid = (n_pad + 255) / 256;
-        if (lgrid > (uint32_t)a.n_ll_partials) lgrid = (uint32_t)a.n_ll_partials;
-        if (lgrid > 4u * (uint32_t)num_cus) lgrid = 4u * (uint32_t)num_cus;
-        hipLaunchKernelGGL(em_lse_rows_kernel, dim3(lgrid), dim3(256), 0, stream, a.lw, a.ldr, a.n, n_pad, a.K, a.lse, a.ll_partials, P,
-                           (const double*)a.scratch, a.params, (size_t)a.D + (size_t)a.D * (a.D + 1) / 2 + 1);
-        return (int)lgrid;
-    }
-    const size_t smem = sizeof(double) * ((size_t)a.D * 16 + 64);     // 64.5 KB at D = 512, 128.5 KB at D = 1024
-    if (smem > 64 * 1024 &&                                           // (per device: asked for on every such launch)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(em_estep_big_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess)
-        return -1;
-    const int per_cu = (int)(size_t(160 * 1024) / (smem + 1024));
-    uint32_t grid = (uint32_t)num_cus * (uint32_t)(per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
-    const uint32_t blocks = n_pad / 16;
-    if (grid > blocks) grid = blocks;
-    if (grid > (uint32_t)a.n_ll_partials) grid = (uint32_t)a.n_ll_partials;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(em_estep_big_kernel, dim3(grid), dim3(256), smem, stream, a.xt, a.ldx, a.n, n_pad, a.D, a.params, a.K, a.lw, a.ldr,
-                       a.lse, a.ll_partials);
-    return (int)grid;
+    static_assert(kSampleTile % GS == 0, "a sample tile of the product must divide the padding granule of N");
+    const int P = estep_parts(n_pad / GS * (uint32_t)a.K, a.D, 2 * num_cus, a.scratch ? a.scratch_doubles / ((size_t)a.K * a.ldr) : 0);
+    const uint32_t units = n_pad / GS * (uint32_t)a.K * (uint32_t)P;
+    uint32_t grid = 2u * (uint32_t)num_cus;
+    if (grid > units) grid = units;
+    hipLaunchKernelGGL(em_estep_gemm_kernel, dim3(grid), dim3(256), 0, stream, a.xt, a.ldx, n_pad, a.D, a.params, a.K, a.lw, a.ldr, P, a.scratch);
+    uint32_t lgrid = (n_pad + 255) / 256;
+    if (lgrid > (uint32_t)a.n_ll_partials) lgrid = (uint32_t)a.n_ll_partials;
+    if (lgrid > 4u * (uint32_t)num_cus) lgrid = 4u * (uint32_t)num_cus;
+    hipLaunchKernelGGL(em_lse_rows_kernel, dim3(lgrid), dim3(256), 0, stream, a.lw, a.ldr, a.n, n_pad, a.K, a.lse, a.ll_partials, P,
+                       (const double*)a.scratch, a.params, (size_t)a.D + (size_t)a.D * (a.D + 1) / 2 + 1);
+    return (int)lgrid;
 }
 
 /// Returns the number of partial blocks [K][F] written, or < 0.

@@ -60,18 +60,8 @@ struct EstepArgs {
 int launch_em_estep(const EstepArgs& a, hipStream_t stream);
 /// d > kMaxDim (generic_dim.hip): the same passes in a plain form, any dimension.
 int launch_em_estep_generic(const EstepArgs& a, hipStream_t stream);
-#ifdef MLHIP_EXPERIMENTS
-/// 16x16x4 block-triangular variant (experiments/em_estep_mfma16.hip); params use the estep_mfma_param_stride(D) layout.
-int launch_em_estep_mfma(const EstepArgs& a, int num_cus, hipStream_t stream);
-#endif
 /// 4x4-block triangular variant (em_estep_mfma4.hip); params use the estep_mfma4_param_stride(D) record layout.
 int launch_em_estep_mfma4(const EstepArgs& a, int num_cus, hipStream_t stream);
-#ifdef MLHIP_EXPERIMENTS
-/// Component-stationary variant of it (experiments/em_estep_cs.hip): FOLD form, lw only (a.fold && !a.with_lse), same records;
-/// returns <0 when it does not serve the shape (em_estep_cs_supported).
-bool em_estep_cs_supported(int D, int K);
-int launch_em_estep_cs(const EstepArgs& a, int num_cus, hipStream_t stream);
-#endif
 
 enum MstatsMode : int {
     kFromLogResp = 0,   // r = exp(lw - lse)          (after an E-step)
@@ -254,9 +244,5 @@ void launch_kmeans_reduce(const KmeansArgs& a, int n_partials, hipStream_t strea
 /// from the same kernel -- the host then only waits for the stream; a separate hipMemcpyAsync of these 2 + K (d + 1) doubles goes
 /// through a copy engine and costs more than the kernel itself.
 void launch_kmeans_close(double* out, int K, int d, int D, double* next, double* mirror, hipStream_t stream);
-/// launch_kmeans_reduce + launch_kmeans_close in one launch (no all-reduce in between). `ticket`: one unsigned of device memory, zeroed once;
-/// `ticket_base`: the tickets drawn from it so far -- the return value (this launch's workgroups) is added to it by the caller.
-unsigned launch_kmeans_reduce_close(const KmeansArgs& a, int n_partials, int D, double* next, double* mirror, unsigned* ticket,
-                                    unsigned ticket_base, hipStream_t stream);
 
 }  // namespace mlhip

@@ -1,7 +1,7 @@
 // E-step of Gaussian-mixture EM on the gfx950 fp64 matrix cores with ELEMENT-BLOCK triangular work (dimensions 12..128)
 // -- replaces EM::expectation_step (reference ML/EM.cpp:190-219) and its xAx_symmetric calls (ML/LinearAlgebra.cpp:8-31).
 //
-// Same arithmetic as the 16x16x4 variant it superseded (experiments/em_estep_mfma16.hip) (z = x - mu_k, y = W_k z with W_k = L_k^-1 lower triangular, q = |y|^2,
+// Same arithmetic as the 16x16x4 variant it superseded (z = x - mu_k, y = W_k z with W_k = L_k^-1 lower triangular, q = |y|^2,
 // lw = log pi_k - sum log L_jj - q/2, online log-sum-exp), but on v_mfma_f64_4x4x4_4b_f64: one instruction multiplies
 // FOUR independent 4x4 blocks, D_b[4 rows][4 samples] += A_b[4 x 4] * B_b[4 x 4 samples]. With the same 4x4 block of W in
 // all four A blocks and four different sample quads in B, one instruction advances 4 rows of y for 16 samples, and only
@@ -24,8 +24,6 @@
 //   !LSE  no online log-sum-exp, only lw is written: the statistics kernel normalises a sample's K log-responsibilities
 //         itself while staging its tile (em_mstats_wide.hip, one exp per (sample, component) instead of one in each
 //         kernel) and produces lse and the log-likelihood sum. Used whenever K fits one row-block group of that kernel.
-#include <cstdlib>
-
 #include "device.hpp"
 #include "exp_nonpos.hpp"
 
@@ -52,7 +50,7 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-/// (As in experiments/em_estep_mfma16.hip:) group g = lane>>4 ends with the sum over groups of v[g] (v_permlane16/32_swap reduce-scatter).
+/// Group g = lane>>4 ends with the sum over groups of v[g] (v_permlane16/32_swap reduce-scatter).
 __device__ __forceinline__ double reduce_scatter_groups(double v0, double v1, double v2, double v3)
 {
     auto swap16 = [](double& a, double& b) {
@@ -178,7 +176,7 @@ __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_
 #pragma unroll
                     for (int sb = 0; sb < SB; ++sb)
                         acc[sb][R] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, z[sb], C == 0 ? init : acc[sb][R], 0, 0, 0);
-                    // Pin the block order (column-quad major, the sample blocks back to back); the same pinning as in experiments/em_estep_mfma16.hip.
+                    // Pin the block order (column-quad major, the sample blocks back to back).
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -283,14 +281,12 @@ int launch_sb(const EstepArgs& a, int num_cus, hipStream_t stream)
     uint32_t per_cu = 2 * default_waves<SB>() / NW;                          // the CU's resident workgroups, persistent
     if constexpr (SB == 4 && D <= 20) {
         // small d: a component is 6 - 21 blocks short, the per-component barrier and the epilogue weigh more, and the kernel needs
-        // few registers (92 - 138): as many workgroups per CU as fit, up to 4 [r3] (MLHIP_ESTEP_WGS=2: the two of larger d; at d = 24
-        // three fit, the E-step gains 1 % and the statistics kernel behind it loses 2 %: not used there)
+        // few registers (92 - 138): as many workgroups per CU as fit, up to 4 [r3] (at d = 24 three fit, the E-step gains 1 % and the
+        // statistics kernel behind it loses 2 %: not used there)
         static const int fit = [] {
             int blocks = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, em_estep_mfma4_kernel<D, SB, FOLD, LSE, NW>, NT, sizeof(double) * 2 * NLD * NT) != hipSuccess) blocks = 2;
-            const char* e = ab_env("MLHIP_ESTEP_WGS");
-            const int want = e ? std::atoi(e) : 4;
-            return blocks < 2 ? 2 : (blocks > want ? want : blocks);
+            return blocks < 2 ? 2 : (blocks > 4 ? 4 : blocks);
         }();
         if ((uint32_t)fit > per_cu) per_cu = (uint32_t)fit;
     }

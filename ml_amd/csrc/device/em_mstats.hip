@@ -17,8 +17,6 @@
 // column-block) tile space when it does not fit one workgroup's registers. A wave holds RBW x CBW
 // 16x16 accumulators (8 VGPRs each). Per-workgroup partial sums go to scratch and are combined in a
 // fixed order by em_reduce_kernel (no atomics: bitwise reproducible).
-#include <cstdlib>
-
 #include "em_mstats_common.hpp"
 
 namespace mlhip {
@@ -118,11 +116,6 @@ Plan make_plan(int d, int K, int num_cus)
     const int F = stats_count(d);
     p.RB = (K + 15) / 16;
     p.CB = (F + 15) / 16;
-#ifdef MLHIP_EXPERIMENTS
-    static const bool force_narrow = [] { const char* e = std::getenv("MLHIP_MSTATS"); return e && e[0] == 'n'; }();
-#else
-    constexpr bool force_narrow = false;     // the workgroup-tile variant (experiments/em_mstats_narrow.hip) is not built
-#endif
     if (d > kMaxDim) {
         // generic_dim.hip: one workgroup per (row of the packed triangle, component), ONE partial block [K][F]
         p.RBW = p.CBW = 1;
@@ -133,7 +126,7 @@ Plan make_plan(int d, int K, int num_cus)
         p.wg_per_cu = 1;
         return p;
     }
-    p.wide = p.CB >= 5 && !force_narrow;
+    p.wide = p.CB >= 5;
     if (p.wide) {
         // One 512-thread workgroup per CU; its 8 waves take the column blocks round-robin (wave w: w, w+8, ...), every
         // wave holds all (<= 4) row blocks of the group: RBW x CBW <= 20 accumulator tiles.
@@ -151,15 +144,13 @@ Plan make_plan(int d, int K, int num_cus)
         // Few components (K <= 32) at d <= 32: a wave holds only 1 - 6 accumulator tiles, the contraction of a 64-sample tile is
         // shorter than the latency of the next tile's loads, and one workgroup per CU waits for memory most of the time. These
         // instantiations need <= 128 registers and <= 70 KB of LDS: TWO workgroups per CU [r3] (N = 1M, d = 16, K = 16: 202 ->
-        // 160 us; N = 5M, d = 24, K = 32: 2.31 -> 1.97 ms; profiles/r03_mstats_wg2.txt). MLHIP_MSTATS_WG2=0: one.
-        static const bool wg2_allowed = [] { const char* e = ab_env("MLHIP_MSTATS_WG2"); return !(e && e[0] == '0'); }();
-        if (wg2_allowed && d <= kRegDim && p.n_rbg == 1 && p.n_cbg == 1 && (p.RBW == 1 || (p.RBW == 2 && p.CBW <= 3))) {
+        // 160 us; N = 5M, d = 24, K = 32: 2.31 -> 1.97 ms; profiles/r03_mstats_wg2.txt).
+        if (d <= kRegDim && p.n_rbg == 1 && p.n_cbg == 1 && (p.RBW == 1 || (p.RBW == 2 && p.CBW <= 3))) {
             p.wg_per_cu = 2;                                       // (three, where registers and LDS allow: no faster, slower at d >= 20)
             p.grid_x = p.wg_per_cu * num_cus;
         }
-    } else if (p.CB <= 4 && !force_narrow) {
+    } else {
         // d <= 9: independent waves, each with all column blocks and up to 4 row blocks (em_mstats_small.hip)
-        p.small = true;
         p.RBW = p.RB >= 3 ? 4 : (p.RB >= 2 ? 2 : 1);
         p.CBW = p.CB;
         p.n_rbg = (p.RB + p.RBW - 1) / p.RBW;
@@ -167,16 +158,6 @@ Plan make_plan(int d, int K, int num_cus)
         p.KP = p.n_rbg * p.RBW * 16;
         p.FP = p.CB * 16;
         p.grid_x = 2 * num_cus / p.n_rbg;
-    } else {
-        // Few column blocks (small d): 256-thread workgroups, 4 waves split the column blocks, two workgroups per CU.
-        const int cb_per_wave = (p.CB + 3) / 4;
-        p.RBW = p.RB >= 4 ? 4 : (p.RB >= 2 ? 2 : 1);
-        p.CBW = cb_per_wave >= 2 ? 2 : 1;
-        p.n_rbg = (p.RB + p.RBW - 1) / p.RBW;
-        p.n_cbg = (p.CB + 4 * p.CBW - 1) / (4 * p.CBW);
-        p.KP = p.n_rbg * p.RBW * 16;
-        p.FP = p.n_cbg * 4 * p.CBW * 16;
-        p.grid_x = 2 * num_cus / (p.n_rbg * p.n_cbg);
     }
     if (p.grid_x < 1) p.grid_x = 1;
     return p;
@@ -214,13 +195,7 @@ int launch_em_mstats(const MstatsArgs& a, int num_cus, hipStream_t stream)
     if ((uint32_t)grid_x > n_tiles) grid_x = (int)(n_tiles ? n_tiles : 1);
     if ((size_t)grid_x * p.KP * p.FP > a.partials_capacity) return -2;
     if (a.mode == kFromLogRespSelfNorm && !(p.wide && p.n_rbg == 1)) return -3;
-    if (p.wide) return launch_wide(a, p, grid_x, stream);
-    if (p.small) return launch_small(a, p, grid_x, stream);
-#ifdef MLHIP_EXPERIMENTS
-    return mstats::launch_narrow(a, p, grid_x, stream);
-#else
-    return -1;
-#endif
+    return p.wide ? launch_wide(a, p, grid_x, stream) : launch_small(a, p, grid_x, stream);
 }
 
 void launch_fill_responsibilities(const uint32_t* labels, uint32_t n, int K, double* resp, size_t ldr, hipStream_t stream)

@@ -400,69 +400,6 @@ __global__ __launch_bounds__(256) void kmeans_close_kernel(double* __restrict__ 
 }
 }  // namespace
 
-#ifdef MLHIP_EXPERIMENTS
-namespace {
-/// kmeans_reduce_kernel and kmeans_close_kernel in ONE launch (single rank: no all-reduce between the two; round 5): every workgroup
-/// reduces its four output elements as before, takes a ticket, and the workgroup that draws the last one -- every element of `out` is
-/// then written and, behind the fences, visible -- forms the means, the next centroid table and the pinned mirror. One dependent
-/// dispatch less per step -- and measured SLOWER: 32.2 us for the one launch against 11.8 + 4.2 us for the two (K = 256, d = 8, 512
-/// partial blocks: the last workgroup closes 2 048 entries and writes the 18 KB mirror alone, behind the slowest of 577 reductions),
-/// 1.094 against 1.074 ms per step at N = 12.5M. `make EXPERIMENTS=1` + MLHIP_KMEANS_FUSED=1 only (profiles/r05_kmeans_step.txt).
-__global__ __launch_bounds__(256) void kmeans_reduce_close_kernel(const double* __restrict__ partials, int n_blocks, size_t pstride, int K, int d,
-                                                                   int D, const double* __restrict__ scale, double* out, double* __restrict__ next,
-                                                                   double* __restrict__ mirror, unsigned* __restrict__ ticket, unsigned ticket_base)
-{
-    __shared__ int is_last;
-    const int total = 2 + K * (d + 1);
-    kmeans_reduce_element(partials, n_blocks, pstride, K, d, scale, out, blockIdx.x * 4 + (threadIdx.x >> 6), total, threadIdx.x & 63);
-    // The in-launch combine of the gfx950 guide (counter form of its hand-off): every wave's stores drained, ONE agent-scope release
-    // and ONE relaxed ticket per workgroup; the workgroup that draws the launch's last ticket acquires once and reads with plain loads.
-    // The counter is never reset: launch number m of a handle owns the tickets ticket_base .. ticket_base + gridDim.x - 1.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = t - ticket_base == gridDim.x - 1 ? 1 : 0;
-        if (is_last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!is_last) return;
-    const int threads = K * D > K + 2 ? K * D : K + 2;
-    for (int t = threadIdx.x; t < threads; t += 256) {        // kmeans_close_kernel's body
-        if (mirror && t < 2 + K) mirror[t] = out[t];
-        if (t >= K * D) continue;
-        const int k = t / D, j = t - k * D;
-        double v = 0.0;
-        if (j < d) {
-            const double c = out[2 + k];
-            double* sum = out + 2 + K + (size_t)k * d + j;
-            v = c > 0 ? *sum / c : 0.0;
-            *sum = v;
-            if (mirror) mirror[2 + K + (size_t)k * d + j] = v;
-        }
-        next[t] = v;
-    }
-}
-}  // namespace
-
-unsigned launch_kmeans_reduce_close(const KmeansArgs& a, int n_partials, int D, double* next, double* mirror, unsigned* ticket,
-                                    unsigned ticket_base, hipStream_t stream)
-{
-    const size_t pstride = 2 + (size_t)a.K * (3 * a.d + 1);
-    const int total = 2 + a.K * (a.d + 1);
-    const unsigned grid = (unsigned)((total + 3) / 4);
-    hipLaunchKernelGGL(kmeans_reduce_close_kernel, dim3(grid), dim3(256), 0, stream, a.partials, n_partials, pstride, a.K, a.d, D, a.scale, a.out,
-                       next, mirror, ticket, ticket_base);
-    return grid;
-}
-
-#endif
-
 void launch_kmeans_close(double* out, int K, int d, int D, double* next, double* mirror, hipStream_t stream)
 {
     const int threads = K * D > K + 2 ? K * D : K + 2;

@@ -2,22 +2,8 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
-#include <cstdlib>
 
 namespace mlhip {
-
-/// Environment switches that exist only to measure a decision against its alternative (A/B runs; DESIGN.md section 7 lists them with
-/// the profile that settled each): honoured by the `make EXPERIMENTS=1` library, compiled to "not set" in the default one -- the
-/// shipped binary has one code path per decision and no getenv on it.
-inline const char* ab_env(const char* name)
-{
-#ifdef MLHIP_EXPERIMENTS
-    return std::getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
 
 // ---- layout constants shared by host and device code -------------------------------------------
 constexpr int kSampleTile = 256;  // N is padded to a multiple of this in HBM
@@ -58,14 +44,6 @@ inline int padded_dim(int d)
 /// with Sigma = L L^T and coef = log(pi) - sum_j log L_jj.
 inline int estep_param_stride(int D) { return D + D * (D + 1) / 2 + 1; }
 
-/// Matrix-core E-step (dimensions 12..32, multiples of 4): W is cut into 16-row blocks J and 4-column slabs ls; only
-/// the slabs on or below the block diagonal exist. Record of one component, estep_mfma_param_stride(D) doubles:
-///   [ slab c = (J, ls) in (J-major) order: 64 doubles, lane l holds W[16J + (l&15)][4ls + (l>>4)] | mean(D) | coef ].
-inline int estep_mfma_slabs_of(int D, int J) { const int ls = D / 4; return 4 * (J + 1) < ls ? 4 * (J + 1) : ls; }
-inline int estep_mfma_slab_count(int D) { return D <= 16 ? estep_mfma_slabs_of(D, 0) : estep_mfma_slabs_of(D, 0) + estep_mfma_slabs_of(D, 1); }
-inline int estep_mfma_param_stride(int D) { return estep_mfma_slab_count(D) * 64 + D + 1; }
-inline bool estep_mfma_supported(int D) { return D >= 12 && D <= 32 && D % 4 == 0; }
-
 /// 4x4-block E-step (v_mfma_f64_4x4x4_4b_f64; dimensions 12..128, multiples of 4): W is cut into 4x4 blocks (R, C); only
 /// blocks on or below the diagonal exist, ordered by column quad C, then row quad R. Record of one component,
 /// estep_mfma4_param_stride(D) doubles:
@@ -91,12 +69,9 @@ inline int stats_count(int d) { return (d + 1) * (d + 2) / 2; }
 /// the operands of the shift-centred forms, a = 1 / sigma, b = -(mean - shift) / sigma, dimension-major so that one dimension's
 /// operands of all components are contiguous:
 ///   [ aT: D rows of KP doubles, aT[j KP + k] = a_kj | bT: D rows of KP, bT[j KP + k] = b_kj ]
-/// B2 (NaN / inf when a parameter is not finite) is what the kernels' guards read, the same on every workgroup and rank:
-///   * two-operation form  q += fma(a, x~, b)^2  (error ~ eps |b| per term): while every B2 <= kDiagAbLimit^2;
-///   * expanded form on the matrix cores  lw = coef - B2/2 + sum_j (-a^2/2) x~^2 + (-a b) x~  (error ~ eps 4 B2 in q, i.e. in a
-///     log-responsibility): while every B2 <= kDiagExpandLimit -- 4.5e-13, inside the 1e-12 parity tolerances.
+/// B2 (NaN / inf when a parameter is not finite) is what the kernels' guard reads, the same on every workgroup and rank: the
+/// two-operation form  q += fma(a, x~, b)^2  (error ~ eps |b| per term) runs while every B2 <= kDiagAbLimit^2.
 /// Padding records k >= K: a = b = 0, coef = -inf, B2 = 0.
-constexpr double kDiagExpandLimit = 1024.0;
 constexpr int diag_param_stride_c(int D) { return 2 * D + 2; }
 inline int diag_param_stride(int D) { return diag_param_stride_c(D); }
 inline size_t diag_param_doubles(int D, int KP) { return (size_t)KP * diag_param_stride_c(D) + 2 * (size_t)D * KP; }

@@ -187,32 +187,6 @@ double whitening_matrix(int d, const double* cov, std::vector<double>& L, std::v
 }
 }  // namespace
 
-#ifdef MLHIP_EXPERIMENTS
-void build_estep_params_mfma(int d, int D, int K, const double* mixing, const double* means, const double* covariances,
-                             double* records)
-{
-    const int PS = estep_mfma_param_stride(D);
-    const int NC = estep_mfma_slab_count(D);
-    const int JB = (D + 15) / 16;
-    std::vector<double> L((size_t)d * d), W((size_t)d * d);
-    for (int k = 0; k < K; ++k) {
-        double* rec = records + (size_t)k * PS;
-        for (int i = 0; i < PS; ++i) rec[i] = 0.0;
-        const double log_det_half = whitening_matrix(d, covariances + (size_t)k * d * d, L, W);
-        int c = 0;
-        for (int J = 0; J < JB; ++J)
-            for (int ls = 0; ls < estep_mfma_slabs_of(D, J); ++ls, ++c)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int row = 16 * J + (lane & 15), col = 4 * ls + (lane >> 4);
-                    rec[c * 64 + lane] = (row < d && col <= row) ? W[col * d + row] : 0.0;
-                }
-        for (int j = 0; j < d; ++j) rec[NC * 64 + j] = means[(size_t)k * d + j];
-        rec[NC * 64 + D] = std::log(mixing[k]) - log_det_half;
-    }
-}
-
-#endif
-
 bool build_estep_params_mfma4(int d, int D, int K, const double* mixing, const double* means, const double* covariances,
                               const double* shift, double fold_limit, double* records)
 {

@@ -21,10 +21,6 @@ void process_covariance(int d, const double* cov, double* inverse, double* sqrt_
 void build_estep_params(int d, int D, int K, const double* mixing, const double* means, const double* covariances,
                         double* records);
 
-/// Same for the matrix-core E-step kernel (layout: device/layout.hpp estep_mfma_param_stride).
-void build_estep_params_mfma(int d, int D, int K, const double* mixing, const double* means, const double* covariances,
-                             double* records);
-
 /// Same for the 4x4-block matrix-core E-step kernel (layout: device/layout.hpp estep_mfma4_param_stride). With a `shift`
 /// (the data's d-vector) the second vector of every record, -W (mu - shift), is filled too; returns whether the kernel's FOLD
 /// form may use it: every entry of every W_k (mu_k - shift) finite and at most `fold_limit` in magnitude.

@@ -15,9 +15,6 @@ void ensure_em_workspace(mlhip_data* dt, int K)
     dt->lse.reserve(sizeof(double) * dt->n_pad);
     dt->ll_partials.reserve(sizeof(double) * kMaxLlPartials);
     size_t ps = (size_t)estep_param_stride(dt->D) * K * sizeof(double);
-#ifdef MLHIP_EXPERIMENTS
-    if (estep_mfma_supported(dt->D)) ps = std::max(ps, (size_t)estep_mfma_param_stride(dt->D) * K * sizeof(double));
-#endif
     if (estep_mfma4_supported(dt->D)) ps = std::max(ps, (size_t)estep_mfma4_param_stride(dt->D) * K * sizeof(double));
     dt->params_dev.reserve(ps);
     dt->params_host.reserve(ps);
@@ -38,23 +35,15 @@ void prepare_estep(mlhip_data* dt, int K, const double* mixing, const double* me
     {   // (params_dev / params_next are swapped by mlhip_em_iterate and may have been sized for diagonal records)
         size_t ps = (size_t)estep_param_stride(dt->D) * K * sizeof(double);
         if (estep_mfma4_supported(dt->D)) ps = std::max(ps, (size_t)estep_mfma4_param_stride(dt->D) * K * sizeof(double));
-#ifdef MLHIP_EXPERIMENTS
-        if (estep_mfma_supported(dt->D)) ps = std::max(ps, (size_t)estep_mfma_param_stride(dt->D) * K * sizeof(double));
-#endif
         target->reserve(ps);
         dt->params_host.reserve(ps);
     }
     // d in 12..128: 4x4-block triangular matrix-core kernel (mfma4). For d <= 32, MLHIP_ESTEP=valu selects the scalar-fed
-    // VALU kernel (the only one below d = 12) and, in a `make EXPERIMENTS=1` build, MLHIP_ESTEP=mfma16 the 16x16x4
-    // block-triangular one, for A/B runs.
-    bool use_mfma = false, use_mfma4 = estep_mfma4_supported(dt->D);
+    // VALU kernel (the only one below d = 12), for A/B runs.
+    bool use_mfma4 = estep_mfma4_supported(dt->D);
     if (dt->D <= kRegDim) {
-        if (const char* e = std::getenv("MLHIP_ESTEP")) {
-            if (std::strcmp(e, "valu") == 0) use_mfma4 = false;
-#ifdef MLHIP_EXPERIMENTS
-            if (std::strcmp(e, "mfma16") == 0 && estep_mfma_supported(dt->D)) { use_mfma4 = false; use_mfma = true; }
-#endif
-        }
+        const char* e = std::getenv("MLHIP_ESTEP");
+        if (e && std::strcmp(e, "valu") == 0) use_mfma4 = false;
     }
     dt->estep_fold = false;
     // d > 64: the K factorizations on the device (em_close_big.hip launch_em_records_big -- the closing arithmetic's kernels, started
@@ -66,7 +55,7 @@ void prepare_estep(mlhip_data* dt, int K, const double* mixing, const double* me
         const char* e = r && *r ? r : std::getenv("MLHIP_DEVICE_CLOSE");
         return !(e && e[0] == '0');
     }();
-    if (records_on_device && em_close_big_supported(dt->d) && !use_mfma) {
+    if (records_on_device && em_close_big_supported(dt->d)) {
         const int d = dt->d;
         const size_t n_par = (size_t)K * ((size_t)d * d + d + 1);
         dt->close_work.reserve(sizeof(double) * em_close_work_doubles(d, K));
@@ -94,18 +83,12 @@ void prepare_estep(mlhip_data* dt, int K, const double* mixing, const double* me
                                                         kEstepFoldLimit, dt->params_host.as<double>());
         HIP_CHECK(hipMemcpyAsync(target->p, dt->params_host.p, sizeof(double) * estep_mfma4_param_stride(dt->D) * K,
                                  hipMemcpyHostToDevice, ctx->stream));
-#ifdef MLHIP_EXPERIMENTS
-    } else if (use_mfma) {
-        host::build_estep_params_mfma(dt->d, dt->D, K, mixing, means, covs, dt->params_host.as<double>());
-        HIP_CHECK(hipMemcpyAsync(target->p, dt->params_host.p, sizeof(double) * estep_mfma_param_stride(dt->D) * K,
-                                 hipMemcpyHostToDevice, ctx->stream));
-#endif
     } else {
         host::build_estep_params(dt->d, dt->D, K, mixing, means, covs, dt->params_host.as<double>());
         HIP_CHECK(hipMemcpyAsync(target->p, dt->params_host.p, sizeof(double) * estep_param_stride(dt->D) * K,
                                  hipMemcpyHostToDevice, ctx->stream));
     }
-    dt->estep_variant = use_mfma4 ? 2 : (use_mfma ? 1 : 0);
+    dt->estep_variant = use_mfma4 ? 2 : 0;
 }
 
 
@@ -125,20 +108,7 @@ void launch_estep(mlhip_data* dt, int K, bool with_lse, const DevBuf* records, i
     a.scratch = dt->partials.as<double>(); a.scratch_doubles = dt->partials.bytes / sizeof(double);   // (written by the statistics kernel AFTER the E-step, on the same stream)
     int grid = 0;
     ctx->timed("em_estep", [&] {
-        if (dt->estep_variant == 2) {
-            grid = -1;
-#ifdef MLHIP_EXPERIMENTS
-            // component-stationary form (experiments/em_estep_cs.hip: W blocks in registers, samples from LDS): measured slower
-            // than the kernel below; MLHIP_ESTEP_CS=1 selects it for A/B runs
-            static const bool cs = [] { const char* e = std::getenv("MLHIP_ESTEP_CS"); return e && e[0] == '1'; }();
-            if (cs && a.fold && !a.with_lse && em_estep_cs_supported(a.D, K)) grid = launch_em_estep_cs(a, ctx->num_cus, ctx->stream);
-#endif
-            if (grid < 0) grid = launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream);
-        }
-#ifdef MLHIP_EXPERIMENTS
-        else if (dt->estep_variant == 1) grid = launch_em_estep_mfma(a, ctx->num_cus, ctx->stream);
-#endif
-        else grid = launch_em_estep(a, ctx->stream);
+        grid = dt->estep_variant == 2 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
     });
     if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
     HIP_CHECK(hipGetLastError());

@@ -55,8 +55,6 @@ struct EmLoop {
     bool fused = false, self_norm = false;
     int resident_grid = 0;                      // > 0: the whole loop can run in one launch of this many resident workgroups
     bool resident_gave_up = false;
-    bool info_pinned = false;                   // full covariances: the closing kernel writes its info block into pinned host memory
-    bool pack_pinned = false;                   // diagonal mode: its whole (small) pack lives there
     size_t n_cov = 0, F = 0, n_info = 0, n_pack = 0;
     double refine_limit = 0;
     bool fold_allowed = true;
@@ -69,7 +67,8 @@ struct EmLoop {
     EmLoop(mlhip_data* dt, int K_, bool diag_, double* mixing_, double* means_, double* covs_)
         : data(dt), ctx(dt->ctx), K(K_), d(dt->d), diag(diag_), mixing(mixing_), means(means_), covs(covs_) {}
 
-    double* pack_base(int slot) const { return pack_pinned ? data->it_info_slot[slot].as<double>() : data->it_pack[slot].as<double>(); }
+    // The closing kernel writes its info block into pinned host memory (it_info_slot); in diagonal mode the whole (small) pack lives there.
+    double* pack_base(int slot) const { return diag ? data->it_info_slot[slot].as<double>() : data->it_pack[slot].as<double>(); }
     double* pack_mixing(int slot) const { return pack_base(slot) + n_info; }
     double* pack_means(int slot) const { return pack_mixing(slot) + K; }
     double* pack_covs(int slot) const { return pack_means(slot) + (size_t)K * d; }
@@ -83,15 +82,11 @@ struct EmLoop {
         if (!env_allows("MLHIP_DEVICE_CLOSE") || !em_close_supported(d) || (diag && !mstats::em_diag_supported(d, K))) return false;
         if (!diag) {
             prepare_estep(data, K, mixing, means, covs);           // -> params_dev, estep_variant, estep_fold
-            if (data->estep_variant == 1) return false;            // (experimental record layout: host closing only)
         }
         n_cov = diag ? (size_t)K * d : (size_t)K * d * d;
         F = diag ? diag_stats_count(d) : stats_count(d);
         n_info = em_close_info_doubles(K);
         n_pack = n_info + K + (size_t)K * d + n_cov;
-        const bool pinned = !(ab_env("MLHIP_INFO_PINNED") && ab_env("MLHIP_INFO_PINNED")[0] == '0');
-        info_pinned = pinned && !diag;
-        pack_pinned = pinned && diag;
         for (int s = 0; s < 3; ++s) {
             data->it_pack[s].reserve(sizeof(double) * n_pack);
             data->it_info_slot[s].reserve(sizeof(double) * n_pack);
@@ -147,13 +142,10 @@ struct EmLoop {
         ca.layout = data->estep_variant; ca.refine_limit = refine_limit;
         ca.mixing = pack_mixing(out); ca.means = pack_means(out); ca.covs = pack_covs(out);
         ca.records = rec[out]->as<double>();
-        ca.info = info_pinned ? data->it_info_slot[out].as<double>() : pack_base(out);
+        ca.info = data->it_info_slot[out].as<double>();
         ca.work = data->close_work.as<double>();
         ctx->timed("em_close", [&] { if (diag) launch_em_close_diag(ca, ctx->stream); else launch_em_close(ca, ctx->stream); });
         HIP_CHECK(hipGetLastError());
-        if (!info_pinned && !pack_pinned)
-            HIP_CHECK(hipMemcpyAsync(data->it_info_slot[out].p, data->it_pack[out].p, sizeof(double) * (diag ? n_pack : n_info),
-                                     hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipEventRecord(data->it_event[out], ctx->stream));
         launched = i + 1;
     }
@@ -193,7 +185,7 @@ struct EmLoop {
         a.shift = data->shift_dev.as<double>();
         for (int s = 0; s < 3; ++s) {
             a.records[s] = rec[s]->as<double>();
-            a.info[s] = info_pinned ? data->it_info_slot[s].as<double>() : pack_base(s);
+            a.info[s] = data->it_info_slot[s].as<double>();
             a.mixing[s] = pack_mixing(s); a.means[s] = pack_means(s); a.covs[s] = pack_covs(s);
         }
         a.xch = data->it_xch.as<double>(); a.sync = data->it_sync.as<unsigned>(); a.vgrid = resident_grid;
@@ -351,14 +343,12 @@ struct EmLoop {
     /// host's share to matter -- the speculative iteration is thrown away once per fit, which a long iteration never earns back
     /// (N = 10M, d = 8, K = 32: 2.2 ms per iteration against ~10 us saved) -- and never with a host-side all-reduce. Decided from the
     /// GLOBAL row count: every rank (every shard of a device group) must take the same loop, or a lagged rank's speculative
-    /// all-reduce would meet another rank's end-of-fit exchange. MLHIP_LAGGED=0: off; MLHIP_LAGGED_WORK: the bound on
-    /// N K d^2 per rank (default 2e9; diagonal: N K d <= 1e9).
+    /// all-reduce would meet another rank's end-of-fit exchange. Bound on the work per rank: N K d^2 <= 2e9 (diagonal:
+    /// N K d <= 1e9).
     bool lagged_applies(uint32_t max_steps) const
     {
-        static const double work_limit = [] { const char* e = ab_env("MLHIP_LAGGED_WORK"); return e ? std::atof(e) : 2.0e9; }();
         const double pair_work = (double)data->n_global / (double)std::max(1, ctx->world_size) * K * (diag ? d : d * d);
-        return !(ab_env("MLHIP_LAGGED") && ab_env("MLHIP_LAGGED")[0] == '0') && (!ctx->reduce_fn || ctx->reduce_on_device) && max_steps >= 2 &&
-               pair_work <= (diag ? 1.0e9 : work_limit);
+        return (!ctx->reduce_fn || ctx->reduce_on_device) && max_steps >= 2 && pair_work <= (diag ? 1.0e9 : 2.0e9);
     }
 
     /// Lagged policy: the convergence test of ML/EM.cpp:161-168 fires one iteration late and the speculative iteration is simply
@@ -418,7 +408,7 @@ struct EmLoop {
     }
 };
 
-/// d > 1024 (no device closing), MLHIP_DEVICE_CLOSE=0, experimental record layouts: the loop over the per-step functions.
+/// d > 1024 (no device closing), MLHIP_DEVICE_CLOSE=0: the loop over the per-step functions.
 void host_closing_loop(mlhip_data* data, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps,
                        ConvergenceTest& test)
 {

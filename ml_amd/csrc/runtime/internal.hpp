@@ -371,7 +371,7 @@ struct mlhip_data {
     int n_ll = 0;
     bool have_estep = false;
     bool lw_valid = false;        // false after a fused step: lw is rebuilt from params_dev on demand (ensure_lw)
-    int estep_variant = 0;        // record layout currently in params_dev: 0 = valu, 1 = mfma16, 2 = mfma4
+    int estep_variant = 0;        // record layout currently in params_dev: 0 = valu, 2 = mfma4 (CloseArgs::layout codes)
     bool estep_fold = false;      // mfma4 records in FOLD form (vector slot = -W (mu - shift)): layout.hpp kEstepFoldLimit
     // diagonal-covariance extension: parameters of the last mlhip_em_step_diag (the N x K block is rebuilt from them on demand)
     bool diag_step = false;
@@ -401,8 +401,6 @@ struct mlhip_data {
     DevBuf km_labels[2], km_cent, km_cent_next, km_partials, km_out, km_mind, km_probe, km_scale, km_cnorm, km_xt_pad;
     PinnedBuf km_host;
     DevBuf kpp_w, kpp_scr;               // mlhip_kpp_draw: the running-minimum weights, block sums / offsets / result
-    DevBuf km_ticket;                    // kmeans_reduce_close_kernel: the arrival counter, never reset ...
-    unsigned km_ticket_base = 0;         // ... and the tickets drawn from it so far (wraps with it)
     int km_cur = 0;
     bool km_have_old = false;
 
@@ -410,7 +408,7 @@ struct mlhip_data {
     void attach_pool(BufferPool* pool)
     {
         for (DevBuf* b : {&xt, &shift_dev, &lw, &lse, &esum, &ll_partials, &params_dev, &partials, &stats_dev, &resp_dev,
-                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr, &km_ticket,
+                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr,
                           &refine_shift, &refine_stats, &nz_dev, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
             b->pool = pool;
         for (PinnedBuf* b : {&params_host, &stats_host, &nz_host, &km_host, &it_info_slot[0], &it_info_slot[1], &it_info_slot[2], &it_history}) b->pool = pool;
@@ -420,7 +418,7 @@ struct mlhip_data {
     {
         for (mlhip_data* p : parts) mlhip_data_free(p);
         for (DevBuf* b : {&xt, &shift_dev, &lw, &lse, &esum, &ll_partials, &params_dev, &partials, &stats_dev, &resp_dev,
-                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr, &km_ticket,
+                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr,
                           &refine_shift, &refine_stats, &nz_dev, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
             b->release();
         for (auto& sl : it_info_slot) sl.release();
@@ -540,10 +538,7 @@ void km_upload_centroids(mlhip_data* dt, int K, const KmBlock& b, const double* 
 
 /// Assignment (+ optional accumulation) against the table in km_cent, partials reduced into km_out =
 /// [inertia, changed, counts, sums] and summed across ranks there when the all-reduce works on device memory.
-/// `close_next` (with accumulate, single rank): the closing arithmetic rides in the reduction's launch (kmeans_reduce_close_kernel) --
-/// means into km_out, the next table into close_next, the block into the pinned close_mirror (may be null); returns true when it did.
-bool km_launch(mlhip_data* dt, int K, const KmBlock& b, bool accumulate, double* min_dist_out, double* close_next = nullptr,
-               double* close_mirror = nullptr);
+void km_launch(mlhip_data* dt, int K, const KmBlock& b, bool accumulate, double* min_dist_out);
 
 /// km_out -> km_host (`count` doubles), summed across ranks on the host when the all-reduce works on host memory.
 void km_fetch(mlhip_data* dt, size_t count);

@@ -236,9 +236,8 @@ def test_bad_arguments(ctx):
 
 @pytest.mark.parametrize("d,K", [(12, 7), (16, 16), (20, 5), (24, 9), (28, 3), (32, 64)])
 def test_estep_kernel_variants_agree(ctx, oracle, d, K, monkeypatch):
-    """The two E-step kernels of the default build that exist for d in 12..32 (4x4x4 MFMA = default, scalar-fed VALU) compute
-    the same log-likelihood / responsibilities / labels; the default one is also checked against the oracle. (The 16x16x4
-    variant is an experiment: `make EXPERIMENTS=1`.)"""
+    """The two E-step kernels that exist for d in 12..32 (4x4x4 MFMA = default, scalar-fed VALU) compute the same
+    log-likelihood / responsibilities / labels; the default one is also checked against the oracle."""
     rng = np.random.default_rng(d * 100 + K)
     n = 3000
     means = 2.5 * rng.standard_normal((K, d))
