@@ -103,6 +103,22 @@ public:
     DLL_DECLSPEC void init(ConstMatrixRef data, std::default_random_engine& prng, unsigned int number_components, MatrixRef centroids) const override;
 };
 
+/** @brief Extension (not in the reference): K-means++ seeding from exact integer cumulative weights. It samples the same D^2
+distribution as KPP but NOT with KPP's draws (KPP reproduces std::discrete_distribution bit for bit); in exchange the draw on the GPU
+never falls back to the host, whatever N, and does not depend on how many ranks or shards hold the sample. The rule, which the
+host init() states and the device route reproduces bit for bit:
+  - N < 2: every centroid is row 0, no draw. Otherwise one std::generate_canonical<double, 53> call per centroid (the same prng).
+  - Centroid 0: row floor(u N).
+  - Centroid c >= 1: w_i = the running minimum of the squared distances of row i to the centroids chosen so far, each the
+    ascending-j chain s = fma(x_j - c_j, x_j - c_j, s). E = the largest frexp exponent of any w_i of the whole sample,
+    q_i = floor(w_i 2^(52 - E)) (an integer below 2^52), T = sum q_i (integer arithmetic), t = floor(u T) (exact). The pick is
+    the smallest row i with q_0 + ... + q_i > t (a row with q_i = 0 is never picked); T = 0: row floor(u N).
+@throw std::invalid_argument (init) If a weight is not finite, or the sample is empty. */
+class FixedPointKPP : public CentroidsInitialiser {
+public:
+    DLL_DECLSPEC void init(ConstMatrixRef data, std::default_random_engine& prng, unsigned int number_components, MatrixRef centroids) const override;
+};
+
 /** @brief Extension (not in the reference): returns the centroids it was constructed with. */
 class FixedCentroids : public CentroidsInitialiser {
 public:

@@ -72,6 +72,7 @@ protected:
 class Forgy : public CentroidsInitialiser { public: Forgy() { detail::check(mlpp_forgy_create(&h_)); } };
 class RandomPartition : public CentroidsInitialiser { public: RandomPartition() { detail::check(mlpp_random_partition_create(&h_)); } };
 class KPP : public CentroidsInitialiser { public: KPP() { detail::check(mlpp_kpp_create(&h_)); } };
+class FixedPointKPP : public CentroidsInitialiser { public: FixedPointKPP() { detail::check(mlpp_fixed_point_kpp_create(&h_)); } };
 
 class ResponsibilitiesInitialiser {
 public:

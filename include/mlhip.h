@@ -252,6 +252,16 @@ int mlhip_kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int
 /* The running-minimum weights the draws of mlhip_kpp_draw have left on the device (n_local doubles): fetched by the caller only when
  * a draw was not certain -- a certified draw never moves them (ML/Clustering.cpp:44-51 keeps them in a host vector). */
 int mlhip_kpp_weights(mlhip_ctx* ctx, mlhip_data* data, double* weights_out);
+/* One draw of FixedPointKPP (include/ML/Clustering.hpp; not the reference's KPP draws) on the resident block(s): the weights become
+ * min(weights, |x_i - centroid|^2) (first != 0: the distances themselves; ascending-j fma chain), then with E the largest frexp
+ * exponent of any weight of the WHOLE sample, q_i = floor(w_i 2^(52 - E)) and T = sum q_i (exact integers), *index is the smallest
+ * row of the whole sample with q_0 + ... + q_i > floor(u T) -- or floor(u N) when T = 0. Every route (any number of ranks or shards,
+ * the host restatement) gives the same row; only O(1) values per draw leave the device. Row-sharded jobs: every rank calls it with
+ * the same centroid and u and the global index of its first row (first_row; 0 on a single rank); the ranks exchange their largest
+ * exponents and integer totals through the context's all-reduce. MLHIP_E_INVALID_ARGUMENT on every rank when a weight is not
+ * finite. */
+int mlhip_kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int first, double u, uint64_t first_row,
+                               uint64_t* index);
 /* min_k |x_i - c_k|^2 per sample of this rank's shard (the weights of KPP::init, ML/Clustering.cpp:44-51). */
 int mlhip_min_squared_distances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* dist2);
 

@@ -22,6 +22,9 @@ typedef struct mlpp_kmeans mlpp_kmeans;
 int mlpp_forgy_create(mlpp_centroids_initialiser** out);
 int mlpp_random_partition_create(mlpp_centroids_initialiser** out);
 int mlpp_kpp_create(mlpp_centroids_initialiser** out);
+/* Extension: K-means++ seeding from exact integer cumulative weights (ML::Clustering::FixedPointKPP): the D^2 distribution of KPP,
+ * but not its draws; on the GPU every draw stays on the device, whatever N. */
+int mlpp_fixed_point_kpp_create(mlpp_centroids_initialiser** out);
 /* Extension: fixed centroids, K x d row-major (row k = centroid k). */
 int mlpp_fixed_centroids_create(const double* centroids, uint32_t K, uint32_t d, mlpp_centroids_initialiser** out);
 int mlpp_centroids_initialiser_destroy(mlpp_centroids_initialiser* h);

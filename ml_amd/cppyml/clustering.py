@@ -8,7 +8,7 @@ Conventions kept from the reference:
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
 Extensions (not in the reference surface): `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
-`KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`.
+`KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`.
 """
 import ctypes as C
 
@@ -106,6 +106,15 @@ class KPP(CentroidsInitialiser):
     def __init__(self):
         self._h = C.c_void_p()
         _check(_l.mlpp_kpp_create(C.byref(self._h)))
+
+
+class FixedPointKPP(CentroidsInitialiser):
+    """Extension: K-means++ seeding from exact integer cumulative weights. Same D^2 distribution as KPP, different draws (KPP
+    reproduces the reference's draws bit for bit); on the GPU every draw stays on the device, whatever the sample size."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        _check(_l.mlpp_fixed_point_kpp_create(C.byref(self._h)))
 
 
 class FixedCentroids(CentroidsInitialiser):

@@ -36,6 +36,21 @@ void launch_kpp_update(double* weights, const double* dist, uint32_t n, int firs
 void launch_kpp_find(const double* weights, uint32_t n, const double* bsum, const double* boff, double offset, double total, double u,
                      double delta, uint64_t row0, uint64_t n_global, double* out, hipStream_t stream);
 
+/// One fixed-point K-means++ draw (FixedPointKPP) on the device (kpp_fixed_point.hip); fp_kpp_blocks(n) workgroups of 4096 rows.
+/// update:   w = first ? |x_i - centroid|^2 : min(w, |x_i - centroid|^2) over the n rows of xt (centroid: d doubles of device memory);
+///           bmax[b] = the bits of block b's largest new weight, *wmax = the largest of them;
+/// quantise: q_i = floor(w_i 2^(52 - E)); bsum[2b], bsum[2b + 1] = the sums of q_i >> 32 and q_i mod 2^32 over block b, total[0] /
+///           total[1] = their sums over the blocks;
+/// (n = 0: nothing is launched, the outputs keep what the caller put there)
+/// locate:   out[0] = row0 + the smallest row i with q_0 + ... + q_i > target (target = target_hi 2^64 + target_lo, below the sum
+///           of all q_i; one workgroup). out[0] is left untouched when the target lies beyond the sum.
+int fp_kpp_blocks(uint32_t n);
+void launch_fp_kpp_update(const double* xt, size_t ldx, int d, uint32_t n, const double* centroid, int first, double* w, uint64_t* bmax,
+                          uint64_t* wmax, hipStream_t stream);
+void launch_fp_kpp_quantise(const double* w, uint32_t n, int E, uint64_t* bsum, uint64_t* total, hipStream_t stream);
+void launch_fp_kpp_locate(const double* w, uint32_t n, int E, const uint64_t* bsum, uint64_t target_lo, uint64_t target_hi, uint64_t row0,
+                          uint64_t* out, hipStream_t stream);
+
 /// Fixed-order sum of the n <= kGroupMaxShards buffers slots.p[0..n) (`count` doubles each) into out: the all-reduce of a device
 /// group whose shards share a process (runtime/group.cpp).
 constexpr int kGroupMaxShards = 64;

@@ -9,6 +9,8 @@
 #include <numeric>
 #include <stdexcept>
 
+#include "device/fixed_point.hpp"
+
 namespace ml {
 namespace Clustering {
 
@@ -71,6 +73,54 @@ void KPP::init(ConstMatrixRef data, std::default_random_engine& prng, const unsi
         }
         std::discrete_distribution<Index> draw(weights.begin(), weights.end());
         std::copy_n(data.col(draw(prng)), d, centroids.col(chosen));
+    }
+}
+
+void FixedPointKPP::init(ConstMatrixRef data, std::default_random_engine& prng, const unsigned int number_components, MatrixRef centroids) const
+{
+    using mlhip::fixed_point::u128;
+    using mlhip::fixed_point::scaled_floor;
+    const Index n = data.cols(), d = data.rows();
+    if (n == 0) throw std::invalid_argument("FixedPointKPP: at least one sample required");
+    const std::size_t count = static_cast<std::size_t>(n);
+    std::vector<double> weights(count);
+    for (unsigned int chosen = 0; chosen < number_components; ++chosen) {
+        Index pick = 0;
+        if (n >= 2) {
+            const double u = std::generate_canonical<double, std::numeric_limits<double>::digits>(prng);
+            u128 total = 0;
+            std::vector<uint64_t> q;
+            if (chosen > 0) {
+                double largest = 0.0;
+                for (std::size_t i = 0; i < count; ++i) {
+                    const double s = squared_distance(data.col(static_cast<Index>(i)), centroids.col(chosen - 1), d);
+                    const double w = chosen == 1 ? s : std::min(weights[i], s);
+                    if (!std::isfinite(w)) throw std::invalid_argument("FixedPointKPP: a weight (squared distance to a chosen centroid) is not finite");
+                    weights[i] = w;
+                    largest = std::max(largest, w);
+                }
+                if (largest > 0.0) {
+                    int E = 0;
+                    std::frexp(largest, &E);
+                    q.resize(count);
+                    for (std::size_t i = 0; i < count; ++i) {
+                        q[i] = static_cast<uint64_t>(std::floor(std::ldexp(weights[i], 52 - E)));   // exact: a power-of-two scaling
+                        total += q[i];
+                    }
+                }
+            }
+            if (total == 0) {
+                pick = static_cast<Index>(scaled_floor(u, static_cast<u128>(n)));
+            } else {
+                const u128 target = scaled_floor(u, total);
+                u128 cumulative = 0;
+                for (std::size_t i = 0; i < count; ++i) {
+                    cumulative += q[i];
+                    if (cumulative > target) { pick = static_cast<Index>(i); break; }
+                }
+            }
+        }
+        std::copy_n(data.col(pick), d, centroids.col(chosen));
     }
 }
 

@@ -6,10 +6,12 @@
 #include <iterator>
 #include <limits>
 #include <random>
+#include <stdexcept>
 #include <typeinfo>
 #include <vector>
 
 #include "ML/Device.hpp"
+#include "device/fixed_point.hpp"
 #include "mlhip.h"
 
 namespace ml {
@@ -232,6 +234,39 @@ void kpp_sharded(const Shard& sh, ConstMatrixRef data, std::default_random_engin
     }
 }
 
+/// FixedPointKPP on the whole sample, the draws on the devices (mlhip_kpp_draw_fixed_point): every rank gets the same global row
+/// per centroid -- the one the host rule picks, whatever the number of ranks -- and its owner contributes it. A single rank is the
+/// world-of-one case.
+void fixed_point_kpp_sharded(const Shard& sh, ConstMatrixRef data, std::default_random_engine& prng, unsigned int K, MatrixRef centroids,
+                             mlhip_ctx* ctx, mlhip_data* device_data)
+{
+    if (sh.n_global == 0) throw std::invalid_argument("FixedPointKPP: at least one sample required");
+    const Index d = data.rows();
+    std::vector<double> pick(static_cast<std::size_t>(d));
+    for (unsigned int chosen = 0; chosen < K; ++chosen) {
+        Index global = 0;
+        if (sh.n_global >= 2) {
+            const double u = std::generate_canonical<double, std::numeric_limits<double>::digits>(prng);
+            if (chosen == 0) {
+                global = static_cast<Index>(mlhip::fixed_point::scaled_floor(u, static_cast<mlhip::fixed_point::u128>(sh.n_global)));
+            } else {
+                uint64_t index = 0;
+                device::check(mlhip_kpp_draw_fixed_point(ctx, device_data, centroids.col(chosen - 1), chosen == 1 ? 1 : 0, u,
+                                                         static_cast<uint64_t>(sh.lo), &index));
+                global = static_cast<Index>(index);
+            }
+        }
+        if (sh.world == 1) {
+            std::copy_n(data.col(global), d, centroids.col(chosen));
+            continue;
+        }
+        std::fill(pick.begin(), pick.end(), 0.0);
+        if (global >= sh.lo && global < sh.hi) std::copy_n(data.col(global - sh.lo), d, pick.data());
+        device::check(mlhip_ctx_allreduce(ctx, pick.data(), pick.size()));   // only the owner's copy is non-zero
+        std::copy_n(pick.data(), d, centroids.col(chosen));
+    }
+}
+
 }  // namespace
 
 void locate_rows(mlhip_ctx* ctx, Index n_local, Index& first_row, Index& n_global)
@@ -259,11 +294,19 @@ void init_centroids(const CentroidsInitialiser& initialiser, ConstMatrixRef data
             random_partition_sharded(sh, data, prng, number_components, centroids, ctx, device_data);
         } else if (typeid(initialiser) == typeid(KPP) && device_data) {
             kpp_sharded(sh, data, prng, number_components, centroids, ctx, device_data);
+        } else if (typeid(initialiser) == typeid(FixedPointKPP) && device_data) {
+            fixed_point_kpp_sharded(sh, data, prng, number_components, centroids, ctx, device_data);
         } else {
             initialiser.init(data, prng, number_components, centroids);
             if (rank != 0) centroids.setZero();
             allreduce_matrix(ctx, centroids);
         }
+        return;
+    }
+    if (ctx && device_data && typeid(initialiser) == typeid(FixedPointKPP)) {
+        Shard sh;                                   // the whole sample on one rank (or one device group)
+        sh.hi = sh.n_global = data.cols();
+        fixed_point_kpp_sharded(sh, data, prng, number_components, centroids, ctx, device_data);
         return;
     }
     if (ctx && device_data && typeid(initialiser) == typeid(RandomPartition)) {

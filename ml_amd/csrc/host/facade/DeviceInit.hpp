@@ -16,7 +16,8 @@ namespace detail {
 
 /// Runs `initialiser` for `data`; when it is exactly the library's KPP and the context is single-rank, the
 /// nearest-chosen-centroid distances (ML/Clustering.cpp:44-51) are computed on the device incrementally
-/// (min with the distance to the newest centroid: one N*d pass per centroid instead of N*n*d).
+/// (min with the distance to the newest centroid: one N*d pass per centroid instead of N*n*d). FixedPointKPP draws every row on the
+/// device(s) (mlhip_kpp_draw_fixed_point), single-rank and sharded alike.
 void init_centroids(const CentroidsInitialiser& initialiser, ConstMatrixRef data, std::default_random_engine& prng,
                     unsigned int number_components, MatrixRef centroids, mlhip_ctx* ctx, mlhip_data* device_data);
 

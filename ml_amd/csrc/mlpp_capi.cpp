@@ -48,6 +48,10 @@ extern "C" {
 int mlpp_forgy_create(mlpp_centroids_initialiser** out) { return guarded([&] { need(out); *out = new mlpp_centroids_initialiser{std::make_shared<Clustering::Forgy>()}; }); }
 int mlpp_random_partition_create(mlpp_centroids_initialiser** out) { return guarded([&] { need(out); *out = new mlpp_centroids_initialiser{std::make_shared<Clustering::RandomPartition>()}; }); }
 int mlpp_kpp_create(mlpp_centroids_initialiser** out) { return guarded([&] { need(out); *out = new mlpp_centroids_initialiser{std::make_shared<Clustering::KPP>()}; }); }
+int mlpp_fixed_point_kpp_create(mlpp_centroids_initialiser** out)
+{
+    return guarded([&] { need(out); *out = new mlpp_centroids_initialiser{std::make_shared<Clustering::FixedPointKPP>()}; });
+}
 int mlpp_fixed_centroids_create(const double* centroids, uint32_t K, uint32_t d, mlpp_centroids_initialiser** out)
 {
     return guarded([&] {

@@ -671,6 +671,19 @@ void kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int firs
     *certain = sure[0];
 }
 
+void kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int first, double u, uint64_t first_row, uint64_t* index)
+{
+    check_group_data(ctx, data);
+    require(centroid && index, "null argument");
+    require(first_row == 0, "a device group holds the whole sample: first_row must be 0");
+    mlhip_group* g = group_of(ctx);
+    std::vector<uint64_t> idx((size_t)g->n, 0);
+    each_shard(ctx, [&](int s, mlhip_ctx* c) {
+        check_status(mlhip_kpp_draw_fixed_point(c, data->parts[(size_t)s], centroid, first, u, data->first_row[(size_t)s], &idx[(size_t)s]));
+    });
+    *index = idx[0];
+}
+
 void kpp_weights(mlhip_ctx* ctx, mlhip_data* data, double* weights_out)
 {
     check_group_data(ctx, data);

@@ -401,6 +401,8 @@ struct mlhip_data {
     DevBuf km_labels[2], km_cent, km_cent_next, km_partials, km_out, km_mind, km_probe, km_scale, km_cnorm, km_xt_pad;
     PinnedBuf km_host;
     DevBuf kpp_w, kpp_scr;               // mlhip_kpp_draw: the running-minimum weights, block sums / offsets / result
+    DevBuf fp_w, fp_scr;                 // mlhip_kpp_draw_fixed_point: the running-minimum weights; [slots | block sums | block maxima | centroid]
+    PinnedBuf fp_host;                   // its read-back slots
     int km_cur = 0;
     bool km_have_old = false;
 
@@ -408,22 +410,22 @@ struct mlhip_data {
     void attach_pool(BufferPool* pool)
     {
         for (DevBuf* b : {&xt, &shift_dev, &lw, &lse, &esum, &ll_partials, &params_dev, &partials, &stats_dev, &resp_dev,
-                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr,
+                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr, &fp_w, &fp_scr,
                           &refine_shift, &refine_stats, &nz_dev, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
             b->pool = pool;
-        for (PinnedBuf* b : {&params_host, &stats_host, &nz_host, &km_host, &it_info_slot[0], &it_info_slot[1], &it_info_slot[2], &it_history}) b->pool = pool;
+        for (PinnedBuf* b : {&params_host, &stats_host, &nz_host, &km_host, &fp_host, &it_info_slot[0], &it_info_slot[1], &it_info_slot[2], &it_history}) b->pool = pool;
     }
 
     ~mlhip_data()
     {
         for (mlhip_data* p : parts) mlhip_data_free(p);
         for (DevBuf* b : {&xt, &shift_dev, &lw, &lse, &esum, &ll_partials, &params_dev, &partials, &stats_dev, &resp_dev,
-                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr,
+                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr, &fp_w, &fp_scr,
                           &refine_shift, &refine_stats, &nz_dev, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
             b->release();
         for (auto& sl : it_info_slot) sl.release();
         for (auto& e : it_event) if (e) (void)hipEventDestroy(e);
-        params_host.release(); stats_host.release(); nz_host.release(); km_host.release(); it_history.release();
+        params_host.release(); stats_host.release(); nz_host.release(); km_host.release(); fp_host.release(); it_history.release();
     }
 };
 
@@ -641,6 +643,7 @@ void kmeans_distances(mlhip_ctx* ctx, mlhip_data* data, double* dist2);
 void kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int first, double u, uint64_t first_row, uint64_t* index,
               int* certain, double* weights_out);
 void kpp_weights(mlhip_ctx* ctx, mlhip_data* data, double* weights_out);
+void kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int first, double u, uint64_t first_row, uint64_t* index);
 void min_squared_distances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* dist2);
 void timing_enable(mlhip_ctx* ctx, int on);
 void timing_reset(mlhip_ctx* ctx);

@@ -2,6 +2,7 @@
 #include <cmath>
 #include <vector>
 
+#include "device/fixed_point.hpp"
 #include "internal.hpp"
 
 namespace mlhip_rt {
@@ -417,6 +418,106 @@ int mlhip_kpp_weights(mlhip_ctx* ctx, mlhip_data* data, double* weights_out)
         require(data->kpp_w.p != nullptr, "no K-means++ draw on the device yet");
         ctx->sync();
         download_columns(ctx, reinterpret_cast<char*>(weights_out), 0, data->kpp_w.as<char>(), 0, sizeof(double) * data->n, 1);
+    });
+}
+
+int mlhip_kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int first, double u, uint64_t first_row,
+                               uint64_t* index)
+{
+    return guarded([&] {
+        if (ctx && ctx->group) { grp::kpp_draw_fixed_point(ctx, data, centroid, first, u, first_row, index); return; }
+        using fixed_point::u128;
+        check_em_args(ctx, data, 1);
+        require(centroid && index, "null argument");
+        require(u >= 0.0 && u < 1.0, "u must be a canonical uniform draw");
+        const uint64_t n_global = data->n_global;
+        require(first_row + data->n <= n_global, "first_row beyond the sample");
+        require(first || data->fp_w.p, "no fixed-point K-means++ weights on the device yet: the first draw needs first != 0");
+        const int d = data->d;
+        const int nb = fp_kpp_blocks(data->n);
+        data->fp_w.reserve(sizeof(double) * data->n_pad);
+        data->fp_scr.reserve(sizeof(uint64_t) * (4 + 3 * (size_t)nb) + sizeof(double) * (size_t)d);
+        data->fp_host.reserve(sizeof(uint64_t) * 4);
+        uint64_t* slots = data->fp_scr.as<uint64_t>();   // [0] largest weight's bits, [1] / [2] the rank's totals, [3] the row
+        uint64_t* bsum = slots + 4;                      // 2 per block
+        uint64_t* bmax = bsum + 2 * (size_t)nb;          // 1 per block
+        double* cdev = reinterpret_cast<double*>(bmax + nb);
+        uint64_t* res = data->fp_host.as<uint64_t>();
+        HIP_CHECK(hipMemcpyAsync(cdev, centroid, sizeof(double) * (size_t)d, hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipMemsetAsync(slots, 0, sizeof(uint64_t) * 3, ctx->stream));
+        ctx->timed("kpp_fixed_point", [&] {
+            launch_fp_kpp_update(data->xt.as<double>(), data->ldx, d, data->n, cdev, first ? 1 : 0, data->fp_w.as<double>(), bmax, slots,
+                                 ctx->stream);
+        });
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(res, slots, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        // Every value that crosses the (double) all-reduce is an integer below 2^53 in its rank's slot: the sums are exact.
+        int world = 1, rank = 0;
+        if (ctx->reduce_fn) { world = ctx->world_size; rank = ctx->rank; }
+        const size_t W = (size_t)world, R = (size_t)rank;
+        // 1. the largest exponent of the whole sample and whether any weight is non-finite: [exponent + bias | flag] per rank
+        std::vector<double> ex(2 * W, 0.0);
+        const bool bad = res[0] >= 0x7ff0000000000000ull;
+        if (bad) {
+            ex[2 * R + 1] = 1.0;
+        } else if (res[0] != 0) {
+            double m = 0.0;
+            std::memcpy(&m, &res[0], sizeof m);
+            int e = 0;
+            std::frexp(m, &e);
+            ex[2 * R] = (double)(e + fixed_point::kExponentBias);
+        }
+        if (world > 1) ctx->allreduce_host(ex.data(), ex.size());
+        int code = 0;
+        bool any_bad = false;
+        for (size_t r = 0; r < W; ++r) {
+            code = std::max(code, (int)ex[2 * r]);
+            any_bad = any_bad || ex[2 * r + 1] != 0.0;
+        }
+        if (any_bad) throw InvalidArgument("FixedPointKPP: a weight (squared distance to a chosen centroid) is not finite");
+        // 2. the ranks' integer totals T_r = (a + b) 2^32 + c, exchanged as a = sum of the high parts (< 2^52), b, c = the upper and
+        //    lower 32 bits of the sum of the low parts (< 2^64)
+        u128 total = 0, offset = 0, mine = 0;
+        const int E = code - fixed_point::kExponentBias;
+        if (code != 0) {
+            ctx->timed("kpp_fixed_point", [&] { launch_fp_kpp_quantise(data->fp_w.as<double>(), data->n, E, bsum, slots + 1, ctx->stream); });
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(res + 1, slots + 1, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost, ctx->stream));
+            ctx->sync();
+            std::vector<double> tot(3 * W, 0.0);
+            tot[3 * R] = (double)res[1];
+            tot[3 * R + 1] = (double)(res[2] >> 32);
+            tot[3 * R + 2] = (double)(res[2] & 0xffffffffull);
+            if (world > 1) ctx->allreduce_host(tot.data(), tot.size());
+            for (size_t r = 0; r < W; ++r) {
+                const u128 t_r = ((u128)((uint64_t)tot[3 * r] + (uint64_t)tot[3 * r + 1]) << 32) + (uint64_t)tot[3 * r + 2];
+                if (r == R) { offset = total; mine = t_r; }
+                total += t_r;
+            }
+        }
+        if (total == 0) {                               // every weight 0 (or none): a uniform row, as for the first centroid
+            *index = (uint64_t)fixed_point::scaled_floor(u, n_global);
+            return;
+        }
+        // 3. the target t = floor(u T) and the row whose cumulative sum first exceeds it, on the rank that holds it
+        const u128 target = fixed_point::scaled_floor(u, total);
+        double pick = 0.0;
+        if (target >= offset && target - offset < mine) {
+            const u128 local = target - offset;
+            HIP_CHECK(hipMemsetAsync(slots + 3, 0xff, sizeof(uint64_t), ctx->stream));
+            ctx->timed("kpp_fixed_point", [&] {
+                launch_fp_kpp_locate(data->fp_w.as<double>(), data->n, E, bsum, (uint64_t)local, (uint64_t)(local >> 64), first_row, slots + 3,
+                                     ctx->stream);
+            });
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(res + 3, slots + 3, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+            ctx->sync();
+            if (res[3] == ~0ull) throw std::runtime_error("FixedPointKPP: the device scan did not find the drawn row");
+            pick = (double)res[3];
+        }
+        if (world > 1) ctx->allreduce_host(&pick, 1);   // only the owner's slot is non-zero
+        *index = (uint64_t)pick;
     });
 }
 
