@@ -16,11 +16,19 @@ sufficient statistics per iteration: ncclAllReduce on the library's own RCCL com
 `--allreduce torch` routes it through torch.distributed's nccl backend instead). torch.distributed carries the
 RCCL unique id, the barriers around the timed region and the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line on rank 0. At N=1 the line also carries `secondary`, a list: K-means (BASELINE.json configs[4]) at one
-GPU's share of that job, N=12.5M, d=8, K=256, the diagonal-covariance GMM of configs[1] (N=1M, d=16, K=16) and the reference's own
-benchmark case configs[0] (bm_EM.cpp: N=10k, d=4, K=3 -- latency-bound: three dependent launches per iteration), each with its
-own roofline and cpu_baseline. Every line carries `allreduce_ms` (average device time of the statistics all-reduce, max over
-ranks; 0 on one GPU) and the spread of the ranks' own time per step (`ms_per_step_min` / `_max`).
+Prints ONE JSON line on rank 0. A plain run does only what that line's headline needs: it sets up, warms up, times the steps,
+writes --dump-outputs if asked and prints the line. Every line carries the spread of the ranks' own time per step
+(`ms_per_step_min` / `_max`); where the kernels' times come from the timed steps themselves (HIP events inside the region), it
+also carries `roofline` and `allreduce_ms` (average device time of the statistics all-reduce, max over ranks; 0 on one GPU).
+
+    python bench.py ... --full                             everything else as well. Kernel times of steps too short for events
+        inside the timed region come from a replay of the same steps after it (`roofline`, `allreduce_ms`). With one GPU the
+        line carries `cpu_baseline` (full-covariance EM: also `cpu_baseline_all_cores`). At the default EM shape it carries
+        `secondary`, a list: K-means (BASELINE.json configs[4]) at one GPU's share of that job, N=12.5M, d=8, K=256, the
+        diagonal-covariance GMM of configs[1] (N=1M, d=16, K=16), the reference's own benchmark case configs[0] (bm_EM.cpp:
+        N=10k, d=4, K=3 -- latency-bound: three dependent launches per iteration), each with its own roofline and
+        cpu_baseline, and the whole bm_EM.cpp fit at N=10k next to its CPU time; with N > 1 GPUs, K-means at 12.5M rows per
+        GPU. --no-cpu-baseline and --no-secondary leave those parts out of a --full run.
 
     python bench.py --gpus N --single-process              the same line from ONE process: the library's device group
         (mlhip_ctx_create_group: the caller's one N x d block row-sharded inside the library, one host thread per shard, RCCL
@@ -310,12 +318,13 @@ class Job:
 
     def timed(self, run, steps, warmup, names=(), live=True, after=None):
         """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.
-        run(k) executes k steps. Returns (seconds, {kernel family: average ms per launch}).
+        run(k) executes k steps. Returns (seconds, {kernel family: average ms per launch}, or None if not measured).
         live: the kernels of the timed steps themselves carry HIP event pairs on the stream they are launched on; the
         pairs are only recorded inside the region and read after its closing barrier, so the region runs without any
         extra synchronisation (cost: a few microseconds per pair -- 0.1 % of an EM iteration, 0.5 % of a K-means step).
         not live (iterations of ~0.1 ms, where those microseconds would be 10 % of the metric): the region runs without
-        events and the same K steps are replayed with them right afterwards.
+        events; with --full (or --replay-events) the same K steps are replayed with them right afterwards, otherwise the
+        kernel times are not measured.
         after(): called once the timed region has closed, before any replay -- it sees the state of the last timed step."""
         if warmup:
             run(warmup)
@@ -330,19 +339,23 @@ class Job:
         elapsed = self.max_over_ranks(time.perf_counter() - t0)
         if after is not None:
             after()
-        if names and not live:
+        replay = bool(names) and not live and (self.args.full or self.args.replay_events)
+        if replay:
             self.ctx.timing_enable(True)
             run(steps)
-        names = list(names) + ["allreduce"]
-        kernel_ms = {name: self.ctx.timing_get(name)[0] for name in names}
+        kernel_ms = None
+        if live or replay:
+            kernel_ms = {name: self.ctx.timing_get(name)[0] for name in list(names) + ["allreduce"]}
         self.ctx.timing_enable(False)
         # diagnosability of a multi-GPU run: every rank's own time per step and its average all-reduce time (which, on a rank
         # that arrives early, includes the wait for the slowest one)
-        per_rank = self.gather({"ms_per_step": own / steps * 1e3, "allreduce_ms": kernel_ms["allreduce"]})
+        per_rank = self.gather({"ms_per_step": own / steps * 1e3,
+                                "allreduce_ms": None if kernel_ms is None else kernel_ms["allreduce"]})
         self.last_ranks = {"ms_per_step_min": min(r["ms_per_step"] for r in per_rank),
-                           "ms_per_step_max": max(r["ms_per_step"] for r in per_rank),
-                           "allreduce_ms": max(r["allreduce_ms"] for r in per_rank),
-                           "allreduce_ms_per_rank": [r["allreduce_ms"] for r in per_rank]}
+                           "ms_per_step_max": max(r["ms_per_step"] for r in per_rank)}
+        if kernel_ms is not None:
+            self.last_ranks.update(allreduce_ms=max(r["allreduce_ms"] for r in per_rank),
+                                   allreduce_ms_per_rank=[r["allreduce_ms"] for r in per_rank])
         return elapsed, kernel_ms
 
     def rows_per_unit(self, data, own_rows):
@@ -528,7 +541,6 @@ def em_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples, diagonal=Fals
     elapsed, ms = job.timed(run, steps, warmup, names, live=(elapsed_hint_ms(n, d, K, diagonal, job.units) >= 1.0), after=keep_last)
     if dump_dir and job.rank == 0:
         dump_outputs(dump_dir, last)
-    ms.setdefault("em_fused_wide", 0.0)
     n_locals = job.rows_per_unit(data, hi - lo)
     if job.rank != 0:
         data.close()
@@ -537,7 +549,9 @@ def em_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples, diagonal=Fals
     n_local = n_locals[0]
     headline = (n, d, K) == (N_TOTAL, DIM, COMPONENTS) and not diagonal
     it_tflops = (diag_flops if diagonal else algorithmic_flops)(n_local, d, K) / (elapsed / steps) / 1e12
-    if diagonal:
+    if ms is None:
+        roof = None                                             # no kernel times: not live, and no --full replay
+    elif diagonal:
         k_ms = ms["em_diag"]
         # N K (8d + 25) flops over N d 8 bytes (X once, fused) = 19 flop/B at d = K = 16, above the ridge (78.6 TFLOP/s /
         # 8 TB/s = 9.8): the BINDING roof is fp64 issue, the HBM fraction is reported beside it
@@ -547,7 +561,7 @@ def em_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples, diagonal=Fals
                 "frac": tfl / FP64_PEAK_TFLOPS, "traffic": None, "kernel_ms": {"em_diag": k_ms},
                 "hbm_algorithmic_gbs": gbs, "hbm_peak_gbs": HBM_PEAK_GBS, "hbm_frac": gbs / HBM_PEAK_GBS,
                 "iteration_algorithmic_tflops": it_tflops}
-    elif ms["em_fused_wide"] > 0:
+    elif ms.get("em_fused_wide", 0.0) > 0:
         k_ms = ms["em_fused_wide"]                              # E-step + statistics in one kernel: the whole iteration's flops
         achieved = algorithmic_flops(n_local, d, K) / (k_ms * 1e-3) / 1e12
         traffic, source = traffic_for("em_fused_wide", headline and job.units == 1)
@@ -601,8 +615,9 @@ def em_measure(job, n, d, K, steps, warmup, with_cpu, cpu_samples, diagonal=Fals
         "config": {"workload": f"GMM-EM N={n} d={d} K={K} {kind}, row-sharded over {job.units} GPU(s)",
                    "N": n, "d": d, "K": K, "parallelism": f"dp{job.units}", "final_mean_log_likelihood": state["ll"]},
         "rccl_ranks": job.rccl_ranks, "allreduce": job.allreduce, "n_local": n_locals, **job.layout(), **job.last_ranks,
-        "roofline": roof,
     }
+    if roof is not None:
+        out["roofline"] = roof
     data.close()
     if with_cpu:
         sec, n_cpu = cpu_baseline(mix, d, K, cpu_samples, CPU_ITERATIONS, diagonal)
@@ -680,8 +695,11 @@ def main():
                     help="total samples (default: the BASELINE.json configuration)")
     ap.add_argument("--dim", type=int, default=None)
     ap.add_argument("--components", type=int, default=None, help="mixture components / clusters")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the K-means `secondary` object of the N=1 EM line")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything the line can carry, not only its headline: CPU baselines, the `secondary` "
+                         "workloads, kernel times that take a replay of the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the `secondary` list of the default EM line")
     ap.add_argument("--cpu-samples", type=int, default=200_000)
     ap.add_argument("--allreduce", choices=("native", "torch", "gloo"), default="native",
                     help="native: ncclAllReduce on the library's own RCCL communicator; torch: torch.distributed nccl hook; "
@@ -753,7 +771,8 @@ def main():
         os.dup2(saved_stdout, 1)
         os.close(saved_stdout)
 
-    with_cpu = args.gpus == 1 and not args.no_cpu_baseline
+    with_cpu = args.full and args.gpus == 1 and not args.no_cpu_baseline
+    with_secondary = args.full and not args.no_secondary
     if args.workload == "kmeans":
         out = kmeans_measure(job, args.n or 100_000_000, args.dim or 8, args.components or 256, args.steps, args.warmup,
                              with_cpu, args.cpu_samples, dump_dir=args.dump_outputs)
@@ -764,7 +783,7 @@ def main():
         out = em_measure(job, args.n or N_TOTAL, args.dim or DIM, args.components or COMPONENTS, args.steps, args.warmup,
                          with_cpu, args.cpu_samples, dump_dir=args.dump_outputs)
         default_shape = (args.n, args.dim, args.components) == (None, None, None)
-        if args.gpus == 1 and default_shape and not args.no_secondary:
+        if args.gpus == 1 and default_shape and with_secondary:
             # In the same driver-timed run (the EM block has been freed above), as a LIST:
             # [0] BASELINE.json configs[4] (K-means N=100M, d=8, K=256 on 8 GPUs) at ONE GPU's share of it;
             # [1] BASELINE.json configs[1] (N=1M, d=16, K=16 diagonal-covariance GMM on one GPU) -- an iteration is ~0.1 ms, so
@@ -787,7 +806,7 @@ def main():
                 diag["config"]["workload"] += " = BASELINE.json configs[1]"
                 small["config"]["workload"] += " = BASELINE.json configs[0] (bm_EM.cpp)"
                 out["secondary"] = [sec, diag, small] + ([bm] if bm else [])
-        elif args.gpus > 1 and default_shape and not args.no_secondary:
+        elif args.gpus > 1 and default_shape and with_secondary:
             # multi-GPU runs: BASELINE.json configs[4] at 12.5M rows per GPU in the same driver-timed run -- N = 100M at 8 GPUs is
             # the configuration itself (weak scaling over the driver's 1 / 2 / 4 / 8 series: per-GPU work is fixed)
             sec = kmeans_measure(job, 12_500_000 * args.gpus, 8, 256, args.steps, args.warmup, False, args.cpu_samples)

@@ -24,8 +24,9 @@ def _bench(*args):
 
 
 def test_two_rank_em_line_matches_the_single_rank_run():
-    one = _bench("--samples", "400000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
-    two = _bench("--gpus", "2", "--allreduce", "gloo", "--n", "400000", "--steps", "3", "--warmup", "1")
+    # --full: at 400 000 rows an iteration is too short for events inside the timed region, the kernel times need the replay
+    one = _bench("--samples", "400000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full")
+    two = _bench("--gpus", "2", "--allreduce", "gloo", "--n", "400000", "--steps", "3", "--warmup", "1", "--full")
     # two ranks on the ONE GPU of this box: `n_gpus` counts physical GPUs, `units` the ranks; the line says it is a rehearsal
     assert two["n_gpus"] == 1 and two["units"] == 2 and "rehearsal" in two
     assert two["n_local"] == [200000, 200000] and two["steps"] == 3
@@ -55,7 +56,7 @@ def test_three_rank_kmeans_and_diag_lines():
 def test_dumped_outputs_are_the_last_timed_step(tmp_path, workload, n):
     """--dump-outputs writes what the primary workload's last timed step returned: warmup + steps iterations of mlhip_em_iterate
     from the benchmark's start, and the same bytes on a second run with the same arguments (em-diag: the kernel times come from a
-    replay of the steps after the timed region, which must not leak into the dump)."""
+    replay of the steps after the timed region in a --full run, which must not leak into the dump)."""
     import numpy as np
     from ml_amd import _lib, synth
     sys.path.insert(0, ROOT)
@@ -65,7 +66,7 @@ def test_dumped_outputs_are_the_last_timed_step(tmp_path, workload, n):
     for r in range(2):
         out = tmp_path / f"run{r}"
         line = _bench("--workload", workload, "--samples", str(n), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                      "--dump-outputs", str(out))
+                      "--full", "--dump-outputs", str(out))
         assert line["steps"] == 3 and line["ms_per_step"] > 0
         runs.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
     cov_name = "variances" if diagonal else "covariances"
@@ -87,3 +88,19 @@ def test_dumped_outputs_are_the_last_timed_step(tmp_path, workload, n):
     assert steps == 4 and abs(got["log_likelihood"][0] - ll) <= 1e-12 * abs(ll)
     for name, want in (("mixing", pi), ("means", mu), (cov_name, S)):
         assert np.max(np.abs(got[name] - want)) <= 1e-11 * np.max(np.abs(want)), name
+
+
+def test_a_plain_run_measures_the_headline_alone():
+    """Without --full the line is the headline's: no CPU baseline, and no kernel times where they would take a replay of their
+    own (400 000 rows: too short an iteration for events inside the timed region). --full adds them; the timed steps and what
+    they compute are the same either way."""
+    args = ("--samples", "400000", "--steps", "3", "--warmup", "1")
+    plain = _bench(*args)
+    full = _bench(*args, "--full", "--cpu-samples", "2000")
+    for key in ("cpu_baseline", "cpu_baseline_all_cores", "secondary", "roofline", "allreduce_ms"):
+        assert key not in plain, key
+    assert full["cpu_baseline"]["value"] > 0 and full["roofline"]["kernel_ms"]["em_estep"] > 0 and full["allreduce_ms"] == 0
+    for key in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus"):
+        assert plain[key] == full[key], key
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["config"]["final_mean_log_likelihood"] == full["config"]["final_mean_log_likelihood"]

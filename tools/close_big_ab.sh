@@ -7,7 +7,7 @@ O=$R/gpurun_out/close_big_ab.txt
 for cfg in "1000000 128 32" "1000000 72 32" "100000 256 8" "100000 512 4" "50000 1024 4"; do
   set -- $cfg
   for dc in 0 1; do
-    MLHIP_DEVICE_CLOSE=$dc python3 "$R/bench.py" --samples $1 --dim $2 --components $3 --steps 10 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | python3 -c "
+    MLHIP_DEVICE_CLOSE=$dc python3 "$R/bench.py" --samples $1 --dim $2 --components $3 --steps 10 --warmup 2 --full --no-cpu-baseline --no-secondary 2>/dev/null | python3 -c "
 import json,sys
 b=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=b['roofline']
 print('N=$1 d=$2 K=$3 MLHIP_DEVICE_CLOSE=$dc: ms/it %.3f'%b['ms_per_step'], {k:round(v,3) for k,v in r['kernel_ms'].items()}, 'frac %.3f'%r['frac'], 'll', b['config'].get('final_mean_log_likelihood'))" >> "$O"

@@ -5,7 +5,7 @@ OLD=$1; shift
 for cfg in "$@"; do
     set -- $cfg
     for lib in "$OLD" "" "$OLD" ""; do
-        MLHIP_LIBRARY=$lib python3 "$R/bench.py" --samples $1 --dim $2 --components $3 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null |
+        MLHIP_LIBRARY=$lib python3 "$R/bench.py" --samples $1 --dim $2 --components $3 --steps 20 --warmup 3 --full --no-cpu-baseline --no-secondary 2>/dev/null |
             python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())

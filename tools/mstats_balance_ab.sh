@@ -7,7 +7,7 @@ O=$R/gpurun_out/${TAG}_mstats_balance.txt
 for cfg in "5000000 16 64" "5000000 12 64" "5000000 16 32" "5000000 16 48" "5000000 12 48"; do
     set -- $cfg
     for b in 0 1; do
-        MLHIP_MSTATS_BALANCED=$b python3 "$R/bench.py" --samples $1 --dim $2 --components $3 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary 2>/dev/null |
+        MLHIP_MSTATS_BALANCED=$b python3 "$R/bench.py" --samples $1 --dim $2 --components $3 --steps 20 --warmup 3 --full --no-cpu-baseline --no-secondary 2>/dev/null |
             python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
