@@ -455,17 +455,11 @@ __global__ __launch_bounds__(256) void kmeans_assign_big_kernel(const double* __
     }
 }
 
-bool big_dim_enabled()
-{
-    const char* e = std::getenv("MLHIP_BIG_DIM");
-    return !(e && e[0] == '0');
-}
-
 }  // namespace
 
-bool big_dim_applies(int d) { return d > kMaxDim && d <= kBigMaxDim && big_dim_enabled(); }
+bool big_dim_applies(int d) { return d > kMaxDim && d <= kBigMaxDim; }
 /// The K-means assignment kernel of this file has no upper limit on d (no tile in LDS).
-bool big_dim_kmeans_applies(int d) { return d > kMaxDim && big_dim_enabled(); }
+bool big_dim_kmeans_applies(int d) { return d > kMaxDim; }
 
 constexpr int kMaxSplits = 64;      // (32 until late in round 5: 12 units x 32 = 384 workgroups on 512 slots at d = 192, K = 8)
 /// Sample ranges a statistics tile is cut into (= partial blocks written), at most kMaxSplits: the count whose workgroups fill whole rounds of

@@ -70,6 +70,7 @@ struct EstepArgs {
     int with_lse;                                           // 0: write lw only (the statistics kernel normalises)
     int num_cus;                                            // compute units of the context's device (0: ask the current device)
     double* scratch; size_t scratch_doubles;                // a block free for the launch (the statistics partials): the big tier's q parts
+    int plain;                                              // d > kMaxDim: 1 = the plain tier even where big_dim.hip applies
 };
 /// Returns the grid size used (= number of ll partials written), or <0 if D is not instantiated.
 int launch_em_estep(const EstepArgs& a, hipStream_t stream);
@@ -94,9 +95,11 @@ struct MstatsArgs {
     double* ll_scratch;                                      // kFromLogRespSelfNorm: >= 1024 doubles for the ll partials
     double* lse_out; double* ll_out;                         // kFromLogRespSelfNorm: per-sample max (-> lse) and exp-sum (n_pad each)
     unsigned long long* nz_count;                            // kFromLogRespSelfNorm (may be null): += nonzero responsibilities
+    int plain;                                               // 1: the plain forms -- d <= kRegDim: whole column blocks per wave (no
+                                                             // balanced dealing); d > kMaxDim: the plain tier even where big_dim.hip applies
 };
 int launch_em_mstats_generic(const MstatsArgs& a, hipStream_t stream);   // d > kMaxDim: writes ONE partial block [K][F]
-/// 128 < d <= 1024 on the matrix cores (big_dim.hip); the plain tier above it and with MLHIP_BIG_DIM=0.
+/// 128 < d <= 1024 on the matrix cores (big_dim.hip); the plain tier above it (and where the caller asks for it: Args::plain).
 bool big_dim_applies(int d);
 bool big_dim_kmeans_applies(int d);                                       // (its K-means kernel: any d > 128)
 int big_dim_splits(int d, int K, int num_cus);
@@ -116,13 +119,25 @@ struct FusedArgs {
     double* lse;                                             // out: per-sample log-sum-exp
     double* partials; size_t partials_capacity;              // scratch: [grid][KP][FP]
     double* ll_partials; int n_ll_partials;                  // out: per-workgroup log-likelihood sums (grid of them)
+    int form;                                                // FusedForm
+};
+enum FusedForm : int {
+    kFusedLdsFeed = 0,                                       // matrix-core form, records fed from LDS
+    kFusedScalarFeed = 1,                                    // matrix-core form, records fed from scalar registers
+    kFusedValu = 2,                                          // vector-unit form (one instantiation per (d, K))
 };
 namespace mstats {
 bool em_fused_supported(int d, int K);
+/// Tuning rules of the fused kernel's forms (em_fused_small.hip), functions of the shape alone: where the vector-unit form is
+/// built and where it is the faster one; where the matrix-core form can take its records from LDS and where scalar registers win.
+bool em_fused_valu_supported(int d, int K);
+bool em_fused_valu_preferred(int d, int K, uint32_t n);
+bool em_fused_lds_feed_supported(int d);
+bool em_fused_scalar_feed(int d, uint32_t n);
 int em_fused_partial_rows(int K);
 int em_fused_partial_cols(int d);
 int launch_em_fused_small(const FusedArgs& a, int num_cus, hipStream_t stream);
-/// The grid launch_em_fused_small would use for these arguments if the shape takes the vector-unit form with at most one
+/// The grid launch_em_fused_small would use for these arguments if they ask for the vector-unit form and it runs with at most one
 /// workgroup per CU; 0 otherwise.
 int em_fused_valu_small_grid(const FusedArgs& a, int num_cus);
 }
@@ -165,6 +180,7 @@ struct DiagArgs {
     int two_op;                                              // the records' (a, b) operands were built for THIS shift (the data's): the
                                                              // mixed-feed kernel may take its two-operation density form; 0 for a
                                                              // refinement pass about another shift (exact form)
+    int exact;                                               // 1: the exact density form always
 };
 namespace mstats {
 bool em_diag_supported(int d, int K);                        // d <= 32, K <= 64
@@ -229,8 +245,18 @@ struct KmeansArgs {
     double* partials; size_t partials_capacity;
     double* cnorm;                             // device scratch, K rounded up to 16 doubles: -|c_k|^2/2 (chunked-table kernel)
     double* out;                               // device: [inertia, n_changed, counts(K), sums(K*d)]
+    int kernel;                                // KmKernel: which assignment kernel runs
+};
+enum KmKernel : int {
+    kKmDirect = 0,                             // direct form (kmeans.hip), d <= kMaxDim
+    kKmMatrix = 1,                             // matrix-core search with exact recheck (kmeans_mfma.hip)
+    kKmBigDim = 2,                             // d > kMaxDim, register-blocked (big_dim.hip)
+    kKmPlain = 3,                              // d > kMaxDim, plain (generic_dim.hip)
 };
 size_t kmeans_scratch_doubles(int d, int K, int num_cus);
+bool kmeans_mfma_supported(int D, int K);
+/// Tuning rule: few clusters on many samples, where the direct-form kernel beats the matrix-core search (kmeans.hip).
+bool kmeans_few_clusters(int D, int K, uint32_t n);
 /// The whole step loop of KMeans::fit_once in one launch of one workgroup (kmeans_resident.hip): small blocks, few clusters, the
 /// dimensions whose step runs on the direct-form kernel. `out` is host-visible pinned memory:
 /// [steps, converged, inertia, label buffer, counts(K), centroids(K d), old centroids(K d)].

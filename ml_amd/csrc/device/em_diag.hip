@@ -583,12 +583,8 @@ __global__ __launch_bounds__(256, 2) void em_diag_mixed_kernel(
 
 constexpr int rbw_of(int RBT) { return RBT >= 2 ? 2 : 1; }
 
-/// MLHIP_DIAG_AB=0: the exact form of the density loop always (A/B runs).
-inline double diag_ab_limit()
-{
-    const char* e = std::getenv("MLHIP_DIAG_AB");          // (read per launch: tests switch it inside one process)
-    return e && e[0] == '0' ? -1.0 : kDiagAbLimit;
-}
+/// Bound of the two-operation density form; a.exact: the exact form always.
+inline double ab_limit(const DiagArgs& a) { return a.exact ? -1.0 : kDiagAbLimit; }
 
 /// Samples per lane: 2 while coordinates + densities of both fit the registers of 2 waves per SIMD, else 1.
 constexpr int samples_per_lane(int D, int RBT) { return (D <= 16 && RBT == 1) || (D <= 8 && RBT == 2) ? 2 : 1; }
@@ -601,13 +597,13 @@ int launch_t(const DiagArgs& a, int grid, hipStream_t stream)
         const size_t smem = sizeof(double) * (4 * ((size_t)TS * XSS + (size_t)TS * RSS) + (size_t)32 * D);
         hipLaunchKernelGGL((em_diag_mixed_kernel<D, CB, S>), dim3(grid), dim3(256), smem, stream, a.xt, a.ldx, a.n, a.d, a.shift,
                            a.params, a.K, a.lse, a.partials, em_diag_partial_rows(a.K), em_diag_partial_cols(a.d), a.ll_partials,
-                           (a.two_op && diag_ab_limit() > 0) ? 1 : 0);
+                           (a.two_op && ab_limit(a) > 0) ? 1 : 0);
         return grid;
     } else {
         const size_t smem = sizeof(double) * (4 * ((size_t)TS * XSS + (size_t)TS * RSS) + (size_t)16 * RBT * PS);
         hipLaunchKernelGGL((em_diag_kernel<D, RBT, RBW, CB, S>), dim3(grid, RBT / RBW), dim3(256), smem, stream, a.xt, a.ldx, a.n, a.d,
                            a.shift, a.params, a.K, a.lse, a.partials, em_diag_partial_rows(a.K), em_diag_partial_cols(a.d),
-                           a.ll_partials, diag_ab_limit());
+                           a.ll_partials, ab_limit(a));
         return grid;
     }
 }

@@ -115,7 +115,7 @@ int launch_em_estep(const EstepArgs& a, hipStream_t stream)
     case 32: return launch_t<32>(a, stream);
     default:
         if (a.D <= kMaxDim) return -1;
-        if (big_dim_applies(a.D)) {
+        if (!a.plain && big_dim_applies(a.D)) {
             int cus = a.num_cus;                              // (per context: a device group may span different devices -- ADVICE r4)
             if (cus < 1) {
                 int dev = 0;

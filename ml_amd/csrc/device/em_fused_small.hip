@@ -268,24 +268,11 @@ int launch_t(const FusedArgs& a, int grid, hipStream_t stream)
     return grid;
 }
 
-/// Which feed the density loop takes its records from (tools/sfeed_sweep.sh, profiles/r04_fused_feed.txt). Scalar registers: d = 7, 8
-/// always (no LDS-fed form is built there); d >= 3 from 2^19 samples on (N = 8.4M: d = 6, K = 32 1.32 -> 1.04 ms, d = 4, K = 16
-/// 0.416 -> 0.371 ms, d = 3, K = 16 0.346 -> 0.336 ms; below, with one or two tiles per wave, the scalar-load latency of every
-/// record row is exposed: 1 - 6 us slower) ; d = 1, 2: LDS (0.97 against 1.04 ms at d = 1, K = 64). MLHIP_FUSED_SFEED=0 / 1 forces
-/// one feed for d <= 6 (A/B runs).
-template <int D> bool scalar_feed(uint32_t n)
-{
-    if constexpr (D >= 8) return true;
-    const char* e = std::getenv("MLHIP_FUSED_SFEED");
-    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
-    return D >= 3 && n >= (1u << 19);
-}
-
 template <int D, int CB>
 int launch_d(const FusedArgs& a, int grid, hipStream_t stream)
 {
     const int RB = (a.K + 15) / 16;
-    if (scalar_feed<D>(a.n)) {
+    if (a.form == kFusedScalarFeed) {
         if (RB == 1) return launch_t<D, 1, CB, true>(a, grid, stream);
         if (RB == 2) return launch_t<D, 2, CB, true>(a, grid, stream);
         if constexpr (CB == 1) { if (RB <= 4) return launch_t<D, 4, CB, true>(a, grid, stream); }
@@ -342,21 +329,6 @@ template <int D> int launch_valu(const FusedArgs& a, int num_cus, hipStream_t st
     return grid;                                                     // straight-line code, the records sit in scalar registers
 }
 
-/// Shapes that take the vector-unit form (tools/small_shape_sweep.sh, tools/small_shape_ab.sh; profiles/r04_small_shapes.txt):
-/// K F <= 64 accumulators -- at every sample count (d = 2, K = 3: 15.0 against 17.7 us per iteration at N = 16 384, 52 against
-/// 104 us at N = 4 194 304; never slower); up to valu_max_k (K F ~ 100: one or two waves per SIMD, a longer epilogue) from 2^20
-/// samples on, where it still wins by 6 - 36 % (below that the matrix-core form is up to 4 us faster).
-/// MLHIP_FUSED_VALU=0: the matrix-core form instead; =2: the vector-unit form at every N for all shapes it is built for (A/B runs,
-/// tests; read per call).
-[[maybe_unused]] bool valu_form_applies(const FusedArgs& a)
-{
-    const char* e = std::getenv("MLHIP_FUSED_VALU");
-    if (e && e[0] == '0') return false;
-    const int D = padded_dim(a.d);
-    if (D != a.d || D > 6 || a.K > valu_max_k(D)) return false;
-    return a.K * stats_count(a.d) <= 64 || a.n >= (1u << 20) || (e && e[0] == '2');     // (2: every shape it is built for -- tests)
-}
-
 }  // namespace
 
 #if MLHIP_PART == 1
@@ -371,6 +343,29 @@ bool em_fused_supported(int d, int K)
 
 int em_fused_partial_rows(int K) { const int RB = (K + 15) / 16; return (RB == 1 ? 1 : RB == 2 ? 2 : 4) * 16; }
 int em_fused_partial_cols(int d) { return ((stats_count(d) + 15) / 16) * 16; }
+
+/// The vector-unit form is instantiated for d = 1 .. 4, 6 with K <= valu_max_k(d).
+bool em_fused_valu_supported(int d, int K)
+{
+    const int D = padded_dim(d);
+    return D == d && D <= 6 && K <= valu_max_k(D);
+}
+
+/// Shapes where the vector-unit form is the faster one (tools/small_shape_sweep.sh, tools/small_shape_ab.sh;
+/// profiles/r04_small_shapes.txt): K F <= 64 accumulators -- at every sample count (d = 2, K = 3: 15.0 against 17.7 us per
+/// iteration at N = 16 384, 52 against 104 us at N = 4 194 304; never slower); up to valu_max_k (K F ~ 100: one or two waves per
+/// SIMD, a longer epilogue) from 2^20 samples on, where it still wins by 6 - 36 % (below that the matrix-core form is up to 4 us
+/// faster).
+bool em_fused_valu_preferred(int d, int K, uint32_t n) { return K * stats_count(d) <= 64 || n >= (1u << 20); }
+
+/// d = 7, 8: the matrix-core form takes its records from scalar registers only (no LDS-fed form is built there).
+bool em_fused_lds_feed_supported(int d) { return padded_dim(d) < 8; }
+
+/// Which feed the matrix-core form's density loop is faster with (tools/sfeed_sweep.sh, profiles/r04_fused_feed.txt). Scalar
+/// registers: d = 7, 8 always; d >= 3 from 2^19 samples on (N = 8.4M: d = 6, K = 32 1.32 -> 1.04 ms, d = 4, K = 16 0.416 -> 0.371
+/// ms, d = 3, K = 16 0.346 -> 0.336 ms; below, with one or two tiles per wave, the scalar-load latency of every record row is
+/// exposed: 1 - 6 us slower) ; d = 1, 2: LDS (0.97 against 1.04 ms at d = 1, K = 64).
+bool em_fused_scalar_feed(int d, uint32_t n) { return !em_fused_lds_feed_supported(d) || (padded_dim(d) >= 3 && n >= (1u << 19)); }
 #endif
 
 // ---- compiled in six parts by padded dimension (parts.hpp): part 1 .. 6 = D 1, 2, 3, 4, 6, 8
@@ -381,8 +376,11 @@ int MLHIP_PART_FN(launch_em_fused_small)(const FusedArgs& a, int num_cus, hipStr
 {
     constexpr int D = kPartDim, CB = D <= 4 ? 1 : (D == 6 ? 2 : 3);
     if (padded_dim(a.d) != D) return -1;
-    if constexpr (valu_max_k(D) > 0) {
-        if (valu_form_applies(a)) return launch_valu<D>(a, num_cus, stream);
+    if (a.form == kFusedValu) {
+        if constexpr (valu_max_k(D) > 0) {
+            if (em_fused_valu_supported(a.d, a.K)) return launch_valu<D>(a, num_cus, stream);
+        }
+        return -1;
     }
     const uint32_t n_tiles = (a.n + TS - 1) / TS;
     const int RB = (a.K + 15) / 16;
@@ -404,11 +402,11 @@ int launch_em_fused_small_part5(const FusedArgs&, int, hipStream_t);
 int launch_em_fused_small_part6(const FusedArgs&, int, hipStream_t);
 
 /// The grid the vector-unit form would be launched with for these arguments when that is at most one workgroup per CU (no
-/// register cut applies then); 0 when the shape takes another form or a larger grid. What the device-resident loop
+/// register cut applies then); 0 when the arguments ask for another form or the grid is larger. What the device-resident loop
 /// (em_resident.hip) needs to reproduce the partial blocks of this kernel.
 int em_fused_valu_small_grid(const FusedArgs& a, int num_cus)
 {
-    if (!em_fused_supported(a.d, a.K) || !valu_form_applies(a)) return 0;
+    if (a.form != kFusedValu || !em_fused_supported(a.d, a.K) || !em_fused_valu_supported(a.d, a.K)) return 0;
     const int grid = valu_grid_uncut(a, num_cus);
     return grid >= 1 && grid <= num_cus ? grid : 0;
 }

@@ -188,7 +188,7 @@ size_t em_mstats_scratch_doubles(int d, int K, int num_cus)
 
 int launch_em_mstats(const MstatsArgs& a, int num_cus, hipStream_t stream)
 {
-    if (a.d > kMaxDim) return big_dim_applies(a.d) ? launch_em_mstats_big(a, num_cus, stream) : launch_em_mstats_generic(a, stream);
+    if (a.d > kMaxDim) return !a.plain && big_dim_applies(a.d) ? launch_em_mstats_big(a, num_cus, stream) : launch_em_mstats_generic(a, stream);
     const Plan p = make_plan(a.d, a.K, num_cus);
     const uint32_t n_tiles = (a.n + TS - 1) / TS;
     int grid_x = p.grid_x;

@@ -353,9 +353,8 @@ int MLHIP_PART_FN(launch_wide)(const MstatsArgs& a, const Plan& p, int grid_x, h
     return grid_x;
 #else
     // balanced dealing of (column block, row block) units where whole column blocks leave the waves unevenly loaded
-    // (MLHIP_MSTATS_BALANCED=0: off)
-    static const bool balanced = [] { const char* e = std::getenv("MLHIP_MSTATS_BALANCED"); return !(e && e[0] == '0'); }();
-    if (balanced && p.n_rbg == 1 && p.n_cbg == 1) {
+    // (a.plain: off)
+    if (!a.plain && p.n_rbg == 1 && p.n_cbg == 1) {
         if constexpr (R == 4) {
             if (p.CB == 6) { launch_t<4, 1, kRegDim, 6>(a, p, grid_x, stream); return grid_x; }      // d = 12
             if (p.CB == 10) { launch_t<4, 2, kRegDim, 10>(a, p, grid_x, stream); return grid_x; }    // d = 16

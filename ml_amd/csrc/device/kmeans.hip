@@ -310,28 +310,26 @@ void launch_kmeans_update(const KmeansArgs& a, int grid, size_t pstride, hipStre
                        a.n, a.d, a.labels, a.scale, a.K, KC, DC, a.partials, pstride);
 }
 
-bool kmeans_mfma_supported(int D, int K);
 int launch_kmeans_mfma(const KmeansArgs& a, int num_cus, hipStream_t stream);
+
+/// Few clusters (K <= 16, d <= 32): the direct-form kernel of this file is the faster one -- the matrix-core search (kmeans_mfma.hip)
+/// pads K to 16 rows and pays its exact recheck per sample whatever K is (round 4, N = 10M: d = 4, K = 8 0.230 -> 0.155 ms, K = 16
+/// 0.212 -> 0.164; d = 8, K = 16 0.318 -> 0.276; d = 16, K = 8 0.595 -> 0.515; d = 32, K = 16 0.486 -> 0.474; K = 32: the matrix
+/// cores win again). Labels and distances are the same bits either way.
+/// From 2^21 samples on: below, this kernel's 1024-thread workgroups (zeroing and flushing their LDS accumulators) are the
+/// slower ones (N = 20k, d = 32, K = 4: 69 against 52 us per step; N = 1M, d = 16, K = 16: 87 against 83).
+bool kmeans_few_clusters(int D, int K, uint32_t n)
+{
+    return K <= (D <= 8 ? 24 : 16) && D <= kRegDim && n >= (1u << 21);   // (K = 24: d = 4 -14 %, d = 8 -7 %)
+}
 
 int launch_kmeans_assign(const KmeansArgs& a_in, int num_cus, hipStream_t stream)
 {
-    // Matrix-core search with exact recheck (kmeans_mfma.hip) where it applies; MLHIP_KMEANS=valu forces this file's kernel,
-    // MLHIP_KMEANS=mfma the matrix-core one wherever it exists.
-    const char* e = std::getenv("MLHIP_KMEANS");
-    const bool force_valu = e && e[0] == 'v', force_mfma = e && e[0] == 'm';
-    // Few clusters (K <= 16, d <= 32): the direct-form kernel of this file -- the matrix-core search pads K to 16 rows and pays its
-    // exact recheck per sample whatever K is (round 4, N = 10M: d = 4, K = 8 0.230 -> 0.155 ms, K = 16 0.212 -> 0.164; d = 8, K = 16
-    // 0.318 -> 0.276; d = 16, K = 8 0.595 -> 0.515; d = 32, K = 16 0.486 -> 0.474; K = 32: the matrix cores win again). Labels and
-    // distances are the same bits either way.
-    // From 2^21 samples on: below, this kernel's 1024-thread workgroups (zeroing and flushing their LDS accumulators) are the
-    // slower ones (N = 20k, d = 32, K = 4: 69 against 52 us per step; N = 1M, d = 16, K = 16: 87 against 83).
-    const bool few = a_in.K <= (a_in.D <= 8 ? 24 : 16) && a_in.D <= kRegDim && a_in.n >= (1u << 21) && !force_mfma;   // (K = 24: d = 4 -14 %, d = 8 -7 %)
-    // (above d = 64 only the matrix-core kernel exists)
-    if ((!(force_valu || few) || a_in.D > kMidDim) && kmeans_mfma_supported(a_in.D, a_in.K)) return launch_kmeans_mfma(a_in, num_cus, stream);
+    if (a_in.kernel == kKmMatrix) return kmeans_mfma_supported(a_in.D, a_in.K) ? launch_kmeans_mfma(a_in, num_cus, stream) : -1;
     const size_t pstride = 2 + (size_t)a_in.K * (3 * a_in.d + 1);
     if (a_in.D > kMaxDim) {
         // big_dim.hip (register-blocked) or generic_dim.hip (plain): exact assignment, update sums by the separate sweep
-        if (big_dim_kmeans_applies(a_in.D) && (size_t)kmeans_grid(num_cus) * pstride <= a_in.partials_capacity) {
+        if (a_in.kernel == kKmBigDim && big_dim_kmeans_applies(a_in.D) && (size_t)kmeans_grid(num_cus) * pstride <= a_in.partials_capacity) {
             const int used = launch_kmeans_assign_big(a_in, kmeans_grid(num_cus), pstride, stream);
             if (used > 0) {
                 if (a_in.accumulate) launch_kmeans_update(a_in, used, pstride, stream);

@@ -233,7 +233,7 @@ int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, doub
         ensure_em_workspace(data, 1);
         data->have_estep = false;
         launch_fill_responsibilities(nullptr, data->n, 1, data->lw.as<double>(), data->ldr, ctx->stream);
-        run_mstats(data, 1, kFromResp, data->lw.as<double>(), data->ldr, false);
+        run_mstats(data, em_route(data, 1, false), 1, kFromResp, data->lw.as<double>(), data->ldr, false);
         const double* s = data->stats_host.as<double>();
         const int d = data->d;
         const double n = (double)data->n_global;
@@ -265,7 +265,7 @@ int mlhip_xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt,
         HIP_CHECK(hipMemsetAsync(w + data->ldr, 0, sizeof(double) * data->ldr, ctx->stream));
         if (data->n)
             HIP_CHECK(hipMemcpyAsync(w + data->ldr, y, sizeof(double) * data->n, hipMemcpyHostToDevice, ctx->stream));
-        run_mstats(data, 2, kFromResp, w, data->ldr, false);
+        run_mstats(data, em_route(data, 2, false), 2, kFromResp, w, data->ldr, false);
         const int d = data->d, F = stats_count(d);
         const double* s0 = data->stats_host.as<double>();
         const double* s1 = s0 + F;

@@ -26,8 +26,8 @@ void ensure_em_workspace(mlhip_data* dt, int K)
 }
 
 
-/// Builds the per-component records for the E-step kernel that fits (d, env) and uploads them to params_dev.
-void prepare_estep(mlhip_data* dt, int K, const double* mixing, const double* means, const double* covs, DevBuf* target)
+/// Builds the per-component records for the route's E-step kernel and uploads them to params_dev.
+void prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs, DevBuf* target)
 {
     mlhip_ctx* ctx = dt->ctx;
     ensure_em_workspace(dt, K);
@@ -38,24 +38,13 @@ void prepare_estep(mlhip_data* dt, int K, const double* mixing, const double* me
         target->reserve(ps);
         dt->params_host.reserve(ps);
     }
-    // d in 12..128: 4x4-block triangular matrix-core kernel (mfma4). For d <= 32, MLHIP_ESTEP=valu selects the scalar-fed
-    // VALU kernel (the only one below d = 12), for A/B runs.
-    bool use_mfma4 = estep_mfma4_supported(dt->D);
-    if (dt->D <= kRegDim) {
-        const char* e = std::getenv("MLHIP_ESTEP");
-        if (e && std::strcmp(e, "valu") == 0) use_mfma4 = false;
-    }
+    // d in 12..128: 4x4-block triangular matrix-core kernel (mfma4); below, and where the route asks for it, the scalar-fed one.
+    const bool use_mfma4 = r.estep == Estep::kMatrix4;
     dt->estep_fold = false;
     // d > 64: the K factorizations on the device (em_close_big.hip launch_em_records_big -- the closing arithmetic's kernels, started
     // from the given covariances; the host's operations in the host's order, so the records are the host builders' except through
-    // log()). On the host they were 60 ms at d = 1024, K = 4 -- once per fit, but a short fit is a few iterations. MLHIP_DEVICE_CLOSE=0
-    // (or MLHIP_DEVICE_RECORDS=0 for this step alone): the host builders.
-    const bool records_on_device = [] {                  // (read per call: tests switch it; MLHIP_DEVICE_RECORDS=0/1 decides for the records alone)
-        const char* r = std::getenv("MLHIP_DEVICE_RECORDS");
-        const char* e = r && *r ? r : std::getenv("MLHIP_DEVICE_CLOSE");
-        return !(e && e[0] == '0');
-    }();
-    if (records_on_device && em_close_big_supported(dt->d)) {
+    // log()). On the host they were 60 ms at d = 1024, K = 4 -- once per fit, but a short fit is a few iterations.
+    if (r.records_on_device) {
         const int d = dt->d;
         const size_t n_par = (size_t)K * ((size_t)d * d + d + 1);
         dt->close_work.reserve(sizeof(double) * em_close_work_doubles(d, K));
@@ -76,10 +65,8 @@ void prepare_estep(mlhip_data* dt, int K, const double* mixing, const double* me
         ctx->sync();                                     // (the caller's arrays may change once this returns)
     } else if (use_mfma4) {
         // FOLD form (no per-component mean subtraction in the kernel) while every |W_k (mu_k - shift)| is small enough for
-        // the parity tolerances; the exact form otherwise. Every rank decides from the same parameters. MLHIP_ESTEP_FOLD=0: off.
-        static const bool fold_allowed = [] { const char* e = std::getenv("MLHIP_ESTEP_FOLD"); return !(e && e[0] == '0'); }();
-        const bool try_fold = fold_allowed && dt->D <= kRegDim;
-        dt->estep_fold = host::build_estep_params_mfma4(dt->d, dt->D, K, mixing, means, covs, try_fold ? dt->shift.data() : nullptr,
+        // the parity tolerances; the exact form otherwise. Every rank decides from the same parameters.
+        dt->estep_fold = host::build_estep_params_mfma4(dt->d, dt->D, K, mixing, means, covs, r.fold_allowed ? dt->shift.data() : nullptr,
                                                         kEstepFoldLimit, dt->params_host.as<double>());
         HIP_CHECK(hipMemcpyAsync(target->p, dt->params_host.p, sizeof(double) * estep_mfma4_param_stride(dt->D) * K,
                                  hipMemcpyHostToDevice, ctx->stream));
@@ -94,7 +81,7 @@ void prepare_estep(mlhip_data* dt, int K, const double* mixing, const double* me
 
 /// E-step kernel on the records in params_dev: fills lw and -- unless the statistics kernel is going to normalise the
 /// log-responsibilities itself (`with_lse` false, matrix-core kernel only) -- lse and the log-likelihood partials.
-void launch_estep(mlhip_data* dt, int K, bool with_lse, const DevBuf* records, int fold)
+void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const DevBuf* records, int fold)
 {
     mlhip_ctx* ctx = dt->ctx;
     EstepArgs a{};
@@ -106,6 +93,7 @@ void launch_estep(mlhip_data* dt, int K, bool with_lse, const DevBuf* records, i
     a.with_lse = (with_lse || dt->estep_variant != 2) ? 1 : 0;
     a.num_cus = ctx->num_cus;
     a.scratch = dt->partials.as<double>(); a.scratch_doubles = dt->partials.bytes / sizeof(double);   // (written by the statistics kernel AFTER the E-step, on the same stream)
+    a.plain = r.estep == Estep::kPlain;
     int grid = 0;
     ctx->timed("em_estep", [&] {
         grid = dt->estep_variant == 2 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
@@ -118,17 +106,17 @@ void launch_estep(mlhip_data* dt, int K, bool with_lse, const DevBuf* records, i
 }
 
 
-void run_estep(mlhip_data* dt, int K, const double* mixing, const double* means, const double* covs, bool with_lse)
+void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs, bool with_lse)
 {
     dt->diag_step = false;
-    prepare_estep(dt, K, mixing, means, covs);
-    launch_estep(dt, K, with_lse);
+    prepare_estep(dt, r, K, mixing, means, covs);
+    launch_estep(dt, r, K, with_lse);
 }
 
 
 /// After a fused step only lse exists on the device; whoever needs the log-responsibility block (labels,
 /// responsibilities, a separate M-step, the refinement pass) gets it rebuilt from the same parameter records.
-void ensure_lw(mlhip_data* dt, int K)
+void ensure_lw(mlhip_data* dt, const EmRoute& r, int K)
 {
     if (!dt->have_estep || dt->lw_valid) return;
     if (dt->diag_step) {
@@ -137,10 +125,10 @@ void ensure_lw(mlhip_data* dt, int K)
         std::vector<double> covs((size_t)K * d * d, 0.0);
         for (int k = 0; k < K; ++k)
             for (int j = 0; j < d; ++j) covs[(size_t)k * d * d + (size_t)j * d + j] = dt->diag_vars[(size_t)k * d + j];
-        prepare_estep(dt, K, dt->diag_mixing.data(), dt->diag_means.data(), covs.data());
+        prepare_estep(dt, r, K, dt->diag_mixing.data(), dt->diag_means.data(), covs.data());
         dt->diag_step = false;
     }
-    launch_estep(dt, K);
+    launch_estep(dt, r, K);
 }
 
 
@@ -161,18 +149,9 @@ void collect_stats(mlhip_data* dt, int K, size_t count)
 }
 
 
-/// One EM iteration's device work in a single kernel where the shape allows (d <= 8, K <= 32 or d <= 4, K <= 64: em_fused_small.hip): no
-/// N x K block in HBM. MLHIP_FUSED=0 keeps the two-kernel path. Returns false when the shape is not covered.
-bool fused_step_applies(const mlhip_data* dt, int K)
-{
-    const char* env = std::getenv("MLHIP_FUSED");
-    return !(env && env[0] == '0') && mstats::em_fused_supported(dt->d, K);
-}
-
-
 /// The fused kernel + reduction on the records already in params_dev; statistics end in stats_dev (and, with `collect`, all-
 /// reduced in stats_host).
-void launch_fused_step(mlhip_data* dt, int K, bool collect, const DevBuf* records)
+void launch_fused_step(mlhip_data* dt, const EmRoute& r, int K, bool collect, const DevBuf* records)
 {
     mlhip_ctx* ctx = dt->ctx;
     FusedArgs a{};
@@ -181,6 +160,7 @@ void launch_fused_step(mlhip_data* dt, int K, bool collect, const DevBuf* record
     a.lse = dt->lse.as<double>();
     a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
     a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
+    a.form = r.fused_form;
     int grid = 0;
     ctx->timed("em_fused", [&] { grid = mstats::launch_em_fused_small(a, ctx->num_cus, ctx->stream); });
     if (grid <= 0) throw std::runtime_error("fused EM kernel launch failed");
@@ -197,20 +177,19 @@ void launch_fused_step(mlhip_data* dt, int K, bool collect, const DevBuf* record
 }
 
 
-bool run_fused_step(mlhip_data* dt, int K, const double* mixing, const double* means, const double* covs)
+bool run_fused_step(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs)
 {
-    if (!fused_step_applies(dt, K)) return false;
+    if (!r.fused) return false;
     dt->diag_step = false;
-    prepare_estep(dt, K, mixing, means, covs);
-    if (dt->estep_variant != 0) return false;            // (cannot happen for d <= 8; the fused kernel reads VALU records)
-    launch_fused_step(dt, K, true);
+    prepare_estep(dt, r, K, mixing, means, covs);
+    launch_fused_step(dt, r, K, true);
     return true;
 }
 
 
 /// Runs the statistics kernel on log-responsibilities (mode kFromLogResp: the E-step's lw/lse) or on plain
 /// responsibilities `resp_dev` ([K][ld_resp], ld_resp >= n_pad), all-reduces, leaves [K*F stats, ll_sum] in stats_host.
-void run_mstats(mlhip_data* dt, int K, int mode, const double* resp_dev, size_t ld_resp, bool with_ll, bool collect)
+void run_mstats(mlhip_data* dt, const EmRoute& r, int K, int mode, const double* resp_dev, size_t ld_resp, bool with_ll, bool collect)
 {
     mlhip_ctx* ctx = dt->ctx;
     ensure_em_workspace(dt, K);
@@ -226,6 +205,7 @@ void run_mstats(mlhip_data* dt, int K, int mode, const double* resp_dev, size_t 
     a.n_ll_partials = with_ll ? dt->n_ll : 0;
     a.stats = dt->stats_dev.as<double>();
     a.lse_out = dt->lse.as<double>(); a.ll_scratch = dt->ll_partials.as<double>();
+    a.plain = r.stats_plain(dt->d);
     if (mode == kFromLogRespSelfNorm) {
         dt->esum.reserve(sizeof(double) * dt->n_pad);
         a.ll_out = dt->esum.as<double>();
@@ -236,7 +216,7 @@ void run_mstats(mlhip_data* dt, int K, int mode, const double* resp_dev, size_t 
     dt->stats_ld = a.ldr;
     int rc = 0;
     if (mode == kFromLogRespSelfNorm) {
-        const bool sparse = mstats_sparse_applies(dt, K);
+        const bool sparse = mstats_sparse_applies(dt, r, K);
         const int slot = (int)(dt->sn_calls % 3);
         dt->sn_calls++;
         a.nz_count = dt->nz_dev.as<unsigned long long>();
@@ -297,11 +277,11 @@ double refine_ratio()
 /// Second statistics pass for ONE component with the shift at that component's new mean (K = 1 launch of the same
 /// kernels on column k of the responsibilities of the last pass), all-reduced like the first; replaces covariance k
 /// (and adds the tiny mean correction). Tight clusters far from the global mean need it; the headline shapes never do.
-void refine_component(mlhip_data* dt, int k, double* mean_k, double* cov_k)
+void refine_component(mlhip_data* dt, const EmRoute& r, int k, double* mean_k, double* cov_k)
 {
     mlhip_ctx* ctx = dt->ctx;
     const int d = dt->d, F = stats_count(d);
-    if (dt->stats_mode == kFromLogResp) ensure_lw(dt, dt->em_K);   // after a fused step the block is not in HBM yet
+    if (dt->stats_mode == kFromLogResp) ensure_lw(dt, r, dt->em_K);   // after a fused step the block is not in HBM yet
     dt->refine_shift.reserve(sizeof(double) * d);
     dt->refine_stats.reserve(sizeof(double) * (F + 1));
     HIP_CHECK(hipMemcpyAsync(dt->refine_shift.p, mean_k, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
@@ -313,6 +293,7 @@ void refine_component(mlhip_data* dt, int k, double* mean_k, double* cov_k)
     a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
     a.ll_partials = nullptr; a.n_ll_partials = 0;
     a.stats = dt->refine_stats.as<double>();
+    a.plain = r.stats_plain(d);
     int rc = 0;
     ctx->timed("em_refine", [&] { rc = launch_em_mstats(a, ctx->num_cus, ctx->stream); });
     if (rc <= 0) throw std::runtime_error("statistics kernel launch failed (refinement pass)");
@@ -345,7 +326,7 @@ void refine_component(mlhip_data* dt, int k, double* mean_k, double* cov_k)
 }
 
 
-void finalize_out(mlhip_data* dt, int K, double* mixing_out, double* means_out, double* cov_out)
+void finalize_out(mlhip_data* dt, const EmRoute& r, int K, double* mixing_out, double* means_out, double* cov_out)
 {
     const int d = dt->d;
     host::finalize_mstep(d, K, dt->stats_host.as<double>(), dt->shift.data(), (double)dt->n_global, mixing_out,
@@ -363,14 +344,14 @@ void finalize_out(mlhip_data* dt, int K, double* mixing_out, double* means_out, 
             if (!std::isfinite(off) || !std::isfinite(var)) { flag = false; break; }   // NaN stays NaN (ML/EM.cpp:236)
             flag = off * off > limit * var;                                      // also catches var <= 0 from cancellation
         }
-        if (flag) refine_component(dt, k, means_out + (size_t)k * d, cov_out + (size_t)k * d * d);
+        if (flag) refine_component(dt, r, k, means_out + (size_t)k * d, cov_out + (size_t)k * d * d);
     }
 }
 
 
 /// One diagonal-covariance EM iteration's device work (em_diag.hip) with the statistics shift at `shift_dev`; leaves the
 /// all-reduced [K * (2d+1) statistics, ll_sum] in stats_host. The records must already be in params_dev.
-void run_diag_kernel(mlhip_data* dt, int K, const double* shift_dev, bool collect, const DevBuf* records)
+void run_diag_kernel(mlhip_data* dt, const EmRoute& r, int K, const double* shift_dev, bool collect, const DevBuf* records)
 {
     mlhip_ctx* ctx = dt->ctx;
     DiagArgs a{};
@@ -380,6 +361,7 @@ void run_diag_kernel(mlhip_data* dt, int K, const double* shift_dev, bool collec
     a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
     a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
     a.two_op = shift_dev == dt->shift_dev.as<double>() ? 1 : 0;     // (the records' a, b are relative to the data's shift)
+    a.exact = r.diag_exact ? 1 : 0;
     int grid = 0;
     ctx->timed("em_diag", [&] { grid = mstats::launch_em_diag(a, ctx->num_cus, ctx->stream); });
     if (grid <= 0) throw std::runtime_error("diagonal EM kernel launch failed");
@@ -391,24 +373,13 @@ void run_diag_kernel(mlhip_data* dt, int K, const double* shift_dev, bool collec
 }
 
 
-/// K within one row-block group of the wide statistics kernel: the matrix-core E-step writes the log-responsibilities only and
-/// the statistics kernel normalises them (one exp per pair in the iteration); otherwise the E-step keeps its online
-/// log-sum-exp. MLHIP_SELF_NORM=0 forces the latter (A/B runs).
-bool self_norm_applies(const mlhip_data* dt, int K)
-{
-    static const bool allowed = [] { const char* e = std::getenv("MLHIP_SELF_NORM"); return !(e && e[0] == '0'); }();
-    return allowed && estep_mfma4_supported(dt->D) && !std::getenv("MLHIP_ESTEP") &&
-           em_mstats_self_norm_supported(dt->d, K, dt->ctx->num_cus);
-}
-
-
 /// Whether the next self-normalising statistics pass of `dt` runs the sparse kernel (em_mstats_sparse.hip) instead of the dense
 /// one. The sparse kernel's cost grows with the nonzero responsibilities, the dense kernel's does not: sparse while the pass two
 /// passes back (the last whose count every loop has in hand) had at most kSparseMaxPairs nonzero pairs per sample. The first two
 /// passes with a K are dense. The choice depends only on the handle's call history, so a loop of mlhip_em_step and
-/// mlhip_em_iterate take the same kernels in the same order. MLHIP_MSTATS_SPARSE=1 / 0 forces the sparse / dense kernel (A/B
-/// runs; where the sparse kernel exists).
-bool mstats_sparse_applies(mlhip_data* dt, int K)
+/// mlhip_em_iterate take the same kernels in the same order. The route may force the sparse / dense kernel (r.sparse; where the
+/// sparse kernel exists).
+bool mstats_sparse_applies(mlhip_data* dt, const EmRoute& r, int K)
 {
     constexpr double kSparseMaxPairs = 16.0;
     if (dt->sn_K != K) {
@@ -418,8 +389,7 @@ bool mstats_sparse_applies(mlhip_data* dt, int K)
     dt->nz_dev.reserve(sizeof(unsigned long long));
     dt->nz_host.reserve(3 * sizeof(unsigned long long));
     if (!em_mstats_sparse_supported(dt->d, K, dt->ctx->num_cus)) return false;
-    const char* e = std::getenv("MLHIP_MSTATS_SPARSE");
-    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+    if (r.sparse >= 0) return r.sparse == 1;
     if (dt->sn_calls < 2) return false;
     const unsigned long long nz = dt->nz_host.as<unsigned long long>()[(dt->sn_calls - 2) % 3];
     return (double)nz <= kSparseMaxPairs * (double)dt->n;
@@ -427,21 +397,20 @@ bool mstats_sparse_applies(mlhip_data* dt, int K)
 
 
 /// One full-covariance EM iteration with the closing arithmetic on the HOST (the body of mlhip_em_step).
-void em_step_full(mlhip_data* data, int K, const double* mixing, const double* means, const double* covariances,
+void em_step_full(mlhip_data* data, const EmRoute& r, int K, const double* mixing, const double* means, const double* covariances,
                   double* log_likelihood, double* mixing_out, double* means_out, double* covariances_out)
 {
     PhaseTrace tr;
-    if (run_fused_step(data, K, mixing, means, covariances)) {
+    if (run_fused_step(data, r, K, mixing, means, covariances)) {
         tr.mark("fused E+M launch+sync+D2H");
     } else {
-        const bool self_norm = self_norm_applies(data, K);
-        run_estep(data, K, mixing, means, covariances, !self_norm);
+        run_estep(data, r, K, mixing, means, covariances, !r.self_norm);
         tr.mark("params+launch E");
-        run_mstats(data, K, self_norm && data->estep_variant == 2 ? kFromLogRespSelfNorm : kFromLogResp, nullptr, 0, true);
+        run_mstats(data, r, K, r.self_norm ? kFromLogRespSelfNorm : kFromLogResp, nullptr, 0, true);
         tr.mark("M launch+sync+D2H");
     }
     *log_likelihood = ll_from_stats(data, K);
-    finalize_out(data, K, mixing_out, means_out, covariances_out);
+    finalize_out(data, r, K, mixing_out, means_out, covariances_out);
     tr.mark("closing arithmetic");
 }
 
@@ -481,7 +450,7 @@ void upload_diag_records(mlhip_data* data, int K, const double* mixing, const do
 /// Same cancellation guard as the full-covariance path (refine_ratio): a component whose mean sits far from the shared shift,
 /// measured in its own standard deviations, gets its variances from a second pass with the shift at its new mean (the E part of
 /// that pass re-evaluates the SAME input parameters, still in params_dev).
-void refine_diag(mlhip_data* data, int K, const double* mixing_out, double* means_out, double* variances_out)
+void refine_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixing_out, double* means_out, double* variances_out)
 {
     mlhip_ctx* ctx = data->ctx;
     const int d = data->d, F = diag_stats_count(d);
@@ -499,7 +468,7 @@ void refine_diag(mlhip_data* data, int K, const double* mixing_out, double* mean
         data->refine_shift.reserve(sizeof(double) * data->D);
         HIP_CHECK(hipMemsetAsync(data->refine_shift.p, 0, sizeof(double) * data->D, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(data->refine_shift.p, means_out + (size_t)k * d, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
-        run_diag_kernel(data, K, data->refine_shift.as<double>());
+        run_diag_kernel(data, r, K, data->refine_shift.as<double>());
         const double* s = data->stats_host.as<double>() + (size_t)k * F;
         const double s0 = s[2 * d];
         for (int a = 0; a < d; ++a) {
@@ -512,7 +481,7 @@ void refine_diag(mlhip_data* data, int K, const double* mixing_out, double* mean
 }
 
 
-void em_step_diag(mlhip_data* data, int K, const double* mixing, const double* means, const double* variances,
+void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixing, const double* means, const double* variances,
                   double* log_likelihood, double* mixing_out, double* means_out, double* variances_out)
 {
     const int d = data->d;
@@ -524,7 +493,7 @@ void em_step_diag(mlhip_data* data, int K, const double* mixing, const double* m
         std::vector<double> cov((size_t)K * d * d, 0.0), cov_out((size_t)K * d * d);
         for (int k = 0; k < K; ++k)
             for (int j = 0; j < d; ++j) cov[((size_t)k * d + j) * d + j] = variances[(size_t)k * d + j];
-        em_step_full(data, K, mixing, means, cov.data(), log_likelihood, mixing_out, means_out, cov_out.data());
+        em_step_full(data, r, K, mixing, means, cov.data(), log_likelihood, mixing_out, means_out, cov_out.data());
         for (int k = 0; k < K; ++k)
             for (int j = 0; j < d; ++j) variances_out[(size_t)k * d + j] = cov_out[((size_t)k * d + j) * d + j];
         return;
@@ -535,7 +504,7 @@ void em_step_diag(mlhip_data* data, int K, const double* mixing, const double* m
     data->diag_means.assign(means, means + (size_t)K * d);
     data->diag_vars.assign(variances, variances + (size_t)K * d);
     upload_diag_records(data, K, mixing, means, variances, data->params_dev);
-    run_diag_kernel(data, K, data->shift_dev.as<double>());
+    run_diag_kernel(data, r, K, data->shift_dev.as<double>());
     data->have_estep = true;
     data->lw_valid = false;
     data->diag_step = true;
@@ -543,7 +512,7 @@ void em_step_diag(mlhip_data* data, int K, const double* mixing, const double* m
     const double* st = data->stats_host.as<double>();
     *log_likelihood = st[(size_t)K * F] / (double)data->n_global - (double)d * log_two_pi() / 2;   // ML/EM.cpp:197-198, 211
     host::finalize_mstep_diag(d, K, st, data->shift.data(), (double)data->n_global, mixing_out, means_out, variances_out);
-    refine_diag(data, K, mixing_out, means_out, variances_out);
+    refine_diag(data, r, K, mixing_out, means_out, variances_out);
 }
 
 
@@ -559,7 +528,7 @@ int mlhip_em_expectation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const dou
         if (ctx && ctx->group) { grp::em_expectation(ctx, data, K, mixing, means, covariances, log_likelihood); return; }
         check_em_args(ctx, data, K);
         require(mixing && means && covariances && log_likelihood, "null argument");
-        run_estep(data, (int)K, mixing, means, covariances);
+        run_estep(data, em_route(data, (int)K, false), (int)K, mixing, means, covariances);
         double* slot = data->stats_dev.as<double>() + (size_t)K * stats_count(data->d);
         launch_ll_reduce(data->ll_partials.as<double>(), data->n_ll, slot, ctx->stream);
         HIP_CHECK(hipGetLastError());
@@ -579,9 +548,10 @@ int mlhip_em_maximisation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* 
         check_em_args(ctx, data, K);
         require(mixing_out && means_out && covariances_out, "null argument");
         require(data->have_estep && data->em_K == (int)K, "no E-step results on the device for this K");
-        ensure_lw(data, (int)K);
-        run_mstats(data, (int)K, kFromLogResp, nullptr, 0, true);
-        finalize_out(data, (int)K, mixing_out, means_out, covariances_out);
+        const EmRoute r = em_route(data, (int)K, false);
+        ensure_lw(data, r, (int)K);
+        run_mstats(data, r, (int)K, kFromLogResp, nullptr, 0, true);
+        finalize_out(data, r, (int)K, mixing_out, means_out, covariances_out);
     });
 }
 
@@ -596,7 +566,7 @@ int mlhip_em_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* mi
         }
         check_em_args(ctx, data, K);
         require(mixing && means && covariances && log_likelihood && mixing_out && means_out && covariances_out, "null argument");
-        em_step_full(data, (int)K, mixing, means, covariances, log_likelihood, mixing_out, means_out, covariances_out);
+        em_step_full(data, em_route(data, (int)K, false), (int)K, mixing, means, covariances, log_likelihood, mixing_out, means_out, covariances_out);
     });
 }
 
@@ -611,7 +581,7 @@ int mlhip_em_step_diag(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const doubl
         }
         check_em_args(ctx, data, K);
         require(mixing && means && variances && log_likelihood && mixing_out && means_out && variances_out, "null argument");
-        em_step_diag(data, (int)K, mixing, means, variances, log_likelihood, mixing_out, means_out, variances_out);
+        em_step_diag(data, em_route(data, (int)K, true), (int)K, mixing, means, variances, log_likelihood, mixing_out, means_out, variances_out);
     });
 }
 
@@ -633,7 +603,7 @@ int mlhip_em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covarianc
         require(max_steps >= 1, "at least one step required");
         if (absolute_tolerance < 0 || relative_tolerance < 0) throw DomainError("negative tolerance");
         const bool diag = covariance_type == MLHIP_COVARIANCE_DIAGONAL;
-        em_iterate(data, (int)K, diag, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance, steps_done,
+        em_iterate(data, em_route(data, (int)K, diag), (int)K, diag, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance, steps_done,
                    converged, log_likelihood, log_likelihood_history);
         const size_t cov_doubles = (size_t)K * data->d * (diag ? 1 : data->d);
         ctx->check_ranks_agree("the EM parameters", {{mixing, K}, {means, (size_t)K * data->d}, {covariances, cov_doubles}, {log_likelihood, 1}});
@@ -654,8 +624,9 @@ int mlhip_em_maximisation_from(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, con
         if (data->n)
             HIP_CHECK(hipMemcpy2DAsync(data->resp_dev.p, sizeof(double) * data->ldr, resp, sizeof(double) * ldr,
                                        sizeof(double) * data->n, K, hipMemcpyHostToDevice, ctx->stream));
-        run_mstats(data, (int)K, kFromResp, data->resp_dev.as<double>(), data->ldr, false);
-        finalize_out(data, (int)K, mixing_out, means_out, covariances_out);
+        const EmRoute r = em_route(data, (int)K, false);
+        run_mstats(data, r, (int)K, kFromResp, data->resp_dev.as<double>(), data->ldr, false);
+        finalize_out(data, r, (int)K, mixing_out, means_out, covariances_out);
     });
 }
 
@@ -673,8 +644,9 @@ int mlhip_em_maximisation_from_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t
         // One-hot responsibilities are materialised in the (still unused) log-responsibility buffer of the workspace.
         data->have_estep = false;
         launch_fill_responsibilities(data->labels_dev.as<uint32_t>(), data->n, (int)K, data->lw.as<double>(), data->ldr, ctx->stream);
-        run_mstats(data, (int)K, kFromResp, data->lw.as<double>(), data->ldr, false);
-        finalize_out(data, (int)K, mixing_out, means_out, covariances_out);
+        const EmRoute r = em_route(data, (int)K, false);
+        run_mstats(data, r, (int)K, kFromResp, data->lw.as<double>(), data->ldr, false);
+        finalize_out(data, r, (int)K, mixing_out, means_out, covariances_out);
     });
 }
 
@@ -689,7 +661,7 @@ int mlhip_em_responsibilities_rows(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
         require(ldr >= (int64_t)n_rows, "ldr must be >= the number of rows");
         require(data->have_estep && data->em_K == (int)K, "no E-step results on the device for this K");
         if (!n_rows) return;
-        ensure_lw(data, (int)K);
+        ensure_lw(data, em_route(data, (int)K, false), (int)K);
         const size_t ldo = (size_t)padded_samples(n_rows);
         data->resp_dev.reserve(sizeof(double) * ldo * K);
         RespArgs a{data->lw.as<double>() + first_row, data->ldr, data->lse.as<double>() + first_row, (uint32_t)n_rows, (int)K,
@@ -716,7 +688,7 @@ int mlhip_em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labe
         check_em_args(ctx, data, K);
         require(labels || data->n == 0, "null argument");
         require(data->have_estep && data->em_K == (int)K, "no E-step results on the device for this K");
-        ensure_lw(data, (int)K);
+        ensure_lw(data, em_route(data, (int)K, false), (int)K);
         data->labels_dev.reserve(sizeof(uint32_t) * data->n_pad);
         RespArgs a{data->lw.as<double>(), data->ldr, data->lse.as<double>(), data->n, (int)K, nullptr, 0,
                    data->labels_dev.as<uint32_t>()};
@@ -757,12 +729,12 @@ int mlhip_em_plan(const mlhip_data* data, uint32_t K, uint32_t* flags)
     return guarded([&] {
         require(data && flags && K >= 1, "null argument");
         if (!data->parts.empty()) data = data->parts[0];        // (a group's block: every shard takes the same plan)
+        const EmRoute r = em_route(data, (int)K, false);
         uint32_t f = 0;
-        const bool matrix = estep_mfma4_supported(data->D) && !(data->D <= kRegDim && std::getenv("MLHIP_ESTEP"));
-        if (fused_step_applies(data, (int)K)) f |= MLHIP_PLAN_FUSED;
+        if (r.fused) f |= MLHIP_PLAN_FUSED;
         else {
-            if (matrix) f |= MLHIP_PLAN_MATRIX_ESTEP;
-            if (matrix && self_norm_applies(data, (int)K)) f |= MLHIP_PLAN_SELF_NORM;
+            if (r.estep == Estep::kMatrix4) f |= MLHIP_PLAN_MATRIX_ESTEP;
+            if (r.self_norm) f |= MLHIP_PLAN_SELF_NORM;
         }
         *flags = f;
     });

@@ -9,7 +9,7 @@
 //   * the loop policies        -- run_synchronous (launch, wait, test: every shape), run_lagged (iteration i + 1 is launched before
 //                                 the host looks at iteration i: short iterations), run_resident (the WHOLE loop in one launch of
 //                                 resident workgroups, em_resident.hip: fits whose iteration is a few microseconds),
-//                                 host_closing_loop (d > 1024, MLHIP_DEVICE_CLOSE=0);
+//                                 host_closing_loop (d > 1024, no device closing on the route);
 //   * close_on_host(i)         -- the one iteration a refinement flag (far, tight component) sends through the per-step arithmetic.
 // finish() leaves the device state as the per-step entry points expect it (records of the LAST E-step in params_dev).
 #include "internal.hpp"
@@ -39,15 +39,10 @@ struct ConvergenceTest {
     }
 };
 
-bool env_allows(const char* name)
-{
-    const char* e = std::getenv(name);
-    return !(e && e[0] == '0');
-}
-
 struct EmLoop {
     mlhip_data* data;
     mlhip_ctx* ctx;
+    const EmRoute& route;
     const int K, d;
     const bool diag;
     double *mixing, *means, *covs;              // the caller's arrays (start -> result)
@@ -57,15 +52,14 @@ struct EmLoop {
     bool resident_gave_up = false;
     size_t n_cov = 0, F = 0, n_info = 0, n_pack = 0;
     double refine_limit = 0;
-    bool fold_allowed = true;
     // ---- ring: slot s holds the records R_i of every iteration i with i % 3 == s, pack s the parameters P_i
     DevBuf* rec[3] = {nullptr, nullptr, nullptr};
     bool fold[3] = {false, false, false};       // matrix-core E-step: whether the records of a slot are evaluated in FOLD form
     std::vector<double> shadow[3];              // diagonal mode: host copy of P_i (ensure_lw rebuilds the block from an E-step's inputs)
     uint32_t launched = 0;                      // iterations launched so far
 
-    EmLoop(mlhip_data* dt, int K_, bool diag_, double* mixing_, double* means_, double* covs_)
-        : data(dt), ctx(dt->ctx), K(K_), d(dt->d), diag(diag_), mixing(mixing_), means(means_), covs(covs_) {}
+    EmLoop(mlhip_data* dt, const EmRoute& r, int K_, bool diag_, double* mixing_, double* means_, double* covs_)
+        : data(dt), ctx(dt->ctx), route(r), K(K_), d(dt->d), diag(diag_), mixing(mixing_), means(means_), covs(covs_) {}
 
     // The closing kernel writes its info block into pinned host memory (it_info_slot); in diagonal mode the whole (small) pack lives there.
     double* pack_base(int slot) const { return diag ? data->it_info_slot[slot].as<double>() : data->it_pack[slot].as<double>(); }
@@ -79,9 +73,9 @@ struct EmLoop {
     bool prepare()
     {
         ensure_em_workspace(data, K);
-        if (!env_allows("MLHIP_DEVICE_CLOSE") || !em_close_supported(d) || (diag && !mstats::em_diag_supported(d, K))) return false;
+        if (!route.device_close) return false;
         if (!diag) {
-            prepare_estep(data, K, mixing, means, covs);           // -> params_dev, estep_variant, estep_fold
+            prepare_estep(data, route, K, mixing, means, covs);    // -> params_dev, estep_variant, estep_fold
         }
         n_cov = diag ? (size_t)K * d : (size_t)K * d * d;
         F = diag ? diag_stats_count(d) : stats_count(d);
@@ -104,17 +98,15 @@ struct EmLoop {
             rec[2]->reserve(rec[0]->bytes);
         }
         data->diag_step = diag;
-        fused = !diag && data->estep_variant == 0 && fused_step_applies(data, K);
-        self_norm = !diag && !fused && data->estep_variant == 2 && self_norm_applies(data, K);
+        fused = !diag && route.fused;
+        self_norm = !diag && route.self_norm;
         // Single rank, a shape of the vector-unit E+M form with at most one workgroup per CU: the whole loop in one launch.
-        // MLHIP_RESIDENT=0: off.
         resident_grid = 0;
-        if (fused && !ctx->reduce_fn && ctx->world_size <= 1 && env_allows("MLHIP_RESIDENT")) {
+        if (!diag && route.resident) {
             const FusedArgs fa = fused_args(rec[0]);
             const int g = mstats::em_fused_valu_small_grid(fa, ctx->num_cus);
             if (g > 0 && mstats::em_resident_supported(d, K, g, ctx->num_cus)) resident_grid = g;
         }
-        fold_allowed = env_allows("MLHIP_ESTEP_FOLD");
         refine_limit = refine_ratio();
         fold[0] = data->estep_fold;
         return true;
@@ -126,12 +118,12 @@ struct EmLoop {
     {
         const int in = (int)(i % 3), out = (int)((i + 1) % 3);
         if (diag) {
-            run_diag_kernel(data, K, data->shift_dev.as<double>(), false, rec[in]);
+            run_diag_kernel(data, route, K, data->shift_dev.as<double>(), false, rec[in]);
         } else if (fused) {
-            launch_fused_step(data, K, false, rec[in]);
+            launch_fused_step(data, route, K, false, rec[in]);
         } else {
-            launch_estep(data, K, !self_norm, rec[in], fold[in] ? 1 : 0);
-            run_mstats(data, K, self_norm ? kFromLogRespSelfNorm : kFromLogResp, nullptr, 0, true, false);
+            launch_estep(data, route, K, !self_norm, rec[in], fold[in] ? 1 : 0);
+            run_mstats(data, route, K, self_norm ? kFromLogRespSelfNorm : kFromLogResp, nullptr, 0, true, false);
         }
         data->have_estep = true;
         data->lw_valid = !(diag || fused);
@@ -159,6 +151,7 @@ struct EmLoop {
         a.lse = data->lse.as<double>();
         a.partials = data->partials.as<double>(); a.partials_capacity = data->partials.bytes / sizeof(double);
         a.ll_partials = data->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
+        a.form = route.fused_form;
         return a;
     }
 
@@ -309,15 +302,15 @@ struct EmLoop {
         ctx->sync();
         if (diag) {
             host::finalize_mstep_diag(d, K, data->stats_host.as<double>(), data->shift.data(), (double)data->n_global, mixing, means, covs);
-            refine_diag(data, K, mixing, means, covs);
+            refine_diag(data, route, K, mixing, means, covs);
             upload_diag_records(data, K, mixing, means, covs, *rec[out]);
             shadow[out].assign(mixing, mixing + K);
             shadow[out].insert(shadow[out].end(), means, means + (size_t)K * d);
             shadow[out].insert(shadow[out].end(), covs, covs + n_cov);
         } else {
-            finalize_out(data, K, mixing, means, covs);
+            finalize_out(data, route, K, mixing, means, covs);
             const int variant = data->estep_variant;
-            prepare_estep(data, K, mixing, means, covs, rec[out]);
+            prepare_estep(data, route, K, mixing, means, covs, rec[out]);
             fold[out] = data->estep_fold;
             data->estep_fold = fold[in];                     // (still describes the records in params_dev)
             if (data->estep_variant != variant) throw std::runtime_error("E-step record layout changed inside a fit");
@@ -398,7 +391,7 @@ struct EmLoop {
                 latest_on_host = true;
             } else {
                 latest_on_host = false;
-                fold[(i + 1) % 3] = fold_allowed && data->estep_variant == 2 && data->D <= kRegDim && v.cmax <= kEstepFoldLimit;
+                fold[(i + 1) % 3] = route.fold_allowed && data->estep_variant == 2 && v.cmax <= kEstepFoldLimit;   // (d <= 32)
             }
             last = i;
             if (test(i, v.ll)) break;
@@ -408,29 +401,29 @@ struct EmLoop {
     }
 };
 
-/// d > 1024 (no device closing), MLHIP_DEVICE_CLOSE=0: the loop over the per-step functions.
-void host_closing_loop(mlhip_data* data, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps,
-                       ConvergenceTest& test)
+/// No device closing on the route (d > 1024, MLHIP_DEVICE_CLOSE=0): the loop over the per-step functions.
+void host_closing_loop(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mixing, double* means, double* covs,
+                       uint32_t max_steps, ConvergenceTest& test)
 {
     for (uint32_t step = 0; step < max_steps; ++step) {
         double ll = 0;
-        if (diag) em_step_diag(data, K, mixing, means, covs, &ll, mixing, means, covs);
-        else em_step_full(data, K, mixing, means, covs, &ll, mixing, means, covs);
+        if (diag) em_step_diag(data, r, K, mixing, means, covs, &ll, mixing, means, covs);
+        else em_step_full(data, r, K, mixing, means, covs, &ll, mixing, means, covs);
         if (test(step, ll)) break;
     }
 }
 
 }  // namespace
 
-void em_iterate(mlhip_data* data, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps, double atol,
-                double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history)
+void em_iterate(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps,
+                double atol, double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history)
 {
     *steps_done = 0;
     *converged = 0;
     ConvergenceTest test{atol, rtol, steps_done, converged, log_likelihood, history};
-    EmLoop loop(data, K, diag, mixing, means, covs);
+    EmLoop loop(data, r, K, diag, mixing, means, covs);
     if (!loop.prepare()) {
-        host_closing_loop(data, K, diag, mixing, means, covs, max_steps, test);
+        host_closing_loop(data, r, K, diag, mixing, means, covs, max_steps, test);
         return;
     }
     uint32_t first = 0;

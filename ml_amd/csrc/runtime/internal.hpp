@@ -458,6 +458,39 @@ struct KmBlock {
     int D;
 };
 
+// ---- routes (route.cpp): which kernels one EM or K-means entry-point call runs, decided once per call from the shape (the
+// tuning rules next to the kernels) and the routing switches of DESIGN.md §7 -- the only place the library reads those. Sizing,
+// launching and reporting take their decisions from the route.
+
+/// The E-step kernels: scalar-fed (em_estep.hip, d <= 128), 4x4 matrix-core (em_estep_mfma4.hip, d = 12 .. 128), and above d = 128
+/// the matrix-core tier (big_dim.hip, d <= 1024) or the plain one (generic_dim.hip).
+enum class Estep { kScalarFed, kMatrix4, kBigDim, kPlain };
+
+struct EmRoute {
+    Estep estep = Estep::kScalarFed;
+    bool records_on_device = false;    // d > 64: a fit's first records are factored by the closing kernels (em_close_big.hip)
+    bool fold_allowed = false;         // d <= 32: the matrix-core E-step may take its FOLD form (kEstepFoldLimit)
+    bool fused = false;                // E-step + statistics in one kernel (em_fused_small.hip)
+    int fused_form = kFusedLdsFeed;    // FusedArgs::form
+    bool self_norm = false;            // the matrix-core E-step writes lw only, the statistics kernel normalises it
+    int sparse = -1;                   // self-normalising statistics: 1 the sparse kernel, 0 the dense one, -1 by call history
+    bool balanced = true;              // d <= 32: the wide statistics kernel deals balanced (column block, row block) units
+    bool diag_exact = false;           // diagonal mode: the exact density form always
+    bool device_close = false;         // mlhip_em_iterate closes every iteration on the device (em_close.hip)
+    bool resident = false;             // mlhip_em_iterate may run the whole loop in one launch (em_resident.hip)
+    /// MstatsArgs::plain: the plain tier above d = 128, whole column blocks per wave at d <= 32.
+    int stats_plain(int d) const { return d > kMaxDim ? estep == Estep::kPlain : !balanced; }
+};
+/// `diag`: the call runs the diagonal-covariance kernel where it exists (em_diag.hip), else the full-covariance kernels.
+EmRoute em_route(const mlhip_data* data, int K, bool diag);
+
+struct KmRoute {
+    bool pad = false;                  // the block runs on a copy zero-padded to a multiple of 4 dimensions (km_xt_pad)
+    int kernel = kKmDirect;            // KmeansArgs::kernel
+    bool resident = false;             // mlhip_kmeans_iterate runs the whole loop in one launch (kmeans_resident.hip)
+};
+KmRoute km_route(const mlhip_data* data, int K);
+
 // ---- shared between the families (definitions: context.cpp, data.cpp, em.cpp, kmeans.cpp) ----
 
 int env_int(const char* name, int fallback);
@@ -476,37 +509,38 @@ void download_columns(mlhip_ctx* ctx, char* dst, size_t dst_pitch, const char* s
 
 void ensure_em_workspace(mlhip_data* dt, int K);
 
-/// Builds the per-component records for the E-step kernel that fits (d, env) and uploads them to params_dev.
-void prepare_estep(mlhip_data* dt, int K, const double* mixing, const double* means, const double* covs, DevBuf* target = nullptr);
+/// Builds the per-component records for the route's E-step kernel and uploads them to params_dev.
+void prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs,
+                   DevBuf* target = nullptr);
 
 /// E-step kernel on the records in params_dev: fills lw and -- unless the statistics kernel is going to normalise the
 /// log-responsibilities itself (`with_lse` false, matrix-core kernel only) -- lse and the log-likelihood partials.
 /// `records` / `fold`: another record buffer than params_dev and its form (mlhip_em_iterate keeps a ring of them); default: params_dev
 /// and dt->estep_fold.
-void launch_estep(mlhip_data* dt, int K, bool with_lse = true, const DevBuf* records = nullptr, int fold = -1);
+void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse = true, const DevBuf* records = nullptr, int fold = -1);
 
-void run_estep(mlhip_data* dt, int K, const double* mixing, const double* means, const double* covs, bool with_lse = true);
+void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs,
+               bool with_lse = true);
 
 /// After a fused step only lse exists on the device; whoever needs the log-responsibility block (labels,
 /// responsibilities, a separate M-step, the refinement pass) gets it rebuilt from the same parameter records.
-void ensure_lw(mlhip_data* dt, int K);
+void ensure_lw(mlhip_data* dt, const EmRoute& r, int K);
 
 /// All-reduces the reduced statistics buffer [K*F stats, ll_sum] and leaves it in stats_host.
 void collect_stats(mlhip_data* dt, int K, size_t count = 0);
 
-/// One EM iteration's device work in a single kernel where the shape allows (d <= 6, K <= 32 or d <= 4, K <= 64: em_fused_small.hip): no
-/// N x K block in HBM. MLHIP_FUSED=0 keeps the two-kernel path. Returns false when the shape is not covered.
-bool fused_step_applies(const mlhip_data* dt, int K);
-
 /// The fused kernel + reduction on the records already in params_dev; statistics end in stats_dev (and, with `collect`, all-
 /// reduced in stats_host).
-void launch_fused_step(mlhip_data* dt, int K, bool collect, const DevBuf* records = nullptr);
+void launch_fused_step(mlhip_data* dt, const EmRoute& r, int K, bool collect, const DevBuf* records = nullptr);
 
-bool run_fused_step(mlhip_data* dt, int K, const double* mixing, const double* means, const double* covs);
+/// One EM iteration's device work in a single kernel where the route has it (r.fused): no N x K block in HBM. Returns false
+/// otherwise.
+bool run_fused_step(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs);
 
 /// Runs the statistics kernel on log-responsibilities (mode kFromLogResp: the E-step's lw/lse) or on plain
 /// responsibilities `resp_dev` ([K][ld_resp], ld_resp >= n_pad), all-reduces, leaves [K*F stats, ll_sum] in stats_host.
-void run_mstats(mlhip_data* dt, int K, int mode, const double* resp_dev, size_t ld_resp, bool with_ll, bool collect = true);
+void run_mstats(mlhip_data* dt, const EmRoute& r, int K, int mode, const double* resp_dev, size_t ld_resp, bool with_ll,
+                bool collect = true);
 
 double log_two_pi();
 
@@ -523,30 +557,31 @@ double refine_ratio();
 /// Second statistics pass for ONE component with the shift at that component's new mean (K = 1 launch of the same
 /// kernels on column k of the responsibilities of the last pass), all-reduced like the first; replaces covariance k
 /// (and adds the tiny mean correction). Tight clusters far from the global mean need it; the headline shapes never do.
-void refine_component(mlhip_data* dt, int k, double* mean_k, double* cov_k);
+void refine_component(mlhip_data* dt, const EmRoute& r, int k, double* mean_k, double* cov_k);
 
-void finalize_out(mlhip_data* dt, int K, double* mixing_out, double* means_out, double* cov_out);
+void finalize_out(mlhip_data* dt, const EmRoute& r, int K, double* mixing_out, double* means_out, double* cov_out);
 
 /// One diagonal-covariance EM iteration's device work (em_diag.hip) with the statistics shift at `shift_dev`; leaves the
 /// all-reduced [K * (2d+1) statistics, ll_sum] in stats_host. The records must already be in params_dev.
-void run_diag_kernel(mlhip_data* dt, int K, const double* shift_dev, bool collect = true, const DevBuf* records = nullptr);
+void run_diag_kernel(mlhip_data* dt, const EmRoute& r, int K, const double* shift_dev, bool collect = true,
+                     const DevBuf* records = nullptr);
 
 void ensure_km_workspace(mlhip_data* dt, int K);
 
-KmBlock km_block(mlhip_data* dt, int K);
+KmBlock km_block(mlhip_data* dt, const KmRoute& r, int K);
 
 /// Host centroids [K][d] -> the device table km_cent [K][D] (padded coordinates zero).
 void km_upload_centroids(mlhip_data* dt, int K, const KmBlock& b, const double* centroids);
 
 /// Assignment (+ optional accumulation) against the table in km_cent, partials reduced into km_out =
 /// [inertia, changed, counts, sums] and summed across ranks there when the all-reduce works on device memory.
-void km_launch(mlhip_data* dt, int K, const KmBlock& b, bool accumulate, double* min_dist_out);
+void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool accumulate, double* min_dist_out);
 
 /// km_out -> km_host (`count` doubles), summed across ranks on the host when the all-reduce works on host memory.
 void km_fetch(mlhip_data* dt, size_t count);
 
 /// Assignment (+ optional accumulation); leaves all-reduced [inertia, changed, counts, sums] in km_host.
-void run_kmeans(mlhip_data* dt, int K, const double* centroids, bool accumulate, double* min_dist_out = nullptr);
+void run_kmeans(mlhip_data* dt, const KmRoute& r, int K, const double* centroids, bool accumulate, double* min_dist_out = nullptr);
 
 /// update_step's closing arithmetic on the host (ML/KMeans.cpp:180-192 as sums / counts; empty cluster -> origin, :184).
 void km_close_host(const double* r, int K, int d, double* counts, double* centroids_out);
@@ -554,17 +589,13 @@ void km_close_host(const double* r, int K, int d, double* counts, double* centro
 /// The step loop of KMeans::fit_once (ML/KMeans.cpp:80-110). With the all-reduce on device memory (or none) the centroid
 /// table never leaves the device between trips: sums -> means -> next table by launch_kmeans_close, one read-back per trip
 /// for the two stopping tests. With a host-memory all-reduce (gloo rehearsals) every trip goes through run_kmeans.
-void km_iterate(mlhip_data* dt, int K, double* centroids, double* old_centroids, uint32_t max_steps, double atol,
+void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, double* old_centroids, uint32_t max_steps, double atol,
                 uint32_t* steps_done, int* converged, double* inertia, double* counts);
 
-/// K within one row-block group of the wide statistics kernel: the matrix-core E-step writes the log-responsibilities only and
-/// the statistics kernel normalises them (one exp per pair in the iteration); otherwise the E-step keeps its online
-/// log-sum-exp. MLHIP_SELF_NORM=0 forces the latter (A/B runs).
-bool self_norm_applies(const mlhip_data* dt, int K);
-bool mstats_sparse_applies(mlhip_data* dt, int K);
+bool mstats_sparse_applies(mlhip_data* dt, const EmRoute& r, int K);
 
 /// One full-covariance EM iteration with the closing arithmetic on the HOST (the body of mlhip_em_step).
-void em_step_full(mlhip_data* data, int K, const double* mixing, const double* means, const double* covariances,
+void em_step_full(mlhip_data* data, const EmRoute& r, int K, const double* mixing, const double* means, const double* covariances,
                   double* log_likelihood, double* mixing_out, double* means_out, double* covariances_out);
 
 /// Sums `count` doubles at the head of stats_dev across ranks, whatever kind of hook is installed (device buffer on the
@@ -577,17 +608,17 @@ void upload_diag_records(mlhip_data* data, int K, const double* mixing, const do
 /// Same cancellation guard as the full-covariance path (refine_ratio): a component whose mean sits far from the shared shift,
 /// measured in its own standard deviations, gets its variances from a second pass with the shift at its new mean (the E part of
 /// that pass re-evaluates the SAME input parameters, still in params_dev).
-void refine_diag(mlhip_data* data, int K, const double* mixing_out, double* means_out, double* variances_out);
+void refine_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixing_out, double* means_out, double* variances_out);
 
-void em_step_diag(mlhip_data* data, int K, const double* mixing, const double* means, const double* variances,
+void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixing, const double* means, const double* variances,
                   double* log_likelihood, double* mixing_out, double* means_out, double* variances_out);
 
 /// The loop of EM::fit (ML/EM.cpp:143-170) with everything between two convergence tests on the device (em_loop.cpp): E-step,
 /// statistics, all-reduce, closing arithmetic + next records (em_close.hip); per iteration the host reads back 1 + 2K doubles (log-
 /// likelihood sum, refinement flags, FOLD criterion) and decides. A flagged component (far, tight cluster) sends that one
-/// iteration through the host closing with its refinement pass, exactly as mlhip_em_step would. MLHIP_DEVICE_CLOSE=0, or
-/// d > 64, runs the whole loop through the per-step functions.
-void em_iterate(mlhip_data* data, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps, double atol,
+/// iteration through the host closing with its refinement pass, exactly as mlhip_em_step would. Without device closing
+/// (r.device_close) the whole loop runs through the per-step functions.
+void em_iterate(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps, double atol,
                 double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history);
 
 /// The all-reduce hook of a context that owns an RCCL communicator: one ncclAllReduce(double, sum), in place, on the

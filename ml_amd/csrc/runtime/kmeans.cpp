@@ -57,15 +57,12 @@ void ensure_km_workspace(mlhip_data* dt, int K)
 }
 
 
-KmBlock km_block(mlhip_data* dt, int K)
+KmBlock km_block(mlhip_data* dt, const KmRoute& r, int K)
 {
     mlhip_ctx* ctx = dt->ctx;
     ensure_km_workspace(dt, K);
-    // The matrix-core kernel needs a multiple of 4 dimensions. For d = 1, 2, 3, 5, 6 (stored with D = d or 6 rows) and many
-    // clusters it still beats the direct-form kernel (d = 6, K = 256: 1.9 -> 1.2 ms at N = 10M), so such blocks get a copy
-    // padded with zero rows once: zero coordinates add exactly 0 to every distance, labels and sums are unchanged.
     KmBlock b{dt->xt.as<double>(), dt->D};
-    if (b.D % 4 != 0 && K >= 128 && !std::getenv("MLHIP_KMEANS")) {
+    if (r.pad) {                                                  // (zero rows: every distance, label and sum unchanged)
         const int Dp = (b.D + 3) & ~3;
         if (!dt->km_xt_pad.p) {
             dt->km_xt_pad.reserve(sizeof(double) * dt->ldx * Dp);
@@ -93,7 +90,7 @@ void km_upload_centroids(mlhip_data* dt, int K, const KmBlock& b, const double* 
 
 /// Assignment (+ optional accumulation) against the table in km_cent, partials reduced into km_out =
 /// [inertia, changed, counts, sums] and summed across ranks there when the all-reduce works on device memory.
-void km_launch(mlhip_data* dt, int K, const KmBlock& b, bool accumulate, double* min_dist_out)
+void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool accumulate, double* min_dist_out)
 {
     mlhip_ctx* ctx = dt->ctx;
     const int nxt = dt->km_cur ^ 1;
@@ -109,6 +106,7 @@ void km_launch(mlhip_data* dt, int K, const KmBlock& b, bool accumulate, double*
     a.partials = dt->km_partials.as<double>(); a.partials_capacity = dt->km_partials.bytes / sizeof(double);
     a.cnorm = dt->km_cnorm.as<double>();
     a.out = dt->km_out.as<double>();
+    a.kernel = r.kernel;
     int rc = 0;
     ctx->timed("kmeans_assign", [&] { rc = launch_kmeans_assign(a, ctx->num_cus, ctx->stream); });
     if (rc == -1) throw Unsupported("K-means kernel not instantiated for this dimension");
@@ -138,11 +136,11 @@ void km_fetch(mlhip_data* dt, size_t count)
 
 
 /// Assignment (+ optional accumulation); leaves all-reduced [inertia, changed, counts, sums] in km_host.
-void run_kmeans(mlhip_data* dt, int K, const double* centroids, bool accumulate, double* min_dist_out)
+void run_kmeans(mlhip_data* dt, const KmRoute& r, int K, const double* centroids, bool accumulate, double* min_dist_out)
 {
-    const KmBlock b = km_block(dt, K);
+    const KmBlock b = km_block(dt, r, K);
     km_upload_centroids(dt, K, b, centroids);
-    km_launch(dt, K, b, accumulate, min_dist_out);
+    km_launch(dt, r, K, b, accumulate, min_dist_out);
     km_fetch(dt, 2 + (accumulate ? (size_t)K * (dt->d + 1) : 0));
 }
 
@@ -161,21 +159,18 @@ void km_close_host(const double* r, int K, int d, double* counts, double* centro
 /// The step loop of KMeans::fit_once (ML/KMeans.cpp:80-110). With the all-reduce on device memory (or none) the centroid
 /// table never leaves the device between trips: sums -> means -> next table by launch_kmeans_close, one read-back per trip
 /// for the two stopping tests. With a host-memory all-reduce (gloo rehearsals) every trip goes through run_kmeans.
-void km_iterate(mlhip_data* dt, int K, double* centroids, double* old_centroids, uint32_t max_steps, double atol,
+void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, double* old_centroids, uint32_t max_steps, double atol,
                 uint32_t* steps_done, int* converged, double* inertia, double* counts)
 {
     mlhip_ctx* ctx = dt->ctx;
     const int d = dt->d;
     const size_t kd = (size_t)K * d;
     const bool device_route = !(ctx->reduce_fn && !ctx->reduce_on_device);
-    const KmBlock b = km_block(dt, K);
+    const KmBlock b = km_block(dt, route, K);
     std::vector<double> cur(centroids, centroids + kd), old(kd, 0.0), upd(kd);
     // Small blocks with few clusters in the dimensions of the direct-form kernel: the whole loop in ONE launch of one workgroup
-    // (device/kmeans_resident.hip; bit-identical to the launches below; MLHIP_RESIDENT=0: off).
-    const char* const res_env = std::getenv("MLHIP_RESIDENT");                 // (per call, as the EM loop reads it: the tests flip it)
-    const bool resident_allowed = !(res_env && res_env[0] == '0');
-    if (device_route && !ctx->reduce_fn && ctx->world_size <= 1 && b.xt == dt->xt.as<double>() && resident_allowed &&
-        kmeans_resident_supported(b.D, d, K, dt->n)) {
+    // (device/kmeans_resident.hip; bit-identical to the launches below).
+    if (route.resident) {
         const size_t n_out = 4 + (size_t)K + 2 * kd;
         dt->km_host.reserve(sizeof(double) * (n_out > (size_t)K * b.D ? n_out : (size_t)K * b.D));
         km_upload_centroids(dt, K, b, cur.data());
@@ -212,7 +207,7 @@ void km_iterate(mlhip_data* dt, int K, double* centroids, double* old_centroids,
     for (uint32_t step = 0; step < max_steps; ++step) {
         if (device_route) {
             // (the closing arithmetic writes the block into the pinned km_host as well: no copy-engine transfer in the loop)
-            km_launch(dt, K, b, true, nullptr);
+            km_launch(dt, route, K, b, true, nullptr);
             launch_kmeans_close(dt->km_out.as<double>(), K, d, b.D, dt->km_cent_next.as<double>(), dt->km_host.as<double>(), ctx->stream);
             HIP_CHECK(hipGetLastError());
             ctx->sync();
@@ -220,7 +215,7 @@ void km_iterate(mlhip_data* dt, int K, double* centroids, double* old_centroids,
             if (counts) std::copy(r + 2, r + 2 + K, counts);
             std::copy(r + 2 + K, r + 2 + K + kd, upd.begin());
         } else {
-            run_kmeans(dt, K, cur.data(), true);
+            run_kmeans(dt, route, K, cur.data(), true);
             km_close_host(dt->km_host.as<double>(), K, d, counts, upd.data());
         }
         const double* r = dt->km_host.as<double>();
@@ -242,10 +237,10 @@ void km_iterate(mlhip_data* dt, int K, double* centroids, double* old_centroids,
             }
             if (shift < atol) {           // (:103-108) one more assignment under the final centroids
                 if (device_route) {
-                    km_launch(dt, K, b, false, nullptr);
+                    km_launch(dt, route, K, b, false, nullptr);
                     km_fetch(dt, 2);
                 } else {
-                    run_kmeans(dt, K, cur.data(), false);
+                    run_kmeans(dt, route, K, cur.data(), false);
                 }
                 *inertia = dt->km_host.as<double>()[0];
                 *converged = 1;
@@ -269,7 +264,7 @@ int mlhip_kmeans_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double
         if (ctx && ctx->group) { grp::kmeans_step(ctx, data, K, true, centroids, inertia, n_changed, counts, centroids_out); return; }
         check_em_args(ctx, data, K);
         require(centroids && inertia && n_changed && counts && centroids_out, "null argument");
-        run_kmeans(data, (int)K, centroids, true);
+        run_kmeans(data, km_route(data, (int)K), (int)K, centroids, true);
         const double* r = data->km_host.as<double>();
         *inertia = r[0];
         *n_changed = (uint64_t)std::llround(r[1]);
@@ -292,7 +287,7 @@ int mlhip_kmeans_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* c
         require(centroids && steps_done && converged && inertia, "null argument");
         require(max_steps >= 1, "at least one step");
         require(absolute_tolerance >= 0, "negative tolerance");
-        km_iterate(data, (int)K, centroids, old_centroids, max_steps, absolute_tolerance, steps_done, converged, inertia, counts);
+        km_iterate(data, km_route(data, (int)K), (int)K, centroids, old_centroids, max_steps, absolute_tolerance, steps_done, converged, inertia, counts);
         ctx->check_ranks_agree("the K-means centroids", {{centroids, (size_t)K * data->d}, {inertia, 1}});
     });
 }
@@ -304,7 +299,7 @@ int mlhip_kmeans_assign(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const doub
         if (ctx && ctx->group) { grp::kmeans_step(ctx, data, K, false, centroids, inertia, n_changed, nullptr, nullptr); return; }
         check_em_args(ctx, data, K);
         require(centroids && inertia && n_changed, "null argument");
-        run_kmeans(data, (int)K, centroids, false);
+        run_kmeans(data, km_route(data, (int)K), (int)K, centroids, false);
         const double* r = data->km_host.as<double>();
         *inertia = r[0];
         *n_changed = (uint64_t)std::llround(r[1]);
@@ -351,9 +346,10 @@ int mlhip_kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int
         const int cur = data->km_cur;
         const bool have = data->km_have_old;
         data->km_probe.reserve(sizeof(double) * data->n_pad);
-        const KmBlock b = km_block(data, 1);
+        const KmRoute route = km_route(data, 1);
+        const KmBlock b = km_block(data, route, 1);
         km_upload_centroids(data, 1, b, centroid);
-        km_launch(data, 1, b, false, data->km_probe.as<double>());
+        km_launch(data, route, 1, b, false, data->km_probe.as<double>());
         if (have) data->km_cur = cur;
         data->km_have_old = have;
         const int nb = kpp_blocks(data->n);
@@ -532,7 +528,7 @@ int mlhip_min_squared_distances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, co
         const int cur = data->km_cur;
         const bool have = data->km_have_old;
         data->km_probe.reserve(sizeof(double) * data->n_pad);
-        run_kmeans(data, (int)K, centroids, false, data->km_probe.as<double>());
+        run_kmeans(data, km_route(data, (int)K), (int)K, centroids, false, data->km_probe.as<double>());
         if (have) {
             // The assignment wrote labels into the *other* buffer; keep the previous labels current.
             data->km_cur = cur;

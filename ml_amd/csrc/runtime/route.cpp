@@ -1,0 +1,110 @@
+// Routes: which kernels one EM or K-means entry-point call runs. The shape rules are the kernels' own (device/*.hip, plain functions
+// of the shape); the routing switches of DESIGN.md §7 are read here, once per call, and nowhere else.
+#include "internal.hpp"
+
+namespace mlhip_rt {
+namespace {
+
+/// First character of an environment variable; '\0' when it is unset or empty.
+char env_char(const char* name)
+{
+    const char* e = std::getenv(name);
+    return e ? e[0] : '\0';
+}
+
+/// 0 / 1 when the variable starts with that digit, -1 (automatic) otherwise.
+int env_force(const char* name)
+{
+    const char c = env_char(name);
+    return c == '0' || c == '1' ? c - '0' : -1;
+}
+
+struct Switches {
+    bool estep_valu;            // MLHIP_ESTEP=valu
+    bool fold, self_norm, balanced, fused, diag_ab, big_dim, device_close, records, resident;   // on unless "0"
+    int sparse, sfeed;          // MLHIP_MSTATS_SPARSE, MLHIP_FUSED_SFEED: 0 / 1 forced, -1 automatic
+    int fused_valu;             // MLHIP_FUSED_VALU: 0 never, 2 wherever built, -1 by shape
+    int kmeans;                 // MLHIP_KMEANS=valu / mfma: kKmDirect / kKmMatrix forced, -1 automatic
+};
+
+Switches read_switches()
+{
+    Switches s;
+    const char* estep = std::getenv("MLHIP_ESTEP");
+    s.estep_valu = estep && std::strcmp(estep, "valu") == 0;
+    s.fold = env_char("MLHIP_ESTEP_FOLD") != '0';
+    s.self_norm = env_char("MLHIP_SELF_NORM") != '0';
+    s.balanced = env_char("MLHIP_MSTATS_BALANCED") != '0';
+    s.fused = env_char("MLHIP_FUSED") != '0';
+    s.diag_ab = env_char("MLHIP_DIAG_AB") != '0';
+    s.big_dim = env_char("MLHIP_BIG_DIM") != '0';
+    s.device_close = env_char("MLHIP_DEVICE_CLOSE") != '0';
+    const int records = env_force("MLHIP_DEVICE_RECORDS");   // (unset: follows MLHIP_DEVICE_CLOSE)
+    s.records = records >= 0 ? records == 1 : s.device_close;
+    s.resident = env_char("MLHIP_RESIDENT") != '0';
+    s.sparse = env_force("MLHIP_MSTATS_SPARSE");
+    s.sfeed = env_force("MLHIP_FUSED_SFEED");
+    const char valu = env_char("MLHIP_FUSED_VALU");
+    s.fused_valu = valu == '0' ? 0 : valu == '2' ? 2 : -1;
+    const char km = env_char("MLHIP_KMEANS");
+    s.kmeans = km == 'v' ? kKmDirect : km == 'm' ? kKmMatrix : -1;
+    return s;
+}
+
+}  // namespace
+
+EmRoute em_route(const mlhip_data* data, int K, bool diag)
+{
+    const Switches sw = read_switches();
+    const mlhip_ctx* ctx = data->ctx;
+    const int d = data->d, D = data->D;
+    const bool diag_kernel = diag && mstats::em_diag_supported(d, K);
+    EmRoute r;
+    if (estep_mfma4_supported(D) && !(D <= kRegDim && sw.estep_valu)) r.estep = Estep::kMatrix4;
+    else if (D <= kMaxDim) r.estep = Estep::kScalarFed;
+    else r.estep = sw.big_dim && big_dim_applies(D) ? Estep::kBigDim : Estep::kPlain;
+    r.records_on_device = sw.records && em_close_big_supported(d);
+    r.fold_allowed = sw.fold && D <= kRegDim;
+    // (the fused kernel reads the scalar-fed E-step's records)
+    r.fused = !diag_kernel && sw.fused && r.estep == Estep::kScalarFed && mstats::em_fused_supported(d, K);
+    if (r.fused) {
+        if (sw.fused_valu != 0 && mstats::em_fused_valu_supported(d, K) &&
+            (sw.fused_valu == 2 || mstats::em_fused_valu_preferred(d, K, data->n)))
+            r.fused_form = kFusedValu;
+        else if (sw.sfeed >= 0 && mstats::em_fused_lds_feed_supported(d))
+            r.fused_form = sw.sfeed ? kFusedScalarFeed : kFusedLdsFeed;
+        else
+            r.fused_form = mstats::em_fused_scalar_feed(d, data->n) ? kFusedScalarFeed : kFusedLdsFeed;
+    }
+    // K within one row-block group of the wide statistics kernel: one exp per pair in the iteration (MLHIP_ESTEP=valu: at no d)
+    r.self_norm = !diag_kernel && !r.fused && sw.self_norm && !sw.estep_valu && r.estep == Estep::kMatrix4 &&
+                  em_mstats_self_norm_supported(d, K, ctx->num_cus);
+    r.sparse = sw.sparse;
+    r.balanced = sw.balanced;
+    r.diag_exact = !sw.diag_ab;
+    r.device_close = sw.device_close && em_close_supported(d) && (!diag || diag_kernel);
+    // single rank, the vector-unit form (em_loop.cpp checks the grid)
+    r.resident = sw.resident && r.fused && r.fused_form == kFusedValu && !ctx->reduce_fn && ctx->world_size <= 1;
+    return r;
+}
+
+KmRoute km_route(const mlhip_data* data, int K)
+{
+    const Switches sw = read_switches();
+    const mlhip_ctx* ctx = data->ctx;
+    KmRoute r;
+    // The matrix-core kernel needs a multiple of 4 dimensions. For d = 1, 2, 3, 5, 6 (stored with D = d or 6 rows) and many
+    // clusters it still beats the direct-form kernel (d = 6, K = 256: 1.9 -> 1.2 ms at N = 10M), so such blocks get a copy
+    // padded with zero rows once: zero coordinates add exactly 0 to every distance, labels and sums are unchanged.
+    r.pad = data->D % 4 != 0 && K >= 128 && sw.kmeans < 0;
+    const int D = r.pad ? (data->D + 3) & ~3 : data->D;
+    const bool direct = sw.kmeans == kKmDirect || (sw.kmeans < 0 && kmeans_few_clusters(D, K, data->n));
+    if ((!direct || D > kMidDim) && kmeans_mfma_supported(D, K)) r.kernel = kKmMatrix;   // (above d = 64 only the matrix-core kernel exists)
+    else if (D > kMaxDim) r.kernel = sw.big_dim && big_dim_kmeans_applies(D) ? kKmBigDim : kKmPlain;
+    else r.kernel = kKmDirect;
+    // small blocks with few clusters, single rank: the whole step loop in one launch of one workgroup
+    r.resident = sw.resident && !r.pad && !ctx->reduce_fn && ctx->world_size <= 1 && kmeans_resident_supported(D, data->d, K, data->n);
+    return r;
+}
+
+}  // namespace mlhip_rt

@@ -271,6 +271,33 @@ def test_estep_kernel_variants_agree(ctx, oracle, d, K, monkeypatch):
             assert np.max(np.abs(a - b)) <= 1e-11 * np.max(np.abs(b))
 
 
+def test_estep_switch_other_than_valu_routes_as_unset(ctx, monkeypatch):
+    """MLHIP_ESTEP means one thing: `valu` selects the scalar-fed E-step at d <= 32. Any other value routes as if it were unset:
+    the plan reports the matrix-core E-step with self-normalisation, and the fit is the same bits."""
+    from ml_amd import synth
+    d, K, n = 16, 16, 20000
+    mix = synth.Mixture(d, K, seed=116)
+    X, _ = mix.sample(n)
+    pi0, mu0 = np.full(K, 1.0 / K), mix.initial_means()
+    S0 = np.stack([np.cov(X.T)] * K)
+    out = {}
+    for value in (None, "mfma4"):
+        if value is None:
+            monkeypatch.delenv("MLHIP_ESTEP", raising=False)
+        else:
+            monkeypatch.setenv("MLHIP_ESTEP", value)
+        dt = _data(ctx, X)
+        out[value] = (dt.em_plan(K), dt.em_iterate(pi0, mu0, S0, 12, atol=1e-10))
+        dt.close()
+    monkeypatch.delenv("MLHIP_ESTEP", raising=False)
+    (plan0, fit0), (plan1, fit1) = out[None], out["mfma4"]
+    assert plan0 == {"fused": False, "matrix_estep": True, "self_norm": True}
+    assert plan1 == plan0
+    assert fit1[0] == fit0[0] and fit1[1] == fit0[1] and fit1[2] == fit0[2]
+    for a, b in zip(fit1[3:], fit0[3:]):
+        assert np.array_equal(a, b, equal_nan=True)
+
+
 @pytest.mark.parametrize("n,d,K", [(5000, 4, 3), (20000, 8, 256), (7001, 8, 17), (3000, 16, 40), (3000, 32, 64), (2000, 12, 1),
                                    (3000, 40, 9), (2500, 64, 33), (3000, 50, 160), (6000, 16, 256), (9000, 8, 1500),
                                    (5000, 32, 700), (4000, 64, 300), (70000, 4, 5000), (3000, 100, 70), (2000, 128, 260), (30000, 8, 10000), (20000, 2, 4000), (9000, 3, 256), (9000, 6, 300), (5000, 5, 130), (4000, 1, 128)])
