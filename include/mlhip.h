@@ -289,6 +289,36 @@ int mlhip_timing_get(mlhip_ctx* ctx, const char* name, double* avg_ms, uint64_t*
                                         (the one exponential per (sample, component) runs THERE) */
 int mlhip_em_plan(const mlhip_data* data, uint32_t K, uint32_t* flags);
 
+/* The whole route of one call (diagnostic; tests assert which kernel a case runs): what the library's routing decides, once
+ * per entry-point call, from the block's shape, K and the MLHIP_* routing switches as they are set when this is called. Nothing
+ * is launched. covariance_type: 0 full, 1 diagonal. A device group's block reports the route of its shards. Decisions taken
+ * at launch -- sparse = -1, the resident loop's grid check, FOLD's per-iteration test against the parameters -- are not in here:
+ * pin them by their switch or read the launch counters (mlhip_timing_get). */
+enum { MLHIP_ESTEP_SCALAR_FED = 0, MLHIP_ESTEP_MATRIX4 = 1, MLHIP_ESTEP_BIG_DIM = 2, MLHIP_ESTEP_PLAIN = 3 };
+enum { MLHIP_FUSED_LDS_FEED = 0, MLHIP_FUSED_SCALAR_FEED = 1, MLHIP_FUSED_VALU = 2 };
+enum { MLHIP_KMEANS_DIRECT = 0, MLHIP_KMEANS_MATRIX = 1, MLHIP_KMEANS_BIG_DIM = 2, MLHIP_KMEANS_PLAIN = 3 };
+typedef struct mlhip_em_route_info {
+    int32_t estep;              /* MLHIP_ESTEP_* */
+    int32_t fused;              /* E-step + statistics in one kernel */
+    int32_t fused_form;         /* MLHIP_FUSED_* (meaningful when fused) */
+    int32_t self_norm;          /* the statistics kernel normalises the log-responsibilities */
+    int32_t sparse;             /* self-normalising statistics: 1 sparse kernel, 0 dense kernel, -1 by the call history */
+    int32_t balanced;           /* d <= 32: the wide statistics kernel deals (column block, row block) units */
+    int32_t fold_allowed;       /* the matrix-core E-step may take its FOLD form */
+    int32_t diag_kernel;        /* covariance_type 1: the diagonal kernel exists for this (d, K) and runs */
+    int32_t diag_exact;         /* diagonal mode: the exact density form always */
+    int32_t device_close;       /* mlhip_em_iterate closes its iterations on the device */
+    int32_t records_on_device;  /* d > 64: a fit's first records are factored on the device */
+    int32_t resident;           /* mlhip_em_iterate may run the whole loop in one launch */
+} mlhip_em_route_info;
+typedef struct mlhip_kmeans_route_info {
+    int32_t kernel;             /* MLHIP_KMEANS_* */
+    int32_t pad;                /* the block runs on a copy zero-padded to a multiple of 4 dimensions */
+    int32_t resident;           /* mlhip_kmeans_iterate runs the whole loop in one launch */
+} mlhip_kmeans_route_info;
+int mlhip_em_route(const mlhip_data* data, uint32_t K, int covariance_type, mlhip_em_route_info* out);
+int mlhip_kmeans_route(const mlhip_data* data, uint32_t K, mlhip_kmeans_route_info* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -252,6 +252,17 @@ class Context:
         return ms.value, cnt.value
 
 
+class EmRouteInfo(C.Structure):
+    """mlhip_em_route_info"""
+    _fields_ = [(name, C.c_int32) for name in ("estep", "fused", "fused_form", "self_norm", "sparse", "balanced", "fold_allowed",
+                                               "diag_kernel", "diag_exact", "device_close", "records_on_device", "resident")]
+
+
+class KmeansRouteInfo(C.Structure):
+    """mlhip_kmeans_route_info"""
+    _fields_ = [(name, C.c_int32) for name in ("kernel", "pad", "resident")]
+
+
 class Data:
     """A d x N sample block resident in HBM (mlhip_data). `x` is N x d float64 C-contiguous."""
 
@@ -354,6 +365,25 @@ class Data:
         f = C.c_uint32()
         check(lib.mlhip_em_plan(self._h, C.c_uint32(K), C.byref(f)))
         return {"fused": bool(f.value & 1), "matrix_estep": bool(f.value & 2), "self_norm": bool(f.value & 4)}
+
+    def em_route(self, K, covariance_type="full"):
+        """The whole route of an EM call of K components under the switches as they are set now (mlhip_em_route): a dict of
+        the fields of mlhip_em_route_info, `estep` / `fused_form` by name, the flags as bool, `sparse` as None (by the call
+        history), False or True."""
+        info = EmRouteInfo()
+        check(lib.mlhip_em_route(self._h, C.c_uint32(K), {"full": 0, "diag": 1}[covariance_type], C.byref(info)))
+        out = {name: bool(getattr(info, name)) for name, _ in EmRouteInfo._fields_}
+        out["estep"] = ("scalar_fed", "matrix4", "big_dim", "plain")[info.estep]
+        out["fused_form"] = ("lds_feed", "scalar_feed", "valu")[info.fused_form] if info.fused else None
+        out["sparse"] = None if info.sparse < 0 else bool(info.sparse)
+        return out
+
+    def kmeans_route(self, K):
+        """The route of a K-means call of K clusters (mlhip_kmeans_route): {'kernel': 'direct' | 'matrix' | 'big_dim' | 'plain',
+        'pad': bool, 'resident': bool}."""
+        info = KmeansRouteInfo()
+        check(lib.mlhip_kmeans_route(self._h, C.c_uint32(K), C.byref(info)))
+        return {"kernel": ("direct", "matrix", "big_dim", "plain")[info.kernel], "pad": bool(info.pad), "resident": bool(info.resident)}
 
     def em_expectation(self, mixing, means, covs):
         K = len(mixing)

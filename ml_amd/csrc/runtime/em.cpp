@@ -740,4 +740,29 @@ int mlhip_em_plan(const mlhip_data* data, uint32_t K, uint32_t* flags)
     });
 }
 
+int mlhip_em_route(const mlhip_data* data, uint32_t K, int covariance_type, mlhip_em_route_info* out)
+{
+    return guarded([&] {
+        require(data && out && K >= 1 && (covariance_type == 0 || covariance_type == 1), "bad argument");
+        if (!data->parts.empty()) data = data->parts[0];
+        const bool diag = covariance_type == 1;
+        const EmRoute r = em_route(data, (int)K, diag);
+        out->estep = r.estep == Estep::kScalarFed ? MLHIP_ESTEP_SCALAR_FED : r.estep == Estep::kMatrix4 ? MLHIP_ESTEP_MATRIX4
+                   : r.estep == Estep::kBigDim ? MLHIP_ESTEP_BIG_DIM : MLHIP_ESTEP_PLAIN;
+        out->fused = r.fused;
+        static_assert(kFusedLdsFeed == MLHIP_FUSED_LDS_FEED && kFusedScalarFeed == MLHIP_FUSED_SCALAR_FEED && kFusedValu == MLHIP_FUSED_VALU,
+                      "mlhip.h names the forms by FusedArgs::form");
+        out->fused_form = r.fused_form;
+        out->self_norm = r.self_norm;
+        out->sparse = r.sparse;
+        out->balanced = r.balanced;
+        out->fold_allowed = r.fold_allowed;
+        out->diag_kernel = diag && mstats::em_diag_supported(data->d, (int)K);
+        out->diag_exact = r.diag_exact;
+        out->device_close = r.device_close;
+        out->records_on_device = r.records_on_device;
+        out->resident = r.resident;
+    });
+}
+
 }  // extern "C"

@@ -539,4 +539,18 @@ int mlhip_min_squared_distances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, co
     });
 }
 
+int mlhip_kmeans_route(const mlhip_data* data, uint32_t K, mlhip_kmeans_route_info* out)
+{
+    return guarded([&] {
+        require(data && out && K >= 1, "bad argument");
+        if (!data->parts.empty()) data = data->parts[0];
+        static_assert(kKmDirect == MLHIP_KMEANS_DIRECT && kKmMatrix == MLHIP_KMEANS_MATRIX && kKmBigDim == MLHIP_KMEANS_BIG_DIM &&
+                      kKmPlain == MLHIP_KMEANS_PLAIN, "mlhip.h names the kernels by KmeansArgs::kernel");
+        const KmRoute r = km_route(data, (int)K);
+        out->kernel = r.kernel;
+        out->pad = r.pad;
+        out->resident = r.resident;
+    });
+}
+
 }  // extern "C"

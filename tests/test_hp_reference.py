@@ -1,0 +1,280 @@
+"""The extended-precision reference (oracle/hp_reference.py) pinned against 50-digit arithmetic, the CPU oracle measured
+against the reference at d = 2 ... 256 (its first independent pin above d = 32), and the comparison helper itself. CPU only.
+
+Oracle bound: every output of one E + M step within  C_ORACLE * sqrt(N_k) * 2^-53 * kappa_k  of the
+reference in section 4's norms (max-norm relative; per component for means and covariances with N_k = N pi_k and kappa_k =
+|L_k|_inf |L_k^-1|_inf of the component's input covariance; N and the largest kappa for the log-likelihood, the mixing weights
+and the responsibilities). C_ORACLE is 4 x the largest constant the oracle needed over CASES / DIAG_CASES in one CPU run
+(the per-case figures are in DESIGN.md section 5 and oracle/README.md); `python tests/test_hp_reference.py` prints them."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from oracle import hp_reference as hp   # noqa: E402  (raises where long double is not extended precision: a failure, not a skip)
+from oracle.hp_cases import KMEANS_SHAPES, edge_problem, oracle_step, problem, refinement_problem   # noqa: E402
+
+LD = np.longdouble
+MP_LIMIT = hp.EPS64 / 64
+C_ORACLE = 4 * 7.0        # measured: the largest constant over all cases is 6.99 (diagonal d = 7, K = 40: a component of ~15 samples,
+                          # where sqrt(N_k) 2^-53 is close to the few roundings any route makes); DESIGN.md section 5
+
+
+# ---- the reference against mpmath at 50 digits ---------------------------------------------------------------------------
+
+def _mp_problem(d, K, n, seed, diagonal=False):
+    rng = np.random.default_rng(seed)
+    means = 1.5 * rng.standard_normal((K, d))
+    comp = rng.integers(0, K, n)
+    X = means[comp] + rng.standard_normal((n, d)) + 0.25
+    mu0 = means + 0.3 * rng.standard_normal((K, d))
+    pi0 = rng.uniform(0.5, 1.5, K)
+    pi0 /= pi0.sum()
+    if diagonal:
+        S0 = rng.uniform(0.7, 1.6, (K, d))
+    else:
+        A = rng.standard_normal((K, d, d))
+        S0 = np.stack([a @ a.T / d + np.eye(d) for a in A])
+    return X, pi0, mu0, S0
+
+
+def _mp_em_step(X, pi0, mu0, S0, diagonal):
+    import mpmath as mp
+    mp.mp.dps = 50
+    n, d = X.shape
+    K = len(pi0)
+    x = [[mp.mpf(float(v)) for v in row] for row in X]
+    lw = [[None] * K for _ in range(n)]
+    for k in range(K):
+        mu = [mp.mpf(float(v)) for v in mu0[k]]
+        if diagonal:
+            var = [mp.mpf(float(v)) for v in S0[k]]
+            half_log_det = sum(mp.log(v) for v in var) / 2
+        else:
+            L = mp.cholesky(mp.matrix([[mp.mpf(float(v)) for v in row] for row in S0[k]]))
+            half_log_det = sum(mp.log(L[j, j]) for j in range(d))
+        for i in range(n):
+            c = [x[i][j] - mu[j] for j in range(d)]
+            if diagonal:
+                q = sum(c[j] * c[j] / var[j] for j in range(d))
+            else:
+                y = []
+                for j in range(d):
+                    y.append((c[j] - sum(L[j, l] * y[l] for l in range(j))) / L[j, j])
+                q = sum(v * v for v in y)
+            lw[i][k] = mp.log(mp.mpf(float(pi0[k]))) - half_log_det - q / 2 - d * mp.log(2 * mp.pi) / 2
+    resp = [[None] * K for _ in range(n)]
+    ll = mp.mpf(0)
+    for i in range(n):
+        m = max(lw[i])
+        total = sum(mp.exp(v - m) for v in lw[i])
+        ll += m + mp.log(total)
+        for k in range(K):
+            resp[i][k] = mp.exp(lw[i][k] - m) / total
+    s0 = [sum(resp[i][k] for i in range(n)) for k in range(K)]
+    means = [[sum(resp[i][k] * x[i][j] for i in range(n)) / s0[k] for j in range(d)] for k in range(K)]
+    if diagonal:
+        second = [[sum(resp[i][k] * (x[i][j] - means[k][j]) ** 2 for i in range(n)) / s0[k] for j in range(d)] for k in range(K)]
+    else:
+        second = [[[sum(resp[i][k] * (x[i][a] - means[k][a]) * (x[i][b] - means[k][b]) for i in range(n)) / s0[k]
+                    for b in range(d)] for a in range(d)] for k in range(K)]
+    return ll / n, resp, [v / n for v in s0], means, second
+
+
+def _mp_rel_err(got, ref):
+    """max |got - ref| / max |ref| with the difference taken at 50 digits (a long double converts to mpmath exactly)."""
+    import mpmath as mp
+    got = np.asarray(got, dtype=LD).ravel()
+    flat = ref
+    while isinstance(flat, list) and flat and isinstance(flat[0], list):
+        flat = [v for row in flat for v in row]
+    if not isinstance(flat, list):
+        flat = [flat]
+    assert got.size == len(flat)
+    as_mp = [mp.mpf(int(m * LD(2) ** 64)) * mp.mpf(2) ** (int(e) - 64) for m, e in (np.frexp(v) for v in got)]
+    return float(max(abs(a - b) for a, b in zip(as_mp, flat)) / max(abs(b) for b in flat))
+
+
+@pytest.mark.parametrize("d,K,n,seed,diagonal", [(2, 3, 60, 1, False), (3, 2, 47, 2, False), (6, 3, 60, 3, False), (5, 1, 33, 4, False),
+                                                 (4, 3, 60, 5, True), (6, 2, 51, 6, True)])
+def test_em_reference_against_50_digits(d, K, n, seed, diagonal):
+    X, pi0, mu0, S0 = _mp_problem(d, K, n, seed, diagonal)
+    got = (hp.em_step_diag if diagonal else hp.em_step)(X, pi0, mu0, S0)
+    want = _mp_em_step(X, pi0, mu0, S0, diagonal)
+    for name, g, w in zip(("log-likelihood", "responsibilities", "mixing", "means", "covariances"), got, want):
+        err = _mp_rel_err(g, w)
+        print(f"d={d} K={K} n={n} {name}: {err:.2e} (limit {MP_LIMIT:.2e})")
+        assert err <= MP_LIMIT, name
+
+
+@pytest.mark.parametrize("d,K,n,seed", [(2, 3, 60, 11), (5, 2, 41, 12), (6, 3, 57, 13)])
+def test_kmeans_reference_against_50_digits(d, K, n, seed):
+    import mpmath as mp
+    mp.mp.dps = 50
+    X, _, C0, _ = _mp_problem(d, K, n, seed)
+    dist, label, margin, inertia, counts, new = hp.kmeans_step(X, C0)
+    x = [[mp.mpf(float(v)) for v in row] for row in X]
+    c = [[mp.mpf(float(v)) for v in row] for row in C0]
+    D2 = [[sum((x[i][j] - c[k][j]) ** 2 for j in range(d)) for k in range(K)] for i in range(n)]
+    want_label = [min(range(K), key=lambda k: D2[i][k]) for i in range(n)]
+    assert list(label) == want_label
+    want_dist = [D2[i][want_label[i]] for i in range(n)]
+    want_margin = [min(D2[i][k] for k in range(K) if k != want_label[i]) - want_dist[i] for i in range(n)]
+    assert _mp_rel_err(dist, want_dist) <= MP_LIMIT
+    assert _mp_rel_err(margin, want_margin) <= MP_LIMIT
+    assert _mp_rel_err(inertia, sum(want_dist)) <= MP_LIMIT
+    assert list(counts) == [want_label.count(k) for k in range(K)] and min(counts) > 0
+    want_new = [[sum(x[i][j] for i in range(n) if want_label[i] == k) / int(counts[k]) for j in range(d)] for k in range(K)]
+    assert _mp_rel_err(new, want_new) <= MP_LIMIT
+    assert _mp_rel_err(hp.min_squared_distances(X, C0), want_dist) <= MP_LIMIT
+    # an empty cluster's centroid is the origin
+    far = np.vstack([C0, np.full((1, d), 1e3)])
+    out = hp.kmeans_step(X, far)
+    assert out[4][K] == 0 and not out[5][K].any()
+
+
+def test_moments_reference_against_50_digits():
+    import mpmath as mp
+    mp.mp.dps = 50
+    X, _, _, _ = _mp_problem(5, 2, 50, 21)
+    y = np.random.default_rng(22).standard_normal(50)
+    x = [[mp.mpf(float(v)) for v in row] for row in X]
+    mean = [sum(r[j] for r in x) / 50 for j in range(5)]
+    cov = [[sum((r[a] - mean[a]) * (r[b] - mean[b]) for r in x) / 49 for b in range(5)] for a in range(5)]
+    got_mean, got_cov = hp.sample_covariance(X)
+    assert _mp_rel_err(got_mean, mean) <= MP_LIMIT and _mp_rel_err(got_cov, cov) <= MP_LIMIT
+    xxt, xy = hp.xxt_xy(X, y)
+    assert _mp_rel_err(xxt, [[sum(r[a] * r[b] for r in x) for b in range(5)] for a in range(5)]) <= MP_LIMIT
+    assert _mp_rel_err(xy, [sum(r[a] * mp.mpf(float(v)) for r, v in zip(x, y)) for a in range(5)]) <= MP_LIMIT
+
+
+def test_conditioning_quantities():
+    shift = np.array([1.0, -2.0])
+    means = np.array([[4.0, -2.0], [1.0, 6.0]])
+    covs = np.stack([np.diag([0.25, 4.0]), np.diag([1.0, 16.0])])
+    c = hp.conditioning(shift, means, covs=covs)
+    assert np.allclose(c["ratio"], [36.0, 4.0]) and np.allclose(c["fold"], [6.0, 2.0]) and np.allclose(c["b2"], [36.0, 4.0])
+    assert np.allclose(c["kappa"], [4.0, 4.0])
+    v = hp.conditioning(shift, means, variances=np.array([[0.25, 4.0], [1.0, 16.0]]))
+    assert np.allclose(v["ratio"], [36.0, 4.0]) and np.allclose(v["b2"], [36.0, 4.0]) and np.allclose(v["kappa"], [4.0, 4.0])
+
+
+# ---- the oracle against the reference ------------------------------------------------------------------------------------
+
+# (d, K, N, offset of the data from the origin); N never a multiple of 64
+CASES = [(2, 3, 3001, 0.0), (3, 4, 3001, 5.0), (13, 5, 3001, 0.0), (16, 8, 4001, 0.0), (32, 16, 6001, 0.0), (33, 4, 3001, 0.0),
+         (64, 4, 3001, 3.0), (72, 2, 2501, 0.0), (128, 3, 2001, 0.0), (256, 2, 1501, 0.0), (8, 5, 3001, 40.0)]
+DIAG_CASES = [(4, 3, 3001, 0.0), (7, 40, 4001, 0.0), (16, 16, 4001, 2.0), (32, 8, 3001, 0.0)]
+
+
+def step_errors(got, ref, kappa, n):
+    """Per output: (error in section 4's norm, the unit sqrt(N_k) 2^-53 kappa_k it is bounded in), the worst component."""
+    n_k = n * np.asarray(ref[2], dtype=np.float64)
+    whole = np.sqrt(n) * hp.EPS64 * kappa.max()
+    out = {"ll": (abs(float((LD(got[0]) - ref[0]) / ref[0])), whole),
+           "resp": (hp.abs_err(got[1], ref[1]), whole),
+           "mixing": (hp.rel_err(got[2], ref[2]), whole)}
+    for name, i in (("means", 3), ("covs", 4)):
+        per = [(hp.rel_err(got[i][k], ref[i][k]), np.sqrt(n_k[k]) * hp.EPS64 * kappa[k]) for k in range(len(n_k))]
+        out[name] = max(per, key=lambda eu: eu[0] / eu[1])
+    return out
+
+
+def _oracle_case(d, K, n, offset, diagonal):
+    from oracle import oracle_ctypes as orc
+    X, pi0, mu0, S0 = problem(d, K, n, offset, diagonal)
+    ref = (hp.em_step_diag if diagonal else hp.em_step)(X, pi0, mu0, S0)
+    got = oracle_step(orc, X, pi0, mu0, S0, diagonal)
+    cond = hp.conditioning(X.mean(axis=0), mu0, **({"variances": S0} if diagonal else {"covs": S0}))
+    return step_errors(got, ref, cond["kappa"], n)
+
+
+@pytest.mark.parametrize("d,K,n,offset", CASES)
+def test_oracle_step_within_its_bound_of_the_reference(d, K, n, offset):
+    for name, (err, unit) in _oracle_case(d, K, n, offset, False).items():
+        print(f"d={d} K={K} N={n} offset={offset} {name}: err {err:.2e} = {err / unit:.3f} units of {unit:.2e}")
+        assert err <= C_ORACLE * unit, name
+
+
+@pytest.mark.parametrize("d,K,n,offset", DIAG_CASES)
+def test_oracle_diagonal_step_within_its_bound_of_the_reference(d, K, n, offset):
+    for name, (err, unit) in _oracle_case(d, K, n, offset, True).items():
+        print(f"diag d={d} K={K} N={n} offset={offset} {name}: err {err:.2e} = {err / unit:.3f} units of {unit:.2e}")
+        assert err <= C_ORACLE * unit, name
+
+
+def test_oracle_kmeans_step_against_the_reference():
+    from oracle import oracle_ctypes as orc
+    for d, K, n in KMEANS_SHAPES:
+        X, _, C0, _ = problem(d, K, n, 2.0)
+        dist, label, margin, inertia, counts, new = hp.kmeans_step(X, C0)
+        km = orc.KMeans(K)
+        km.set_centroids(C0, n)
+        km.assignment_step(X)
+        safe = margin > 64 * hp.EPS64 * dist
+        print(f"K-means d={d} K={K} N={n}: {int((~safe).sum())} rows within 64 * 2^-53 * dist of a tie")
+        assert safe.mean() >= 0.999 and np.array_equal(km.labels[safe], label[safe])
+        assert abs(float((LD(km.inertia) - inertia) / inertia)) <= np.sqrt(n) * hp.EPS64
+        km.update_step(X)
+        if safe.all():                                    # (the same labels, so the same sums: N_k terms each, kappa = 1)
+            assert hp.rel_err(km.centroids, new) <= C_ORACLE * np.sqrt(counts.max()) * hp.EPS64
+
+@pytest.mark.parametrize("d,diagonal,reach", [(16, False, 0.9 * 64), (32, False, 0.9 * 64), (16, False, 1.1 * 64), (32, False, 1.1 * 64),
+                                              (16, True, 64 * 0.9 ** 0.5), (16, True, 64 * 1.1 ** 0.5)])
+def test_edge_problems_sit_at_their_guard_with_overlapping_components(d, diagonal, reach):
+    """The guard sweeps of tests/test_gpu_hp_error.py mean something only if the guarded quantity is where it is meant to be AND
+    the outputs depend on the density form: hundreds of rows with responsibilities strictly inside (0, 1)."""
+    X, pi0, mu0, S0 = edge_problem(d, reach, diagonal)
+    cond = hp.conditioning(X.astype(LD).mean(axis=0), mu0, **({"variances": S0} if diagonal else {"covs": S0}))
+    achieved = np.sqrt(cond["b2"].max()) if diagonal else cond["fold"].max()
+    assert abs(achieved / reach - 1) < 1e-6, (achieved, reach)
+    resp = (hp.em_step_diag if diagonal else hp.em_step)(X, pi0, mu0, S0)[1].astype(np.float64)
+    assert (((resp > 1e-3) & (resp < 1 - 1e-3)).any(axis=1)).sum() >= 500
+
+
+def test_refinement_problems_reach_their_ratio():
+    for d in (4, 32):
+        for target in (5e3, 9e3, 1.1e4):
+            X, pi0, mu0, S0 = refinement_problem(d, target)
+            ref = hp.em_step(X, pi0, mu0, S0)
+            ratio = hp.conditioning(X.astype(LD).mean(axis=0), ref[3], covs=ref[4])["ratio"]
+            assert abs(ratio.max() / target - 1) < 0.02, (d, target, ratio)
+
+
+# ---- the comparison helper ------------------------------------------------------------------------------------------------
+
+def test_comparison_helper_tells_a_lost_digit_from_rounding_noise():
+    rng = np.random.default_rng(5)
+    ref = (rng.standard_normal((7, 9)) + 3).astype(LD) * (1 + LD(2) ** -60)
+    limit = 8 * hp.EPS64
+    noisy = (ref * (1 + hp.EPS64 * rng.uniform(-1, 1, ref.shape))).astype(np.float64)
+    assert not hp.over_limit(noisy, ref, limit)
+    assert not hp.over_limit(ref.astype(np.float64), ref, limit)
+    wrong = ref.astype(np.float64)
+    worst = np.unravel_index(np.abs(ref).argmax(), ref.shape)
+    wrong[worst] *= 1 + 1e-12
+    assert hp.over_limit(wrong, ref, limit)
+    for entry in [(0, 0), (6, 8), (3, 4)]:
+        wrong = ref.astype(np.float64)
+        wrong[entry] += 1e-12 * float(np.abs(ref).max())          # (the norm is relative to the largest entry)
+        assert hp.over_limit(wrong, ref, limit), entry
+    broken = ref.astype(np.float64)
+    broken[2, 2] = np.nan
+    assert hp.over_limit(broken, ref, limit) and hp.over_limit(ref[:, :8].astype(np.float64), ref, limit)
+    assert hp.over_limit(np.array([1e-12]), np.array([0.0], LD), 1e-13, absolute=True)
+    assert not hp.over_limit(np.array([1e-14]), np.array([0.0], LD), 1e-13, absolute=True)
+
+
+if __name__ == "__main__":
+    import time
+    for diagonal, cases in ((False, CASES), (True, DIAG_CASES)):
+        for case in cases:
+            t = time.time()
+            res = _oracle_case(*case, diagonal)
+            print(("diag " if diagonal else "full ") + str(case), "%.1fs" % (time.time() - t),
+                  " ".join(f"{k} {e:.1e} ({e / u:.3f})" for k, (e, u) in res.items()), flush=True)
