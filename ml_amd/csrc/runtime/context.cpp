@@ -113,7 +113,7 @@ void destroy_single_context(mlhip_ctx* ctx)
     {
         std::lock_guard<std::mutex> lock(ctx->handles_m);
         for (mlhip_data* h : ctx->handles) {          // (handles that outlive their context: see mlhip_ctx::handles)
-            h->attach_pool(nullptr);
+            h->pool = nullptr;
             h->ctx = nullptr;
         }
         ctx->handles.clear();

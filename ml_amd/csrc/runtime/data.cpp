@@ -35,7 +35,6 @@ void finish_upload(mlhip_data* dt)
     std::vector<double> v(dt->d + 1);
     HIP_CHECK(hipMemcpyAsync(v.data(), sums.p, sizeof(double) * dt->d, hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
-    scratch.release(); sums.release();
     v[dt->d] = (double)dt->n;
     ctx->allreduce_host(v.data(), v.size());
     dt->n_global = (uint64_t)std::llround(v[dt->d]);
@@ -61,7 +60,7 @@ mlhip_data* upload_common(mlhip_ctx* ctx, const double* x, bool on_device, uint3
     auto* dt = new mlhip_data;
     try {
         dt->ctx = ctx;
-        dt->attach_pool(&ctx->pool);
+        dt->pool = &ctx->pool;
         dt->d = (int)d;
         dt->D = D;
         dt->n = (uint32_t)n;
@@ -226,12 +225,10 @@ int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, doub
         if (ctx && ctx->group) { grp::sample_covariance(ctx, data, mean, covariance); return; }
         check_em_args(ctx, data, 1);
         require(covariance, "null argument");
-        const int saved_K = data->em_K;
-        (void)saved_K;
         // K = 1, r = 1: S_0 = sum_i xt_i xt_i^T about the global mean. The E-step workspace for another K is
         // left untouched only if K == 1; otherwise it is rebuilt on the next E-step.
         ensure_em_workspace(data, 1);
-        data->have_estep = false;
+        data->estep.invalidate();
         launch_fill_responsibilities(nullptr, data->n, 1, data->lw.as<double>(), data->ldr, ctx->stream);
         run_mstats(data, em_route(data, 1, false), 1, kFromResp, data->lw.as<double>(), data->ldr, false);
         const double* s = data->stats_host.as<double>();
@@ -257,7 +254,7 @@ int mlhip_xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt,
         check_em_args(ctx, data, 2);
         require((y || data->n == 0) && xxt && xy, "null argument");
         ensure_em_workspace(data, 2);
-        data->have_estep = false;
+        data->estep.invalidate();
         // weight rows: [0] = 1 (valid samples), [1] = y; the statistics kernel then yields, about the shift s,
         //   component 0: N, sum (x - s), sum (x - s)(x - s)^T      component 1: sum y, sum y (x - s)
         double* w = data->lw.as<double>();
@@ -293,8 +290,7 @@ int mlhip_random_partition_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, c
         require(offsets[0] == 0 && offsets[K] == data->n, "offsets must cover this rank's rows");
         for (uint32_t k = 0; k < K; ++k) require(offsets[k] <= offsets[k + 1], "offsets must ascend");
         const int d = data->d;
-        DevBuf order_dev, small;   // released below (one initialisation per fit: no point in keeping them)
-        struct Release { DevBuf& a; DevBuf& b; ~Release() { a.release(); b.release(); } } release{order_dev, small};
+        DevBuf order_dev, small;   // (one initialisation per fit: no point in keeping them)
         const size_t off_bytes = ((sizeof(uint32_t) * (K + 1) + 15) / 16) * 16;
         const size_t mean_doubles = (size_t)K * d;
         order_dev.reserve(std::max<size_t>(16, sizeof(uint32_t) * data->n));

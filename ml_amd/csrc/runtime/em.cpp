@@ -9,7 +9,7 @@ void ensure_em_workspace(mlhip_data* dt, int K)
 {
     mlhip_ctx* ctx = dt->ctx;
     if (dt->em_K == K) return;
-    dt->have_estep = false;
+    dt->estep.invalidate();
     dt->ldr = dt->n_pad;
     dt->lw.reserve(sizeof(double) * dt->ldr * K);
     dt->lse.reserve(sizeof(double) * dt->n_pad);
@@ -26,12 +26,13 @@ void ensure_em_workspace(mlhip_data* dt, int K)
 }
 
 
-/// Builds the per-component records for the route's E-step kernel and uploads them to params_dev.
-void prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs, DevBuf* target)
+/// Builds the per-component records for the route's E-step kernel and uploads them to params_dev (or `target`).
+RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs, DevBuf* target)
 {
     mlhip_ctx* ctx = dt->ctx;
     ensure_em_workspace(dt, K);
-    if (!target) target = &dt->params_dev;
+    const bool own = !target;
+    if (own) target = &dt->params_dev;
     {   // (params_dev / params_next are swapped by mlhip_em_iterate and may have been sized for diagonal records)
         size_t ps = (size_t)estep_param_stride(dt->D) * K * sizeof(double);
         if (estep_mfma4_supported(dt->D)) ps = std::max(ps, (size_t)estep_mfma4_param_stride(dt->D) * K * sizeof(double));
@@ -40,7 +41,7 @@ void prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing
     }
     // d in 12..128: 4x4-block triangular matrix-core kernel (mfma4); below, and where the route asks for it, the scalar-fed one.
     const bool use_mfma4 = r.estep == Estep::kMatrix4;
-    dt->estep_fold = false;
+    RecordForm form{use_mfma4 ? 2 : 0, false};
     // d > 64: the K factorizations on the device (em_close_big.hip launch_em_records_big -- the closing arithmetic's kernels, started
     // from the given covariances; the host's operations in the host's order, so the records are the host builders' except through
     // log()). On the host they were 60 ms at d = 1024, K = 4 -- once per fit, but a short fit is a few iterations.
@@ -55,7 +56,7 @@ void prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing
         HIP_CHECK(hipMemcpyAsync(area + K + (size_t)K * d, covs, sizeof(double) * K * d * d, hipMemcpyHostToDevice, ctx->stream));
         CloseArgs ca{};
         ca.K = K; ca.d = d; ca.D = dt->D; ca.shift = dt->shift_dev.as<double>();
-        ca.layout = use_mfma4 ? 2 : 0;
+        ca.layout = form.layout;
         ca.mixing = area; ca.means = area + K; ca.covs = area + K + (size_t)K * d;
         ca.records = target->as<double>();
         ca.info = area + n_par;
@@ -66,8 +67,8 @@ void prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing
     } else if (use_mfma4) {
         // FOLD form (no per-component mean subtraction in the kernel) while every |W_k (mu_k - shift)| is small enough for
         // the parity tolerances; the exact form otherwise. Every rank decides from the same parameters.
-        dt->estep_fold = host::build_estep_params_mfma4(dt->d, dt->D, K, mixing, means, covs, r.fold_allowed ? dt->shift.data() : nullptr,
-                                                        kEstepFoldLimit, dt->params_host.as<double>());
+        form.fold = host::build_estep_params_mfma4(dt->d, dt->D, K, mixing, means, covs, r.fold_allowed ? dt->shift.data() : nullptr,
+                                                   kEstepFoldLimit, dt->params_host.as<double>());
         HIP_CHECK(hipMemcpyAsync(target->p, dt->params_host.p, sizeof(double) * estep_mfma4_param_stride(dt->D) * K,
                                  hipMemcpyHostToDevice, ctx->stream));
     } else {
@@ -75,7 +76,8 @@ void prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing
         HIP_CHECK(hipMemcpyAsync(target->p, dt->params_host.p, sizeof(double) * estep_param_stride(dt->D) * K,
                                  hipMemcpyHostToDevice, ctx->stream));
     }
-    dt->estep_variant = use_mfma4 ? 2 : 0;
+    if (own) dt->estep.records_are(form.layout, form.fold);
+    return form;
 }
 
 
@@ -89,26 +91,23 @@ void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const 
     a.params = (records ? records : &dt->params_dev)->as<double>(); a.K = K;
     a.lw = dt->lw.as<double>(); a.ldr = dt->ldr; a.lse = dt->lse.as<double>();
     a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
-    a.shift = dt->shift_dev.as<double>(); a.fold = (fold < 0 ? dt->estep_fold : fold != 0) ? 1 : 0;
-    a.with_lse = (with_lse || dt->estep_variant != 2) ? 1 : 0;
+    a.shift = dt->shift_dev.as<double>(); a.fold = (fold < 0 ? dt->estep.rec_fold : fold != 0) ? 1 : 0;
+    a.with_lse = (with_lse || dt->estep.rec_layout != 2) ? 1 : 0;
     a.num_cus = ctx->num_cus;
     a.scratch = dt->partials.as<double>(); a.scratch_doubles = dt->partials.bytes / sizeof(double);   // (written by the statistics kernel AFTER the E-step, on the same stream)
     a.plain = r.estep == Estep::kPlain;
     int grid = 0;
     ctx->timed("em_estep", [&] {
-        grid = dt->estep_variant == 2 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
+        grid = dt->estep.rec_layout == 2 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
     });
     if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
     HIP_CHECK(hipGetLastError());
-    dt->n_ll = grid;
-    dt->have_estep = true;
-    dt->lw_valid = true;
+    dt->estep.block_written(grid);
 }
 
 
 void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs, bool with_lse)
 {
-    dt->diag_step = false;
     prepare_estep(dt, r, K, mixing, means, covs);
     launch_estep(dt, r, K, with_lse);
 }
@@ -118,15 +117,14 @@ void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, co
 /// responsibilities, a separate M-step, the refinement pass) gets it rebuilt from the same parameter records.
 void ensure_lw(mlhip_data* dt, const EmRoute& r, int K)
 {
-    if (!dt->have_estep || dt->lw_valid) return;
-    if (dt->diag_step) {
+    if (!dt->estep.needs_rebuild()) return;
+    if (dt->estep.diagonal()) {
         // params_dev holds diagonal records: expand the same parameters to full (diagonal) covariances for the E-step kernel
         const int d = dt->d;
         std::vector<double> covs((size_t)K * d * d, 0.0);
         for (int k = 0; k < K; ++k)
-            for (int j = 0; j < d; ++j) covs[(size_t)k * d * d + (size_t)j * d + j] = dt->diag_vars[(size_t)k * d + j];
-        prepare_estep(dt, r, K, dt->diag_mixing.data(), dt->diag_means.data(), covs.data());
-        dt->diag_step = false;
+            for (int j = 0; j < d; ++j) covs[(size_t)k * d * d + (size_t)j * d + j] = dt->estep.diag_vars[(size_t)k * d + j];
+        prepare_estep(dt, r, K, dt->estep.diag_mixing.data(), dt->estep.diag_means.data(), covs.data());
     }
     launch_estep(dt, r, K);
 }
@@ -137,15 +135,29 @@ void collect_stats(mlhip_data* dt, int K, size_t count)
 {
     mlhip_ctx* ctx = dt->ctx;
     if (!count) count = (size_t)K * stats_count(dt->d) + 1;
-    if (ctx->reduce_fn && ctx->reduce_on_device) {
-        ctx->reduce_device(dt->stats_dev.as<double>(), count);
-    }
-    HIP_CHECK(hipMemcpyAsync(dt->stats_host.p, dt->stats_dev.p, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-    if (ctx->reduce_fn && !ctx->reduce_on_device) {
-        if (ctx->reduce_fn(ctx->reduce_user, dt->stats_host.as<double>(), count, 0, ctx->stream) != 0)
-            throw hook_failure();
-    }
+    ctx->reduce_to_host(dt->stats_host.as<double>(), dt->stats_dev.as<double>(), count);
+}
+
+
+FusedArgs fused_args(const mlhip_data* dt, const EmRoute& r, int K, const DevBuf* records)
+{
+    FusedArgs a{};
+    a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.d = dt->d;
+    a.shift = dt->shift_dev.as<double>(); a.params = records->as<double>(); a.K = K;
+    a.lse = dt->lse.as<double>();
+    a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
+    a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
+    a.form = r.fused_form;
+    return a;
+}
+
+
+/// What a fused pass (em_fused_small.hip, or the resident loop that runs the same pass) leaves behind: lse and `grid` log-likelihood
+/// partials, no N x K block; a refinement pass reads the block ensure_lw rebuilds.
+void fused_pass_done(mlhip_data* dt, int grid)
+{
+    dt->estep.records_only(grid);
+    dt->estep.stats_from(kFromLogResp, dt->lw.as<double>(), dt->ldr);
 }
 
 
@@ -154,25 +166,14 @@ void collect_stats(mlhip_data* dt, int K, size_t count)
 void launch_fused_step(mlhip_data* dt, const EmRoute& r, int K, bool collect, const DevBuf* records)
 {
     mlhip_ctx* ctx = dt->ctx;
-    FusedArgs a{};
-    a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.d = dt->d;
-    a.shift = dt->shift_dev.as<double>(); a.params = (records ? records : &dt->params_dev)->as<double>(); a.K = K;
-    a.lse = dt->lse.as<double>();
-    a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
-    a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
-    a.form = r.fused_form;
+    const FusedArgs a = fused_args(dt, r, K, records ? records : &dt->params_dev);
     int grid = 0;
     ctx->timed("em_fused", [&] { grid = mstats::launch_em_fused_small(a, ctx->num_cus, ctx->stream); });
     if (grid <= 0) throw std::runtime_error("fused EM kernel launch failed");
     launch_em_reduce_blocks(a.partials, grid, mstats::em_fused_partial_rows(K), mstats::em_fused_partial_cols(dt->d), K,
                             stats_count(dt->d), a.ll_partials, grid, dt->stats_dev.as<double>(), ctx->stream);
     HIP_CHECK(hipGetLastError());
-    dt->n_ll = grid;
-    dt->have_estep = true;
-    dt->lw_valid = false;
-    dt->stats_mode = kFromLogResp;
-    dt->stats_resp = dt->lw.as<double>();
-    dt->stats_ld = dt->ldr;
+    fused_pass_done(dt, grid);
     if (collect) collect_stats(dt, K);
 }
 
@@ -180,10 +181,25 @@ void launch_fused_step(mlhip_data* dt, const EmRoute& r, int K, bool collect, co
 bool run_fused_step(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs)
 {
     if (!r.fused) return false;
-    dt->diag_step = false;
     prepare_estep(dt, r, K, mixing, means, covs);
     launch_fused_step(dt, r, K, true);
     return true;
+}
+
+
+/// The statistics kernels' arguments for `K` columns of `resp` (log-responsibilities or responsibilities, by `mode`) about `shift`.
+static MstatsArgs mstats_args(const mlhip_data* dt, const EmRoute& r, int K, int mode, const double* shift, const double* resp, size_t ld,
+                              double* stats)
+{
+    MstatsArgs a{};
+    a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.d = dt->d;
+    a.shift = shift;
+    a.lw = resp; a.ldr = ld; a.lse = dt->lse.as<double>();
+    a.K = K; a.mode = mode;
+    a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
+    a.stats = stats;
+    a.plain = r.stats_plain(dt->d);
+    return a;
 }
 
 
@@ -193,27 +209,17 @@ void run_mstats(mlhip_data* dt, const EmRoute& r, int K, int mode, const double*
 {
     mlhip_ctx* ctx = dt->ctx;
     ensure_em_workspace(dt, K);
-    MstatsArgs a{};
-    a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.d = dt->d;
-    a.shift = dt->shift_dev.as<double>();
-    a.lw = (mode == kFromResp) ? resp_dev : dt->lw.as<double>();
-    a.ldr = (mode == kFromResp) ? ld_resp : dt->ldr;
-    a.lse = dt->lse.as<double>();
-    a.K = K; a.mode = mode;
-    a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
+    MstatsArgs a = mstats_args(dt, r, K, mode, dt->shift_dev.as<double>(), mode == kFromResp ? resp_dev : dt->lw.as<double>(),
+                               mode == kFromResp ? ld_resp : dt->ldr, dt->stats_dev.as<double>());
     a.ll_partials = with_ll ? dt->ll_partials.as<double>() : nullptr;
-    a.n_ll_partials = with_ll ? dt->n_ll : 0;
-    a.stats = dt->stats_dev.as<double>();
+    a.n_ll_partials = with_ll ? dt->estep.n_ll : 0;
     a.lse_out = dt->lse.as<double>(); a.ll_scratch = dt->ll_partials.as<double>();
-    a.plain = r.stats_plain(dt->d);
     if (mode == kFromLogRespSelfNorm) {
         dt->esum.reserve(sizeof(double) * dt->n_pad);
         a.ll_out = dt->esum.as<double>();
     }
     // after a self-normalising pass lse is in HBM like after an LSE-writing E-step: a refinement pass reads it
-    dt->stats_mode = mode == kFromLogRespSelfNorm ? (int)kFromLogResp : mode;
-    dt->stats_resp = a.lw;
-    dt->stats_ld = a.ldr;
+    dt->estep.stats_from(mode == kFromLogRespSelfNorm ? (int)kFromLogResp : mode, a.lw, a.ldr);
     int rc = 0;
     if (mode == kFromLogRespSelfNorm) {
         const bool sparse = mstats_sparse_applies(dt, r, K);
@@ -281,34 +287,20 @@ void refine_component(mlhip_data* dt, const EmRoute& r, int k, double* mean_k, d
 {
     mlhip_ctx* ctx = dt->ctx;
     const int d = dt->d, F = stats_count(d);
-    if (dt->stats_mode == kFromLogResp) ensure_lw(dt, r, dt->em_K);   // after a fused step the block is not in HBM yet
+    const EstepState& st = dt->estep;
+    if (st.stats_mode == kFromLogResp) ensure_lw(dt, r, dt->em_K);   // after a fused step the block is not in HBM yet
     dt->refine_shift.reserve(sizeof(double) * d);
     dt->refine_stats.reserve(sizeof(double) * (F + 1));
     HIP_CHECK(hipMemcpyAsync(dt->refine_shift.p, mean_k, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
-    MstatsArgs a{};
-    a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.d = d;
-    a.shift = dt->refine_shift.as<double>();
-    a.lw = dt->stats_resp + (size_t)k * dt->stats_ld; a.ldr = dt->stats_ld; a.lse = dt->lse.as<double>();
-    a.K = 1; a.mode = dt->stats_mode;
-    a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
-    a.ll_partials = nullptr; a.n_ll_partials = 0;
-    a.stats = dt->refine_stats.as<double>();
-    a.plain = r.stats_plain(d);
+    const MstatsArgs a = mstats_args(dt, r, 1, st.stats_mode, dt->refine_shift.as<double>(), st.stats_resp + (size_t)k * st.stats_ld,
+                                     st.stats_ld, dt->refine_stats.as<double>());
     int rc = 0;
     ctx->timed("em_refine", [&] { rc = launch_em_mstats(a, ctx->num_cus, ctx->stream); });
     if (rc <= 0) throw std::runtime_error("statistics kernel launch failed (refinement pass)");
     launch_em_reduce(a, ctx->num_cus, rc, ctx->stream);
     HIP_CHECK(hipGetLastError());
     std::vector<double> s((size_t)F);
-    if (ctx->reduce_fn && ctx->reduce_on_device) {
-        if (ctx->reduce_fn(ctx->reduce_user, dt->refine_stats.as<double>(), (size_t)F, 1, ctx->stream) != 0)
-            throw hook_failure();
-    }
-    HIP_CHECK(hipMemcpyAsync(s.data(), dt->refine_stats.p, sizeof(double) * F, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-    if (ctx->reduce_fn && !ctx->reduce_on_device) {
-        if (ctx->reduce_fn(ctx->reduce_user, s.data(), (size_t)F, 0, ctx->stream) != 0) throw hook_failure();
-    }
+    ctx->reduce_to_host(s.data(), dt->refine_stats.as<double>(), (size_t)F);
     const double s0 = s[stats_index(d, d)];
     std::vector<double> m(d);
     for (int a2 = 0; a2 < d; ++a2) m[a2] = s[stats_index(d, a2)] / s0;          // ~0: the shift is the mean already
@@ -322,7 +314,6 @@ void refine_component(mlhip_data* dt, const EmRoute& r, int k, double* mean_k, d
         cov_k[a2 * d + a2] += 1e-15;                                            // ML/EM.cpp:252
         mean_k[a2] += m[a2];
     }
-    dt->refined_components += 1;
 }
 
 
@@ -368,7 +359,7 @@ void run_diag_kernel(mlhip_data* dt, const EmRoute& r, int K, const double* shif
     launch_em_reduce_blocks(a.partials, grid, mstats::em_diag_partial_rows(K), mstats::em_diag_partial_cols(dt->d), K,
                             diag_stats_count(dt->d), a.ll_partials, grid, dt->stats_dev.as<double>(), ctx->stream);
     HIP_CHECK(hipGetLastError());
-    dt->n_ll = grid;
+    dt->estep.diag_records_only(grid);
     if (collect) collect_stats(dt, K, (size_t)K * diag_stats_count(dt->d) + 1);
 }
 
@@ -415,24 +406,6 @@ void em_step_full(mlhip_data* data, const EmRoute& r, int K, const double* mixin
 }
 
 
-/// Sums `count` doubles at the head of stats_dev across ranks, whatever kind of hook is installed (device buffer on the
-/// stream, or a host buffer: down, hook, up). No-op on a single rank.
-void allreduce_stats_dev(mlhip_data* dt, size_t count)
-{
-    mlhip_ctx* ctx = dt->ctx;
-    if (!ctx->reduce_fn) return;
-    if (ctx->reduce_on_device) {
-        ctx->reduce_device(dt->stats_dev.as<double>(), count);
-        return;
-    }
-    HIP_CHECK(hipMemcpyAsync(dt->stats_host.p, dt->stats_dev.p, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-    if (ctx->reduce_fn(ctx->reduce_user, dt->stats_host.as<double>(), count, 0, ctx->stream) != 0)
-        throw hook_failure();
-    HIP_CHECK(hipMemcpyAsync(dt->stats_dev.p, dt->stats_host.p, sizeof(double) * count, hipMemcpyHostToDevice, ctx->stream));
-}
-
-
 /// Records of a diagonal-covariance parameter set -> `target` (padded to whole 16-component row blocks with neutral records).
 void upload_diag_records(mlhip_data* data, int K, const double* mixing, const double* means, const double* variances, DevBuf& target)
 {
@@ -476,7 +449,6 @@ void refine_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixing
             variances_out[(size_t)k * d + a] = (s[d + a] - s[a] * m) / s0 + 1e-15;
             means_out[(size_t)k * d + a] += m;
         }
-        data->refined_components += 1;
     }
 }
 
@@ -500,14 +472,9 @@ void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixin
     }
     ensure_em_workspace(data, K);
     // keep the input parameters: labels / responsibilities are produced from them on demand (ensure_lw)
-    data->diag_mixing.assign(mixing, mixing + K);
-    data->diag_means.assign(means, means + (size_t)K * d);
-    data->diag_vars.assign(variances, variances + (size_t)K * d);
+    data->estep.diag_parameters(K, d, mixing, means, variances);
     upload_diag_records(data, K, mixing, means, variances, data->params_dev);
     run_diag_kernel(data, r, K, data->shift_dev.as<double>());
-    data->have_estep = true;
-    data->lw_valid = false;
-    data->diag_step = true;
     const int F = diag_stats_count(d);
     const double* st = data->stats_host.as<double>();
     *log_likelihood = st[(size_t)K * F] / (double)data->n_global - (double)d * log_two_pi() / 2;   // ML/EM.cpp:197-198, 211
@@ -530,7 +497,7 @@ int mlhip_em_expectation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const dou
         require(mixing && means && covariances && log_likelihood, "null argument");
         run_estep(data, em_route(data, (int)K, false), (int)K, mixing, means, covariances);
         double* slot = data->stats_dev.as<double>() + (size_t)K * stats_count(data->d);
-        launch_ll_reduce(data->ll_partials.as<double>(), data->n_ll, slot, ctx->stream);
+        launch_ll_reduce(data->ll_partials.as<double>(), data->estep.n_ll, slot, ctx->stream);
         HIP_CHECK(hipGetLastError());
         double* host_slot = data->stats_host.as<double>() + (size_t)K * stats_count(data->d);
         HIP_CHECK(hipMemcpyAsync(host_slot, slot, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -547,7 +514,7 @@ int mlhip_em_maximisation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* 
         if (ctx && ctx->group) { grp::em_maximisation(ctx, data, K, 0, nullptr, 0, nullptr, mixing_out, means_out, covariances_out); return; }
         check_em_args(ctx, data, K);
         require(mixing_out && means_out && covariances_out, "null argument");
-        require(data->have_estep && data->em_K == (int)K, "no E-step results on the device for this K");
+        require(data->has_estep_results((int)K), "no E-step results on the device for this K");
         const EmRoute r = em_route(data, (int)K, false);
         ensure_lw(data, r, (int)K);
         run_mstats(data, r, (int)K, kFromLogResp, nullptr, 0, true);
@@ -642,7 +609,7 @@ int mlhip_em_maximisation_from_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t
         if (data->n)
             HIP_CHECK(hipMemcpyAsync(data->labels_dev.p, labels, sizeof(uint32_t) * data->n, hipMemcpyHostToDevice, ctx->stream));
         // One-hot responsibilities are materialised in the (still unused) log-responsibility buffer of the workspace.
-        data->have_estep = false;
+        data->estep.invalidate();
         launch_fill_responsibilities(data->labels_dev.as<uint32_t>(), data->n, (int)K, data->lw.as<double>(), data->ldr, ctx->stream);
         const EmRoute r = em_route(data, (int)K, false);
         run_mstats(data, r, (int)K, kFromResp, data->lw.as<double>(), data->ldr, false);
@@ -659,7 +626,7 @@ int mlhip_em_responsibilities_rows(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
         require(first_row <= data->n && n_rows <= data->n - first_row, "row range beyond this block");
         require(resp || n_rows == 0, "null argument");
         require(ldr >= (int64_t)n_rows, "ldr must be >= the number of rows");
-        require(data->have_estep && data->em_K == (int)K, "no E-step results on the device for this K");
+        require(data->has_estep_results((int)K), "no E-step results on the device for this K");
         if (!n_rows) return;
         ensure_lw(data, em_route(data, (int)K, false), (int)K);
         const size_t ldo = (size_t)padded_samples(n_rows);
@@ -687,7 +654,7 @@ int mlhip_em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labe
         if (ctx && ctx->group) { grp::em_labels(ctx, data, K, labels); return; }
         check_em_args(ctx, data, K);
         require(labels || data->n == 0, "null argument");
-        require(data->have_estep && data->em_K == (int)K, "no E-step results on the device for this K");
+        require(data->has_estep_results((int)K), "no E-step results on the device for this K");
         ensure_lw(data, em_route(data, (int)K, false), (int)K);
         data->labels_dev.reserve(sizeof(uint32_t) * data->n_pad);
         RespArgs a{data->lw.as<double>(), data->ldr, data->lse.as<double>(), data->n, (int)K, nullptr, 0,

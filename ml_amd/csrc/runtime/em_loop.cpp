@@ -54,6 +54,7 @@ struct EmLoop {
     double refine_limit = 0;
     // ---- ring: slot s holds the records R_i of every iteration i with i % 3 == s, pack s the parameters P_i
     DevBuf* rec[3] = {nullptr, nullptr, nullptr};
+    int layout = 0;                             // record layout of every slot (CloseArgs::layout codes): fixed for the fit
     bool fold[3] = {false, false, false};       // matrix-core E-step: whether the records of a slot are evaluated in FOLD form
     std::vector<double> shadow[3];              // diagonal mode: host copy of P_i (ensure_lw rebuilds the block from an E-step's inputs)
     uint32_t launched = 0;                      // iterations launched so far
@@ -75,7 +76,7 @@ struct EmLoop {
         ensure_em_workspace(data, K);
         if (!route.device_close) return false;
         if (!diag) {
-            prepare_estep(data, route, K, mixing, means, covs);    // -> params_dev, estep_variant, estep_fold
+            prepare_estep(data, route, K, mixing, means, covs);    // -> params_dev and its descriptor
         }
         n_cov = diag ? (size_t)K * d : (size_t)K * d * d;
         F = diag ? diag_stats_count(d) : stats_count(d);
@@ -97,18 +98,18 @@ struct EmLoop {
             rec[1]->reserve(rec[0]->bytes);
             rec[2]->reserve(rec[0]->bytes);
         }
-        data->diag_step = diag;
         fused = !diag && route.fused;
         self_norm = !diag && route.self_norm;
         // Single rank, a shape of the vector-unit E+M form with at most one workgroup per CU: the whole loop in one launch.
         resident_grid = 0;
         if (!diag && route.resident) {
-            const FusedArgs fa = fused_args(rec[0]);
+            const FusedArgs fa = fused_args(data, route, K, rec[0]);
             const int g = mstats::em_fused_valu_small_grid(fa, ctx->num_cus);
             if (g > 0 && mstats::em_resident_supported(d, K, g, ctx->num_cus)) resident_grid = g;
         }
         refine_limit = refine_ratio();
-        fold[0] = data->estep_fold;
+        layout = data->estep.rec_layout;
+        fold[0] = data->estep.rec_fold;
         return true;
     }
 
@@ -125,13 +126,11 @@ struct EmLoop {
             launch_estep(data, route, K, !self_norm, rec[in], fold[in] ? 1 : 0);
             run_mstats(data, route, K, self_norm ? kFromLogRespSelfNorm : kFromLogResp, nullptr, 0, true, false);
         }
-        data->have_estep = true;
-        data->lw_valid = !(diag || fused);
-        allreduce_stats_dev(data, (size_t)K * F + 1);
+        ctx->reduce_in_place(data->stats_dev.as<double>(), data->stats_host.as<double>(), (size_t)K * F + 1);
         CloseArgs ca{};
         ca.stats = data->stats_dev.as<double>(); ca.K = K; ca.d = d; ca.D = data->D;
         ca.shift = data->shift_dev.as<double>(); ca.n_global = (double)data->n_global;
-        ca.layout = data->estep_variant; ca.refine_limit = refine_limit;
+        ca.layout = layout; ca.refine_limit = refine_limit;
         ca.mixing = pack_mixing(out); ca.means = pack_means(out); ca.covs = pack_covs(out);
         ca.records = rec[out]->as<double>();
         ca.info = data->it_info_slot[out].as<double>();
@@ -140,19 +139,6 @@ struct EmLoop {
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(data->it_event[out], ctx->stream));
         launched = i + 1;
-    }
-
-    /// The fused kernel's arguments on the records of `records` (launch_fused_step builds the same).
-    FusedArgs fused_args(const DevBuf* records) const
-    {
-        FusedArgs a{};
-        a.xt = data->xt.as<double>(); a.ldx = data->ldx; a.n = data->n; a.d = d;
-        a.shift = data->shift_dev.as<double>(); a.params = records->as<double>(); a.K = K;
-        a.lse = data->lse.as<double>();
-        a.partials = data->partials.as<double>(); a.partials_capacity = data->partials.bytes / sizeof(double);
-        a.ll_partials = data->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
-        a.form = route.fused_form;
-        return a;
     }
 
     /// Resident policy (em_resident.hip): ONE launch runs the iterations 0 .. until the convergence test of ML/EM.cpp:161-168 fires
@@ -193,7 +179,6 @@ struct EmLoop {
             HIP_CHECK(hipMemsetAsync(stamps.p, 0, stamps.bytes, ctx->stream));
             a.profile = stamps.as<unsigned long long>();
         }
-        struct Release { DevBuf& b; ~Release() { b.release(); } } release_stamps{stamps};
         bool ok = false;
         ctx->timed("em_resident", [&] { ok = mstats::launch_em_resident(a, ctx->stream); });
         if (!ok) throw std::runtime_error("resident EM kernel not instantiated for this shape");
@@ -230,12 +215,7 @@ struct EmLoop {
             resident_gave_up = true;                                      // (the ring may hold later iterations' records by now)
             return false;
         }
-        data->n_ll = resident_grid;                                       // (what launch_fused_step leaves behind on the host side)
-        data->have_estep = true;
-        data->lw_valid = false;
-        data->stats_mode = kFromLogResp;
-        data->stats_resp = data->lw.as<double>();
-        data->stats_ld = data->ldr;
+        fused_pass_done(data, resident_grid);
         for (uint32_t i = 0; i < evaluated; ++i) {                        // the host's own test over the history: the same decisions
             const bool stopped = test(i, history[i]);
             if (stopped != (status == 1 && i + 1 == evaluated && result[2] != 0))
@@ -274,12 +254,12 @@ struct EmLoop {
     /// The records of ring slot `slot` become data->params_dev -- what the per-step functions (refinement pass, ensure_lw) read.
     void bring_to_params_dev(int slot)
     {
+        data->estep.records_are(layout, fold[slot]);
         if (rec[slot] == &data->params_dev) return;
         int j = 0;
         while (rec[j] != &data->params_dev) ++j;
         std::swap(*rec[slot], data->params_dev);            // the contents change places ...
         std::swap(rec[slot], rec[j]);                       // ... and the ring's names follow them
-        data->estep_fold = fold[slot];
     }
 
     /// Parameters P_slot -> the caller's arrays.
@@ -309,11 +289,9 @@ struct EmLoop {
             shadow[out].insert(shadow[out].end(), covs, covs + n_cov);
         } else {
             finalize_out(data, route, K, mixing, means, covs);
-            const int variant = data->estep_variant;
-            prepare_estep(data, route, K, mixing, means, covs, rec[out]);
-            fold[out] = data->estep_fold;
-            data->estep_fold = fold[in];                     // (still describes the records in params_dev)
-            if (data->estep_variant != variant) throw std::runtime_error("E-step record layout changed inside a fit");
+            const RecordForm form = prepare_estep(data, route, K, mixing, means, covs, rec[out]);
+            fold[out] = form.fold;
+            if (form.layout != layout) throw std::runtime_error("E-step record layout changed inside a fit");
         }
     }
 
@@ -322,13 +300,10 @@ struct EmLoop {
     void finish(uint32_t last)
     {
         bring_to_params_dev((int)(last % 3));
-        data->estep_fold = fold[last % 3];
-        if (launched > last + 1) data->lw_valid = false;
+        if (launched > last + 1) data->estep.block_overwritten();
         if (diag) {
-            const std::vector<double>& sh = shadow[last % 3];
-            data->diag_mixing.assign(sh.begin(), sh.begin() + K);
-            data->diag_means.assign(sh.begin() + K, sh.begin() + K + (size_t)K * d);
-            data->diag_vars.assign(sh.begin() + K + (size_t)K * d, sh.end());
+            const double* sh = shadow[last % 3].data();
+            data->estep.diag_parameters(K, d, sh, sh + K, sh + K + (size_t)K * d);
         }
     }
 
@@ -391,7 +366,7 @@ struct EmLoop {
                 latest_on_host = true;
             } else {
                 latest_on_host = false;
-                fold[(i + 1) % 3] = route.fold_allowed && data->estep_variant == 2 && v.cmax <= kEstepFoldLimit;   // (d <= 32)
+                fold[(i + 1) % 3] = route.fold_allowed && layout == 2 && v.cmax <= kEstepFoldLimit;   // (d <= 32)
             }
             last = i;
             if (test(i, v.ll)) break;

@@ -35,12 +35,6 @@ struct mlhip_group {
     std::vector<uint64_t> allreduces;   // per shard, counted for the hook above
 };
 
-namespace mlhip_rt {
-namespace {
-
-}  // namespace
-}  // namespace mlhip_rt
-
 /// SlotAllreduce's device operations: shard r's stream, the slots' buffers and events. (Slots on other GPUs are read through peer access.)
 struct mlhip_group::DeviceOps {
     mlhip_group* g;

@@ -119,50 +119,54 @@ struct BufferPool {
     }
 };
 
-/// Growable device buffer. `bytes` is what was asked for (the largest request so far: sizes derived from it -- grids, capacities --
-/// do not depend on which block the pool handed out), `cap` the block behind it.
-struct DevBuf {
+/// Growable device (hipMalloc) or pinned host (hipHostMalloc) buffer; its destructor releases the block. `bytes` is what was asked
+/// for (the largest request so far: sizes derived from it -- grids, capacities -- do not depend on which block the pool handed out),
+/// `cap` the block behind it. `pool` points at its owner's pool field (a data handle's mlhip_data::pool), read at every allocation
+/// and release: detaching a handle from its context is one store there. Null: straight from / to the driver (local scratch, the
+/// context's own buffers, a group's slots). Moving and swapping exchange the BLOCKS; a buffer stays with the pool it was declared with.
+template <bool Pinned> struct Buffer {
     void* p = nullptr;
     size_t bytes = 0, cap = 0;
-    BufferPool* pool = nullptr;
+    BufferPool* const* pool = nullptr;
+    Buffer() = default;
+    explicit Buffer(BufferPool* const* owner_pool) : pool(owner_pool) {}
+    Buffer(const Buffer&) = delete;
+    Buffer& operator=(const Buffer&) = delete;
+    Buffer(Buffer&& o) noexcept : p(o.p), bytes(o.bytes), cap(o.cap), pool(o.pool) { o.p = nullptr; o.bytes = o.cap = 0; }
+    Buffer& operator=(Buffer&& o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p; bytes = o.bytes; cap = o.cap;
+            o.p = nullptr; o.bytes = o.cap = 0;
+        }
+        return *this;
+    }
+    ~Buffer() { release(); }
     void reserve(size_t b)
     {
         if (b <= bytes) return;
         if (b <= cap) { bytes = b; return; }
         release();
-        const size_t want = pool && pool->enabled ? BufferPool::block_size(b) : b;
-        if (pool && pool->enabled) p = pool->take(false, want);
-        if (!p) HIP_CHECK(hipMalloc(&p, want));
+        BufferPool* from = pool ? *pool : nullptr;
+        const size_t want = from && from->enabled ? BufferPool::block_size(b) : b;
+        if (from && from->enabled) p = from->take(Pinned, want);
+        if (!p) {
+            if (Pinned) HIP_CHECK(hipHostMalloc(&p, want, hipHostMallocDefault));
+            else HIP_CHECK(hipMalloc(&p, want));
+        }
         bytes = b; cap = want;
     }
     void release()
     {
-        if (p && !(pool && pool->give(false, cap, p))) (void)hipFree(p);
+        BufferPool* to = pool ? *pool : nullptr;
+        if (p && !(to && to->give(Pinned, cap, p))) (void)(Pinned ? hipHostFree(p) : hipFree(p));
         p = nullptr; bytes = 0; cap = 0;
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
-struct PinnedBuf {
-    void* p = nullptr;
-    size_t bytes = 0, cap = 0;
-    BufferPool* pool = nullptr;
-    void reserve(size_t b)
-    {
-        if (b <= bytes) return;
-        if (b <= cap) { bytes = b; return; }
-        release();
-        const size_t want = pool && pool->enabled ? BufferPool::block_size(b) : b;
-        if (pool && pool->enabled) p = pool->take(true, want);
-        if (!p) HIP_CHECK(hipHostMalloc(&p, want, hipHostMallocDefault));
-        bytes = b; cap = want;
-    }
-    void release()
-    {
-        if (p && !(pool && pool->give(true, cap, p))) (void)hipHostFree(p);
-        p = nullptr; bytes = 0; cap = 0;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
+using DevBuf = Buffer<false>;
+using PinnedBuf = Buffer<true>;
 
 struct Timer {
     double total_ms = 0;
@@ -334,6 +338,12 @@ struct mlhip_ctx {
                                              " differs from rank 0): the statistics all-reduce did not give every rank the same sums");
     }
 
+    /// The installed hook on a HOST buffer.
+    void reduce_host(double* v, size_t count)
+    {
+        if (reduce_fn(reduce_user, v, count, 0, stream) != 0) throw hook_failure();
+    }
+
     /// Sum `count` host doubles across ranks (no-op single rank).
     void allreduce_host(double* v, size_t count)
     {
@@ -345,12 +355,87 @@ struct mlhip_ctx {
             HIP_CHECK(hipMemcpyAsync(v, small_dev.p, count * sizeof(double), hipMemcpyDeviceToHost, stream));
             sync();
         } else {
-            if (reduce_fn(reduce_user, v, count, 0, stream) != 0) throw hook_failure();
+            reduce_host(v, count);
         }
+    }
+
+    /// `count` doubles of a device buffer, summed across ranks, into a host buffer, in two halves (mlhip_kmeans_iterate runs its
+    /// closing kernel between them): the device hook on the stream ...
+    void reduce_on_stream(double* dev, size_t count)
+    {
+        if (reduce_fn && reduce_on_device) reduce_device(dev, count);
+    }
+    /// ... then down, wait, and the host hook where that is the installed kind. Single rank: the plain read-back.
+    void fetch_reduced(double* host, const double* dev, size_t count)
+    {
+        HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, stream));
+        sync();
+        if (reduce_fn && !reduce_on_device) reduce_host(host, count);
+    }
+    void reduce_to_host(double* host, double* dev, size_t count)
+    {
+        reduce_on_stream(dev, count);
+        fetch_reduced(host, dev, count);
+    }
+
+    /// `count` doubles of a device buffer summed across ranks in place, nothing waits with a device hook; a host hook goes down
+    /// through `stage` (pinned), and up again. No-op on a single rank.
+    void reduce_in_place(double* dev, double* stage, size_t count)
+    {
+        if (!reduce_fn) return;
+        if (reduce_on_device) { reduce_device(dev, count); return; }
+        HIP_CHECK(hipMemcpyAsync(stage, dev, sizeof(double) * count, hipMemcpyDeviceToHost, stream));
+        sync();
+        reduce_host(stage, count);
+        HIP_CHECK(hipMemcpyAsync(dev, stage, sizeof(double) * count, hipMemcpyHostToDevice, stream));
     }
 };
 
+/// What the last E-step left on the device for a data handle, and what has to be rebuilt before somebody reads the N x K block:
+///   kNone        -- nothing usable (the workspace was resized for another K, or lw was borrowed as scratch);
+///   kBlock       -- lw (and lse, once the E-step or the self-normalising statistics pass wrote it);
+///   kRecords     -- lse and the full-covariance records in params_dev (after a fused step, the resident loop, a lagged loop that
+///                   ran one iteration ahead): ensure_lw reruns the E-step kernel on the same records;
+///   kDiagRecords -- lse, diagonal records in params_dev and the parameters' host copy: ensure_lw expands them to full covariances.
+/// Only the members below assign the fields.
+struct EstepState {
+    enum What { kNone, kBlock, kRecords, kDiagRecords };
+    What what = kNone;
+    int rec_layout = 0;           // record layout currently in params_dev: 0 = valu, 2 = mfma4 (CloseArgs::layout codes)
+    bool rec_fold = false;        // mfma4 records in FOLD form (vector slot = -W (mu - shift)): layout.hpp kEstepFoldLimit
+    int n_ll = 0;                 // log-likelihood partials the last pass wrote
+    // source of the last statistics pass (for the per-component refinement pass)
+    int stats_mode = 0;
+    const double* stats_resp = nullptr;
+    size_t stats_ld = 0;
+    // diagonal-covariance extension: parameters of the last diagonal E-step (the N x K block is rebuilt from them on demand)
+    std::vector<double> diag_mixing, diag_means, diag_vars;
+
+    void invalidate() { what = kNone; }
+    void block_written(int grid) { what = kBlock; n_ll = grid; }
+    void records_only(int grid) { what = kRecords; n_ll = grid; }
+    void diag_records_only(int grid) { what = kDiagRecords; n_ll = grid; }
+    /// A later (speculative) pass overwrote lw / lse; the records in params_dev still stand.
+    void block_overwritten() { if (what == kBlock) what = kRecords; }
+    /// The parameters behind the diagonal records in params_dev (mlhip_em_iterate: set once, when the loop is over).
+    void diag_parameters(int K, int d, const double* mixing, const double* means, const double* vars)
+    {
+        diag_mixing.assign(mixing, mixing + K);
+        diag_means.assign(means, means + (size_t)K * d);
+        diag_vars.assign(vars, vars + (size_t)K * d);
+    }
+    void records_are(int layout, bool fold) { rec_layout = layout; rec_fold = fold; }
+    void stats_from(int mode, const double* resp, size_t ld) { stats_mode = mode; stats_resp = resp; stats_ld = ld; }
+
+    bool on_device() const { return what != kNone; }
+    bool needs_rebuild() const { return what == kRecords || what == kDiagRecords; }
+    bool diagonal() const { return what == kDiagRecords; }
+};
+
 struct mlhip_data {
+    // The context's pool while the context lives (null after it: blocks go back to the driver). Declared first: every buffer below
+    // is bound to this field by its initialiser, so a new buffer needs its declaration and nothing else.
+    BufferPool* pool = nullptr;
     mlhip_ctx* ctx = nullptr;
     // A block uploaded through a device group: `parts[s]` is shard s's resident block (rows first_row[s] .. first_row[s+1] of the
     // caller's sample); nothing else below is used then.
@@ -360,72 +445,52 @@ struct mlhip_data {
     uint32_t n = 0, n_pad = 0;
     uint64_t n_global = 0;
     size_t ldx = 0;
-    DevBuf xt;                    // [D][ldx]
-    DevBuf shift_dev;             // d doubles
+    DevBuf xt{&pool};             // [D][ldx]
+    DevBuf shift_dev{&pool};      // d doubles
     std::vector<double> shift;    // host copy
     // EM workspace (sized for em_K)
     int em_K = 0;
     size_t ldr = 0;
-    DevBuf lw, lse, esum, ll_partials, params_dev, partials, stats_dev, resp_dev, labels_dev;
-    PinnedBuf params_host, stats_host;
-    int n_ll = 0;
-    bool have_estep = false;
-    bool lw_valid = false;        // false after a fused step: lw is rebuilt from params_dev on demand (ensure_lw)
-    int estep_variant = 0;        // record layout currently in params_dev: 0 = valu, 2 = mfma4 (CloseArgs::layout codes)
-    bool estep_fold = false;      // mfma4 records in FOLD form (vector slot = -W (mu - shift)): layout.hpp kEstepFoldLimit
-    // diagonal-covariance extension: parameters of the last mlhip_em_step_diag (the N x K block is rebuilt from them on demand)
-    bool diag_step = false;
-    std::vector<double> diag_mixing, diag_means, diag_vars;
+    DevBuf lw{&pool}, lse{&pool}, esum{&pool}, ll_partials{&pool}, params_dev{&pool}, partials{&pool}, stats_dev{&pool}, resp_dev{&pool},
+        labels_dev{&pool};
+    PinnedBuf params_host{&pool}, stats_host{&pool};
+    EstepState estep;
+    bool has_estep_results(int K) const { return estep.on_device() && em_K == K; }
     // mlhip_em_iterate (em_loop.cpp): parameters and the E-steps' records stay on the device between iterations, in a ring of three --
     // iteration i reads the records of slot i % 3 (params_dev / params_next / params_prev take turns) and writes pack and records
     // (i + 1) % 3; it_pack: [info (1 + 2K) | mixing (K) | means (K d) | covariances]; one pinned read-back slot and event per pack
-    DevBuf params_next, params_prev, it_pack[3];
-    DevBuf it_sync, it_xch;       // device-resident loop (em_resident.hip): arrival counter / give-up flag, exchange blocks
-    DevBuf close_work;            // closing arithmetic at d > 64 (em_close_big.hip): the components' L and W
-    PinnedBuf it_info_slot[3], it_history;   // it_history: [result words | log-likelihood history] of the resident loop
+    DevBuf params_next{&pool}, params_prev{&pool}, it_pack[3] = {DevBuf{&pool}, DevBuf{&pool}, DevBuf{&pool}};
+    DevBuf it_sync{&pool}, it_xch{&pool};   // device-resident loop (em_resident.hip): arrival counter / give-up flag, exchange blocks
+    DevBuf close_work{&pool};     // closing arithmetic at d > 64 (em_close_big.hip): the components' L and W
+    PinnedBuf it_info_slot[3] = {PinnedBuf{&pool}, PinnedBuf{&pool}, PinnedBuf{&pool}};
+    PinnedBuf it_history{&pool};  // [result words | log-likelihood history] of the resident loop
     hipEvent_t it_event[3] = {nullptr, nullptr, nullptr};
-    // source of the last statistics pass (for the per-component refinement pass)
-    int stats_mode = 0;
-    const double* stats_resp = nullptr;
-    size_t stats_ld = 0;
-    DevBuf refine_shift, refine_stats;
-    uint64_t refined_components = 0;   // diagnostic counter
+    DevBuf refine_shift{&pool}, refine_stats{&pool};   // the per-component refinement pass
     // self-normalising statistics passes (run_mstats): both kernels add the number of nonzero responsibilities to nz_dev, which
     // is copied to slot sn_calls % 3 of nz_host; pass t chooses the sparse kernel from the count of pass t - 2 (in hand in every
     // loop: mlhip_em_iterate has waited for iteration t - 2 before it launches t)
-    DevBuf nz_dev;
-    PinnedBuf nz_host;
+    DevBuf nz_dev{&pool};
+    PinnedBuf nz_host{&pool};
     uint64_t sn_calls = 0;
     int sn_K = 0;
     // K-means workspace
-    DevBuf km_labels[2], km_cent, km_cent_next, km_partials, km_out, km_mind, km_probe, km_scale, km_cnorm, km_xt_pad;
-    PinnedBuf km_host;
-    DevBuf kpp_w, kpp_scr;               // mlhip_kpp_draw: the running-minimum weights, block sums / offsets / result
-    DevBuf fp_w, fp_scr;                 // mlhip_kpp_draw_fixed_point: the running-minimum weights; [slots | block sums | block maxima | centroid]
-    PinnedBuf fp_host;                   // its read-back slots
+    DevBuf km_labels[2] = {DevBuf{&pool}, DevBuf{&pool}};
+    DevBuf km_cent{&pool}, km_cent_next{&pool}, km_partials{&pool}, km_out{&pool}, km_mind{&pool}, km_probe{&pool}, km_scale{&pool},
+        km_cnorm{&pool}, km_xt_pad{&pool};
+    PinnedBuf km_host{&pool};
+    DevBuf kpp_w{&pool}, kpp_scr{&pool};   // mlhip_kpp_draw: the running-minimum weights, block sums / offsets / result
+    DevBuf fp_w{&pool}, fp_scr{&pool};     // mlhip_kpp_draw_fixed_point: the running-minimum weights; [slots | block sums | block maxima | centroid]
+    PinnedBuf fp_host{&pool};              // its read-back slots
     int km_cur = 0;
     bool km_have_old = false;
 
-    /// Every buffer of the handle draws from / returns to the context's pool.
-    void attach_pool(BufferPool* pool)
-    {
-        for (DevBuf* b : {&xt, &shift_dev, &lw, &lse, &esum, &ll_partials, &params_dev, &partials, &stats_dev, &resp_dev,
-                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr, &fp_w, &fp_scr,
-                          &refine_shift, &refine_stats, &nz_dev, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
-            b->pool = pool;
-        for (PinnedBuf* b : {&params_host, &stats_host, &nz_host, &km_host, &fp_host, &it_info_slot[0], &it_info_slot[1], &it_info_slot[2], &it_history}) b->pool = pool;
-    }
-
+    mlhip_data() = default;
+    mlhip_data(const mlhip_data&) = delete;      // (the buffers point at this object's pool field)
+    mlhip_data& operator=(const mlhip_data&) = delete;
     ~mlhip_data()
     {
         for (mlhip_data* p : parts) mlhip_data_free(p);
-        for (DevBuf* b : {&xt, &shift_dev, &lw, &lse, &esum, &ll_partials, &params_dev, &partials, &stats_dev, &resp_dev,
-                          &labels_dev, &km_labels[0], &km_labels[1], &km_cent, &km_cent_next, &km_partials, &km_out, &km_mind, &km_probe, &km_scale, &km_cnorm, &km_xt_pad, &kpp_w, &kpp_scr, &fp_w, &fp_scr,
-                          &refine_shift, &refine_stats, &nz_dev, &params_next, &params_prev, &it_pack[0], &it_pack[1], &it_pack[2], &it_sync, &it_xch, &close_work})
-            b->release();
-        for (auto& sl : it_info_slot) sl.release();
         for (auto& e : it_event) if (e) (void)hipEventDestroy(e);
-        params_host.release(); stats_host.release(); nz_host.release(); km_host.release(); fp_host.release(); it_history.release();
     }
 };
 
@@ -509,14 +574,21 @@ void download_columns(mlhip_ctx* ctx, char* dst, size_t dst_pitch, const char* s
 
 void ensure_em_workspace(mlhip_data* dt, int K);
 
-/// Builds the per-component records for the route's E-step kernel and uploads them to params_dev.
-void prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs,
-                   DevBuf* target = nullptr);
+/// Layout (CloseArgs::layout codes) and form of a set of E-step records.
+struct RecordForm {
+    int layout;
+    bool fold;
+};
+
+/// Builds the per-component records for the route's E-step kernel and uploads them to params_dev, whose descriptor they become -- or
+/// to `target` (mlhip_em_iterate's ring), whose descriptor is the caller's to keep. Returns the records' form.
+RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs,
+                         DevBuf* target = nullptr);
 
 /// E-step kernel on the records in params_dev: fills lw and -- unless the statistics kernel is going to normalise the
 /// log-responsibilities itself (`with_lse` false, matrix-core kernel only) -- lse and the log-likelihood partials.
 /// `records` / `fold`: another record buffer than params_dev and its form (mlhip_em_iterate keeps a ring of them); default: params_dev
-/// and dt->estep_fold.
+/// and its form.
 void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse = true, const DevBuf* records = nullptr, int fold = -1);
 
 void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs,
@@ -528,6 +600,12 @@ void ensure_lw(mlhip_data* dt, const EmRoute& r, int K);
 
 /// All-reduces the reduced statistics buffer [K*F stats, ll_sum] and leaves it in stats_host.
 void collect_stats(mlhip_data* dt, int K, size_t count = 0);
+
+/// The fused kernel's arguments on the records in `records`.
+FusedArgs fused_args(const mlhip_data* dt, const EmRoute& r, int K, const DevBuf* records);
+
+/// What a fused pass (launch_fused_step, or the resident loop that runs the same pass) leaves behind on the handle.
+void fused_pass_done(mlhip_data* dt, int grid);
 
 /// The fused kernel + reduction on the records already in params_dev; statistics end in stats_dev (and, with `collect`, all-
 /// reduced in stats_host).
@@ -597,10 +675,6 @@ bool mstats_sparse_applies(mlhip_data* dt, const EmRoute& r, int K);
 /// One full-covariance EM iteration with the closing arithmetic on the HOST (the body of mlhip_em_step).
 void em_step_full(mlhip_data* data, const EmRoute& r, int K, const double* mixing, const double* means, const double* covariances,
                   double* log_likelihood, double* mixing_out, double* means_out, double* covariances_out);
-
-/// Sums `count` doubles at the head of stats_dev across ranks, whatever kind of hook is installed (device buffer on the
-/// stream, or a host buffer: down, hook, up). No-op on a single rank.
-void allreduce_stats_dev(mlhip_data* dt, size_t count);
 
 /// Records of a diagonal-covariance parameter set -> `target` (padded to whole 16-component row blocks with neutral records).
 void upload_diag_records(mlhip_data* data, int K, const double* mixing, const double* means, const double* variances, DevBuf& target);

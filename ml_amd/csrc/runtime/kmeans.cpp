@@ -22,7 +22,6 @@ void ensure_km_workspace(mlhip_data* dt, int K)
         std::vector<double> m(dt->d);
         HIP_CHECK(hipMemcpyAsync(m.data(), mx.p, sizeof(double) * dt->d, hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
-        scratch.release(); mx.release();
         // Every rank must cut its coordinates on the SAME fixed-point grid (the limb sums are added across ranks): the
         // column maxima are exchanged through the sum hook, one slot per rank, and every rank takes the maximum.
         if (ctx->world_size > 1) {
@@ -115,23 +114,14 @@ void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool a
     HIP_CHECK(hipGetLastError());
     dt->km_cur = nxt;
     dt->km_have_old = true;
-    if (ctx->reduce_fn && ctx->reduce_on_device) {
-        const size_t count = 2 + (accumulate ? (size_t)K * (dt->d + 1) : 0);
-        ctx->reduce_device(dt->km_out.as<double>(), count);
-    }
+    ctx->reduce_on_stream(dt->km_out.as<double>(), 2 + (accumulate ? (size_t)K * (dt->d + 1) : 0));
 }
 
 
 /// km_out -> km_host (`count` doubles), summed across ranks on the host when the all-reduce works on host memory.
 void km_fetch(mlhip_data* dt, size_t count)
 {
-    mlhip_ctx* ctx = dt->ctx;
-    double* ch = dt->km_host.as<double>();
-    HIP_CHECK(hipMemcpyAsync(ch, dt->km_out.p, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-    if (ctx->reduce_fn && !ctx->reduce_on_device) {
-        if (ctx->reduce_fn(ctx->reduce_user, ch, count, 0, ctx->stream) != 0) throw hook_failure();
-    }
+    dt->ctx->fetch_reduced(dt->km_host.as<double>(), dt->km_out.as<double>(), count);
 }
 
 
