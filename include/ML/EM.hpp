@@ -76,6 +76,22 @@ public:
     /** Posterior component probabilities of one point under the fitted parameters (host-side).
     @throw std::invalid_argument If `x.size() != means().rows()` or `u.size() != number_components()`. */
     DLL_DECLSPEC void assign_responsibilities(ConstVectorRef x, VectorRef u) const;
+    /** Extension (not in the reference surface): log sum_k pi_k N(x_i | mu_k, Sigma_k) of every column of `data` (a data point in
+    every column, like fit's; any number of them) under the fitted parameters, computed on the device in one pass that writes 12
+    bytes per point (mlhip_em_score). The block is uploaded in row batches (2^24 points; MLHIP_SCORE_ROWS overrides), so it may be
+    larger than the fit's; the results do not depend on the batch size. The fit's own device block and responsibilities() are not
+    touched. In a row-sharded job every rank scores its own block and must pass the same number of batches.
+    @throw std::invalid_argument If `data.rows() != means().rows()` or the model has not been fitted.
+    @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
+    DLL_DECLSPEC VectorXd log_densities(ConstMatrixRef data) const;
+    /** Extension: the mean of log_densities(data), summed sequentially in row order (comparable with log_likelihood()); NaN for an
+    empty block (the other batch queries return empty results for one). */
+    DLL_DECLSPEC double mean_log_density(ConstMatrixRef data) const;
+    /** Extension: argmax_k of every point's log-responsibilities, first maximum wins (the same pass as log_densities). */
+    DLL_DECLSPEC std::vector<unsigned int> assign_labels(ConstMatrixRef data) const;
+    /** Extension: the data.cols() x number_components() posteriors of `data` (the batch form of assign_responsibilities, normalised
+    in the log domain). This one needs the N x K block: an E-step per row batch on a temporary device block. */
+    DLL_DECLSPEC MatrixXd calculate_responsibilities(ConstMatrixRef data) const;
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }
     /** Extension: number of E-M iterations the last fit() ran. */
@@ -108,6 +124,8 @@ private:
     mlhip_data* device_data_ = nullptr;
 
     void process_covariances(Index number_dimensions);
+    void require_fitted_for(ConstMatrixRef data) const;
+    void score(ConstMatrixRef data, double* log_density, unsigned int* labels) const;
 };
 
 }  // namespace ml

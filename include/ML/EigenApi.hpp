@@ -150,6 +150,18 @@ public:
         detail::check(mlpp_kmeans_assign_label(h_, contiguous.data(), static_cast<uint32_t>(contiguous.size()), &label, &dist2));
         return std::make_pair(static_cast<unsigned int>(label), dist2);
     }
+    /** Extension (not in the reference surface): assign_label for every column of `data`, on the device; with
+    `squared_distances` also the squared distance of every point to its centroid. */
+    std::vector<unsigned int> assign_labels(Eigen::Ref<const Eigen::MatrixXd> data, Eigen::VectorXd* squared_distances = nullptr) const
+    {
+        const detail::Block block(data);
+        std::vector<unsigned int> labels(static_cast<std::size_t>(data.cols()));
+        if (squared_distances) squared_distances->resize(data.cols());
+        static_assert(sizeof(unsigned int) == sizeof(uint32_t), "labels are 32-bit");
+        detail::check(mlpp_kmeans_predict(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()),
+                                          reinterpret_cast<uint32_t*>(labels.data()), squared_distances ? squared_distances->data() : nullptr));
+        return labels;
+    }
     double inertia() const { return inertia_; }
     bool converged() const override { return converged_; }
 
@@ -248,6 +260,40 @@ public:
         detail::check(mlpp_em_assign_responsibilities(h_, contiguous.data(), static_cast<uint32_t>(contiguous.size()), out.data(),
                                                       static_cast<uint32_t>(out.size())));
         u = out;
+    }
+    /** Extensions (not in the reference surface): the batch queries of a fitted model on a block with a data point in every column
+    (any number of them), computed on the device. log_densities: log sum_k pi_k N(x_i | mu_k, Sigma_k) per point; mean_log_density:
+    their mean, summed in row order (NaN for an empty block); assign_labels: argmax_k of the log-responsibilities, first maximum
+    wins; calculate_responsibilities: the data.cols() x number_components() posteriors.
+    @throw std::invalid_argument If `data.rows() != means().rows()` or the model has not been fitted. */
+    Eigen::VectorXd log_densities(Eigen::Ref<const Eigen::MatrixXd> data) const
+    {
+        const detail::Block block(data);
+        Eigen::VectorXd out(data.cols());
+        detail::check(mlpp_em_score_samples(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()), out.data()));
+        return out;
+    }
+    double mean_log_density(Eigen::Ref<const Eigen::MatrixXd> data) const
+    {
+        const Eigen::VectorXd v = log_densities(data);
+        double sum = 0;
+        for (Eigen::Index i = 0; i < v.size(); ++i) sum += v[i];
+        return sum / static_cast<double>(v.size());
+    }
+    std::vector<unsigned int> assign_labels(Eigen::Ref<const Eigen::MatrixXd> data) const
+    {
+        const detail::Block block(data);
+        std::vector<unsigned int> out(static_cast<std::size_t>(data.cols()));
+        detail::check(mlpp_em_predict(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()),
+                                      reinterpret_cast<uint32_t*>(out.data())));
+        return out;
+    }
+    Eigen::MatrixXd calculate_responsibilities(Eigen::Ref<const Eigen::MatrixXd> data) const
+    {
+        const detail::Block block(data);
+        Eigen::MatrixXd out(data.cols(), static_cast<Eigen::Index>(number_components_));
+        detail::check(mlpp_em_predict_proba(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()), out.data()));
+        return out;
     }
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }

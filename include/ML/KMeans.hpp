@@ -44,6 +44,11 @@ public:
     void set_verbose(bool verbose) { verbose_ = verbose; }
     /** Label and squared Euclidean distance of the nearest centroid (host-side point query). */
     DLL_DECLSPEC std::pair<unsigned int, double> assign_label(ConstVectorRef x) const;
+    /** Extension (not in the reference surface): assign_label for every column of `data` on the device (the assignment kernel of
+    fit on a temporary device block, uploaded in row batches of 2^24 points; MLHIP_SCORE_ROWS overrides): the labels, and in
+    `*squared_distances` (when given) the squared distance of every point to its centroid -- the values assign_label returns.
+    @throw std::invalid_argument If `data.rows() != centroids().rows()`. @throw std::runtime_error On device failures. */
+    DLL_DECLSPEC std::vector<unsigned int> assign_labels(ConstMatrixRef data, VectorXd* squared_distances = nullptr) const;
     double inertia() const { return inertia_; }
     bool converged() const override { return converged_; }
     /** Extension: number of Lloyd steps the last fit_once ran. */

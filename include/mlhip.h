@@ -191,6 +191,19 @@ int mlhip_em_responsibilities_rows(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
 /* argmax_k of those responsibilities, first maximum wins (EM::calculate_labels, ML/EM.cpp:289-304). */
 int mlhip_em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labels);
 
+/* EXTENSION (not in the reference surface): per-sample log-density  log sum_k pi_k N(x_i | mu_k, Sigma_k)  and label
+ * argmax_k of the log-responsibilities (first maximum wins; 0xffffffff where the density is NaN) of this rank's rows of `data`
+ * under the given mixture -- the batch form of EM::assign_responsibilities (ML/EM.cpp:176-188), in the log domain: a row the
+ * reference's linear-domain sum underflows on still gets its finite log-density. covariance_type as in mlhip_em_iterate (diagonal:
+ * K*d variances). log_density (n_local doubles) and labels (n_local) may each be NULL. No N x K block is allocated (d <= 128: one
+ * kernel that writes 8 + 4 bytes per row; above, and under MLHIP_SCORE=composed, the E-step kernel on row chunks into a scratch block
+ * of at most 256 MB); nothing the handle holds from earlier calls (E-step results, records, label history, the statistics pass's call
+ * history) is changed. A device group scores every shard's rows; a row-sharded job needs no communication. Arguments are checked
+ * as by mlhip_em_expectation. */
+int mlhip_em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type,
+                   const double* mixing, const double* means, const double* covariances,
+                   double* log_density, uint32_t* labels);
+
 /* (X - mean)(X - mean)^T / (N - 1) over ALL ranks' samples (EM::calculate_sample_covariance,
  * ML/EM.cpp:265-272). mean may be NULL. */
 int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance);
@@ -275,7 +288,7 @@ int mlhip_random_partition_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, c
 
 /* ---- timing (for bench.py / profiling) -------------------------------------------------------------- */
 /* Average device time in ms of the named kernel family over its launches since the last reset, measured with
- * HIP events on the context's stream. name: "em_estep", "em_mstats", "kmeans_assign", ... Returns count in *launches.
+ * HIP events on the context's stream. name: "em_estep", "em_mstats", "em_score", "kmeans_assign", ... Returns count in *launches.
  * While enabled, every launch is bracketed by a pair of events that is only recorded; the times are read (one stream
  * synchronisation) when mlhip_timing_get / _reset / _enable(off) is called, so a timed region is not perturbed. */
 int mlhip_timing_enable(mlhip_ctx* ctx, int on);
@@ -317,6 +330,11 @@ typedef struct mlhip_kmeans_route_info {
     int32_t resident;           /* mlhip_kmeans_iterate runs the whole loop in one launch */
 } mlhip_kmeans_route_info;
 int mlhip_em_route(const mlhip_data* data, uint32_t K, int covariance_type, mlhip_em_route_info* out);
+/* Which kernel mlhip_em_score runs for K components on `data` (diagnostic, nothing is launched): the scalar-fed score kernel and the
+ * matrix-core E-step's SCORE form wherever mlhip_em_route reports MLHIP_ESTEP_SCALAR_FED / MLHIP_ESTEP_MATRIX4; composed above d = 128
+ * and under MLHIP_SCORE=composed. */
+enum { MLHIP_SCORE_SCALAR_FED = 0, MLHIP_SCORE_MATRIX4 = 1, MLHIP_SCORE_COMPOSED = 2 };
+int mlhip_em_score_route(const mlhip_data* data, uint32_t K, int* kernel);
 int mlhip_kmeans_route(const mlhip_data* data, uint32_t K, mlhip_kmeans_route_info* out);
 
 #ifdef __cplusplus

@@ -69,6 +69,11 @@ int mlpp_em_labels(const mlpp_em* h, uint32_t* out);
 int mlpp_em_converged(const mlpp_em* h, int* out);
 int mlpp_em_steps_done(const mlpp_em* h, uint32_t* out);
 int mlpp_em_assign_responsibilities(const mlpp_em* h, const double* x, uint32_t xlen, double* u, uint32_t ulen);
+/* Extensions (not in the reference surface): the batch queries of ml::EM on N x d row-major data under the fitted parameters --
+ * EM::log_densities (out: n doubles), EM::assign_labels (out: n labels), EM::calculate_responsibilities (out: N x K column-major). */
+int mlpp_em_score_samples(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out);
+int mlpp_em_predict(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, uint32_t* out);
+int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out);
 
 /* ---- KMeans (cppyml/clustering.cpp:148-183) ---- */
 int mlpp_kmeans_create(uint32_t number_clusters, mlpp_kmeans** out);
@@ -88,6 +93,8 @@ int mlpp_kmeans_inertia(const mlpp_kmeans* h, double* out);
 int mlpp_kmeans_converged(const mlpp_kmeans* h, int* out);
 int mlpp_kmeans_steps_done(const mlpp_kmeans* h, uint32_t* out);
 int mlpp_kmeans_assign_label(const mlpp_kmeans* h, const double* x, uint32_t xlen, uint32_t* label, double* dist2);
+/* Extension: KMeans::assign_labels on N x d row-major data -- labels (n) and, unless dist2 is NULL, the squared distances (n doubles). */
+int mlpp_kmeans_predict(const mlpp_kmeans* h, const double* data, uint64_t n, uint32_t d, uint32_t* labels, double* dist2);
 
 /* ---- LinearAlgebra helpers (ML/LinearAlgebra.hpp:18-31), column-major ---- */
 int mlpp_xAx_symmetric(const double* A, uint32_t rows, uint32_t cols, const double* x, uint32_t xlen, double* out);

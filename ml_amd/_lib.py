@@ -385,6 +385,27 @@ class Data:
         check(lib.mlhip_kmeans_route(self._h, C.c_uint32(K), C.byref(info)))
         return {"kernel": ("direct", "matrix", "big_dim", "plain")[info.kernel], "pad": bool(info.pad), "resident": bool(info.resident)}
 
+    def em_score(self, mixing, means, covs, diagonal=False, densities=True, labels=True):
+        """Per-row log-density and label under the given mixture (mlhip_em_score): (log_density, labels), None for the one not
+        asked for. covs: K x d x d (or K x d variances with diagonal=True). Nothing the handle holds is changed."""
+        K = len(mixing)
+        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
+        means = np.ascontiguousarray(means, dtype=np.float64)
+        covs = np.ascontiguousarray(covs, dtype=np.float64)
+        assert means.shape == (K, self.d) and covs.shape == ((K, self.d) if diagonal else (K, self.d, self.d))
+        dens = np.empty(self.n) if densities else None
+        lab = np.empty(self.n, dtype=np.uint32) if labels else None
+        check(lib.mlhip_em_score(self.ctx.handle, self._h, K, int(bool(diagonal)), dptr(mixing), dptr(means), dptr(covs),
+                                 dptr(dens) if densities else None, u32ptr(lab) if labels else None))
+        return dens, lab
+
+    def em_score_route(self, K):
+        """The kernel mlhip_em_score runs for K components under the switches as they are set now (mlhip_em_score_route):
+        'scalar_fed' | 'matrix4' | 'composed'."""
+        k = C.c_int()
+        check(lib.mlhip_em_score_route(self._h, C.c_uint32(K), C.byref(k)))
+        return ("scalar_fed", "matrix4", "composed")[k.value]
+
     def em_expectation(self, mixing, means, covs):
         K = len(mixing)
         mixing = np.ascontiguousarray(mixing, dtype=np.float64)

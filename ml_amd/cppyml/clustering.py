@@ -7,7 +7,7 @@ Conventions kept from the reference:
   * `EM.means` is `d x K` (NOT transposed, clustering.cpp:126), `KMeans.centroids` is `K x d` (clustering.cpp:66-69,172);
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
-Extensions (not in the reference surface): `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
+Extensions (not in the reference surface): `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`.
 """
 import ctypes as C
@@ -269,6 +269,41 @@ class EM:
         return u
 
     # ---- extensions ----
+    def score_samples(self, X):
+        """Extension: log-density of every row of X (N x d, what `fit` takes) under the fitted mixture, on the GPU."""
+        X = _require_data(X)
+        n, d = X.shape
+        out = np.empty(n)
+        _check(_l.mlpp_em_score_samples(self._h, _dp(X), C.c_uint64(n), d, _dp(out)))
+        return out
+
+    def score(self, X):
+        """Extension: mean of score_samples(X), summed sequentially in row order (comparable with `log_likelihood`); NaN for
+        an empty X, like the C++ `mean_log_density`."""
+        v = self.score_samples(X)
+        if not len(v):
+            return float("nan")
+        total = 0.0
+        for x in v.tolist():
+            total += x
+        return total / len(v)
+
+    def predict(self, X):
+        """Extension: component of the largest log-responsibility for every row of X (first maximum wins), uint32 array."""
+        X = _require_data(X)
+        n, d = X.shape
+        out = np.empty(n, dtype=np.uint32)
+        _check(_l.mlpp_em_predict(self._h, _dp(X), C.c_uint64(n), d, _lib.u32ptr(out)))
+        return out
+
+    def predict_proba(self, X):
+        """Extension: posterior component probabilities of every row of X (N x K, Fortran order like `responsibilities`)."""
+        X = _require_data(X)
+        n, d = X.shape
+        out = np.empty((n, self.number_components), order="F")
+        _check(_l.mlpp_em_predict_proba(self._h, _dp(X), C.c_uint64(n), d, _dp(out)))
+        return out
+
     @property
     def labels(self):
         _, n = self._dims()
@@ -390,6 +425,16 @@ class KMeans:
         return label.value, dist.value
 
     # ---- extensions ----
+    def predict(self, X, return_distances=False):
+        """Extension: `assign_label` for every row of X on the GPU: uint32 labels, and with return_distances=True also the
+        squared distance of every row to its centroid."""
+        X = _require_data(X)
+        n, d = X.shape
+        labels = np.empty(n, dtype=np.uint32)
+        dist = np.empty(n) if return_distances else None
+        _check(_l.mlpp_kmeans_predict(self._h, _dp(X), C.c_uint64(n), d, _lib.u32ptr(labels), _dp(dist) if return_distances else None))
+        return (labels, dist) if return_distances else labels
+
     @property
     def converged(self):
         v = C.c_int()

@@ -71,6 +71,7 @@ struct EstepArgs {
     int num_cus;                                            // compute units of the context's device (0: ask the current device)
     double* scratch; size_t scratch_doubles;                // a block free for the launch (the statistics partials): the big tier's q parts
     int plain;                                              // d > kMaxDim: 1 = the plain tier even where big_dim.hip applies
+    uint32_t* labels;                                       // em_estep_mfma4's SCORE form only (launch_em_score_mfma4): out, may be null
 };
 /// Returns the grid size used (= number of ll partials written), or <0 if D is not instantiated.
 int launch_em_estep(const EstepArgs& a, hipStream_t stream);
@@ -78,6 +79,22 @@ int launch_em_estep(const EstepArgs& a, hipStream_t stream);
 int launch_em_estep_generic(const EstepArgs& a, hipStream_t stream);
 /// 4x4-block triangular variant (em_estep_mfma4.hip); params use the estep_mfma4_param_stride(D) record layout.
 int launch_em_estep_mfma4(const EstepArgs& a, int num_cus, hipStream_t stream);
+
+/// Scoring pass (em_score.hip; em_estep_mfma4.hip's SCORE form): per sample the log-sum-exp of the K log-densities-times-weights and
+/// the label argmax_k lw (first maximum wins; 0xffffffff where lse is NaN) -- no N x K block. Both outputs hold padded_samples(n)
+/// entries; either may be null.
+struct ScoreArgs {
+    const double* xt; size_t ldx; uint32_t n; int D;      // D = padded dimension
+    const double* params; int K;                            // K records: estep_param_stride(D) (scalar-fed) / estep_mfma4_param_stride(D)
+    double* lse; uint32_t* labels;                          // out
+};
+/// d <= 32, the scalar-fed tier. Returns the grid, or < 0 if D is not instantiated.
+int launch_em_score(const ScoreArgs& a, hipStream_t stream);
+/// 12 <= d <= 128 on the matrix cores: em_estep_mfma4_kernel's SCORE form, exact (never FOLD). In a code object of its own.
+int launch_em_score_mfma4(const ScoreArgs& a, int num_cus, hipStream_t stream);
+/// Label and lse of n rows from the lw [K][ldr] / lse an E-step kernel wrote (the composed scoring route's second kernel).
+void launch_em_score_finish(const double* lw, size_t ldr, const double* lse, uint32_t n, int K, double* lse_out, uint32_t* labels_out,
+                            hipStream_t stream);
 
 enum MstatsMode : int {
     kFromLogResp = 0,   // r = exp(lw - lse)          (after an E-step)

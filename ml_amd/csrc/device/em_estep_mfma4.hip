@@ -24,8 +24,14 @@
 //   !LSE  no online log-sum-exp, only lw is written: the statistics kernel normalises a sample's K log-responsibilities
 //         itself while staging its tile (em_mstats_wide.hip, one exp per (sample, component) instead of one in each
 //         kernel) and produces lse and the log-likelihood sum. Used whenever K fits one row-block group of that kernel.
+// A third option makes the scoring pass (mlhip_em_score) out of the same kernel:
+//   SCORE the LSE epilogue without the lw store and without the log-likelihood partials; the label argmax_k lw (first maximum
+//         wins) is carried next to m / ssum in the owner lanes -- the running maximum of the log-sum-exp is the running best lw,
+//         both move on the strict lw > m -- and lw_out points at the labels. Exact form only. Its instantiations are part 2 of
+//         this file (parts.hpp), a code object of their own: a fit loads what it loaded without them.
 #include "device.hpp"
 #include "exp_nonpos.hpp"
+#include "parts.hpp"
 
 namespace mlhip {
 namespace {
@@ -43,7 +49,7 @@ template <int D> struct Blocks {
     static constexpr int window() { for (int w = 9; w > 1; --w) if (NB % w == 0) return w; return 1; }
 };
 
-__device__ __forceinline__ double wave_sum(double v)
+[[maybe_unused]] __device__ __forceinline__ double wave_sum(double v)   // (part 2, the SCORE form, sums nothing)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -80,12 +86,16 @@ __device__ __forceinline__ double reduce_scatter_groups(double v0, double v1, do
 /// per component sweep for SB = 4 and 2 (128 for SB = 1); the component record is staged once per sweep.
 template <int SB> constexpr int default_waves() { return SB == 1 ? 8 : 16 / SB; }
 
-template <int D, int SB, bool FOLD, bool LSE, int NW = default_waves<SB>()>
+template <bool SCORE> struct BlockOut { using type = double; };       // lw_out: the log-responsibility block ...
+template <> struct BlockOut<true> { using type = uint32_t; };         // ... or, in the SCORE form, the labels
+
+template <int D, int SB, bool FOLD, bool LSE, int NW = default_waves<SB>(), bool SCORE = false>
 __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_kernel(
     const double* __restrict__ xt, size_t ldx, uint32_t n, uint32_t n_groups, const double* __restrict__ params, int K,
-    const double* __restrict__ shift, double* __restrict__ lw_out, size_t ldr, double* __restrict__ lse_out,
+    const double* __restrict__ shift, typename BlockOut<SCORE>::type* __restrict__ lw_out, size_t ldr, double* __restrict__ lse_out,
     double* __restrict__ ll_partials)
 {
+    static_assert(!SCORE || (LSE && !FOLD), "the SCORE form is the exact LSE form");
     using B = Blocks<D>;
     constexpr int Q = B::Q, NB = B::NB, PS = B::PS;
     constexpr int NT = 64 * NW, NWV = NW;          // threads / waves per workgroup
@@ -128,6 +138,7 @@ __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_
         }
 
         double m = -__builtin_inf(), ssum = 0.0;
+        [[maybe_unused]] uint32_t arg = 0xffffffffu;   // SCORE: the component of the running maximum (ML/EM.cpp:294 starts from label -1)
 
         // first record -> its LDS buffer (the barrier at the top of the component loop publishes it)
         double stage[NLD];
@@ -209,7 +220,7 @@ __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_
                 q = t + __shfl_xor(t, 32, 64);
             }
             const double lw = __builtin_fma(-0.5, q, coef);
-            if (owner) lw_out[(size_t)k * ldr + base + lane] = lw;
+            if constexpr (!SCORE) { if (owner) lw_out[(size_t)k * ldr + base + lane] = lw; }
             if constexpr (LSE) {
                 // exp(t) is exactly 0 in fp64 for t < -745.2: when that holds for the whole wave the update would add 0 to
                 // every ssum and leave every m unchanged, so it is skipped (bit-identical result, one exp saved).
@@ -220,6 +231,7 @@ __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_
                     const bool up = lw > m;
                     ssum = up ? __builtin_fma(ssum, e, 1.0) : ssum + e;
                     m = up ? lw : m;
+                    if constexpr (SCORE) arg = up ? (uint32_t)k : arg;   // (a skipped update had lw < m for the whole wave)
                 }
             }
             // publish record k+1 in the other buffer: nobody reads it now (last read during k-1, before this
@@ -229,7 +241,12 @@ __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_
         }
         if constexpr (LSE) {
             const double lse = m + log(ssum);
-            if (owner) {
+            if constexpr (SCORE) {
+                if (owner) {
+                    if (lse_out) lse_out[base + lane] = lse;
+                    if (lw_out) lw_out[base + lane] = lse != lse ? 0xffffffffu : arg;   // (a NaN row has no maximum: em_post.hip)
+                }
+            } else if (owner) {
                 lse_out[base + lane] = lse;
                 if (base + lane < n) ll_acc += lse;
             }
@@ -252,7 +269,7 @@ __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_
             process((full_tiles + u / kTailChunks) * NWV + wave, c * K / kTailChunks, (c + 1) * K / kTailChunks);
         }
     }
-    if constexpr (LSE) {
+    if constexpr (LSE && !SCORE) {
         ll_acc = wave_sum(ll_acc);
         if (lane == 0) red[wave] = ll_acc;
         __syncthreads();
@@ -265,7 +282,7 @@ __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_
     }
 }
 
-template <int D, int SB, bool FOLD, bool LSE, int NW = default_waves<SB>()>
+template <int D, int SB, bool FOLD, bool LSE, int NW = default_waves<SB>(), bool SCORE = false>
 int launch_sb(const EstepArgs& a, int num_cus, hipStream_t stream)
 {
     // the waves of a workgroup share barriers inside the component loop: a workgroup sweep must cover a whole number of
@@ -285,7 +302,7 @@ int launch_sb(const EstepArgs& a, int num_cus, hipStream_t stream)
         // statistics kernel behind it loses 2 %: not used there)
         static const int fit = [] {
             int blocks = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, em_estep_mfma4_kernel<D, SB, FOLD, LSE, NW>, NT, sizeof(double) * 2 * NLD * NT) != hipSuccess) blocks = 2;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, em_estep_mfma4_kernel<D, SB, FOLD, LSE, NW, SCORE>, NT, sizeof(double) * 2 * NLD * NT) != hipSuccess) blocks = 2;
             return blocks < 2 ? 2 : (blocks > 4 ? 4 : blocks);
         }();
         if ((uint32_t)fit > per_cu) per_cu = (uint32_t)fit;
@@ -293,18 +310,24 @@ int launch_sb(const EstepArgs& a, int num_cus, hipStream_t stream)
     const uint32_t cap = (uint32_t)num_cus * per_cu;
     if (grid > cap) grid = cap;
     if (grid > (uint32_t)a.n_ll_partials) grid = (uint32_t)a.n_ll_partials;
-    hipLaunchKernelGGL((em_estep_mfma4_kernel<D, SB, FOLD, LSE, NW>), dim3(grid), dim3(NT), smem, stream, a.xt, a.ldx, a.n, n_groups,
-                       a.params, a.K, a.shift, a.lw, a.ldr, a.lse, a.ll_partials);
+    typename BlockOut<SCORE>::type* block_out;
+    if constexpr (SCORE) block_out = a.labels; else block_out = a.lw;
+    hipLaunchKernelGGL((em_estep_mfma4_kernel<D, SB, FOLD, LSE, NW, SCORE>), dim3(grid), dim3(NT), smem, stream, a.xt, a.ldx, a.n, n_groups,
+                       a.params, a.K, a.shift, block_out, a.ldr, a.lse, a.ll_partials);
     return (int)grid;
 }
 
 template <int D, int SB>
 int launch_v(const EstepArgs& a, int num_cus, hipStream_t stream)
 {
+#if MLHIP_PART == 2
+    return launch_sb<D, SB, false, true, default_waves<SB>(), true>(a, num_cus, stream);
+#else
     if constexpr (D <= kRegDim) {
         if (a.fold) return a.with_lse ? launch_sb<D, SB, true, true>(a, num_cus, stream) : launch_sb<D, SB, true, false>(a, num_cus, stream);
     }
     return a.with_lse ? launch_sb<D, SB, false, true>(a, num_cus, stream) : launch_sb<D, SB, false, false>(a, num_cus, stream);
+#endif
 }
 
 template <int D>
@@ -322,9 +345,8 @@ int launch_t(const EstepArgs& a, int num_cus, hipStream_t stream)
 static_assert(Blocks<32>::NB == 36 && Blocks<12>::NB == 6, "block count");
 static_assert(Blocks<32>::C(0) == 0 && Blocks<32>::R(7) == 7 && Blocks<32>::C(8) == 1 && Blocks<32>::R(8) == 1 && Blocks<32>::C(35) == 7, "block order");
 
-}  // namespace
-
-int launch_em_estep_mfma4(const EstepArgs& a, int num_cus, hipStream_t stream)
+/// Part 1: the E-step's forms (what a fit launches); part 2: the SCORE form.
+int dispatch(const EstepArgs& a, int num_cus, hipStream_t stream)
 {
     switch (a.D) {
     case 12: return launch_t<12>(a, num_cus, stream);
@@ -348,5 +370,22 @@ int launch_em_estep_mfma4(const EstepArgs& a, int num_cus, hipStream_t stream)
     default: return -1;
     }
 }
+
+}  // namespace
+
+#if MLHIP_PART == 1
+int launch_em_estep_mfma4(const EstepArgs& a, int num_cus, hipStream_t stream) { return dispatch(a, num_cus, stream); }
+#else
+int launch_em_score_mfma4(const ScoreArgs& s, int num_cus, hipStream_t stream)
+{
+    EstepArgs a{};
+    a.xt = s.xt; a.ldx = s.ldx; a.n = s.n; a.D = s.D;
+    a.params = s.params; a.K = s.K;
+    a.lse = s.lse; a.labels = s.labels;
+    a.with_lse = 1;
+    a.n_ll_partials = 0x7fffffff;                          // (no log-likelihood partials in the SCORE form: nothing bounds the grid)
+    return dispatch(a, num_cus, stream);
+}
+#endif
 
 }  // namespace mlhip

@@ -278,6 +278,13 @@ void locate_rows(mlhip_ctx* ctx, Index n_local, Index& first_row, Index& n_globa
 
 void sum_across_ranks(mlhip_ctx* ctx, MatrixRef m) { allreduce_matrix(ctx, m); }
 
+Index score_batch_rows()
+{
+    const char* e = std::getenv("MLHIP_SCORE_ROWS");
+    const long v = e && *e ? std::atol(e) : 0;
+    return v > 0 ? static_cast<Index>(v) : Index(1) << 24;
+}
+
 void init_centroids(const CentroidsInitialiser& initialiser, ConstMatrixRef data, std::default_random_engine& prng,
                     const unsigned int number_components, MatrixRef centroids, mlhip_ctx* ctx, mlhip_data* device_data)
 {

@@ -25,6 +25,10 @@ void init_centroids(const CentroidsInitialiser& initialiser, ConstMatrixRef data
 /// all-reduce). Single rank: 0 and n_local.
 void locate_rows(mlhip_ctx* ctx, Index n_local, Index& first_row, Index& n_global);
 
+/// Points per upload of the batch queries (EM::log_densities ..., KMeans::assign_labels): 2^24, or MLHIP_SCORE_ROWS (the knob that
+/// also sizes the chunks of mlhip_em_score's composed route).
+Index score_batch_rows();
+
 /// Sums a d x K block across ranks in place (each rank contributes its own columns, zeros elsewhere).
 void sum_across_ranks(mlhip_ctx* ctx, MatrixRef m);
 

@@ -348,6 +348,78 @@ void EM::assign_responsibilities(ConstVectorRef x, VectorRef u) const
     for (unsigned int k = 0; k < number_components_; ++k) u[k] /= total;
 }
 
+void EM::require_fitted_for(ConstMatrixRef data) const
+{
+    if (data.rows() != means().rows()) throw std::invalid_argument("Wrong data size");
+    (void)device::context();                                 // (no GPU: the "no CPU fallback" error, whatever the model holds)
+    if (inverse_covariances_.empty() || inverse_covariances_[0].rows() != data.rows())
+        throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+}
+
+void EM::score(ConstMatrixRef data, double* log_density, unsigned int* labels) const
+{
+    require_fitted_for(data);
+    const Index d = data.rows(), n = data.cols(), batch = Clustering::detail::score_batch_rows();
+    if (!n) return;
+    const std::size_t dd = static_cast<std::size_t>(d) * d;
+    std::vector<double> cov_flat(dd * number_components_);
+    for (unsigned int k = 0; k < number_components_; ++k) std::copy_n(covariances_[k].data(), dd, cov_flat.data() + dd * k);
+    mlhip_ctx* ctx = device::context();
+    for (Index first = 0; first < n; first += batch) {
+        const Index rows = std::min(batch, n - first);
+        DataGuard dev;
+        check(mlhip_data_upload(ctx, data.col(first), static_cast<uint32_t>(d), static_cast<uint64_t>(rows), data.outerStride(), &dev.h));
+        check(mlhip_em_score(ctx, dev.h, number_components_, MLHIP_COVARIANCE_FULL, mixing_probabilities_.data(), means_.data(),
+                             cov_flat.data(), log_density ? log_density + first : nullptr, labels ? labels + first : nullptr));
+    }
+}
+
+VectorXd EM::log_densities(ConstMatrixRef data) const
+{
+    VectorXd out(data.cols());
+    score(data, out.data(), nullptr);
+    return out;
+}
+
+double EM::mean_log_density(ConstMatrixRef data) const
+{
+    const VectorXd v = log_densities(data);
+    double sum = 0;
+    for (Index i = 0; i < v.size(); ++i) sum += v[i];
+    return sum / static_cast<double>(v.size());
+}
+
+std::vector<unsigned int> EM::assign_labels(ConstMatrixRef data) const
+{
+    std::vector<unsigned int> out(static_cast<std::size_t>(data.cols()));
+    score(data, nullptr, out.data());
+    return out;
+}
+
+MatrixXd EM::calculate_responsibilities(ConstMatrixRef data) const
+{
+    require_fitted_for(data);
+    const Index d = data.rows(), n = data.cols();
+    const unsigned int K = number_components_;
+    MatrixXd out(n, K);
+    if (!n) return out;
+    // (a batch holds its rows x K log-responsibilities on the device: at most 2^27 doubles of them)
+    const Index batch = std::max<Index>(256, std::min(Clustering::detail::score_batch_rows(), (Index(1) << 27) / K));
+    const std::size_t dd = static_cast<std::size_t>(d) * d;
+    std::vector<double> cov_flat(dd * K);
+    for (unsigned int k = 0; k < K; ++k) std::copy_n(covariances_[k].data(), dd, cov_flat.data() + dd * k);
+    mlhip_ctx* ctx = device::context();
+    for (Index first = 0; first < n; first += batch) {
+        const Index rows = std::min(batch, n - first);
+        DataGuard dev;
+        double ll = 0;
+        check(mlhip_data_upload(ctx, data.col(first), static_cast<uint32_t>(d), static_cast<uint64_t>(rows), data.outerStride(), &dev.h));
+        check(mlhip_em_expectation(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), cov_flat.data(), &ll));
+        check(mlhip_em_responsibilities(ctx, dev.h, K, out.data() + first, n));
+    }
+    return out;
+}
+
 void EM::process_covariances(const Index number_dimensions)
 {
     // Inverse and sqrt(det) of every covariance for the host point query (ML/EM.cpp:274-287).

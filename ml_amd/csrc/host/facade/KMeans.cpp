@@ -88,6 +88,30 @@ std::pair<unsigned int, double> KMeans::assign_label(ConstVectorRef x) const
     return std::make_pair(label, nearest);
 }
 
+std::vector<unsigned int> KMeans::assign_labels(ConstMatrixRef data, VectorXd* squared_distances) const
+{
+    if (data.rows() != centroids_.rows()) throw std::invalid_argument("Wrong data size");
+    const Index d = data.rows(), n = data.cols(), batch = Clustering::detail::score_batch_rows();
+    std::vector<unsigned int> labels(static_cast<std::size_t>(n));
+    if (squared_distances) squared_distances->resize(n);
+    if (!n) return labels;
+    mlhip_ctx* ctx = device::context();
+    for (Index first = 0; first < n; first += batch) {
+        const Index rows = std::min(batch, n - first);
+        struct Block {
+            mlhip_data* h = nullptr;
+            ~Block() { if (h) mlhip_data_free(h); }
+        } block;
+        check(mlhip_data_upload(ctx, data.col(first), static_cast<uint32_t>(d), static_cast<uint64_t>(rows), data.outerStride(), &block.h));
+        double inertia = 0;
+        uint64_t changed = 0;
+        check(mlhip_kmeans_assign(ctx, block.h, num_clusters_, centroids_.data(), &inertia, &changed));
+        check(mlhip_kmeans_labels(ctx, block.h, labels.data() + first));
+        if (squared_distances) check(mlhip_kmeans_distances(ctx, block.h, squared_distances->data() + first));
+    }
+    return labels;
+}
+
 void KMeans::fetch_assignment(mlhip_data* device_data, std::size_t sample_size)
 {
     mlhip_ctx* ctx = device::context();

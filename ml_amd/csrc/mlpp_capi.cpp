@@ -150,6 +150,31 @@ int mlpp_em_assign_responsibilities(const mlpp_em* h, const double* x, uint32_t 
     return guarded([&] { need(h); need(x); need(u); h->em.assign_responsibilities(ConstVectorRef(x, xlen), VectorRef(u, ulen)); });
 }
 
+int mlpp_em_score_samples(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out)
+{
+    return guarded([&] {
+        need(h); need(data); need(out);
+        const VectorXd v = h->em.log_densities(ConstMatrixRef(data, d, static_cast<Index>(n), d));
+        std::copy_n(v.data(), v.size(), out);
+    });
+}
+int mlpp_em_predict(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, uint32_t* out)
+{
+    return guarded([&] {
+        need(h); need(data); need(out);
+        const std::vector<unsigned int> v = h->em.assign_labels(ConstMatrixRef(data, d, static_cast<Index>(n), d));
+        std::copy(v.begin(), v.end(), out);
+    });
+}
+int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out)
+{
+    return guarded([&] {
+        need(h); need(data); need(out);
+        const MatrixXd r = h->em.calculate_responsibilities(ConstMatrixRef(data, d, static_cast<Index>(n), d));
+        std::copy_n(r.data(), r.size(), out);
+    });
+}
+
 // ---- KMeans ----
 int mlpp_kmeans_create(uint32_t K, mlpp_kmeans** out) { return guarded([&] { need(out); *out = new mlpp_kmeans(K); }); }
 int mlpp_kmeans_destroy(mlpp_kmeans* h) { delete h; return MLHIP_OK; }
@@ -184,6 +209,17 @@ int mlpp_kmeans_assign_label(const mlpp_kmeans* h, const double* x, uint32_t xle
         const auto r = h->km.assign_label(ConstVectorRef(x, xlen));
         *label = r.first;
         *dist2 = r.second;
+    });
+}
+
+int mlpp_kmeans_predict(const mlpp_kmeans* h, const double* data, uint64_t n, uint32_t d, uint32_t* labels, double* dist2)
+{
+    return guarded([&] {
+        need(h); need(data); need(labels);
+        VectorXd dist;
+        const std::vector<unsigned int> v = h->km.assign_labels(ConstMatrixRef(data, d, static_cast<Index>(n), d), dist2 ? &dist : nullptr);
+        std::copy(v.begin(), v.end(), labels);
+        if (dist2) std::copy_n(dist.data(), dist.size(), dist2);
     });
 }
 

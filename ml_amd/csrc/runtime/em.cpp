@@ -26,18 +26,17 @@ void ensure_em_workspace(mlhip_data* dt, int K)
 }
 
 
-/// Builds the per-component records for the route's E-step kernel and uploads them to params_dev (or `target`).
-RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs, DevBuf* target)
+/// The K component records for the route's E-step kernel, from host parameters into `target`: the host factorization through `staging`,
+/// or (d > 64) the device factorization with `work` as its scratch. `allow_fold`: matrix-core records may take the FOLD form.
+RecordForm build_records(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs,
+                         bool allow_fold, DevBuf& target, PinnedBuf& staging, DevBuf& work)
 {
     mlhip_ctx* ctx = dt->ctx;
-    ensure_em_workspace(dt, K);
-    const bool own = !target;
-    if (own) target = &dt->params_dev;
     {   // (params_dev / params_next are swapped by mlhip_em_iterate and may have been sized for diagonal records)
         size_t ps = (size_t)estep_param_stride(dt->D) * K * sizeof(double);
         if (estep_mfma4_supported(dt->D)) ps = std::max(ps, (size_t)estep_mfma4_param_stride(dt->D) * K * sizeof(double));
-        target->reserve(ps);
-        dt->params_host.reserve(ps);
+        target.reserve(ps);
+        staging.reserve(ps);
     }
     // d in 12..128: 4x4-block triangular matrix-core kernel (mfma4); below, and where the route asks for it, the scalar-fed one.
     const bool use_mfma4 = r.estep == Estep::kMatrix4;
@@ -48,8 +47,8 @@ RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* 
     if (r.records_on_device) {
         const int d = dt->d;
         const size_t n_par = (size_t)K * ((size_t)d * d + d + 1);
-        dt->close_work.reserve(sizeof(double) * em_close_work_doubles(d, K));
-        double* area = em_close_big_param_area(dt->close_work.as<double>(), d, K);
+        work.reserve(sizeof(double) * em_close_work_doubles(d, K));
+        double* area = em_close_big_param_area(work.as<double>(), d, K);
         // (straight from the caller's arrays: the covariances alone are K d^2 doubles -- 0.5 GB at K = 64, d = 1024 --, no pinned copy of that)
         HIP_CHECK(hipMemcpyAsync(area, mixing, sizeof(double) * K, hipMemcpyHostToDevice, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(area + K, means, sizeof(double) * K * d, hipMemcpyHostToDevice, ctx->stream));
@@ -58,24 +57,35 @@ RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* 
         ca.K = K; ca.d = d; ca.D = dt->D; ca.shift = dt->shift_dev.as<double>();
         ca.layout = form.layout;
         ca.mixing = area; ca.means = area + K; ca.covs = area + K + (size_t)K * d;
-        ca.records = target->as<double>();
+        ca.records = target.as<double>();
         ca.info = area + n_par;
-        ca.work = dt->close_work.as<double>();
+        ca.work = work.as<double>();
         launch_em_records_big(ca, ctx->stream);
         HIP_CHECK(hipGetLastError());
         ctx->sync();                                     // (the caller's arrays may change once this returns)
     } else if (use_mfma4) {
         // FOLD form (no per-component mean subtraction in the kernel) while every |W_k (mu_k - shift)| is small enough for
         // the parity tolerances; the exact form otherwise. Every rank decides from the same parameters.
-        form.fold = host::build_estep_params_mfma4(dt->d, dt->D, K, mixing, means, covs, r.fold_allowed ? dt->shift.data() : nullptr,
-                                                   kEstepFoldLimit, dt->params_host.as<double>());
-        HIP_CHECK(hipMemcpyAsync(target->p, dt->params_host.p, sizeof(double) * estep_mfma4_param_stride(dt->D) * K,
+        form.fold = host::build_estep_params_mfma4(dt->d, dt->D, K, mixing, means, covs, allow_fold ? dt->shift.data() : nullptr,
+                                                   kEstepFoldLimit, staging.as<double>());
+        HIP_CHECK(hipMemcpyAsync(target.p, staging.p, sizeof(double) * estep_mfma4_param_stride(dt->D) * K,
                                  hipMemcpyHostToDevice, ctx->stream));
     } else {
-        host::build_estep_params(dt->d, dt->D, K, mixing, means, covs, dt->params_host.as<double>());
-        HIP_CHECK(hipMemcpyAsync(target->p, dt->params_host.p, sizeof(double) * estep_param_stride(dt->D) * K,
+        host::build_estep_params(dt->d, dt->D, K, mixing, means, covs, staging.as<double>());
+        HIP_CHECK(hipMemcpyAsync(target.p, staging.p, sizeof(double) * estep_param_stride(dt->D) * K,
                                  hipMemcpyHostToDevice, ctx->stream));
     }
+    return form;
+}
+
+
+/// Builds the per-component records for the route's E-step kernel and uploads them to params_dev (or `target`).
+RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs, DevBuf* target)
+{
+    ensure_em_workspace(dt, K);
+    const bool own = !target;
+    if (own) target = &dt->params_dev;
+    const RecordForm form = build_records(dt, r, K, mixing, means, covs, r.fold_allowed, *target, dt->params_host, dt->close_work);
     if (own) dt->estep.records_are(form.layout, form.fold);
     return form;
 }
@@ -659,7 +669,7 @@ int mlhip_em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labe
         data->labels_dev.reserve(sizeof(uint32_t) * data->n_pad);
         RespArgs a{data->lw.as<double>(), data->ldr, data->lse.as<double>(), data->n, (int)K, nullptr, 0,
                    data->labels_dev.as<uint32_t>()};
-        launch_em_responsibilities(a, ctx->stream);
+        ctx->timed("em_resp", [&] { launch_em_responsibilities(a, ctx->stream); });
         HIP_CHECK(hipGetLastError());
         ctx->sync();
         download_columns(ctx, reinterpret_cast<char*>(labels), 0, data->labels_dev.as<char>(), 0, sizeof(uint32_t) * data->n, 1);

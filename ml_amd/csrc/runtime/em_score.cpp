@@ -1,0 +1,116 @@
+// mlhip_em_score: per-sample log-density and label of a resident block under caller-given mixture parameters -- the batch form of
+// EM::assign_responsibilities (reference ML/EM.cpp:176-188). One pass, no N x K block; every buffer is the call's own (taken from the
+// context's pool, given back at the end), so what earlier calls left on the handle -- E-step results, records, label history, the
+// statistics pass's call history -- stays as it was.
+#include "internal.hpp"
+
+namespace mlhip_rt {
+namespace {
+
+/// The composed route: the E-step kernel of `r.em` in its LSE-writing form on chunks of r.chunk_rows rows into a scratch block of
+/// K x chunk doubles, each followed by em_score_finish_kernel.
+void score_composed(mlhip_data* dt, const ScoreRoute& r, int K, const DevBuf& records, double* lse_out, uint32_t* labels_out)
+{
+    mlhip_ctx* ctx = dt->ctx;
+    const uint32_t chunk = r.chunk_rows;
+    DevBuf lw{&dt->pool}, lse{&dt->pool}, ll{&dt->pool};
+    lw.reserve(sizeof(double) * (size_t)chunk * K);
+    lse.reserve(sizeof(double) * chunk);
+    ll.reserve(sizeof(double) * kMaxLlPartials);
+    for (uint32_t row = 0; row < dt->n; row += chunk) {
+        const uint32_t rows = std::min(chunk, dt->n - row);   // (padded_samples(rows) <= chunk: the chunk is whole tiles)
+        EstepArgs a{};
+        a.xt = dt->xt.as<double>() + row; a.ldx = dt->ldx; a.n = rows; a.D = dt->D;
+        a.params = records.as<double>(); a.K = K;
+        a.lw = lw.as<double>(); a.ldr = chunk; a.lse = lse.as<double>();
+        a.ll_partials = ll.as<double>(); a.n_ll_partials = kMaxLlPartials;
+        a.shift = dt->shift_dev.as<double>(); a.fold = 0; a.with_lse = 1;
+        a.num_cus = ctx->num_cus;
+        a.plain = r.em.estep == Estep::kPlain;
+        int grid = 0;
+        ctx->timed("em_estep", [&] {
+            grid = r.em.estep == Estep::kMatrix4 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
+        });
+        if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
+        ctx->timed("em_score", [&] {
+            launch_em_score_finish(a.lw, a.ldr, a.lse, rows, K, lse_out ? lse_out + row : nullptr, labels_out ? labels_out + row : nullptr,
+                                   ctx->stream);
+        });
+        HIP_CHECK(hipGetLastError());
+    }
+    ctx->sync();                                         // (the scratch goes back to the pool behind the last kernel)
+}
+
+void em_score(mlhip_data* dt, int K, bool diag, const double* mixing, const double* means, const double* covs, double* log_density,
+              uint32_t* labels)
+{
+    mlhip_ctx* ctx = dt->ctx;
+    if (!dt->n || (!log_density && !labels)) return;
+    const ScoreRoute r = score_route(dt, K);
+    const int d = dt->d;
+    std::vector<double> full;
+    if (diag) {
+        // the same kernels on diagonal matrices, as ensure_lw (em.cpp) does after a diagonal step
+        full.assign((size_t)K * d * d, 0.0);
+        for (int k = 0; k < K; ++k)
+            for (int j = 0; j < d; ++j) full[((size_t)k * d + j) * d + j] = covs[(size_t)k * d + j];
+        covs = full.data();
+    }
+    DevBuf records{&dt->pool}, work{&dt->pool}, lse_dev{&dt->pool}, labels_dev{&dt->pool};
+    PinnedBuf staging{&dt->pool};
+    build_records(dt, r.em, K, mixing, means, covs, false, records, staging, work);   // (always the exact form: no FOLD)
+    if (log_density) lse_dev.reserve(sizeof(double) * dt->n_pad);
+    if (labels) labels_dev.reserve(sizeof(uint32_t) * dt->n_pad);
+    if (r.kernel == kScoreComposed) {
+        score_composed(dt, r, K, records, lse_dev.as<double>(), labels_dev.as<uint32_t>());
+    } else {
+        ScoreArgs a{};
+        a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.D = dt->D;
+        a.params = records.as<double>(); a.K = K;
+        a.lse = lse_dev.as<double>(); a.labels = labels_dev.as<uint32_t>();
+        int grid = 0;
+        ctx->timed("em_score", [&] {
+            grid = r.kernel == kScoreMatrix4 ? launch_em_score_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_score(a, ctx->stream);
+        });
+        if (grid < 0) throw Unsupported("score kernel not instantiated for this dimension");
+        HIP_CHECK(hipGetLastError());
+        ctx->sync();
+    }
+    if (labels) download_columns(ctx, reinterpret_cast<char*>(labels), 0, labels_dev.as<char>(), 0, sizeof(uint32_t) * dt->n, 1);
+    if (log_density) {
+        download_columns(ctx, reinterpret_cast<char*>(log_density), 0, lse_dev.as<char>(), 0, sizeof(double) * dt->n, 1);
+        // the kernels' lw leave the density's constant out, like the E-step's (ML/EM.cpp:197-198 applies it to the mean)
+        const double offset = (double)d * log_two_pi() / 2;
+        for (uint32_t i = 0; i < dt->n; ++i) log_density[i] -= offset;
+    }
+}
+
+}  // namespace
+}  // namespace mlhip_rt
+
+extern "C" {
+
+int mlhip_em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type, const double* mixing, const double* means,
+                   const double* covariances, double* log_density, uint32_t* labels)
+{
+    return guarded([&] {
+        if (ctx && ctx->group) { grp::em_score(ctx, data, K, covariance_type, mixing, means, covariances, log_density, labels); return; }
+        check_em_args(ctx, data, K);
+        require(mixing && means && covariances, "null argument");
+        require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL, "bad covariance_type");
+        em_score(data, (int)K, covariance_type == MLHIP_COVARIANCE_DIAGONAL, mixing, means, covariances, log_density, labels);
+    });
+}
+
+int mlhip_em_score_route(const mlhip_data* data, uint32_t K, int* kernel)
+{
+    return guarded([&] {
+        require(data && kernel && K >= 1, "bad argument");
+        if (!data->parts.empty()) data = data->parts[0];        // (a group's block: every shard takes the same route)
+        static_assert(kScoreScalarFed == MLHIP_SCORE_SCALAR_FED && kScoreMatrix4 == MLHIP_SCORE_MATRIX4 && kScoreComposed == MLHIP_SCORE_COMPOSED,
+                      "mlhip.h names the kernels by ScoreKernel");
+        *kernel = score_route(data, (int)K).kernel;
+    });
+}
+
+}  // extern "C"

@@ -580,6 +580,18 @@ void em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labels)
     });
 }
 
+void em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type, const double* mixing, const double* means,
+              const double* covs, double* log_density, uint32_t* labels)
+{
+    check_group_data(ctx, data);
+    // (every shard scores its own rows: no collective, nothing to put together but the rows' places in the caller's arrays)
+    each_shard(ctx, [&](int s, mlhip_ctx* c) {
+        const uint64_t lo = data->first_row[(size_t)s];
+        check_status(mlhip_em_score(c, data->parts[(size_t)s], K, covariance_type, mixing, means, covs,
+                                    log_density ? log_density + lo : nullptr, labels ? labels + lo : nullptr));
+    });
+}
+
 void kmeans_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, bool accumulate, const double* centroids, double* inertia,
                  uint64_t* n_changed, double* counts, double* centroids_out)
 {

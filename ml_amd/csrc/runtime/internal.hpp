@@ -549,6 +549,18 @@ struct EmRoute {
 /// `diag`: the call runs the diagonal-covariance kernel where it exists (em_diag.hip), else the full-covariance kernels.
 EmRoute em_route(const mlhip_data* data, int K, bool diag);
 
+/// mlhip_em_score: the scalar-fed score kernel (em_score.hip) and the matrix-core E-step's SCORE form (em_estep_mfma4.hip) where the
+/// E-step's route is scalar-fed / matrix-core; composed -- the E-step kernel on row chunks into a bounded scratch block, then
+/// em_score_finish_kernel -- above d = 128 and under MLHIP_SCORE=composed. (mlhip.h names the kernels by these values.)
+enum ScoreKernel : int { kScoreScalarFed = 0, kScoreMatrix4 = 1, kScoreComposed = 2 };
+constexpr uint64_t kScoreScratchBytes = uint64_t(256) << 20;
+struct ScoreRoute {
+    int kernel = kScoreScalarFed;
+    EmRoute em;                        // the E-step's route for the same block and K: record layout, where the records are factored
+    uint32_t chunk_rows = 0;           // composed: rows per chunk, a multiple of kSampleTile (MLHIP_SCORE_ROWS, else by kScoreScratchBytes)
+};
+ScoreRoute score_route(const mlhip_data* data, int K);
+
 struct KmRoute {
     bool pad = false;                  // the block runs on a copy zero-padded to a multiple of 4 dimensions (km_xt_pad)
     int kernel = kKmDirect;            // KmeansArgs::kernel
@@ -579,6 +591,12 @@ struct RecordForm {
     int layout;
     bool fold;
 };
+
+/// The K component records for the route's E-step kernel, from host parameters into `target`: the host factorization through `staging`,
+/// or (d > 64) the device factorization with `work` as its scratch; touches nothing else of the handle (prepare_estep passes the
+/// handle's buffers, mlhip_em_score buffers of its own). `allow_fold`: matrix-core records may take the FOLD form.
+RecordForm build_records(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs,
+                         bool allow_fold, DevBuf& target, PinnedBuf& staging, DevBuf& work);
 
 /// Builds the per-component records for the route's E-step kernel and uploads them to params_dev, whose descriptor they become -- or
 /// to `target` (mlhip_em_iterate's ring), whose descriptor is the caller's to keep. Returns the records' form.
@@ -738,6 +756,8 @@ void em_maximisation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int source, c
                      double* mixing_out, double* means_out, double* covs_out);
 void em_responsibilities(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* resp, int64_t ldr, uint64_t first, uint64_t count);
 void em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labels);
+void em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type, const double* mixing, const double* means,
+              const double* covs, double* log_density, uint32_t* labels);
 /// accumulate: the update's sums as well (mlhip_kmeans_step), else the assignment only
 void kmeans_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, bool accumulate, const double* centroids, double* inertia,
                  uint64_t* n_changed, double* counts, double* centroids_out);

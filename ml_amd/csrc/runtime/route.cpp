@@ -25,6 +25,8 @@ struct Switches {
     int sparse, sfeed;          // MLHIP_MSTATS_SPARSE, MLHIP_FUSED_SFEED: 0 / 1 forced, -1 automatic
     int fused_valu;             // MLHIP_FUSED_VALU: 0 never, 2 wherever built, -1 by shape
     int kmeans;                 // MLHIP_KMEANS=valu / mfma: kKmDirect / kKmMatrix forced, -1 automatic
+    bool score_composed;        // MLHIP_SCORE=composed
+    long score_rows;            // MLHIP_SCORE_ROWS=n: rows per chunk of the composed scoring route (0: by the scratch bound)
 };
 
 Switches read_switches()
@@ -48,6 +50,10 @@ Switches read_switches()
     s.fused_valu = valu == '0' ? 0 : valu == '2' ? 2 : -1;
     const char km = env_char("MLHIP_KMEANS");
     s.kmeans = km == 'v' ? kKmDirect : km == 'm' ? kKmMatrix : -1;
+    const char* score = std::getenv("MLHIP_SCORE");
+    s.score_composed = score && std::strcmp(score, "composed") == 0;
+    const char* rows = std::getenv("MLHIP_SCORE_ROWS");
+    s.score_rows = rows && *rows ? std::atol(rows) : 0;
     return s;
 }
 
@@ -85,6 +91,22 @@ EmRoute em_route(const mlhip_data* data, int K, bool diag)
     r.device_close = sw.device_close && em_close_supported(d) && (!diag || diag_kernel);
     // single rank, the vector-unit form (em_loop.cpp checks the grid)
     r.resident = sw.resident && r.fused && r.fused_form == kFusedValu && !ctx->reduce_fn && ctx->world_size <= 1;
+    return r;
+}
+
+ScoreRoute score_route(const mlhip_data* data, int K)
+{
+    const Switches sw = read_switches();
+    ScoreRoute r;
+    r.em = em_route(data, K, false);
+    if (sw.score_composed || r.em.estep == Estep::kBigDim || r.em.estep == Estep::kPlain) r.kernel = kScoreComposed;
+    else r.kernel = r.em.estep == Estep::kMatrix4 ? kScoreMatrix4 : kScoreScalarFed;
+    // the composed route's scratch: the largest whole number of sample tiles whose K x rows doubles stay within kScoreScratchBytes
+    uint64_t rows = sw.score_rows > 0 ? (uint64_t)sw.score_rows : kScoreScratchBytes / (sizeof(double) * (uint64_t)K);
+    rows = rows / kSampleTile * kSampleTile;
+    if (rows < (uint64_t)kSampleTile) rows = kSampleTile;
+    if (rows > data->n_pad) rows = data->n_pad;
+    r.chunk_rows = (uint32_t)rows;
     return r;
 }
 
