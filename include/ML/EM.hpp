@@ -54,6 +54,12 @@ public:
     @throw std::invalid_argument If `data` has no rows or fewer columns than components.
     @throw std::runtime_error On device failures (no GPU, HIP or collective errors). */
     DLL_DECLSPEC bool fit(ConstMatrixRef data) override;
+    /** Extension (not in the reference surface): the same fit of a WEIGHTED sample -- `weights[i]` >= 0 is the frequency weight of
+    column i of `data` (integer weights: the fit of the sample with point i repeated weights[i] times, without the copies). The
+    log-likelihood, its convergence test and every M-step are weighted; responsibilities() and labels() stay per point; the
+    initialisers see points, not weights; the N < K and N == K branches count points (mlhip_data_set_weights).
+    @throw std::invalid_argument If `weights.size() != data.cols()`, a weight is negative or not finite, or their total is not positive. */
+    DLL_DECLSPEC bool fit(ConstMatrixRef data, ConstVectorRef weights);
 
     unsigned int number_components() const { return number_components_; }
     unsigned int number_clusters() const override { return number_components(); }
@@ -100,6 +106,7 @@ public:
     DLL_DECLSPEC void release_device_data();
 
 private:
+    bool fit_weighted(ConstMatrixRef data, const double* weights);   // weights: null for the unweighted fit
     std::default_random_engine prng_;
     std::shared_ptr<const Clustering::CentroidsInitialiser> means_initialiser_;
     std::shared_ptr<const Clustering::ResponsibilitiesInitialiser> responsibilities_initialiser_;

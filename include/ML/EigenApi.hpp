@@ -205,11 +205,23 @@ public:
     void set_verbose(bool verbose) { detail::check(mlpp_em_set_verbose(h_, verbose ? 1 : 0)); }
     void set_maximise_first(bool maximise_first) { detail::check(mlpp_em_set_maximise_first(h_, maximise_first ? 1 : 0)); }
 
-    bool fit(Eigen::Ref<const Eigen::MatrixXd> data) override
+    bool fit(Eigen::Ref<const Eigen::MatrixXd> data) override { return fit_block(data, nullptr); }
+    /** Extension: the fit of a weighted sample (ml::EM::fit(data, weights) of ML/EM.hpp): weights(i) >= 0 is the frequency weight of
+    column i. @throw std::invalid_argument If `weights.size() != data.cols()` or the weights are refused. */
+    bool fit(Eigen::Ref<const Eigen::MatrixXd> data, Eigen::Ref<const Eigen::VectorXd> weights)
+    {
+        if (weights.size() != data.cols()) throw std::invalid_argument("EM: One weight per data point required");
+        return fit_block(data, weights.data());                      // (a Ref<const VectorXd> is contiguous)
+    }
+
+private:
+    bool fit_block(Eigen::Ref<const Eigen::MatrixXd> data, const double* weights)
     {
         const detail::Block block(data);
         int converged = 0;
-        detail::check(mlpp_em_fit(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()), &converged));
+        const uint64_t n = static_cast<uint64_t>(data.cols());
+        const uint32_t dims = static_cast<uint32_t>(data.rows());
+        detail::check(weights ? mlpp_em_fit_weighted(h_, block.p, weights, n, dims, &converged) : mlpp_em_fit(h_, block.p, n, dims, &converged));
         const Eigen::Index d = data.rows();
         means_.resize(d, number_components_);
         detail::check(mlpp_em_means(h_, means_.data()));
@@ -228,6 +240,7 @@ public:
         return converged_;
     }
 
+public:
     unsigned int number_components() const { return number_components_; }
     unsigned int number_clusters() const override { return number_components_; }
     const Eigen::MatrixXd& means() const { return means_; }

@@ -126,6 +126,33 @@ int mlhip_data_shard_rows(const mlhip_data* data, int shard, uint64_t* first_row
 /* Global column means used as the numerical shift of the second-moment accumulation (d doubles). */
 int mlhip_data_shift(const mlhip_data* data, double* shift);
 
+/* EXTENSION (no counterpart in the reference): frequency weights w_i of the block's rows -- de-duplicated or binned samples, importance
+ * weights, coresets -- without replicating rows. `weights` holds this rank's n_local values (a device group: all N, sharded like the
+ * rows); every w_i finite and >= 0, their total W over ALL ranks > 0 (checked on the device, W summed in a fixed order per shard and
+ * all-reduced like the statistics; otherwise MLHIP_E_INVALID_ARGUMENT on every rank and the block is left UNWEIGHTED). NULL removes
+ * the weights: every entry point then does exactly what it did before they were set. The array is only read during the call; the
+ * weights stay with the handle until replaced or removed. E-step results the handle holds are dropped. With weights attached:
+ *   * every log-likelihood the EM entry points report (mlhip_em_expectation / _step / _step_diag / _iterate and its history) is
+ *     (1/W) sum_i w_i log sum_k pi_k N(x_i | mu_k, Sigma_k), and the convergence test of mlhip_em_iterate runs on it;
+ *   * every M-step (mlhip_em_step / _step_diag / _iterate / _maximisation / _maximisation_from / _from_labels, the refinement pass
+ *     about a component's own mean included) forms sum_i w_i r_ik vech(xt_i xt_i^T); mixing_k = S0_k / W; the caller's
+ *     responsibilities / labels are not changed;
+ *   * mlhip_sample_covariance is sum_i w_i (x_i - m)(x_i - m)^T / (W - 1) about m = sum_i w_i x_i / W.
+ * With integer weights this is the unweighted result on the sample with row i repeated w_i times; scaling all weights by a constant
+ * changes nothing beyond rounding. NOT weighted: per-row results (mlhip_em_responsibilities, mlhip_em_labels, mlhip_em_score: a row
+ * of weight 0 still gets its responsibilities, its label and its density), the statistics shift (mlhip_data_shift stays the plain
+ * column mean), mlhip_xxt_xy, mlhip_random_partition_means, and every K-means and kpp_* entry point (their sums are exact
+ * integer-limb accumulations a product w x does not live on): K-means and the initialisers see rows, not weights.
+ * A weighted block runs the E-step tier of its shape; where the unweighted fit runs the self-normalising statistics form (d = 12 ..
+ * 128, K <= 64) so does the weighted one, with the weight applied while the kernel stages a responsibility (one exponential per pair,
+ * no second N x K block); elsewhere one pass writes w_i r_ik for the statistics kernel of the shape. It never takes the fused,
+ * resident, sparse or diagonal-kernel routes (mlhip_em_route reports the route it takes). Responsibilities and labels after a
+ * weighted E-step are, bit for bit, those of the unweighted E-step on the same kernel route -- the default route wherever that is not
+ * the fused kernel (there: the route of MLHIP_FUSED=0). */
+int mlhip_data_set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weights);
+/* W, the all-reduced total of the attached weights; n_global (as a double) for an unweighted block. */
+int mlhip_data_weight_sum(const mlhip_data* data, double* total);
+
 /* ---- Gaussian-mixture EM -------------------------------------------------------------------------- */
 /* One EM iteration == EM::expectation_step + EM::maximisation_step (ML/EM.cpp:190-263, incl.
  * process_covariances :274-287) on the resident shard, statistics all-reduced across ranks.

@@ -56,6 +56,8 @@ int mlpp_em_set_maximise_first(mlpp_em* h, int v);
 /* Extension (ml::EM::set_covariance_type): 0 = full covariances (the reference), 1 = diagonal. */
 int mlpp_em_set_covariance_type(mlpp_em* h, int diagonal);
 int mlpp_em_fit(mlpp_em* h, const double* data, uint64_t n, uint32_t d, int* converged);
+/* Extension (ml::EM::fit(data, weights)): the fit of a weighted sample, weights[i] >= 0 the frequency weight of point i (n values). */
+int mlpp_em_fit_weighted(mlpp_em* h, const double* data, const double* weights, uint64_t n, uint32_t d, int* converged);
 int mlpp_em_number_components(const mlpp_em* h, uint32_t* out);
 int mlpp_em_dims(const mlpp_em* h, uint32_t* d, uint64_t* n);
 int mlpp_em_means(const mlpp_em* h, double* out /* d x K column-major, like EM::means() */);

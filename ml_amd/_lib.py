@@ -252,6 +252,16 @@ class Context:
         return ms.value, cnt.value
 
 
+def require_weights(w, n):
+    """Row weights as the library takes them: TypeError unless a float64 numpy array (no conversion, like `fit`'s data),
+    ValueError unless 1-D, C-contiguous and of length n. Checked before any device call."""
+    if not (isinstance(w, np.ndarray) and w.dtype == np.float64):
+        raise TypeError("weights must be a float64 numpy array")
+    if w.ndim != 1 or not w.flags.c_contiguous or w.shape[0] != n:
+        raise ValueError(f"weights must be a 1-D C-contiguous array with one value per row ({n})")
+    return w
+
+
 class EmRouteInfo(C.Structure):
     """mlhip_em_route_info"""
     _fields_ = [(name, C.c_int32) for name in ("estep", "fused", "fused_form", "self_norm", "sparse", "balanced", "fold_allowed",
@@ -311,6 +321,22 @@ class Data:
         out = np.empty(self.d)
         check(lib.mlhip_data_shift(self._h, dptr(out)))
         return out
+
+    def set_weights(self, w):
+        """Frequency weights of the block's rows (mlhip_data_set_weights): a 1-D C-contiguous float64 array of length N, every
+        value finite and >= 0, their total positive; None removes them. TypeError for another type or dtype, ValueError for a
+        wrong length or refused values (the block is then unweighted). EM entry points are weighted from here on; per-row
+        results (responsibilities, labels, em_score), K-means and the initialisers are not."""
+        if w is not None:
+            w = require_weights(w, self.n)
+        check(lib.mlhip_data_set_weights(self.ctx.handle, self._h, None if w is None else dptr(w)))
+
+    @property
+    def weight_sum(self):
+        """W, the all-reduced total of the attached weights (the row count of an unweighted block)."""
+        total = C.c_double()
+        check(lib.mlhip_data_weight_sum(self._h, C.byref(total)))
+        return total.value
 
     # ---- EM -----------------------------------------------------------------------------------------------
     # Parameter conventions (Python side): means K x d, covariances K x d x d, mixing K.

@@ -197,12 +197,21 @@ class EM:
             raise ValueError("covariance_type must be 'full' or 'diag'")
         _check(_l.mlpp_em_set_covariance_type(self._h, int(covariance_type == "diag")))
 
-    def fit(self, data):
-        """Fits the components to the data (2D array with data points in rows). Returns True if EM converged."""
+    def fit(self, data, sample_weight=None):
+        """Fits the components to the data (2D array with data points in rows). Returns True if EM converged.
+
+        Extension: `sample_weight`, a 1-D C-contiguous float64 array with one frequency weight >= 0 per row (integer weights: the
+        fit of the data with row i repeated sample_weight[i] times, without the copies). TypeError for another type or dtype,
+        ValueError for a wrong length, a negative or non-finite weight or a total that is not positive. The log-likelihood and
+        every M-step are weighted; `responsibilities` and `labels` stay per row; initialisers see rows, not weights."""
         data = _require_data(data)
         n, d = data.shape
         conv = C.c_int()
-        _check(_l.mlpp_em_fit(self._h, _dp(data), C.c_uint64(n), d, C.byref(conv)))
+        if sample_weight is None:
+            _check(_l.mlpp_em_fit(self._h, _dp(data), C.c_uint64(n), d, C.byref(conv)))
+        else:
+            w = _lib.require_weights(sample_weight, n)
+            _check(_l.mlpp_em_fit_weighted(self._h, _dp(data), _dp(w), C.c_uint64(n), d, C.byref(conv)))
         return bool(conv.value)
 
     def _dims(self):

@@ -544,7 +544,7 @@ int launch_em_estep_big(const EstepArgs& a, int num_cus, hipStream_t stream)
 int launch_em_mstats_big(const MstatsArgs& a, int num_cus, hipStream_t stream)
 {
     const int F = stats_count(a.d);
-    if (a.mode == kFromLogRespSelfNorm) return -3;
+    if (a.mode == kFromLogRespSelfNorm || a.mode == kFromLogRespSelfNormWeighted) return -3;
     int splits = big_dim_splits(a.d, a.K, num_cus);
     const uint32_t n_chunks = (a.n + SC - 1) / SC;
     if ((uint32_t)splits > n_chunks) splits = (int)(n_chunks ? n_chunks : 1);

@@ -101,6 +101,9 @@ enum MstatsMode : int {
     kFromResp = 1,      // r = lw                     (plain responsibilities: caller-given, one-hot, or all ones)
     kFromLogRespSelfNorm = 2   // r = e_k / sum_k e_k with the normalisation done by the statistics kernel itself (wide kernel, one
                                // row-block group); launch_em_reduce then also finishes lse = max + log(sum) and the ll partials
+    ,
+    kFromLogRespSelfNormWeighted = 3   // mode 2 on a block with row weights (MstatsArgs::weights): r w_i is accumulated, the ll
+                                       // partials are those of w_i lse_i; lse itself stays the sample's own
 };
 struct MstatsArgs {
     const double* xt; size_t ldx; uint32_t n; int d;        // d = true dimension
@@ -114,6 +117,7 @@ struct MstatsArgs {
     unsigned long long* nz_count;                            // kFromLogRespSelfNorm (may be null): += nonzero responsibilities
     int plain;                                               // 1: the plain forms -- d <= kRegDim: whole column blocks per wave (no
                                                              // balanced dealing); d > kMaxDim: the plain tier even where big_dim.hip applies
+    const double* weights;                                   // kFromLogRespSelfNormWeighted: the rows' weights (n_pad doubles, zero beyond n)
 };
 int launch_em_mstats_generic(const MstatsArgs& a, hipStream_t stream);   // d > kMaxDim: writes ONE partial block [K][F]
 /// 128 < d <= 1024 on the matrix cores (big_dim.hip); the plain tier above it (and where the caller asks for it: Args::plain).
@@ -243,6 +247,24 @@ int launch_em_mstats(const MstatsArgs& a, int num_cus, hipStream_t stream);
 void launch_em_reduce(const MstatsArgs& a, int num_cus, int n_partials, hipStream_t stream);
 /// out[0] = sum of n_ll log-likelihood partials (fixed order).
 void launch_ll_reduce(const double* ll_partials, int n_ll, double* out, hipStream_t stream);
+
+// ---- row weights (em_weights.hip): the passes a weighted block adds next to the unweighted kernels ----
+/// Partials one weights pass writes (one per workgroup): a function of n alone, so every pass over the same block sums in the same order.
+int weights_grid(uint32_t n);
+/// Attach pass over `n` weights (w has n_pad entries; the pass zeroes w[n .. n_pad)): sum_partials[b] = workgroup b's sum of the valid
+/// weights (finite, >= 0), bad_partials[b] = how many of its weights are not valid. Returns the number of partials.
+int launch_weights_attach(double* w, uint32_t n, uint32_t n_pad, double* sum_partials, double* bad_partials, hipStream_t stream);
+/// ll_partials[b] = workgroup b's sum of w_i lse_i over the rows with w_i != 0, in the layout launch_ll_reduce / launch_em_reduce read.
+/// Returns the number of partials (<= 1024).
+int launch_weighted_ll(const double* w, const double* lse, uint32_t n, double* ll_partials, hipStream_t stream);
+/// out[k*ldo + i] = w_i r_ik for i < n, 0 for n <= i < n_pad, with r_ik = exp(src - lse_i) (mode kFromLogResp) or src (kFromResp),
+/// src = src[k*lds + i]: the plain responsibilities the statistics kernels then take in mode kFromResp.
+/// After a weighted self-normalising statistics pass: em_lse_finish_kernel's work (lse[i] = max + log(esum[i]) in place) with the
+/// partials of w_i lse_i in its layout and on its tree; `n_ll` workgroups, the number launch_em_reduce uses for the unweighted form.
+void launch_weighted_lse_finish(double* lse, const double* esum, const double* w, uint32_t n, int n_ll, double* ll_partials,
+                                hipStream_t stream);
+void launch_weighted_resp(const double* src, size_t lds, const double* lse, int mode, const double* w, uint32_t n, uint32_t n_pad, int K,
+                          double* out, size_t ldo, hipStream_t stream);
 
 struct RespArgs {
     const double* lw; size_t ldr; const double* lse; uint32_t n; int K;

@@ -194,7 +194,7 @@ int launch_em_mstats(const MstatsArgs& a, int num_cus, hipStream_t stream)
     int grid_x = p.grid_x;
     if ((uint32_t)grid_x > n_tiles) grid_x = (int)(n_tiles ? n_tiles : 1);
     if ((size_t)grid_x * p.KP * p.FP > a.partials_capacity) return -2;
-    if (a.mode == kFromLogRespSelfNorm && !(p.wide && p.n_rbg == 1)) return -3;
+    if ((a.mode == kFromLogRespSelfNorm || a.mode == kFromLogRespSelfNormWeighted) && !(p.wide && p.n_rbg == 1)) return -3;
     return p.wide ? launch_wide(a, p, grid_x, stream) : launch_small(a, p, grid_x, stream);
 }
 
@@ -216,10 +216,13 @@ void launch_em_reduce(const MstatsArgs& a, int num_cus, int grid_x, hipStream_t 
     // a self-normalising pass left (max, exp-sum) per sample: finish lse and produce the log-likelihood partials first
     const double* ll = a.ll_partials;
     int n_ll = a.n_ll_partials;
-    if (a.mode == kFromLogRespSelfNorm) {
+    if (a.mode == kFromLogRespSelfNorm || a.mode == kFromLogRespSelfNormWeighted) {
         const uint32_t n_pad = padded_samples(a.n);
         n_ll = (int)((n_pad / 256 < 1024u) ? n_pad / 256 : 1024u);
-        hipLaunchKernelGGL(em_lse_finish_kernel, dim3(n_ll), dim3(256), 0, stream, a.lse_out, a.ll_out, a.n, n_pad, a.ll_scratch);
+        if (a.mode == kFromLogRespSelfNorm)
+            hipLaunchKernelGGL(em_lse_finish_kernel, dim3(n_ll), dim3(256), 0, stream, a.lse_out, a.ll_out, a.n, n_pad, a.ll_scratch);
+        else
+            launch_weighted_lse_finish(a.lse_out, a.ll_out, a.weights, a.n, n_ll, a.ll_scratch, stream);
         ll = a.ll_scratch;
     }
     hipLaunchKernelGGL(em_reduce_kernel, dim3(red_blocks), dim3(256), 0, stream, a.partials, grid_x, p.KP, p.FP, a.K, F,

@@ -55,10 +55,13 @@ __device__ __forceinline__ double allreduce_sum_bits345(double v)
 /// Normalises the NRV log-responsibilities rv[] of sample `sR` (components NRV cg .. NRV cg + NRV - 1; the 8 lanes with the
 /// same lane & 7 hold all K of the sample), writes r = exp(lw - max) / sum to Rb[sR * RS + component] (0 for padding samples
 /// and components >= K) and, if `write_lse`, max and sum to lse_out[i] / esum_out[i]. Returns how many of the wave's 64 x NRV
-/// written responsibilities are nonzero (wave-uniform).
-template <int NRV, int RS>
+/// written responsibilities are nonzero (wave-uniform). WEIGHTED (a block with row weights): the value written is r w_i, the
+/// sample's frequency weight `wi` applied AFTER the normalisation (one rounding more than r); max and sum -- hence lse -- stay the
+/// sample's own.
+template <int NRV, int RS, bool WEIGHTED = false>
 __device__ __forceinline__ uint32_t stage_self_norm(double (&rv)[NRV], int cg, int K, uint32_t i, bool live, double* Rb, int sR,
-                                                     bool write_lse, double* __restrict__ lse_out, double* __restrict__ esum_out)
+                                                     bool write_lse, double* __restrict__ lse_out, double* __restrict__ esum_out,
+                                                     double wi = 1.0)
 {
     double m = -__builtin_inf();
 #pragma unroll
@@ -79,7 +82,8 @@ __device__ __forceinline__ uint32_t stage_self_norm(double (&rv)[NRV], int cg, i
     uint32_t nonzero = 0;
 #pragma unroll
     for (int it = 0; it < NRV; ++it) {
-        const double r = rv[it] * inv;
+        double r = rv[it] * inv;
+        if constexpr (WEIGHTED) r = wi != 0.0 ? r * wi : 0.0;         // a row of weight 0 is not in the sample, whatever its density
         Rb[sR * RS + cg * NRV + it] = r;
         nonzero += (uint32_t)__builtin_popcountll(__ballot(r != 0.0));
     }

@@ -18,11 +18,23 @@
 //     xor-shuffle steps inside the wave, no extra barrier; lanes of component group 0 write the sample's maximum and the sum of
 //     its exponentials, which a small follow-up kernel (em_lse_finish_kernel, em_mstats.hip) turns into lse and the log-
 //     likelihood partials. Needs all K components in this workgroup (a single row-block group, K <= 64).
+//     3 = form 2 on a block with row weights: the staged value is r w_i (stage_self_norm<WEIGHTED>), the weights arrive in the
+//     `lse` argument, which form 2 does not read (the kernels' signature, and with it every unweighted instantiation, stays as it
+//     was); max and sum are written as in form 2, the weighted follow-up kernel is in em_weights.hip. Forms 0-2 are compiled in
+//     parts 1-8, form 3 alone in parts 9-16: an unweighted fit loads no more code than before.
 #include <type_traits>
 #include "parts.hpp"
 
 #include "em_mstats_common.hpp"
 #include "em_mstats_stage.hpp"
+
+// parts 9-16: the weighted self-normalising form (EXP = 3) of the shapes of parts 1-8
+#if MLHIP_PART > 8
+#define MLHIP_WIDE_WEIGHTED 1
+#define MLHIP_WIDE_BASE (MLHIP_PART - 8)
+#else
+#define MLHIP_WIDE_BASE MLHIP_PART
+#endif
 
 #ifndef MSTATS_UNROLL_GEN
 #define MSTATS_UNROLL_GEN 16   // the 16 sample groups of a tile, all of them (see the contraction loop)
@@ -110,7 +122,7 @@ __global__ __launch_bounds__(512, 2) void em_mstats_wide_kernel(
     // (contiguous components per thread: with the odd row stride RS the 16 lanes of an LDS write phase then hit 16 different
     // bank pairs; the interleaved assignment cg + 8 it collides up to 8-fold and cost 1 ms at the headline shape).
     const int sS = lane;
-    const int sR = EXP == 2 ? 8 * wave + (lane & 7) : lane;
+    const int sR = EXP >= 2 ? 8 * wave + (lane & 7) : lane;
     const int cg = lane >> 3;
     double xv[NXV], rv[NRV], lv = 0.0;
     uint32_t nonzero = 0;                // EXP == 2: nonzero responsibilities staged by this wave (the runtime's kernel choice)
@@ -118,9 +130,10 @@ __global__ __launch_bounds__(512, 2) void em_mstats_wide_kernel(
         const uint32_t i = tile * TS + sS;           // < n_pad: always inside the allocation
 #pragma unroll
         for (int it = 0; it < NXV; ++it) xv[it] = xt[(size_t)min(wave + NW * it, D - 1) * ldx + i];
-        if constexpr (EXP == 2) {
+        if constexpr (EXP >= 2) {
 #pragma unroll
             for (int it = 0; it < NRV; ++it) rv[it] = lw[(size_t)min(cg * NRV + it, K - 1) * ldr + tile * TS + sR];
+            if constexpr (EXP == 3) lv = lse[tile * TS + sR];   // the sample's weight (n_pad entries, zero beyond n)
         } else {
 #pragma unroll
             for (int it = 0; it < NRV; ++it) rv[it] = lw[(size_t)min(rb0 * 16 + wave + NW * it, K - 1) * ldr + i];
@@ -128,7 +141,10 @@ __global__ __launch_bounds__(512, 2) void em_mstats_wide_kernel(
         }
     };
     auto stage = [&](double* Xb, double* Rb, uint32_t tile) {
-        if constexpr (EXP == 2) {
+        if constexpr (EXP == 3) {
+            const uint32_t i = tile * TS + sR;
+            nonzero += stage_self_norm<NRV, RS, true>(rv, cg, K, i, i < n, Rb, sR, blockIdx.y == 0, lse_out, ll_out, lv);
+        } else if constexpr (EXP == 2) {
             const uint32_t i = tile * TS + sR;
             nonzero += stage_self_norm<NRV, RS>(rv, cg, K, i, i < n, Rb, sR, blockIdx.y == 0, lse_out, ll_out);
         } else {
@@ -276,7 +292,7 @@ __global__ __launch_bounds__(512, 2) void em_mstats_wide_kernel(
         __builtin_amdgcn_s_setprio(0);
     }
 
-    if constexpr (EXP == 2) {
+    if constexpr (EXP >= 2) {
         if (nz_count && blockIdx.y == 0 && lane == 0) atomicAdd(nz_count, (unsigned long long)nonzero);   // (an integer sum: order-free)
     }
     // ---- epilogue: partials[blockIdx.x][k][f]; C/D layout of v_mfma_f64_16x16x4: col = lane&15, row = (lane>>4) + 4*reg
@@ -317,6 +333,11 @@ void launch_t(const MstatsArgs& a, const Plan& p, int grid_x, hipStream_t stream
     constexpr int XSD = tile_stride<DM>();
     const size_t smem = (DM <= kMidDim ? 2 : 1) * sizeof(double) * ((size_t)TS * XSD + (size_t)TS * (RBW * 16 + 1));
     const dim3 grid(grid_x, p.n_rbg * p.n_cbg);
+#ifdef MLHIP_WIDE_WEIGHTED
+    hipLaunchKernelGGL((em_mstats_wide_kernel<RBW, CBW, 3, DM, CBT>), grid, dim3(512), smem, stream, a.xt, a.ldx, a.n, a.d,
+                       padded_dim(a.d), a.shift, a.lw, a.ldr, a.weights, a.K, p.n_rbg, p.CB, a.partials, p.KP, p.FP,
+                       a.lse_out, a.ll_out, a.nz_count);
+#else
     if (a.mode == kFromLogRespSelfNorm)
         hipLaunchKernelGGL((em_mstats_wide_kernel<RBW, CBW, 2, DM, CBT>), grid, dim3(512), smem, stream, a.xt, a.ldx, a.n, a.d,
                            padded_dim(a.d), a.shift, a.lw, a.ldr, a.lse, a.K, p.n_rbg, p.CB, a.partials, p.KP, p.FP,
@@ -329,6 +350,7 @@ void launch_t(const MstatsArgs& a, const Plan& p, int grid_x, hipStream_t stream
         hipLaunchKernelGGL((em_mstats_wide_kernel<RBW, CBW, 0, DM, CBT>), grid, dim3(512), smem, stream, a.xt, a.ldx, a.n, a.d,
                            padded_dim(a.d), a.shift, a.lw, a.ldr, a.lse, a.K, p.n_rbg, p.CB, a.partials, p.KP, p.FP,
                            nullptr, nullptr, nullptr);
+#endif
 }
 
 }  // namespace
@@ -339,9 +361,14 @@ void launch_t(const MstatsArgs& a, const Plan& p, int grid_x, hipStream_t stream
 // kernels instead of the 2.1 MB of all 147 instantiations (round 5: the first call of a shape was dominated by that load).
 int MLHIP_PART_FN(launch_wide)(const MstatsArgs& a, const Plan& p, int grid_x, hipStream_t stream)
 {
-    constexpr int R = (MLHIP_PART - 1) % 4 + 1;
+    constexpr int R = (MLHIP_WIDE_BASE - 1) % 4 + 1;
     if (p.RBW != R) return -1;
-#if MLHIP_PART > 4
+#ifdef MLHIP_WIDE_WEIGHTED
+    if (a.mode != kFromLogRespSelfNormWeighted || !a.weights) return -1;
+#else
+    if (a.mode == kFromLogRespSelfNormWeighted) return -1;
+#endif
+#if MLHIP_WIDE_BASE > 4
     // 32 < d <= 128: 38..525 column blocks in column groups of 8 waves x (3, 4 or 5) blocks
 #define MLHIP_BIG(C) \
     if (p.CBW == C) { \
@@ -386,10 +413,27 @@ int launch_wide_part5(const MstatsArgs&, const Plan&, int, hipStream_t);
 int launch_wide_part6(const MstatsArgs&, const Plan&, int, hipStream_t);
 int launch_wide_part7(const MstatsArgs&, const Plan&, int, hipStream_t);
 int launch_wide_part8(const MstatsArgs&, const Plan&, int, hipStream_t);
+int launch_wide_part9(const MstatsArgs&, const Plan&, int, hipStream_t);
+int launch_wide_part10(const MstatsArgs&, const Plan&, int, hipStream_t);
+int launch_wide_part11(const MstatsArgs&, const Plan&, int, hipStream_t);
+int launch_wide_part12(const MstatsArgs&, const Plan&, int, hipStream_t);
+int launch_wide_part13(const MstatsArgs&, const Plan&, int, hipStream_t);
+int launch_wide_part14(const MstatsArgs&, const Plan&, int, hipStream_t);
+int launch_wide_part15(const MstatsArgs&, const Plan&, int, hipStream_t);
+int launch_wide_part16(const MstatsArgs&, const Plan&, int, hipStream_t);
 
 int launch_wide(const MstatsArgs& a, const Plan& p, int grid_x, hipStream_t stream)
 {
     const bool big = a.d > kRegDim;
+    if (a.mode == kFromLogRespSelfNormWeighted) {
+        switch (p.RBW) {
+        case 1: return big ? launch_wide_part13(a, p, grid_x, stream) : launch_wide_part9(a, p, grid_x, stream);
+        case 2: return big ? launch_wide_part14(a, p, grid_x, stream) : launch_wide_part10(a, p, grid_x, stream);
+        case 3: return big ? launch_wide_part15(a, p, grid_x, stream) : launch_wide_part11(a, p, grid_x, stream);
+        case 4: return big ? launch_wide_part16(a, p, grid_x, stream) : launch_wide_part12(a, p, grid_x, stream);
+        default: return -1;
+        }
+    }
     switch (p.RBW) {
     case 1: return big ? launch_wide_part5(a, p, grid_x, stream) : launch_wide_part1(a, p, grid_x, stream);
     case 2: return big ? launch_wide_part6(a, p, grid_x, stream) : launch_wide_part2(a, p, grid_x, stream);

@@ -163,7 +163,7 @@ int launch_em_mstats_generic(const MstatsArgs& a, hipStream_t stream)
 {
     const int F = stats_count(a.d);
     if ((size_t)a.K * F > a.partials_capacity) return -2;
-    if (a.mode == kFromLogRespSelfNorm) return -3;
+    if (a.mode == kFromLogRespSelfNorm || a.mode == kFromLogRespSelfNormWeighted) return -3;
     hipLaunchKernelGGL(em_mstats_generic_kernel, dim3(a.d + 1, a.K), dim3(256), 0, stream, a.xt, a.ldx, a.n, a.d, a.shift, a.lw, a.ldr,
                        a.lse, a.mode, a.partials, F);
     return 1;                                                               // one partial block

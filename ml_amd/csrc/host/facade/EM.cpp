@@ -136,7 +136,15 @@ MatrixXd EM::responsibilities_rows(Index first_row, Index number_rows) const
     return out;
 }
 
-bool EM::fit(ConstMatrixRef data)
+bool EM::fit(ConstMatrixRef data) { return fit_weighted(data, nullptr); }
+
+bool EM::fit(ConstMatrixRef data, ConstVectorRef weights)
+{
+    if (weights.size() != data.cols()) throw std::invalid_argument("EM: One weight per data point required");
+    return fit_weighted(data, weights.data());
+}
+
+bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
 {
     converged_ = false;
     steps_done_ = 0;
@@ -181,6 +189,9 @@ bool EM::fit(ConstMatrixRef data)
     // ---- move the sample block to HBM (stays resident for the whole fit) ---------------------------------
     DataGuard dev;
     check(mlhip_data_upload(ctx, data.data(), number_dimensions, sample_size, data.outerStride(), &dev.h));
+    // Row weights stay attached for the handle's lifetime: every statistics pass and log-likelihood below is weighted, the
+    // initialisers' draws and the nearest-centroid pass see rows (mlhip.h, mlhip_data_set_weights).
+    if (weights) check(mlhip_data_set_weights(ctx, dev.h, weights));
     uint64_t n_global = 0;
     check(mlhip_data_shape(dev.h, nullptr, nullptr, &n_global));
     if (n_global < K) throw std::invalid_argument("EM: Not enough data ");       // the same on every rank

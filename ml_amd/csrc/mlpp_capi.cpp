@@ -127,6 +127,17 @@ int mlpp_em_fit(mlpp_em* h, const double* data, uint64_t n, uint32_t d, int* con
         *converged = ok ? 1 : 0;
     });
 }
+int mlpp_em_fit_weighted(mlpp_em* h, const double* data, const double* weights, uint64_t n, uint32_t d, int* converged)
+{
+    return guarded([&] {
+        need(h); need(converged);
+        if (n && d) need(data);
+        if (n) need(weights);
+        const bool ok = h->em.fit(ConstMatrixRef(data, d, static_cast<Index>(n)), ConstVectorRef(weights, static_cast<Index>(n)));
+        h->d = d; h->n = static_cast<Index>(n);
+        *converged = ok ? 1 : 0;
+    });
+}
 int mlpp_em_number_components(const mlpp_em* h, uint32_t* out) { return guarded([&] { need(h); need(out); *out = h->em.number_components(); }); }
 int mlpp_em_dims(const mlpp_em* h, uint32_t* d, uint64_t* n) { return guarded([&] { need(h); if (d) *d = static_cast<uint32_t>(h->em.means().rows()); if (n) *n = static_cast<uint64_t>(h->em.labels().size()); }); }
 int mlpp_em_means(const mlpp_em* h, double* out) { return guarded([&] { need(h); need(out); std::copy_n(h->em.means().data(), h->em.means().size(), out); }); }

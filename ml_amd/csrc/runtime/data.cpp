@@ -219,6 +219,54 @@ int mlhip_data_shift(const mlhip_data* data, double* shift)
     });
 }
 
+int mlhip_data_set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weights)
+{
+    return guarded([&] {
+        if (ctx && ctx->group) { grp::set_weights(ctx, data, weights); return; }
+        check_em_args(ctx, data, 1);
+        // whatever the outcome, E-step results computed under the old weights (their log-likelihood partials) are gone
+        data->estep.invalidate();
+        data->weighted = false;
+        data->weight_sum = 0;
+        data->wresp.release();                                 // (sized again by the next weighted statistics pass)
+        if (!weights) {
+            data->weights.release();
+            return;
+        }
+        data->weights.reserve(sizeof(double) * data->n_pad);
+        if (data->n) HIP_CHECK(hipMemcpyAsync(data->weights.p, weights, sizeof(double) * data->n, hipMemcpyHostToDevice, ctx->stream));
+        // validation and W on the device: per-workgroup partials in a fixed order, then the fixed-order tree of the log-likelihood
+        DevBuf scratch;
+        const int grid = weights_grid(data->n);
+        scratch.reserve(sizeof(double) * (2 * (size_t)grid + 2));
+        double* sums = scratch.as<double>();
+        double* bad = sums + grid;
+        double* out = bad + grid;
+        launch_weights_attach(data->weights.as<double>(), data->n, data->n_pad, sums, bad, ctx->stream);
+        launch_ll_reduce(sums, grid, out, ctx->stream);
+        launch_ll_reduce(bad, grid, out + 1, ctx->stream);
+        HIP_CHECK(hipGetLastError());
+        double v[2] = {0, 0};                                  // [this rank's sum of valid weights, its count of invalid ones]
+        HIP_CHECK(hipMemcpyAsync(v, out, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();                                           // (also: the caller's array may change once this returns)
+        ctx->allreduce_host(v, 2);                             // every rank holds the same W and the same verdict
+        if (v[1] != 0 || !(v[0] > 0) || !std::isfinite(v[0])) {
+            data->weights.release();
+            throw InvalidArgument(v[1] != 0 ? "weights must be finite and >= 0" : "the weights' total must be positive and finite");
+        }
+        data->weight_sum = v[0];
+        data->weighted = true;
+    });
+}
+
+int mlhip_data_weight_sum(const mlhip_data* data, double* total)
+{
+    return guarded([&] {
+        require(data && total, "null argument");
+        *total = data->total_weight();
+    });
+}
+
 int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance)
 {
     return guarded([&] {
@@ -233,7 +281,7 @@ int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, doub
         run_mstats(data, em_route(data, 1, false), 1, kFromResp, data->lw.as<double>(), data->ldr, false);
         const double* s = data->stats_host.as<double>();
         const int d = data->d;
-        const double n = (double)data->n_global;
+        const double n = data->total_weight();                 // (W of a weighted block: run_mstats took w_i as the responsibilities)
         // shift == global mean, so S1' is rounding noise; subtract its (tiny) contribution anyway.
         for (int a = 0; a < d; ++a) {
             const double ma = s[stats_index(d, a)] / n;
@@ -262,7 +310,7 @@ int mlhip_xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt,
         HIP_CHECK(hipMemsetAsync(w + data->ldr, 0, sizeof(double) * data->ldr, ctx->stream));
         if (data->n)
             HIP_CHECK(hipMemcpyAsync(w + data->ldr, y, sizeof(double) * data->n, hipMemcpyHostToDevice, ctx->stream));
-        run_mstats(data, em_route(data, 2, false), 2, kFromResp, w, data->ldr, false);
+        run_mstats(data, em_route(data, 2, false), 2, kFromResp, w, data->ldr, false, true, false);
         const int d = data->d, F = stats_count(d);
         const double* s0 = data->stats_host.as<double>();
         const double* s1 = s0 + F;

@@ -113,6 +113,14 @@ void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const 
     if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
     HIP_CHECK(hipGetLastError());
     dt->estep.block_written(grid);
+    if (dt->weighted && a.with_lse) {
+        // the log-likelihood of a weighted block is sum_i w_i lse_i: its partials replace the E-step's, lse itself stays per row
+        // (without lse the weighted self-normalising statistics pass finishes both: launch_em_reduce)
+        int wgrid = 0;
+        ctx->timed("em_weights", [&] { wgrid = launch_weighted_ll(dt->weights.as<double>(), a.lse, dt->n, a.ll_partials, ctx->stream); });
+        HIP_CHECK(hipGetLastError());
+        dt->estep.ll_weighted(wgrid);
+    }
 }
 
 
@@ -215,23 +223,40 @@ static MstatsArgs mstats_args(const mlhip_data* dt, const EmRoute& r, int K, int
 
 /// Runs the statistics kernel on log-responsibilities (mode kFromLogResp: the E-step's lw/lse) or on plain
 /// responsibilities `resp_dev` ([K][ld_resp], ld_resp >= n_pad), all-reduces, leaves [K*F stats, ll_sum] in stats_host.
-void run_mstats(mlhip_data* dt, const EmRoute& r, int K, int mode, const double* resp_dev, size_t ld_resp, bool with_ll, bool collect)
+void run_mstats(mlhip_data* dt, const EmRoute& r, int K, int mode, const double* resp_dev, size_t ld_resp, bool with_ll, bool collect,
+                bool use_weights)
 {
     mlhip_ctx* ctx = dt->ctx;
     ensure_em_workspace(dt, K);
+    const bool weighted = use_weights && dt->weighted;
+    const bool self_norm = mode == kFromLogRespSelfNorm;
+    if (weighted && !self_norm) {
+        // w_i r_ik as plain responsibilities (one rounding more than r_ik), then the statistics kernel of the shape in mode kFromResp
+        // (the self-normalising wide kernel applies the weight itself while it stages: no second block)
+        dt->wresp.reserve(sizeof(double) * dt->ldr * K);
+        const double* src = mode == kFromResp ? resp_dev : dt->lw.as<double>();
+        const size_t lds = mode == kFromResp ? ld_resp : dt->ldr;
+        ctx->timed("em_weights", [&] {
+            launch_weighted_resp(src, lds, dt->lse.as<double>(), mode, dt->weights.as<double>(), dt->n, dt->n_pad, K, dt->wresp.as<double>(),
+                                 dt->ldr, ctx->stream);
+        });
+        HIP_CHECK(hipGetLastError());
+        mode = kFromResp; resp_dev = dt->wresp.as<double>(); ld_resp = dt->ldr;
+    }
     MstatsArgs a = mstats_args(dt, r, K, mode, dt->shift_dev.as<double>(), mode == kFromResp ? resp_dev : dt->lw.as<double>(),
                                mode == kFromResp ? ld_resp : dt->ldr, dt->stats_dev.as<double>());
     a.ll_partials = with_ll ? dt->ll_partials.as<double>() : nullptr;
     a.n_ll_partials = with_ll ? dt->estep.n_ll : 0;
     a.lse_out = dt->lse.as<double>(); a.ll_scratch = dt->ll_partials.as<double>();
-    if (mode == kFromLogRespSelfNorm) {
+    if (self_norm) {
         dt->esum.reserve(sizeof(double) * dt->n_pad);
         a.ll_out = dt->esum.as<double>();
+        if (weighted) { a.mode = kFromLogRespSelfNormWeighted; a.weights = dt->weights.as<double>(); }
     }
     // after a self-normalising pass lse is in HBM like after an LSE-writing E-step: a refinement pass reads it
-    dt->estep.stats_from(mode == kFromLogRespSelfNorm ? (int)kFromLogResp : mode, a.lw, a.ldr);
+    dt->estep.stats_from(self_norm ? (int)kFromLogResp : mode, a.lw, a.ldr);
     int rc = 0;
-    if (mode == kFromLogRespSelfNorm) {
+    if (self_norm) {
         const bool sparse = mstats_sparse_applies(dt, r, K);
         const int slot = (int)(dt->sn_calls % 3);
         dt->sn_calls++;
@@ -263,7 +288,7 @@ double ll_from_stats(const mlhip_data* dt, int K)
 {
     const double log_2_pi = log_two_pi();
     const double sum = dt->stats_host.as<double>()[(size_t)K * stats_count(dt->d)];
-    return sum / (double)dt->n_global - (double)dt->d * log_2_pi / 2;
+    return sum / dt->total_weight() - (double)dt->d * log_2_pi / 2;
 }
 
 
@@ -302,8 +327,18 @@ void refine_component(mlhip_data* dt, const EmRoute& r, int k, double* mean_k, d
     dt->refine_shift.reserve(sizeof(double) * d);
     dt->refine_stats.reserve(sizeof(double) * (F + 1));
     HIP_CHECK(hipMemcpyAsync(dt->refine_shift.p, mean_k, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
-    const MstatsArgs a = mstats_args(dt, r, 1, st.stats_mode, dt->refine_shift.as<double>(), st.stats_resp + (size_t)k * st.stats_ld,
-                                     st.stats_ld, dt->refine_stats.as<double>());
+    int mode = st.stats_mode;
+    const double* column = st.stats_resp + (size_t)k * st.stats_ld;
+    if (dt->weighted && mode == kFromLogResp) {
+        // the last pass of a weighted block normalised lw itself (self-normalising form): column k as w_i r_ik, like every other tier
+        dt->wresp.reserve(sizeof(double) * dt->ldr);
+        launch_weighted_resp(column, st.stats_ld, dt->lse.as<double>(), mode, dt->weights.as<double>(), dt->n, dt->n_pad, 1,
+                             dt->wresp.as<double>(), dt->ldr, ctx->stream);
+        HIP_CHECK(hipGetLastError());
+        mode = kFromResp;
+        column = dt->wresp.as<double>();
+    }
+    const MstatsArgs a = mstats_args(dt, r, 1, mode, dt->refine_shift.as<double>(), column, st.stats_ld, dt->refine_stats.as<double>());
     int rc = 0;
     ctx->timed("em_refine", [&] { rc = launch_em_mstats(a, ctx->num_cus, ctx->stream); });
     if (rc <= 0) throw std::runtime_error("statistics kernel launch failed (refinement pass)");
@@ -330,7 +365,7 @@ void refine_component(mlhip_data* dt, const EmRoute& r, int k, double* mean_k, d
 void finalize_out(mlhip_data* dt, const EmRoute& r, int K, double* mixing_out, double* means_out, double* cov_out)
 {
     const int d = dt->d;
-    host::finalize_mstep(d, K, dt->stats_host.as<double>(), dt->shift.data(), (double)dt->n_global, mixing_out,
+    host::finalize_mstep(d, K, dt->stats_host.as<double>(), dt->shift.data(), dt->total_weight(), mixing_out,
                          means_out, cov_out);
     const double limit = refine_ratio();
     if (!(limit > 0)) return;
@@ -467,8 +502,8 @@ void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixin
                   double* log_likelihood, double* mixing_out, double* means_out, double* variances_out)
 {
     const int d = data->d;
-    if (!mstats::em_diag_supported(d, K)) {
-        // Shapes the one-kernel diagonal iteration is not built for (d > 32 or K > 64): the same iteration through the
+    if (!r.diag_kernel) {
+        // Shapes the one-kernel diagonal iteration is not built for (d > 32 or K > 64) and weighted blocks: the same iteration through the
         // full-covariance kernels on diagonal matrices -- the E-step's Cholesky of a diagonal matrix is its square root, and
         // the diagonal of the M-step's full covariance IS the diagonal-mode variance (ML/EM.cpp:245-257 entry by entry); the
         // off-diagonal sums are computed and dropped. Slower than it could be, never refused.
@@ -734,7 +769,7 @@ int mlhip_em_route(const mlhip_data* data, uint32_t K, int covariance_type, mlhi
         out->sparse = r.sparse;
         out->balanced = r.balanced;
         out->fold_allowed = r.fold_allowed;
-        out->diag_kernel = diag && mstats::em_diag_supported(data->d, (int)K);
+        out->diag_kernel = r.diag_kernel;
         out->diag_exact = r.diag_exact;
         out->device_close = r.device_close;
         out->records_on_device = r.records_on_device;

@@ -129,7 +129,7 @@ struct EmLoop {
         ctx->reduce_in_place(data->stats_dev.as<double>(), data->stats_host.as<double>(), (size_t)K * F + 1);
         CloseArgs ca{};
         ca.stats = data->stats_dev.as<double>(); ca.K = K; ca.d = d; ca.D = data->D;
-        ca.shift = data->shift_dev.as<double>(); ca.n_global = (double)data->n_global;
+        ca.shift = data->shift_dev.as<double>(); ca.n_global = data->total_weight();
         ca.layout = layout; ca.refine_limit = refine_limit;
         ca.mixing = pack_mixing(out); ca.means = pack_means(out); ca.covs = pack_covs(out);
         ca.records = rec[out]->as<double>();
@@ -242,7 +242,7 @@ struct EmLoop {
     {
         const int out = (int)((i + 1) % 3);
         const double* inf = host_info(out);
-        Verdict v{inf[0] / (double)data->n_global - (double)d * log_two_pi() / 2, false, 0.0};   // ML/EM.cpp:197-198, 211
+        Verdict v{inf[0] / data->total_weight() - (double)d * log_two_pi() / 2, false, 0.0};   // ML/EM.cpp:197-198, 211
         for (int k = 0; k < K; ++k) {
             v.flagged = v.flagged || inf[1 + k] != 0.0;
             v.cmax = std::max(v.cmax, inf[1 + K + k]);

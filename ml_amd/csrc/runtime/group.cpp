@@ -415,6 +415,19 @@ void sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* c
     });
 }
 
+void set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weights)
+{
+    check_group_data(ctx, data);
+    data->weighted = false;
+    data->weight_sum = 0;
+    // every shard validates its rows and all-reduces [sum, invalid count]: all accept, or all refuse and stay unweighted
+    each_shard(ctx, [&](int s, mlhip_ctx* c) {
+        check_status(mlhip_data_set_weights(c, data->parts[(size_t)s], weights ? weights + data->first_row[(size_t)s] : nullptr));
+    });
+    data->weighted = data->parts[0]->weighted;
+    data->weight_sum = data->parts[0]->weight_sum;
+}
+
 void xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt, double* xy)
 {
     check_group_data(ctx, data);

@@ -413,6 +413,8 @@ struct EstepState {
 
     void invalidate() { what = kNone; }
     void block_written(int grid) { what = kBlock; n_ll = grid; }
+    /// A weighted block: the E-step's log-likelihood partials were replaced by `grid` partials of w_i lse_i (launch_estep).
+    void ll_weighted(int grid) { n_ll = grid; }
     void records_only(int grid) { what = kRecords; n_ll = grid; }
     void diag_records_only(int grid) { what = kDiagRecords; n_ll = grid; }
     /// A later (speculative) pass overwrote lw / lse; the records in params_dev still stand.
@@ -448,6 +450,14 @@ struct mlhip_data {
     DevBuf xt{&pool};             // [D][ldx]
     DevBuf shift_dev{&pool};      // d doubles
     std::vector<double> shift;    // host copy
+    // Row weights (mlhip_data_set_weights; a group's handle mirrors `weighted` / `weight_sum` of its parts): n_pad doubles, zero
+    // beyond n. wresp: [em_K][ldr], w_i r_ik of the last statistics pass of a weighted block on a route without the self-
+    // normalising statistics kernel (run_mstats), or the one column of a refinement pass.
+    DevBuf weights{&pool}, wresp{&pool};
+    bool weighted = false;
+    double weight_sum = 0;        // W over all ranks
+    /// What the log-likelihood and the mixing proportions are divided by: W, or the row count of an unweighted block.
+    double total_weight() const { return weighted ? weight_sum : (double)n_global; }
     // EM workspace (sized for em_K)
     int em_K = 0;
     size_t ldr = 0;
@@ -541,6 +551,7 @@ struct EmRoute {
     int sparse = -1;                   // self-normalising statistics: 1 the sparse kernel, 0 the dense one, -1 by call history
     bool balanced = true;              // d <= 32: the wide statistics kernel deals balanced (column block, row block) units
     bool diag_exact = false;           // diagonal mode: the exact density form always
+    bool diag_kernel = false;          // diagonal mode: the one-kernel iteration (em_diag.hip), else the full-covariance kernels
     bool device_close = false;         // mlhip_em_iterate closes every iteration on the device (em_close.hip)
     bool resident = false;             // mlhip_em_iterate may run the whole loop in one launch (em_resident.hip)
     /// MstatsArgs::plain: the plain tier above d = 128, whole column blocks per wave at d <= 32.
@@ -635,8 +646,10 @@ bool run_fused_step(mlhip_data* dt, const EmRoute& r, int K, const double* mixin
 
 /// Runs the statistics kernel on log-responsibilities (mode kFromLogResp: the E-step's lw/lse) or on plain
 /// responsibilities `resp_dev` ([K][ld_resp], ld_resp >= n_pad), all-reduces, leaves [K*F stats, ll_sum] in stats_host.
+/// A weighted block's responsibilities are multiplied by the rows' weights on the way (by the self-normalising kernel while it
+/// stages, else into wresp; the source is not changed) unless `use_weights` is false (mlhip_xxt_xy: its rows are not an EM sample).
 void run_mstats(mlhip_data* dt, const EmRoute& r, int K, int mode, const double* resp_dev, size_t ld_resp, bool with_ll,
-                bool collect = true);
+                bool collect = true, bool use_weights = true);
 
 double log_two_pi();
 
@@ -741,6 +754,7 @@ mlhip_ctx* shard_context(const mlhip_ctx* ctx, int shard);
 const char* reduce_kind(const mlhip_ctx* ctx);
 mlhip_data* upload(mlhip_ctx* ctx, const double* x, bool on_device, uint32_t d, uint64_t n, int64_t ld);
 void sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance);
+void set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weights);
 void xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt, double* xy);
 void random_partition_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const uint32_t* order, const uint32_t* offsets, double* means,
                             double* sizes);

@@ -64,15 +64,20 @@ EmRoute em_route(const mlhip_data* data, int K, bool diag)
     const Switches sw = read_switches();
     const mlhip_ctx* ctx = data->ctx;
     const int d = data->d, D = data->D;
-    const bool diag_kernel = diag && mstats::em_diag_supported(d, K);
+    // A weighted block (mlhip_data_set_weights) runs the E-step tier of its shape and either the self-normalising wide statistics
+    // kernel in its weighted form or the statistics kernels on w_i r_ik: the fused, resident and diagonal kernels and the sparse
+    // statistics kernel have no weighted form.
+    const bool weighted = data->weighted;
+    const bool diag_kernel = diag && !weighted && mstats::em_diag_supported(d, K);
     EmRoute r;
+    r.diag_kernel = diag_kernel;
     if (estep_mfma4_supported(D) && !(D <= kRegDim && sw.estep_valu)) r.estep = Estep::kMatrix4;
     else if (D <= kMaxDim) r.estep = Estep::kScalarFed;
     else r.estep = sw.big_dim && big_dim_applies(D) ? Estep::kBigDim : Estep::kPlain;
     r.records_on_device = sw.records && em_close_big_supported(d);
     r.fold_allowed = sw.fold && D <= kRegDim;
     // (the fused kernel reads the scalar-fed E-step's records)
-    r.fused = !diag_kernel && sw.fused && r.estep == Estep::kScalarFed && mstats::em_fused_supported(d, K);
+    r.fused = !diag_kernel && !weighted && sw.fused && r.estep == Estep::kScalarFed && mstats::em_fused_supported(d, K);
     if (r.fused) {
         if (sw.fused_valu != 0 && mstats::em_fused_valu_supported(d, K) &&
             (sw.fused_valu == 2 || mstats::em_fused_valu_preferred(d, K, data->n)))
@@ -85,7 +90,7 @@ EmRoute em_route(const mlhip_data* data, int K, bool diag)
     // K within one row-block group of the wide statistics kernel: one exp per pair in the iteration (MLHIP_ESTEP=valu: at no d)
     r.self_norm = !diag_kernel && !r.fused && sw.self_norm && !sw.estep_valu && r.estep == Estep::kMatrix4 &&
                   em_mstats_self_norm_supported(d, K, ctx->num_cus);
-    r.sparse = sw.sparse;
+    r.sparse = weighted ? 0 : sw.sparse;
     r.balanced = sw.balanced;
     r.diag_exact = !sw.diag_ab;
     r.device_close = sw.device_close && em_close_supported(d) && (!diag || diag_kernel);
