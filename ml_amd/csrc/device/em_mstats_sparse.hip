@@ -10,10 +10,17 @@
 //   * staging: the wide kernel's roles and normalisation code (em_mstats_stage.hpp) -> (max, sum) bit-identical to it. The x~ row
 //     of a sample is stored with the extra "1" coordinate left out, zero-padded to 32 coordinates and with its first 12 repeated
 //     behind them (row stride XE = 45, odd): quad q of the row (4 coordinates) can then be read as quad q .. q + 2 (mod 8);
-//   * compaction: wave w owns components w, w + 8, ... (K <= 64: up to 8). Per component, lane s reads r_sc of tile sample s; a
-//     ballot gives the nonzero set, v_mbcnt its rank: lane s writes s to slot rank of the component's list -- the bucket in sample
-//     order, no atomics, the same order in every run. (Building all 8 buckets first, so that their LDS round trips overlap, measured
-//     slower: 5.83 against 5.48 ms at the headline shape, 24 registers spilled instead of 16);
+//   * buckets from the staging ballots: stage_self_norm's ballot of "staged value `it` is nonzero" holds, in byte cg, the nonzero
+//     mask of component 8 cg + it over the wave's 8 samples; every wave stores its 64 mask bytes in a table [component][wave]
+//     (512 bytes per tile, double-buffered with it), so the 64-bit word of a component is its bucket: bit s = tile sample s. After
+//     the tile barrier wave w fetches the words of its components w, w + 8, ... (K <= 64: up to 8) in one batch and keeps them in
+//     scalar registers. Entry e of a bucket is the e-th set bit -- scalar bit scans, ascending sample order, the same order in every
+//     run; no list in LDS, no read of r to find the bucket, nothing that waits for an LDS store;
+//   * one LDS round trip per step of four entries, issued a step ahead: the operands of the next step -- of this bucket, or the
+//     first of the wave's next nonempty one, known from its mask -- are loaded behind the MFMAs that free their registers (the
+//     9-double window is not doubled: 192 accumulator registers leave no room for that). Entries past a bucket's end read r from
+//     a zero slot, x~ from sample row 0. (The parent of this form read r, balloted, wrote and re-read a list and then the
+//     operands: ~7 dependent round trips per component, 5.5 ms at the headline shape; DESIGN.md section 3.3e has both measured);
 //   * accumulation on v_mfma_f64_4x4x4_4b (lane layout as in em_estep_mfma4.hip: A[b][i][k] <- lane 16k + 4b + i,
 //     B[b][k][j] <- lane 16k + 4b + j, D[b][i][j] -> lane 16i + 4b + j): four bucket entries per step, sample k = lane >> 4. The
 //     32 x 32 Gram matrix has 36 quad pairs {Q, P} with P = Q + delta (mod 8): delta = 0..3 for every Q, delta = 4 for Q < 4.
@@ -46,6 +53,15 @@ template <int N, int I = 0, class F> __device__ __forceinline__ void static_for(
     }
 }
 
+/// The wave-uniform value of a 64-bit quantity every lane holds: kept in scalar registers from here on.
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long clear_lowest(unsigned long long m) { return m & (m - 1); }
+__device__ __forceinline__ int lowest_or_none(unsigned long long m) { return m ? __builtin_ctzll(m) : -1; }
+
 __global__ __launch_bounds__(512, 2) void em_mstats_sparse_kernel(
     const double* __restrict__ xt, size_t ldx, uint32_t n, int d, int D, const double* __restrict__ shift,
     const double* __restrict__ lw, size_t ldr, int K, double* __restrict__ partials, int KP, int FP,
@@ -54,10 +70,12 @@ __global__ __launch_bounds__(512, 2) void em_mstats_sparse_kernel(
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int NXV = kRegDim / SNW;                // x rows staged per thread (4)
     constexpr int tile_doubles = TS * SXE + TS * SRS;
-    int* lists = reinterpret_cast<int*>(smem + 2 * tile_doubles);   // [SNW][TS]: the current component's bucket per wave
+    // [2][64 components]: byte w of a component's word = its nonzero mask over samples 8w .. 8w + 7 (written by wave w)
+    unsigned long long* masks = reinterpret_cast<unsigned long long*>(smem + 2 * tile_doubles);
+    double* zero = smem + 2 * tile_doubles + 2 * SCPW * SNW;   // one 0.0: the "responsibility" of the entries past a bucket's end
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int* list = lists + wave * TS;
+    if (tid == 0) *zero = 0.0;                        // (visible after the first tile's barrier)
 
     double acc[SCPW][SNA];
 #pragma unroll
@@ -75,12 +93,23 @@ __global__ __launch_bounds__(512, 2) void em_mstats_sparse_kernel(
         const uint32_t i = tile * TS + sS;           // < n_pad: always inside the allocation
 #pragma unroll
         for (int it = 0; it < NXV; ++it) xv[it] = xt[(size_t)min(wave + SNW * it, D - 1) * ldx + i];
+        int c0 = cg * SNRV;
+        asm volatile("" : "+v"(c0));                 // the eight row offsets are recomputed per tile: hoisted, they are 16 registers
 #pragma unroll
-        for (int it = 0; it < SNRV; ++it) rv[it] = lw[(size_t)min(cg * SNRV + it, K - 1) * ldr + tile * TS + sR];
+        for (int it = 0; it < SNRV; ++it) rv[it] = lw[(size_t)(uint32_t)min(c0 + it, K - 1) * ldr + tile * TS + sR];
     };
-    auto stage = [&](double* Xe, double* Rb, uint32_t tile) {
+    auto stage = [&](double* Xe, double* Rb, unsigned long long* Mk, uint32_t tile) {
         const uint32_t i = tile * TS + sR;
-        nonzero += stage_self_norm<SNRV, SRS>(rv, cg, K, i, i < n, Rb, sR, true, lse_out, esum_out);
+        unsigned long long nz[SNRV];
+        int cgt = cg;
+        asm volatile("" : "+v"(cgt));                // (the per-value "component >= K" lane masks: per tile, not 16 scalar registers)
+        nonzero += stage_self_norm<SNRV, SRS, false, true>(rv, cgt, K, i, i < n, Rb, sR, true, lse_out, esum_out, 1.0, nz);
+        // byte cg of ballot `it` = component 8 cg + it over this wave's 8 samples (lanes 8 cg .. 8 cg + 7)
+        if ((lane & 7) == 0) {
+            unsigned char* mb = reinterpret_cast<unsigned char*>(Mk + cg * SNRV) + wave;
+#pragma unroll
+            for (int it = 0; it < SNRV; ++it) mb[8 * it] = (unsigned char)(nz[it] >> (8 * cg));
+        }
 #pragma unroll
         for (int it = 0; it < NXV; ++it) {
             const int j = wave + SNW * it;
@@ -98,41 +127,81 @@ __global__ __launch_bounds__(512, 2) void em_mstats_sparse_kernel(
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, buf ^= 1) {
         double* Xe = smem + buf * tile_doubles;
         double* Rb = Xe + TS * SXE;
-        stage(Xe, Rb, tile);
+        unsigned long long* Mk = masks + buf * (SCPW * SNW);
+        stage(Xe, Rb, Mk, tile);
         __syncthreads();
+        // the buckets of the wave's components: one batch of independent reads, wave-uniform from here on
+        unsigned long long mk[SCPW];
+#pragma unroll
+        for (int sl = 0; sl < SCPW; ++sl) mk[sl] = Mk[sl * SNW + wave];
+#pragma unroll
+        for (int sl = 0; sl < SCPW; ++sl) mk[sl] = uniform64(mk[sl]);
+        __builtin_amdgcn_sched_barrier(0);           // (the 16 registers of the batch are free again before the prefetch takes its own)
         const uint32_t next = tile + gridDim.x;
         prefetch(next < n_tiles ? next : tile);      // the last iteration re-reads its own tile (discarded)
         __builtin_amdgcn_s_setprio(kMatrixPhasePriority);
+
+        // operands of one step: the four lowest samples of `rem` (a bucket's remaining entries), of component c; lane group k4
+        // takes its own. Entries past the end: r = 0 (the zero slot) on sample row 0
+        const double* xlane = Xe + 4 * bq + i4;
+        auto operand_rows = [&](unsigned long long rem, int c, const double*& xr, const double*& rp) {
+            const unsigned long long t1 = clear_lowest(rem), t2 = clear_lowest(t1), t3 = clear_lowest(t2);
+            const int s0 = lowest_or_none(rem), s1 = lowest_or_none(t1), s2 = lowest_or_none(t2), s3 = lowest_or_none(t3);
+            const uint32_t four = (uint32_t)(s0 & 0xff) | (uint32_t)(s1 & 0xff) << 8 | (uint32_t)(s2 & 0xff) << 16 | (uint32_t)s3 << 24;
+            const int s = (int)(signed char)(four >> (8 * k4));   // scalar up to here; one shift and one sign extension per lane
+            xr = xlane + max(s, 0) * SXE;
+            rp = s >= 0 ? Rb + s * SRS + c : zero;
+        };
+        // the first nonempty bucket at or behind slot J (none: an empty step)
+        auto bucket_from = [&](auto J_, unsigned long long& rem, int& c) {
+            constexpr int J = J_;
+            rem = 0;
+            c = 0;
+#pragma unroll
+            for (int j = SCPW - 1; j >= J; --j)
+                if (mk[j]) {
+                    rem = mk[j];
+                    c = j * SNW + wave;
+                }
+        };
+
+        double r, y[8];
+        {
+            unsigned long long rem;
+            int c;
+            const double *xr, *rp;
+            bucket_from(std::integral_constant<int, 0>{}, rem, c);
+            operand_rows(rem, c, xr, rp);
+            r = *rp;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) y[m] = xr[4 * m];
+        }
         static_for<SCPW>([&](auto sl_) {
             constexpr int sl = sl_;
-            const int c = sl * SNW + wave;
-            if (c < K) {
-                // compaction: the nonzero responsibilities of component c, in sample order
-                const double r_own = Rb[lane * SRS + c];
-                const unsigned long long mask = __ballot(r_own != 0.0);
-                const uint32_t cnt = (uint32_t)__builtin_popcountll(mask);
-                if (r_own != 0.0)
-                    list[__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u))] = lane;
-                for (uint32_t e0 = 0; e0 < cnt; e0 += 4) {
-                    const uint32_t e = e0 + k4;
-                    const bool valid = e < cnt;
-                    const int s = valid ? list[e] : 0;
-                    const double r = valid ? Rb[s * SRS + c] : 0.0;   // (entries past the bucket: r = 0 on a real sample row)
-                    const double* xr = Xe + s * SXE + 4 * bq + i4;
-                    double y[8];
+            // a nonempty bucket finds the operands of its first step loaded; each step loads the next one's -- this bucket's or
+            // the first of the next nonempty one -- behind the MFMAs that free the registers
+            for (unsigned long long cur = mk[sl]; cur;) {
+                cur = clear_lowest(clear_lowest(clear_lowest(clear_lowest(cur))));
+                unsigned long long rem = cur;
+                int c = sl * SNW + wave;
+                if (!cur) bucket_from(std::integral_constant<int, sl + 1>{}, rem, c);
+                const double *xr, *rp;
+                operand_rows(rem, c, xr, rp);
+                const double ry0 = r * y[0], ry1 = r * y[4];
+                acc[sl][11] = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, r, acc[sl][11], 0, 0, 0);
 #pragma unroll
-                    for (int m = 0; m < 8; ++m) y[m] = xr[4 * m];
-                    const double ry0 = r * y[0], ry1 = r * y[4];
+                for (int dl = 0; dl < 4; ++dl) acc[sl][dl] = __builtin_amdgcn_mfma_f64_4x4x4f64(y[dl], ry0, acc[sl][dl], 0, 0, 0);
+                acc[sl][8] = __builtin_amdgcn_mfma_f64_4x4x4f64(y[4], ry0, acc[sl][8], 0, 0, 0);
+                acc[sl][9] = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, ry0, acc[sl][9], 0, 0, 0);
+                r = *rp;
 #pragma unroll
-                    for (int dl = 0; dl < 4; ++dl) {
-                        acc[sl][dl] = __builtin_amdgcn_mfma_f64_4x4x4f64(y[dl], ry0, acc[sl][dl], 0, 0, 0);
-                        acc[sl][4 + dl] = __builtin_amdgcn_mfma_f64_4x4x4f64(y[4 + dl], ry1, acc[sl][4 + dl], 0, 0, 0);
-                    }
-                    acc[sl][8] = __builtin_amdgcn_mfma_f64_4x4x4f64(y[4], ry0, acc[sl][8], 0, 0, 0);
-                    acc[sl][9] = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, ry0, acc[sl][9], 0, 0, 0);
-                    acc[sl][10] = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, ry1, acc[sl][10], 0, 0, 0);
-                    acc[sl][11] = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, r, acc[sl][11], 0, 0, 0);
-                }
+                for (int m = 0; m < 4; ++m) y[m] = xr[4 * m];
+#pragma unroll
+                for (int dl = 0; dl < 4; ++dl)
+                    acc[sl][4 + dl] = __builtin_amdgcn_mfma_f64_4x4x4f64(y[4 + dl], ry1, acc[sl][4 + dl], 0, 0, 0);
+                acc[sl][10] = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, ry1, acc[sl][10], 0, 0, 0);
+#pragma unroll
+                for (int m = 4; m < 8; ++m) y[m] = xr[4 * m];
             }
         });
         __builtin_amdgcn_s_setprio(0);
@@ -183,7 +252,7 @@ int launch_em_mstats_sparse(const MstatsArgs& a, int num_cus, hipStream_t stream
     int grid_x = num_cus < p.grid_x ? num_cus : p.grid_x;       // one workgroup per CU (the dense plan may have two)
     if ((uint32_t)grid_x > n_tiles) grid_x = (int)(n_tiles ? n_tiles : 1);
     if ((size_t)grid_x * p.KP * p.FP > a.partials_capacity || p.KP < a.K || p.FP < stats_count(a.d)) return -2;
-    const size_t smem = sizeof(double) * 2 * ((size_t)TS * SXE + (size_t)TS * SRS) + sizeof(int) * SNW * TS;
+    const size_t smem = sizeof(double) * (2 * ((size_t)TS * SXE + (size_t)TS * SRS) + 2 * SCPW * SNW + 1);
     hipLaunchKernelGGL(em_mstats_sparse_kernel, dim3(grid_x), dim3(512), smem, stream, a.xt, a.ldx, a.n, a.d, padded_dim(a.d),
                        a.shift, a.lw, a.ldr, a.K, a.partials, p.KP, p.FP, a.lse_out, a.ll_out, a.nz_count);
     return grid_x;

@@ -57,11 +57,12 @@ __device__ __forceinline__ double allreduce_sum_bits345(double v)
 /// and components >= K) and, if `write_lse`, max and sum to lse_out[i] / esum_out[i]. Returns how many of the wave's 64 x NRV
 /// written responsibilities are nonzero (wave-uniform). WEIGHTED (a block with row weights): the value written is r w_i, the
 /// sample's frequency weight `wi` applied AFTER the normalisation (one rounding more than r); max and sum -- hence lse -- stay the
-/// sample's own.
-template <int NRV, int RS, bool WEIGHTED = false>
+/// sample's own. MASKS: nz[it] receives the wave's ballot of "written value `it` is nonzero" (bit = lane) -- the ballots the count
+/// is made of anyway; the sparse kernel builds its buckets from them.
+template <int NRV, int RS, bool WEIGHTED = false, bool MASKS = false>
 __device__ __forceinline__ uint32_t stage_self_norm(double (&rv)[NRV], int cg, int K, uint32_t i, bool live, double* Rb, int sR,
                                                      bool write_lse, double* __restrict__ lse_out, double* __restrict__ esum_out,
-                                                     double wi = 1.0)
+                                                     double wi = 1.0, unsigned long long* nz = nullptr)
 {
     double m = -__builtin_inf();
 #pragma unroll
@@ -85,7 +86,9 @@ __device__ __forceinline__ uint32_t stage_self_norm(double (&rv)[NRV], int cg, i
         double r = rv[it] * inv;
         if constexpr (WEIGHTED) r = wi != 0.0 ? r * wi : 0.0;         // a row of weight 0 is not in the sample, whatever its density
         Rb[sR * RS + cg * NRV + it] = r;
-        nonzero += (uint32_t)__builtin_popcountll(__ballot(r != 0.0));
+        const unsigned long long b = __ballot(r != 0.0);
+        if constexpr (MASKS) nz[it] = b;
+        nonzero += (uint32_t)__builtin_popcountll(b);
     }
     // lse = m + log(sum) is finished by a separate pass over these two N-vectors (em_lse_finish_kernel): a log in
     // this loop, next to 160 accumulator registers, cost 0.8 ms at the headline shape in spills and scheduling
