@@ -128,6 +128,14 @@ void destroy_single_context(mlhip_ctx* ctx)
     delete ctx;
 }
 
+namespace {
+/// A timing switch of a group's context: the same call on each shard's context (no data, no collective: nothing to fan out).
+void on_every_shard(mlhip_ctx* ctx, const std::function<int(mlhip_ctx*)>& call)
+{
+    for (int s = 0; s < grp::shard_count(ctx); ++s) check_status(call(grp::shard_context(ctx, s)));
+}
+}  // namespace
+
 }  // namespace mlhip_rt
 
 extern "C" {
@@ -386,7 +394,7 @@ int mlhip_timing_enable(mlhip_ctx* ctx, int on)
 {
     return guarded([&] {
         require(ctx, "null context");
-        if (ctx->group) { grp::timing_enable(ctx, on); return; }
+        if (ctx->group) { on_every_shard(ctx, [on](mlhip_ctx* c) { return mlhip_timing_enable(c, on); }); return; }
         ctx->use();
         if (!on) ctx->resolve_timers();
         ctx->timing = on != 0;
@@ -396,7 +404,7 @@ int mlhip_timing_reset(mlhip_ctx* ctx)
 {
     return guarded([&] {
         require(ctx, "null context");
-        if (ctx->group) { grp::timing_reset(ctx); return; }
+        if (ctx->group) { on_every_shard(ctx, mlhip_timing_reset); return; }
         ctx->use();
         ctx->resolve_timers();
         ctx->timers.clear();

@@ -197,7 +197,7 @@ int mlhip_data_shape(const mlhip_data* data, uint32_t* d, uint64_t* n_local, uin
     return guarded([&] {
         require(data, "null data");
         if (d) *d = (uint32_t)data->d;
-        if (n_local) *n_local = data->parts.empty() ? (uint64_t)data->n : data->n_global;   // (a group holds the whole sample)
+        if (n_local) *n_local = data->rows();
         if (n_global) *n_global = data->n_global;
     });
 }
@@ -222,8 +222,16 @@ int mlhip_data_shift(const mlhip_data* data, double* shift)
 int mlhip_data_set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weights)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::set_weights(ctx, data, weights); return; }
-        check_em_args(ctx, data, 1);
+        check_call(ctx, data, 1);
+        if (ctx->group) {
+            data->weighted = false;
+            data->weight_sum = 0;
+            // every shard validates its rows and all-reduces [sum, invalid count]: all accept, or all refuse and stay unweighted
+            fan_out(ctx, data, [&](Shard& sh) { return mlhip_data_set_weights(sh.ctx, sh.part, sh.rows(weights)); });
+            data->weighted = data->parts[0]->weighted;
+            data->weight_sum = data->parts[0]->weight_sum;
+            return;
+        }
         // whatever the outcome, E-step results computed under the old weights (their log-likelihood partials) are gone
         data->estep.invalidate();
         data->weighted = false;
@@ -270,9 +278,15 @@ int mlhip_data_weight_sum(const mlhip_data* data, double* total)
 int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::sample_covariance(ctx, data, mean, covariance); return; }
-        check_em_args(ctx, data, 1);
+        check_call(ctx, data, 1);
         require(covariance, "null argument");
+        if (ctx->group) {
+            const size_t d = (size_t)data->d;
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_sample_covariance(sh.ctx, sh.part, sh.replicated(mean, d), sh.replicated(covariance, d * d));
+            });
+            return;
+        }
         // K = 1, r = 1: S_0 = sum_i xt_i xt_i^T about the global mean. The E-step workspace for another K is
         // left untouched only if K == 1; otherwise it is rebuilt on the next E-step.
         ensure_em_workspace(data, 1);
@@ -298,9 +312,15 @@ int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, doub
 int mlhip_xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt, double* xy)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::xxt_xy(ctx, data, y, xxt, xy); return; }
-        check_em_args(ctx, data, 2);
-        require((y || data->n == 0) && xxt && xy, "null argument");
+        check_call(ctx, data, 2);
+        require((y || data->rows() == 0) && xxt && xy, "null argument");
+        if (ctx->group) {
+            const size_t d = (size_t)data->d;
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_xxt_xy(sh.ctx, sh.part, sh.rows(y), sh.replicated(xxt, d * d), sh.replicated(xy, d));
+            });
+            return;
+        }
         ensure_em_workspace(data, 2);
         data->estep.invalidate();
         // weight rows: [0] = 1 (valid samples), [1] = y; the statistics kernel then yields, about the shift s,
@@ -332,11 +352,11 @@ int mlhip_random_partition_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, c
                                  double* means, double* sizes)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::random_partition_means(ctx, data, K, order, offsets, means, sizes); return; }
-        check_em_args(ctx, data, K);
-        require(offsets && means && sizes && (order || data->n == 0), "null argument");
-        require(offsets[0] == 0 && offsets[K] == data->n, "offsets must cover this rank's rows");
+        check_call(ctx, data, K);
+        require(offsets && means && sizes && (order || data->rows() == 0), "null argument");
+        require(offsets[0] == 0 && offsets[K] == data->rows(), "offsets must cover this rank's rows");
         for (uint32_t k = 0; k < K; ++k) require(offsets[k] <= offsets[k + 1], "offsets must ascend");
+        if (ctx->group) { grp::random_partition_means(ctx, data, K, order, offsets, means, sizes); return; }
         const int d = data->d;
         DevBuf order_dev, small;   // (one initialisation per fit: no point in keeping them)
         const size_t off_bytes = ((sizeof(uint32_t) * (K + 1) + 15) / 16) * 16;

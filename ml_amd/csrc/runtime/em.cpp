@@ -292,12 +292,13 @@ double ll_from_stats(const mlhip_data* dt, int K)
 }
 
 
-void check_em_args(mlhip_ctx* ctx, mlhip_data* dt, uint32_t K)
+void check_call(mlhip_ctx* ctx, mlhip_data* dt, uint32_t K)
 {
     require(ctx && dt, "null context or data");
     require(dt->ctx == ctx, "data belongs to another context");
+    if (ctx->group) require((int)dt->parts.size() == grp::shard_count(ctx), "data was not uploaded through this device group");
     require(K >= 1, "At least one component required");
-    ctx->use();
+    if (!ctx->group) ctx->use();
 }
 
 
@@ -528,6 +529,21 @@ void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixin
 }
 
 
+namespace {
+
+/// mlhip_em_step / mlhip_em_step_diag (`step`) through a device group: the outputs may alias the inputs, so the shards read copies.
+void group_em_step(decltype(&mlhip_em_step) step, mlhip_ctx* ctx, mlhip_data* data, uint32_t K, size_t cov_doubles, const double* mixing,
+                   const double* means, const double* covs, double* log_likelihood, double* mixing_out, double* means_out, double* covs_out)
+{
+    const size_t kd = (size_t)K * data->d;
+    const std::vector<double> pi(mixing, mixing + K), mu(means, means + kd), cv(covs, covs + cov_doubles);
+    fan_out(ctx, data, [&](Shard& sh) {
+        return step(sh.ctx, sh.part, K, pi.data(), mu.data(), cv.data(), sh.scalar(log_likelihood), sh.replicated(mixing_out, K),
+                    sh.replicated(means_out, kd), sh.replicated(covs_out, cov_doubles));
+    });
+}
+
+}  // namespace
 }  // namespace mlhip_rt
 
 extern "C" {
@@ -537,9 +553,14 @@ int mlhip_em_expectation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const dou
                          const double* covariances, double* log_likelihood)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::em_expectation(ctx, data, K, mixing, means, covariances, log_likelihood); return; }
-        check_em_args(ctx, data, K);
+        check_call(ctx, data, K);
         require(mixing && means && covariances && log_likelihood, "null argument");
+        if (ctx->group) {
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_em_expectation(sh.ctx, sh.part, K, mixing, means, covariances, sh.scalar(log_likelihood));
+            });
+            return;
+        }
         run_estep(data, em_route(data, (int)K, false), (int)K, mixing, means, covariances);
         double* slot = data->stats_dev.as<double>() + (size_t)K * stats_count(data->d);
         launch_ll_reduce(data->ll_partials.as<double>(), data->estep.n_ll, slot, ctx->stream);
@@ -556,9 +577,16 @@ int mlhip_em_maximisation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* 
                           double* covariances_out)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::em_maximisation(ctx, data, K, 0, nullptr, 0, nullptr, mixing_out, means_out, covariances_out); return; }
-        check_em_args(ctx, data, K);
+        check_call(ctx, data, K);
         require(mixing_out && means_out && covariances_out, "null argument");
+        if (ctx->group) {
+            const size_t kd = (size_t)K * data->d;
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_em_maximisation(sh.ctx, sh.part, K, sh.replicated(mixing_out, K), sh.replicated(means_out, kd),
+                                            sh.replicated(covariances_out, kd * data->d));
+            });
+            return;
+        }
         require(data->has_estep_results((int)K), "no E-step results on the device for this K");
         const EmRoute r = em_route(data, (int)K, false);
         ensure_lw(data, r, (int)K);
@@ -572,12 +600,13 @@ int mlhip_em_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* mi
                   double* covariances_out)
 {
     return guarded([&] {
-        if (ctx && ctx->group) {
-            grp::em_step(ctx, data, K, false, mixing, means, covariances, log_likelihood, mixing_out, means_out, covariances_out);
+        check_call(ctx, data, K);
+        require(mixing && means && covariances && log_likelihood && mixing_out && means_out && covariances_out, "null argument");
+        if (ctx->group) {
+            group_em_step(mlhip_em_step, ctx, data, K, (size_t)K * data->d * data->d, mixing, means, covariances, log_likelihood, mixing_out,
+                          means_out, covariances_out);
             return;
         }
-        check_em_args(ctx, data, K);
-        require(mixing && means && covariances && log_likelihood && mixing_out && means_out && covariances_out, "null argument");
         em_step_full(data, em_route(data, (int)K, false), (int)K, mixing, means, covariances, log_likelihood, mixing_out, means_out, covariances_out);
     });
 }
@@ -587,12 +616,13 @@ int mlhip_em_step_diag(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const doubl
                        double* variances_out)
 {
     return guarded([&] {
-        if (ctx && ctx->group) {
-            grp::em_step(ctx, data, K, true, mixing, means, variances, log_likelihood, mixing_out, means_out, variances_out);
+        check_call(ctx, data, K);
+        require(mixing && means && variances && log_likelihood && mixing_out && means_out && variances_out, "null argument");
+        if (ctx->group) {
+            group_em_step(mlhip_em_step_diag, ctx, data, K, (size_t)K * data->d, mixing, means, variances, log_likelihood, mixing_out, means_out,
+                          variances_out);
             return;
         }
-        check_em_args(ctx, data, K);
-        require(mixing && means && variances && log_likelihood && mixing_out && means_out && variances_out, "null argument");
         em_step_diag(data, em_route(data, (int)K, true), (int)K, mixing, means, variances, log_likelihood, mixing_out, means_out, variances_out);
     });
 }
@@ -602,23 +632,28 @@ int mlhip_em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covarianc
                      uint32_t* steps_done, int* converged, double* log_likelihood, double* log_likelihood_history)
 {
     return guarded([&] {
-        if (ctx && ctx->group) {
-            require(max_steps >= 1, "at least one step required");
-            if (absolute_tolerance < 0 || relative_tolerance < 0) throw DomainError("negative tolerance");
-            grp::em_iterate(ctx, data, K, covariance_type, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance,
-                            steps_done, converged, log_likelihood, log_likelihood_history);
-            return;
-        }
-        check_em_args(ctx, data, K);
+        check_call(ctx, data, K);
         require(mixing && means && covariances && steps_done && converged && log_likelihood, "null argument");
         require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL, "bad covariance_type");
         require(max_steps >= 1, "at least one step required");
         if (absolute_tolerance < 0 || relative_tolerance < 0) throw DomainError("negative tolerance");
         const bool diag = covariance_type == MLHIP_COVARIANCE_DIAGONAL;
+        const size_t kd = (size_t)K * data->d, cov_doubles = kd * (diag ? 1 : data->d);
+        if (ctx->group) {
+            // the parameters are in/out: shard 0 updates the caller's, the others copies of their own (the ranks' end-of-fit
+            // checksum exchange inside the shards' calls holds them to bit-identical results)
+            const std::vector<double> pi(mixing, mixing + K), mu(means, means + kd), cv(covariances, covariances + cov_doubles);
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_em_iterate(sh.ctx, sh.part, K, covariance_type, sh.replicated(mixing, K, pi.data()), sh.replicated(means, kd, mu.data()),
+                                        sh.replicated(covariances, cov_doubles, cv.data()), max_steps, absolute_tolerance, relative_tolerance,
+                                        sh.scalar(steps_done, "iterations"), sh.scalar(converged, "iterations"), sh.scalar(log_likelihood),
+                                        sh.replicated(log_likelihood_history, max_steps));
+            });
+            return;
+        }
         em_iterate(data, em_route(data, (int)K, diag), (int)K, diag, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance, steps_done,
                    converged, log_likelihood, log_likelihood_history);
-        const size_t cov_doubles = (size_t)K * data->d * (diag ? 1 : data->d);
-        ctx->check_ranks_agree("the EM parameters", {{mixing, K}, {means, (size_t)K * data->d}, {covariances, cov_doubles}, {log_likelihood, 1}});
+        ctx->check_ranks_agree("the EM parameters", {{mixing, K}, {means, kd}, {covariances, cov_doubles}, {log_likelihood, 1}});
     });
 }
 
@@ -626,10 +661,17 @@ int mlhip_em_maximisation_from(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, con
                                double* mixing_out, double* means_out, double* covariances_out)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::em_maximisation(ctx, data, K, 1, resp, ldr, nullptr, mixing_out, means_out, covariances_out); return; }
-        check_em_args(ctx, data, K);
-        require((resp || data->n == 0) && mixing_out && means_out && covariances_out, "null argument");   // (an empty shard has no rows)
-        require(ldr >= (int64_t)data->n, "ldr must be >= n_local");
+        check_call(ctx, data, K);
+        require((resp || data->rows() == 0) && mixing_out && means_out && covariances_out, "null argument");   // (an empty shard has no rows)
+        require(ldr >= 0 && (uint64_t)ldr >= data->rows(), "ldr must be >= n_local");
+        if (ctx->group) {
+            const size_t kd = (size_t)K * data->d;
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_em_maximisation_from(sh.ctx, sh.part, K, sh.rows(resp), ldr, sh.replicated(mixing_out, K), sh.replicated(means_out, kd),
+                                                 sh.replicated(covariances_out, kd * data->d));
+            });
+            return;
+        }
         ensure_em_workspace(data, (int)K);
         data->resp_dev.reserve(sizeof(double) * data->ldr * K);
         HIP_CHECK(hipMemsetAsync(data->resp_dev.p, 0, sizeof(double) * data->ldr * K, ctx->stream));
@@ -646,9 +688,16 @@ int mlhip_em_maximisation_from_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t
                                       double* mixing_out, double* means_out, double* covariances_out)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::em_maximisation(ctx, data, K, 2, nullptr, 0, labels, mixing_out, means_out, covariances_out); return; }
-        check_em_args(ctx, data, K);
-        require((labels || data->n == 0) && mixing_out && means_out && covariances_out, "null argument");
+        check_call(ctx, data, K);
+        require((labels || data->rows() == 0) && mixing_out && means_out && covariances_out, "null argument");
+        if (ctx->group) {
+            const size_t kd = (size_t)K * data->d;
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_em_maximisation_from_labels(sh.ctx, sh.part, K, sh.rows(labels), sh.replicated(mixing_out, K), sh.replicated(means_out, kd),
+                                                        sh.replicated(covariances_out, kd * data->d));
+            });
+            return;
+        }
         ensure_em_workspace(data, (int)K);
         data->labels_dev.reserve(sizeof(uint32_t) * data->n_pad);
         if (data->n)
@@ -666,11 +715,12 @@ int mlhip_em_responsibilities_rows(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
                                    int64_t ldr)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::em_responsibilities(ctx, data, K, resp, ldr, first_row, n_rows); return; }
-        check_em_args(ctx, data, K);
-        require(first_row <= data->n && n_rows <= data->n - first_row, "row range beyond this block");
+        check_call(ctx, data, K);
+        require(first_row <= data->rows() && n_rows <= data->rows() - first_row,
+                ctx->group ? "row range beyond the sample" : "row range beyond this block");
         require(resp || n_rows == 0, "null argument");
-        require(ldr >= (int64_t)n_rows, "ldr must be >= the number of rows");
+        require(ldr >= 0 && (uint64_t)ldr >= n_rows, "ldr must be >= the number of rows");
+        if (ctx->group) { grp::em_responsibilities(ctx, data, K, resp, ldr, first_row, n_rows); return; }
         require(data->has_estep_results((int)K), "no E-step results on the device for this K");
         if (!n_rows) return;
         ensure_lw(data, em_route(data, (int)K, false), (int)K);
@@ -689,16 +739,18 @@ int mlhip_em_responsibilities_rows(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
 int mlhip_em_responsibilities(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* resp, int64_t ldr)
 {
     if (!data) return mlhip_em_responsibilities_rows(ctx, data, K, 0, 0, resp, ldr);      // (reports the null argument)
-    const uint64_t n = data->parts.empty() ? (uint64_t)data->n : data->n_global;
-    return mlhip_em_responsibilities_rows(ctx, data, K, 0, n, resp, ldr);
+    return mlhip_em_responsibilities_rows(ctx, data, K, 0, data->rows(), resp, ldr);
 }
 
 int mlhip_em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labels)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::em_labels(ctx, data, K, labels); return; }
-        check_em_args(ctx, data, K);
-        require(labels || data->n == 0, "null argument");
+        check_call(ctx, data, K);
+        require(labels || data->rows() == 0, "null argument");
+        if (ctx->group) {
+            fan_out(ctx, data, [&](Shard& sh) { return mlhip_em_labels(sh.ctx, sh.part, K, sh.rows(labels)); });
+            return;
+        }
         require(data->has_estep_results((int)K), "no E-step results on the device for this K");
         ensure_lw(data, em_route(data, (int)K, false), (int)K);
         data->labels_dev.reserve(sizeof(uint32_t) * data->n_pad);

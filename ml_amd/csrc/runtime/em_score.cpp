@@ -94,10 +94,16 @@ int mlhip_em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_
                    const double* covariances, double* log_density, uint32_t* labels)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::em_score(ctx, data, K, covariance_type, mixing, means, covariances, log_density, labels); return; }
-        check_em_args(ctx, data, K);
+        check_call(ctx, data, K);
         require(mixing && means && covariances, "null argument");
         require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL, "bad covariance_type");
+        if (ctx->group) {
+            // (every shard scores its own rows: no collective, nothing to put together but the rows' places in the caller's arrays)
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_em_score(sh.ctx, sh.part, K, covariance_type, mixing, means, covariances, sh.rows(log_density), sh.rows(labels));
+            });
+            return;
+        }
         em_score(data, (int)K, covariance_type == MLHIP_COVARIANCE_DIAGONAL, mixing, means, covariances, log_density, labels);
     });
 }

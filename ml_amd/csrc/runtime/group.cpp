@@ -138,37 +138,30 @@ mlhip_group* group_of(const mlhip_ctx* ctx)
     return ctx->group;
 }
 
-void check_group_data(const mlhip_ctx* ctx, const mlhip_data* data)
+/// GPUs `from_devices` read the memory of GPU `to_device` from now on -- or, where one of them cannot, the call is refused (a kernel
+/// that reads memory it cannot reach faults, and a fault can take the node's GPUs down). `remedy`: what the caller can do instead.
+void enable_peer_access(const std::vector<int>& from_devices, int to_device, const char* remedy)
 {
-    require(ctx && data, "null context or data");
-    require(data->ctx == ctx, "data belongs to another context");
-    require((int)data->parts.size() == ctx->group->n, "data was not uploaded through this device group");
+    for (int dev : from_devices) {
+        if (dev == to_device) continue;
+        int can = 0;
+        HIP_CHECK(hipDeviceCanAccessPeer(&can, dev, to_device));
+        if (!can)
+            throw Unsupported("device group: GPU " + std::to_string(dev) + " cannot read the memory of GPU " + std::to_string(to_device) +
+                              " (no peer access): " + remedy);
+        HIP_CHECK(hipSetDevice(dev));
+        const hipError_t e = hipDeviceEnablePeerAccess(to_device, 0);
+        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIP_CHECK(e);
+        (void)hipGetLastError();
+    }
 }
 
-template <class F> void each_shard(mlhip_ctx* ctx, F&& f)
+std::vector<int> distinct_devices(const mlhip_group* g)
 {
-    mlhip_group* g = group_of(ctx);
-    run_on_shards(g, [&](int s) { f(s, g->shard[(size_t)s]); });
-}
-
-uint64_t rows_of(const mlhip_data* data, int s) { return data->first_row[(size_t)s + 1] - data->first_row[(size_t)s]; }
-
-void enable_peer_access(const std::vector<int>& devices)
-{
-    for (int a : devices)
-        for (int b : devices) {
-            if (a == b) continue;
-            int can = 0;
-            HIP_CHECK(hipDeviceCanAccessPeer(&can, a, b));
-            if (!can)
-                throw Unsupported("device group: GPUs " + std::to_string(a) + " and " + std::to_string(b) +
-                                  " cannot access each other's memory (the in-process all-reduce needs peer access; use RCCL: "
-                                  "MLHIP_GROUP_REDUCE=rccl)");
-            HIP_CHECK(hipSetDevice(a));
-            const hipError_t e = hipDeviceEnablePeerAccess(b, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIP_CHECK(e);
-            (void)hipGetLastError();
-        }
+    std::vector<int> unique;
+    for (int dev : g->devices)
+        if (std::find(unique.begin(), unique.end(), dev) == unique.end()) unique.push_back(dev);
+    return unique;
 }
 
 }  // namespace
@@ -182,6 +175,29 @@ void enable_peer_access(const std::vector<int>& devices)
     case MLHIP_E_UNSUPPORTED: throw Unsupported(message);
     default: throw std::runtime_error(message);
     }
+}
+
+void fan_out(mlhip_ctx* ctx, mlhip_data* data, const std::function<int(Shard&)>& f)
+{
+    mlhip_group* g = group_of(ctx);
+    std::vector<Shard> view((size_t)g->n);
+    for (int s = 0; s < g->n; ++s) {
+        Shard& sh = view[(size_t)s];
+        sh.index = s;
+        sh.ctx = g->shard[(size_t)s];
+        sh.part = data->parts[(size_t)s];
+        sh.first_row = data->first_row[(size_t)s];
+        sh.n_rows = data->first_row[(size_t)s + 1] - sh.first_row;
+        sh.scratch.reserve(8);                                // (so that the shard's thread allocates its outputs only)
+        sh.scalars.reserve(4);
+    }
+    run_on_shards(g, [&](int s) { check_status(f(view[(size_t)s])); });
+    const std::vector<Shard::Scalar>& first = view[0].scalars;
+    for (const Shard& sh : view)
+        for (size_t i = 0; i < first.size(); ++i)
+            if (first[i].stopped_at && std::memcmp(first[i].mine, sh.scalars[i].mine, first[i].bytes) != 0)
+                throw std::runtime_error(std::string("device group: the shards stopped at different ") + first[i].stopped_at);
+    for (const Shard::Scalar& v : first) std::memcpy(v.caller, v.mine, v.bytes);
 }
 
 namespace grp {
@@ -244,10 +260,9 @@ mlhip_ctx* create(int n_shards, const int* device_ids)
                 }
             }
             if (!rccl) {
-                std::vector<int> unique;
-                for (int dev : g->devices)
-                    if (std::find(unique.begin(), unique.end(), dev) == unique.end()) unique.push_back(dev);
-                enable_peer_access(unique);
+                const std::vector<int> unique = distinct_devices(g);
+                for (int dev : unique)
+                    enable_peer_access(unique, dev, "the in-process all-reduce needs it; use RCCL: MLHIP_GROUP_REDUCE=rccl");
                 for (int p = 0; p < 2; ++p) {
                     g->slot[p].resize((size_t)n_shards);
                     g->ready[p].assign((size_t)n_shards, nullptr);
@@ -373,26 +388,13 @@ mlhip_data* upload(mlhip_ctx* ctx, const double* x, bool on_device, uint32_t d, 
         for (int s = 0; s < g->n; ++s) gd->first_row[(size_t)s + 1] = gd->first_row[(size_t)s] + base + ((uint64_t)s < rem ? 1 : 0);
         if (on_device && n) {
             // a block already in device memory must be readable from every shard's GPU: its own GPU, or a peer with access enabled
-            // (a kernel that reads memory it cannot reach faults -- and a fault can take the node's GPUs down)
             hipPointerAttribute_t attr{};
             if (hipPointerGetAttributes(&attr, x) != hipSuccess) { (void)hipGetLastError(); throw InvalidArgument("x_dev is not a device pointer"); }
-            std::vector<int> others;
-            for (int dev : g->devices)
-                if (dev != attr.device && std::find(others.begin(), others.end(), dev) == others.end()) others.push_back(dev);
-            for (int dev : others) {
-                int can = 0;
-                HIP_CHECK(hipDeviceCanAccessPeer(&can, dev, attr.device));
-                if (!can) throw Unsupported("device group: the block lives on GPU " + std::to_string(attr.device) + ", which GPU " +
-                                            std::to_string(dev) + " cannot read (no peer access): upload it from host memory");
-                HIP_CHECK(hipSetDevice(dev));
-                const hipError_t e = hipDeviceEnablePeerAccess(attr.device, 0);
-                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIP_CHECK(e);
-                (void)hipGetLastError();
-            }
+            enable_peer_access(distinct_devices(g), attr.device, "upload the block from host memory");
         }
-        each_shard(ctx, [&](int s, mlhip_ctx* c) {
-            const uint64_t lo = gd->first_row[(size_t)s];
-            gd->parts[(size_t)s] = upload_common(c, x ? x + (int64_t)lo * ld : nullptr, on_device, d, rows_of(gd, s), ld);
+        run_on_shards(g, [&](int s) {
+            const uint64_t lo = gd->first_row[(size_t)s], rows = gd->first_row[(size_t)s + 1] - lo;
+            gd->parts[(size_t)s] = upload_common(g->shard[(size_t)s], x ? x + (int64_t)lo * ld : nullptr, on_device, d, rows, ld);
         });
         gd->shift = gd->parts[0]->shift;
         require(gd->parts[0]->n_global == n, "device group: the shards disagree on the sample size");
@@ -404,49 +406,10 @@ mlhip_data* upload(mlhip_ctx* ctx, const double* x, bool on_device, uint32_t d, 
     return gd;
 }
 
-void sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance)
-{
-    check_group_data(ctx, data);
-    require(covariance, "null argument");
-    const size_t d = (size_t)data->d;
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        std::vector<double> m(d), cov(d * d);                 // every shard holds the same all-reduced result: shard 0's goes out
-        check_status(mlhip_sample_covariance(c, data->parts[(size_t)s], s == 0 && mean ? mean : m.data(), s == 0 ? covariance : cov.data()));
-    });
-}
-
-void set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weights)
-{
-    check_group_data(ctx, data);
-    data->weighted = false;
-    data->weight_sum = 0;
-    // every shard validates its rows and all-reduces [sum, invalid count]: all accept, or all refuse and stay unweighted
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        check_status(mlhip_data_set_weights(c, data->parts[(size_t)s], weights ? weights + data->first_row[(size_t)s] : nullptr));
-    });
-    data->weighted = data->parts[0]->weighted;
-    data->weight_sum = data->parts[0]->weight_sum;
-}
-
-void xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt, double* xy)
-{
-    check_group_data(ctx, data);
-    require((y || data->n_global == 0) && xxt && xy, "null argument");
-    const size_t d = (size_t)data->d;
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        std::vector<double> a(s ? d * d : 0), b(s ? d : 0);
-        check_status(mlhip_xxt_xy(c, data->parts[(size_t)s], y ? y + data->first_row[(size_t)s] : nullptr, s ? a.data() : xxt, s ? b.data() : xy));
-    });
-}
-
 void random_partition_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const uint32_t* order, const uint32_t* offsets, double* means,
                             double* sizes)
 {
-    check_group_data(ctx, data);
     mlhip_group* g = group_of(ctx);
-    require(K >= 1 && offsets && means && sizes && (order || data->n_global == 0), "null argument");
-    require(offsets[0] == 0 && offsets[K] == data->n_global, "offsets must cover the sample's rows");
-    for (uint32_t k = 0; k < K; ++k) require(offsets[k] <= offsets[k + 1], "offsets must ascend");
     // The running means are order dependent (ML/Clustering.cpp:33-35): the shards continue each other's K d chains in row order,
     // one after the other. A cluster's rows are listed ascending, so a shard's share of every list is one contiguous piece.
     std::vector<uint32_t> local_order, local_offsets((size_t)K + 1);
@@ -468,267 +431,13 @@ void random_partition_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const 
     }
 }
 
-namespace {
-/// Parameter sets of the shards: inputs may alias outputs and every shard writes its (identical) results, so each works on copies
-/// of its own; shard 0's copy goes back to the caller.
-struct ShardParams {
-    std::vector<double> mixing, means, covs;
-    double ll = 0;
-};
-}  // namespace
-
-void em_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, bool diag, const double* mixing, const double* means, const double* covs,
-             double* log_likelihood, double* mixing_out, double* means_out, double* covs_out)
-{
-    check_group_data(ctx, data);
-    require(K >= 1, "At least one component required");
-    require(mixing && means && covs && log_likelihood && mixing_out && means_out && covs_out, "null argument");
-    mlhip_group* g = group_of(ctx);
-    const size_t d = (size_t)data->d, n_cov = diag ? K * d : K * d * d;
-    std::vector<ShardParams> p((size_t)g->n);
-    for (auto& q : p) { q.mixing.assign(mixing, mixing + K); q.means.assign(means, means + K * d); q.covs.assign(covs, covs + n_cov); }
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        ShardParams& q = p[(size_t)s];
-        check_status(diag ? mlhip_em_step_diag(c, data->parts[(size_t)s], K, q.mixing.data(), q.means.data(), q.covs.data(), &q.ll,
-                                               q.mixing.data(), q.means.data(), q.covs.data())
-                          : mlhip_em_step(c, data->parts[(size_t)s], K, q.mixing.data(), q.means.data(), q.covs.data(), &q.ll,
-                                          q.mixing.data(), q.means.data(), q.covs.data()));
-    });
-    std::copy(p[0].mixing.begin(), p[0].mixing.end(), mixing_out);
-    std::copy(p[0].means.begin(), p[0].means.end(), means_out);
-    std::copy(p[0].covs.begin(), p[0].covs.end(), covs_out);
-    *log_likelihood = p[0].ll;
-}
-
-void em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type, double* mixing, double* means, double* covs,
-                uint32_t max_steps, double atol, double rtol, uint32_t* steps_done, int* converged, double* log_likelihood,
-                double* history)
-{
-    check_group_data(ctx, data);
-    require(K >= 1, "At least one component required");
-    require(mixing && means && covs && steps_done && converged && log_likelihood, "null argument");
-    require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL, "bad covariance_type");
-    mlhip_group* g = group_of(ctx);
-    const size_t d = (size_t)data->d, n_cov = covariance_type == MLHIP_COVARIANCE_DIAGONAL ? K * d : K * d * d;
-    std::vector<ShardParams> p((size_t)g->n);
-    for (size_t s = 1; s < p.size(); ++s) {
-        p[s].mixing.assign(mixing, mixing + K); p[s].means.assign(means, means + K * d); p[s].covs.assign(covs, covs + n_cov);
-    }
-    std::vector<uint32_t> steps((size_t)g->n, 0);
-    std::vector<int> conv((size_t)g->n, 0);
-    // (the ranks' end-of-fit checksum exchange inside mlhip_em_iterate holds the shards to bit-identical parameters)
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        ShardParams& q = p[(size_t)s];
-        std::vector<double> own_history(s && history ? max_steps : 0);
-        check_status(mlhip_em_iterate(c, data->parts[(size_t)s], K, covariance_type, s ? q.mixing.data() : mixing, s ? q.means.data() : means,
-                                      s ? q.covs.data() : covs, max_steps, atol, rtol, &steps[(size_t)s], &conv[(size_t)s], &q.ll,
-                                      s ? (history ? own_history.data() : nullptr) : history));
-    });
-    for (int s = 1; s < g->n; ++s)
-        if (steps[(size_t)s] != steps[0] || conv[(size_t)s] != conv[0]) throw std::runtime_error("device group: the shards stopped at different iterations");
-    *steps_done = steps[0];
-    *converged = conv[0];
-    *log_likelihood = p[0].ll;
-}
-
-void em_expectation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* mixing, const double* means, const double* covs,
-                    double* log_likelihood)
-{
-    check_group_data(ctx, data);
-    require(mixing && means && covs && log_likelihood, "null argument");
-    std::vector<double> ll((size_t)group_of(ctx)->n, 0.0);
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        check_status(mlhip_em_expectation(c, data->parts[(size_t)s], K, mixing, means, covs, &ll[(size_t)s]));
-    });
-    *log_likelihood = ll[0];
-}
-
-void em_maximisation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int source, const double* resp, int64_t ldr, const uint32_t* labels,
-                     double* mixing_out, double* means_out, double* covs_out)
-{
-    check_group_data(ctx, data);
-    require(K >= 1, "At least one component required");
-    require(mixing_out && means_out && covs_out, "null argument");
-    if (source == 1) {
-        require(resp || data->n_global == 0, "null argument");
-        require(ldr >= 0 && (uint64_t)ldr >= data->n_global, "ldr must be >= the number of rows");
-    }
-    if (source == 2) require(labels || data->n_global == 0, "null argument");
-    mlhip_group* g = group_of(ctx);
-    const size_t d = (size_t)data->d;
-    std::vector<ShardParams> p((size_t)g->n);
-    for (size_t s = 1; s < p.size(); ++s) { p[s].mixing.resize(K); p[s].means.resize(K * d); p[s].covs.resize(K * d * d); }
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        ShardParams& q = p[(size_t)s];
-        double* pi = s ? q.mixing.data() : mixing_out;
-        double* mu = s ? q.means.data() : means_out;
-        double* cv = s ? q.covs.data() : covs_out;
-        mlhip_data* part = data->parts[(size_t)s];
-        const uint64_t lo = data->first_row[(size_t)s];
-        if (source == 0) check_status(mlhip_em_maximisation(c, part, K, pi, mu, cv));
-        else if (source == 1) check_status(mlhip_em_maximisation_from(c, part, K, resp ? resp + lo : nullptr, ldr, pi, mu, cv));
-        else check_status(mlhip_em_maximisation_from_labels(c, part, K, labels ? labels + lo : nullptr, pi, mu, cv));
-    });
-}
-
 void em_responsibilities(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* resp, int64_t ldr, uint64_t first, uint64_t count)
 {
-    check_group_data(ctx, data);
-    require(first <= data->n_global && count <= data->n_global - first, "row range beyond the sample");
-    require(resp || count == 0, "null argument");
-    require(ldr >= 0 && (uint64_t)ldr >= count, "ldr must be >= the number of rows");
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        const uint64_t lo = std::max(first, data->first_row[(size_t)s]), hi = std::min(first + count, data->first_row[(size_t)s + 1]);
-        if (lo >= hi) return;                                 // (no collective inside: a shard may sit this one out)
-        check_status(mlhip_em_responsibilities_rows(c, data->parts[(size_t)s], K, lo - data->first_row[(size_t)s], hi - lo, resp + (lo - first), ldr));
+    fan_out(ctx, data, [&](Shard& sh) {
+        const uint64_t lo = std::max(first, sh.first_row), hi = std::min(first + count, sh.first_row + sh.n_rows);
+        if (lo >= hi) return (int)MLHIP_OK;                   // (no collective inside: a shard may sit this one out)
+        return mlhip_em_responsibilities_rows(sh.ctx, sh.part, K, lo - sh.first_row, hi - lo, resp + (lo - first), ldr);
     });
-}
-
-void em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labels)
-{
-    check_group_data(ctx, data);
-    require(labels || data->n_global == 0, "null argument");
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        check_status(mlhip_em_labels(c, data->parts[(size_t)s], K, labels ? labels + data->first_row[(size_t)s] : nullptr));
-    });
-}
-
-void em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type, const double* mixing, const double* means,
-              const double* covs, double* log_density, uint32_t* labels)
-{
-    check_group_data(ctx, data);
-    // (every shard scores its own rows: no collective, nothing to put together but the rows' places in the caller's arrays)
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        const uint64_t lo = data->first_row[(size_t)s];
-        check_status(mlhip_em_score(c, data->parts[(size_t)s], K, covariance_type, mixing, means, covs,
-                                    log_density ? log_density + lo : nullptr, labels ? labels + lo : nullptr));
-    });
-}
-
-void kmeans_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, bool accumulate, const double* centroids, double* inertia,
-                 uint64_t* n_changed, double* counts, double* centroids_out)
-{
-    check_group_data(ctx, data);
-    require(K >= 1, "At least one component required");
-    require(centroids && inertia && n_changed && (!accumulate || (counts && centroids_out)), "null argument");
-    mlhip_group* g = group_of(ctx);
-    const size_t kd = (size_t)K * data->d;
-    const std::vector<double> in(centroids, centroids + kd);   // (centroids_out may alias centroids)
-    std::vector<double> inert((size_t)g->n, 0.0);
-    std::vector<uint64_t> changed((size_t)g->n, 0);
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        mlhip_data* part = data->parts[(size_t)s];
-        if (accumulate) {
-            std::vector<double> cnt(s ? K : 0), out(s ? kd : 0);
-            check_status(mlhip_kmeans_step(c, part, K, in.data(), &inert[(size_t)s], &changed[(size_t)s], s ? cnt.data() : counts,
-                                           s ? out.data() : centroids_out));
-        } else {
-            check_status(mlhip_kmeans_assign(c, part, K, in.data(), &inert[(size_t)s], &changed[(size_t)s]));
-        }
-    });
-    *inertia = inert[0];
-    *n_changed = changed[0];
-}
-
-void kmeans_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* centroids, double* old_centroids, uint32_t max_steps,
-                    double atol, uint32_t* steps_done, int* converged, double* inertia, double* counts)
-{
-    check_group_data(ctx, data);
-    require(K >= 1, "At least one component required");
-    require(centroids && steps_done && converged && inertia, "null argument");
-    mlhip_group* g = group_of(ctx);
-    const size_t kd = (size_t)K * data->d;
-    const std::vector<double> start(centroids, centroids + kd);
-    std::vector<uint32_t> steps((size_t)g->n, 0);
-    std::vector<int> conv((size_t)g->n, 0);
-    std::vector<double> inert((size_t)g->n, 0.0);
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        std::vector<double> cur(s ? start : std::vector<double>()), old(s ? kd : 0), cnt(s ? K : 0);
-        check_status(mlhip_kmeans_iterate(c, data->parts[(size_t)s], K, s ? cur.data() : centroids, s ? old.data() : old_centroids, max_steps,
-                                          atol, &steps[(size_t)s], &conv[(size_t)s], &inert[(size_t)s], s ? cnt.data() : counts));
-    });
-    for (int s = 1; s < g->n; ++s)
-        if (steps[(size_t)s] != steps[0] || conv[(size_t)s] != conv[0]) throw std::runtime_error("device group: the shards stopped at different steps");
-    *steps_done = steps[0];
-    *converged = conv[0];
-    *inertia = inert[0];
-}
-
-void kmeans_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t* labels)
-{
-    check_group_data(ctx, data);
-    require(labels || data->n_global == 0, "null argument");
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        check_status(mlhip_kmeans_labels(c, data->parts[(size_t)s], labels ? labels + data->first_row[(size_t)s] : nullptr));
-    });
-}
-
-void kmeans_distances(mlhip_ctx* ctx, mlhip_data* data, double* dist2)
-{
-    check_group_data(ctx, data);
-    require(dist2 || data->n_global == 0, "null argument");
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        check_status(mlhip_kmeans_distances(c, data->parts[(size_t)s], dist2 ? dist2 + data->first_row[(size_t)s] : nullptr));
-    });
-}
-
-void kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int first, double u, uint64_t first_row, uint64_t* index,
-              int* certain, double* weights_out)
-{
-    check_group_data(ctx, data);
-    require(centroid && index && certain, "null argument");
-    require(first_row == 0, "a device group holds the whole sample: first_row must be 0");
-    mlhip_group* g = group_of(ctx);
-    std::vector<uint64_t> idx((size_t)g->n, 0);
-    std::vector<int> sure((size_t)g->n, 0);
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        const uint64_t lo = data->first_row[(size_t)s];
-        check_status(mlhip_kpp_draw(c, data->parts[(size_t)s], centroid, first, u, lo, &idx[(size_t)s], &sure[(size_t)s],
-                                    weights_out ? weights_out + lo : nullptr));
-    });
-    *index = idx[0];
-    *certain = sure[0];
-}
-
-void kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int first, double u, uint64_t first_row, uint64_t* index)
-{
-    check_group_data(ctx, data);
-    require(centroid && index, "null argument");
-    require(first_row == 0, "a device group holds the whole sample: first_row must be 0");
-    mlhip_group* g = group_of(ctx);
-    std::vector<uint64_t> idx((size_t)g->n, 0);
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        check_status(mlhip_kpp_draw_fixed_point(c, data->parts[(size_t)s], centroid, first, u, data->first_row[(size_t)s], &idx[(size_t)s]));
-    });
-    *index = idx[0];
-}
-
-void kpp_weights(mlhip_ctx* ctx, mlhip_data* data, double* weights_out)
-{
-    check_group_data(ctx, data);
-    require(weights_out || data->n_global == 0, "null argument");
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        check_status(mlhip_kpp_weights(c, data->parts[(size_t)s], weights_out ? weights_out + data->first_row[(size_t)s] : nullptr));
-    });
-}
-
-void min_squared_distances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* dist2)
-{
-    check_group_data(ctx, data);
-    require(centroids && (dist2 || data->n_global == 0), "null argument");
-    each_shard(ctx, [&](int s, mlhip_ctx* c) {
-        check_status(mlhip_min_squared_distances(c, data->parts[(size_t)s], K, centroids, dist2 ? dist2 + data->first_row[(size_t)s] : nullptr));
-    });
-}
-
-void timing_enable(mlhip_ctx* ctx, int on)
-{
-    for (mlhip_ctx* c : group_of(ctx)->shard) check_status(mlhip_timing_enable(c, on));
-}
-
-void timing_reset(mlhip_ctx* ctx)
-{
-    for (mlhip_ctx* c : group_of(ctx)->shard) check_status(mlhip_timing_reset(c));
 }
 
 /// The slowest shard's average (launch counts of that shard): what bounds the group's step.

@@ -18,15 +18,18 @@
 #include <functional>
 #include <mutex>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <ctime>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "device/device.hpp"
@@ -456,6 +459,8 @@ struct mlhip_data {
     DevBuf weights{&pool}, wresp{&pool};
     bool weighted = false;
     double weight_sum = 0;        // W over all ranks
+    /// Rows behind the host arrays of a call on this handle: this block's -- a group's handle holds the whole sample.
+    uint64_t rows() const { return parts.empty() ? (uint64_t)n : n_global; }
     /// What the log-likelihood and the mixing proportions are divided by: W, or the row count of an unweighted block.
     double total_weight() const { return weighted ? weight_sum : (double)n_global; }
     // EM workspace (sized for em_K)
@@ -655,7 +660,9 @@ double log_two_pi();
 
 double ll_from_stats(const mlhip_data* dt, int K);
 
-void check_em_args(mlhip_ctx* ctx, mlhip_data* dt, uint32_t K);
+/// What every entry point on a data handle checks first: a context with a handle of its own -- a single context (made current) with a
+/// block uploaded to it, or a device group's with a block uploaded through the group -- and K >= 1.
+void check_call(mlhip_ctx* ctx, mlhip_data* dt, uint32_t K);
 
 /// Ratio (mean offset from the shared shift)^2 / variance above which a component's covariance is recomputed about its
 /// own mean. The one-GEMM statistics share one shift (the global mean), so Sigma_k = M2'/S0 - m m^T cancels
@@ -743,8 +750,59 @@ inline void check_status(int status) { if (status != MLHIP_OK) throw_status(stat
 mlhip_ctx* create_single_context(int device_id);
 void destroy_single_context(mlhip_ctx* ctx);
 
-// ---- device group (group.cpp): one caller-visible context over n shards. Every function is the group form of the entry point of
-// the same name: host arrays are the caller's WHOLE arrays (rows of all shards), results are what a single context would return.
+// ---- device group (group.cpp): one caller-visible context over n shards. An entry point called with a group's context checks its
+// arguments as for a single context (check_call; host arrays are the caller's WHOLE arrays, mlhip_data::rows() rows) and then calls
+// itself on every shard through fan_out; results are what a single context would return.
+
+/// One shard's side of a fanned-out call: its ordinary context, its part of the block, its rows of the caller's sample, and the
+/// three rules by which the caller's arguments become the shard's.
+struct Shard {
+    int index = 0;
+    mlhip_ctx* ctx = nullptr;
+    mlhip_data* part = nullptr;
+    uint64_t first_row = 0, n_rows = 0;
+
+    /// The shard's rows of a per-row array of the caller's, `ld` values per row (null stays null).
+    template <class T> T* rows(T* p, int64_t ld = 1) const { return p ? p + (int64_t)first_row * ld : nullptr; }
+    /// An output every shard computes alike (all-reduced statistics behind it): the caller's array on shard 0, scratch of `count`
+    /// values elsewhere (null stays null) -- starting from `init` where the array is in/out. `init` is a copy the entry point made
+    /// BEFORE the fan-out, as is every input that may alias an output: shard 0 writes the caller's arrays while the others still read
+    /// (so a call that fails on some shard leaves the caller's output ARRAYS unspecified).
+    template <class T> T* replicated(T* out, size_t count, const T* init = nullptr)
+    {
+        if (index == 0 || !out) return out;
+        T* mine = scratch_of<T>(count);
+        if (init) std::copy(init, init + count, mine);
+        return mine;
+    }
+    /// A scalar output: every shard writes one of its own, and shard 0's goes to the caller once ALL shards have succeeded (null stays
+    /// null). `stopped_at` ("iterations", "steps"): the call fails unless every shard's value is the same.
+    template <class T> T* scalar(T* out, const char* stopped_at = nullptr)
+    {
+        if (!out) return out;
+        T* mine = scratch_of<T>(1);
+        scalars.push_back({out, mine, sizeof(T), stopped_at});
+        return mine;
+    }
+
+    struct Scalar { void* caller; const void* mine; size_t bytes; const char* stopped_at; };
+    std::vector<Scalar> scalars;                                  // (in the order of the call's arguments: the same on every shard)
+    std::vector<std::unique_ptr<unsigned char[]>> scratch;
+
+private:
+    template <class T> T* scratch_of(size_t count)
+    {
+        static_assert(std::is_trivial<T>::value && alignof(T) <= alignof(std::max_align_t), "plain values only");
+        scratch.emplace_back(new unsigned char[count * sizeof(T)]());
+        return reinterpret_cast<T*>(scratch.back().get());
+    }
+};
+
+/// f(shard) on every shard's thread (ShardTeam: a failure of one shard fails the call on the caller's thread, the group recovers
+/// before the next one); f returns the status of the shard's own mlhip_* call.
+void fan_out(mlhip_ctx* ctx, mlhip_data* data, const std::function<int(Shard&)>& f);
+
+// What is not a plain fan-out:
 namespace grp {
 mlhip_ctx* create(int n_shards, const int* device_ids);
 void destroy(mlhip_ctx* ctx);
@@ -753,39 +811,11 @@ int shard_count(const mlhip_ctx* ctx);
 mlhip_ctx* shard_context(const mlhip_ctx* ctx, int shard);
 const char* reduce_kind(const mlhip_ctx* ctx);
 mlhip_data* upload(mlhip_ctx* ctx, const double* x, bool on_device, uint32_t d, uint64_t n, int64_t ld);
-void sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance);
-void set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weights);
-void xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt, double* xy);
+/// (the shards one after the other: they continue each other's running means)
 void random_partition_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const uint32_t* order, const uint32_t* offsets, double* means,
                             double* sizes);
-void em_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, bool diag, const double* mixing, const double* means, const double* covs,
-             double* log_likelihood, double* mixing_out, double* means_out, double* covs_out);
-void em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type, double* mixing, double* means, double* covs,
-                uint32_t max_steps, double atol, double rtol, uint32_t* steps_done, int* converged, double* log_likelihood,
-                double* history);
-void em_expectation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* mixing, const double* means, const double* covs,
-                    double* log_likelihood);
-/// source: 0 = the last E-step (mlhip_em_maximisation), 1 = caller's responsibilities, 2 = caller's labels
-void em_maximisation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int source, const double* resp, int64_t ldr, const uint32_t* labels,
-                     double* mixing_out, double* means_out, double* covs_out);
+/// (every shard the part of the row range it holds)
 void em_responsibilities(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* resp, int64_t ldr, uint64_t first, uint64_t count);
-void em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labels);
-void em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type, const double* mixing, const double* means,
-              const double* covs, double* log_density, uint32_t* labels);
-/// accumulate: the update's sums as well (mlhip_kmeans_step), else the assignment only
-void kmeans_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, bool accumulate, const double* centroids, double* inertia,
-                 uint64_t* n_changed, double* counts, double* centroids_out);
-void kmeans_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* centroids, double* old_centroids, uint32_t max_steps,
-                    double atol, uint32_t* steps_done, int* converged, double* inertia, double* counts);
-void kmeans_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t* labels);
-void kmeans_distances(mlhip_ctx* ctx, mlhip_data* data, double* dist2);
-void kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int first, double u, uint64_t first_row, uint64_t* index,
-              int* certain, double* weights_out);
-void kpp_weights(mlhip_ctx* ctx, mlhip_data* data, double* weights_out);
-void kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int first, double u, uint64_t first_row, uint64_t* index);
-void min_squared_distances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* dist2);
-void timing_enable(mlhip_ctx* ctx, int on);
-void timing_reset(mlhip_ctx* ctx);
 void timing_get(mlhip_ctx* ctx, const char* name, double* avg_ms, uint64_t* launches);
 }  // namespace grp
 

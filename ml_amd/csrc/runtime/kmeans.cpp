@@ -251,9 +251,17 @@ int mlhip_kmeans_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double
                       uint64_t* n_changed, double* counts, double* centroids_out)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::kmeans_step(ctx, data, K, true, centroids, inertia, n_changed, counts, centroids_out); return; }
-        check_em_args(ctx, data, K);
+        check_call(ctx, data, K);
         require(centroids && inertia && n_changed && counts && centroids_out, "null argument");
+        if (ctx->group) {
+            const size_t kd = (size_t)K * data->d;
+            const std::vector<double> in(centroids, centroids + kd);   // (centroids_out may alias centroids)
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_kmeans_step(sh.ctx, sh.part, K, in.data(), sh.scalar(inertia), sh.scalar(n_changed), sh.replicated(counts, K),
+                                         sh.replicated(centroids_out, kd));
+            });
+            return;
+        }
         run_kmeans(data, km_route(data, (int)K), (int)K, centroids, true);
         const double* r = data->km_host.as<double>();
         *inertia = r[0];
@@ -267,16 +275,20 @@ int mlhip_kmeans_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* c
                          double* inertia, double* counts)
 {
     return guarded([&] {
-        if (ctx && ctx->group) {
-            require(max_steps >= 1, "at least one step");
-            require(absolute_tolerance >= 0, "negative tolerance");
-            grp::kmeans_iterate(ctx, data, K, centroids, old_centroids, max_steps, absolute_tolerance, steps_done, converged, inertia, counts);
-            return;
-        }
-        check_em_args(ctx, data, K);
+        check_call(ctx, data, K);
         require(centroids && steps_done && converged && inertia, "null argument");
         require(max_steps >= 1, "at least one step");
         require(absolute_tolerance >= 0, "negative tolerance");
+        if (ctx->group) {
+            const size_t kd = (size_t)K * data->d;
+            const std::vector<double> start(centroids, centroids + kd);   // (in/out: shard 0 updates the caller's, the others copies)
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_kmeans_iterate(sh.ctx, sh.part, K, sh.replicated(centroids, kd, start.data()), sh.replicated(old_centroids, kd),
+                                            max_steps, absolute_tolerance, sh.scalar(steps_done, "steps"), sh.scalar(converged, "steps"),
+                                            sh.scalar(inertia), sh.replicated(counts, K));
+            });
+            return;
+        }
         km_iterate(data, km_route(data, (int)K), (int)K, centroids, old_centroids, max_steps, absolute_tolerance, steps_done, converged, inertia, counts);
         ctx->check_ranks_agree("the K-means centroids", {{centroids, (size_t)K * data->d}, {inertia, 1}});
     });
@@ -286,9 +298,14 @@ int mlhip_kmeans_assign(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const doub
                         uint64_t* n_changed)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::kmeans_step(ctx, data, K, false, centroids, inertia, n_changed, nullptr, nullptr); return; }
-        check_em_args(ctx, data, K);
+        check_call(ctx, data, K);
         require(centroids && inertia && n_changed, "null argument");
+        if (ctx->group) {
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_kmeans_assign(sh.ctx, sh.part, K, centroids, sh.scalar(inertia), sh.scalar(n_changed));
+            });
+            return;
+        }
         run_kmeans(data, km_route(data, (int)K), (int)K, centroids, false);
         const double* r = data->km_host.as<double>();
         *inertia = r[0];
@@ -299,9 +316,12 @@ int mlhip_kmeans_assign(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const doub
 int mlhip_kmeans_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t* labels)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::kmeans_labels(ctx, data, labels); return; }
-        check_em_args(ctx, data, 1);
-        require(labels || data->n == 0, "null argument");
+        check_call(ctx, data, 1);
+        require(labels || data->rows() == 0, "null argument");
+        if (ctx->group) {
+            fan_out(ctx, data, [&](Shard& sh) { return mlhip_kmeans_labels(sh.ctx, sh.part, sh.rows(labels)); });
+            return;
+        }
         require(data->km_have_old, "no K-means assignment on the device yet");
         ctx->sync();
         download_columns(ctx, reinterpret_cast<char*>(labels), 0, data->km_labels[data->km_cur].as<char>(), 0,
@@ -312,9 +332,12 @@ int mlhip_kmeans_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t* labels)
 int mlhip_kmeans_distances(mlhip_ctx* ctx, mlhip_data* data, double* dist2)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::kmeans_distances(ctx, data, dist2); return; }
-        check_em_args(ctx, data, 1);
-        require(dist2 || data->n == 0, "null argument");
+        check_call(ctx, data, 1);
+        require(dist2 || data->rows() == 0, "null argument");
+        if (ctx->group) {
+            fan_out(ctx, data, [&](Shard& sh) { return mlhip_kmeans_distances(sh.ctx, sh.part, sh.rows(dist2)); });
+            return;
+        }
         require(data->km_have_old, "no K-means assignment on the device yet");
         ctx->sync();
         download_columns(ctx, reinterpret_cast<char*>(dist2), 0, data->km_mind.as<char>(), 0, sizeof(double) * data->n, 1);
@@ -325,11 +348,17 @@ int mlhip_kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int
                    int* certain, double* weights_out)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::kpp_draw(ctx, data, centroid, first, u, first_row, index, certain, weights_out); return; }
-        check_em_args(ctx, data, 1);
+        check_call(ctx, data, 1);
         require(centroid && index && certain, "null argument");
         require(data->n_global >= 2, "at least two rows");
         require(u >= 0.0 && u < 1.0, "u must be a canonical uniform draw");
+        if (ctx->group) {
+            require(first_row == 0, "a device group holds the whole sample: first_row must be 0");
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_kpp_draw(sh.ctx, sh.part, centroid, first, u, sh.first_row, sh.scalar(index), sh.scalar(certain), sh.rows(weights_out));
+            });
+            return;
+        }
         const uint64_t n_global = data->n_global;
         require(first_row + data->n <= n_global, "first_row beyond the sample");
         // distances to the new centroid -> km_probe (as mlhip_min_squared_distances, label history untouched)
@@ -398,9 +427,12 @@ int mlhip_kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int
 int mlhip_kpp_weights(mlhip_ctx* ctx, mlhip_data* data, double* weights_out)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::kpp_weights(ctx, data, weights_out); return; }
-        check_em_args(ctx, data, 1);
-        require(weights_out || data->n == 0, "null argument");
+        check_call(ctx, data, 1);
+        require(weights_out || data->rows() == 0, "null argument");
+        if (ctx->group) {
+            fan_out(ctx, data, [&](Shard& sh) { return mlhip_kpp_weights(sh.ctx, sh.part, sh.rows(weights_out)); });
+            return;
+        }
         require(data->kpp_w.p != nullptr, "no K-means++ draw on the device yet");
         ctx->sync();
         download_columns(ctx, reinterpret_cast<char*>(weights_out), 0, data->kpp_w.as<char>(), 0, sizeof(double) * data->n, 1);
@@ -411,11 +443,17 @@ int mlhip_kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* c
                                uint64_t* index)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::kpp_draw_fixed_point(ctx, data, centroid, first, u, first_row, index); return; }
         using fixed_point::u128;
-        check_em_args(ctx, data, 1);
+        check_call(ctx, data, 1);
         require(centroid && index, "null argument");
         require(u >= 0.0 && u < 1.0, "u must be a canonical uniform draw");
+        if (ctx->group) {
+            require(first_row == 0, "a device group holds the whole sample: first_row must be 0");
+            fan_out(ctx, data, [&](Shard& sh) {
+                return mlhip_kpp_draw_fixed_point(sh.ctx, sh.part, centroid, first, u, sh.first_row, sh.scalar(index));
+            });
+            return;
+        }
         const uint64_t n_global = data->n_global;
         require(first_row + data->n <= n_global, "first_row beyond the sample");
         require(first || data->fp_w.p, "no fixed-point K-means++ weights on the device yet: the first draw needs first != 0");
@@ -510,9 +548,12 @@ int mlhip_kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* c
 int mlhip_min_squared_distances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* dist2)
 {
     return guarded([&] {
-        if (ctx && ctx->group) { grp::min_squared_distances(ctx, data, K, centroids, dist2); return; }
-        check_em_args(ctx, data, K);
-        require(centroids && (dist2 || data->n == 0), "null argument");
+        check_call(ctx, data, K);
+        require(centroids && (dist2 || data->rows() == 0), "null argument");
+        if (ctx->group) {
+            fan_out(ctx, data, [&](Shard& sh) { return mlhip_min_squared_distances(sh.ctx, sh.part, K, centroids, sh.rows(dist2)); });
+            return;
+        }
         // Must disturb neither the label history used for n_changed nor the per-sample distances of the last assignment
         // (mlhip_kmeans_distances): the labels go to the spare buffer, the distances to a buffer of their own.
         const int cur = data->km_cur;
