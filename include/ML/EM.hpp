@@ -44,8 +44,13 @@ public:
     `Diagonal` every covariance is restricted to its diagonal (the E-/M-step loops of ML/EM.cpp:190-263 on the diagonal
     entries only; covariances() returns diagonal matrices). Default `Full` == the reference's behaviour.
     One fused kernel serves number_dimensions <= 32 and number_components <= 64; other shapes run the full-covariance kernels on
-    diagonal matrices (slower, never refused). */
-    enum class CovarianceType { Full, Diagonal };
+    diagonal matrices (slower, never refused).
+    With `Tied` all components share ONE covariance (scikit-learn's 'tied'): Sigma = sum_k pi_k Sigma_k of the full M-step, ridge
+    1e-15 once; covariances() returns number_components() copies of it, so the point query and the batch queries work unchanged. The
+    start is the pooled sum_k pi_k Sigma_k of the starting covariances (the sample covariance on the default start). One kernel per
+    iteration serves unweighted fits with number_dimensions <= 32 and number_components <= 64; other shapes and weighted fits run the
+    full-covariance kernels on copies of Sigma and pool the result (mlhip_em_step_tied). */
+    enum class CovarianceType { Full, Diagonal, Tied };
     void set_covariance_type(CovarianceType covariance_type) { covariance_type_ = covariance_type; }
     CovarianceType covariance_type() const { return covariance_type_; }
 

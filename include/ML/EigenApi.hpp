@@ -204,6 +204,9 @@ public:
     }
     void set_verbose(bool verbose) { detail::check(mlpp_em_set_verbose(h_, verbose ? 1 : 0)); }
     void set_maximise_first(bool maximise_first) { detail::check(mlpp_em_set_maximise_first(h_, maximise_first ? 1 : 0)); }
+    /** Extension (ML/EM.hpp): full covariances (default, the reference), diagonal ones, or ONE covariance tied across the components. */
+    enum class CovarianceType { Full = 0, Diagonal = 1, Tied = 2 };
+    void set_covariance_type(CovarianceType covariance_type) { detail::check(mlpp_em_set_covariance_type(h_, static_cast<int>(covariance_type))); }
 
     bool fit(Eigen::Ref<const Eigen::MatrixXd> data) override { return fit_block(data, nullptr); }
     /** Extension: the fit of a weighted sample (ml::EM::fit(data, weights) of ML/EM.hpp): weights(i) >= 0 is the frequency weight of

@@ -175,6 +175,24 @@ int mlhip_em_step_diag(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
                        const double* mixing, const double* means, const double* variances,
                        double* log_likelihood, double* mixing_out, double* means_out, double* variances_out);
 
+/* EXTENSION (no counterpart in the reference): one EM iteration with a TIED covariance -- K means and ONE covariance Sigma shared by
+ * every component (scikit-learn's covariance_type='tied'; the LDA-style mixture). covariance / covariance_out: d*d doubles (symmetric,
+ * column-major). The E-step, the log-likelihood, labels and responsibilities are those of mlhip_em_step on K components that all
+ * carry Sigma; the M-step, with xt = x - shift, W the total weight (N when unweighted), S0_k = sum_i w_i r_ik, S1_k = sum_i w_i r_ik xt_i
+ * and T = sum_i w_i xt_i xt_i^T (constant over a fit: formed once per handle, all-reduced once), is
+ *   pi_k = S0_k / W,  mu_k = shift + S1_k / S0_k,  Sigma = (T - sum_k S1_k S1_k^T / S0_k) / W + 1e-15 I     (the ridge of ML/EM.cpp:252, once)
+ * == sum_k pi_k Sigma_k over mlhip_em_step's covariances; an empty component behaves as there. One kernel for unweighted blocks with
+ * d <= 32, K <= 64 (the sample is whitened once, not once per component; K (d + 1) + 1 statistics are all-reduced); other shapes,
+ * weighted blocks, the few-component shapes whose full-covariance step is the vector-unit fused kernel (measured faster composed;
+ * MLHIP_TIED=kernel takes the kernel there too) and MLHIP_TIED=composed run mlhip_em_step on K copies of Sigma and pool its
+ * covariances (slower than it could be, never refused). Output arrays may alias the input arrays. mlhip_em_responsibilities / _responsibilities_rows / mlhip_em_labels
+ * afterwards work as after mlhip_em_step (the block is rebuilt from the same parameters on demand).
+ * Conditioning: T / W - sum_k pi_k (mu_k - shift)(mu_k - shift)^T loses about log10(|T / W| / lambda_min(Sigma)) digits (the formula
+ * scikit-learn uses); the composed route's refinement pass does not. */
+int mlhip_em_step_tied(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
+                       const double* mixing, const double* means, const double* covariance,
+                       double* log_likelihood, double* mixing_out, double* means_out, double* covariance_out);
+
 /* The iteration loop of EM::fit (ML/EM.cpp:143-170) in ONE call: up to max_steps trips of E-step + M-step, each followed by the
  * reference's convergence test |ll - ll_old| < absolute_tolerance + relative_tolerance * max(|ll_old|, |ll|) from the second
  * trip on (:161-168). Parameters are updated IN PLACE (covariances: K*d*d doubles, or K*d variances with
@@ -182,10 +200,13 @@ int mlhip_em_step_diag(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
  * the reference). Between two tests everything stays on the device -- statistics, all-reduce, the M-step's closing arithmetic
  * and the K Cholesky / inverse factorizations of EM::process_covariances (:274-287), the next E-step's records -- and the
  * host reads back 1 + 2K doubles per iteration (d <= 1024: one wave per component with the matrices in LDS up to d = 64, panelled
- * factorizations in global memory above; beyond d = 1024, or with MLHIP_DEVICE_CLOSE=0, the loop runs through mlhip_em_step). Same results as calling mlhip_em_step in a loop, to the last bits of log().
+ * factorizations in global memory above; beyond d = 1024, or with MLHIP_DEVICE_CLOSE=0, the loop runs through mlhip_em_step).
+ * MLHIP_COVARIANCE_TIED (covariances: d*d doubles, the one shared matrix): every trip is one mlhip_em_step_tied, closed on the HOST --
+ * closing tied iterations on the device is not built. Same results as calling mlhip_em_step in a loop, to the last bits of log().
  * log_likelihood_history (max_steps doubles) may be NULL. Tolerances 0 run exactly max_steps iterations. */
 #define MLHIP_COVARIANCE_FULL 0
 #define MLHIP_COVARIANCE_DIAGONAL 1
+#define MLHIP_COVARIANCE_TIED 2
 int mlhip_em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type,
                      double* mixing, double* means, double* covariances,
                      uint32_t max_steps, double absolute_tolerance, double relative_tolerance,
@@ -222,7 +243,7 @@ int mlhip_em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labe
  * argmax_k of the log-responsibilities (first maximum wins; 0xffffffff where the density is NaN) of this rank's rows of `data`
  * under the given mixture -- the batch form of EM::assign_responsibilities (ML/EM.cpp:176-188), in the log domain: a row the
  * reference's linear-domain sum underflows on still gets its finite log-density. covariance_type as in mlhip_em_iterate (diagonal:
- * K*d variances). log_density (n_local doubles) and labels (n_local) may each be NULL. No N x K block is allocated (d <= 128: one
+ * K*d variances; tied: the d*d shared matrix, scored by the full-covariance routes on K components that carry it). log_density (n_local doubles) and labels (n_local) may each be NULL. No N x K block is allocated (d <= 128: one
  * kernel that writes 8 + 4 bytes per row; above, and under MLHIP_SCORE=composed, the E-step kernel on row chunks into a scratch block
  * of at most 256 MB); nothing the handle holds from earlier calls (E-step results, records, label history, the statistics pass's call
  * history) is changed. A device group scores every shard's rows; a row-sharded job needs no communication. Arguments are checked
@@ -247,6 +268,13 @@ int mlhip_xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt,
 int mlhip_em_statistics_count(uint32_t d, uint32_t* count_per_component);
 int mlhip_em_finalize_statistics(uint32_t d, uint32_t K, const double* statistics, const double* shift,
                                  double n_global, double* mixing_out, double* means_out, double* covariances_out);
+
+/* The tied mode's counterpart (no GPU needed; the closing of both routes of mlhip_em_step_tied is this arithmetic). `statistics`: K
+ * records of d + 1 doubles, [S1_k (d) | S0_k] with S1_k = sum_i w_i r_ik (x_i - shift); `total_scatter`: sum_i w_i xt_i xt_i^T,
+ * xt_i = [x_i - shift ; 1], in the packed layout above (one component's record: (d+1)(d+2)/2 doubles; only the d x d part is read).
+ * covariance_out: d*d doubles. */
+int mlhip_em_finalize_statistics_tied(uint32_t d, uint32_t K, const double* statistics, const double* total_scatter, const double* shift,
+                                      double total_weight, double* mixing_out, double* means_out, double* covariance_out);
 
 /* Host helper, no GPU needed: covariance -> what EM::process_covariances (ML/EM.cpp:274-287) derives:
  * inverse (d*d), sqrt(det). Used by the facade for point queries (EM::assign_responsibilities). */
@@ -362,6 +390,11 @@ int mlhip_em_route(const mlhip_data* data, uint32_t K, int covariance_type, mlhi
  * and under MLHIP_SCORE=composed. */
 enum { MLHIP_SCORE_SCALAR_FED = 0, MLHIP_SCORE_MATRIX4 = 1, MLHIP_SCORE_COMPOSED = 2 };
 int mlhip_em_score_route(const mlhip_data* data, uint32_t K, int* kernel);
+/* Which route mlhip_em_step_tied (and mlhip_em_iterate with MLHIP_COVARIANCE_TIED) takes for K components on `data` (diagnostic,
+ * nothing is launched): the tied kernel for unweighted blocks with d <= 32, K <= 64 except where mlhip_em_route reports the fused kernel in its
+ * vector-unit form (MLHIP_TIED=kernel: there too); composed elsewhere and under MLHIP_TIED=composed. */
+enum { MLHIP_TIED_COMPOSED = 0, MLHIP_TIED_KERNEL = 1 };
+int mlhip_em_tied_route(const mlhip_data* data, uint32_t K, int* kernel);
 int mlhip_kmeans_route(const mlhip_data* data, uint32_t K, mlhip_kmeans_route_info* out);
 
 #ifdef __cplusplus

@@ -53,8 +53,9 @@ int mlpp_em_set_means_initialiser(mlpp_em* h, const mlpp_centroids_initialiser* 
 int mlpp_em_set_responsibilities_initialiser(mlpp_em* h, const mlpp_responsibilities_initialiser* init);
 int mlpp_em_set_verbose(mlpp_em* h, int v);
 int mlpp_em_set_maximise_first(mlpp_em* h, int v);
-/* Extension (ml::EM::set_covariance_type): 0 = full covariances (the reference), 1 = diagonal. */
-int mlpp_em_set_covariance_type(mlpp_em* h, int diagonal);
+/* Extension (ml::EM::set_covariance_type): 0 = full covariances (the reference), 1 = diagonal, 2 = tied (one covariance shared by
+ * all components); any other nonzero value selects diagonal, as it always did. */
+int mlpp_em_set_covariance_type(mlpp_em* h, int covariance_type);
 int mlpp_em_fit(mlpp_em* h, const double* data, uint64_t n, uint32_t d, int* converged);
 /* Extension (ml::EM::fit(data, weights)): the fit of a weighted sample, weights[i] >= 0 the frequency weight of point i (n values). */
 int mlpp_em_fit_weighted(mlpp_em* h, const double* data, const double* weights, uint64_t n, uint32_t d, int* converged);

@@ -370,18 +370,40 @@ class Data:
             v1 = np.stack([np.diag(row) for row in v1])
         return ll.value, pi1, mu1, v1
 
-    def em_iterate(self, mixing, means, covs, max_steps, atol=0.0, rtol=0.0, diagonal=False):
+    def em_step_tied(self, mixing, means, cov):
+        """Tied-covariance extension (mlhip_em_step_tied). cov: the one d x d matrix shared by all components.
+        Returns (log_likelihood, mixing, means, cov)."""
+        K = len(mixing)
+        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
+        means = np.ascontiguousarray(means, dtype=np.float64)
+        cov = np.ascontiguousarray(cov, dtype=np.float64)
+        assert means.shape == (K, self.d) and cov.shape == (self.d, self.d)
+        ll = C.c_double()
+        pi1, mu1, S1 = np.empty(K), np.empty((K, self.d)), np.empty((self.d, self.d))
+        check(lib.mlhip_em_step_tied(self.ctx.handle, self._h, K, dptr(mixing), dptr(means), dptr(cov), C.byref(ll),
+                                     dptr(pi1), dptr(mu1), dptr(S1)))
+        return ll.value, pi1, mu1, S1
+
+    def em_tied_route(self, K):
+        """The route of a tied-covariance step of K components under the switches as they are set now (mlhip_em_tied_route):
+        'composed' | 'kernel'."""
+        k = C.c_int()
+        check(lib.mlhip_em_tied_route(self._h, C.c_uint32(K), C.byref(k)))
+        return ("composed", "kernel")[k.value]
+
+    def em_iterate(self, mixing, means, covs, max_steps, atol=0.0, rtol=0.0, diagonal=False, tied=False):
         """The EM loop in one call (mlhip_em_iterate): up to max_steps iterations with the reference's convergence test, the
-        closing arithmetic on the device. covs: K x d x d (or K x d variances with diagonal=True).
+        closing arithmetic on the device. covs: K x d x d (or K x d variances with diagonal=True, the one d x d matrix with tied=True).
         Returns (steps_done, converged, log_likelihood, mixing, means, covs, log_likelihood_history)."""
         K = len(mixing)
         pi = np.array(mixing, dtype=np.float64, order="C")
         mu = np.array(means, dtype=np.float64, order="C")
         S = np.array(covs, dtype=np.float64, order="C")
-        assert mu.shape == (K, self.d) and S.shape == ((K, self.d) if diagonal else (K, self.d, self.d))
+        assert not (diagonal and tied)
+        assert mu.shape == (K, self.d) and S.shape == ((self.d, self.d) if tied else (K, self.d) if diagonal else (K, self.d, self.d))
         steps, conv, ll = C.c_uint32(), C.c_int(), C.c_double()
         hist = np.full(int(max_steps), np.nan)
-        check(lib.mlhip_em_iterate(self.ctx.handle, self._h, K, int(bool(diagonal)), dptr(pi), dptr(mu), dptr(S), C.c_uint32(max_steps),
+        check(lib.mlhip_em_iterate(self.ctx.handle, self._h, K, 2 if tied else int(bool(diagonal)), dptr(pi), dptr(mu), dptr(S), C.c_uint32(max_steps),
                                    C.c_double(atol), C.c_double(rtol), C.byref(steps), C.byref(conv), C.byref(ll), dptr(hist)))
         return steps.value, bool(conv.value), ll.value, pi, mu, S, hist[:steps.value]
 
@@ -411,17 +433,19 @@ class Data:
         check(lib.mlhip_kmeans_route(self._h, C.c_uint32(K), C.byref(info)))
         return {"kernel": ("direct", "matrix", "big_dim", "plain")[info.kernel], "pad": bool(info.pad), "resident": bool(info.resident)}
 
-    def em_score(self, mixing, means, covs, diagonal=False, densities=True, labels=True):
+    def em_score(self, mixing, means, covs, diagonal=False, densities=True, labels=True, tied=False):
         """Per-row log-density and label under the given mixture (mlhip_em_score): (log_density, labels), None for the one not
-        asked for. covs: K x d x d (or K x d variances with diagonal=True). Nothing the handle holds is changed."""
+        asked for. covs: K x d x d (or K x d variances with diagonal=True, the one d x d matrix with tied=True). Nothing the handle
+        holds is changed."""
         K = len(mixing)
         mixing = np.ascontiguousarray(mixing, dtype=np.float64)
         means = np.ascontiguousarray(means, dtype=np.float64)
         covs = np.ascontiguousarray(covs, dtype=np.float64)
-        assert means.shape == (K, self.d) and covs.shape == ((K, self.d) if diagonal else (K, self.d, self.d))
+        assert not (diagonal and tied)
+        assert means.shape == (K, self.d) and covs.shape == ((self.d, self.d) if tied else (K, self.d) if diagonal else (K, self.d, self.d))
         dens = np.empty(self.n) if densities else None
         lab = np.empty(self.n, dtype=np.uint32) if labels else None
-        check(lib.mlhip_em_score(self.ctx.handle, self._h, K, int(bool(diagonal)), dptr(mixing), dptr(means), dptr(covs),
+        check(lib.mlhip_em_score(self.ctx.handle, self._h, K, 2 if tied else int(bool(diagonal)), dptr(mixing), dptr(means), dptr(covs),
                                  dptr(dens) if densities else None, u32ptr(lab) if labels else None))
         return dens, lab
 
@@ -539,6 +563,20 @@ def calculate_XXt_beta(X, y, lam):
     check(lib.mlpp_calculate_XXt_beta(dptr(X), C.c_uint64(n), q, dptr(y), C.c_uint64(y.size), dptr(lam), lam.size,
                                       dptr(XXt), dptr(beta)))
     return XXt, beta
+
+
+def finalize_statistics_tied(statistics, total_scatter, shift, total_weight):
+    """The tied M-step's closing arithmetic on the host (mlhip_em_finalize_statistics_tied, no GPU): statistics K x (d + 1) rows
+    [S1_k | S0_k], total_scatter the packed (d+1)(d+2)/2 lower triangle of sum_i w_i [x~_i; 1][x~_i; 1]^T. Returns
+    (mixing, means K x d, covariance d x d)."""
+    st = np.ascontiguousarray(statistics, dtype=np.float64)
+    K, d = st.shape[0], st.shape[1] - 1
+    T = np.ascontiguousarray(total_scatter, dtype=np.float64)
+    shift = np.ascontiguousarray(shift, dtype=np.float64)
+    assert T.shape == ((d + 1) * (d + 2) // 2,) and shift.shape == (d,)
+    pi, mu, S = np.empty(K), np.empty((K, d)), np.empty((d, d))
+    check(lib.mlhip_em_finalize_statistics_tied(d, K, dptr(st), dptr(T), dptr(shift), C.c_double(total_weight), dptr(pi), dptr(mu), dptr(S)))
+    return pi, mu, S
 
 
 def process_covariance(cov):

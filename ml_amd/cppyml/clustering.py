@@ -190,12 +190,14 @@ class EM:
         _check(_l.mlpp_em_set_maximise_first(self._h, int(bool(maximise_first))))
 
     def set_covariance_type(self, covariance_type):
-        """Extension (not in the reference surface): "full" (default, the reference's only mode) or "diag" -- every
-        covariance restricted to its diagonal; `covariance(k)` then returns a diagonal matrix. One fused kernel per iteration for
-        d <= 32, K <= 64; other shapes run the full-covariance kernels on diagonal matrices."""
-        if covariance_type not in ("full", "diag"):
-            raise ValueError("covariance_type must be 'full' or 'diag'")
-        _check(_l.mlpp_em_set_covariance_type(self._h, int(covariance_type == "diag")))
+        """Extension (not in the reference surface): "full" (default, the reference's only mode), "diag" -- every
+        covariance restricted to its diagonal; `covariance(k)` then returns a diagonal matrix -- or "tied" -- one covariance
+        shared by all components (scikit-learn's 'tied'); `covariance(k)` then returns the same matrix for every k. One fused
+        kernel per iteration for d <= 32, K <= 64 (tied: unweighted fits); other shapes run the full-covariance kernels."""
+        codes = {"full": 0, "diag": 1, "tied": 2}
+        if covariance_type not in codes:
+            raise ValueError("covariance_type must be 'full', 'diag' or 'tied'")
+        _check(_l.mlpp_em_set_covariance_type(self._h, codes[covariance_type]))
 
     def fit(self, data, sample_weight=None):
         """Fits the components to the data (2D array with data points in rows). Returns True if EM converged.

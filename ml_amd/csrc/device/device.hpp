@@ -211,6 +211,24 @@ int em_diag_grid(int d, int K, uint32_t n, int num_cus);
 /// Returns the number of per-workgroup partial blocks written (stats and log-likelihood alike), or < 0.
 int launch_em_diag(const DiagArgs& a, int num_cus, hipStream_t stream);
 }
+/// Tied-covariance EM iteration in one kernel (em_tied.hip): winv holds the shared whitening matrix (tied_winv_doubles(D) doubles,
+/// D = padded_dim(d)), params em_tied_partial_rows(K) records of tied_param_stride(D) -- K real ones, then neutral padding
+/// (coef = -inf) -- and shift D doubles (zeros beyond d).
+struct TiedArgs {
+    const double* xt; size_t ldx; uint32_t n; int d;
+    const double* shift; const double* winv; const double* params; int K;
+    double* lse;                                             // out: per-sample log-sum-exp
+    double* partials; size_t partials_capacity;              // scratch: [grid][KP][FP], row = [S1 (d) | S0]
+    double* ll_partials; int n_ll_partials;                  // out: per-workgroup log-likelihood sums
+};
+namespace mstats {
+bool em_tied_supported(int d, int K);                        // d <= 32, K <= 64
+int em_tied_partial_rows(int K);
+int em_tied_partial_cols(int d);
+int em_tied_grid(int d, int K, uint32_t n, int num_cus);
+/// Returns the number of per-workgroup partial blocks written (stats and log-likelihood alike), or < 0.
+int launch_em_tied(const TiedArgs& a, int num_cus, hipStream_t stream);
+}
 /// M-step closing arithmetic + next E-step records on the device (em_close.hip): one workgroup per component.
 struct CloseArgs {
     const double* stats; int K; int d; int D;                // all-reduced statistics [K][F] + ll sum (F: full or diagonal)

@@ -77,5 +77,14 @@ inline int diag_param_stride(int D) { return diag_param_stride_c(D); }
 inline size_t diag_param_doubles(int D, int KP) { return (size_t)KP * diag_param_stride_c(D) + 2 * (size_t)D * KP; }
 inline int diag_stats_count(int d) { return 2 * d + 1; }
 inline int stats_index(int a, int b) { return a * (a + 1) / 2 + b; }
+/// Tied-covariance extension (device/em_tied.hip): ONE Sigma = L L^T for all components. The shared whitening matrix W = L^-1 is a
+/// block of its own, tied_winv_doubles(D) doubles: the lower triangle packed row by row (row i holds i + 1 entries; rows d .. D-1
+/// are zero). Parameter record of one component, tied_param_stride(D) doubles (even: 16-byte aligned reads):
+///   [ m = W (mean - shift) (D) | coef = log(pi) - sum_j log L_jj | padding ]
+/// Padding records k >= K: m = 0, coef = -inf. Statistics of one component, tied_stats_count(d) doubles: [ S1 (d) | S0 ].
+constexpr int tied_param_stride_c(int D) { return (D + 2) & ~1; }
+inline int tied_param_stride(int D) { return tied_param_stride_c(D); }
+inline int tied_winv_doubles(int D) { return D * (D + 1) / 2; }
+inline int tied_stats_count(int d) { return d + 1; }
 
 }  // namespace mlhip

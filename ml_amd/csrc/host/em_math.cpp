@@ -328,6 +328,53 @@ void finalize_mstep_diag(int d, int K, const double* stats, const double* shift,
     }
 }
 
+void build_tied_params(int d, int D, int K, int K_padded, const double* mixing, const double* means, const double* covariance,
+                       const double* shift, double* winv, double* records)
+{
+    const int PS = tied_param_stride(D);
+    std::vector<double> L((size_t)d * d), W((size_t)d * d);
+    const double log_det_half = whitening_matrix(d, covariance, L, W);
+    for (int i = 0; i < tied_winv_doubles(D); ++i) winv[i] = 0.0;       // padded coordinates: y_i = 0, m_ki = 0 -> contribute exactly 0
+    for (int l = 0; l < d; ++l)
+        for (int j = l; j < d; ++j) winv[(size_t)j * (j + 1) / 2 + l] = W[(size_t)l * d + j];
+    for (int k = 0; k < K_padded; ++k) {
+        double* rec = records + (size_t)k * PS;
+        for (int i = 0; i < PS; ++i) rec[i] = 0.0;
+        if (k >= K) { rec[D] = -HUGE_VAL; continue; }
+        for (int row = 0; row < d; ++row) {
+            double c = 0.0;
+            for (int col = 0; col <= row; ++col) c += W[(size_t)col * d + row] * (means[(size_t)k * d + col] - shift[col]);
+            rec[row] = c;
+        }
+        rec[D] = std::log(mixing[k]) - log_det_half;
+    }
+}
+
+void finalize_mstep_tied(int d, int K, const double* stats, const double* total_scatter, const double* shift, double total_weight,
+                         double* mixing, double* means, double* covariance)
+{
+    const int F = tied_stats_count(d);
+    std::vector<double> m((size_t)K * d);
+    for (int k = 0; k < K; ++k) {
+        const double* s = stats + (size_t)k * F;
+        const double s0 = s[d];
+        for (int a = 0; a < d; ++a) {
+            m[(size_t)k * d + a] = s[a] / s0;                                   // (an empty component: 0 / 0, as finalize_mstep)
+            means[(size_t)k * d + a] = shift[a] + m[(size_t)k * d + a];
+        }
+        mixing[k] = s0 / total_weight;                                          // ML/EM.cpp:257
+    }
+    for (int a = 0; a < d; ++a)
+        for (int b = 0; b <= a; ++b) {
+            double v = total_scatter[stats_index(a, b)];
+            for (int k = 0; k < K; ++k) v -= stats[(size_t)k * F + a] * m[(size_t)k * d + b];
+            v /= total_weight;
+            covariance[(size_t)b * d + a] = v;
+            covariance[(size_t)a * d + b] = v;
+        }
+    for (int a = 0; a < d; ++a) covariance[(size_t)a * d + a] += 1e-15;         // ridge: ML/EM.cpp:252, once
+}
+
 void set_host_ranks(int local_ranks) { g_host_threads.store(resolve_host_threads(local_ranks), std::memory_order_relaxed); }
 
 }  // namespace host

@@ -46,6 +46,19 @@ void build_diag_params(int d, int D, int K, int K_padded, const double* mixing, 
 void finalize_mstep_diag(int d, int K, const double* stats, const double* shift, double n_global, double* mixing,
                          double* means, double* variances);
 
+/// Tied-covariance extension (ONE Sigma = L L^T for all components): the whitening block winv = L^-1 (layout.hpp
+/// tied_winv_doubles: packed lower triangle, rows d .. D-1 zero) and K_padded records [m_k = L^-1 (mean_k - shift) (D) |
+/// log(pi_k) - sum_j log L_jj] (tied_param_stride) from the one d x d covariance; records beyond K are neutral (coef = -inf).
+void build_tied_params(int d, int D, int K, int K_padded, const double* mixing, const double* means, const double* covariance,
+                       const double* shift, double* winv, double* records);
+
+/// Tied closing arithmetic from the all-reduced statistics [S1'(d) | S0] per component and the total scatter
+/// T = sum_i w_i xt_i xt_i^T (packed like one component's full statistics: stats_count(d) doubles, xt = [x - shift ; 1]):
+///   mean_k = shift + S1'_k/S0_k ; pi_k = S0_k / W ; Sigma = (T - sum_k S1'_k (S1'_k/S0_k)^T) / W + 1e-15 I
+/// (k ascending per entry; the ridge of ML/EM.cpp:252-256 once) == sum_k pi_k Sigma_k over finalize_mstep's Sigma_k.
+void finalize_mstep_tied(int d, int K, const double* stats, const double* total_scatter, const double* shift, double total_weight,
+                         double* mixing, double* means, double* covariance);
+
 /// Tells the host-side math how many ranks share this node, so that the OpenMP teams of the per-component
 /// factorizations together stay within the host's cores (MLHIP_HOST_THREADS overrides the per-rank thread count).
 void set_host_ranks(int local_ranks);

@@ -218,7 +218,9 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
     const std::size_t dd = static_cast<std::size_t>(number_dimensions) * number_dimensions;
     const bool diagonal = covariance_type_ == CovarianceType::Diagonal;   // extension, see ML/EM.hpp
     std::vector<double> cov_flat(dd * K);
+    const bool tied = covariance_type_ == CovarianceType::Tied;           // extension, see ML/EM.hpp
     std::vector<double> var_flat;                                          // diagonal mode: K x d variances
+    std::vector<double> tied_cov;                                          // tied mode: the one d x d covariance
     auto unpack_covariances = [&] {
         for (unsigned int k = 0; k < K; ++k) {
             covariances_[k].resize(number_dimensions, number_dimensions);
@@ -267,13 +269,22 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
                 var_flat[static_cast<std::size_t>(k) * number_dimensions + j] = cov_flat[dd * k + static_cast<std::size_t>(j) * number_dimensions + j];
     }
 
+    if (tied) {
+        // the pooled sum_k pi_k Sigma_k of the starting covariances (ascending k) is the tied start: the tied M-step of the starting
+        // responsibilities, or -- K copies of the sample covariance with pi_k = 1 / K -- the sample covariance itself
+        tied_cov.assign(dd, 0.0);
+        for (std::size_t e = 0; e < dd; ++e)
+            for (unsigned int k = 0; k < K; ++k) tied_cov[e] += mixing_probabilities_[k] * cov_flat[dd * k + e];
+    }
+
     if (!verbose_) {
         // The whole loop below in one library call (same steps, same convergence test: ML/EM.cpp:143-170), with the M-step's
         // closing arithmetic and the K covariance factorizations on the device between two tests.
         uint32_t steps = 0;
         int conv = 0;
-        check(mlhip_em_iterate(ctx, dev.h, K, diagonal ? MLHIP_COVARIANCE_DIAGONAL : MLHIP_COVARIANCE_FULL,
-                               mixing_probabilities_.data(), means_.data(), diagonal ? var_flat.data() : cov_flat.data(),
+        check(mlhip_em_iterate(ctx, dev.h, K, tied ? MLHIP_COVARIANCE_TIED : diagonal ? MLHIP_COVARIANCE_DIAGONAL : MLHIP_COVARIANCE_FULL,
+                               mixing_probabilities_.data(), means_.data(),
+                               tied ? tied_cov.data() : diagonal ? var_flat.data() : cov_flat.data(),
                                maximum_steps_, absolute_tolerance_, relative_tolerance_, &steps, &conv, &log_likelihood_, nullptr));
         steps_done_ = steps;
         if (conv) {
@@ -285,7 +296,10 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
     double old_log_likelihood = -std::numeric_limits<double>::infinity();
     for (unsigned int step = 0; verbose_ && step < maximum_steps_; ++step) {
         // One E-step + M-step on the device; parameters are updated in place (ML/EM.cpp:145-147).
-        if (diagonal)
+        if (tied)
+            check(mlhip_em_step_tied(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), tied_cov.data(), &log_likelihood_,
+                                     mixing_probabilities_.data(), means_.data(), tied_cov.data()));
+        else if (diagonal)
             check(mlhip_em_step_diag(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), var_flat.data(), &log_likelihood_,
                                      mixing_probabilities_.data(), means_.data(), var_flat.data()));
         else
@@ -332,6 +346,8 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
             for (unsigned int j = 0; j < number_dimensions; ++j)
                 cov_flat[dd * k + static_cast<std::size_t>(j) * number_dimensions + j] = var_flat[static_cast<std::size_t>(k) * number_dimensions + j];
     }
+    if (tied)
+        for (unsigned int k = 0; k < K; ++k) std::copy_n(tied_cov.data(), dd, cov_flat.data() + dd * k);   // every covariances_[k] holds Sigma
     unpack_covariances();
     process_covariances(number_dimensions);
     // The responsibilities of the last E-step stay in HBM; responsibilities() allocates and fetches them on demand.

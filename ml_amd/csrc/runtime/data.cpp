@@ -160,6 +160,16 @@ void download_columns(mlhip_ctx* ctx, char* dst, size_t dst_pitch, const char* s
     for (int k = 0; k < 2; ++k) (void)hipEventDestroy(done[k]);
 }
 
+void run_total_scatter(mlhip_data* data)
+{
+    // K = 1, r = 1: S_0 = sum_i xt_i xt_i^T about the global mean. The E-step workspace for another K is
+    // left untouched only if K == 1; otherwise it is rebuilt on the next E-step.
+    ensure_em_workspace(data, 1);
+    data->estep.invalidate();
+    launch_fill_responsibilities(nullptr, data->n, 1, data->lw.as<double>(), data->ldr, data->ctx->stream);
+    run_mstats(data, em_route(data, 1, false), 1, kFromResp, data->lw.as<double>(), data->ldr, false);
+}
+
 }  // namespace mlhip_rt
 
 extern "C" {
@@ -237,6 +247,7 @@ int mlhip_data_set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weigh
         data->weighted = false;
         data->weight_sum = 0;
         data->wresp.release();                                 // (sized again by the next weighted statistics pass)
+        data->total_scatter.clear();                           // (the tied mode's sum_i w_i xt_i xt_i^T: formed again on demand)
         if (!weights) {
             data->weights.release();
             return;
@@ -287,12 +298,7 @@ int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, doub
             });
             return;
         }
-        // K = 1, r = 1: S_0 = sum_i xt_i xt_i^T about the global mean. The E-step workspace for another K is
-        // left untouched only if K == 1; otherwise it is rebuilt on the next E-step.
-        ensure_em_workspace(data, 1);
-        data->estep.invalidate();
-        launch_fill_responsibilities(nullptr, data->n, 1, data->lw.as<double>(), data->ldr, ctx->stream);
-        run_mstats(data, em_route(data, 1, false), 1, kFromResp, data->lw.as<double>(), data->ldr, false);
+        run_total_scatter(data);
         const double* s = data->stats_host.as<double>();
         const int d = data->d;
         const double n = data->total_weight();                 // (W of a weighted block: run_mstats took w_i as the responsibilities)

@@ -1,5 +1,5 @@
-// EM family of the C ABI: E-step / statistics / closing orchestration of the gfx950 kernels per step (closing on the host), full
-// and diagonal covariances; the whole loop of EM::fit (mlhip_em_iterate: closing on the device) lives in em_loop.cpp.
+// EM family of the C ABI: E-step / statistics / closing orchestration of the gfx950 kernels per step (closing on the host), full,
+// diagonal and tied covariances; the whole loop of EM::fit (mlhip_em_iterate: closing on the device) lives in em_loop.cpp.
 #include "internal.hpp"
 
 namespace mlhip_rt {
@@ -142,6 +142,12 @@ void ensure_lw(mlhip_data* dt, const EmRoute& r, int K)
         std::vector<double> covs((size_t)K * d * d, 0.0);
         for (int k = 0; k < K; ++k)
             for (int j = 0; j < d; ++j) covs[(size_t)k * d * d + (size_t)j * d + j] = dt->estep.diag_vars[(size_t)k * d + j];
+        prepare_estep(dt, r, K, dt->estep.diag_mixing.data(), dt->estep.diag_means.data(), covs.data());
+    } else if (dt->estep.tied()) {
+        // params_dev holds tied records: the same parameters as K full components that all carry the one covariance
+        const size_t dd = (size_t)dt->d * dt->d;
+        std::vector<double> covs((size_t)K * dd);
+        for (int k = 0; k < K; ++k) std::copy(dt->estep.tied_cov.begin(), dt->estep.tied_cov.end(), covs.begin() + (size_t)k * dd);
         prepare_estep(dt, r, K, dt->estep.diag_mixing.data(), dt->estep.diag_means.data(), covs.data());
     }
     launch_estep(dt, r, K);
@@ -529,9 +535,89 @@ void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixin
 }
 
 
+/// One tied-covariance EM iteration's device work (em_tied.hip) on the records [K padded records | whitening block] in params_dev;
+/// leaves the all-reduced [K * (d+1) statistics, ll_sum] in stats_host.
+static void run_tied_kernel(mlhip_data* dt, int K)
+{
+    mlhip_ctx* ctx = dt->ctx;
+    TiedArgs a{};
+    a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.d = dt->d;
+    a.shift = dt->shift_dev.as<double>(); a.params = dt->params_dev.as<double>(); a.K = K;
+    a.winv = a.params + (size_t)mstats::em_tied_partial_rows(K) * tied_param_stride(dt->D);
+    a.lse = dt->lse.as<double>();
+    a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
+    a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
+    int grid = 0;
+    ctx->timed("em_tied", [&] { grid = mstats::launch_em_tied(a, ctx->num_cus, ctx->stream); });
+    if (grid <= 0) throw std::runtime_error("tied EM kernel launch failed");
+    launch_em_reduce_blocks(a.partials, grid, mstats::em_tied_partial_rows(K), mstats::em_tied_partial_cols(dt->d), K,
+                            tied_stats_count(dt->d), a.ll_partials, grid, dt->stats_dev.as<double>(), ctx->stream);
+    HIP_CHECK(hipGetLastError());
+    dt->estep.tied_records_only(grid);
+    collect_stats(dt, K, (size_t)K * tied_stats_count(dt->d) + 1);
+}
+
+
+/// Records of a tied-covariance parameter set -> params_dev: K records padded to whole 16-component row blocks with neutral ones,
+/// then the shared whitening block (layout.hpp).
+static void upload_tied_records(mlhip_data* data, int K, const double* mixing, const double* means, const double* cov)
+{
+    mlhip_ctx* ctx = data->ctx;
+    const int KP = mstats::em_tied_partial_rows(K);
+    const size_t rec_doubles = (size_t)KP * tied_param_stride(data->D);
+    const size_t bytes = sizeof(double) * (rec_doubles + tied_winv_doubles(data->D));
+    data->params_dev.reserve(bytes);
+    data->params_host.reserve(bytes);
+    double* h = data->params_host.as<double>();
+    host::build_tied_params(data->d, data->D, K, KP, mixing, means, cov, data->shift.data(), h + rec_doubles, h);
+    HIP_CHECK(hipMemcpyAsync(data->params_dev.p, data->params_host.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    ctx->sync();                                     // params_host may be rewritten right away by the caller's next upload
+}
+
+
+void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mixing, const double* means, const double* cov,
+                  double* log_likelihood, double* mixing_out, double* means_out, double* cov_out)
+{
+    const int d = data->d;
+    const size_t dd = (size_t)d * d;
+    if (r.kernel != kTiedKernel) {
+        // COMPOSED: one full-covariance step on K copies of the covariance, on whatever route this shape takes (weights, the
+        // refinement pass, big dimensions and the plain tier included), then  Sigma = sum_k pi_k Sigma_k  in ascending k -- the tied
+        // M-step, since sum_k S0_k Sigma_k = T - sum_k S1_k S1_k^T / S0_k. Every Sigma_k carries the ridge 1e-15 I (ML/EM.cpp:252),
+        // and sum_k pi_k = 1 up to rounding: the K ridges pool to the one ridge of the tied mode. Nothing is subtracted or re-added.
+        // Slower than it could be, never refused.
+        std::vector<double> covs((size_t)K * dd), covs_out((size_t)K * dd);
+        for (int k = 0; k < K; ++k) std::copy(cov, cov + dd, covs.begin() + (size_t)k * dd);
+        em_step_full(data, r.em, K, mixing, means, covs.data(), log_likelihood, mixing_out, means_out, covs_out.data());
+        for (size_t e = 0; e < dd; ++e) {
+            double v = 0.0;
+            for (int k = 0; k < K; ++k) v += mixing_out[k] * covs_out[(size_t)k * dd + e];
+            cov_out[e] = v;
+        }
+        return;
+    }
+    // T = sum_i xt_i xt_i^T does not depend on the responsibilities: once per handle, all-reduced like the statistics
+    if (data->total_scatter.empty()) {
+        run_total_scatter(data);
+        const double* t = data->stats_host.as<double>();
+        data->total_scatter.assign(t, t + stats_count(d));
+    }
+    ensure_em_workspace(data, K);
+    // keep the input parameters: labels / responsibilities are produced from them on demand (ensure_lw)
+    data->estep.tied_parameters(K, d, mixing, means, cov);
+    upload_tied_records(data, K, mixing, means, cov);
+    run_tied_kernel(data, K);
+    const int F = tied_stats_count(d);
+    const double* st = data->stats_host.as<double>();
+    *log_likelihood = st[(size_t)K * F] / (double)data->n_global - (double)d * log_two_pi() / 2;   // ML/EM.cpp:197-198, 211
+    host::finalize_mstep_tied(d, K, st, data->total_scatter.data(), data->shift.data(), (double)data->n_global, mixing_out, means_out,
+                              cov_out);
+}
+
+
 namespace {
 
-/// mlhip_em_step / mlhip_em_step_diag (`step`) through a device group: the outputs may alias the inputs, so the shards read copies.
+/// mlhip_em_step / mlhip_em_step_diag / mlhip_em_step_tied (`step`) through a device group: the outputs may alias the inputs, so the shards read copies.
 void group_em_step(decltype(&mlhip_em_step) step, mlhip_ctx* ctx, mlhip_data* data, uint32_t K, size_t cov_doubles, const double* mixing,
                    const double* means, const double* covs, double* log_likelihood, double* mixing_out, double* means_out, double* covs_out)
 {
@@ -627,6 +713,22 @@ int mlhip_em_step_diag(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const doubl
     });
 }
 
+int mlhip_em_step_tied(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* mixing, const double* means,
+                       const double* covariance, double* log_likelihood, double* mixing_out, double* means_out,
+                       double* covariance_out)
+{
+    return guarded([&] {
+        check_call(ctx, data, K);
+        require(mixing && means && covariance && log_likelihood && mixing_out && means_out && covariance_out, "null argument");
+        if (ctx->group) {
+            group_em_step(mlhip_em_step_tied, ctx, data, K, (size_t)data->d * data->d, mixing, means, covariance, log_likelihood, mixing_out,
+                          means_out, covariance_out);
+            return;
+        }
+        em_step_tied(data, tied_route(data, (int)K), (int)K, mixing, means, covariance, log_likelihood, mixing_out, means_out, covariance_out);
+    });
+}
+
 int mlhip_em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type, double* mixing, double* means,
                      double* covariances, uint32_t max_steps, double absolute_tolerance, double relative_tolerance,
                      uint32_t* steps_done, int* converged, double* log_likelihood, double* log_likelihood_history)
@@ -634,11 +736,14 @@ int mlhip_em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covarianc
     return guarded([&] {
         check_call(ctx, data, K);
         require(mixing && means && covariances && steps_done && converged && log_likelihood, "null argument");
-        require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL, "bad covariance_type");
+        require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL ||
+                    covariance_type == MLHIP_COVARIANCE_TIED,
+                "bad covariance_type");
         require(max_steps >= 1, "at least one step required");
         if (absolute_tolerance < 0 || relative_tolerance < 0) throw DomainError("negative tolerance");
         const bool diag = covariance_type == MLHIP_COVARIANCE_DIAGONAL;
-        const size_t kd = (size_t)K * data->d, cov_doubles = kd * (diag ? 1 : data->d);
+        const bool tied = covariance_type == MLHIP_COVARIANCE_TIED;
+        const size_t kd = (size_t)K * data->d, cov_doubles = tied ? (size_t)data->d * data->d : kd * (diag ? 1 : data->d);
         if (ctx->group) {
             // the parameters are in/out: shard 0 updates the caller's, the others copies of their own (the ranks' end-of-fit
             // checksum exchange inside the shards' calls holds them to bit-identical results)
@@ -651,8 +756,12 @@ int mlhip_em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covarianc
             });
             return;
         }
-        em_iterate(data, em_route(data, (int)K, diag), (int)K, diag, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance, steps_done,
-                   converged, log_likelihood, log_likelihood_history);
+        if (tied)
+            em_iterate_tied(data, tied_route(data, (int)K), (int)K, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance,
+                            steps_done, converged, log_likelihood, log_likelihood_history);
+        else
+            em_iterate(data, em_route(data, (int)K, diag), (int)K, diag, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance, steps_done,
+                       converged, log_likelihood, log_likelihood_history);
         ctx->check_ranks_agree("the EM parameters", {{mixing, K}, {means, kd}, {covariances, cov_doubles}, {log_likelihood, 1}});
     });
 }
@@ -777,6 +886,25 @@ int mlhip_em_finalize_statistics(uint32_t d, uint32_t K, const double* statistic
     return guarded([&] {
         require(d >= 1 && K >= 1 && statistics && shift && mixing_out && means_out && covariances_out, "bad argument");
         host::finalize_mstep((int)d, (int)K, statistics, shift, n_global, mixing_out, means_out, covariances_out);
+    });
+}
+
+int mlhip_em_finalize_statistics_tied(uint32_t d, uint32_t K, const double* statistics, const double* total_scatter, const double* shift,
+                                      double total_weight, double* mixing_out, double* means_out, double* covariance_out)
+{
+    return guarded([&] {
+        require(d >= 1 && K >= 1 && statistics && total_scatter && shift && mixing_out && means_out && covariance_out, "bad argument");
+        host::finalize_mstep_tied((int)d, (int)K, statistics, total_scatter, shift, total_weight, mixing_out, means_out, covariance_out);
+    });
+}
+
+int mlhip_em_tied_route(const mlhip_data* data, uint32_t K, int* kernel)
+{
+    return guarded([&] {
+        require(data && kernel && K >= 1, "bad argument");
+        if (!data->parts.empty()) data = data->parts[0];        // (a group's block: every shard takes the same route)
+        static_assert(kTiedComposed == MLHIP_TIED_COMPOSED && kTiedKernel == MLHIP_TIED_KERNEL, "mlhip.h names the routes by TiedKernel");
+        *kernel = tied_route(data, (int)K).kernel;
     });
 }
 

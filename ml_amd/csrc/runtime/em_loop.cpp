@@ -377,18 +377,29 @@ struct EmLoop {
 };
 
 /// No device closing on the route (d > 1024, MLHIP_DEVICE_CLOSE=0): the loop over the per-step functions.
+/// `tied`: a tied-covariance loop (covs: d*d doubles) on that route -- tied iterations are never closed on the device.
 void host_closing_loop(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mixing, double* means, double* covs,
-                       uint32_t max_steps, ConvergenceTest& test)
+                       uint32_t max_steps, ConvergenceTest& test, const TiedRoute* tied = nullptr)
 {
     for (uint32_t step = 0; step < max_steps; ++step) {
         double ll = 0;
-        if (diag) em_step_diag(data, r, K, mixing, means, covs, &ll, mixing, means, covs);
+        if (tied) em_step_tied(data, *tied, K, mixing, means, covs, &ll, mixing, means, covs);
+        else if (diag) em_step_diag(data, r, K, mixing, means, covs, &ll, mixing, means, covs);
         else em_step_full(data, r, K, mixing, means, covs, &ll, mixing, means, covs);
         if (test(step, ll)) break;
     }
 }
 
 }  // namespace
+
+void em_iterate_tied(mlhip_data* data, const TiedRoute& r, int K, double* mixing, double* means, double* cov, uint32_t max_steps, double atol,
+                     double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history)
+{
+    *steps_done = 0;
+    *converged = 0;
+    ConvergenceTest test{atol, rtol, steps_done, converged, log_likelihood, history};
+    host_closing_loop(data, r.em, K, false, mixing, means, cov, max_steps, test, &r);
+}
 
 void em_iterate(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps,
                 double atol, double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history)

@@ -41,7 +41,7 @@ void score_composed(mlhip_data* dt, const ScoreRoute& r, int K, const DevBuf& re
     ctx->sync();                                         // (the scratch goes back to the pool behind the last kernel)
 }
 
-void em_score(mlhip_data* dt, int K, bool diag, const double* mixing, const double* means, const double* covs, double* log_density,
+void em_score(mlhip_data* dt, int K, int covariance_type, const double* mixing, const double* means, const double* covs, double* log_density,
               uint32_t* labels)
 {
     mlhip_ctx* ctx = dt->ctx;
@@ -49,7 +49,15 @@ void em_score(mlhip_data* dt, int K, bool diag, const double* mixing, const doub
     const ScoreRoute r = score_route(dt, K);
     const int d = dt->d;
     std::vector<double> full;
-    if (diag) {
+    if (covariance_type == MLHIP_COVARIANCE_TIED) {
+        // the same kernels on K components that all carry the one covariance; no kernel of its own. The record builders work per
+        // component, so the one matrix is factored K times: K - 1 wasted factorizations, microseconds at d <= 32 but K d^3 / 3 flop
+        // each at large d (on the device above d = 64) -- records derived from one factorization are not built
+        const size_t dd = (size_t)d * d;
+        full.resize((size_t)K * dd);
+        for (int k = 0; k < K; ++k) std::copy(covs, covs + dd, full.begin() + (size_t)k * dd);
+        covs = full.data();
+    } else if (covariance_type == MLHIP_COVARIANCE_DIAGONAL) {
         // the same kernels on diagonal matrices, as ensure_lw (em.cpp) does after a diagonal step
         full.assign((size_t)K * d * d, 0.0);
         for (int k = 0; k < K; ++k)
@@ -96,7 +104,9 @@ int mlhip_em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_
     return guarded([&] {
         check_call(ctx, data, K);
         require(mixing && means && covariances, "null argument");
-        require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL, "bad covariance_type");
+        require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL ||
+                    covariance_type == MLHIP_COVARIANCE_TIED,
+                "bad covariance_type");
         if (ctx->group) {
             // (every shard scores its own rows: no collective, nothing to put together but the rows' places in the caller's arrays)
             fan_out(ctx, data, [&](Shard& sh) {
@@ -104,7 +114,7 @@ int mlhip_em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_
             });
             return;
         }
-        em_score(data, (int)K, covariance_type == MLHIP_COVARIANCE_DIAGONAL, mixing, means, covariances, log_density, labels);
+        em_score(data, (int)K, covariance_type, mixing, means, covariances, log_density, labels);
     });
 }
 

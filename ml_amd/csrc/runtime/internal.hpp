@@ -400,9 +400,10 @@ struct mlhip_ctx {
 ///   kRecords     -- lse and the full-covariance records in params_dev (after a fused step, the resident loop, a lagged loop that
 ///                   ran one iteration ahead): ensure_lw reruns the E-step kernel on the same records;
 ///   kDiagRecords -- lse, diagonal records in params_dev and the parameters' host copy: ensure_lw expands them to full covariances.
+///   kTiedRecords -- the same after a tied-covariance kernel step: ensure_lw replicates the one covariance K times.
 /// Only the members below assign the fields.
 struct EstepState {
-    enum What { kNone, kBlock, kRecords, kDiagRecords };
+    enum What { kNone, kBlock, kRecords, kDiagRecords, kTiedRecords };
     What what = kNone;
     int rec_layout = 0;           // record layout currently in params_dev: 0 = valu, 2 = mfma4 (CloseArgs::layout codes)
     bool rec_fold = false;        // mfma4 records in FOLD form (vector slot = -W (mu - shift)): layout.hpp kEstepFoldLimit
@@ -413,6 +414,8 @@ struct EstepState {
     size_t stats_ld = 0;
     // diagonal-covariance extension: parameters of the last diagonal E-step (the N x K block is rebuilt from them on demand)
     std::vector<double> diag_mixing, diag_means, diag_vars;
+    // tied-covariance extension: the one covariance of the last tied kernel step (its mixing / means sit in diag_mixing / diag_means)
+    std::vector<double> tied_cov;
 
     void invalidate() { what = kNone; }
     void block_written(int grid) { what = kBlock; n_ll = grid; }
@@ -420,6 +423,7 @@ struct EstepState {
     void ll_weighted(int grid) { n_ll = grid; }
     void records_only(int grid) { what = kRecords; n_ll = grid; }
     void diag_records_only(int grid) { what = kDiagRecords; n_ll = grid; }
+    void tied_records_only(int grid) { what = kTiedRecords; n_ll = grid; }
     /// A later (speculative) pass overwrote lw / lse; the records in params_dev still stand.
     void block_overwritten() { if (what == kBlock) what = kRecords; }
     /// The parameters behind the diagonal records in params_dev (mlhip_em_iterate: set once, when the loop is over).
@@ -429,12 +433,20 @@ struct EstepState {
         diag_means.assign(means, means + (size_t)K * d);
         diag_vars.assign(vars, vars + (size_t)K * d);
     }
+    /// The parameters behind the tied records in params_dev.
+    void tied_parameters(int K, int d, const double* mixing, const double* means, const double* cov)
+    {
+        diag_mixing.assign(mixing, mixing + K);
+        diag_means.assign(means, means + (size_t)K * d);
+        tied_cov.assign(cov, cov + (size_t)d * d);
+    }
     void records_are(int layout, bool fold) { rec_layout = layout; rec_fold = fold; }
     void stats_from(int mode, const double* resp, size_t ld) { stats_mode = mode; stats_resp = resp; stats_ld = ld; }
 
     bool on_device() const { return what != kNone; }
-    bool needs_rebuild() const { return what == kRecords || what == kDiagRecords; }
+    bool needs_rebuild() const { return what == kRecords || what == kDiagRecords || what == kTiedRecords; }
     bool diagonal() const { return what == kDiagRecords; }
+    bool tied() const { return what == kTiedRecords; }
 };
 
 struct mlhip_data {
@@ -459,6 +471,9 @@ struct mlhip_data {
     DevBuf weights{&pool}, wresp{&pool};
     bool weighted = false;
     double weight_sum = 0;        // W over all ranks
+    // Tied-covariance extension: T = sum_i w_i xt_i xt_i^T over ALL ranks (packed, stats_count(d) doubles; the K = 1, r = 1 statistics
+    // pass), formed by the first tied kernel step on the handle; empty: not formed yet. mlhip_data_set_weights drops it.
+    std::vector<double> total_scatter;
     /// Rows behind the host arrays of a call on this handle: this block's -- a group's handle holds the whole sample.
     uint64_t rows() const { return parts.empty() ? (uint64_t)n : n_global; }
     /// What the log-likelihood and the mixing proportions are divided by: W, or the row count of an unweighted block.
@@ -564,6 +579,16 @@ struct EmRoute {
 };
 /// `diag`: the call runs the diagonal-covariance kernel where it exists (em_diag.hip), else the full-covariance kernels.
 EmRoute em_route(const mlhip_data* data, int K, bool diag);
+
+/// A tied-covariance step (mlhip_em_step_tied): the one-kernel iteration (em_tied.hip: unweighted blocks, d <= 32, K <= 64, unless
+/// MLHIP_TIED=composed or the composed step was measured faster: route.cpp) or COMPOSED -- one full-covariance step on `em`, the route of K full components on this block, with the
+/// covariance replicated and the result pooled. (mlhip.h names the routes by these values.)
+enum TiedKernel : int { kTiedComposed = 0, kTiedKernel = 1 };
+struct TiedRoute {
+    int kernel = kTiedComposed;
+    EmRoute em;                        // full-covariance route: the composed step, and the E-step kernel that rebuilds the N x K block
+};
+TiedRoute tied_route(const mlhip_data* data, int K);
 
 /// mlhip_em_score: the scalar-fed score kernel (em_score.hip) and the matrix-core E-step's SCORE form (em_estep_mfma4.hip) where the
 /// E-step's route is scalar-fed / matrix-core; composed -- the E-step kernel on row chunks into a bounded scratch block, then
@@ -725,6 +750,14 @@ void refine_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixing
 void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixing, const double* means, const double* variances,
                   double* log_likelihood, double* mixing_out, double* means_out, double* variances_out);
 
+/// The K = 1, r = 1 statistics pass (what mlhip_sample_covariance runs): leaves the all-reduced packed sum_i w_i xt_i xt_i^T in
+/// stats_host. Resizes the EM workspace to K = 1 (E-step results on the handle are dropped).
+void run_total_scatter(mlhip_data* data);
+
+/// One tied-covariance EM iteration (the body of mlhip_em_step_tied): cov / cov_out hold d*d doubles.
+void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mixing, const double* means, const double* cov,
+                  double* log_likelihood, double* mixing_out, double* means_out, double* cov_out);
+
 /// The loop of EM::fit (ML/EM.cpp:143-170) with everything between two convergence tests on the device (em_loop.cpp): E-step,
 /// statistics, all-reduce, closing arithmetic + next records (em_close.hip); per iteration the host reads back 1 + 2K doubles (log-
 /// likelihood sum, refinement flags, FOLD criterion) and decides. A flagged component (far, tight cluster) sends that one
@@ -732,6 +765,9 @@ void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixin
 /// (r.device_close) the whole loop runs through the per-step functions.
 void em_iterate(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps, double atol,
                 double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history);
+/// The same loop for a tied covariance (covs: d*d doubles): one em_step_tied per trip, closing on the host.
+void em_iterate_tied(mlhip_data* data, const TiedRoute& r, int K, double* mixing, double* means, double* cov, uint32_t max_steps, double atol,
+                     double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history);
 
 /// The all-reduce hook of a context that owns an RCCL communicator: one ncclAllReduce(double, sum), in place, on the
 /// context's stream -- ordered with the kernels before it and the copies after it, no host synchronisation.

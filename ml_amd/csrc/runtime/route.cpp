@@ -27,6 +27,7 @@ struct Switches {
     int kmeans;                 // MLHIP_KMEANS=valu / mfma: kKmDirect / kKmMatrix forced, -1 automatic
     bool score_composed;        // MLHIP_SCORE=composed
     long score_rows;            // MLHIP_SCORE_ROWS=n: rows per chunk of the composed scoring route (0: by the scratch bound)
+    int tied;                   // MLHIP_TIED=composed / kernel: kTiedComposed / kTiedKernel forced (the kernel: where it exists), -1 automatic
 };
 
 Switches read_switches()
@@ -54,6 +55,8 @@ Switches read_switches()
     s.score_composed = score && std::strcmp(score, "composed") == 0;
     const char* rows = std::getenv("MLHIP_SCORE_ROWS");
     s.score_rows = rows && *rows ? std::atol(rows) : 0;
+    const char* tied = std::getenv("MLHIP_TIED");
+    s.tied = !tied ? -1 : std::strcmp(tied, "composed") == 0 ? kTiedComposed : std::strcmp(tied, "kernel") == 0 ? kTiedKernel : -1;
     return s;
 }
 
@@ -112,6 +115,22 @@ ScoreRoute score_route(const mlhip_data* data, int K)
     if (rows < (uint64_t)kSampleTile) rows = kSampleTile;
     if (rows > data->n_pad) rows = data->n_pad;
     r.chunk_rows = (uint32_t)rows;
+    return r;
+}
+
+TiedRoute tied_route(const mlhip_data* data, int K)
+{
+    const Switches sw = read_switches();
+    TiedRoute r;
+    r.em = em_route(data, K, false);
+    // the kernel has no weighted form (like the diagonal one); every other shape, and MLHIP_TIED=composed, takes the composed route
+    if (sw.tied == kTiedComposed || data->weighted || !mstats::em_tied_supported(data->d, K)) return r;
+    // Measured (profiles/tied_timing.txt): where the full-covariance step is the fused kernel in its vector-unit form -- few components
+    // in few dimensions, no padding to 16-component row blocks -- the composed step is the faster one (N = 10M, d = 4, K = 3: 0.135
+    // against 0.261 ms; the ONE shape of that form that was timed, the rule extends it to the others): those shapes stay composed
+    // unless MLHIP_TIED=kernel asks for the kernel.
+    const bool composed_faster = r.em.fused && r.em.fused_form == kFusedValu;
+    if (sw.tied == kTiedKernel || !composed_faster) r.kernel = kTiedKernel;
     return r;
 }
 
