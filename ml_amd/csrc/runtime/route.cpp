@@ -123,6 +123,10 @@ TiedRoute tied_route(const mlhip_data* data, int K)
     const Switches sw = read_switches();
     TiedRoute r;
     r.em = em_route(data, K, false);
+    // The composed route is the tied mode's accurate one (it is where the kernel's weighted, large and ill-conditioned cases go, and
+    // what the kernel is compared with): its matrix-core E-step takes the exact form, never FOLD, whose 1e-13 in a
+    // log-responsibility would be the route's largest error (tests/test_gpu_tied_hp.py, reach 0.9 x 64: 1.1e-14 against 1.9e-15).
+    r.em.fold_allowed = false;
     // the kernel has no weighted form (like the diagonal one); every other shape, and MLHIP_TIED=composed, takes the composed route
     if (sw.tied == kTiedComposed || data->weighted || !mstats::em_tied_supported(data->d, K)) return r;
     // Measured (profiles/tied_timing.txt): where the full-covariance step is the fused kernel in its vector-unit form -- few components

@@ -103,3 +103,171 @@ def edge_problem(d, reach, diagonal=False, seed=4):
     mu0 = np.vstack([np.full(d, 0.75), p, p + L[1] @ w])
     second = np.stack([var[0], var[1], var[1]]) if diagonal else np.stack([S[0], S[1], S[1]])
     return X, np.array([n0 / n, n1 / n, n1 / n]), mu0, second
+
+
+# ---- tied covariance: tests/test_gpu_tied_hp.py on the GPU, the data conditions in tests/test_hp_reference.py ----
+
+TIED_N = 709                      # 12 tiles of 64 rows with a ragged last one, in 3 workgroups
+# every padded dimension of em_tied_kernel (1, 2, 3, 4, 6, 8, 12, 16, 20, 24, 28, 32) at the largest d below it that still pads to
+# it, d = D itself at D = 20, 24, 28, each with 1, 2 and 3 row blocks of components; then the other row-block boundaries
+TIED_CODE_OBJECT_CASES = ([(d, K) for d in (1, 2, 3, 4, 5, 7, 11, 15, 17, 21, 25, 29, 20, 24, 28) for K in (5, 17, 33)] +
+                          [(d, K) for d in (7, 21) for K in (16, 32, 48, 49, 64)])
+# (offset, separation) at d = 8, K = 5, N = 3001
+TIED_SWEEP_CASES = [(0.0, 2.5), (0.0, 30.0), (0.0, 300.0), (50.0, 30.0)]
+TIED_REACHES = [0.9 * 64, 1.1 * 64, 10 * 64]
+# The whitening model's constant (section 4): the largest ratio of tied_kernel_log_resp()'s log-responsibility error to
+# 2^-53 * whiten over TIED_SWEEP_CASES and TIED_REACHES is 1.21 (tests/test_hp_reference.py measures it), rounded up to the next
+# integer. It comes from this CPU restatement, never from what the kernel gives.
+C_WHITEN = 2
+
+
+def tied_problem(d, K, n, offset=0.0, sep=2.5, seed=None):
+    """A tied mixture sample and a perturbed start (X, pi0, mu0, Sigma0) -- tests/test_gpu_tied.py's tied_sample with the component
+    means `sep` apart per axis and everything moved `offset` from the origin."""
+    rng = np.random.default_rng(100 * d + K + n if seed is None else seed)
+    means = sep * rng.standard_normal((K, d))
+    A = rng.standard_normal((d, d))
+    Sigma = A @ A.T / d + 0.5 * np.eye(d)
+    X = means[rng.integers(0, K, n)] + rng.standard_normal((n, d)) @ np.linalg.cholesky(Sigma).T
+    B = 0.1 * rng.standard_normal((d, d))
+    pi0 = rng.dirichlet(4 * np.ones(K))
+    mu0 = means + 0.2 * rng.standard_normal((K, d))
+    return np.ascontiguousarray(X + offset), pi0, mu0 + offset, Sigma + B @ B.T + 0.1 * np.eye(d)
+
+
+def tied_reach_problem(reach):
+    """edge_problem(16, reach) -- components 1 and 2 share one covariance and overlap, `reach` of their whitened units from the
+    shift -- with its three covariances pooled as the one starting covariance."""
+    X, pi0, mu0, S = edge_problem(16, reach)
+    return X, pi0, mu0, np.einsum("k,kab->ab", pi0, S)
+
+
+def tied_edge_problem(kind):
+    """d = 7, K = 5, N = 709 with one input no plain sample holds. `zero_weight`: pi_2 = 0. `empty`: component 4's mean 1e4 whitened
+    units from the data mean, so that every one of its responsibilities underflows to exactly 0 (in long double too). `tail`: twenty
+    rows moved out along random directions until the NEAREST mean is 40 whitened units away (log-densities near -800)."""
+    d, K, n = 7, 5, TIED_N
+    X, pi0, mu0, S0 = tied_problem(d, K, n, 2.0, 2.5)
+    L = np.linalg.cholesky(S0)
+    if kind == "zero_weight":
+        pi0 = pi0.copy()
+        pi0[2] = 0.0
+        pi0 /= pi0.sum()
+    elif kind == "empty":
+        mu0 = mu0.copy()
+        mu0[4] = X.mean(axis=0) + 1e4 * L[:, 0]
+    elif kind == "tail":
+        rng = np.random.default_rng(5)
+        X = X.copy()
+        centre = X.mean(axis=0)
+        M = np.linalg.solve(L, (mu0 - centre).T).T
+        for row in rng.choice(n, 20, replace=False):
+            u = rng.standard_normal(d)
+            u /= np.linalg.norm(u)
+            lo, hi = 0.0, 200.0                       # (the nearest mean's distance grows with t beyond the means themselves)
+            for _ in range(60):
+                t = (lo + hi) / 2
+                lo, hi = (t, hi) if np.linalg.norm(t * u - M, axis=1).min() < 40 else (lo, t)
+            X[row] = centre + L @ (hi * u)
+    else:
+        raise ValueError(kind)
+    return np.ascontiguousarray(X), pi0, mu0, S0
+
+
+def oracle_tied_step(orc, X, pi0, mu0, S0):
+    """The CPU yardstick of a tied step, in em_step_tied's output form: the oracle's full-covariance step on K copies of the
+    covariance, pooled as sum_k pi_k Sigma_k in ascending k in fp64 (the composed route's arithmetic, runtime/em.cpp), the ridge --
+    every Sigma_k carries it and the weights sum to 1 -- taken off once."""
+    K, d = len(pi0), X.shape[1]
+    em = orc.EM(K)
+    em.set_parameters(mu0, np.stack([S0] * K), pi0)
+    em.expectation_step(X)
+    ll, resp = em.log_likelihood, em.responsibilities
+    em.maximisation_step(X)
+    pi1, covs = em.mixing_probabilities, em.covariances
+    pooled = np.zeros((d, d))
+    for k in range(K):
+        pooled = pooled + pi1[k] * covs[k]
+    return ll, resp, pi1, em.means, pooled.astype(LD) - LD(1e-15) * np.eye(d, dtype=LD)
+
+
+def tied_kernel_log_resp(X, pi0, mu0, S0):
+    """em_tied_kernel's density arithmetic restated in fp64 numpy (device/em_tied.hip, host::build_tied_params): W = L^-1,
+    x~ = x - shift, y_i = sum_(j <= i) W_ij x~_j and m_ki = sum_(j <= i) W_ij (mu_kj - shift_j) as ascending-j chains without
+    fused multiply-adds, z = y - m_k, q = sum_j z_j^2 ascending, lw_k = (log pi_k - sum_j log L_jj) - q / 2, then the
+    log-sum-exp about the maximum. Returns the N x K log-responsibilities."""
+    n, d = X.shape
+    shift = X.mean(axis=0)
+    L = np.linalg.cholesky(S0)
+    W = np.linalg.solve(L, np.eye(d))
+    Xt = X - shift
+    Y = np.empty((n, d))
+    for i in range(d):
+        t = W[i, 0] * Xt[:, 0]
+        for j in range(1, i + 1):
+            t = t + W[i, j] * Xt[:, j]
+        Y[:, i] = t
+    with np.errstate(divide="ignore"):
+        coef = np.log(pi0) - np.log(np.diag(L)).sum()
+    lw = np.empty((n, len(pi0)))
+    for k in range(len(pi0)):
+        q = np.zeros(n)
+        for i in range(d):
+            m = 0.0
+            for j in range(i + 1):
+                m = m + W[i, j] * (mu0[k, j] - shift[j])
+            z = Y[:, i] - m
+            q = q + z * z
+        lw[:, k] = coef[k] - 0.5 * q
+    top = lw.max(axis=1)
+    lse = top + np.log(np.exp(lw - top[:, None]).sum(axis=1))
+    return lw - lse[:, None]
+
+
+def tied_whitening_ratio(X, pi0, mu0, S0):
+    """(the restatement's largest log-responsibility error over the pairs with r_ik >= 1e-6) / (2^-53 * whiten), and whiten."""
+    from oracle import hp_reference as hp
+    ref = hp.em_step_tied(X, pi0, mu0, S0)
+    whiten = hp.tied_conditioning(X, X.astype(LD).mean(axis=0), mu0, S0, ref[4], resp=ref[1])["whiten"]
+    pairs = ref[1] >= 1e-6
+    err = np.abs(tied_kernel_log_resp(X, pi0, mu0, S0).astype(LD)[pairs] - np.log(ref[1][pairs])).max()
+    return float(err) / (hp.EPS64 * whiten), whiten
+
+
+def tied_step_fp64(X, pi, mu, S):
+    """One tied EM step in fp64 numpy for blocks too long for the long-double reference: whitens the sample ONCE, one N x d
+    temporary per component, the covariance in its two-pass form + 1e-15 I. Returns (ll, responsibilities, pi1, mu1, Sigma1)."""
+    n, d = X.shape
+    K = len(pi)
+    L = np.linalg.cholesky(S)
+    Y = np.linalg.solve(L, X.T).T
+    M = np.linalg.solve(L, mu.T).T
+    lw = np.empty((n, K))
+    for k in range(K):
+        Z = Y - M[k]
+        lw[:, k] = np.log(pi[k]) - np.log(np.diag(L)).sum() - 0.5 * (Z * Z).sum(axis=1) - 0.5 * d * math.log(2 * math.pi)
+    top = lw.max(axis=1)
+    lse = top + np.log(np.exp(lw - top[:, None]).sum(axis=1))
+    R = np.exp(lw - lse[:, None])
+    s0 = R.sum(axis=0)
+    mu1 = R.T @ X / s0[:, None]
+    S1 = np.zeros((d, d))
+    for k in range(K):
+        D = X - mu1[k]
+        S1 += (D * R[:, k][:, None]).T @ D
+    return lse.mean(), R, s0 / n, mu1, S1 / n + 1e-15 * np.eye(d)
+
+
+def tied_grid(d, K, n, num_cus):
+    """Workgroups in x of an em_tied_kernel launch (device/em_tied.hip, em_tied_grid): one or two per CU by registers and LDS,
+    halved when the components need two row-block groups, never more than the 64-row tiles fill at 4 waves each."""
+    padded = next(p for p in (1, 2, 3, 4, 6, 8, 12, 16, 20, 24, 28, 32) if p >= d)
+    row_blocks = (K + 15) // 16
+    per_cu = 2 if padded <= 16 and row_blocks <= 2 else 1
+    grid = per_cu * num_cus // (2 if row_blocks >= 3 else 1)
+    return max(1, min(grid, ((n + 63) // 64 + 3) // 4))
+
+
+def tied_many_tiles_rows(d, K, num_cus):
+    """N at which every wave of the launch takes two whole tiles and the first ones a third, ragged one."""
+    return 64 * 4 * tied_grid(d, K, 2 ** 31, num_cus) * 2 + 37

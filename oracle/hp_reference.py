@@ -111,6 +111,39 @@ def em_step_diag(X, mixing, means, variances):
     return (lse.sum() / len(lse), resp.T) + _close(_ld(X), resp, True)
 
 
+def em_step_tied(X, mixing, means, cov, weights=None):
+    """One E + M step with ONE covariance shared by all components (the tied mode). Returns (mean
+    log-likelihood, responsibilities N x K, mixing, means, covariance d x d). Densities from one Cholesky factor of `cov`; the new
+    covariance in its two-pass form  sum_k sum_i w_i r_ik (x_i - mu_k)(x_i - mu_k)^T / W  about the NEW means, W = sum_i w_i (row
+    weights `weights`, all 1 when None; the log-likelihood is the weighted mean). No ridge; mixing weights of 0 are allowed. A
+    component whose weighted responsibilities are all exactly 0 has no mean (0 / 0 = NaN) and adds nothing to the covariance: its
+    term is a sum of exact zeros and is left out, as the limit is."""
+    X, mixing, means = _ld(X), _ld(mixing), _ld(means)
+    n, d = X.shape
+    K = len(mixing)
+    L = cholesky(cov)
+    half_log_det = np.log(np.diag(L)).sum()
+    with np.errstate(divide="ignore"):
+        log_pi = np.log(mixing)
+    Xt = np.ascontiguousarray(X.T)                   # d x N: rows contiguous over the samples
+    lw = np.empty((K, n), LD)
+    for k in range(K):
+        y = solve_lower(L, Xt - means[k][:, None])
+        lw[k] = log_pi[k] - half_log_det - (y * y).sum(axis=0) / 2 - d * _LOG_2PI / 2
+    resp, lse = _normalise(lw)
+    w = np.ones(n, LD) if weights is None else _ld(weights)
+    total = w.sum()
+    wr = resp * w
+    s0 = wr.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        new_means = (wr @ X) / s0[:, None]
+    second = np.zeros((d, d), LD)
+    for k in np.nonzero(s0 > 0)[0]:
+        c = Xt - new_means[k][:, None]
+        second += np.einsum("an,bn->ab", c * wr[k], c)
+    return (w * lse).sum() / total, resp.T, s0 / total, new_means, second / total
+
+
 def squared_distances(X, centroids):
     """N x K block |x_i - c_k|^2."""
     X, centroids = _ld(X), _ld(centroids)
@@ -191,6 +224,35 @@ def conditioning(shift, means, covs=None, variances=None):
         out.update(ratio=(off ** 2 / v).max(axis=1).astype(np.float64),
                    kappa=np.sqrt(v.max(axis=1) / v.min(axis=1)).astype(np.float64))
     out["b2"] = (off ** 2 / _ld(variances)).sum(axis=1).astype(np.float64)
+    return out
+
+
+def tied_conditioning(X, shift, means, cov_old, cov_new, resp=None):
+    """The quantities the tied kernel's error models are stated in, as floats in a dict. `means` and
+    `cov_old` are the parameters the E-step is called with, `cov_new` the step's result, `shift` the statistics' shift (the data
+    mean, Data.shift); with L L^T = cov_old, x~ = x - shift, y_i = L^-1 x~_i, m_k = L^-1 (mu_k - shift), z_ik = y_i - m_k:
+
+    tratio  max_j (T / N)_jj / cov_new_jj, T = sum_i x~_i x~_i^T   -- the cancellation of Sigma = T / N - sum_k pi_k mu~_k mu~_k^T
+    reach   max_k max_j |m_kj|                                      -- how far the whitening reaches from the shift
+    whiten  max over the pairs with r_ik >= 1e-6 of  sum_j |z_ikj| (|y_ij| + |m_kj|)   -- the first-order coefficient of the
+            whitening model (each y_j, m_kj carries an absolute error ~ 2^-53 of its size) in a log-responsibility;
+            `resp`: the step's N x K responsibilities (only this entry needs them; left out when None)."""
+    X, shift, means = _ld(X), _ld(shift), _ld(means)
+    Xt = X - shift
+    T = (Xt * Xt).sum(axis=0) / X.shape[0]
+    L = cholesky(cov_old)
+    Y = solve_lower(L, Xt.T).T                       # N x d
+    M = solve_lower(L, (means - shift).T).T          # K x d
+    out = {"tratio": float((T / np.diag(_ld(cov_new))).max()), "reach": float(np.abs(M).max())}
+    if resp is not None:
+        resp = np.asarray(resp, dtype=np.float64)
+        worst = 0.0
+        for k in range(means.shape[0]):
+            rows = resp[:, k] >= 1e-6
+            if rows.any():
+                y = Y[rows]
+                worst = max(worst, float((np.abs(y - M[k]) * (np.abs(y) + np.abs(M[k]))).sum(axis=1).max()))
+        out["whiten"] = worst
     return out
 
 

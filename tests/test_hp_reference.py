@@ -17,6 +17,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from oracle import hp_reference as hp   # noqa: E402  (raises where long double is not extended precision: a failure, not a skip)
+from oracle import hp_cases   # noqa: E402
 from oracle.hp_cases import KMEANS_SHAPES, edge_problem, oracle_step, problem, refinement_problem   # noqa: E402
 
 LD = np.longdouble
@@ -109,6 +110,62 @@ def test_em_reference_against_50_digits(d, K, n, seed, diagonal):
     for name, g, w in zip(("log-likelihood", "responsibilities", "mixing", "means", "covariances"), got, want):
         err = _mp_rel_err(g, w)
         print(f"d={d} K={K} n={n} {name}: {err:.2e} (limit {MP_LIMIT:.2e})")
+        assert err <= MP_LIMIT, name
+
+
+def _mp_em_step_tied(X, pi0, mu0, S0, w):
+    """em_step_tied at 50 digits: one factor, the covariance about the new means, a component of zero mass left out of it."""
+    import mpmath as mp
+    mp.mp.dps = 50
+    n, d = X.shape
+    K = len(pi0)
+    x = [[mp.mpf(float(v)) for v in row] for row in X]
+    wt = [mp.mpf(float(v)) for v in w]
+    L = mp.cholesky(mp.matrix([[mp.mpf(float(v)) for v in row] for row in S0]))
+    half_log_det = sum(mp.log(L[j, j]) for j in range(d))
+    resp = [[None] * K for _ in range(n)]
+    ll = mp.mpf(0)
+    for i in range(n):
+        lw = []
+        for k in range(K):
+            c = [x[i][j] - mp.mpf(float(mu0[k, j])) for j in range(d)]
+            y = []
+            for j in range(d):
+                y.append((c[j] - sum(L[j, l] * y[l] for l in range(j))) / L[j, j])
+            log_pi = mp.log(mp.mpf(float(pi0[k]))) if pi0[k] > 0 else mp.mpf("-inf")
+            lw.append(log_pi - half_log_det - sum(v * v for v in y) / 2 - d * mp.log(2 * mp.pi) / 2)
+        m = max(lw)
+        e = [mp.exp(v - m) if v != mp.mpf("-inf") else mp.mpf(0) for v in lw]
+        ll += wt[i] * (m + mp.log(sum(e)))
+        resp[i] = [v / sum(e) for v in e]
+    total = sum(wt)
+    s0 = [sum(wt[i] * resp[i][k] for i in range(n)) for k in range(K)]
+    live = [k for k in range(K) if s0[k] > 0]
+    means = {k: [sum(wt[i] * resp[i][k] * x[i][j] for i in range(n)) / s0[k] for j in range(d)] for k in live}
+    cov = [[sum(wt[i] * resp[i][k] * (x[i][a] - means[k][a]) * (x[i][b] - means[k][b]) for k in live for i in range(n)) / total
+            for b in range(d)] for a in range(d)]
+    return ll / total, resp, [v / total for v in s0], means, cov
+
+
+@pytest.mark.parametrize("d,K,n,seed,weighted,zero", [(2, 3, 60, 31, False, None), (5, 2, 47, 32, False, None), (3, 3, 53, 33, True, None),
+                                                      (4, 3, 60, 34, False, 1)])
+def test_tied_reference_against_50_digits(d, K, n, seed, weighted, zero):
+    X, pi0, mu0, S = _mp_problem(d, K, n, seed)
+    S0 = S[0]
+    w = np.random.default_rng(seed).integers(0, 4, n).astype(np.float64) if weighted else None
+    if zero is not None:
+        pi0[zero] = 0.0
+        pi0 /= pi0.sum()
+    got = hp.em_step_tied(X, pi0, mu0, S0, w)
+    ll, resp, mixing, means, cov = _mp_em_step_tied(X, pi0, mu0, S0, np.ones(n) if w is None else w)
+    live = sorted(means)
+    assert live == [k for k in range(K) if k != zero]
+    if zero is not None:                                   # the empty component: no mass, no mean, nothing in the covariance
+        assert got[2][zero] == 0 and not got[1][:, zero].any() and np.isnan(got[3][zero].astype(np.float64)).all()
+    for name, g, want in (("log-likelihood", got[0], ll), ("responsibilities", got[1], resp), ("mixing", got[2], mixing),
+                          ("means", got[3][live], [means[k] for k in live]), ("covariance", got[4], cov)):
+        err = _mp_rel_err(g, want)
+        print(f"tied d={d} K={K} n={n} weighted={weighted} zero={zero} {name}: {err:.2e} (limit {MP_LIMIT:.2e})")
         assert err <= MP_LIMIT, name
 
 
@@ -244,6 +301,97 @@ def test_refinement_problems_reach_their_ratio():
             ref = hp.em_step(X, pi0, mu0, S0)
             ratio = hp.conditioning(X.astype(LD).mean(axis=0), ref[3], covs=ref[4])["ratio"]
             assert abs(ratio.max() / target - 1) < 0.02, (d, target, ratio)
+
+
+# ---- the tied-covariance cases of tests/test_gpu_tied_hp.py: what each one needs of its data --------------------------------
+
+def test_tied_conditioning_quantities():
+    X = np.array([[3.0, 0.0], [-3.0, 0.0], [0.0, 4.0], [0.0, -4.0]])
+    means = np.array([[2.0, 0.0], [0.0, -8.0]])
+    resp = np.array([[1.0, 0.0], [1e-7, 1.0], [0.5, 0.5], [0.0, 1.0]])
+    c = hp.tied_conditioning(X, np.zeros(2), means, np.diag([1.0, 4.0]), np.diag([0.5, 2.0]), resp=resp)
+    # T / N = diag(4.5, 8); m = (2, 0), (0, -4); y = (3, 0), (-3, 0), (0, 2), (0, -2)
+    assert np.isclose(c["tratio"], 9.0) and np.isclose(c["reach"], 4.0)
+    # pairs with r >= 1e-6: (0, 0): 1 * 5 = 5; (2, 0): 2 * 2 + 2 * 2 = 8; (1, 1): 3 * 3 + 4 * 4 = 25; (2, 1): 6 * 6 = 36; (3, 1): 2 * 6 = 12
+    assert np.isclose(c["whiten"], 36.0)
+
+
+@pytest.mark.parametrize("d,K", hp_cases.TIED_CODE_OBJECT_CASES)
+def test_tied_code_object_cases_have_comparable_labels(d, K):
+    """Labels are compared on the rows whose two largest reference responsibilities differ by more than 1e-9: at least 99.9 % of
+    the rows must qualify, and on them the oracle's labels and responsibilities are the reference's."""
+    from oracle import oracle_ctypes as orc
+    X, pi0, mu0, S0 = hp_cases.tied_problem(d, K, hp_cases.TIED_N, 2.0, 2.5)
+    ref = hp.em_step_tied(X, pi0, mu0, S0)
+    top = np.sort(ref[1], axis=1)
+    clear = (top[:, -1] - top[:, -2]) > 1e-9
+    assert clear.mean() >= 0.999
+    cpu = hp_cases.oracle_tied_step(orc, X, pi0, mu0, S0)
+    assert np.array_equal(cpu[1].argmax(axis=1)[clear], ref[1].argmax(axis=1)[clear])
+    assert hp.abs_err(cpu[1], ref[1]) <= 1e-12
+    assert np.all(ref[2] > 0)
+
+
+def test_tied_sweep_and_reach_cases_and_the_whitening_constant():
+    """The conditioning sweep spans tratio 10 ... 1e5 and sends components of the composed route above the refinement guard; the
+    reach cases sit below / above / far above 64 with >= 500 rows inside (1e-3, 1 - 1e-3); and C_WHITEN is the fp64 restatement's
+    largest log-responsibility error in units of 2^-53 * whiten over all of them, rounded up."""
+    worst, tratios = 0.0, []
+    for offset, sep in hp_cases.TIED_SWEEP_CASES:
+        X, pi0, mu0, S0 = hp_cases.tied_problem(8, 5, 3001, offset, sep)
+        ref = hp.em_step_tied(X, pi0, mu0, S0)
+        shift = X.astype(LD).mean(axis=0)
+        tratios.append(hp.tied_conditioning(X, shift, mu0, S0, ref[4])["tratio"])
+        ratio = hp.conditioning(shift, ref[3], covs=hp.m_step(X, ref[1])[2])["ratio"]
+        ratio_w, whiten = hp_cases.tied_whitening_ratio(X, pi0, mu0, S0)
+        print(f"tied sweep offset={offset} sep={sep}: tratio {tratios[-1]:.4g}, composed ratio max {ratio.max():.4g}, "
+              f"{int((ratio > 1e4).sum())} above 1e4, whiten {whiten:.4g}, restatement {ratio_w:.3f} x 2^-53 whiten")
+        assert (ratio.max() > 1e4) == (sep >= 300)
+        worst = max(worst, ratio_w)
+    assert 10 < tratios[0] < 20 and 1e3 < tratios[1] < 2e3 and tratios[2] > 1e5 and abs(tratios[3] / tratios[1] - 1) < 1e-9
+    for reach in hp_cases.TIED_REACHES:
+        X, pi0, mu0, S0 = hp_cases.tied_reach_problem(reach)
+        ref = hp.em_step_tied(X, pi0, mu0, S0)
+        cond = hp.tied_conditioning(X, X.astype(LD).mean(axis=0), mu0, S0, ref[4], resp=ref[1])
+        soft = int(((ref[1] > 1e-3) & (ref[1] < 1 - 1e-3)).any(axis=1).sum())
+        ratio_w, whiten = hp_cases.tied_whitening_ratio(X, pi0, mu0, S0)
+        print(f"tied reach {reach}: achieved {cond['reach']:.4g}, {soft} soft rows, whiten {whiten:.4g}, restatement {ratio_w:.3f} x 2^-53 whiten")
+        assert soft >= 500 and abs(cond["reach"] / reach - 1) < 0.05 and (cond["reach"] > 64) == (reach > 64)
+        worst = max(worst, ratio_w)
+    assert hp_cases.C_WHITEN - 1 < worst <= hp_cases.C_WHITEN, worst
+
+
+def test_tied_edge_problems_hold_what_they_are_built_for():
+    X, pi0, mu0, S0 = hp_cases.tied_edge_problem("zero_weight")
+    ref = hp.em_step_tied(X, pi0, mu0, S0)
+    assert pi0[2] == 0 and abs(pi0.sum() - 1) < 1e-15 and not ref[1][:, 2].any() and np.isfinite(float(ref[0]))
+    X, pi0, mu0, S0 = hp_cases.tied_edge_problem("empty")
+    ref = hp.em_step_tied(X, pi0, mu0, S0)
+    L = np.linalg.cholesky(S0)
+    assert np.linalg.norm(np.linalg.solve(L, (X - mu0[4]).T), axis=0).min() > 9.9e3
+    assert not ref[1][:, 4].any() and ref[2][4] == 0 and np.all(ref[2][:4] > 0)            # exactly 0, in long double too
+    assert np.isnan(ref[3][4].astype(np.float64)).all() and np.isfinite(ref[4].astype(np.float64)).all()
+    X, pi0, mu0, S0 = hp_cases.tied_edge_problem("tail")
+    dist = np.stack([np.linalg.norm(np.linalg.solve(L, (X - m).T), axis=0) for m in mu0], axis=1).min(axis=1)
+    far = np.sort(dist)[-20:]
+    assert np.all(np.abs(far - 40) < 1e-6) and np.sort(dist)[-21] < 10
+    ref = hp.em_step_tied(X, pi0, mu0, S0)
+    assert np.isfinite(float(ref[0])) and hp.abs_err(ref[1].sum(axis=1), np.ones(len(X))) < 1e-18
+
+
+def test_tied_fp64_restatement_and_many_tile_shapes():
+    """The fp64 yardstick of the longest many-tiles case agrees with the reference at a small size far inside
+    tests/test_gpu_tied.py's tolerances, and on a 256-CU card every many-tiles shape gives a wave a third tile."""
+    X, pi0, mu0, S0 = hp_cases.tied_problem(32, 40, 1501, 2.0, 2.5)
+    ref = hp.em_step_tied(X, pi0, mu0, S0)
+    got = hp_cases.tied_step_fp64(X, pi0, mu0, S0)
+    assert abs(float((LD(got[0]) - ref[0]) / ref[0])) < 1e-14 and hp.abs_err(got[1], ref[1]) < 1e-13
+    assert hp.rel_err(got[2], ref[2]) < 1e-13 and hp.rel_err(got[3], ref[3]) < 1e-13
+    assert hp.rel_err(got[4] - 1e-15 * np.eye(32), ref[4]) < 1e-12
+    for d, K, rows in ((3, 2, 262181), (21, 5, 131109), (32, 40, 65573)):
+        grid = hp_cases.tied_grid(d, K, 2 ** 31, 256)
+        n = hp_cases.tied_many_tiles_rows(d, K, 256)
+        assert n == rows and (n + 63) // 64 > 2 * 4 * grid == 2 * 4 * hp_cases.tied_grid(d, K, n, 256)
 
 
 # ---- the comparison helper ------------------------------------------------------------------------------------------------
