@@ -58,8 +58,9 @@ __device__ __forceinline__ double allreduce_sum_bits345(double v)
 /// written responsibilities are nonzero (wave-uniform). WEIGHTED (a block with row weights): the value written is r w_i, the
 /// sample's frequency weight `wi` applied AFTER the normalisation (one rounding more than r); max and sum -- hence lse -- stay the
 /// sample's own. MASKS: nz[it] receives the wave's ballot of "written value `it` is nonzero" (bit = lane) -- the ballots the count
-/// is made of anyway; the sparse kernel builds its buckets from them.
-template <int NRV, int RS, bool WEIGHTED = false, bool MASKS = false>
+/// is made of anyway; the sparse kernel builds its buckets from them. KMASK = false: the caller has already set the rv[] of the
+/// components >= K to -inf (the sparse kernel, which skips that when K fills every slot).
+template <int NRV, int RS, bool WEIGHTED = false, bool MASKS = false, bool KMASK = true>
 __device__ __forceinline__ uint32_t stage_self_norm(double (&rv)[NRV], int cg, int K, uint32_t i, bool live, double* Rb, int sR,
                                                      bool write_lse, double* __restrict__ lse_out, double* __restrict__ esum_out,
                                                      double wi = 1.0, unsigned long long* nz = nullptr)
@@ -67,7 +68,8 @@ __device__ __forceinline__ uint32_t stage_self_norm(double (&rv)[NRV], int cg, i
     double m = -__builtin_inf();
 #pragma unroll
     for (int it = 0; it < NRV; ++it) {
-        if (cg * NRV + it >= K) rv[it] = -__builtin_inf();          // components beyond K: exp(-inf) = 0
+        if constexpr (KMASK)
+            if (cg * NRV + it >= K) rv[it] = -__builtin_inf();      // components beyond K: exp(-inf) = 0
         m = fmax(m, rv[it]);
     }
     m = allreduce_max_bits345(m);
