@@ -1,5 +1,6 @@
-"""Inputs shared by tests/test_hp_reference.py (CPU) and tests/test_gpu_hp_error.py (GPU): mixture problems, the oracle's step in
-the reference's output form, and the problems that sit just below / above a guard of DESIGN.md section 4 (test infrastructure)."""
+"""Inputs shared by tests/test_hp_reference.py (CPU) and tests/test_gpu_hp_error.py / test_gpu_hp_edges.py (GPU): mixture problems,
+the oracle's step in the reference's output form, the problems that sit just below / above a guard of DESIGN.md section 4, and the
+inputs no plain sample holds -- a component without mass, rows far in a tail (test infrastructure)."""
 import importlib.util
 import math
 import os
@@ -103,6 +104,139 @@ def edge_problem(d, reach, diagonal=False, seed=4):
     mu0 = np.vstack([np.full(d, 0.75), p, p + L[1] @ w])
     second = np.stack([var[0], var[1], var[1]]) if diagonal else np.stack([S[0], S[1], S[1]])
     return X, np.array([n0 / n, n1 / n, n1 / n]), mu0, second
+
+
+# ---- inputs no plain sample holds (tests/test_gpu_hp_edges.py on the GPU, their data conditions in tests/test_hp_reference.py) -----
+
+MASSLESS_KINDS = ("zero_weight_first", "zero_weight_last", "far", "hole")
+TAIL_ROWS = 20
+TAIL_GAP = 8.0                    # a moved row's runner-up lies at least this far below its winner, in log-weight
+HOLE_UNITS = 400.0
+ZERO_ROWS = 40
+# (d, K, N, offset) of the GPU module's cases: one step on every full-covariance route, the loops' extra shape, the diagonal routes
+# (K <= 16 and K = 17..64) and the weighted routes
+EDGE_SHAPES = [(2, 3, 3001, 0.0), (8, 5, 3001, 3.0), (6, 8, 3001, 2.0), (16, 8, 4001, 2.0), (16, 24, 5001, 1.0), (32, 16, 6001, 0.0),
+               (32, 64, 2001, 0.0), (33, 4, 3001, 0.0), (136, 2, 1001, 0.0)]
+EDGE_LOOP_SHAPES = [(72, 2, 2501, 0.0)]
+EDGE_DIAG_SHAPES = [(16, 8, 4001, 0.5), (7, 40, 4001, 0.0)]
+EDGE_WEIGHTED_SHAPES = [(16, 8, 4001, 2.0), (8, 5, 3001, 3.0)]
+# (d, the dead component in front) of massless_refinement_problem: the fused kernel, the matrix-core E-step + statistics kernel
+MASSLESS_REFINEMENT_CASES = [(8, True), (32, False)]
+
+
+def tail_window(d):
+    """The open interval a moved tail row's largest log-weight must lie in: (-900, -750) -- below the underflow of a linear-domain
+    density, yet of the size the 40 whitened units are chosen for. At d = 136 the density's constant -d/2 log 2 pi = -125 alone puts
+    the same 40 units at -943: (-950, -750) there."""
+    return (-950.0 if d >= 136 else -900.0), -750.0
+
+
+def tail_row_is_clear(k, top, gap, winner, d):
+    """The condition on ONE moved row (tests/test_hp_reference.py asserts it for every row): won by its own component, inside
+    tail_window(d), the runner-up at least TAIL_GAP below."""
+    lo, hi = tail_window(d)
+    return bool(winner == k and lo < top < hi and gap >= TAIL_GAP)
+
+
+def _factors(S0, diagonal):
+    return [np.diag(np.sqrt(v)) for v in S0] if diagonal else [np.linalg.cholesky(s) for s in S0]
+
+
+def massless_problem(kind, d, K, n, offset, diagonal=False):
+    """problem(d, K, n, offset, diagonal) with ONE component that takes no mass in the step: (X, pi0, mu0, S0, k).
+    `zero_weight_first` / `zero_weight_last`: pi_k = 0 for k = 0 / K - 1, the rest renormalised. `far`: mu_(K-1) = shift +
+    1e4 sqrt(diag Sigma_(K-1)), shift the fp64 data mean -- beyond every reach guard, so the exact density forms run. `hole`:
+    mu_(K-1) = shift and Sigma_(K-1) = tiny^2 I with tiny = (the smallest distance of a row from the shift) / 400 -- at reach 0
+    (fold = b2 = 0: the FOLD and two-operation forms stay on), yet every row at least 400 of its whitened units away."""
+    X, pi0, mu0, S0 = problem(d, K, n, offset, diagonal)
+    pi0, mu0, S0 = pi0.copy(), mu0.copy(), S0.copy()
+    shift = X.mean(axis=0)
+    k = 0 if kind == "zero_weight_first" else K - 1
+    if kind in ("zero_weight_first", "zero_weight_last"):
+        pi0[k] = 0.0
+        pi0 /= pi0.sum()
+    elif kind == "far":
+        mu0[k] = shift + 1e4 * np.sqrt(S0[k] if diagonal else np.diag(S0[k]))
+    elif kind == "hole":
+        tiny = np.linalg.norm(X - shift, axis=1).min() / HOLE_UNITS
+        mu0[k] = shift
+        S0[k] = np.full(d, tiny ** 2) if diagonal else tiny ** 2 * np.eye(d)
+    else:
+        raise ValueError(kind)
+    return X, pi0, mu0, S0, k
+
+
+def tail_problem(d, K, n, offset, diagonal=False, only_clear=False, seed=5):
+    """problem(...) with TAIL_ROWS seeded rows moved 40 whitened units straight out behind a mean: for t = 0 .. TAIL_ROWS - 1 and
+    k = t mod K the row becomes mu_k + 40 L_k u, u = unit(L_k^-1 (mu_k - shift)) (log-weights near -800, where a linear-domain
+    sum has underflowed). `only_clear` (K above TAIL_ROWS, where neighbours crowd): a row is moved only if tail_row_margins() of
+    its new place passes. Returns (X, pi0, mu0, S0, rows, their components)."""
+    X, pi0, mu0, S0 = problem(d, K, n, offset, diagonal)
+    X = X.copy()
+    shift = X.mean(axis=0)
+    L = _factors(S0, diagonal)
+    picked = np.random.default_rng(seed).choice(n, TAIL_ROWS, replace=False)
+    rows, comps = [], []
+    for t, row in enumerate(picked):
+        k = t % K
+        u = np.linalg.solve(L[k], mu0[k] - shift)
+        x = mu0[k] + 40.0 * (L[k] @ (u / np.linalg.norm(u)))
+        if only_clear:
+            top, gap, winner = tail_row_margins(x[None], pi0, mu0, S0, diagonal)
+            if not tail_row_is_clear(k, top[0], gap[0], winner[0], d):
+                continue
+        X[row] = x
+        rows.append(int(row))
+        comps.append(k)
+    return np.ascontiguousarray(X), pi0, mu0, S0, np.array(rows), np.array(comps)
+
+
+def tail_row_margins(rows, pi0, mu0, S0, diagonal=False):
+    """(largest log-weight, its distance to the runner-up, the winner) of each row, from the extended-precision log-weights."""
+    from oracle import hp_reference as hp
+    lw = (hp.log_weights_diag if diagonal else hp.log_weights)(rows, pi0, mu0, S0)
+    order = np.sort(lw, axis=0)
+    return order[-1].astype(np.float64), (order[-1] - order[-2]).astype(np.float64), lw.argmax(axis=0)
+
+
+def zero_weight_rows_problem(d, K, n, offset, w, seed=6):
+    """A component alive on the block and exactly massless on the WEIGHTED sample: mu_(K-1) = shift + 200 L e_0 (L the factor of
+    Sigma_(K-1): 200 whitened units from the data mean), ZERO_ROWS seeded rows overwritten with mu_(K-1) + 0.05 L z and given
+    weight 0; every other row keeps its weight in `w`. Returns (X, weights, pi0, mu0, S0, the rows)."""
+    X, pi0, mu0, S0 = problem(d, K, n, offset)
+    X, mu0, w = X.copy(), mu0.copy(), np.array(w, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    L = np.linalg.cholesky(S0[K - 1])
+    mu0[K - 1] = X.mean(axis=0) + 200.0 * L[:, 0]
+    rows = np.sort(rng.choice(n, ZERO_ROWS, replace=False))
+    X[rows] = mu0[K - 1] + 0.05 * rng.standard_normal((ZERO_ROWS, d)) @ L.T
+    w[rows] = 0.0
+    return np.ascontiguousarray(X), w, pi0, mu0, S0, rows
+
+
+def massless_refinement_problem(d, target, first):
+    """refinement_problem(d, target) -- one live component at `target` x its variance from the shift, above MLHIP_REFINE_RATIO for
+    target > 1e4 -- with a third component of mixing weight 0 put in front (`first`) or behind: the refinement pass must run for the
+    live component above the guard and skip the dead one. Returns (X, pi0, mu0, S0, k)."""
+    X, pi0, mu0, S0 = refinement_problem(d, target)
+    k = 0 if first else 2
+    dead_mu, dead_S = X.mean(axis=0)[None], np.eye(d)[None]
+    order = (lambda dead, live: np.concatenate([dead, live])) if first else (lambda dead, live: np.concatenate([live, dead]))
+    return X, order(np.zeros(1), pi0), order(dead_mu, mu0), order(dead_S, S0), k
+
+
+def massless_pattern(step, k):
+    """True when a step's (ll, resp, mixing, means, second moments) shows the documented pattern of a component without mass
+    (DESIGN.md section 4.1): column k of the responsibilities exactly 0, pi_k = 0, mu_k and Sigma_k / var_k NaN in every entry,
+    everything else (the log-likelihood included) finite. `resp` may be None."""
+    ll, resp, mixing, means, second = step
+    f = lambda a: np.asarray(a, dtype=np.float64)   # noqa: E731
+    live = np.arange(len(f(mixing))) != k
+    ok = bool(np.isfinite(float(ll))) and f(mixing)[k] == 0 and bool(np.isfinite(f(mixing)).all())
+    if resp is not None:
+        ok = ok and not f(resp)[:, k].any() and bool(np.isfinite(f(resp)).all())
+    return bool(ok and np.isnan(f(means)[k]).all() and np.isfinite(f(means)[live]).all()
+                and np.isnan(f(second)[k]).all() and np.isfinite(f(second)[live]).all())
 
 
 # ---- tied covariance (DESIGN.md section 3.3i): tests/test_gpu_tied_hp.py on the GPU, the data conditions in tests/test_hp_reference.py ----

@@ -55,15 +55,17 @@ def _normalise(lw):
 
 
 def _close(X, resp, diagonal):
-    """Two-pass M-step: the means first, then the second moments about them."""
+    """Two-pass M-step: the means first, then the second moments about them. A component whose responsibilities are all exactly 0
+    has no mean and no second moments: 0 / 0 = NaN in every entry, silently."""
     n = X.shape[0]
     s0 = resp.sum(axis=1)
-    means = (resp @ X) / s0[:, None]
-    K, d = means.shape
-    second = np.empty((K, d) if diagonal else (K, d, d), LD)
-    for k in range(K):
-        c = X - means[k]
-        second[k] = (resp[k][:, None] * c * c).sum(axis=0) / s0[k] if diagonal else (c.T * resp[k]) @ c / s0[k]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        means = (resp @ X) / s0[:, None]
+        K, d = means.shape
+        second = np.empty((K, d) if diagonal else (K, d, d), LD)
+        for k in range(K):
+            c = X - means[k]
+            second[k] = (resp[k][:, None] * c * c).sum(axis=0) / s0[k] if diagonal else (c.T * resp[k]) @ c / s0[k]
     return s0 / n, means, second
 
 

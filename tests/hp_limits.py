@@ -1,7 +1,10 @@
-"""The error norms and limit rules of the extended-precision error suites (tests/test_gpu_hp_error.py, tests/test_gpu_tied_hp.py;
-DESIGN.md section 4.1) -- a plain module, no fixtures. The rules are stated in test_gpu_hp_error.py's docstring."""
+"""The error norms and limit rules of the extended-precision error suites (tests/test_gpu_hp_error.py, tests/test_gpu_tied_hp.py,
+tests/test_gpu_hp_edges.py) -- a plain module, no fixtures. The rules are stated in test_gpu_hp_error.py's
+docstring; the checkers of test_gpu_hp_edges.py's inputs (a component without mass, rows far in a tail) live here too, so that
+tests/test_hp_reference.py can show on the CPU that they reject a wrong result."""
 import numpy as np
 
+from oracle import hp_cases
 from oracle import hp_reference as hp
 
 LD = np.longdouble
@@ -51,3 +54,80 @@ def _report_and_check(name, e_gpu, e_cpu, ratio, estep_model=None, model_name=""
     for k in np.nonzero(~(e_gpu["covs"] <= limit))[0]:
         failures.append(f"covs[{k}]: {e_gpu['covs'][k]:.2e} > {limit[k]:.2e} (ratio {ratio[k]:.3g})")
     assert not failures, (name, failures)
+
+
+# ---- the inputs of tests/test_gpu_hp_edges.py ----------------------------------------------------------------------------------
+
+def finite_errors(e):
+    """The oracle's errors as a yardstick: an error that is not finite (the oracle has no value there) counts as 0."""
+    def clean(v):
+        if v is None:
+            return None
+        if isinstance(v, np.ndarray):
+            return np.where(np.isfinite(v), v, 0.0)
+        return v if np.isfinite(v) else 0.0
+    return {k: clean(v) for k, v in e.items()}
+
+
+def live_part(step, live):
+    """A step with the massless component's mean and covariance left out (compared as a NaN pattern instead)."""
+    return (step[0], step[1], step[2], np.asarray(step[3])[live], np.asarray(step[4])[live])
+
+
+def edge_references(X, pi0, mu0, S0, k, diagonal, shift_of=None):
+    """The reference and the oracle on one input -> dict: ref, cpu (the oracle's step), live (the components compared entry by entry),
+    e_cpu (the oracle's errors on the live part, non-finite ones 0), ratio (the live components' refinement ratios about the
+    block's shift), old (conditioning of the parameters the E-step is called with), lse_max."""
+    from oracle import oracle_ctypes as orc
+    K = len(pi0)
+    live = np.array([j for j in range(K) if j != k])
+    ref = (hp.em_step_diag if diagonal else hp.em_step)(X, pi0, mu0, S0)
+    with np.errstate(all="ignore"):
+        cpu = hp_cases.oracle_step(orc, X, pi0, mu0, S0, diagonal)
+        e_cpu = finite_errors(_errors(live_part(cpu, live), live_part(ref, live)))
+    shift = (X if shift_of is None else shift_of).astype(LD).mean(axis=0)
+    key = "variances" if diagonal else "covs"
+    ratio = hp.conditioning(shift, ref[3][live], **{key: ref[4][live]})["ratio"]
+    old = hp.conditioning(shift, mu0, **{key: S0})
+    lw = (hp.log_weights_diag if diagonal else hp.log_weights)(X, pi0, mu0, S0)
+    return {"ref": ref, "cpu": cpu, "live": live, "e_cpu": e_cpu, "ratio": ratio, "old": old,
+            "lse_max": float(np.abs(lw.max(axis=0)).max()), "k": k}
+
+
+def check_massless(name, got, labels, refs, refined, estep_model=None, model_name="", rows=None):
+    """The massless pattern, then the live part within the module's limits. `rows`: the rows the reference holds (a weighted block:
+    those of positive weight); got[1] None where the route hands out no responsibilities."""
+    k, live, ref = refs["k"], refs["live"], refs["ref"]
+    if got[1] is not None:
+        assert not got[1][:, k].any(), f"{name}: a responsibility of the massless component is not exactly 0"
+        assert not (labels == k).any(), f"{name}: a row is labelled with the massless component"
+    assert got[2][k] == 0, (name, got[2][k])
+    assert hp_cases.massless_pattern(got, k), f"{name}: not the massless pattern (finite ll {np.isfinite(got[0])}, mu_k {got[3][k]})"
+    assert hp_cases.massless_pattern(refs["cpu"], k) and hp_cases.massless_pattern(ref, k)
+    resp = got[1] if rows is None or got[1] is None else got[1][rows]
+    e_gpu = _errors(live_part((got[0], resp) + tuple(got[2:]), live), live_part(ref, live))
+    e_cpu = refs["e_cpu"] if resp is not None else dict(refs["e_cpu"], resp=None)
+    above = refs["ratio"] > 1e4
+    assert refined == int(above.sum()), (name, refined, refs["ratio"])
+    _report_and_check(name, e_gpu, e_cpu, refs["ratio"], estep_model, model_name, abs(float(ref[0])), refined=above,
+                      mix_max=float(ref[2].max()))
+
+
+def check_tail(name, got, labels, refs, moved, comps, refined, estep_model=None, model_name="", rows=None):
+    """Rows far in a tail: a finite log-likelihood (the mean of the per-row log-sum-exp: finite exactly when each of them is), rows
+    summing to 1, the moved rows `moved` labelled with their own components `comps`, then the module's limits with
+    2 * 2^-53 * lse_max -- the rounding of an fp64 log-weight of that size -- as the responsibilities' yardstick (the oracle has
+    no finite value on such data). `rows` as in check_massless."""
+    ref = refs["ref"]
+    yard = 2 * hp.EPS64 * refs["lse_max"]
+    assert np.isfinite(got[0]), f"{name}: a per-row log-sum-exp is not finite (log-likelihood {got[0]})"
+    if got[1] is not None:
+        assert np.abs(got[1].sum(axis=1) - 1).max() <= 4 * max(FLOOR, yard), name
+        assert np.array_equal(labels[moved], comps), (name, labels[moved], comps)
+    resp = got[1] if rows is None or got[1] is None else got[1][rows]
+    e_gpu = _errors((got[0], resp) + tuple(got[2:]), ref)
+    e_cpu = dict(refs["e_cpu"], resp=yard if resp is not None else None)
+    above = refs["ratio"] > 1e4
+    assert refined == int(above.sum()), (name, refined, refs["ratio"])
+    _report_and_check(f"{name} [lse max {refs['lse_max']:.4g}]", e_gpu, e_cpu, refs["ratio"], estep_model, model_name, abs(float(ref[0])),
+                      refined=above, mix_max=float(ref[2].max()))

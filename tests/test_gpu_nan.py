@@ -26,7 +26,7 @@ def _problem(d, K, n, seed):
 @pytest.mark.parametrize("d,K,n,diagonal", [
     (32, 64, 6000, False),    # matrix-core E-step, self-normalising statistics kernel
     (16, 40, 6000, False),    # matrix-core E-step with its own log-sum-exp
-    (8, 5, 5000, False),      # scalar-fed E-step
+    (8, 5, 5000, False),      # fused kernel, density loop fed from scalar registers
     (4, 3, 5000, False),      # fused small-shape kernel
     (48, 4, 3000, False),
     (16, 16, 6000, True),     # diagonal kernel
@@ -65,7 +65,7 @@ def test_nan_parameters_poison_the_log_likelihood(ctx, oracle, d, K, n, diagonal
 @pytest.mark.parametrize("d,K,n", [
     (16, 40, 6000),      # matrix-core E-step with its own log-sum-exp
     (32, 64, 6000),      # ... without (the statistics kernel normalises)
-    (8, 5, 5000),        # scalar-fed E-step
+    (8, 5, 5000),        # em_expectation: scalar-fed E-step; em_step: the fused kernel (scalar-register feed)
     (4, 3, 5000),        # fused small-shape kernel
     (150, 3, 1500),      # plain tier (d > 128)
 ])

@@ -394,6 +394,167 @@ def test_tied_fp64_restatement_and_many_tile_shapes():
         assert n == rows and (n + 63) // 64 > 2 * 4 * grid == 2 * 4 * hp_cases.tied_grid(d, K, n, 256)
 
 
+# ---- the inputs of tests/test_gpu_hp_edges.py: what each kind needs of its data -----------------------------------------------
+
+EDGE_CASES = ([(s, False) for s in hp_cases.EDGE_SHAPES + hp_cases.EDGE_LOOP_SHAPES] + [(s, True) for s in hp_cases.EDGE_DIAG_SHAPES])
+EDGE_IDS = [f"d={s[0]}-K={s[1]}{'-diag' if dg else ''}" for s, dg in EDGE_CASES]
+
+
+@pytest.mark.parametrize("shape,diagonal", EDGE_CASES, ids=EDGE_IDS)
+@pytest.mark.parametrize("kind", hp_cases.MASSLESS_KINDS)
+def test_massless_kinds_give_the_documented_pattern(kind, shape, diagonal):
+    """Reference and oracle agree on the massless component -- responsibilities exactly 0 (in long double too), pi_k = 0, mu_k and
+    Sigma_k / var_k NaN throughout, everything else finite --, the oracle's live part keeps its bound, and a `hole` sits at reach
+    0 with the other components inside the guard of the fast density form."""
+    from oracle import oracle_ctypes as orc
+    d, K, n, _ = shape
+    X, pi0, mu0, S0, k = hp_cases.massless_problem(kind, *shape, diagonal)
+    live = np.array([j for j in range(K) if j != k])
+    ref = (hp.em_step_diag if diagonal else hp.em_step)(X, pi0, mu0, S0)
+    with np.errstate(all="ignore"):
+        cpu = oracle_step(orc, X, pi0, mu0, S0, diagonal)
+    assert not ref[1][:, k].any() and not np.asarray(cpu[1])[:, k].any()
+    assert hp_cases.massless_pattern(ref, k) and hp_cases.massless_pattern(cpu, k)
+    key = "variances" if diagonal else "covs"
+    cond = hp.conditioning(X.astype(LD).mean(axis=0), mu0, **{key: S0})
+    part = lambda s: (s[0], s[1], np.asarray(s[2])[live], np.asarray(s[3])[live], np.asarray(s[4])[live])   # noqa: E731
+    for name, (err, unit) in step_errors(part(cpu), part(ref), cond["kappa"][live], n).items():
+        print(f"{kind} d={d} K={K} diag={diagonal} {name}: err {err:.2e} = {err / unit:.3f} units of {unit:.2e}")
+        assert err <= C_ORACLE * unit, name
+    if kind == "far":
+        assert cond["b2"][k] > 64.0 ** 2 and (diagonal or cond["fold"][k] > 64)
+    if kind == "hole":
+        reach = cond["b2"] if diagonal else cond["fold"]
+        assert reach[k] <= 1e-9 and reach[live].max() <= (64.0 ** 2 if diagonal else 64.0)
+        whiten = np.sqrt(S0[k].min()) if diagonal else np.sqrt(S0[k][0, 0])
+        assert np.linalg.norm(X - X.mean(axis=0), axis=1).min() / whiten >= hp_cases.HOLE_UNITS * (1 - 1e-12)
+
+
+@pytest.mark.parametrize("shape,diagonal", [c for c in EDGE_CASES if c[0] not in hp_cases.EDGE_LOOP_SHAPES],
+                         ids=[i for c, i in zip(EDGE_CASES, EDGE_IDS) if c[0] not in hp_cases.EDGE_LOOP_SHAPES])
+def test_tail_rows_are_decided_by_their_own_component(shape, diagonal):
+    """Each moved row: won by the component it was moved behind, at a log-weight in (-900, -750) -- below the underflow of a
+    linear-domain density, so the oracle's log-likelihood is not finite --, the runner-up at least TAIL_GAP = 8 below: an error
+    delta in that row's log-weights moves a responsibility by at most e^-8 delta. The window is hp_cases.tail_window(d), the one
+    the generator selects by: at d = 136 the density's constant -d/2 log 2 pi = -125 alone puts the same 40 whitened units at
+    -943, and the window is (-950, -750) there. With K above the number of rows
+    (diagonal K = 40) only the rows that meet this are moved, at least 8 of them."""
+    from oracle import oracle_ctypes as orc
+    d, K, n, _ = shape
+    X, pi0, mu0, S0, rows, comps = hp_cases.tail_problem(*shape, diagonal, only_clear=K > hp_cases.TAIL_ROWS)
+    assert len(rows) == hp_cases.TAIL_ROWS or (K > hp_cases.TAIL_ROWS and len(rows) >= 8)
+    assert np.array_equal(comps, np.arange(hp_cases.TAIL_ROWS)[:len(comps)] % K) or K > hp_cases.TAIL_ROWS
+    top, gap, winner = hp_cases.tail_row_margins(X[rows], pi0, mu0, S0, diagonal)
+    print(f"tail d={d} K={K} diag={diagonal}: {len(rows)} rows, log-weight {top.min():.1f} .. {top.max():.1f}, smallest gap {gap.min():.3g}")
+    assert hp_cases.tail_window(d) == ((-950.0, -750.0) if d == 136 else (-900.0, -750.0))
+    assert all(hp_cases.tail_row_is_clear(k, t, g, w, d) for k, t, g, w in zip(comps, top, gap, winner))
+    assert np.array_equal(winner, comps) and gap.min() >= hp_cases.TAIL_GAP
+    L = hp_cases._factors(S0, diagonal)
+    for row, k in zip(rows, comps):
+        assert abs(np.linalg.norm(np.linalg.solve(L[k], X[row] - mu0[k])) - 40) < 1e-9
+    with np.errstate(all="ignore"):
+        assert not np.isfinite(oracle_step(orc, X, pi0, mu0, S0, diagonal)[0])
+    ref = (hp.em_step_diag if diagonal else hp.em_step)(X, pi0, mu0, S0)
+    assert np.isfinite(float(ref[0])) and hp.abs_err(ref[1].sum(axis=1), np.ones(n)) < 1e-18
+    assert np.array_equal(ref[1][rows].argmax(axis=1), comps)
+
+
+@pytest.mark.parametrize("shape", hp_cases.EDGE_WEIGHTED_SHAPES, ids=[f"d={s[0]}" for s in hp_cases.EDGE_WEIGHTED_SHAPES])
+def test_zero_weight_rows_leave_a_live_component_without_weighted_mass(shape):
+    from test_weights_cases import replicate, weights
+    d, K, n, _ = shape
+    X, w, pi0, mu0, S0, rows = hp_cases.zero_weight_rows_problem(*shape, weights(n))
+    assert len(rows) == hp_cases.ZERO_ROWS and not w[rows].any() and np.array_equal(np.delete(w, rows), np.delete(weights(n), rows))
+    block = hp.em_step(X, pi0, mu0, S0)
+    assert np.all(block[1][rows, K - 1] == 1) and block[2][K - 1] > 0            # alive on the block ...
+    ref = hp.em_step(replicate(X, w), pi0, mu0, S0)
+    assert not ref[1][:, K - 1].any() and hp_cases.massless_pattern(ref, K - 1)   # ... exactly massless on the weighted sample
+
+
+@pytest.mark.parametrize("d,first", hp_cases.MASSLESS_REFINEMENT_CASES)
+def test_massless_refinement_problem_has_one_live_component_above_the_guard(d, first):
+    from oracle import oracle_ctypes as orc
+    X, pi0, mu0, S0, k = hp_cases.massless_refinement_problem(d, 1.1e4, first)
+    assert pi0[k] == 0 and abs(pi0.sum() - 1) < 1e-15
+    ref = hp.em_step(X, pi0, mu0, S0)
+    with np.errstate(all="ignore"):
+        assert hp_cases.massless_pattern(ref, k) and hp_cases.massless_pattern(oracle_step(orc, X, pi0, mu0, S0), k)
+    live = [j for j in range(3) if j != k]
+    ratio = hp.conditioning(X.astype(LD).mean(axis=0), ref[3][live], covs=ref[4][live])["ratio"]
+    assert (ratio > 1e4).tolist() == [False, True] and abs(ratio[1] / 1.1e4 - 1) < 0.02, ratio
+
+
+@pytest.mark.parametrize("kind,shape,diagonal", [("zero_weight_last", (16, 8, 4001, 2.0), False), ("zero_weight_first", (72, 2, 2501, 0.0), False),
+                                                 ("zero_weight_last", (16, 8, 4001, 0.5), True), ("zero_weight_first", (8, 5, 3001, 3.0), False),
+                                                 ("zero_weight_last", (2, 3, 3001, 0.0), False)])
+def test_a_second_step_after_a_component_died_is_nan_throughout(kind, shape, diagonal):
+    """What the loop cases of tests/test_gpu_hp_edges.py expect of two iterations: the oracle's second E-step meets log 0 + NaN in
+    every row."""
+    from oracle import oracle_ctypes as orc
+    X, pi0, mu0, S0, k = hp_cases.massless_problem(kind, *shape, diagonal)
+    em = orc.EM(len(pi0))
+    if diagonal:
+        em.set_covariance_type("diag")
+    em.set_parameters(mu0, np.stack([np.diag(v) for v in S0]) if diagonal else S0, pi0)
+    with np.errstate(all="ignore"):
+        em.expectation_step(X)
+        first = em.log_likelihood
+        em.maximisation_step(X)
+        em.expectation_step(X)
+        second = em.log_likelihood
+        em.maximisation_step(X)
+    assert np.isfinite(first) and np.isnan(second)
+    assert np.isnan(em.mixing_probabilities).all() and np.isnan(em.means).all() and np.isnan(em.covariances).all()
+
+
+def test_edge_checkers_reject_fabricated_results():
+    """The checkers of tests/test_gpu_hp_edges.py (tests/hp_limits.py) on results made up from the reference: the reference rounded
+    to fp64 passes; the empty component's mean 0 instead of NaN, a NaN in a live component and a log-likelihood that lost one
+    tail row's term do not."""
+    from hp_limits import check_massless, check_tail, edge_references
+    shape = (2, 3, 3001, 0.0)
+    X, pi0, mu0, S0, k = hp_cases.massless_problem("zero_weight_last", *shape)
+    refs = edge_references(X, pi0, mu0, S0, k, False)
+    ref = refs["ref"]
+    fp64 = lambda: [float(ref[0])] + [np.array(a, dtype=np.float64) for a in ref[1:]]   # noqa: E731
+    labels = np.asarray(ref[1], dtype=np.float64).argmax(axis=1)
+    check_massless("the reference in fp64", tuple(fp64()), labels, refs, 0)
+    wrong = fp64()
+    wrong[3][k] = 0.0
+    with pytest.raises(AssertionError):
+        check_massless("mean 0 for the empty component", tuple(wrong), labels, refs, 0)
+    wrong = fp64()
+    wrong[3][0, 1] = np.nan
+    with pytest.raises(AssertionError):
+        check_massless("NaN in a live component", tuple(wrong), labels, refs, 0)
+    wrong = fp64()
+    wrong[4][1, 0, 1] = np.nan
+    with pytest.raises(AssertionError):
+        check_massless("NaN in a live covariance", tuple(wrong), labels, refs, 0)
+    wrong = fp64()
+    wrong[1][5, k] = 1e-300
+    with pytest.raises(AssertionError):
+        check_massless("a responsibility of the empty component not exactly 0", tuple(wrong), labels, refs, 0)
+    X, pi0, mu0, S0, rows, comps = hp_cases.tail_problem(*shape)
+    refs = edge_references(X, pi0, mu0, S0, None, False)
+    ref = refs["ref"]
+    labels = np.asarray(ref[1], dtype=np.float64).argmax(axis=1)
+    check_tail("the reference in fp64", tuple(fp64()), labels, refs, rows, comps, 0)
+    lse = hp._normalise(hp.log_weights(X[rows[:1]], pi0, mu0, S0))[1]
+    wrong = fp64()
+    wrong[0] = float(ref[0] - lse[0] / len(X))
+    with pytest.raises(AssertionError):
+        check_tail("one tail row's term dropped", tuple(wrong), labels, refs, rows, comps, 0)
+    wrong = fp64()
+    wrong[0] = -np.inf
+    with pytest.raises(AssertionError):
+        check_tail("a log-sum-exp lost", tuple(wrong), labels, refs, rows, comps, 0)
+    other = labels.copy()
+    other[rows[0]] = (comps[0] + 1) % 3
+    with pytest.raises(AssertionError):
+        check_tail("a moved row with another label", tuple(fp64()), other, refs, rows, comps, 0)
+
+
 # ---- the comparison helper ------------------------------------------------------------------------------------------------
 
 def test_comparison_helper_tells_a_lost_digit_from_rounding_noise():
