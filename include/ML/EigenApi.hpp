@@ -114,11 +114,24 @@ public:
     KMeans(const KMeans&) = delete;
     KMeans& operator=(const KMeans&) = delete;
 
-    bool fit(Eigen::Ref<const Eigen::MatrixXd> data) override
+    bool fit(Eigen::Ref<const Eigen::MatrixXd> data) override { return fit_block(data, nullptr); }
+    /** Extension: the fit of a weighted sample (ml::Clustering::KMeans::fit(data, weights) of ML/KMeans.hpp): weights(i) >= 0 is the
+    frequency weight of column i. @throw std::invalid_argument If `weights.size() != data.cols()` or the weights are refused. */
+    bool fit(Eigen::Ref<const Eigen::MatrixXd> data, Eigen::Ref<const Eigen::VectorXd> weights)
+    {
+        if (weights.size() != data.cols()) throw std::invalid_argument("KMeans: One weight per data point required");
+        return fit_block(data, weights.data());                      // (a Ref<const VectorXd> is contiguous)
+    }
+
+private:
+    bool fit_block(Eigen::Ref<const Eigen::MatrixXd> data, const double* weights)
     {
         const detail::Block block(data);
         int converged = 0;
-        detail::check(mlpp_kmeans_fit(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()), &converged));
+        const uint64_t n = static_cast<uint64_t>(data.cols());
+        const uint32_t dims = static_cast<uint32_t>(data.rows());
+        detail::check(weights ? mlpp_kmeans_fit_weighted(h_, block.p, weights, n, dims, &converged)
+                              : mlpp_kmeans_fit(h_, block.p, n, dims, &converged));
         centroids_.resize(data.rows(), number_clusters_);
         detail::check(mlpp_kmeans_centroids(h_, centroids_.data()));
         labels_.resize(static_cast<std::size_t>(data.cols()));
@@ -128,6 +141,8 @@ public:
         converged_ = converged != 0;
         return converged_;
     }
+
+public:
     unsigned int number_clusters() const override { return number_clusters_; }
     const std::vector<unsigned int>& labels() const override { return labels_; }
     const Eigen::MatrixXd& centroids() const override { return centroids_; }

@@ -29,6 +29,14 @@ public:
     KMeans& operator=(const KMeans&) = delete;
 
     DLL_DECLSPEC bool fit(ConstMatrixRef data) override;
+    /** Extension (not in the reference surface): the same fit of a WEIGHTED sample -- `weights[i]` >= 0 is the frequency weight of
+    column i of `data` (integer weights: the fit of the sample with point i repeated weights[i] times, without the copies). Every
+    update forms the weighted means sum_i w_i x_i / sum_i w_i (a cluster of total weight 0 goes to the origin, like an empty one);
+    inertia() is sum_i w_i dist_i, accumulated sequentially in point order, and is what the initialisations are compared by;
+    labels() cover every point; the initialisers see points, not weights; the N < K and N == K branches count points
+    (mlhip_kmeans_step_weighted). All arguments are checked before any device work.
+    @throw std::invalid_argument If `weights.size() != data.cols()`, a weight is negative or not finite, or their total is not positive. */
+    DLL_DECLSPEC bool fit(ConstMatrixRef data, ConstVectorRef weights);
     unsigned int number_clusters() const override { return num_clusters_; }
     const std::vector<unsigned int>& labels() const override { return labels_; }
     const MatrixXd& centroids() const override { return centroids_; }
@@ -69,7 +77,9 @@ private:
     unsigned int steps_done_;
     bool verbose_;
     bool converged_;
+    const double* fit_weights_ = nullptr;   // the weights of the fit in progress (null: unweighted)
 
+    bool fit_impl(ConstMatrixRef data);
     /// exact_fit: the WHOLE sample has exactly K rows (one cluster per sample, ML/KMeans.cpp:67-75).
     bool fit_once(ConstMatrixRef data, mlhip_data* device_data, bool exact_fit);
     void fetch_assignment(mlhip_data* device_data, std::size_t sample_size);

@@ -141,8 +141,9 @@ int mlhip_data_shift(const mlhip_data* data, double* shift);
  * With integer weights this is the unweighted result on the sample with row i repeated w_i times; scaling all weights by a constant
  * changes nothing beyond rounding. NOT weighted: per-row results (mlhip_em_responsibilities, mlhip_em_labels, mlhip_em_score: a row
  * of weight 0 still gets its responsibilities, its label and its density), the statistics shift (mlhip_data_shift stays the plain
- * column mean), mlhip_xxt_xy, mlhip_random_partition_means, and every K-means and kpp_* entry point (their sums are exact
- * integer-limb accumulations a product w x does not live on): K-means and the initialisers see rows, not weights.
+ * column mean), mlhip_xxt_xy, mlhip_random_partition_means, mlhip_kmeans_step / _iterate / _assign and every kpp_* entry point:
+ * they and the initialisers see rows, not weights, on a weighted handle too (a weighted EM fit with a K-means++ start relies on
+ * that). The weighted K-means is a set of entry points of its own: mlhip_kmeans_step_weighted / _iterate_weighted / _assign_weighted.
  * A weighted block runs the E-step tier of its shape; where the unweighted fit runs the self-normalising statistics form (d = 12 ..
  * 128, K <= 64) so does the weighted one, with the weight applied while the kernel stages a responsibility (one exponential per pair,
  * no second N x K block); elsewhere one pass writes w_i r_ik for the statistics kernel of the shape. It never takes the fused,
@@ -303,6 +304,26 @@ int mlhip_kmeans_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* c
 /* Assignment only (KMeans::assignment_step, :167-178): labels + inertia, no update. */
 int mlhip_kmeans_assign(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids,
                         double* inertia, uint64_t* n_changed);
+/* EXTENSION (no counterpart in the reference): Lloyd's algorithm on a WEIGHTED sample -- the three calls above with the row weights
+ * attached by mlhip_data_set_weights (MLHIP_E_INVALID_ARGUMENT without them), same signatures:
+ *   *inertia = sum_i w_i min_k |x_i - c_k|^2 ; counts[k] = sum of the weights of cluster k's rows ; centroids_out = the weighted means
+ *   sum_i w_i x_i / sum_i w_i per cluster, a cluster of total weight 0 (empty, or rows of weight 0 only) at the origin.
+ * Labels, per-row distances (mlhip_kmeans_labels / _distances) and *n_changed (a count of ROWS) do not depend on the weights: they
+ * are, bit for bit, those of the unweighted call -- the assignment kernel of the shape's route runs unchanged, without its own
+ * accumulation, and one more sweep over X, the labels, the distances and the weights forms the sums (device/kmeans_weighted.hip); the
+ * weighted iterate never takes the one-launch resident loop. With integer weights the results are those of the unweighted calls on
+ * the sample with row i repeated w_i times. The sums are exact sums of the rounded products w_i x_ij on a fixed-point grid set by the
+ * largest weight and the largest |x_j| of the WHOLE sample (exchanged across ranks, cached on the handle until the weights change),
+ * so they do not depend on the summation order, the grid or the number of shards; a product below 2^-94 max w max|x_j| contributes
+ * nothing, likewise a weight below 2^-94 max w to the counts. MLHIP_E_DOMAIN when max w * max|x_j| overflows (the handle stays usable).
+ * mlhip_kmeans_assign_weighted is the assignment plus an inertia-only sweep. */
+int mlhip_kmeans_step_weighted(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids,
+                               double* inertia, uint64_t* n_changed, double* counts, double* centroids_out);
+int mlhip_kmeans_iterate_weighted(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* centroids, double* old_centroids,
+                                  uint32_t max_steps, double absolute_tolerance, uint32_t* steps_done, int* converged,
+                                  double* inertia, double* counts);
+int mlhip_kmeans_assign_weighted(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids,
+                                 double* inertia, uint64_t* n_changed);
 int mlhip_kmeans_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t* labels);
 /* Per-sample squared distance to the assigned centroid from the last assignment (n_local doubles): the very values
  * KMeans::assign_label returns (:153-165), so a caller can re-create the reference's sequential inertia sum (:176). */

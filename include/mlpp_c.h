@@ -88,6 +88,9 @@ int mlpp_kmeans_set_number_initialisations(mlpp_kmeans* h, uint32_t v);
 int mlpp_kmeans_set_centroids_initialiser(mlpp_kmeans* h, const mlpp_centroids_initialiser* init);
 int mlpp_kmeans_set_verbose(mlpp_kmeans* h, int v);
 int mlpp_kmeans_fit(mlpp_kmeans* h, const double* data, uint64_t n, uint32_t d, int* converged);
+/* Extension (ml::Clustering::KMeans::fit(data, weights)): the fit of a weighted sample, weights[i] >= 0 the frequency weight of point i
+ * (n values); checked before any device work. */
+int mlpp_kmeans_fit_weighted(mlpp_kmeans* h, const double* data, const double* weights, uint64_t n, uint32_t d, int* converged);
 int mlpp_kmeans_number_clusters(const mlpp_kmeans* h, uint32_t* out);
 int mlpp_kmeans_dims(const mlpp_kmeans* h, uint32_t* d, uint64_t* n);
 int mlpp_kmeans_centroids(const mlpp_kmeans* h, double* out /* K x d row-major == d x K column-major */);

@@ -326,7 +326,8 @@ class Data:
         """Frequency weights of the block's rows (mlhip_data_set_weights): a 1-D C-contiguous float64 array of length N, every
         value finite and >= 0, their total positive; None removes them. TypeError for another type or dtype, ValueError for a
         wrong length or refused values (the block is then unweighted). EM entry points are weighted from here on; per-row
-        results (responsibilities, labels, em_score), K-means and the initialisers are not."""
+        results (responsibilities, labels, em_score), the initialisers and the K-means calls are not -- unless those are called
+        with weighted=True."""
         if w is not None:
             w = require_weights(w, self.n)
         check(lib.mlhip_data_set_weights(self.ctx.handle, self._h, None if w is None else dptr(w)))
@@ -506,32 +507,39 @@ class Data:
         return mean, cov
 
     # ---- K-means --------------------------------------------------------------------------------------------
-    def kmeans_step(self, centroids):
+    def kmeans_step(self, centroids, weighted=False):
+        """One Lloyd step: (inertia, n_changed, counts, centroids). weighted=True: mlhip_kmeans_step_weighted on the attached
+        weights (set_weights) -- weighted inertia, counts and means; n_changed, labels and distances stay per row."""
         centroids = np.ascontiguousarray(centroids, dtype=np.float64)
         K = centroids.shape[0]
         inertia, changed = C.c_double(), C.c_uint64()
         counts, cout = np.empty(K), np.empty((K, self.d))
-        check(lib.mlhip_kmeans_step(self.ctx.handle, self._h, K, dptr(centroids), C.byref(inertia), C.byref(changed),
+        step = lib.mlhip_kmeans_step_weighted if weighted else lib.mlhip_kmeans_step
+        check(step(self.ctx.handle, self._h, K, dptr(centroids), C.byref(inertia), C.byref(changed),
                                     dptr(counts), dptr(cout)))
         return inertia.value, changed.value, counts, cout
 
-    def kmeans_iterate(self, centroids, max_steps, atol=0.0):
+    def kmeans_iterate(self, centroids, max_steps, atol=0.0, weighted=False):
         """The step loop of KMeans::fit_once in one call (mlhip_kmeans_iterate): the centroid table stays on the device
-        between steps. Returns (steps_done, converged, inertia, counts, centroids, old_centroids)."""
+        between steps. Returns (steps_done, converged, inertia, counts, centroids, old_centroids). weighted=True: the loop of
+        weighted steps (mlhip_kmeans_iterate_weighted)."""
         cur = np.array(centroids, dtype=np.float64, order="C")
         K = cur.shape[0]
         assert cur.shape == (K, self.d)
         old, counts = np.zeros((K, self.d)), np.zeros(K)
         steps, conv, inertia = C.c_uint32(), C.c_int(), C.c_double()
-        check(lib.mlhip_kmeans_iterate(self.ctx.handle, self._h, K, dptr(cur), dptr(old), C.c_uint32(max_steps), C.c_double(atol),
-                                       C.byref(steps), C.byref(conv), C.byref(inertia), dptr(counts)))
+        iterate = lib.mlhip_kmeans_iterate_weighted if weighted else lib.mlhip_kmeans_iterate
+        check(iterate(self.ctx.handle, self._h, K, dptr(cur), dptr(old), C.c_uint32(max_steps), C.c_double(atol),
+                      C.byref(steps), C.byref(conv), C.byref(inertia), dptr(counts)))
         return steps.value, bool(conv.value), inertia.value, counts, cur, old
 
-    def kmeans_assign(self, centroids):
+    def kmeans_assign(self, centroids, weighted=False):
+        """Assignment only: (inertia, n_changed). weighted=True: the weighted inertia (mlhip_kmeans_assign_weighted)."""
         centroids = np.ascontiguousarray(centroids, dtype=np.float64)
         K = centroids.shape[0]
         inertia, changed = C.c_double(), C.c_uint64()
-        check(lib.mlhip_kmeans_assign(self.ctx.handle, self._h, K, dptr(centroids), C.byref(inertia), C.byref(changed)))
+        assign = lib.mlhip_kmeans_assign_weighted if weighted else lib.mlhip_kmeans_assign
+        check(assign(self.ctx.handle, self._h, K, dptr(centroids), C.byref(inertia), C.byref(changed)))
         return inertia.value, changed.value
 
     def kmeans_labels(self):

@@ -8,7 +8,8 @@ Conventions kept from the reference:
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
 Extensions (not in the reference surface): `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
-`KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`.
+`KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
+`KMeans.fit(..., sample_weight=)`.
 """
 import ctypes as C
 
@@ -376,12 +377,22 @@ class KMeans:
         """Turns on/off the verbose mode."""
         _check(_l.mlpp_kmeans_set_verbose(self._h, int(bool(verbose))))
 
-    def fit(self, data):
-        """Fits the clusters to the data (2D array with data points in rows). Returns True if the algorithm converged."""
+    def fit(self, data, sample_weight=None):
+        """Fits the clusters to the data (2D array with data points in rows). Returns True if the algorithm converged.
+
+        Extension: `sample_weight`, a 1-D C-contiguous float64 array with one frequency weight >= 0 per row (integer weights: the
+        fit of the data with row i repeated sample_weight[i] times, without the copies). TypeError for another type or dtype,
+        ValueError for a wrong length, a negative or non-finite weight or a total that is not positive -- all before any device
+        work. Centroids are weighted means (a cluster of total weight 0 goes to the origin), `inertia` is sum_i w_i dist_i;
+        `labels` stay per row; initialisers see rows, not weights."""
         data = _require_data(data)
         n, d = data.shape
         conv = C.c_int()
-        _check(_l.mlpp_kmeans_fit(self._h, _dp(data), C.c_uint64(n), d, C.byref(conv)))
+        if sample_weight is None:
+            _check(_l.mlpp_kmeans_fit(self._h, _dp(data), C.c_uint64(n), d, C.byref(conv)))
+        else:
+            w = _lib.require_weights(sample_weight, n)
+            _check(_l.mlpp_kmeans_fit_weighted(self._h, _dp(data), _dp(w), C.c_uint64(n), d, C.byref(conv)))
         return bool(conv.value)
 
     def _dims(self):

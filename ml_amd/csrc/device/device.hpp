@@ -343,4 +343,21 @@ void launch_kmeans_reduce(const KmeansArgs& a, int n_partials, hipStream_t strea
 /// through a copy engine and costs more than the kernel itself.
 void launch_kmeans_close(double* out, int K, int d, int D, double* next, double* mirror, hipStream_t stream);
 
+/// Weighted update sweep + its reduction (kmeans_weighted.hip), after an assignment that ran with accumulate = 0: out[0] becomes the
+/// weighted inertia sum_i w_i min_dist_i and, with_sums != 0, out[2 ..] the weighted counts sum_i w_i (K) and the sums sum_i w_i x_i
+/// (K*d), exact sums of the rounded products; out[1] (n_changed) is not touched. `factors` (device, 2d + 2 doubles, powers of two):
+/// [f1 (d) | f2 (d) | c1 | c2] with f1_j f2_j = 2^(94 - ej - ew) and c1 c2 = 2^(94 - ew), max|x_j| < 2^ej, max w < 2^ew over all
+/// ranks. xt is the UNPADDED block. Returns the partial blocks used, -2 if the scratch is too small.
+struct KmWeightedArgs {
+    const double* xt; size_t ldx; uint32_t n; int d;
+    const uint32_t* labels; const double* min_dist;       // of the assignment just run
+    const double* weights;                                 // n_pad doubles, zero beyond n
+    const double* factors;
+    int K; int with_sums;
+    double* partials; size_t partials_capacity;
+    double* out;
+};
+size_t kmeans_weighted_scratch_doubles(int d, int K, int num_cus);
+int launch_kmeans_weighted(const KmWeightedArgs& a, int num_cus, hipStream_t stream);
+
 }  // namespace mlhip

@@ -129,12 +129,39 @@ void KMeans::sequential_inertia(mlhip_data* device_data, std::size_t sample_size
         std::vector<double> dist(sample_size);
         check(mlhip_kmeans_distances(ctx, device_data, dist.data()));
         double total = 0;
-        for (double v : dist) total += v;
+        if (fit_weights_) {
+            for (std::size_t i = 0; i < sample_size; ++i) total += fit_weights_[i] * dist[i];   // (the weighted form, same order)
+        } else {
+            for (double v : dist) total += v;
+        }
         inertia_ = total;
     }
 }
 
-bool KMeans::fit(ConstMatrixRef data)
+bool KMeans::fit(ConstMatrixRef data) { return fit_impl(data); }
+
+bool KMeans::fit(ConstMatrixRef data, ConstVectorRef weights)
+{
+    if (weights.size() != data.cols()) throw std::invalid_argument("KMeans: One weight per data point required");
+    double total = 0;
+    for (Index i = 0; i < weights.size(); ++i) {
+        if (!(weights[i] >= 0) || !std::isfinite(weights[i])) throw std::invalid_argument("KMeans: weights must be finite and >= 0");
+        total += weights[i];
+    }
+    // (a row-sharded job's total is over ALL ranks: mlhip_data_set_weights checks it there, the same verdict on every rank)
+    int world = 1;
+    if (mlhip_ctx* shared = device::peek_context()) check(mlhip_ctx_world(shared, &world, nullptr));
+    if (world == 1 && (!(total > 0) || !std::isfinite(total)))
+        throw std::invalid_argument("KMeans: the weights' total must be positive and finite");
+    struct Reset {
+        const double*& p;
+        ~Reset() { p = nullptr; }
+    } reset{fit_weights_};
+    fit_weights_ = weights.data();
+    return fit_impl(data);
+}
+
+bool KMeans::fit_impl(ConstMatrixRef data)
 {
     const auto number_dimensions = static_cast<unsigned int>(data.rows());
     const auto sample_size = static_cast<unsigned int>(data.cols());
@@ -157,6 +184,8 @@ bool KMeans::fit(ConstMatrixRef data)
         check(mlhip_data_shape(dev.h, nullptr, nullptr, &n_global));
         if (n_global < num_clusters_) throw std::invalid_argument("KMeans: Not enough data ");   // the same on every rank
     }
+    // Row weights stay attached for the handle's lifetime; the initialisers and mlhip_kmeans_labels / _distances see rows.
+    if (fit_weights_ && dev.h) check(mlhip_data_set_weights(device::context(), dev.h, fit_weights_));
     const bool exact_fit = n_global == num_clusters_;
 
     if (num_inits_ == 1 || exact_fit) {
@@ -180,7 +209,8 @@ bool KMeans::fit(ConstMatrixRef data)
         centroids_ = best_centroids;
         if (dev.h) {
             uint64_t changed = 0;
-            check(mlhip_kmeans_assign(device::context(), dev.h, num_clusters_, centroids_.data(), &inertia_, &changed));
+            check((fit_weights_ ? mlhip_kmeans_assign_weighted : mlhip_kmeans_assign)(device::context(), dev.h, num_clusters_,
+                                                                                      centroids_.data(), &inertia_, &changed));
         }
     }
     if (dev.h) fetch_assignment(dev.h, sample_size);
@@ -229,8 +259,9 @@ bool KMeans::fit_once(ConstMatrixRef data, mlhip_data* device_data, const bool e
         // arithmetic and the same decisions as the loop below, which prints the centroids of every step).
         uint32_t steps = 0;
         int converged = 0;
-        check(mlhip_kmeans_iterate(ctx, device_data, K, centroids_.data(), old_centroids_.data(), maximum_steps_, absolute_tolerance_,
-                                   &steps, &converged, &inertia_, work_vector_.data()));
+        check((fit_weights_ ? mlhip_kmeans_iterate_weighted : mlhip_kmeans_iterate)(ctx, device_data, K, centroids_.data(),
+                                                                                    old_centroids_.data(), maximum_steps_, absolute_tolerance_,
+                                                                                    &steps, &converged, &inertia_, work_vector_.data()));
         steps_done_ = steps;
         converged_ = converged != 0;
         sequential_inertia(device_data, sample_size);
@@ -241,7 +272,8 @@ bool KMeans::fit_once(ConstMatrixRef data, mlhip_data* device_data, const bool e
     for (unsigned int step = 0; step < maximum_steps_; ++step) {
         // Assignment + the per-cluster sums of the update in one pass over the resident data.
         uint64_t changed = 0;
-        check(mlhip_kmeans_step(ctx, device_data, K, centroids_.data(), &inertia_, &changed, work_vector_.data(), updated.data()));
+        check((fit_weights_ ? mlhip_kmeans_step_weighted : mlhip_kmeans_step)(ctx, device_data, K, centroids_.data(), &inertia_, &changed,
+                                                                              work_vector_.data(), updated.data()));
         ++steps_done_;
 
         if (step > 0 && changed == 0) {   // same labels twice (ML/KMeans.cpp:84-89): centroids stay as they are
@@ -269,7 +301,8 @@ bool KMeans::fit_once(ConstMatrixRef data, mlhip_data* device_data, const bool e
                 centroid_shift += delta * delta;
             }
             if (centroid_shift < absolute_tolerance_) {
-                check(mlhip_kmeans_assign(ctx, device_data, K, centroids_.data(), &inertia_, &changed));
+                check((fit_weights_ ? mlhip_kmeans_assign_weighted : mlhip_kmeans_assign)(ctx, device_data, K, centroids_.data(), &inertia_,
+                                                                                          &changed));
                 converged_ = true;
                 break;
             }

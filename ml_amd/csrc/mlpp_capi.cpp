@@ -209,6 +209,17 @@ int mlpp_kmeans_fit(mlpp_kmeans* h, const double* data, uint64_t n, uint32_t d, 
         *converged = ok ? 1 : 0;
     });
 }
+int mlpp_kmeans_fit_weighted(mlpp_kmeans* h, const double* data, const double* weights, uint64_t n, uint32_t d, int* converged)
+{
+    return guarded([&] {
+        need(h); need(converged);
+        if (n && d) need(data);
+        if (n) need(weights);
+        const bool ok = h->km.fit(ConstMatrixRef(data, d, static_cast<Index>(n)), ConstVectorRef(weights, static_cast<Index>(n)));
+        h->d = d; h->n = static_cast<Index>(n);
+        *converged = ok ? 1 : 0;
+    });
+}
 int mlpp_kmeans_number_clusters(const mlpp_kmeans* h, uint32_t* out) { return guarded([&] { need(h); need(out); *out = h->km.number_clusters(); }); }
 int mlpp_kmeans_dims(const mlpp_kmeans* h, uint32_t* d, uint64_t* n) { return guarded([&] { need(h); if (d) *d = static_cast<uint32_t>(h->km.centroids().rows()); if (n) *n = static_cast<uint64_t>(h->km.labels().size()); }); }
 int mlpp_kmeans_centroids(const mlpp_kmeans* h, double* out) { return guarded([&] { need(h); need(out); std::copy_n(h->km.centroids().data(), h->km.centroids().size(), out); }); }

@@ -248,6 +248,7 @@ int mlhip_data_set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weigh
         data->weight_sum = 0;
         data->wresp.release();                                 // (sized again by the next weighted statistics pass)
         data->total_scatter.clear();                           // (the tied mode's sum_i w_i xt_i xt_i^T: formed again on demand)
+        data->km_wfactors_valid = false;                       // (weighted K-means: the factors follow the largest weight)
         if (!weights) {
             data->weights.release();
             return;

@@ -513,6 +513,12 @@ struct mlhip_data {
     PinnedBuf fp_host{&pool};              // its read-back slots
     int km_cur = 0;
     bool km_have_old = false;
+    // Weighted K-means (mlhip_kmeans_*_weighted): max|x_j| over ALL ranks as ensure_km_workspace found it (d doubles, host), and the
+    // power-of-two factors of the weighted exact sums (KmWeightedArgs::factors), derived once per weight vector from the largest
+    // weight of the whole sample; mlhip_data_set_weights drops them.
+    std::vector<double> km_colmax;
+    DevBuf km_wfactors{&pool};
+    bool km_wfactors_valid = false;
 
     mlhip_data() = default;
     mlhip_data(const mlhip_data&) = delete;      // (the buffers point at this object's pool field)
@@ -716,13 +722,22 @@ void km_upload_centroids(mlhip_data* dt, int K, const KmBlock& b, const double* 
 
 /// Assignment (+ optional accumulation) against the table in km_cent, partials reduced into km_out =
 /// [inertia, changed, counts, sums] and summed across ranks there when the all-reduce works on device memory.
-void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool accumulate, double* min_dist_out);
+/// `weighted`: the assignment runs with accumulate = 0 and the weighted sweep (device/kmeans_weighted.hip) follows it: km_out then
+/// holds the weighted inertia, the row count n_changed, the weighted counts and sums sum_i w_i x_i (ensure_km_weighted first).
+void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool accumulate, double* min_dist_out, bool weighted = false);
 
 /// km_out -> km_host (`count` doubles), summed across ranks on the host when the all-reduce works on host memory.
 void km_fetch(mlhip_data* dt, size_t count);
 
 /// Assignment (+ optional accumulation); leaves all-reduced [inertia, changed, counts, sums] in km_host.
-void run_kmeans(mlhip_data* dt, const KmRoute& r, int K, const double* centroids, bool accumulate, double* min_dist_out = nullptr);
+void run_kmeans(mlhip_data* dt, const KmRoute& r, int K, const double* centroids, bool accumulate, double* min_dist_out = nullptr,
+                bool weighted = false);
+
+/// What a weighted K-means call on a block with weights attached needs on top of ensure_km_workspace: the factors of the
+/// weighted exact sums (derived from the largest weight of the whole sample, exchanged across ranks like the column maxima; cached
+/// until mlhip_data_set_weights), the partial-block scratch sized for 3d + 3 words per cluster. DomainError when max w * max|x_j|
+/// overflows for some dimension j (the handle stays usable).
+void ensure_km_weighted(mlhip_data* dt, int K);
 
 /// update_step's closing arithmetic on the host (ML/KMeans.cpp:180-192 as sums / counts; empty cluster -> origin, :184).
 void km_close_host(const double* r, int K, int d, double* counts, double* centroids_out);
@@ -730,8 +745,9 @@ void km_close_host(const double* r, int K, int d, double* counts, double* centro
 /// The step loop of KMeans::fit_once (ML/KMeans.cpp:80-110). With the all-reduce on device memory (or none) the centroid
 /// table never leaves the device between trips: sums -> means -> next table by launch_kmeans_close, one read-back per trip
 /// for the two stopping tests. With a host-memory all-reduce (gloo rehearsals) every trip goes through run_kmeans.
+/// `weighted`: every trip is a weighted step (km_launch); never the resident one-launch loop.
 void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, double* old_centroids, uint32_t max_steps, double atol,
-                uint32_t* steps_done, int* converged, double* inertia, double* counts);
+                uint32_t* steps_done, int* converged, double* inertia, double* counts, bool weighted = false);
 
 bool mstats_sparse_applies(mlhip_data* dt, const EmRoute& r, int K);
 

@@ -34,6 +34,7 @@ void ensure_km_workspace(mlhip_data* dt, int K)
                     if (!(v <= m[j])) m[j] = v;                            // (keeps a NaN / inf of any rank)
                 }
         }
+        dt->km_colmax = m;                                       // (the weighted sums' overflow test: ensure_km_weighted)
         for (int j = 0; j < dt->d; ++j) {
             if (!std::isfinite(m[j]))
                 throw DomainError("K-means: the data contain non-finite values (the exact fixed-point update sums need finite coordinates)");
@@ -53,6 +54,56 @@ void ensure_km_workspace(mlhip_data* dt, int K)
     dt->km_out.reserve(ob);
     const size_t hb = ob > sizeof(double) * (size_t)K * Dp ? ob : sizeof(double) * (size_t)K * Dp;
     dt->km_host.reserve(hb);
+}
+
+
+void ensure_km_weighted(mlhip_data* dt, int K)
+{
+    mlhip_ctx* ctx = dt->ctx;
+    ensure_km_workspace(dt, K);
+    const size_t scratch = kmeans_weighted_scratch_doubles(dt->d, K, ctx->num_cus);
+    if (scratch > kmeans_scratch_doubles(dt->d, K, ctx->num_cus)) dt->km_partials.reserve(sizeof(double) * scratch);
+    if (dt->km_wfactors_valid) return;
+    // the largest weight of the whole sample: the weight vector as a one-row block, exchanged across ranks like the column maxima
+    const int d = dt->d;
+    DevBuf scratch_dev, mx;
+    scratch_dev.reserve(sizeof(double) * 1024);
+    mx.reserve(sizeof(double));
+    launch_column_maxabs(dt->weights.as<double>(), dt->n_pad, 1, dt->n, scratch_dev.as<double>(), mx.as<double>(), ctx->stream);
+    HIP_CHECK(hipGetLastError());
+    double wmax = 0.0;
+    HIP_CHECK(hipMemcpyAsync(&wmax, mx.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    if (ctx->world_size > 1) {
+        std::vector<double> all((size_t)ctx->world_size, 0.0);
+        all[(size_t)ctx->rank] = wmax;
+        ctx->allreduce_host(all.data(), all.size());
+        for (double v : all)
+            if (!(v <= wmax)) wmax = v;
+    }
+    // (mlhip_data_set_weights accepted the weights: finite, >= 0, a positive total -- so 0 < wmax < inf)
+    int ew = 0;
+    (void)std::frexp(wmax, &ew);                                 // wmax < 2^ew
+    std::vector<double> f(2 * (size_t)d + 2);
+    for (int j = 0; j < d; ++j) {
+        if (!std::isfinite(wmax * dt->km_colmax[j]))
+            throw DomainError("weighted K-means: the largest weight times the largest |x_j| overflows");
+        int ej = 0;
+        if (dt->km_colmax[j] > 0) (void)std::frexp(dt->km_colmax[j], &ej);
+        // |w x_j| 2^E < 2^94, applied as two powers of two so that neither step leaves the normal range; E is capped where the
+        // products themselves are about to underflow (ej + ew < -1946)
+        const int E = std::min(94 - ej - ew, 2040);
+        const int h = E >= 0 ? E / 2 : -((-E) / 2);
+        f[j] = std::ldexp(1.0, h);
+        f[(size_t)d + j] = std::ldexp(1.0, E - h);
+    }
+    const int C = 94 - ew, hc = C >= 0 ? C / 2 : -((-C) / 2);
+    f[2 * (size_t)d] = std::ldexp(1.0, hc);
+    f[2 * (size_t)d + 1] = std::ldexp(1.0, C - hc);
+    dt->km_wfactors.reserve(sizeof(double) * f.size());
+    HIP_CHECK(hipMemcpyAsync(dt->km_wfactors.p, f.data(), sizeof(double) * f.size(), hipMemcpyHostToDevice, ctx->stream));
+    ctx->sync();                                                 // (f is a local)
+    dt->km_wfactors_valid = true;
 }
 
 
@@ -89,7 +140,7 @@ void km_upload_centroids(mlhip_data* dt, int K, const KmBlock& b, const double* 
 
 /// Assignment (+ optional accumulation) against the table in km_cent, partials reduced into km_out =
 /// [inertia, changed, counts, sums] and summed across ranks there when the all-reduce works on device memory.
-void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool accumulate, double* min_dist_out)
+void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool accumulate, double* min_dist_out, bool weighted)
 {
     mlhip_ctx* ctx = dt->ctx;
     const int nxt = dt->km_cur ^ 1;
@@ -101,7 +152,7 @@ void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool a
     a.old_labels = dt->km_labels[dt->km_cur].as<uint32_t>();
     a.have_old = dt->km_have_old ? 1 : 0;
     a.min_dist = min_dist_out ? min_dist_out : dt->km_mind.as<double>();   // a distance-only probe writes elsewhere
-    a.accumulate = accumulate ? 1 : 0;
+    a.accumulate = accumulate && !weighted ? 1 : 0;              // (weighted: the sums are the sweep's, after the assignment)
     a.partials = dt->km_partials.as<double>(); a.partials_capacity = dt->km_partials.bytes / sizeof(double);
     a.cnorm = dt->km_cnorm.as<double>();
     a.out = dt->km_out.as<double>();
@@ -112,6 +163,21 @@ void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool a
     if (rc <= 0) throw std::runtime_error("K-means kernel launch failed");
     launch_kmeans_reduce(a, rc, ctx->stream);
     HIP_CHECK(hipGetLastError());
+    if (weighted) {
+        // labels, distances and n_changed are the unweighted call's; inertia, counts and sums come from the weighted sweep over the
+        // UNPADDED block (the partial blocks are free again: the reduction above is ordered before it on the stream)
+        KmWeightedArgs wa{};
+        wa.xt = dt->xt.as<double>(); wa.ldx = dt->ldx; wa.n = dt->n; wa.d = dt->d;
+        wa.labels = a.labels; wa.min_dist = a.min_dist;
+        wa.weights = dt->weights.as<double>(); wa.factors = dt->km_wfactors.as<double>();
+        wa.K = K; wa.with_sums = accumulate ? 1 : 0;
+        wa.partials = a.partials; wa.partials_capacity = a.partials_capacity;
+        wa.out = a.out;
+        int wrc = 0;
+        ctx->timed("kmeans_weighted", [&] { wrc = launch_kmeans_weighted(wa, ctx->num_cus, ctx->stream); });
+        if (wrc <= 0) throw std::runtime_error("weighted K-means sweep launch failed");
+        HIP_CHECK(hipGetLastError());
+    }
     dt->km_cur = nxt;
     dt->km_have_old = true;
     ctx->reduce_on_stream(dt->km_out.as<double>(), 2 + (accumulate ? (size_t)K * (dt->d + 1) : 0));
@@ -126,11 +192,11 @@ void km_fetch(mlhip_data* dt, size_t count)
 
 
 /// Assignment (+ optional accumulation); leaves all-reduced [inertia, changed, counts, sums] in km_host.
-void run_kmeans(mlhip_data* dt, const KmRoute& r, int K, const double* centroids, bool accumulate, double* min_dist_out)
+void run_kmeans(mlhip_data* dt, const KmRoute& r, int K, const double* centroids, bool accumulate, double* min_dist_out, bool weighted)
 {
     const KmBlock b = km_block(dt, r, K);
     km_upload_centroids(dt, K, b, centroids);
-    km_launch(dt, r, K, b, accumulate, min_dist_out);
+    km_launch(dt, r, K, b, accumulate, min_dist_out, weighted);
     km_fetch(dt, 2 + (accumulate ? (size_t)K * (dt->d + 1) : 0));
 }
 
@@ -150,7 +216,7 @@ void km_close_host(const double* r, int K, int d, double* counts, double* centro
 /// table never leaves the device between trips: sums -> means -> next table by launch_kmeans_close, one read-back per trip
 /// for the two stopping tests. With a host-memory all-reduce (gloo rehearsals) every trip goes through run_kmeans.
 void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, double* old_centroids, uint32_t max_steps, double atol,
-                uint32_t* steps_done, int* converged, double* inertia, double* counts)
+                uint32_t* steps_done, int* converged, double* inertia, double* counts, bool weighted)
 {
     mlhip_ctx* ctx = dt->ctx;
     const int d = dt->d;
@@ -160,7 +226,7 @@ void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, 
     std::vector<double> cur(centroids, centroids + kd), old(kd, 0.0), upd(kd);
     // Small blocks with few clusters in the dimensions of the direct-form kernel: the whole loop in ONE launch of one workgroup
     // (device/kmeans_resident.hip; bit-identical to the launches below).
-    if (route.resident) {
+    if (route.resident && !weighted) {
         const size_t n_out = 4 + (size_t)K + 2 * kd;
         dt->km_host.reserve(sizeof(double) * (n_out > (size_t)K * b.D ? n_out : (size_t)K * b.D));
         km_upload_centroids(dt, K, b, cur.data());
@@ -197,7 +263,7 @@ void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, 
     for (uint32_t step = 0; step < max_steps; ++step) {
         if (device_route) {
             // (the closing arithmetic writes the block into the pinned km_host as well: no copy-engine transfer in the loop)
-            km_launch(dt, route, K, b, true, nullptr);
+            km_launch(dt, route, K, b, true, nullptr, weighted);
             launch_kmeans_close(dt->km_out.as<double>(), K, d, b.D, dt->km_cent_next.as<double>(), dt->km_host.as<double>(), ctx->stream);
             HIP_CHECK(hipGetLastError());
             ctx->sync();
@@ -205,7 +271,7 @@ void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, 
             if (counts) std::copy(r + 2, r + 2 + K, counts);
             std::copy(r + 2 + K, r + 2 + K + kd, upd.begin());
         } else {
-            run_kmeans(dt, route, K, cur.data(), true);
+            run_kmeans(dt, route, K, cur.data(), true, nullptr, weighted);
             km_close_host(dt->km_host.as<double>(), K, d, counts, upd.data());
         }
         const double* r = dt->km_host.as<double>();
@@ -227,10 +293,10 @@ void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, 
             }
             if (shift < atol) {           // (:103-108) one more assignment under the final centroids
                 if (device_route) {
-                    km_launch(dt, route, K, b, false, nullptr);
+                    km_launch(dt, route, K, b, false, nullptr, weighted);
                     km_fetch(dt, 2);
                 } else {
-                    run_kmeans(dt, route, K, cur.data(), false);
+                    run_kmeans(dt, route, K, cur.data(), false, nullptr, weighted);
                 }
                 *inertia = dt->km_host.as<double>()[0];
                 *converged = 1;
@@ -247,22 +313,26 @@ void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, 
 extern "C" {
 
 
-int mlhip_kmeans_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* inertia,
-                      uint64_t* n_changed, double* counts, double* centroids_out)
+namespace {
+// The three Lloyd entry points in their two forms: `weighted` runs the weighted sweep after the (unchanged) assignment.
+int kmeans_step_impl(bool weighted, mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* inertia,
+                     uint64_t* n_changed, double* counts, double* centroids_out)
 {
     return guarded([&] {
         check_call(ctx, data, K);
         require(centroids && inertia && n_changed && counts && centroids_out, "null argument");
+        if (weighted) require(data->weighted, "weighted K-means: no weights attached to the data (mlhip_data_set_weights)");
         if (ctx->group) {
             const size_t kd = (size_t)K * data->d;
             const std::vector<double> in(centroids, centroids + kd);   // (centroids_out may alias centroids)
             fan_out(ctx, data, [&](Shard& sh) {
-                return mlhip_kmeans_step(sh.ctx, sh.part, K, in.data(), sh.scalar(inertia), sh.scalar(n_changed), sh.replicated(counts, K),
-                                         sh.replicated(centroids_out, kd));
+                return kmeans_step_impl(weighted, sh.ctx, sh.part, K, in.data(), sh.scalar(inertia), sh.scalar(n_changed),
+                                        sh.replicated(counts, K), sh.replicated(centroids_out, kd));
             });
             return;
         }
-        run_kmeans(data, km_route(data, (int)K), (int)K, centroids, true);
+        if (weighted) ensure_km_weighted(data, (int)K);
+        run_kmeans(data, km_route(data, (int)K), (int)K, centroids, true, nullptr, weighted);
         const double* r = data->km_host.as<double>();
         *inertia = r[0];
         *n_changed = (uint64_t)std::llround(r[1]);
@@ -270,47 +340,93 @@ int mlhip_kmeans_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double
     });
 }
 
-int mlhip_kmeans_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* centroids, double* old_centroids,
-                         uint32_t max_steps, double absolute_tolerance, uint32_t* steps_done, int* converged,
-                         double* inertia, double* counts)
+int kmeans_iterate_impl(bool weighted, mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* centroids, double* old_centroids,
+                        uint32_t max_steps, double absolute_tolerance, uint32_t* steps_done, int* converged,
+                        double* inertia, double* counts)
 {
     return guarded([&] {
         check_call(ctx, data, K);
         require(centroids && steps_done && converged && inertia, "null argument");
+        if (weighted) require(data->weighted, "weighted K-means: no weights attached to the data (mlhip_data_set_weights)");
         require(max_steps >= 1, "at least one step");
         require(absolute_tolerance >= 0, "negative tolerance");
         if (ctx->group) {
             const size_t kd = (size_t)K * data->d;
             const std::vector<double> start(centroids, centroids + kd);   // (in/out: shard 0 updates the caller's, the others copies)
             fan_out(ctx, data, [&](Shard& sh) {
-                return mlhip_kmeans_iterate(sh.ctx, sh.part, K, sh.replicated(centroids, kd, start.data()), sh.replicated(old_centroids, kd),
-                                            max_steps, absolute_tolerance, sh.scalar(steps_done, "steps"), sh.scalar(converged, "steps"),
-                                            sh.scalar(inertia), sh.replicated(counts, K));
+                return kmeans_iterate_impl(weighted, sh.ctx, sh.part, K, sh.replicated(centroids, kd, start.data()),
+                                           sh.replicated(old_centroids, kd), max_steps, absolute_tolerance, sh.scalar(steps_done, "steps"),
+                                           sh.scalar(converged, "steps"), sh.scalar(inertia), sh.replicated(counts, K));
             });
             return;
         }
-        km_iterate(data, km_route(data, (int)K), (int)K, centroids, old_centroids, max_steps, absolute_tolerance, steps_done, converged, inertia, counts);
+        if (weighted) ensure_km_weighted(data, (int)K);
+        km_iterate(data, km_route(data, (int)K), (int)K, centroids, old_centroids, max_steps, absolute_tolerance, steps_done, converged, inertia,
+                   counts, weighted);
         ctx->check_ranks_agree("the K-means centroids", {{centroids, (size_t)K * data->d}, {inertia, 1}});
     });
+}
+
+int kmeans_assign_impl(bool weighted, mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* inertia,
+                       uint64_t* n_changed)
+{
+    return guarded([&] {
+        check_call(ctx, data, K);
+        require(centroids && inertia && n_changed, "null argument");
+        if (weighted) require(data->weighted, "weighted K-means: no weights attached to the data (mlhip_data_set_weights)");
+        if (ctx->group) {
+            fan_out(ctx, data, [&](Shard& sh) {
+                return kmeans_assign_impl(weighted, sh.ctx, sh.part, K, centroids, sh.scalar(inertia), sh.scalar(n_changed));
+            });
+            return;
+        }
+        if (weighted) ensure_km_weighted(data, (int)K);
+        run_kmeans(data, km_route(data, (int)K), (int)K, centroids, false, nullptr, weighted);
+        const double* r = data->km_host.as<double>();
+        *inertia = r[0];
+        *n_changed = (uint64_t)std::llround(r[1]);
+    });
+}
+}  // namespace
+
+int mlhip_kmeans_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* inertia,
+                      uint64_t* n_changed, double* counts, double* centroids_out)
+{
+    return kmeans_step_impl(false, ctx, data, K, centroids, inertia, n_changed, counts, centroids_out);
+}
+
+int mlhip_kmeans_step_weighted(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* inertia,
+                               uint64_t* n_changed, double* counts, double* centroids_out)
+{
+    return kmeans_step_impl(true, ctx, data, K, centroids, inertia, n_changed, counts, centroids_out);
+}
+
+int mlhip_kmeans_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* centroids, double* old_centroids,
+                         uint32_t max_steps, double absolute_tolerance, uint32_t* steps_done, int* converged,
+                         double* inertia, double* counts)
+{
+    return kmeans_iterate_impl(false, ctx, data, K, centroids, old_centroids, max_steps, absolute_tolerance, steps_done, converged, inertia,
+                               counts);
+}
+
+int mlhip_kmeans_iterate_weighted(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* centroids, double* old_centroids,
+                                  uint32_t max_steps, double absolute_tolerance, uint32_t* steps_done, int* converged,
+                                  double* inertia, double* counts)
+{
+    return kmeans_iterate_impl(true, ctx, data, K, centroids, old_centroids, max_steps, absolute_tolerance, steps_done, converged, inertia,
+                               counts);
 }
 
 int mlhip_kmeans_assign(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* inertia,
                         uint64_t* n_changed)
 {
-    return guarded([&] {
-        check_call(ctx, data, K);
-        require(centroids && inertia && n_changed, "null argument");
-        if (ctx->group) {
-            fan_out(ctx, data, [&](Shard& sh) {
-                return mlhip_kmeans_assign(sh.ctx, sh.part, K, centroids, sh.scalar(inertia), sh.scalar(n_changed));
-            });
-            return;
-        }
-        run_kmeans(data, km_route(data, (int)K), (int)K, centroids, false);
-        const double* r = data->km_host.as<double>();
-        *inertia = r[0];
-        *n_changed = (uint64_t)std::llround(r[1]);
-    });
+    return kmeans_assign_impl(false, ctx, data, K, centroids, inertia, n_changed);
+}
+
+int mlhip_kmeans_assign_weighted(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* centroids, double* inertia,
+                                 uint64_t* n_changed)
+{
+    return kmeans_assign_impl(true, ctx, data, K, centroids, inertia, n_changed);
 }
 
 int mlhip_kmeans_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t* labels)
