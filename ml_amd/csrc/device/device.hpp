@@ -133,13 +133,16 @@ bool em_mstats_self_norm_supported(int d, int K, int num_cus);
 /// written) or <= 0.
 bool em_mstats_sparse_supported(int d, int K, int num_cus);
 int launch_em_mstats_sparse(const MstatsArgs& a, int num_cus, hipStream_t stream);
-/// Fused E-step + statistics for small shapes (em_fused_small.hip): params are the estep_param_stride(D) records.
-struct FusedArgs {
+/// What the one-kernel EM passes (E-step + statistics in one launch: em_fused_small.hip, em_diag.hip, em_tied.hip) all take.
+struct OnePassArgs {
     const double* xt; size_t ldx; uint32_t n; int d;
     const double* shift; const double* params; int K;
     double* lse;                                             // out: per-sample log-sum-exp
     double* partials; size_t partials_capacity;              // scratch: [grid][KP][FP]
     double* ll_partials; int n_ll_partials;                  // out: per-workgroup log-likelihood sums (grid of them)
+};
+/// Fused E-step + statistics for small shapes (em_fused_small.hip): params are the estep_param_stride(D) records.
+struct FusedArgs : OnePassArgs {
     int form;                                                // FusedForm
 };
 enum FusedForm : int {
@@ -192,12 +195,7 @@ bool launch_em_resident(const ResidentArgs& a, hipStream_t stream);
 /// Diagonal-covariance EM iteration in one kernel (em_diag.hip): params are em_diag_partial_rows(K) records of
 /// diag_param_stride(padded_dim(d)) -- K real ones, then neutral padding (coef = -inf) -- and shift holds padded_dim(d)
 /// doubles (zeros beyond d).
-struct DiagArgs {
-    const double* xt; size_t ldx; uint32_t n; int d;
-    const double* shift; const double* params; int K;
-    double* lse;                                             // out: per-sample log-sum-exp
-    double* partials; size_t partials_capacity;              // scratch: [grid][KP][FP]
-    double* ll_partials; int n_ll_partials;                  // out: per-workgroup log-likelihood sums
+struct DiagArgs : OnePassArgs {
     int two_op;                                              // the records' (a, b) operands were built for THIS shift (the data's): the
                                                              // mixed-feed kernel may take its two-operation density form; 0 for a
                                                              // refinement pass about another shift (exact form)
@@ -214,12 +212,8 @@ int launch_em_diag(const DiagArgs& a, int num_cus, hipStream_t stream);
 /// Tied-covariance EM iteration in one kernel (em_tied.hip): winv holds the shared whitening matrix (tied_winv_doubles(D) doubles,
 /// D = padded_dim(d)), params em_tied_partial_rows(K) records of tied_param_stride(D) -- K real ones, then neutral padding
 /// (coef = -inf) -- and shift D doubles (zeros beyond d).
-struct TiedArgs {
-    const double* xt; size_t ldx; uint32_t n; int d;
-    const double* shift; const double* winv; const double* params; int K;
-    double* lse;                                             // out: per-sample log-sum-exp
-    double* partials; size_t partials_capacity;              // scratch: [grid][KP][FP], row = [S1 (d) | S0]
-    double* ll_partials; int n_ll_partials;                  // out: per-workgroup log-likelihood sums
+struct TiedArgs : OnePassArgs {                              // (a row of a partial block: [S1 (d) | S0])
+    const double* winv;
 };
 namespace mstats {
 bool em_tied_supported(int d, int K);                        // d <= 32, K <= 64

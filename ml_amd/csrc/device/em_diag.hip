@@ -18,8 +18,7 @@
 #include "parts.hpp"
 #include <type_traits>
 
-#include "em_mstats_common.hpp"
-#include "exp_nonpos.hpp"
+#include "em_tile_common.hpp"
 
 #ifndef DIAG_STATS_UNROLL
 #define DIAG_STATS_UNROLL 16   // the 16 sample groups of a slot, all of them [r5]: 73.8 -> 73.05 us
@@ -28,10 +27,6 @@
 namespace mlhip {
 namespace mstats {
 namespace {
-
-typedef __attribute__((address_space(3))) const double lds_cdouble;
-constexpr int RSS = 17;                                      // LDS row stride of one 16-component responsibility block (odd)
-template <int D> constexpr int xsd() { return (D + 2) | 1; }  // LDS row stride of the sample tile: d coords + [1, 0], odd
 
 /// RBT = 16-component row blocks that exist (K <= 16 RBT), RBW = row blocks this workgroup accumulates (blockIdx.y picks the
 /// group; every group evaluates all K densities -- the normalisation needs them), CB = 16-column blocks of the 2d features,
@@ -98,12 +93,7 @@ __global__ __launch_bounds__(256, (D <= 16 && RBT <= 2) ? 2 : 1) void em_diag_ke
 
     // feature f of the GEMM: f < d -> x~_f * 1 ; d <= f < 2d -> x~_(f-d)^2 ; beyond -> 0 * 0
     int offa[CB], offb[CB];
-#pragma unroll
-    for (int c = 0; c < CB; ++c) {
-        const int f = c * 16 + (lane & 15);
-        offa[c] = f < d ? f : (f < 2 * d ? f - d : ZERO);
-        offb[c] = f < d ? ONE : (f < 2 * d ? f - d : ZERO);
-    }
+    diag_feature_offsets<CB>(lane, d, ONE, ZERO, offa, offb);
 
     d4 acc[RBW][CB];
     double s0[RBW];                                           // lane (g, c): partial S0 of component c of each row block
@@ -258,17 +248,8 @@ __global__ __launch_bounds__(256, (D <= 16 && RBT <= 2) ? 2 : 1) void em_diag_ke
                 __builtin_amdgcn_wave_barrier();
                 if ((rb0 + rb) * 16 < Kt) {                          // wave-uniform: skip all-zero row blocks
                     __builtin_amdgcn_s_setprio(kMatrixPhasePriority);  // see em_estep_mfma4.hip
-#pragma unroll 4
-                    for (int sg = 0; sg < TS / 4; ++sg) {
-                        const double av = rbase[sg * RSS];           // r of (sample 16 g + sg, component lane & 15)
-                        const double* xr = xbase + sg * XSS;
-                        s0[rb] += av;
-#pragma unroll
-                        for (int c = 0; c < CB; ++c) {
-                            const double bv = xr[offa[c]] * xr[offb[c]];
-                            acc[rb][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[rb][c], 0, 0, 0);
-                        }
-                    }
+                    stats_tile<CB, 4, true>(rbase, [&](int sg, int c) { const double* xr = xbase + sg * XSS; return xr[offa[c]] * xr[offb[c]]; },
+                                            acc[rb], &s0[rb]);
                     __builtin_amdgcn_s_setprio(0);
                 }
             }
@@ -277,44 +258,8 @@ __global__ __launch_bounds__(256, (D <= 16 && RBT <= 2) ? 2 : 1) void em_diag_ke
 
     // ---- epilogue: fold the 4 waves' accumulators, S0 sums and log-likelihood sums in fixed order
     // partial block of this workgroup column: [KP][FP], row = component, columns [0, 2d) features, column 2d = S0
-#pragma unroll
-    for (int r = 0; r < RBW; ++r) {
-        double v = s0[r];
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        s0[r] = v;                                               // every lane (g, c): S0 of component c over the wave's samples
-    }
-    double* out = partials + (size_t)blockIdx.x * KP * FP;
-    for (int w = 0; w < 4; ++w) {
-        if (w == wave) {
-#pragma unroll
-            for (int r = 0; r < RBW; ++r) {
-#pragma unroll
-                for (int c = 0; c < CB; ++c)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int k = (rb0 + r) * 16 + (lane >> 4) + 4 * g;
-                        const int f = c * 16 + (lane & 15);
-                        if (f < 2 * d) {
-                            double* p = out + (size_t)k * FP + f;
-                            *p = (w == 0 ? 0.0 : *p) + acc[r][c][g];
-                        }
-                    }
-                if (lane < 16) {
-                    double* p = out + (size_t)((rb0 + r) * 16 + lane) * FP + 2 * d;
-                    *p = (w == 0 ? 0.0 : *p) + s0[r];
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (blockIdx.y == 0) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) ll_acc += __shfl_down(ll_acc, off, 64);
-        if (lane == 0) red[wave] = ll_acc;
-        __syncthreads();
-        if (tid == 0) ll_partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-    }
+    fold_waves<RBW, CB, true>(partials + (size_t)blockIdx.x * KP * FP, FP, rb0, wave, lane, acc, 2 * d, s0, 2 * d);
+    if (blockIdx.y == 0) fold_log_likelihood(ll_acc, red, wave, lane, tid, ll_partials + blockIdx.x);
 }
 
 /// K <= 16, d <= 16 (BASELINE.json configs[1]): the two-operation density form
@@ -370,12 +315,7 @@ __global__ __launch_bounds__(256, 2) void em_diag_mixed_kernel(
     __syncthreads();
 
     int offa[CB], offb[CB];
-#pragma unroll
-    for (int c = 0; c < CB; ++c) {
-        const int f = c * 16 + (lane & 15);
-        offa[c] = f < d ? f : (f < 2 * d ? f - d : ZERO);
-        offb[c] = f < d ? ONE : (f < 2 * d ? f - d : ZERO);
-    }
+    diag_feature_offsets<CB>(lane, d, ONE, ZERO, offa, offb);
     d4 acc[CB];
     double s0 = 0.0;                                          // lane (g, c): partial S0 of component c
 #pragma unroll
@@ -535,16 +475,7 @@ __global__ __launch_bounds__(256, 2) void em_diag_mixed_kernel(
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_s_setprio(kMatrixPhasePriority);
-#pragma unroll DIAG_STATS_UNROLL
-            for (int sg = 0; sg < TS / 4; ++sg) {
-                const double av = rbase[sg * RSS];               // r of (sample 16 g + sg, component lane & 15)
-                s0 += av;
-#pragma unroll
-                for (int c = 0; c < CB; ++c) {
-                    const double bv = pa[c][sg * XSS] * pb[c][sg * XSS];
-                    acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[c], 0, 0, 0);
-                }
-            }
+            stats_tile<CB, DIAG_STATS_UNROLL, true>(rbase, [&](int sg, int c) { return pa[c][sg * XSS] * pb[c][sg * XSS]; }, acc, &s0);
             __builtin_amdgcn_s_setprio(0);
         }
     }
@@ -574,14 +505,8 @@ __global__ __launch_bounds__(256, 2) void em_diag_mixed_kernel(
         const int e = 4 * CB * 64 + tid;
         out[(size_t)tid * FP + 2 * d] = (((0.0 + smem[e]) + smem[WREG + e]) + smem[2 * WREG + e]) + smem[3 * WREG + e];
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ll_acc += __shfl_down(ll_acc, off, 64);
-    if (lane == 0) red[wave] = ll_acc;
-    __syncthreads();
-    if (tid == 0) ll_partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    fold_log_likelihood(ll_acc, red, wave, lane, tid, ll_partials + blockIdx.x);
 }
-
-constexpr int rbw_of(int RBT) { return RBT >= 2 ? 2 : 1; }
 
 /// Bound of the two-operation density form; a.exact: the exact form always.
 inline double ab_limit(const DiagArgs& a) { return a.exact ? -1.0 : kDiagAbLimit; }
@@ -608,85 +533,33 @@ int launch_t(const DiagArgs& a, int grid, hipStream_t stream)
     }
 }
 
-template <int D>
-int launch_d(const DiagArgs& a, int grid, hipStream_t stream)
-{
-    const int RB = (a.K + 15) / 16;
-    if (RB == 1) return launch_t<D, 1>(a, grid, stream);
-    if (RB == 2) return launch_t<D, 2>(a, grid, stream);
-    if (RB <= 4) return launch_t<D, 4>(a, grid, stream);
-    return -1;
-}
-
 }  // namespace
 
-// ---- compiled in six parts by padded dimension (parts.hpp): 1: D = 1, 2; 2: 3, 4; 3: 6, 8; 4: 12, 16; 5: 20, 24; 6: 28, 32
 int MLHIP_PART_FN(launch_em_diag)(const DiagArgs& a, int grid, hipStream_t stream)
 {
-    switch (padded_dim(a.d)) {
-#if MLHIP_PART == 1
-    case 1: return launch_d<1>(a, grid, stream);
-    case 2: return launch_d<2>(a, grid, stream);
-#elif MLHIP_PART == 2
-    case 3: return launch_d<3>(a, grid, stream);
-    case 4: return launch_d<4>(a, grid, stream);
-#elif MLHIP_PART == 3
-    case 6: return launch_d<6>(a, grid, stream);
-    case 8: return launch_d<8>(a, grid, stream);
-#elif MLHIP_PART == 4
-    case 12: return launch_d<12>(a, grid, stream);
-    case 16: return launch_d<16>(a, grid, stream);
-#elif MLHIP_PART == 5
-    case 20: return launch_d<20>(a, grid, stream);
-    case 24: return launch_d<24>(a, grid, stream);
-#elif MLHIP_PART == 6
-    case 28: return launch_d<28>(a, grid, stream);
-    case 32: return launch_d<32>(a, grid, stream);
-#endif
-    default: return -1;
-    }
+    return dispatch_part_dim(a.d, [&](auto D) {
+        return dispatch_row_blocks(a.K, [&](auto RBT) { return launch_t<decltype(D)::value, decltype(RBT)::value>(a, grid, stream); });
+    });
 }
 
 #if MLHIP_PART == 1
-int launch_em_diag_part2(const DiagArgs&, int, hipStream_t);
-int launch_em_diag_part3(const DiagArgs&, int, hipStream_t);
-int launch_em_diag_part4(const DiagArgs&, int, hipStream_t);
-int launch_em_diag_part5(const DiagArgs&, int, hipStream_t);
-int launch_em_diag_part6(const DiagArgs&, int, hipStream_t);
+MLHIP_DECLARE_DIM_PARTS(launch_em_diag, DiagArgs)
 
-bool em_diag_supported(int d, int K) { return d >= 1 && d <= kRegDim && K >= 1 && K <= 64; }
-int em_diag_partial_rows(int K) { const int RB = (K + 15) / 16; return (RB == 1 ? 1 : RB == 2 ? 2 : 4) * 16; }
+bool em_diag_supported(int d, int K) { return tile_shape_supported(d, K); }
+int em_diag_partial_rows(int K) { return tile_partial_rows(K); }
 int em_diag_partial_cols(int d) { return (2 * d + 1 + 15) / 16 * 16; }
 
-/// Workgroups in x the launch will use for (d, K, n) -- also the number of partial blocks / log-likelihood partials.
 int em_diag_grid(int d, int K, uint32_t n, int num_cus)
 {
-    const int RB = (K + 15) / 16;
-    const int D = padded_dim(d), RBT = RB == 1 ? 1 : (RB == 2 ? 2 : 4);
-    const uint32_t tw = (uint32_t)TS * samples_per_lane(D, RBT);
-    const uint32_t n_tiles = (n + tw - 1) / tw;
-    const int groups = RB >= 4 ? 2 : 1;                          // row-block groups in grid.y
-    int per_cu = (D <= 16 && RB <= 2) ? 2 : 1;                   // workgroups the registers / LDS admit per CU
-    int grid = per_cu * num_cus / groups;
-    if ((uint32_t)grid * 4 > n_tiles) grid = (int)((n_tiles + 3) / 4);
-    return grid < 1 ? 1 : grid;
+    const uint32_t tw = (uint32_t)TS * samples_per_lane(padded_dim(d), tile_partial_rows(K) / 16);
+    return tile_grid(d, K, n, tw, num_cus, 4);
 }
 
 int launch_em_diag(const DiagArgs& a, int num_cus, hipStream_t stream)
 {
     if (!em_diag_supported(a.d, a.K)) return -1;
-    int grid = em_diag_grid(a.d, a.K, a.n, num_cus);
-    if (grid > a.n_ll_partials) grid = a.n_ll_partials;
-    const size_t block = (size_t)em_diag_partial_rows(a.K) * em_diag_partial_cols(a.d);
-    if ((size_t)grid * block > a.partials_capacity) grid = (int)(a.partials_capacity / block);
-    if (grid < 1) return -2;
-    const int D = padded_dim(a.d);
-    if (D <= 2) return launch_em_diag_part1(a, grid, stream);
-    if (D <= 4) return launch_em_diag_part2(a, grid, stream);
-    if (D <= 8) return launch_em_diag_part3(a, grid, stream);
-    if (D <= 16) return launch_em_diag_part4(a, grid, stream);
-    if (D <= 24) return launch_em_diag_part5(a, grid, stream);
-    return launch_em_diag_part6(a, grid, stream);
+    return launch_dim_part(a, em_diag_grid(a.d, a.K, a.n, num_cus), (size_t)em_diag_partial_rows(a.K) * em_diag_partial_cols(a.d),
+                           launch_em_diag_parts, stream);
 }
 #endif
 

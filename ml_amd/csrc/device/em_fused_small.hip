@@ -16,6 +16,7 @@
 // HBM traffic per iteration: X once, LSE once. The log-responsibility block is produced on demand (labels /
 // responsibilities after the fit) by the ordinary E-step kernel from the same parameter records.
 #include "em_fused_valu_body.hpp"
+#include "em_tile_common.hpp"
 #include "parts.hpp"
 
 #ifndef SMALL_STATS_UNROLL
@@ -26,9 +27,7 @@ namespace mlhip {
 namespace mstats {
 namespace {
 
-typedef __attribute__((address_space(3))) const double lds_cdouble;
 template <int D> constexpr int xss() { return D <= 4 ? 7 : 11; }   // LDS row stride of the sample tile (d + 2 doubles used), odd
-constexpr int RSS = 17;   // LDS row stride of one 16-component responsibility block, odd
 
 /// lw = coef - |W (x - mu)|^2 / 2 from one packed record [mean(D) | W lower triangle, row by row | coef] (em_estep.hip's
 /// arithmetic, term by term); P: an LDS pointer (broadcast reads) or a wave-uniform global pointer (scalar loads, SCALAR = true:
@@ -178,43 +177,16 @@ __global__ __launch_bounds__(256, (D <= 4 && RBW <= 2) ? 3 : 2) void em_fused_sm
             __builtin_amdgcn_wave_barrier();
             if (rb * 16 < Kt) {                          // wave-uniform: skip all-zero row blocks
                 __builtin_amdgcn_s_setprio(kMatrixPhasePriority);   // see em_estep_mfma4.hip
-#pragma unroll SMALL_STATS_UNROLL
-                for (int sg = 0; sg < TS / 4; ++sg) {
-                    const double av = rbase[sg * RSS];
-                    const double* xr = xbase + sg * XSS;
-#pragma unroll
-                    for (int c = 0; c < CB; ++c) {
-                        const double bv = xr[offa[c]] * xr[offb[c]];
-                        acc[rb][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[rb][c], 0, 0, 0);
-                    }
-                }
+                stats_tile<CB, SMALL_STATS_UNROLL, false>(
+                    rbase, [&](int sg, int c) { const double* xr = xbase + sg * XSS; return xr[offa[c]] * xr[offb[c]]; }, acc[rb], nullptr);
                 __builtin_amdgcn_s_setprio(0);
             }
         }
     }
 
     // ---- epilogue: fold the 4 waves' accumulators and log-likelihood sums in fixed order
-    double* out = partials + (size_t)blockIdx.x * KP * FP;
-    for (int w = 0; w < 4; ++w) {
-        if (w == wave) {
-#pragma unroll
-            for (int r = 0; r < RBW; ++r)
-#pragma unroll
-                for (int c = 0; c < CB; ++c)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int k = r * 16 + (lane >> 4) + 4 * g;
-                        double* p = out + (size_t)k * FP + c * 16 + (lane & 15);
-                        *p = (w == 0 ? 0.0 : *p) + acc[r][c][g];
-                    }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ll_acc += __shfl_down(ll_acc, off, 64);
-    if (lane == 0) red[wave] = ll_acc;
-    __syncthreads();
-    if (tid == 0) ll_partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    fold_waves<RBW, CB, false>(partials + (size_t)blockIdx.x * KP * FP, FP, 0, wave, lane, acc, CB * 16, nullptr, 0);
+    fold_log_likelihood(ll_acc, red, wave, lane, tid, ll_partials + blockIdx.x);
 }
 
 /// FEW components in FEW dimensions (K F <= 64 numbers, F = (d+1)(d+2)/2: the reference's own benchmark regime, d = 2, K = 3,
@@ -341,7 +313,7 @@ bool em_fused_supported(int d, int K)
     return RB <= 2 || (RB <= 4 && CB == 1);
 }
 
-int em_fused_partial_rows(int K) { const int RB = (K + 15) / 16; return (RB == 1 ? 1 : RB == 2 ? 2 : 4) * 16; }
+int em_fused_partial_rows(int K) { return tile_partial_rows(K); }
 int em_fused_partial_cols(int d) { return ((stats_count(d) + 15) / 16) * 16; }
 
 /// The vector-unit form is instantiated for d = 1 .. 4, 6 with K <= valu_max_k(d).

@@ -9,8 +9,7 @@
 // The exp(lw - lse) normalisation is applied once per (sample, component) while staging, and skipped for padding rows.
 // The four waves of a workgroup fold their accumulators into the workgroup's partial block one after the other (fixed
 // order: the result is bit-reproducible).
-#include "em_mstats_common.hpp"
-#include "exp_nonpos.hpp"
+#include "em_tile_common.hpp"
 
 #ifndef SMALL_STATS_UNROLL
 #define SMALL_STATS_UNROLL 16   // the 16 sample groups of a tile, all of them [r5] (d = 8, K = 32: 1.73 -> 1.69 ms)
@@ -21,7 +20,6 @@ namespace mstats {
 namespace {
 
 constexpr int XSS = 11;   // LDS row stride of the sample tile: d + 1 coordinates + zero slot <= 11 for d <= 9, odd
-constexpr int RSS = 17;   // LDS row stride of one 16-component responsibility block, odd
 
 template <int RBW, int CB, bool EXP>
 __global__ __launch_bounds__(256, 2) void em_mstats_small_kernel(
@@ -104,37 +102,13 @@ __global__ __launch_bounds__(256, 2) void em_mstats_small_kernel(
             if (rb + 1 < RBW) load_rows(tile, rb + 1); else load_rows(next, 0);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-#pragma unroll SMALL_STATS_UNROLL
-            for (int sg = 0; sg < TS / 4; ++sg) {
-                const double av = rbase[sg * RSS];
-                const double* xr = xbase + sg * XSS;
-#pragma unroll
-                for (int c = 0; c < CB; ++c) {
-                    const double bv = xr[offa[c]] * xr[offb[c]];
-                    acc[rb][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[rb][c], 0, 0, 0);
-                }
-            }
+            stats_tile<CB, SMALL_STATS_UNROLL, false>(
+                rbase, [&](int sg, int c) { const double* xr = xbase + sg * XSS; return xr[offa[c]] * xr[offb[c]]; }, acc[rb], nullptr);
         }
     }
 
     // ---- epilogue: the waves fold their accumulators into partials[blockIdx.x] one after the other (fixed order).
-    // C/D layout of v_mfma_f64_16x16x4: col = lane & 15, row = (lane >> 4) + 4 * reg
-    double* out = partials + (size_t)blockIdx.x * KP * FP;
-    for (int w = 0; w < 4; ++w) {
-        if (w == wave) {
-#pragma unroll
-            for (int r = 0; r < RBW; ++r)
-#pragma unroll
-                for (int c = 0; c < CB; ++c)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int k = (rb0 + r) * 16 + (lane >> 4) + 4 * g;
-                        double* p = out + (size_t)k * FP + c * 16 + (lane & 15);
-                        *p = (w == 0 ? 0.0 : *p) + acc[r][c][g];
-                    }
-        }
-        __syncthreads();
-    }
+    fold_waves<RBW, CB, false>(partials + (size_t)blockIdx.x * KP * FP, FP, rb0, wave, lane, acc, CB * 16, nullptr, 0);
 }
 
 template <int RBW, int CB>

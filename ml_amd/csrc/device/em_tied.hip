@@ -24,16 +24,11 @@
 #include <cstdlib>
 #include "parts.hpp"
 
-#include "em_mstats_common.hpp"
-#include "exp_nonpos.hpp"
+#include "em_tile_common.hpp"
 
 namespace mlhip {
 namespace mstats {
 namespace {
-
-typedef __attribute__((address_space(3))) const double lds_cdouble;
-constexpr int RSS = 17;                                      // LDS row stride of one 16-component responsibility block (odd)
-template <int D> constexpr int xsd() { return (D + 2) | 1; }  // LDS row stride of the sample tile: d coords + [1, 0], odd
 
 /// RBT = 16-component row blocks that exist (K <= 16 RBT), RBW = row blocks this workgroup accumulates (blockIdx.y picks the
 /// group; every group evaluates all K densities -- the normalisation needs them), CB = 16-column blocks of the d features.
@@ -209,37 +204,10 @@ __global__ __launch_bounds__(256, (D <= 16 && RBT <= 2) ? 2 : 1) void em_tied_ke
 
     // ---- epilogue: fold the 4 waves' accumulators, S0 sums and log-likelihood sums in fixed order
     // partial block of this workgroup column: [KP][FP], row = component, columns [0, d) = S1, column d = S0
-#pragma unroll
-    for (int r = 0; r < RBW; ++r) {
-        double v = s0[r];
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        s0[r] = v;                                               // every lane (g, c): S0 of component c over the wave's samples
-    }
-    double* out = partials + (size_t)blockIdx.x * KP * FP;
-    for (int w = 0; w < 4; ++w) {
-        if (w == wave) {
-#pragma unroll
-            for (int r = 0; r < RBW; ++r) {
-#pragma unroll
-                for (int c = 0; c < CB; ++c)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int k = (rb0 + r) * 16 + (lane >> 4) + 4 * g;
-                        const int f = c * 16 + (lane & 15);
-                        if (f < d) {
-                            double* p = out + (size_t)k * FP + f;
-                            *p = (w == 0 ? 0.0 : *p) + acc[r][c][g];
-                        }
-                    }
-                if (lane < 16) {
-                    double* p = out + (size_t)((rb0 + r) * 16 + lane) * FP + d;
-                    *p = (w == 0 ? 0.0 : *p) + s0[r];
-                }
-            }
-        }
-        __syncthreads();
-    }
+    fold_waves<RBW, CB, true>(partials + (size_t)blockIdx.x * KP * FP, FP, rb0, wave, lane, acc, d, s0, d);
+    // (the log-likelihood fold in this kernel's own text, not fold_log_likelihood: through the helper the register allocation of
+    // <3, 2, 2, 1> grows from 162 to 172 VGPRs, one wave per SIMD less; the same holds for a shared form of the normalisation above.
+    // The statistics loop is this kernel's own text too: through stats_tile d = 32, K = 40 measured 0.9 % slower, N = 1M)
     if (blockIdx.y == 0) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) ll_acc += __shfl_down(ll_acc, o, 64);
@@ -248,8 +216,6 @@ __global__ __launch_bounds__(256, (D <= 16 && RBT <= 2) ? 2 : 1) void em_tied_ke
         if (tid == 0) ll_partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
     }
 }
-
-constexpr int rbw_of(int RBT) { return RBT >= 2 ? 2 : 1; }
 
 template <int D, int RBT>
 int launch_t(const TiedArgs& a, int grid, hipStream_t stream)
@@ -262,84 +228,28 @@ int launch_t(const TiedArgs& a, int grid, hipStream_t stream)
     return grid;
 }
 
-template <int D>
-int launch_d(const TiedArgs& a, int grid, hipStream_t stream)
-{
-    const int RB = (a.K + 15) / 16;
-    if (RB == 1) return launch_t<D, 1>(a, grid, stream);
-    if (RB == 2) return launch_t<D, 2>(a, grid, stream);
-    if (RB <= 4) return launch_t<D, 4>(a, grid, stream);
-    return -1;
-}
-
 }  // namespace
 
-// ---- compiled in six parts by padded dimension (parts.hpp): 1: D = 1, 2; 2: 3, 4; 3: 6, 8; 4: 12, 16; 5: 20, 24; 6: 28, 32
 int MLHIP_PART_FN(launch_em_tied)(const TiedArgs& a, int grid, hipStream_t stream)
 {
-    switch (padded_dim(a.d)) {
-#if MLHIP_PART == 1
-    case 1: return launch_d<1>(a, grid, stream);
-    case 2: return launch_d<2>(a, grid, stream);
-#elif MLHIP_PART == 2
-    case 3: return launch_d<3>(a, grid, stream);
-    case 4: return launch_d<4>(a, grid, stream);
-#elif MLHIP_PART == 3
-    case 6: return launch_d<6>(a, grid, stream);
-    case 8: return launch_d<8>(a, grid, stream);
-#elif MLHIP_PART == 4
-    case 12: return launch_d<12>(a, grid, stream);
-    case 16: return launch_d<16>(a, grid, stream);
-#elif MLHIP_PART == 5
-    case 20: return launch_d<20>(a, grid, stream);
-    case 24: return launch_d<24>(a, grid, stream);
-#elif MLHIP_PART == 6
-    case 28: return launch_d<28>(a, grid, stream);
-    case 32: return launch_d<32>(a, grid, stream);
-#endif
-    default: return -1;
-    }
+    return dispatch_part_dim(a.d, [&](auto D) {
+        return dispatch_row_blocks(a.K, [&](auto RBT) { return launch_t<decltype(D)::value, decltype(RBT)::value>(a, grid, stream); });
+    });
 }
 
 #if MLHIP_PART == 1
-int launch_em_tied_part2(const TiedArgs&, int, hipStream_t);
-int launch_em_tied_part3(const TiedArgs&, int, hipStream_t);
-int launch_em_tied_part4(const TiedArgs&, int, hipStream_t);
-int launch_em_tied_part5(const TiedArgs&, int, hipStream_t);
-int launch_em_tied_part6(const TiedArgs&, int, hipStream_t);
+MLHIP_DECLARE_DIM_PARTS(launch_em_tied, TiedArgs)
 
-bool em_tied_supported(int d, int K) { return d >= 1 && d <= kRegDim && K >= 1 && K <= 64; }
-int em_tied_partial_rows(int K) { const int RB = (K + 15) / 16; return (RB == 1 ? 1 : RB == 2 ? 2 : 4) * 16; }
+bool em_tied_supported(int d, int K) { return tile_shape_supported(d, K); }
+int em_tied_partial_rows(int K) { return tile_partial_rows(K); }
 int em_tied_partial_cols(int d) { return (d + 1 + 15) / 16 * 16; }
-
-/// Workgroups in x the launch will use for (d, K, n) -- also the number of partial blocks / log-likelihood partials.
-int em_tied_grid(int d, int K, uint32_t n, int num_cus)
-{
-    const int RB = (K + 15) / 16;
-    const int D = padded_dim(d);
-    const uint32_t n_tiles = (n + TS - 1) / TS;
-    const int groups = RB >= 3 ? 2 : 1;                          // row-block groups in grid.y (launch_d: RB = 3 runs as RBT = 4)
-    const int per_cu = (D <= 16 && RB <= 2) ? 2 : 1;             // workgroups the registers / LDS admit per CU
-    int grid = per_cu * num_cus / groups;
-    if ((uint32_t)grid * 4 > n_tiles) grid = (int)((n_tiles + 3) / 4);
-    return grid < 1 ? 1 : grid;
-}
+int em_tied_grid(int d, int K, uint32_t n, int num_cus) { return tile_grid(d, K, n, TS, num_cus, 3); }
 
 int launch_em_tied(const TiedArgs& a, int num_cus, hipStream_t stream)
 {
     if (!em_tied_supported(a.d, a.K)) return -1;
-    int grid = em_tied_grid(a.d, a.K, a.n, num_cus);
-    if (grid > a.n_ll_partials) grid = a.n_ll_partials;
-    const size_t block = (size_t)em_tied_partial_rows(a.K) * em_tied_partial_cols(a.d);
-    if ((size_t)grid * block > a.partials_capacity) grid = (int)(a.partials_capacity / block);
-    if (grid < 1) return -2;
-    const int D = padded_dim(a.d);
-    if (D <= 2) return launch_em_tied_part1(a, grid, stream);
-    if (D <= 4) return launch_em_tied_part2(a, grid, stream);
-    if (D <= 8) return launch_em_tied_part3(a, grid, stream);
-    if (D <= 16) return launch_em_tied_part4(a, grid, stream);
-    if (D <= 24) return launch_em_tied_part5(a, grid, stream);
-    return launch_em_tied_part6(a, grid, stream);
+    return launch_dim_part(a, em_tied_grid(a.d, a.K, a.n, num_cus), (size_t)em_tied_partial_rows(a.K) * em_tied_partial_cols(a.d),
+                           launch_em_tied_parts, stream);
 }
 #endif
 

@@ -131,24 +131,37 @@ void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, co
 }
 
 
+/// K x d variances as K full covariance matrices (zero off the diagonal).
+static std::vector<double> diagonal_as_full(int K, int d, const double* variances)
+{
+    std::vector<double> covs((size_t)K * d * d, 0.0);
+    for (int k = 0; k < K; ++k)
+        for (int j = 0; j < d; ++j) covs[((size_t)k * d + j) * d + j] = variances[(size_t)k * d + j];
+    return covs;
+}
+
+
+/// One d x d covariance as the covariances of K components that all carry it.
+static std::vector<double> tied_as_full(int K, int d, const double* cov)
+{
+    const size_t dd = (size_t)d * d;
+    std::vector<double> covs((size_t)K * dd);
+    for (int k = 0; k < K; ++k) std::copy(cov, cov + dd, covs.begin() + (size_t)k * dd);
+    return covs;
+}
+
+
 /// After a fused step only lse exists on the device; whoever needs the log-responsibility block (labels,
 /// responsibilities, a separate M-step, the refinement pass) gets it rebuilt from the same parameter records.
 void ensure_lw(mlhip_data* dt, const EmRoute& r, int K)
 {
     if (!dt->estep.needs_rebuild()) return;
-    if (dt->estep.diagonal()) {
-        // params_dev holds diagonal records: expand the same parameters to full (diagonal) covariances for the E-step kernel
-        const int d = dt->d;
-        std::vector<double> covs((size_t)K * d * d, 0.0);
-        for (int k = 0; k < K; ++k)
-            for (int j = 0; j < d; ++j) covs[(size_t)k * d * d + (size_t)j * d + j] = dt->estep.diag_vars[(size_t)k * d + j];
-        prepare_estep(dt, r, K, dt->estep.diag_mixing.data(), dt->estep.diag_means.data(), covs.data());
-    } else if (dt->estep.tied()) {
-        // params_dev holds tied records: the same parameters as K full components that all carry the one covariance
-        const size_t dd = (size_t)dt->d * dt->d;
-        std::vector<double> covs((size_t)K * dd);
-        for (int k = 0; k < K; ++k) std::copy(dt->estep.tied_cov.begin(), dt->estep.tied_cov.end(), covs.begin() + (size_t)k * dd);
-        prepare_estep(dt, r, K, dt->estep.diag_mixing.data(), dt->estep.diag_means.data(), covs.data());
+    if (dt->estep.diagonal() || dt->estep.tied()) {
+        // params_dev holds diagonal / tied records: the same parameters as full covariances for the E-step kernel
+        const EstepState::Kept& p = dt->estep.kept;
+        const std::vector<double> covs = dt->estep.diagonal() ? diagonal_as_full(K, dt->d, p.covariance.data())
+                                                              : tied_as_full(K, dt->d, p.covariance.data());
+        prepare_estep(dt, r, K, p.mixing.data(), p.means.data(), covs.data());
     }
     launch_estep(dt, r, K);
 }
@@ -163,14 +176,37 @@ void collect_stats(mlhip_data* dt, int K, size_t count)
 }
 
 
-FusedArgs fused_args(const mlhip_data* dt, const EmRoute& r, int K, const DevBuf* records)
+/// What every one-kernel pass takes: the handle's block and buffers, the records in `records` (null: params_dev), the statistics
+/// shift at `shift_dev`.
+static void one_pass_args(OnePassArgs& a, const mlhip_data* dt, int K, const double* shift_dev, const DevBuf* records)
 {
-    FusedArgs a{};
     a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.d = dt->d;
-    a.shift = dt->shift_dev.as<double>(); a.params = records->as<double>(); a.K = K;
+    a.shift = shift_dev; a.params = (records ? records : &dt->params_dev)->as<double>(); a.K = K;
     a.lse = dt->lse.as<double>();
     a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
     a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
+}
+
+
+/// One one-kernel pass: `launch` (returns its grid) under the timer `timer`, then the fixed-order reduction of its partial blocks
+/// [rows][cols] and log-likelihood partials into stats_dev = [K * F statistics, ll_sum]. Returns the grid.
+template <class Launch>
+static int run_one_pass(mlhip_data* dt, const OnePassArgs& a, const char* timer, const char* what, int rows, int cols, int F, Launch&& launch)
+{
+    mlhip_ctx* ctx = dt->ctx;
+    int grid = 0;
+    ctx->timed(timer, [&] { grid = launch(); });
+    if (grid <= 0) throw std::runtime_error(std::string(what) + " EM kernel launch failed");
+    launch_em_reduce_blocks(a.partials, grid, rows, cols, a.K, F, a.ll_partials, grid, dt->stats_dev.as<double>(), ctx->stream);
+    HIP_CHECK(hipGetLastError());
+    return grid;
+}
+
+
+FusedArgs fused_args(const mlhip_data* dt, const EmRoute& r, int K, const DevBuf* records)
+{
+    FusedArgs a{};
+    one_pass_args(a, dt, K, dt->shift_dev.as<double>(), records);
     a.form = r.fused_form;
     return a;
 }
@@ -190,13 +226,9 @@ void fused_pass_done(mlhip_data* dt, int grid)
 void launch_fused_step(mlhip_data* dt, const EmRoute& r, int K, bool collect, const DevBuf* records)
 {
     mlhip_ctx* ctx = dt->ctx;
-    const FusedArgs a = fused_args(dt, r, K, records ? records : &dt->params_dev);
-    int grid = 0;
-    ctx->timed("em_fused", [&] { grid = mstats::launch_em_fused_small(a, ctx->num_cus, ctx->stream); });
-    if (grid <= 0) throw std::runtime_error("fused EM kernel launch failed");
-    launch_em_reduce_blocks(a.partials, grid, mstats::em_fused_partial_rows(K), mstats::em_fused_partial_cols(dt->d), K,
-                            stats_count(dt->d), a.ll_partials, grid, dt->stats_dev.as<double>(), ctx->stream);
-    HIP_CHECK(hipGetLastError());
+    const FusedArgs a = fused_args(dt, r, K, records);
+    const int grid = run_one_pass(dt, a, "em_fused", "fused", mstats::em_fused_partial_rows(K), mstats::em_fused_partial_cols(dt->d),
+                                  stats_count(dt->d), [&] { return mstats::launch_em_fused_small(a, ctx->num_cus, ctx->stream); });
     fused_pass_done(dt, grid);
     if (collect) collect_stats(dt, K);
 }
@@ -369,6 +401,20 @@ void refine_component(mlhip_data* dt, const EmRoute& r, int k, double* mean_k, d
 }
 
 
+/// The cancellation guard's test for one component: some (mean offset from the shared shift)^2 exceeds limit * variance
+/// (variance[a * stride]: a full matrix's diagonal, or a row of variances). Also catches a variance <= 0 from cancellation; a
+/// non-finite offset or variance leaves the component alone -- NaN stays NaN (ML/EM.cpp:236).
+static bool needs_refinement(int d, const double* mean, const double* shift, const double* variance, size_t stride, double limit)
+{
+    for (int a = 0; a < d; ++a) {
+        const double off = mean[a] - shift[a], var = variance[a * stride];
+        if (!std::isfinite(off) || !std::isfinite(var)) return false;
+        if (off * off > limit * var) return true;
+    }
+    return false;
+}
+
+
 void finalize_out(mlhip_data* dt, const EmRoute& r, int K, double* mixing_out, double* means_out, double* cov_out)
 {
     const int d = dt->d;
@@ -378,16 +424,10 @@ void finalize_out(mlhip_data* dt, const EmRoute& r, int K, double* mixing_out, d
     if (!(limit > 0)) return;
     // Every rank sees the same all-reduced statistics, hence flags the same components in the same order.
     for (int k = 0; k < K; ++k) {
-        const double* mu = means_out + (size_t)k * d;
-        const double* cov = cov_out + (size_t)k * d * d;
         if (!(mixing_out[k] > 0) || !std::isfinite(mixing_out[k])) continue;    // empty / broken component: as the reference
-        bool flag = false;
-        for (int a = 0; a < d && !flag; ++a) {
-            const double off = mu[a] - dt->shift[a], var = cov[a * d + a];
-            if (!std::isfinite(off) || !std::isfinite(var)) { flag = false; break; }   // NaN stays NaN (ML/EM.cpp:236)
-            flag = off * off > limit * var;                                      // also catches var <= 0 from cancellation
-        }
-        if (flag) refine_component(dt, r, k, means_out + (size_t)k * d, cov_out + (size_t)k * d * d);
+        double* mu = means_out + (size_t)k * d;
+        double* cov = cov_out + (size_t)k * d * d;
+        if (needs_refinement(d, mu, dt->shift.data(), cov, (size_t)d + 1, limit)) refine_component(dt, r, k, mu, cov);
     }
 }
 
@@ -398,19 +438,11 @@ void run_diag_kernel(mlhip_data* dt, const EmRoute& r, int K, const double* shif
 {
     mlhip_ctx* ctx = dt->ctx;
     DiagArgs a{};
-    a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.d = dt->d;
-    a.shift = shift_dev; a.params = (records ? records : &dt->params_dev)->as<double>(); a.K = K;
-    a.lse = dt->lse.as<double>();
-    a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
-    a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
+    one_pass_args(a, dt, K, shift_dev, records);
     a.two_op = shift_dev == dt->shift_dev.as<double>() ? 1 : 0;     // (the records' a, b are relative to the data's shift)
     a.exact = r.diag_exact ? 1 : 0;
-    int grid = 0;
-    ctx->timed("em_diag", [&] { grid = mstats::launch_em_diag(a, ctx->num_cus, ctx->stream); });
-    if (grid <= 0) throw std::runtime_error("diagonal EM kernel launch failed");
-    launch_em_reduce_blocks(a.partials, grid, mstats::em_diag_partial_rows(K), mstats::em_diag_partial_cols(dt->d), K,
-                            diag_stats_count(dt->d), a.ll_partials, grid, dt->stats_dev.as<double>(), ctx->stream);
-    HIP_CHECK(hipGetLastError());
+    const int grid = run_one_pass(dt, a, "em_diag", "diagonal", mstats::em_diag_partial_rows(K), mstats::em_diag_partial_cols(dt->d),
+                                  diag_stats_count(dt->d), [&] { return mstats::launch_em_diag(a, ctx->num_cus, ctx->stream); });
     dt->estep.diag_records_only(grid);
     if (collect) collect_stats(dt, K, (size_t)K * diag_stats_count(dt->d) + 1);
 }
@@ -483,13 +515,7 @@ void refine_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixing
     if (!(limit > 0)) return;
     for (int k = 0; k < K; ++k) {
         if (!(mixing_out[k] > 0) || !std::isfinite(mixing_out[k])) continue;
-        bool flag = false;
-        for (int a = 0; a < d && !flag; ++a) {
-            const double off = means_out[(size_t)k * d + a] - data->shift[a], var = variances_out[(size_t)k * d + a];
-            if (!std::isfinite(off) || !std::isfinite(var)) { flag = false; break; }
-            flag = off * off > limit * var;
-        }
-        if (!flag) continue;
+        if (!needs_refinement(d, means_out + (size_t)k * d, data->shift.data(), variances_out + (size_t)k * d, 1, limit)) continue;
         data->refine_shift.reserve(sizeof(double) * data->D);
         HIP_CHECK(hipMemsetAsync(data->refine_shift.p, 0, sizeof(double) * data->D, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(data->refine_shift.p, means_out + (size_t)k * d, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
@@ -514,9 +540,8 @@ void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixin
         // full-covariance kernels on diagonal matrices -- the E-step's Cholesky of a diagonal matrix is its square root, and
         // the diagonal of the M-step's full covariance IS the diagonal-mode variance (ML/EM.cpp:245-257 entry by entry); the
         // off-diagonal sums are computed and dropped. Slower than it could be, never refused.
-        std::vector<double> cov((size_t)K * d * d, 0.0), cov_out((size_t)K * d * d);
-        for (int k = 0; k < K; ++k)
-            for (int j = 0; j < d; ++j) cov[((size_t)k * d + j) * d + j] = variances[(size_t)k * d + j];
+        const std::vector<double> cov = diagonal_as_full(K, d, variances);
+        std::vector<double> cov_out((size_t)K * d * d);
         em_step_full(data, r, K, mixing, means, cov.data(), log_likelihood, mixing_out, means_out, cov_out.data());
         for (int k = 0; k < K; ++k)
             for (int j = 0; j < d; ++j) variances_out[(size_t)k * d + j] = cov_out[((size_t)k * d + j) * d + j];
@@ -541,18 +566,10 @@ static void run_tied_kernel(mlhip_data* dt, int K)
 {
     mlhip_ctx* ctx = dt->ctx;
     TiedArgs a{};
-    a.xt = dt->xt.as<double>(); a.ldx = dt->ldx; a.n = dt->n; a.d = dt->d;
-    a.shift = dt->shift_dev.as<double>(); a.params = dt->params_dev.as<double>(); a.K = K;
+    one_pass_args(a, dt, K, dt->shift_dev.as<double>(), nullptr);
     a.winv = a.params + (size_t)mstats::em_tied_partial_rows(K) * tied_param_stride(dt->D);
-    a.lse = dt->lse.as<double>();
-    a.partials = dt->partials.as<double>(); a.partials_capacity = dt->partials.bytes / sizeof(double);
-    a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
-    int grid = 0;
-    ctx->timed("em_tied", [&] { grid = mstats::launch_em_tied(a, ctx->num_cus, ctx->stream); });
-    if (grid <= 0) throw std::runtime_error("tied EM kernel launch failed");
-    launch_em_reduce_blocks(a.partials, grid, mstats::em_tied_partial_rows(K), mstats::em_tied_partial_cols(dt->d), K,
-                            tied_stats_count(dt->d), a.ll_partials, grid, dt->stats_dev.as<double>(), ctx->stream);
-    HIP_CHECK(hipGetLastError());
+    const int grid = run_one_pass(dt, a, "em_tied", "tied", mstats::em_tied_partial_rows(K), mstats::em_tied_partial_cols(dt->d),
+                                  tied_stats_count(dt->d), [&] { return mstats::launch_em_tied(a, ctx->num_cus, ctx->stream); });
     dt->estep.tied_records_only(grid);
     collect_stats(dt, K, (size_t)K * tied_stats_count(dt->d) + 1);
 }
@@ -586,8 +603,8 @@ void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mix
         // M-step, since sum_k S0_k Sigma_k = T - sum_k S1_k S1_k^T / S0_k. Every Sigma_k carries the ridge 1e-15 I (ML/EM.cpp:252),
         // and sum_k pi_k = 1 up to rounding: the K ridges pool to the one ridge of the tied mode. Nothing is subtracted or re-added.
         // Slower than it could be, never refused.
-        std::vector<double> covs((size_t)K * dd), covs_out((size_t)K * dd);
-        for (int k = 0; k < K; ++k) std::copy(cov, cov + dd, covs.begin() + (size_t)k * dd);
+        const std::vector<double> covs = tied_as_full(K, d, cov);
+        std::vector<double> covs_out((size_t)K * dd);
         em_step_full(data, r.em, K, mixing, means, covs.data(), log_likelihood, mixing_out, means_out, covs_out.data());
         for (size_t e = 0; e < dd; ++e) {
             double v = 0.0;

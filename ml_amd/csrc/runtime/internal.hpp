@@ -412,10 +412,11 @@ struct EstepState {
     int stats_mode = 0;
     const double* stats_resp = nullptr;
     size_t stats_ld = 0;
-    // diagonal-covariance extension: parameters of the last diagonal E-step (the N x K block is rebuilt from them on demand)
-    std::vector<double> diag_mixing, diag_means, diag_vars;
-    // tied-covariance extension: the one covariance of the last tied kernel step (its mixing / means sit in diag_mixing / diag_means)
-    std::vector<double> tied_cov;
+    // kDiagRecords / kTiedRecords: the parameters of that pass (the N x K block is rebuilt from them on demand)
+    struct Kept {
+        std::vector<double> mixing, means;                    // [K], [K][d]
+        std::vector<double> covariance;                       // diagonal: the K x d variances; tied: the one d x d covariance
+    } kept;
 
     void invalidate() { what = kNone; }
     void block_written(int grid) { what = kBlock; n_ll = grid; }
@@ -429,16 +430,12 @@ struct EstepState {
     /// The parameters behind the diagonal records in params_dev (mlhip_em_iterate: set once, when the loop is over).
     void diag_parameters(int K, int d, const double* mixing, const double* means, const double* vars)
     {
-        diag_mixing.assign(mixing, mixing + K);
-        diag_means.assign(means, means + (size_t)K * d);
-        diag_vars.assign(vars, vars + (size_t)K * d);
+        keep(K, d, mixing, means, vars, (size_t)K * d);
     }
     /// The parameters behind the tied records in params_dev.
     void tied_parameters(int K, int d, const double* mixing, const double* means, const double* cov)
     {
-        diag_mixing.assign(mixing, mixing + K);
-        diag_means.assign(means, means + (size_t)K * d);
-        tied_cov.assign(cov, cov + (size_t)d * d);
+        keep(K, d, mixing, means, cov, (size_t)d * d);
     }
     void records_are(int layout, bool fold) { rec_layout = layout; rec_fold = fold; }
     void stats_from(int mode, const double* resp, size_t ld) { stats_mode = mode; stats_resp = resp; stats_ld = ld; }
@@ -447,6 +444,14 @@ struct EstepState {
     bool needs_rebuild() const { return what == kRecords || what == kDiagRecords || what == kTiedRecords; }
     bool diagonal() const { return what == kDiagRecords; }
     bool tied() const { return what == kTiedRecords; }
+
+private:
+    void keep(int K, int d, const double* mixing, const double* means, const double* covariance, size_t covariance_doubles)
+    {
+        kept.mixing.assign(mixing, mixing + K);
+        kept.means.assign(means, means + (size_t)K * d);
+        kept.covariance.assign(covariance, covariance + covariance_doubles);
+    }
 };
 
 struct mlhip_data {
@@ -666,7 +671,7 @@ void ensure_lw(mlhip_data* dt, const EmRoute& r, int K);
 /// All-reduces the reduced statistics buffer [K*F stats, ll_sum] and leaves it in stats_host.
 void collect_stats(mlhip_data* dt, int K, size_t count = 0);
 
-/// The fused kernel's arguments on the records in `records`.
+/// The fused kernel's arguments on the records in `records` (null: params_dev).
 FusedArgs fused_args(const mlhip_data* dt, const EmRoute& r, int K, const DevBuf* records);
 
 /// What a fused pass (launch_fused_step, or the resident loop that runs the same pass) leaves behind on the handle.

@@ -110,7 +110,10 @@ def test_tied_step_matches_sklearn_fixture_on_both_routes(ctx, case, monkeypatch
 EDGE_SHAPES = ([(n, 3, 2) for n in (1, 63, 64, 65, 257)] + [(300, 8, K) for K in (1, 16, 17, 64)] +
                [(300, d, 3) for d in (1, 5, 12, 31, 32)] + [(300, 33, 3), (300, 8, 65)] +
                # d = 32 with 2, 3 and 4 row blocks of components: the largest LDS footprints; K = 40 also at d = 16 (two workgroups per CU below)
-               [(300, 32, 24), (300, 32, 40), (300, 32, 64), (300, 16, 40)])
+               [(300, 32, 24), (300, 32, 40), (300, 32, 64), (300, 16, 40)] +
+               # enough samples that a wave re-stages its LDS tile for a second trip of the tile loop (above grid x 4 x 64 samples:
+               # 131 072 with two workgroups per CU on 256 CUs, 32 768 with one per CU and two row-block groups)
+               [(140001, 8, 17), (40001, 32, 40)])
 
 
 @pytest.mark.parametrize("n,d,K", EDGE_SHAPES)
