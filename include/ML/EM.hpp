@@ -45,14 +45,21 @@ public:
     entries only; covariances() returns diagonal matrices). Default `Full` == the reference's behaviour.
     One fused kernel serves number_dimensions <= 32 and number_components <= 64; other shapes run the full-covariance kernels on
     diagonal matrices (slower, never refused).
-    With `Tied` all components share ONE covariance (scikit-learn's 'tied'): Sigma = sum_k pi_k Sigma_k of the full M-step, ridge
-    1e-15 once; covariances() returns number_components() copies of it, so the point query and the batch queries work unchanged. The
+    With `Tied` all components share ONE covariance (scikit-learn's 'tied'): Sigma = sum_k pi_k Sigma_k of the full M-step, the ridge
+    (covariance_regularisation(), default 1e-15) once; covariances() returns number_components() copies of it, so the point query and the batch queries work unchanged. The
     start is the pooled sum_k pi_k Sigma_k of the starting covariances (the sample covariance on the default start). One kernel per
     iteration serves unweighted fits with number_dimensions <= 32 and number_components <= 64; other shapes and weighted fits run the
     full-covariance kernels on copies of Sigma and pool the result (mlhip_em_step_tied). */
     enum class CovarianceType { Full, Diagonal, Tied };
     void set_covariance_type(CovarianceType covariance_type) { covariance_type_ = covariance_type; }
     CovarianceType covariance_type() const { return covariance_type_; }
+    /** EXTENSION -- scikit-learn's `reg_covar`; the reference hard-wires 1e-15 (ML/EM.cpp:252), which stays the default. Every M-step
+    of the next fit() adds this value to the diagonal of each covariance it forms (Full: every component's; Diagonal: every variance;
+    Tied: the one covariance, once) -- the `maximise_first` start included. The starting covariance (the sample covariance) and the
+    exact N == K fit are not touched (mlhip_data_set_covariance_ridge). 0 is allowed.
+    @throw std::domain_error If the value is negative or not finite. */
+    DLL_DECLSPEC void set_covariance_regularisation(double covariance_regularisation);
+    double covariance_regularisation() const { return covariance_regularisation_; }
 
     /** @brief Fits the model. @param[in] data Column-major, a data point in every column (this rank's row shard when an
     all-reduce hook is installed on the device context). @return `true` if fitting converged.
@@ -134,6 +141,7 @@ private:
     bool converged_;
     CovarianceType covariance_type_ = CovarianceType::Full;
     mlhip_data* device_data_ = nullptr;
+    double covariance_regularisation_ = 1e-15;   // MLHIP_DEFAULT_COVARIANCE_RIDGE
 
     void process_covariances(Index number_dimensions);
     void require_fitted_for(ConstMatrixRef data) const;

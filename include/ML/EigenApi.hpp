@@ -223,6 +223,19 @@ public:
     enum class CovarianceType { Full = 0, Diagonal = 1, Tied = 2 };
     void set_covariance_type(CovarianceType covariance_type) { detail::check(mlpp_em_set_covariance_type(h_, static_cast<int>(covariance_type))); }
 
+    /** Extension (ML/EM.hpp): what every M-step adds to the diagonal of each covariance it forms; default 1e-15, the reference's constant.
+    @throw std::domain_error If the value is negative or not finite. */
+    void set_covariance_regularisation(double covariance_regularisation)
+    {
+        detail::check(mlpp_em_set_covariance_regularisation(h_, covariance_regularisation));
+    }
+    double covariance_regularisation() const
+    {
+        double v = 0;
+        detail::check(mlpp_em_covariance_regularisation(h_, &v));
+        return v;
+    }
+
     bool fit(Eigen::Ref<const Eigen::MatrixXd> data) override { return fit_block(data, nullptr); }
     /** Extension: the fit of a weighted sample (ml::EM::fit(data, weights) of ML/EM.hpp): weights(i) >= 0 is the frequency weight of
     column i. @throw std::invalid_argument If `weights.size() != data.cols()` or the weights are refused. */

@@ -154,12 +154,28 @@ int mlhip_data_set_weights(mlhip_ctx* ctx, mlhip_data* data, const double* weigh
 /* W, the all-reduced total of the attached weights; n_global (as a double) for an unweighted block. */
 int mlhip_data_weight_sum(const mlhip_data* data, double* total);
 
+/* EXTENSION (scikit-learn's reg_covar; the reference hard-wires 1e-15, ML/EM.cpp:252): the covariance ridge r of the handle, what every
+ * M-step on it adds to the diagonal of each covariance it FORMS -- full mode: every Sigma_k = S_k + r I; diagonal mode: every variance;
+ * tied mode: the one Sigma, r once. It is read by mlhip_em_step / _step_diag / _step_tied / _iterate (all three covariance types, closed
+ * on the host or on the device, the one-launch resident loop included), mlhip_em_maximisation / _maximisation_from /
+ * _maximisation_from_labels and the refinement pass about a component's own mean: one plain fp64 add per diagonal entry on every
+ * route, so two routes that agree bit for bit at the default agree bit for bit at any r. r finite and >= 0 (-0.0 counts as 0; r = 0 adds
+ * 0.0); NaN, an infinity or a negative value: MLHIP_E_INVALID_ARGUMENT and the handle keeps its ridge. The default keeps the
+ * reference's bits. NOT touched: parameters a caller GIVES (the first E-step, mlhip_em_expectation, mlhip_em_score use them as they
+ * are), mlhip_sample_covariance, the kernel routes (mlhip_em_route / _tied_route / _score_route report what they reported). Setting
+ * the ridge drops nothing the handle holds: E-step results stay valid. A device group's handle passes the value to every shard's
+ * part and mirrors it. In a multi-process job every rank sets its own handle; nothing is all-reduced (ranks that disagree fail the
+ * end-of-fit checksum exchange of mlhip_em_iterate). */
+#define MLHIP_DEFAULT_COVARIANCE_RIDGE 1e-15
+int mlhip_data_set_covariance_ridge(mlhip_ctx* ctx, mlhip_data* data, double ridge);
+int mlhip_data_covariance_ridge(const mlhip_data* data, double* ridge);
+
 /* ---- Gaussian-mixture EM -------------------------------------------------------------------------- */
 /* One EM iteration == EM::expectation_step + EM::maximisation_step (ML/EM.cpp:190-263, incl.
  * process_covariances :274-287) on the resident shard, statistics all-reduced across ranks.
  *   in : mixing[K], means[d*K] (column k = mean k), covariances[K*d*d] (symmetric, column-major each)
  *   out: *log_likelihood  = mean_i log sum_k pi_k N(x_i|mu_k,Sigma_k)  under the INPUT parameters (:211)
- *        mixing_out/means_out/covariances_out = the M-step result (:229-257, ridge 1e-15 included)
+ *        mixing_out/means_out/covariances_out = the M-step result (:229-257, the handle's ridge, default 1e-15, included)
  * Output arrays may alias the input arrays. The E-step results stay available on the device for
  * mlhip_em_responsibilities / mlhip_em_labels (for small shapes, where the iteration runs as one fused kernel, the
  * N x K block is rebuilt from the same parameter records when one of them is called). */
@@ -169,7 +185,7 @@ int mlhip_em_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
 
 /* EXTENSION (no counterpart in the reference, whose ml::EM is full-covariance only, ML/EM.hpp:175; BASELINE.json configs[1]):
  * one EM iteration with DIAGONAL covariances -- the loops of mlhip_em_step restricted to the diagonal, in one kernel
- * (X read once, no N x K block in HBM). variances / variances_out: K*d doubles, variances[k*d + j] = sigma_kj^2 (ridge 1e-15
+ * (X read once, no N x K block in HBM). variances / variances_out: K*d doubles, variances[k*d + j] = sigma_kj^2 (the handle's ridge, default 1e-15,
  * included on output, ML/EM.cpp:252). One fused kernel for d <= 32, K <= 64; other shapes run the full-covariance kernels on diagonal matrices. mlhip_em_responsibilities /
  * mlhip_em_labels afterwards work as after mlhip_em_step (the block is rebuilt from the same parameters on demand). */
 int mlhip_em_step_diag(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
@@ -181,7 +197,7 @@ int mlhip_em_step_diag(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
  * column-major). The E-step, the log-likelihood, labels and responsibilities are those of mlhip_em_step on K components that all
  * carry Sigma; the M-step, with xt = x - shift, W the total weight (N when unweighted), S0_k = sum_i w_i r_ik, S1_k = sum_i w_i r_ik xt_i
  * and T = sum_i w_i xt_i xt_i^T (constant over a fit: formed once per handle, all-reduced once), is
- *   pi_k = S0_k / W,  mu_k = shift + S1_k / S0_k,  Sigma = (T - sum_k S1_k S1_k^T / S0_k) / W + 1e-15 I     (the ridge of ML/EM.cpp:252, once)
+ *   pi_k = S0_k / W,  mu_k = shift + S1_k / S0_k,  Sigma = (T - sum_k S1_k S1_k^T / S0_k) / W + r I     (r: the handle's ridge, default 1e-15 -- ML/EM.cpp:252 --, once)
  * == sum_k pi_k Sigma_k over mlhip_em_step's covariances; an empty component behaves as there. One kernel for unweighted blocks with
  * d <= 32, K <= 64 (the sample is whitened once, not once per component; K (d + 1) + 1 statistics are all-reduced); other shapes,
  * weighted blocks, the few-component shapes whose full-covariance step is the vector-unit fused kernel (measured faster composed;
@@ -269,6 +285,10 @@ int mlhip_xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt,
 int mlhip_em_statistics_count(uint32_t d, uint32_t* count_per_component);
 int mlhip_em_finalize_statistics(uint32_t d, uint32_t K, const double* statistics, const double* shift,
                                  double n_global, double* mixing_out, double* means_out, double* covariances_out);
+/* Same with the covariance ridge given (mlhip_data_set_covariance_ridge: finite, >= 0, else MLHIP_E_INVALID_ARGUMENT); the function
+ * above is this one at MLHIP_DEFAULT_COVARIANCE_RIDGE. */
+int mlhip_em_finalize_statistics_ridge(uint32_t d, uint32_t K, const double* statistics, const double* shift, double n_global,
+                                       double ridge, double* mixing_out, double* means_out, double* covariances_out);
 
 /* The tied mode's counterpart (no GPU needed; the closing of both routes of mlhip_em_step_tied is this arithmetic). `statistics`: K
  * records of d + 1 doubles, [S1_k (d) | S0_k] with S1_k = sum_i w_i r_ik (x_i - shift); `total_scatter`: sum_i w_i xt_i xt_i^T,
@@ -276,6 +296,10 @@ int mlhip_em_finalize_statistics(uint32_t d, uint32_t K, const double* statistic
  * covariance_out: d*d doubles. */
 int mlhip_em_finalize_statistics_tied(uint32_t d, uint32_t K, const double* statistics, const double* total_scatter, const double* shift,
                                       double total_weight, double* mixing_out, double* means_out, double* covariance_out);
+/* Same with the covariance ridge given (added once); the function above is this one at MLHIP_DEFAULT_COVARIANCE_RIDGE. */
+int mlhip_em_finalize_statistics_tied_ridge(uint32_t d, uint32_t K, const double* statistics, const double* total_scatter,
+                                            const double* shift, double total_weight, double ridge, double* mixing_out,
+                                            double* means_out, double* covariance_out);
 
 /* Host helper, no GPU needed: covariance -> what EM::process_covariances (ML/EM.cpp:274-287) derives:
  * inverse (d*d), sqrt(det). Used by the facade for point queries (EM::assign_responsibilities). */

@@ -56,6 +56,10 @@ int mlpp_em_set_maximise_first(mlpp_em* h, int v);
 /* Extension (ml::EM::set_covariance_type): 0 = full covariances (the reference), 1 = diagonal, 2 = tied (one covariance shared by
  * all components); any other nonzero value selects diagonal, as it always did. */
 int mlpp_em_set_covariance_type(mlpp_em* h, int covariance_type);
+/* EXTENSION: ml::EM::set_covariance_regularisation / covariance_regularisation (scikit-learn's reg_covar; default 1e-15). A negative or
+ * non-finite value: MLHIP_E_DOMAIN, the model keeps its value. */
+int mlpp_em_set_covariance_regularisation(mlpp_em* h, double v);
+int mlpp_em_covariance_regularisation(const mlpp_em* h, double* out);
 int mlpp_em_fit(mlpp_em* h, const double* data, uint64_t n, uint32_t d, int* converged);
 /* Extension (ml::EM::fit(data, weights)): the fit of a weighted sample, weights[i] >= 0 the frequency weight of point i (n values). */
 int mlpp_em_fit_weighted(mlpp_em* h, const double* data, const double* weights, uint64_t n, uint32_t d, int* converged);

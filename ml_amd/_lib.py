@@ -49,6 +49,18 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
 lib.mlhip_last_error.restype = C.c_char_p
 lib.mlhip_version.restype = C.c_char_p
 
+DEFAULT_COVARIANCE_RIDGE = 1e-15      # MLHIP_DEFAULT_COVARIANCE_RIDGE
+# the covariance ridge's entry points take doubles by value: prototypes, so that a Python float converts by itself
+lib.mlhip_data_set_covariance_ridge.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
+lib.mlhip_data_covariance_ridge.argtypes = [C.c_void_p, c_dp]
+lib.mlhip_em_finalize_statistics_ridge.argtypes = [C.c_uint32, C.c_uint32, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp, c_dp]
+lib.mlhip_em_finalize_statistics_tied_ridge.argtypes = [C.c_uint32, C.c_uint32, c_dp, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp, c_dp]
+lib.mlpp_em_set_covariance_regularisation.argtypes = [C.c_void_p, C.c_double]
+lib.mlpp_em_covariance_regularisation.argtypes = [C.c_void_p, c_dp]
+for _name in ("mlhip_data_set_covariance_ridge", "mlhip_data_covariance_ridge", "mlhip_em_finalize_statistics_ridge",
+              "mlhip_em_finalize_statistics_tied_ridge", "mlpp_em_set_covariance_regularisation", "mlpp_em_covariance_regularisation"):
+    getattr(lib, _name).restype = C.c_int
+
 
 class MlhipError(RuntimeError):
     def __init__(self, code, msg):
@@ -339,6 +351,18 @@ class Data:
         check(lib.mlhip_data_weight_sum(self._h, C.byref(total)))
         return total.value
 
+    def set_covariance_ridge(self, ridge):
+        """The covariance ridge of the handle (mlhip_data_set_covariance_ridge): what every M-step on it adds to the diagonal of each
+        covariance it forms. Finite and >= 0; ValueError otherwise (the handle keeps its ridge). E-step results stay valid."""
+        check(lib.mlhip_data_set_covariance_ridge(self.ctx.handle, self._h, float(ridge)))
+
+    @property
+    def covariance_ridge(self):
+        """The handle's covariance ridge (DEFAULT_COVARIANCE_RIDGE = 1e-15 unless set)."""
+        ridge = C.c_double()
+        check(lib.mlhip_data_covariance_ridge(self._h, C.byref(ridge)))
+        return ridge.value
+
     # ---- EM -----------------------------------------------------------------------------------------------
     # Parameter conventions (Python side): means K x d, covariances K x d x d, mixing K.
     def em_step(self, mixing, means, covs):
@@ -573,17 +597,33 @@ def calculate_XXt_beta(X, y, lam):
     return XXt, beta
 
 
-def finalize_statistics_tied(statistics, total_scatter, shift, total_weight):
+def finalize_statistics_ridge(statistics, shift, n_global, ridge):
+    """The full M-step's closing arithmetic on the host with the covariance ridge given (mlhip_em_finalize_statistics_ridge, no GPU):
+    statistics K x (d+1)(d+2)/2 packed records. Returns (mixing, means K x d, covariances K x d x d)."""
+    st = np.ascontiguousarray(statistics, dtype=np.float64)
+    shift = np.ascontiguousarray(shift, dtype=np.float64)
+    K, d = st.shape[0], shift.shape[0]
+    assert st.shape == (K, (d + 1) * (d + 2) // 2)
+    pi, mu, S = np.empty(K), np.empty((K, d)), np.empty((K, d, d))
+    check(lib.mlhip_em_finalize_statistics_ridge(d, K, dptr(st), dptr(shift), float(n_global), float(ridge), dptr(pi), dptr(mu), dptr(S)))
+    return pi, mu, S
+
+
+def finalize_statistics_tied(statistics, total_scatter, shift, total_weight, ridge=None):
     """The tied M-step's closing arithmetic on the host (mlhip_em_finalize_statistics_tied, no GPU): statistics K x (d + 1) rows
     [S1_k | S0_k], total_scatter the packed (d+1)(d+2)/2 lower triangle of sum_i w_i [x~_i; 1][x~_i; 1]^T. Returns
-    (mixing, means K x d, covariance d x d)."""
+    (mixing, means K x d, covariance d x d). `ridge`: the covariance ridge (mlhip_em_finalize_statistics_tied_ridge); None: the default."""
     st = np.ascontiguousarray(statistics, dtype=np.float64)
     K, d = st.shape[0], st.shape[1] - 1
     T = np.ascontiguousarray(total_scatter, dtype=np.float64)
     shift = np.ascontiguousarray(shift, dtype=np.float64)
     assert T.shape == ((d + 1) * (d + 2) // 2,) and shift.shape == (d,)
     pi, mu, S = np.empty(K), np.empty((K, d)), np.empty((d, d))
-    check(lib.mlhip_em_finalize_statistics_tied(d, K, dptr(st), dptr(T), dptr(shift), C.c_double(total_weight), dptr(pi), dptr(mu), dptr(S)))
+    if ridge is None:
+        check(lib.mlhip_em_finalize_statistics_tied(d, K, dptr(st), dptr(T), dptr(shift), C.c_double(total_weight), dptr(pi), dptr(mu), dptr(S)))
+    else:
+        check(lib.mlhip_em_finalize_statistics_tied_ridge(d, K, dptr(st), dptr(T), dptr(shift), float(total_weight), float(ridge), dptr(pi),
+                                                          dptr(mu), dptr(S)))
     return pi, mu, S
 
 

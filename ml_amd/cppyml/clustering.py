@@ -9,7 +9,7 @@ Conventions kept from the reference:
   * std::invalid_argument / std::domain_error surface as ValueError.
 Extensions (not in the reference surface): `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
-`KMeans.fit(..., sample_weight=)`.
+`KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`.
 """
 import ctypes as C
 
@@ -199,6 +199,19 @@ class EM:
         if covariance_type not in codes:
             raise ValueError("covariance_type must be 'full', 'diag' or 'tied'")
         _check(_l.mlpp_em_set_covariance_type(self._h, codes[covariance_type]))
+
+    def set_covariance_regularisation(self, covariance_regularisation):
+        """Extension (scikit-learn's `reg_covar`): the value every M-step of the next fit adds to the diagonal of each covariance
+        it forms ("full": every component's; "diag": every variance; "tied": the one covariance, once). Default 1e-15, the
+        reference's constant; 0 is allowed. ValueError for a negative or non-finite value (the model keeps its value)."""
+        _check(_l.mlpp_em_set_covariance_regularisation(self._h, float(covariance_regularisation)))
+
+    @property
+    def covariance_regularisation(self):
+        """Extension: the value set by `set_covariance_regularisation` (1e-15 unless set)."""
+        v = C.c_double()
+        _check(_l.mlpp_em_covariance_regularisation(self._h, C.byref(v)))
+        return v.value
 
     def fit(self, data, sample_weight=None):
         """Fits the components to the data (2D array with data points in rows). Returns True if EM converged.

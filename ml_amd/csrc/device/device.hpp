@@ -178,6 +178,7 @@ struct ResidentArgs {
     unsigned* sync;                                          // device: [arrivals, give-up flag], zeroed before the launch
     int vgrid;                                               // partial blocks = workgroups (em_fused_valu_small_grid)
     double n_global, refine_limit, atol, rtol, ll_offset;    // log-likelihood = sum / n_global - ll_offset
+    double ridge;                                            // added to every covariance's diagonal by the closing (CloseArgs::ridge)
     uint32_t max_steps;
     double* history;                                         // pinned host: max_steps log-likelihoods
     uint32_t* result;                                        // pinned host: [status, iterations evaluated, converged]; status 1 = loop over,
@@ -229,6 +230,7 @@ struct CloseArgs {
     const double* shift; double n_global;                    // shift: D doubles, zero padded
     int layout;                                              // full covariances: 0 = estep_param_stride records, 2 = mfma4 records
     double refine_limit;                                     // <= 0: no refinement flags
+    double ridge;                                            // added to the diagonal of every covariance formed (the data handle's; ML/EM.cpp:252 has 1e-15)
     double* mixing; double* means; double* covs;             // out (device): [K], [K*d], [K*d*d] (diagonal: [K*d] variances)
     double* records;                                         // out (device): the next E-step's K records
     double* info;                                            // out (device): [ll_sum | refine flag (K) | max |W (mu - shift)| (K)]
@@ -242,7 +244,7 @@ bool em_close_big_supported(int d);
 size_t em_close_big_work_doubles(int d, int K);
 void launch_em_close_big(const CloseArgs& a, hipStream_t stream);
 double* em_close_big_param_area(double* work, int d, int K);   // K (d d + d + 1) + 2 K + 1 doubles behind the matrices
-/// Records of GIVEN parameters (a fit's first E-step): a.mixing / a.means / a.covs are device inputs, a.stats unused.
+/// Records of GIVEN parameters (a fit's first E-step): a.mixing / a.means / a.covs are device inputs, a.stats and a.ridge unused.
 void launch_em_records_big(const CloseArgs& a, hipStream_t stream);
 void launch_em_close(const CloseArgs& a, hipStream_t stream);
 void launch_em_close_diag(const CloseArgs& a, hipStream_t stream);

@@ -21,20 +21,20 @@ using closing::NT;
 
 template <int LAYOUT, int DT>
 __global__ __launch_bounds__(NT) void em_close_kernel(const double* __restrict__ stats, int K, int d, int D,
-                                                        const double* __restrict__ shift, double n_global, double refine_limit,
+                                                        const double* __restrict__ shift, double n_global, double ridge, double refine_limit,
                                                         double* __restrict__ mixing, double* __restrict__ means,
                                                         double* __restrict__ covs, double* __restrict__ records, int PS,
                                                         double* __restrict__ info)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    closing::close_component<LAYOUT, DT>(stats, K, d, D, shift, n_global, refine_limit, mixing, means, covs, records, PS, info,
+    closing::close_component<LAYOUT, DT>(stats, K, d, D, shift, n_global, ridge, refine_limit, mixing, means, covs, records, PS, info,
                                          (int)blockIdx.x, (int)threadIdx.x, sm);
 }
 
 /// Diagonal covariances: elementwise (host/em_math.cpp finalize_mstep_diag + build_diag_params). One workgroup per
 /// component (d <= 32 threads busy); records of the padding rows k >= K are written once by the host and left alone.
 __global__ __launch_bounds__(64) void em_close_diag_kernel(const double* __restrict__ stats, int K, int KP, int d, int D,
-                                                            const double* __restrict__ shift, double n_global, double refine_limit,
+                                                            const double* __restrict__ shift, double n_global, double ridge, double refine_limit,
                                                             double* __restrict__ mixing, double* __restrict__ means,
                                                             double* __restrict__ vars, double* __restrict__ records,
                                                             double* __restrict__ info)
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(64) void em_close_diag_kernel(const double* __restr
     if (tid < d) {
         const double mm = s[tid] / s0;
         const double mean = shift[tid] + mm;
-        const double var = (s[d + tid] - s[tid] * mm) / s0 + 1e-15;
+        const double var = (s[d + tid] - s[tid] * mm) / s0 + ridge;
         means[(size_t)k * d + tid] = mean;
         vars[(size_t)k * d + tid] = var;
         const double off = mean - shift[tid];
@@ -102,7 +102,7 @@ void launch_em_close(const CloseArgs& a, hipStream_t stream)
     const size_t smem = sizeof(double) * closing::scratch_doubles(d);
 #define MLHIP_CLOSE(LAYOUT, DT, PS) \
     hipLaunchKernelGGL((em_close_kernel<LAYOUT, DT>), dim3(a.K), dim3(NT), smem, stream, a.stats, a.K, d, a.D, a.shift, a.n_global, \
-                       a.refine_limit, a.mixing, a.means, a.covs, a.records, PS, a.info)
+                       a.ridge, a.refine_limit, a.mixing, a.means, a.covs, a.records, PS, a.info)
     if (a.layout == 2) {
         const int PS = estep_mfma4_param_stride(a.D);
         switch (a.D) {
@@ -132,7 +132,7 @@ void launch_em_close(const CloseArgs& a, hipStream_t stream)
 void launch_em_close_diag(const CloseArgs& a, hipStream_t stream)
 {
     hipLaunchKernelGGL(em_close_diag_kernel, dim3(a.K), dim3(64), 0, stream, a.stats, a.K, mstats::em_diag_partial_rows(a.K), a.d, a.D, a.shift, a.n_global,
-                       a.refine_limit, a.mixing, a.means, a.covs, a.records, a.info);
+                       a.ridge, a.refine_limit, a.mixing, a.means, a.covs, a.records, a.info);
 }
 
 }  // namespace mlhip

@@ -60,7 +60,7 @@ __device__ __forceinline__ double lane_value(double v, int lane)
 
 /// Covariance entries (one thread each), means, mixing weight, refinement codes (em_close_body.hpp's first part, from global memory).
 __global__ __launch_bounds__(256) void close_big_prepare_kernel(const double* __restrict__ stats, int K, int d, const double* __restrict__ shift,
-                                                                 double n_global, double refine_limit, double* __restrict__ mixing,
+                                                                 double n_global, double ridge, double refine_limit, double* __restrict__ mixing,
                                                                  double* __restrict__ means, double* __restrict__ covs, double* __restrict__ work)
 {
     const int k = blockIdx.x;
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void close_big_prepare_kernel(const double* __
         const int hi = a > b ? a : b, lo = a > b ? b : a;
         const double mlo = s[sidx(d, lo)] / s0;
         double x = (s[sidx(hi, lo)] - s[sidx(d, hi)] * mlo) / s0;
-        if (a == b) x += 1e-15;                                                      // ML/EM.cpp:252
+        if (a == b) x += ridge;                                                      // ML/EM.cpp:252 (its 1e-15: the handle's ridge)
         v.L[e] = x;
         v.Wt[e] = a == b ? 1.0 : 0.0;
         covs[(size_t)k * d * d + e] = x;
@@ -463,7 +463,7 @@ void launch_em_close_big(const CloseArgs& a, hipStream_t stream)
 {
     const int d = a.d, K = a.K;
     hipLaunchKernelGGL(close_big_prepare_kernel, dim3(K, (unsigned)(((size_t)d * d + 255) / 256)), dim3(256), 0, stream, a.stats, K, d, a.shift,
-                       a.n_global, a.refine_limit, a.mixing, a.means, a.covs, a.work);
+                       a.n_global, a.ridge, a.refine_limit, a.mixing, a.means, a.covs, a.work);
     factor_and_finish(a.stats, a.mixing, a, stream);
 }
 

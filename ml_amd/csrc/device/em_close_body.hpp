@@ -35,7 +35,7 @@ __host__ __device__ constexpr size_t scratch_doubles(int d) { return (size_t)(d 
 /// operations on the host's operands, so the bits are the host's (host/em_math.cpp finalize_mstep).
 template <int LAYOUT, int DT, bool STATS_LOCAL = false, typename Probe = NoProbe>
 __device__ __forceinline__ void close_component(const double* __restrict__ stats, int K, int d, int D, const double* __restrict__ shift,
-                                                double n_global, double refine_limit, double* __restrict__ mixing,
+                                                double n_global, double ridge, double refine_limit, double* __restrict__ mixing,
                                                 double* __restrict__ means, double* __restrict__ covs, double* __restrict__ records,
                                                 int PS, double* __restrict__ info, const int k, const int tid, double* sm,
                                                 const Probe& probe = Probe())
@@ -74,7 +74,7 @@ __device__ __forceinline__ void close_component(const double* __restrict__ stats
         const int hi = a > b ? a : b, lo = a > b ? b : a;
         const double mlo = s[sidx(d, lo)] / s0;                                      // = m[lo]: formed again here instead of fetched through LDS behind a barrier
         double v = (s[sidx(hi, lo)] - s[sidx(d, hi)] * mlo) / s0;
-        if (a == b) v += 1e-15;                                                      // ML/EM.cpp:252
+        if (a == b) v += ridge;                                                      // ML/EM.cpp:252 (its 1e-15: the handle's ridge)
         A[e] = v;
         covs[(size_t)k * d * d + e] = v;
     }

@@ -252,7 +252,7 @@ void build_estep_params(int d, int D, int K, const double* mixing, const double*
     });
 }
 
-void finalize_mstep(int d, int K, const double* stats, const double* shift, double n_global, double* mixing,
+void finalize_mstep(int d, int K, const double* stats, const double* shift, double n_global, double ridge, double* mixing,
                     double* means, double* covariances)
 {
     const int F = stats_count(d);
@@ -270,8 +270,7 @@ void finalize_mstep(int d, int K, const double* stats, const double* shift, doub
                 cov[b * d + a] = v;
                 cov[a * d + b] = v;
             }
-        static constexpr double epsilon = 1e-15;   // ML/EM.cpp:252
-        for (int a = 0; a < d; ++a) cov[a * d + a] += epsilon;
+        for (int a = 0; a < d; ++a) cov[a * d + a] += ridge;   // ML/EM.cpp:252 (its 1e-15: the handle's ridge)
         mixing[k] = s0 / n_global;                 // ML/EM.cpp:257
     });
 }
@@ -312,7 +311,7 @@ void build_diag_params(int d, int D, int K, int K_padded, const double* mixing, 
     }
 }
 
-void finalize_mstep_diag(int d, int K, const double* stats, const double* shift, double n_global, double* mixing,
+void finalize_mstep_diag(int d, int K, const double* stats, const double* shift, double n_global, double ridge, double* mixing,
                          double* means, double* variances)
 {
     const int F = diag_stats_count(d);
@@ -322,7 +321,7 @@ void finalize_mstep_diag(int d, int K, const double* stats, const double* shift,
         for (int a = 0; a < d; ++a) {
             const double m = s[a] / s0;
             means[(size_t)k * d + a] = shift[a] + m;
-            variances[(size_t)k * d + a] = (s[d + a] - s[a] * m) / s0 + 1e-15;   // ridge: ML/EM.cpp:252
+            variances[(size_t)k * d + a] = (s[d + a] - s[a] * m) / s0 + ridge;   // ridge: ML/EM.cpp:252
         }
         mixing[k] = s0 / n_global;                                                // ML/EM.cpp:257
     }
@@ -351,7 +350,7 @@ void build_tied_params(int d, int D, int K, int K_padded, const double* mixing, 
 }
 
 void finalize_mstep_tied(int d, int K, const double* stats, const double* total_scatter, const double* shift, double total_weight,
-                         double* mixing, double* means, double* covariance)
+                         double ridge, double* mixing, double* means, double* covariance)
 {
     const int F = tied_stats_count(d);
     std::vector<double> m((size_t)K * d);
@@ -372,7 +371,7 @@ void finalize_mstep_tied(int d, int K, const double* stats, const double* total_
             covariance[(size_t)b * d + a] = v;
             covariance[(size_t)a * d + b] = v;
         }
-    for (int a = 0; a < d; ++a) covariance[(size_t)a * d + a] += 1e-15;         // ridge: ML/EM.cpp:252, once
+    for (int a = 0; a < d; ++a) covariance[(size_t)a * d + a] += ridge;         // ridge: ML/EM.cpp:252, once
 }
 
 void set_host_ranks(int local_ranks) { g_host_threads.store(resolve_host_threads(local_ranks), std::memory_order_relaxed); }

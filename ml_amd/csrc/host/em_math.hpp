@@ -28,9 +28,10 @@ bool build_estep_params_mfma4(int d, int D, int K, const double* mixing, const d
                               const double* shift, double fold_limit, double* records);
 
 /// M-step closing arithmetic from the all-reduced shifted statistics (device/device.hpp stats_count):
-///   mean_k = shift + S1'/S0 ; cov_k = (M2' - S1' (S1'/S0)^T) / S0 + 1e-15 I ; pi_k = S0 / N.
+///   mean_k = shift + S1'/S0 ; cov_k = (M2' - S1' (S1'/S0)^T) / S0 + ridge I ; pi_k = S0 / N.
 /// Algebraically the reference's  sum_i r_ik (x_i - mean_k)(x_i - mean_k)^T / S0  (ML/EM.cpp:245-257).
-void finalize_mstep(int d, int K, const double* stats, const double* shift, double n_global, double* mixing,
+/// `ridge` is the data handle's covariance ridge (mlhip.h: default 1e-15, the constant of ML/EM.cpp:252), one plain add per diagonal entry.
+void finalize_mstep(int d, int K, const double* stats, const double* shift, double n_global, double ridge, double* mixing,
                     double* means, double* covariances);
 
 /// Diagonal-covariance extension: K_padded records [mean(D) | 1/sigma^2 (D) | log(pi) - sum log sigma | two-op flag] and the
@@ -42,8 +43,8 @@ void build_diag_params(int d, int D, int K, int K_padded, const double* mixing, 
                        const double* shift, double* records);
 
 /// Diagonal closing arithmetic from the all-reduced statistics [S1'(d) | S2'(d) | S0] per component:
-///   mean_k = shift + S1'/S0 ; var_kj = (S2'_j - S1'_j (S1'_j/S0)) / S0 + 1e-15 ; pi_k = S0 / N   (ML/EM.cpp:242-257, diagonal).
-void finalize_mstep_diag(int d, int K, const double* stats, const double* shift, double n_global, double* mixing,
+///   mean_k = shift + S1'/S0 ; var_kj = (S2'_j - S1'_j (S1'_j/S0)) / S0 + ridge ; pi_k = S0 / N   (ML/EM.cpp:242-257, diagonal).
+void finalize_mstep_diag(int d, int K, const double* stats, const double* shift, double n_global, double ridge, double* mixing,
                          double* means, double* variances);
 
 /// Tied-covariance extension (ONE Sigma = L L^T for all components): the whitening block winv = L^-1 (layout.hpp
@@ -54,10 +55,10 @@ void build_tied_params(int d, int D, int K, int K_padded, const double* mixing, 
 
 /// Tied closing arithmetic from the all-reduced statistics [S1'(d) | S0] per component and the total scatter
 /// T = sum_i w_i xt_i xt_i^T (packed like one component's full statistics: stats_count(d) doubles, xt = [x - shift ; 1]):
-///   mean_k = shift + S1'_k/S0_k ; pi_k = S0_k / W ; Sigma = (T - sum_k S1'_k (S1'_k/S0_k)^T) / W + 1e-15 I
+///   mean_k = shift + S1'_k/S0_k ; pi_k = S0_k / W ; Sigma = (T - sum_k S1'_k (S1'_k/S0_k)^T) / W + ridge I
 /// (k ascending per entry; the ridge of ML/EM.cpp:252-256 once) == sum_k pi_k Sigma_k over finalize_mstep's Sigma_k.
 void finalize_mstep_tied(int d, int K, const double* stats, const double* total_scatter, const double* shift, double total_weight,
-                         double* mixing, double* means, double* covariance);
+                         double ridge, double* mixing, double* means, double* covariance);
 
 /// Tells the host-side math how many ranks share this node, so that the OpenMP teams of the per-component
 /// factorizations together stay within the host's cores (MLHIP_HOST_THREADS overrides the per-rank thread count).

@@ -83,6 +83,13 @@ void EM::set_relative_tolerance(double relative_tolerance)
     relative_tolerance_ = relative_tolerance;
 }
 
+void EM::set_covariance_regularisation(double covariance_regularisation)
+{
+    if (!(covariance_regularisation >= 0) || !std::isfinite(covariance_regularisation))
+        throw std::domain_error("EM: Negative covariance regularisation");
+    covariance_regularisation_ = covariance_regularisation;
+}
+
 void EM::set_maximum_steps(unsigned int maximum_steps)
 {
     if (maximum_steps < 2) throw std::invalid_argument("EM: At least two steps required for convergence test");
@@ -192,6 +199,8 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
     // Row weights stay attached for the handle's lifetime: every statistics pass and log-likelihood below is weighted, the
     // initialisers' draws and the nearest-centroid pass see rows (mlhip.h, mlhip_data_set_weights).
     if (weights) check(mlhip_data_set_weights(ctx, dev.h, weights));
+    // Before any M-step, so that the `maximise_first` start is regularised like every later one (mlhip_data_set_covariance_ridge).
+    check(mlhip_data_set_covariance_ridge(ctx, dev.h, covariance_regularisation_));
     uint64_t n_global = 0;
     check(mlhip_data_shape(dev.h, nullptr, nullptr, &n_global));
     if (n_global < K) throw std::invalid_argument("EM: Not enough data ");       // the same on every rank

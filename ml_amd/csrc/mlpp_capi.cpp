@@ -108,6 +108,8 @@ int mlpp_em_destroy(mlpp_em* h) { delete h; return MLHIP_OK; }
 int mlpp_em_set_seed(mlpp_em* h, uint32_t v) { return guarded([&] { need(h); h->em.set_seed(v); }); }
 int mlpp_em_set_absolute_tolerance(mlpp_em* h, double v) { return guarded([&] { need(h); h->em.set_absolute_tolerance(v); }); }
 int mlpp_em_set_relative_tolerance(mlpp_em* h, double v) { return guarded([&] { need(h); h->em.set_relative_tolerance(v); }); }
+int mlpp_em_set_covariance_regularisation(mlpp_em* h, double v) { return guarded([&] { need(h); h->em.set_covariance_regularisation(v); }); }
+int mlpp_em_covariance_regularisation(const mlpp_em* h, double* out) { return guarded([&] { need(h); need(out); *out = h->em.covariance_regularisation(); }); }
 int mlpp_em_set_maximum_steps(mlpp_em* h, uint32_t v) { return guarded([&] { need(h); h->em.set_maximum_steps(v); }); }
 int mlpp_em_set_means_initialiser(mlpp_em* h, const mlpp_centroids_initialiser* i) { return guarded([&] { need(h); h->em.set_means_initialiser(i ? i->p : nullptr); }); }
 int mlpp_em_set_responsibilities_initialiser(mlpp_em* h, const mlpp_responsibilities_initialiser* i) { return guarded([&] { need(h); h->em.set_responsibilities_initialiser(i ? i->p : nullptr); }); }

@@ -287,6 +287,25 @@ int mlhip_data_weight_sum(const mlhip_data* data, double* total)
     });
 }
 
+int mlhip_data_set_covariance_ridge(mlhip_ctx* ctx, mlhip_data* data, double ridge)
+{
+    return guarded([&] {
+        check_call(ctx, data, 1);
+        require_ridge(ridge);                                  // (before anything changes: a refused value leaves the handle as it was)
+        if (ctx->group) fan_out(ctx, data, [&](Shard& sh) { return mlhip_data_set_covariance_ridge(sh.ctx, sh.part, ridge); });
+        // only M-steps read it: E-step results, the workspace and the tied mode's total scatter stay valid
+        data->ridge = ridge + 0.0;                             // (-0.0 counts as 0)
+    });
+}
+
+int mlhip_data_covariance_ridge(const mlhip_data* data, double* ridge)
+{
+    return guarded([&] {
+        require(data && ridge, "null argument");
+        *ridge = data->ridge;
+    });
+}
+
 int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance)
 {
     return guarded([&] {

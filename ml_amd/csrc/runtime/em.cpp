@@ -395,7 +395,7 @@ void refine_component(mlhip_data* dt, const EmRoute& r, int k, double* mean_k, d
             cov_k[a2 * d + b] = v;
         }
     for (int a2 = 0; a2 < d; ++a2) {
-        cov_k[a2 * d + a2] += 1e-15;                                            // ML/EM.cpp:252
+        cov_k[a2 * d + a2] += dt->ridge;                                        // ML/EM.cpp:252
         mean_k[a2] += m[a2];
     }
 }
@@ -418,7 +418,7 @@ static bool needs_refinement(int d, const double* mean, const double* shift, con
 void finalize_out(mlhip_data* dt, const EmRoute& r, int K, double* mixing_out, double* means_out, double* cov_out)
 {
     const int d = dt->d;
-    host::finalize_mstep(d, K, dt->stats_host.as<double>(), dt->shift.data(), dt->total_weight(), mixing_out,
+    host::finalize_mstep(d, K, dt->stats_host.as<double>(), dt->shift.data(), dt->total_weight(), dt->ridge, mixing_out,
                          means_out, cov_out);
     const double limit = refine_ratio();
     if (!(limit > 0)) return;
@@ -524,7 +524,7 @@ void refine_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixing
         const double s0 = s[2 * d];
         for (int a = 0; a < d; ++a) {
             const double m = s[a] / s0;                                      // ~0: the shift is the mean already
-            variances_out[(size_t)k * d + a] = (s[d + a] - s[a] * m) / s0 + 1e-15;
+            variances_out[(size_t)k * d + a] = (s[d + a] - s[a] * m) / s0 + data->ridge;
             means_out[(size_t)k * d + a] += m;
         }
     }
@@ -555,7 +555,7 @@ void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixin
     const int F = diag_stats_count(d);
     const double* st = data->stats_host.as<double>();
     *log_likelihood = st[(size_t)K * F] / (double)data->n_global - (double)d * log_two_pi() / 2;   // ML/EM.cpp:197-198, 211
-    host::finalize_mstep_diag(d, K, st, data->shift.data(), (double)data->n_global, mixing_out, means_out, variances_out);
+    host::finalize_mstep_diag(d, K, st, data->shift.data(), (double)data->n_global, data->ridge, mixing_out, means_out, variances_out);
     refine_diag(data, r, K, mixing_out, means_out, variances_out);
 }
 
@@ -600,7 +600,7 @@ void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mix
     if (r.kernel != kTiedKernel) {
         // COMPOSED: one full-covariance step on K copies of the covariance, on whatever route this shape takes (weights, the
         // refinement pass, big dimensions and the plain tier included), then  Sigma = sum_k pi_k Sigma_k  in ascending k -- the tied
-        // M-step, since sum_k S0_k Sigma_k = T - sum_k S1_k S1_k^T / S0_k. Every Sigma_k carries the ridge 1e-15 I (ML/EM.cpp:252),
+        // M-step, since sum_k S0_k Sigma_k = T - sum_k S1_k S1_k^T / S0_k. Every Sigma_k carries the handle's ridge r I (ML/EM.cpp:252),
         // and sum_k pi_k = 1 up to rounding: the K ridges pool to the one ridge of the tied mode. Nothing is subtracted or re-added.
         // Slower than it could be, never refused.
         const std::vector<double> covs = tied_as_full(K, d, cov);
@@ -627,8 +627,8 @@ void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mix
     const int F = tied_stats_count(d);
     const double* st = data->stats_host.as<double>();
     *log_likelihood = st[(size_t)K * F] / (double)data->n_global - (double)d * log_two_pi() / 2;   // ML/EM.cpp:197-198, 211
-    host::finalize_mstep_tied(d, K, st, data->total_scatter.data(), data->shift.data(), (double)data->n_global, mixing_out, means_out,
-                              cov_out);
+    host::finalize_mstep_tied(d, K, st, data->total_scatter.data(), data->shift.data(), (double)data->n_global, data->ridge, mixing_out,
+                              means_out, cov_out);
 }
 
 
@@ -897,22 +897,38 @@ int mlhip_em_statistics_count(uint32_t d, uint32_t* count_per_component)
     });
 }
 
-int mlhip_em_finalize_statistics(uint32_t d, uint32_t K, const double* statistics, const double* shift, double n_global,
-                                 double* mixing_out, double* means_out, double* covariances_out)
+int mlhip_em_finalize_statistics_ridge(uint32_t d, uint32_t K, const double* statistics, const double* shift, double n_global, double ridge,
+                                       double* mixing_out, double* means_out, double* covariances_out)
 {
     return guarded([&] {
         require(d >= 1 && K >= 1 && statistics && shift && mixing_out && means_out && covariances_out, "bad argument");
-        host::finalize_mstep((int)d, (int)K, statistics, shift, n_global, mixing_out, means_out, covariances_out);
+        require_ridge(ridge);
+        host::finalize_mstep((int)d, (int)K, statistics, shift, n_global, ridge, mixing_out, means_out, covariances_out);
+    });
+}
+
+int mlhip_em_finalize_statistics(uint32_t d, uint32_t K, const double* statistics, const double* shift, double n_global,
+                                 double* mixing_out, double* means_out, double* covariances_out)
+{
+    return mlhip_em_finalize_statistics_ridge(d, K, statistics, shift, n_global, MLHIP_DEFAULT_COVARIANCE_RIDGE, mixing_out, means_out,
+                                              covariances_out);
+}
+
+int mlhip_em_finalize_statistics_tied_ridge(uint32_t d, uint32_t K, const double* statistics, const double* total_scatter, const double* shift,
+                                            double total_weight, double ridge, double* mixing_out, double* means_out, double* covariance_out)
+{
+    return guarded([&] {
+        require(d >= 1 && K >= 1 && statistics && total_scatter && shift && mixing_out && means_out && covariance_out, "bad argument");
+        require_ridge(ridge);
+        host::finalize_mstep_tied((int)d, (int)K, statistics, total_scatter, shift, total_weight, ridge, mixing_out, means_out, covariance_out);
     });
 }
 
 int mlhip_em_finalize_statistics_tied(uint32_t d, uint32_t K, const double* statistics, const double* total_scatter, const double* shift,
                                       double total_weight, double* mixing_out, double* means_out, double* covariance_out)
 {
-    return guarded([&] {
-        require(d >= 1 && K >= 1 && statistics && total_scatter && shift && mixing_out && means_out && covariance_out, "bad argument");
-        host::finalize_mstep_tied((int)d, (int)K, statistics, total_scatter, shift, total_weight, mixing_out, means_out, covariance_out);
-    });
+    return mlhip_em_finalize_statistics_tied_ridge(d, K, statistics, total_scatter, shift, total_weight, MLHIP_DEFAULT_COVARIANCE_RIDGE,
+                                                   mixing_out, means_out, covariance_out);
 }
 
 int mlhip_em_tied_route(const mlhip_data* data, uint32_t K, int* kernel)

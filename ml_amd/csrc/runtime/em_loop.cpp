@@ -130,7 +130,7 @@ struct EmLoop {
         CloseArgs ca{};
         ca.stats = data->stats_dev.as<double>(); ca.K = K; ca.d = d; ca.D = data->D;
         ca.shift = data->shift_dev.as<double>(); ca.n_global = data->total_weight();
-        ca.layout = layout; ca.refine_limit = refine_limit;
+        ca.layout = layout; ca.refine_limit = refine_limit; ca.ridge = data->ridge;
         ca.mixing = pack_mixing(out); ca.means = pack_means(out); ca.covs = pack_covs(out);
         ca.records = rec[out]->as<double>();
         ca.info = data->it_info_slot[out].as<double>();
@@ -168,7 +168,7 @@ struct EmLoop {
             a.mixing[s] = pack_mixing(s); a.means[s] = pack_means(s); a.covs[s] = pack_covs(s);
         }
         a.xch = data->it_xch.as<double>(); a.sync = data->it_sync.as<unsigned>(); a.vgrid = resident_grid;
-        a.n_global = (double)data->n_global; a.refine_limit = refine_limit; a.atol = test.atol; a.rtol = test.rtol;
+        a.n_global = (double)data->n_global; a.ridge = data->ridge; a.refine_limit = refine_limit; a.atol = test.atol; a.rtol = test.rtol;
         a.ll_offset = (double)d * log_two_pi() / 2;                       // (read(): the same expression)
         a.max_steps = max_steps; a.history = history; a.result = result;
         // MLHIP_RESIDENT_PROFILE=1: per-phase clock stamps of workgroup 0, averaged over the iterations, on stderr (diagnostic)
@@ -281,7 +281,7 @@ struct EmLoop {
                                  ctx->stream));
         ctx->sync();
         if (diag) {
-            host::finalize_mstep_diag(d, K, data->stats_host.as<double>(), data->shift.data(), (double)data->n_global, mixing, means, covs);
+            host::finalize_mstep_diag(d, K, data->stats_host.as<double>(), data->shift.data(), (double)data->n_global, data->ridge, mixing, means, covs);
             refine_diag(data, route, K, mixing, means, covs);
             upload_diag_records(data, K, mixing, means, covs, *rec[out]);
             shadow[out].assign(mixing, mixing + K);

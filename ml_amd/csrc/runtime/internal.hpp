@@ -483,6 +483,9 @@ struct mlhip_data {
     uint64_t rows() const { return parts.empty() ? (uint64_t)n : n_global; }
     /// What the log-likelihood and the mixing proportions are divided by: W, or the row count of an unweighted block.
     double total_weight() const { return weighted ? weight_sum : (double)n_global; }
+    // Covariance ridge (mlhip_data_set_covariance_ridge; a group's handle mirrors its parts'): what every M-step on this handle adds
+    // to the diagonal of each covariance it FORMS -- on the host and as an argument of the device closings. Finite, >= 0.
+    double ridge = MLHIP_DEFAULT_COVARIANCE_RIDGE;
     // EM workspace (sized for em_K)
     int em_K = 0;
     size_t ldr = 0;
@@ -557,6 +560,8 @@ struct PhaseTrace {
 };
 
 inline void require(bool ok, const char* msg) { if (!ok) throw InvalidArgument(msg); }
+/// A covariance ridge (mlhip.h): finite and >= 0 (NaN fails the comparison).
+inline void require_ridge(double ridge) { require(ridge >= 0 && std::isfinite(ridge), "the covariance ridge must be finite and >= 0"); }
 
 /// What one K-means pass runs on: the data block (a zero-padded copy where the matrix-core kernel needs one) and its rows.
 struct KmBlock {
