@@ -334,7 +334,7 @@ int mlhip_kmeans_assign(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const doub
  *   sum_i w_i x_i / sum_i w_i per cluster, a cluster of total weight 0 (empty, or rows of weight 0 only) at the origin.
  * Labels, per-row distances (mlhip_kmeans_labels / _distances) and *n_changed (a count of ROWS) do not depend on the weights: they
  * are, bit for bit, those of the unweighted call -- the assignment kernel of the shape's route runs unchanged, without its own
- * accumulation, and one more sweep over X, the labels, the distances and the weights forms the sums (device/kmeans_weighted.hip); the
+ * accumulation, and one more sweep over X, the labels, the distances and the weights forms the sums (the weighted form of device/kmeans.hip's update sweep); the
  * weighted iterate never takes the one-launch resident loop. With integer weights the results are those of the unweighted calls on
  * the sample with row i repeated w_i times. The sums are exact sums of the rounded products w_i x_ij on a fixed-point grid set by the
  * largest weight and the largest |x_j| of the WHOLE sample (exchanged across ranks, cached on the handle until the weights change),

@@ -16,6 +16,7 @@
 
 #include "device.hpp"
 #include "em_mstats_common.hpp"
+#include "exact_sum.hpp"
 #include "exp_nonpos.hpp"
 
 namespace mlhip {
@@ -438,21 +439,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_big_kernel(const double* __
             changed += (!have_old || old_labels[i1] != arg1) ? 1.0 : 0.0;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        inertia += __shfl_down(inertia, off, 64);
-        changed += __shfl_down(changed, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6] = inertia;
-        red[4 + (threadIdx.x >> 6)] = changed;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* my_part = partials + (size_t)blockIdx.x * pstride;
-        my_part[0] = ((red[0] + red[1]) + red[2]) + red[3];
-        my_part[1] = ((red[4] + red[5]) + red[6]) + red[7];
-    }
+    fold_block_sums<4>(inertia, changed, red, partials + (size_t)blockIdx.x * pstride);
 }
 
 }  // namespace

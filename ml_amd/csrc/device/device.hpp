@@ -331,6 +331,9 @@ int launch_kmeans_assign(const KmeansArgs& a, int num_cus, hipStream_t stream);
 void launch_kmeans_assign_generic(const KmeansArgs& a, int grid, size_t pstride, hipStream_t stream);   // d > kMaxDim (generic_dim.hip)
 /// 128 < d <= 1024 (big_dim.hip): the same exact arithmetic, register-blocked; returns the partial blocks used, 0: not applicable.
 int launch_kmeans_assign_big(const KmeansArgs& a, int grid_max, size_t pstride, hipStream_t stream);
+/// The update sums as a sweep of their own (kmeans.hip), over the `grid` partial blocks the assignment kernel just wrote: every route
+/// whose accumulators do not fit LDS beside its assignment.
+void launch_kmeans_update(const KmeansArgs& a, int grid, size_t pstride, hipStream_t stream);
 void launch_kmeans_reduce(const KmeansArgs& a, int n_partials, hipStream_t stream);
 /// update_step's closing arithmetic on the (all-reduced) output block [inertia, changed, counts(K), sums(K*d)]: the sums
 /// become the means IN PLACE (empty cluster -> origin, ML/KMeans.cpp:184) and are written as the next centroid table
@@ -339,7 +342,7 @@ void launch_kmeans_reduce(const KmeansArgs& a, int n_partials, hipStream_t strea
 /// through a copy engine and costs more than the kernel itself.
 void launch_kmeans_close(double* out, int K, int d, int D, double* next, double* mirror, hipStream_t stream);
 
-/// Weighted update sweep + its reduction (kmeans_weighted.hip), after an assignment that ran with accumulate = 0: out[0] becomes the
+/// Weighted update sweep + its reduction (kmeans.hip: the weighted forms of the update sweep and of the reduction), after an assignment that ran with accumulate = 0: out[0] becomes the
 /// weighted inertia sum_i w_i min_dist_i and, with_sums != 0, out[2 ..] the weighted counts sum_i w_i (K) and the sums sum_i w_i x_i
 /// (K*d), exact sums of the rounded products; out[1] (n_changed) is not touched. `factors` (device, 2d + 2 doubles, powers of two):
 /// [f1 (d) | f2 (d) | c1 | c2] with f1_j f2_j = 2^(94 - ej - ew) and c1 c2 = 2^(94 - ew), max|x_j| < 2^ej, max w < 2^ew over all

@@ -10,6 +10,7 @@
 //   * kmeans_assign_generic_kernel  KMeans::assignment_step   (ML/KMeans.cpp:153-178)
 #include "device.hpp"
 #include "em_mstats_common.hpp"
+#include "exact_sum.hpp"
 #include "exp_nonpos.hpp"
 
 namespace mlhip {
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void em_mstats_generic_kernel(const double* __
 
 /// One lane per sample, the reference's loop over the clusters (strict '<', ascending k) with the ascending-j fma chain of every
 /// other kernel; [inertia, changed] per workgroup in the partial block's first two doubles. The update sums come from the
-/// separate sweep (kmeans_update_kernel), which is dimension-generic.
+/// separate sweep (kmeans_update_kernel of kmeans.hip), which is dimension-generic.
 __global__ __launch_bounds__(256) void kmeans_assign_generic_kernel(const double* __restrict__ xt, size_t ldx, uint32_t n, int D,
                                                                      const double* __restrict__ cent, int K,
                                                                      uint32_t* __restrict__ labels, const uint32_t* __restrict__ old_labels,
@@ -133,18 +134,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_generic_kernel(const double
         inertia += best;
         changed += (!have_old || old_labels[i] != arg) ? 1.0 : 0.0;
     }
-    inertia = wave_sum_fixed(inertia);
-    changed = wave_sum_fixed(changed);
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6] = inertia;
-        red[4 + (threadIdx.x >> 6)] = changed;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* my_part = partials + (size_t)blockIdx.x * pstride;
-        my_part[0] = ((red[0] + red[1]) + red[2]) + red[3];
-        my_part[1] = ((red[4] + red[5]) + red[6]) + red[7];
-    }
+    fold_block_sums<4>(inertia, changed, red, partials + (size_t)blockIdx.x * pstride);
 }
 
 }  // namespace

@@ -16,6 +16,10 @@
 // workgroups or GPUs contribute: the update step is bitwise reproducible run to run (floating-point atomics are not),
 // which the reference's own test relies on (same seed => same fit => inertia of 3 initialisations <= inertia of the
 // first, Tests/test_KMeans.cpp:75-79). A limb sum cannot overflow: 2^32 samples x 2^32 per limb < 2^64.
+//
+// The limb arithmetic and the workgroup's fixed-order [inertia, n_changed] sums are exact_sum.hpp's; the chunked LDS sweep
+// (kmeans_update_kernel), its chunk plan (sweep_chunks) and the reduction over the partial blocks (kmeans_reduce_element) each exist
+// once, in this file, in an unweighted and a weighted instantiation. No floating-point atomics; plain vector stores.
 #include <cstdlib>
 
 #include "device.hpp"
@@ -106,35 +110,18 @@ __global__ __launch_bounds__(BS) void kmeans_assign_kernel(
             u64* row = (USE_LDS ? acc_lds + (size_t)(tid & (copies - 1)) * K * W : my_words) + (size_t)arg * W;
 #pragma unroll
             for (int j = 0; j < D; ++j) {
-                if (j < d) {
-                    u64 w0, w1, w2;
-                    split_limbs(x[j] * sc[j], w0, w1, w2);
-                    atomicAdd(row + 3 * j, w0);
-                    atomicAdd(row + 3 * j + 1, w1);
-                    atomicAdd(row + 3 * j + 2, w2);
-                }
+                if (j < d) add_limbs(row, j, x[j] * sc[j]);
             }
             atomicAdd(row + 3 * d, (u64)1);
         }
     }
-    // block sums of inertia / changed (fixed order)
+    // block sums of inertia / changed (fixed order): fold_block_sums, its shuffle tree spelled out (see there)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         inertia += __shfl_down(inertia, off, 64);
         changed += __shfl_down(changed, off, 64);
     }
-    constexpr int NWV = BS / 64;
-    if ((tid & 63) == 0) {
-        red[tid >> 6] = inertia;
-        red[NWV + (tid >> 6)] = changed;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double a = 0.0, b = 0.0;
-        for (int w = 0; w < NWV; ++w) { a += red[w]; b += red[NWV + w]; }   // fixed order
-        my_part[0] = a;
-        my_part[1] = b;
-    }
+    fold_wave_sums<BS / 64>(inertia, changed, red, my_part);
     if (accumulate && USE_LDS) {
         for (int e = tid; e < K * W; e += BS) {
             u64 v = acc_lds[e];
@@ -151,52 +138,116 @@ __global__ __launch_bounds__(BS) void kmeans_assign_kernel(
 /// are the clusters chunked as well (KC < K: lanes outside the chunk idle). Same exact limb sums as the fused path
 /// (ds_add_u64), flushed per chunk into the workgroup's partial block -- instead of global-memory atomics, which serialise
 /// on popular clusters (N=12.5M, d=16, K=256: 25 ms; this sweep: 0.7 ms on top of the 2.2 ms assignment).
+///
+/// WEIGHTED (EXTENSION, mlhip_kmeans_*_weighted): the same sweep over the UNPADDED block and the row weights, after the assignment of
+/// the shape's route ran with accumulate = 0 (labels and distances do not depend on the weights) and was reduced. Three things differ:
+///  - the value that is cut into limbs. The sums are EXACT sums of rounded products: p = w_i x_ij is one IEEE product;
+///    t = p 2^(94 - ej - ew) with max|x_j| < 2^ej and max w < 2^ew over the WHOLE sample (all ranks), so |t| < 2^94, and the scaling is
+///    exact: it is applied as two powers of two f1_j, f2_j (each a normal double whatever ej + ew is; the runtime chooses them,
+///    KmWeightedArgs::factors = `scale` here: [f1 (d) | f2 (d) | c1 | c2]). What lies below one unit, i.e. below
+///    2^-94 max w max|x_j|, is dropped. A row of weight 0 is skipped: it adds 0 to every word;
+///  - the count: sum_i w_i from w_i 2^(94 - ew) = (w_i c1) c2, three limbs like a coordinate -- a cluster takes 3d + 3 words, not 3d + 1;
+///  - a prologue writes the block's first two doubles [inertia_w, 0] from the distances the assignment stored; `with_sums` = 0: that
+///    alone (mlhip_kmeans_assign_weighted).
 constexpr int BSU = 1024;
+template <bool WEIGHTED>
 __global__ __launch_bounds__(BSU) void kmeans_update_kernel(
     const double* __restrict__ xt, size_t ldx, uint32_t n, int d, const uint32_t* __restrict__ labels,
-    const double* __restrict__ scale, int K, int KC, int DC, double* __restrict__ partials, size_t pstride)
+    const double* __restrict__ scale, int K, int KC, int DC, double* __restrict__ partials, size_t pstride,
+    const double* __restrict__ min_dist, const double* __restrict__ w, int with_sums)
 {
-    extern __shared__ u64 acc_lds[];      // [KC][3*DC + 1]
+    constexpr int CW = WEIGHTED ? 3 : 1;  // count words per cluster
+    extern __shared__ u64 acc_lds[];      // [KC][3*DC + CW]
     const int tid = threadIdx.x;
-    const int W = 3 * d + 1;              // words per cluster in the partial block
-    const int WC = 3 * DC + 1;            // words per cluster in LDS (last one: the count, used by the first dim chunk)
-    u64* my_words = reinterpret_cast<u64*>(partials + (size_t)blockIdx.x * pstride + 2);
+    const int W = 3 * d + CW;             // words per cluster in the partial block: the limbs of d sums, then the count
+    const int WC = 3 * DC + CW;           // words per cluster in LDS (the last CW: the count, used by the first dim chunk)
+    double* my_part = partials + (size_t)blockIdx.x * pstride;
+    u64* my_words = reinterpret_cast<u64*>(my_part + 2);
+    const uint32_t first = blockIdx.x * (uint32_t)BSU + tid, stride = gridDim.x * (uint32_t)BSU;
+    const double* __restrict__ scale2 = scale + d;            // WEIGHTED: the second factor of every dimension, then c1, c2
+    double c1 = 0.0, c2 = 0.0;
+    if constexpr (WEIGHTED) {
+        // weighted inertia: per-lane sums in row order, then the fixed-order wave and workgroup tree of the unweighted inertia
+        __shared__ double red[BSU / 64];
+        double inertia = 0.0;
+        {
+#pragma clang fp contract(off)
+            for (uint32_t i = first; i < n; i += stride) {
+                const double p = w[i] * min_dist[i];
+                inertia += p;
+            }
+        }
+        fold_block_sums<BSU / 64, false>(inertia, 0.0, red, my_part);
+        if (!with_sums) return;
+        c1 = scale2[d];
+        c2 = scale2[d + 1];
+    }
     for (int k0 = 0; k0 < K; k0 += KC) {
         const int kc = min(KC, K - k0);
         for (int j0 = 0; j0 < d; j0 += DC) {
             const int dc = min(DC, d - j0);
             for (int e = tid; e < kc * WC; e += BSU) acc_lds[e] = 0;
             __syncthreads();
-            for (uint32_t i = blockIdx.x * (uint32_t)BSU + tid; i < n; i += gridDim.x * (uint32_t)BSU) {
+            for (uint32_t i = first; i < n; i += stride) {
                 const uint32_t rel = labels[i] - (uint32_t)k0;
-                if (rel < (uint32_t)kc) {
+                double wi = 1.0;
+                if constexpr (WEIGHTED) wi = w[i];
+                if (rel < (uint32_t)kc && (!WEIGHTED || wi != 0.0)) {
                     u64* row = acc_lds + (size_t)rel * WC;
                     for (int j = 0; j < dc; ++j) {
-                        u64 w0, w1, w2;
-                        split_limbs(xt[(size_t)(j0 + j) * ldx + i] * scale[j0 + j], w0, w1, w2);
-                        atomicAdd(row + 3 * j, w0);
-                        atomicAdd(row + 3 * j + 1, w1);
-                        atomicAdd(row + 3 * j + 2, w2);
+                        const double x = xt[(size_t)(j0 + j) * ldx + i];
+                        if constexpr (WEIGHTED) {
+                            const double p = wi * x;
+                            add_limbs(row, j, (p * scale[j0 + j]) * scale2[j0 + j]);
+                        } else {
+                            add_limbs(row, j, x * scale[j0 + j]);
+                        }
                     }
-                    if (j0 == 0) atomicAdd(row + 3 * DC, (u64)1);
+                    if (j0 == 0) {
+                        if constexpr (WEIGHTED) add_limbs(row, DC, (wi * c1) * c2);
+                        else atomicAdd(row + 3 * DC, (u64)1);
+                    }
                 }
             }
             __syncthreads();
             for (int e = tid; e < kc * 3 * dc; e += BSU) {
-                const int k = e / (3 * dc), w = e - k * 3 * dc;
-                my_words[(size_t)(k0 + k) * W + 3 * j0 + w] = acc_lds[(size_t)k * WC + w];
+                const int k = e / (3 * dc), v = e - k * 3 * dc;
+                my_words[(size_t)(k0 + k) * W + 3 * j0 + v] = acc_lds[(size_t)k * WC + v];
             }
             if (j0 == 0)
-                for (int k = tid; k < kc; k += BSU) my_words[(size_t)(k0 + k) * W + 3 * d] = acc_lds[(size_t)k * WC + 3 * DC];
+                for (int e = tid; e < kc * CW; e += BSU) {
+                    const int k = e / CW, v = e - k * CW;
+                    my_words[(size_t)(k0 + k) * W + 3 * d + v] = acc_lds[(size_t)k * WC + 3 * DC + v];
+                }
             __syncthreads();
         }
     }
 }
 
+/// (KC, DC) of a sweep: as many whole dimensions of all K clusters as fit `budget` words of LDS (a cluster takes 3 words per dimension
+/// and `count_words` for its count); if not even one dimension does, DC = 1 and the clusters are chunked too.
+struct SweepChunks { int KC, DC; };
+inline SweepChunks sweep_chunks(int K, int d, size_t budget, int count_words)
+{
+    const size_t per_cluster = budget / (size_t)K;            // words available per cluster when all K are resident
+    SweepChunks c{K, per_cluster >= (size_t)(3 + count_words) ? (int)((per_cluster - count_words) / 3) : 0};
+    if (c.DC > d) c.DC = d;
+    if (c.DC < 1) {
+        c.DC = 1;
+        c.KC = (int)(budget / (size_t)(3 + count_words));
+        if (c.KC < 1) c.KC = 1;
+    }
+    return c;
+}
+
 /// One output element of [inertia, n_changed, counts(K), sums(K*d)] by one wave, the lanes striding over the per-workgroup partial blocks
 /// four at a time (round 5: the loads of a trip in flight together -- 11.8 -> ... us at K = 256, d = 8 over 512 blocks). inertia / changed:
 /// lane-strided partial sums combined by a shuffle tree (a fixed order for a given number of partials); counts and coordinate sums:
-/// exact integer sums of the limb words (order-free), converted to double once.
+/// exact integer sums of the limb words (order-free), converted to double once and divided by their scale.
+/// WEIGHTED: the blocks of the weighted sweep -- the count is three limbs like a sum, `scale` holds the two factors of every scale
+/// (divided out in that order: the second, then the first), and out[1] (n_changed: a count of rows, written by the assignment's own
+/// reduction) is left alone.
+template <bool WEIGHTED>
 __device__ __forceinline__ void kmeans_reduce_element(const double* __restrict__ partials, int n_blocks, size_t pstride, int K, int d,
                                                       const double* __restrict__ scale, double* out, int e, int total, int lane)
 {
@@ -205,17 +256,18 @@ __device__ __forceinline__ void kmeans_reduce_element(const double* __restrict__
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
         return v;
     };
-    const int W = 3 * d + 1;
+    const int W = 3 * d + (WEIGHTED ? 3 : 1);
     if (e < 2) {
+        if (WEIGHTED && e == 1) return;
         double v = 0.0;
-        for (int b = lane; b < n_blocks; b += 64) v += partials[(size_t)b * pstride + e];   // (the order of kmeans_reduce_kernel: same bits)
+        for (int b = lane; b < n_blocks; b += 64) v += partials[(size_t)b * pstride + e];   // (the resident kernel adds in this order: same bits)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
         if (lane == 0) out[e] = v;
     } else if (e < total) {
-        const int k = (e - 2) / (d + 1), j = (e - 2) - k * (d + 1);
+        const int k = (e - 2) / (d + 1), j = (e - 2) - k * (d + 1);                           // j == d: the count
         const u64* words = reinterpret_cast<const u64*>(partials + 2) + (size_t)k * W;
-        if (j == d) {
+        if (!WEIGHTED && j == d) {
             u64 c0 = 0, c1 = 0, c2 = 0, c3 = 0;
             int b = lane;
             for (; b + 192 < n_blocks; b += 256) {
@@ -248,24 +300,24 @@ __device__ __forceinline__ void kmeans_reduce_element(const double* __restrict__
                 w2 += p[2];
             }
             w0 = wave_sum(w0); w1 = wave_sum(w1); w2 = wave_sum(w2);
-            if (lane == 0) {                                                                  // (the conversion of kmeans_reduce_kernel)
-                w1 += w0 >> 32;  w0 &= 0xffffffffull;
-                const long long top = (long long)w2 + (long long)(w1 >> 32);
-                w1 &= 0xffffffffull;
-                const double v = __builtin_fma((double)top, 0x1p64, __builtin_fma((double)w1, 0x1p32, (double)w0));
-                out[2 + K + (size_t)k * d + j] = v / scale[j];
+            if (lane == 0) {
+                const double v = limbs_to_double(w0, w1, w2);
+                double* sum = j == d ? out + 2 + k : out + 2 + K + (size_t)k * d + j;
+                if (!WEIGHTED) *sum = v / scale[j];
+                else *sum = (v / scale[(j == d ? 2 * d + 1 : d + j)]) / scale[(j == d ? 2 * d : j)];
             }
         }
     }
 }
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void kmeans_reduce_kernel(const double* __restrict__ partials, int n_blocks, size_t pstride,
                                                              int K, int d, int accumulate, const double* __restrict__ scale,
                                                              double* __restrict__ out)
 {
     const int total = 2 + (accumulate ? K * (d + 1) : 0);
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6);        // wave-uniform
-    kmeans_reduce_element(partials, n_blocks, pstride, K, d, scale, out, e, total, threadIdx.x & 63);
+    kmeans_reduce_element<WEIGHTED>(partials, n_blocks, pstride, K, d, scale, out, e, total, threadIdx.x & 63);
 }
 
 template <int D>
@@ -286,6 +338,15 @@ void launch_t(const KmeansArgs& a, int grid, int use_lds, size_t pstride, hipStr
 
 inline int kmeans_grid(int num_cus) { return num_cus * 2; }   // two 1024-thread workgroups (32 waves) per CU
 
+/// The weighted sweep's own grid, set by n alone (the assignment's grid depends on its kernel's workgroup size).
+inline int weighted_grid(uint32_t n, int num_cus)
+{
+    int grid = kmeans_grid(num_cus);
+    const uint32_t need = (n + BSU - 1) / BSU;
+    if ((uint32_t)grid > need) grid = (int)(need ? need : 1);
+    return grid;
+}
+
 }  // namespace
 
 size_t kmeans_scratch_doubles(int d, int K, int num_cus)
@@ -296,18 +357,30 @@ size_t kmeans_scratch_doubles(int d, int K, int num_cus)
 /// Separate update sweep (see kmeans_update_kernel) over the same `grid` partial blocks the assignment kernel used.
 void launch_kmeans_update(const KmeansArgs& a, int grid, size_t pstride, hipStream_t stream)
 {
-    const size_t budget = 72 * 1024 / sizeof(u64);           // words; two 1024-thread workgroups per CU
-    // as many whole dimensions of all K clusters as fit; if not even one does, chunk the clusters too
-    const size_t per_cluster = budget / (size_t)a.K;          // words available per cluster when all K are resident
-    int KC = a.K, DC = per_cluster >= 4 ? (int)((per_cluster - 1) / 3) : 0;
-    if (DC > a.d) DC = a.d;
-    if (DC < 1) {
-        DC = 1;
-        KC = (int)(budget / 4);
-        if (KC < 1) KC = 1;
-    }
-    hipLaunchKernelGGL(kmeans_update_kernel, dim3(grid), dim3(BSU), sizeof(u64) * (size_t)KC * (3 * DC + 1), stream, a.xt, a.ldx,
-                       a.n, a.d, a.labels, a.scale, a.K, KC, DC, a.partials, pstride);
+    const SweepChunks c = sweep_chunks(a.K, a.d, 72 * 1024 / sizeof(u64), 1);   // two 1024-thread workgroups per CU
+    hipLaunchKernelGGL(kmeans_update_kernel<false>, dim3(grid), dim3(BSU), sizeof(u64) * (size_t)c.KC * (3 * c.DC + 1), stream, a.xt,
+                       a.ldx, a.n, a.d, a.labels, a.scale, a.K, c.KC, c.DC, a.partials, pstride, nullptr, nullptr, 1);
+}
+
+size_t kmeans_weighted_scratch_doubles(int d, int K, int num_cus)
+{
+    return (size_t)kmeans_grid(num_cus) * (2 + (size_t)K * (3 * d + 3));
+}
+
+/// The weighted sweep over its own grid and [grid][2 + K (3d + 3)] partial blocks, and its reduction.
+int launch_kmeans_weighted(const KmWeightedArgs& a, int num_cus, hipStream_t stream)
+{
+    const int grid = weighted_grid(a.n, num_cus);
+    const size_t pstride = 2 + (size_t)a.K * (3 * a.d + 3);
+    if ((size_t)grid * pstride > a.partials_capacity) return -2;
+    const SweepChunks c = sweep_chunks(a.K, a.d, 64 * 1024 / sizeof(u64), 3);
+    const size_t smem = a.with_sums ? sizeof(u64) * (size_t)c.KC * (3 * c.DC + 3) : 0;
+    hipLaunchKernelGGL(kmeans_update_kernel<true>, dim3(grid), dim3(BSU), smem, stream, a.xt, a.ldx, a.n, a.d, a.labels, a.factors, a.K,
+                       c.KC, c.DC, a.partials, pstride, a.min_dist, a.weights, a.with_sums);
+    const int total = 2 + (a.with_sums ? a.K * (a.d + 1) : 0);
+    hipLaunchKernelGGL(kmeans_reduce_kernel<true>, dim3((total + 3) / 4), dim3(256), 0, stream, a.partials, grid, pstride, a.K, a.d,
+                       a.with_sums, a.factors, a.out);
+    return grid;
 }
 
 int launch_kmeans_mfma(const KmeansArgs& a, int num_cus, hipStream_t stream);
@@ -408,7 +481,7 @@ void launch_kmeans_reduce(const KmeansArgs& a, int n_partials, hipStream_t strea
 {
     const size_t pstride = 2 + (size_t)a.K * (3 * a.d + 1);
     const int total = 2 + (a.accumulate ? a.K * (a.d + 1) : 0);
-    hipLaunchKernelGGL(kmeans_reduce_kernel, dim3((total + 3) / 4), dim3(256), 0, stream, a.partials, n_partials, pstride,
+    hipLaunchKernelGGL(kmeans_reduce_kernel<false>, dim3((total + 3) / 4), dim3(256), 0, stream, a.partials, n_partials, pstride,
                        a.K, a.d, a.accumulate, a.scale, a.out);
 }
 

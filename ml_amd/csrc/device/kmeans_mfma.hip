@@ -28,7 +28,6 @@
 #include "exact_sum.hpp"
 
 namespace mlhip {
-void launch_kmeans_update(const KmeansArgs& a, int grid, size_t pstride, hipStream_t stream);   // kmeans.hip
 namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -431,36 +430,19 @@ __global__ __launch_bounds__(BSM, (D <= 16) ? 4 : 2) void kmeans_mfma_kernel(
                 u64* row = (USE_LDS ? acc_lds : my_words) + (size_t)arg * W;
 #pragma unroll kExactUnroll
                 for (int j = 0; j < D; ++j) {
-                    if (j < d) {
-                        u64 w0, w1, w2;
-                        split_limbs(x(j) * scale[j], w0, w1, w2);   // wave-uniform index: scalar load
-                        atomicAdd(row + 3 * j, w0);
-                        atomicAdd(row + 3 * j + 1, w1);
-                        atomicAdd(row + 3 * j + 2, w2);
-                    }
+                    if (j < d) add_limbs(row, j, x(j) * scale[j]);   // wave-uniform index: scalar load
                 }
                 atomicAdd(row + 3 * d, (u64)1);
             }
         }
     }
-    // block sums of inertia / changed (fixed order)
+    // block sums of inertia / changed (fixed order): fold_block_sums, its shuffle tree spelled out (see there)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         inertia += __shfl_down(inertia, off, 64);
         changed += __shfl_down(changed, off, 64);
     }
-    constexpr int NWV = BSM / 64;
-    if (lane == 0) {
-        red[wave] = inertia;
-        red[NWV + wave] = changed;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double a = 0.0, b = 0.0;
-        for (int w = 0; w < NWV; ++w) { a += red[w]; b += red[NWV + w]; }
-        my_part[0] = a;
-        my_part[1] = b;
-    }
+    fold_wave_sums<BSM / 64>(inertia, changed, red, my_part);
     if (accumulate && USE_LDS) {
         for (int e = tid; e < K * W; e += BSM) my_words[e] = acc_lds[e];
     }

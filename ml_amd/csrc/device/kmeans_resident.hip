@@ -10,7 +10,7 @@
 //
 // BIT-identical to the three-launch loop (tests/test_gpu_kmeans_resident.py), inertia included: the direct-form distances with the
 // same fma chain and strict '<' (kmeans.hip kmeans_assign_kernel -- the kernel the launches use for D = 1, 2, 3, 6), the same exact
-// limb sums (integer: order-free) and their conversion (kmeans_reduce_element), the same division (kmeans_close_kernel), the host's
+// limb sums (integer: order-free) and their conversion (add_limbs, limbs_to_double of exact_sum.hpp), the same division (kmeans_close_kernel), the host's
 // shift test (km_iterate), and the inertia summed in the ORDER of the launches: thread t of the launches' workgroup b holds sample
 // 1024 b + t -- here thread t walks b = 0, 1, ... itself, every "workgroup" sum is the same shuffle tree per wave and the same
 // wave-by-wave addition, and the sums of the "workgroups" are added as kmeans_reduce_element adds the partial blocks.
@@ -98,13 +98,7 @@ __global__ __launch_bounds__(RBS) void kmeans_resident_kernel(KmResidentArgs a)
                     u64* row = acc_lds + (size_t)(tid & (copies - 1)) * K * W + (size_t)arg * W;
 #pragma unroll
                     for (int j = 0; j < D; ++j) {
-                        if (j < d) {
-                            u64 w0, w1, w2;
-                            split_limbs(x[b][j] * sc[j], w0, w1, w2);
-                            atomicAdd(row + 3 * j, w0);
-                            atomicAdd(row + 3 * j + 1, w1);
-                            atomicAdd(row + 3 * j + 2, w2);
-                        }
+                        if (j < d) add_limbs(row, j, x[b][j] * sc[j]);
                     }
                     atomicAdd(row + 3 * d, (u64)1);
                 }
@@ -162,10 +156,7 @@ __global__ __launch_bounds__(RBS) void kmeans_resident_kernel(KmResidentArgs a)
                     w1 += p[1];
                     w2 += p[2];
                 }
-                w1 += w0 >> 32;  w0 &= 0xffffffffull;
-                const long long top = (long long)w2 + (long long)(w1 >> 32);
-                w1 &= 0xffffffffull;
-                const double sum = __builtin_fma((double)top, 0x1p64, __builtin_fma((double)w1, 0x1p32, (double)w0)) / a.scale[j];
+                const double sum = limbs_to_double(w0, w1, w2) / a.scale[j];
                 const double c = cnt[k];
                 v = c > 0 ? sum / c : 0.0;                  // (empty cluster -> origin, ML/KMeans.cpp:184)
             }

@@ -331,9 +331,9 @@ struct mlhip_ctx {
             const unsigned char* p = reinterpret_cast<const unsigned char*>(b.first);
             for (size_t i = 0; i < b.second * sizeof(double); ++i) { h ^= p[i]; h *= 1099511628211ull; }
         }
-        std::vector<double> v(3 * (size_t)world_size, 0.0);
-        for (int j = 0; j < 3; ++j) v[3 * (size_t)rank + j] = (double)((h >> (16 * j)) & 0xffffu);
-        allreduce_host(v.data(), v.size());
+        double mine[3];
+        for (int j = 0; j < 3; ++j) mine[j] = (double)((h >> (16 * j)) & 0xffffu);
+        const std::vector<double> v = exchange_slots(mine, 3);
         for (int r = 1; r < world_size; ++r)
             for (int j = 0; j < 3; ++j)
                 if (v[3 * (size_t)r + j] != v[j])
@@ -360,6 +360,22 @@ struct mlhip_ctx {
         } else {
             reduce_host(v, count);
         }
+    }
+
+    /// The ranks that take part in a host exchange and this rank's place among them: (1, 0) without a hook.
+    int slot_world() const { return reduce_fn ? world_size : 1; }
+    int slot_rank() const { return reduce_fn ? rank : 0; }
+
+    /// Every rank's `count` doubles in rank order (slot_world() x count): each rank writes its values into its own slot of a zero
+    /// vector and the vector is summed across ranks -- 0 + v is v, so every value arrives as it was sent. One collective; none on a
+    /// single rank.
+    std::vector<double> exchange_slots(const double* mine, size_t count)
+    {
+        const size_t world = (size_t)slot_world();
+        std::vector<double> all(world * count, 0.0);
+        std::copy(mine, mine + count, all.begin() + (size_t)slot_rank() * count);
+        if (world > 1) allreduce_host(all.data(), all.size());
+        return all;
     }
 
     /// `count` doubles of a device buffer, summed across ranks, into a host buffer, in two halves (mlhip_kmeans_iterate runs its
@@ -732,7 +748,7 @@ void km_upload_centroids(mlhip_data* dt, int K, const KmBlock& b, const double* 
 
 /// Assignment (+ optional accumulation) against the table in km_cent, partials reduced into km_out =
 /// [inertia, changed, counts, sums] and summed across ranks there when the all-reduce works on device memory.
-/// `weighted`: the assignment runs with accumulate = 0 and the weighted sweep (device/kmeans_weighted.hip) follows it: km_out then
+/// `weighted`: the assignment runs with accumulate = 0 and the weighted sweep (the weighted form of device/kmeans.hip's update sweep) follows it: km_out then
 /// holds the weighted inertia, the row count n_changed, the weighted counts and sums sum_i w_i x_i (ensure_km_weighted first).
 void km_launch(mlhip_data* dt, const KmRoute& r, int K, const KmBlock& b, bool accumulate, double* min_dist_out, bool weighted = false);
 

@@ -24,15 +24,11 @@ void ensure_km_workspace(mlhip_data* dt, int K)
         ctx->sync();
         // Every rank must cut its coordinates on the SAME fixed-point grid (the limb sums are added across ranks): the
         // column maxima are exchanged through the sum hook, one slot per rank, and every rank takes the maximum.
-        if (ctx->world_size > 1) {
-            std::vector<double> all((size_t)ctx->world_size * dt->d, 0.0);
-            for (int j = 0; j < dt->d; ++j) all[(size_t)ctx->rank * dt->d + j] = m[j];
-            ctx->allreduce_host(all.data(), all.size());
-            for (int r = 0; r < ctx->world_size; ++r)
-                for (int j = 0; j < dt->d; ++j) {
-                    const double v = all[(size_t)r * dt->d + j];
-                    if (!(v <= m[j])) m[j] = v;                            // (keeps a NaN / inf of any rank)
-                }
+        const std::vector<double> all = ctx->exchange_slots(m.data(), m.size());
+        for (size_t t = 0; t < all.size(); ++t) {
+            const double v = all[t];
+            double& mj = m[t % m.size()];
+            if (!(v <= mj)) mj = v;                                        // (keeps a NaN / inf of any rank)
         }
         dt->km_colmax = m;                                       // (the weighted sums' overflow test: ensure_km_weighted)
         for (int j = 0; j < dt->d; ++j) {
@@ -74,13 +70,8 @@ void ensure_km_weighted(mlhip_data* dt, int K)
     double wmax = 0.0;
     HIP_CHECK(hipMemcpyAsync(&wmax, mx.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
-    if (ctx->world_size > 1) {
-        std::vector<double> all((size_t)ctx->world_size, 0.0);
-        all[(size_t)ctx->rank] = wmax;
-        ctx->allreduce_host(all.data(), all.size());
-        for (double v : all)
-            if (!(v <= wmax)) wmax = v;
-    }
+    for (double v : ctx->exchange_slots(&wmax, 1))
+        if (!(v <= wmax)) wmax = v;
     // (mlhip_data_set_weights accepted the weights: finite, >= 0, a positive total -- so 0 < wmax < inf)
     int ew = 0;
     (void)std::frexp(wmax, &ew);                                 // wmax < 2^ew
@@ -505,11 +496,8 @@ int mlhip_kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int
         HIP_CHECK(hipMemcpyAsync(res, out, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
         // the ranks' sums in rank order: this rank's offset and the total are the same sequence of additions on every rank
-        int world = 1, rank = 0;
-        if (ctx->reduce_fn) { world = ctx->world_size; rank = ctx->rank; }
-        std::vector<double> sums((size_t)world, 0.0);
-        sums[(size_t)rank] = res[0];
-        if (world > 1) ctx->allreduce_host(sums.data(), sums.size());
+        const int world = ctx->slot_world(), rank = ctx->slot_rank();
+        const std::vector<double> sums = ctx->exchange_slots(res, 1);
         double offset = 0.0, total = 0.0;
         for (int r = 0; r < world; ++r) {
             if (r == rank) offset = total;
@@ -522,15 +510,10 @@ int mlhip_kpp_draw(mlhip_ctx* ctx, mlhip_data* data, const double* centroid, int
         HIP_CHECK(hipMemcpyAsync(res, out, sizeof(double) * 3, hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
         double lo = res[1], hi = res[2];
-        if (world > 1) {
-            std::vector<double> cand(2 * (size_t)world, 0.0);
-            cand[2 * (size_t)rank] = lo;
-            cand[2 * (size_t)rank + 1] = hi;
-            ctx->allreduce_host(cand.data(), cand.size());
-            for (int r = 0; r < world; ++r) {
-                lo = std::min(lo, cand[2 * (size_t)r]);
-                hi = std::min(hi, cand[2 * (size_t)r + 1]);
-            }
+        const std::vector<double> cand = ctx->exchange_slots(res + 1, 2);
+        for (int r = 0; r < world; ++r) {
+            lo = std::min(lo, cand[2 * (size_t)r]);
+            hi = std::min(hi, cand[2 * (size_t)r + 1]);
         }
         const bool ok = std::isfinite(total) && total > 0.0 && lo == hi;
         *certain = ok ? 1 : 0;
@@ -593,22 +576,20 @@ int mlhip_kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* c
         HIP_CHECK(hipMemcpyAsync(res, slots, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
         // Every value that crosses the (double) all-reduce is an integer below 2^53 in its rank's slot: the sums are exact.
-        int world = 1, rank = 0;
-        if (ctx->reduce_fn) { world = ctx->world_size; rank = ctx->rank; }
-        const size_t W = (size_t)world, R = (size_t)rank;
+        const size_t W = (size_t)ctx->slot_world(), R = (size_t)ctx->slot_rank();
         // 1. the largest exponent of the whole sample and whether any weight is non-finite: [exponent + bias | flag] per rank
-        std::vector<double> ex(2 * W, 0.0);
+        double my_ex[2] = {0.0, 0.0};
         const bool bad = res[0] >= 0x7ff0000000000000ull;
         if (bad) {
-            ex[2 * R + 1] = 1.0;
+            my_ex[1] = 1.0;
         } else if (res[0] != 0) {
             double m = 0.0;
             std::memcpy(&m, &res[0], sizeof m);
             int e = 0;
             std::frexp(m, &e);
-            ex[2 * R] = (double)(e + fixed_point::kExponentBias);
+            my_ex[0] = (double)(e + fixed_point::kExponentBias);
         }
-        if (world > 1) ctx->allreduce_host(ex.data(), ex.size());
+        const std::vector<double> ex = ctx->exchange_slots(my_ex, 2);
         int code = 0;
         bool any_bad = false;
         for (size_t r = 0; r < W; ++r) {
@@ -625,11 +606,8 @@ int mlhip_kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* c
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipMemcpyAsync(res + 1, slots + 1, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost, ctx->stream));
             ctx->sync();
-            std::vector<double> tot(3 * W, 0.0);
-            tot[3 * R] = (double)res[1];
-            tot[3 * R + 1] = (double)(res[2] >> 32);
-            tot[3 * R + 2] = (double)(res[2] & 0xffffffffull);
-            if (world > 1) ctx->allreduce_host(tot.data(), tot.size());
+            const double my_tot[3] = {(double)res[1], (double)(res[2] >> 32), (double)(res[2] & 0xffffffffull)};
+            const std::vector<double> tot = ctx->exchange_slots(my_tot, 3);
             for (size_t r = 0; r < W; ++r) {
                 const u128 t_r = ((u128)((uint64_t)tot[3 * r] + (uint64_t)tot[3 * r + 1]) << 32) + (uint64_t)tot[3 * r + 2];
                 if (r == R) { offset = total; mine = t_r; }
@@ -656,7 +634,7 @@ int mlhip_kpp_draw_fixed_point(mlhip_ctx* ctx, mlhip_data* data, const double* c
             if (res[3] == ~0ull) throw std::runtime_error("FixedPointKPP: the device scan did not find the drawn row");
             pick = (double)res[3];
         }
-        if (world > 1) ctx->allreduce_host(&pick, 1);   // only the owner's slot is non-zero
+        if (W > 1) ctx->allreduce_host(&pick, 1);       // (a plain sum of one double: only the owner's is non-zero)
         *index = (uint64_t)pick;
     });
 }

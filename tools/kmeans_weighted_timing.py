@@ -1,5 +1,5 @@
 """Device time of one weighted K-means step (mlhip_kmeans_step_weighted: the assignment of the shape's route without its own
-accumulation, then the weighted sweep of device/kmeans_weighted.hip) against the unweighted step of the same build on the same
+accumulation, then the weighted form of the update sweep of device/kmeans.hip) against the unweighted step of the same build on the same
 block (mlhip_kmeans_step: assignment + exact update sums), at the two benchmark shapes. Per step the kernels' HIP-event times
 (mlhip_timing_*) are summed, and the MEDIAN over the repeated steps after a warm-up is kept.
 
