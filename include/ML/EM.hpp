@@ -61,6 +61,28 @@ public:
     DLL_DECLSPEC void set_covariance_regularisation(double covariance_regularisation);
     double covariance_regularisation() const { return covariance_regularisation_; }
 
+    /** EXTENSION -- the reference's EM has no restarts (its KMeans has set_number_initialisations; scikit-learn's GaussianMixture has
+    `n_init`). fit() then runs this many EM loops on the one uploaded sample and keeps the best: start r is what a solo fit would
+    begin from, drawn from the seeded PRNG in order r = 0, 1, ... (the loops consume no random numbers, so the starts are those of
+    that many consecutive solo fit() calls on one object after one set_seed). Among the loops that converged the greatest final
+    log-likelihood wins, the first of equals; if none converged the same rule runs over all (mlhip_em_select_restart). fit() returns
+    the winner's converged(); steps_done(), log_likelihood(), the parameters, responsibilities() and labels() are the winner's. Short
+    fits of few components in few dimensions run their restarts side by side on the GPU (mlhip_em_iterate_restarts). The exact
+    N == K fit ignores the setting; verbose mode runs the loops one after the other, an `Initialisation r` line in front of each.
+    (Verbose mode puts the winner's responsibilities back with one E-step on the inputs of its last one: with full covariances that is
+    the solo verbose fit's state bit for bit; in Diagonal and Tied mode it runs the full-covariance E-step on the expanded matrices,
+    so responsibilities() may differ from the solo verbose fit's in the last bits there, and on a multi-rank job it is one more
+    collective E-step. The bit-for-bit statement above is about the non-verbose fit.)
+    Default 1: the reference's behaviour. @throw std::invalid_argument If `number_initialisations == 0`. */
+    DLL_DECLSPEC void set_number_initialisations(unsigned int number_initialisations);
+    unsigned int number_initialisations() const { return number_initialisations_; }
+    /** Extension: the initialisation the fitted state belongs to (0 with one initialisation). */
+    unsigned int best_initialisation() const { return best_initialisation_; }
+    /** Extension: final log-likelihood, iterations and convergence flag (0 / 1) of every initialisation of the last fit(). */
+    const std::vector<double>& initialisation_log_likelihoods() const { return initialisation_log_likelihoods_; }
+    const std::vector<unsigned int>& initialisation_steps() const { return initialisation_steps_; }
+    const std::vector<int>& initialisation_converged() const { return initialisation_converged_; }
+
     /** @brief Fits the model. @param[in] data Column-major, a data point in every column (this rank's row shard when an
     all-reduce hook is installed on the device context). @return `true` if fitting converged.
     @throw std::invalid_argument If `data` has no rows or fewer columns than components.
@@ -142,6 +164,11 @@ private:
     CovarianceType covariance_type_ = CovarianceType::Full;
     mlhip_data* device_data_ = nullptr;
     double covariance_regularisation_ = 1e-15;   // MLHIP_DEFAULT_COVARIANCE_RIDGE
+    unsigned int number_initialisations_ = 1;
+    unsigned int best_initialisation_ = 0;
+    std::vector<double> initialisation_log_likelihoods_;
+    std::vector<unsigned int> initialisation_steps_;
+    std::vector<int> initialisation_converged_;
 
     void process_covariances(Index number_dimensions);
     void require_fitted_for(ConstMatrixRef data) const;

@@ -236,6 +236,45 @@ public:
         return v;
     }
 
+private:
+    template <class T> std::vector<T> per_initialisation(int (*get)(const mlpp_em*, T*, uint32_t, uint32_t*)) const
+    {
+        uint32_t count = 0;
+        detail::check(get(h_, nullptr, 0, &count));
+        std::vector<T> v(count);
+        if (count) detail::check(get(h_, v.data(), count, &count));
+        return v;
+    }
+
+public:
+    /** Extension (ML/EM.hpp): fit() runs this many EM loops from consecutive starts on the one uploaded sample and keeps the best
+    (default 1, the reference). @throw std::invalid_argument If `number_initialisations == 0`. */
+    void set_number_initialisations(unsigned int number_initialisations)
+    {
+        detail::check(mlpp_em_set_number_initialisations(h_, number_initialisations));
+    }
+    unsigned int number_initialisations() const
+    {
+        uint32_t v = 0;
+        detail::check(mlpp_em_number_initialisations(h_, &v));
+        return v;
+    }
+    /** Extension: the initialisation the fitted state belongs to, and every initialisation's final log-likelihood, iterations and
+    convergence flag (0 / 1) from the last fit(). */
+    unsigned int best_initialisation() const
+    {
+        uint32_t v = 0;
+        detail::check(mlpp_em_best_initialisation(h_, &v));
+        return v;
+    }
+    std::vector<double> initialisation_log_likelihoods() const { return per_initialisation<double>(mlpp_em_initialisation_log_likelihoods); }
+    std::vector<unsigned int> initialisation_steps() const
+    {
+        const std::vector<uint32_t> v = per_initialisation<uint32_t>(mlpp_em_initialisation_steps);
+        return std::vector<unsigned int>(v.begin(), v.end());
+    }
+    std::vector<int> initialisation_converged() const { return per_initialisation<int>(mlpp_em_initialisation_converged); }
+
     bool fit(Eigen::Ref<const Eigen::MatrixXd> data) override { return fit_block(data, nullptr); }
     /** Extension: the fit of a weighted sample (ml::EM::fit(data, weights) of ML/EM.hpp): weights(i) >= 0 is the frequency weight of
     column i. @throw std::invalid_argument If `weights.size() != data.cols()` or the weights are refused. */

@@ -229,6 +229,40 @@ int mlhip_em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covarianc
                      uint32_t max_steps, double absolute_tolerance, double relative_tolerance,
                      uint32_t* steps_done, int* converged, double* log_likelihood, double* log_likelihood_history);
 
+/* EXTENSION (the reference's EM has no restarts; its KMeans has set_number_initialisations): R loops of mlhip_em_iterate from R
+ * starts on the one resident block, and the best of them. mixing (R*K), means (R*K*d) and covariances (R*n_cov doubles, n_cov = K*d*d /
+ * K*d / d*d by covariance_type) hold start r at offset r*K, r*K*d, r*n_cov and are updated IN PLACE: the parameters of EVERY restart
+ * come back. steps_done, converged and log_likelihood hold R entries, log_likelihood_history (may be NULL) max_steps entries per
+ * restart (row r at r*max_steps). Every restart's numbers are bit for bit those of mlhip_em_iterate from the same start on the same
+ * handle. *best is the restart mlhip_em_select_restart picks, and the handle is left holding the E-step state of THAT restart:
+ * mlhip_em_responsibilities, _responsibilities_rows and mlhip_em_labels return what they would after its solo mlhip_em_iterate (the
+ * winner is not fitted again: the records of its last E-step are kept, the N x K block is rebuilt from them on demand).
+ * Routes (mlhip_em_restarts_route): SEQUENTIAL -- the solo loop R times, every shape and mode, weighted blocks, device groups and
+ * multi-rank jobs (every rank sees the same log-likelihoods and selects the same restart); BATCHED -- full covariances on an
+ * unweighted block of a single rank whose iteration is the fused kernel in its vector-unit form on at most one workgroup per CU
+ * (d = 1, 2, 3, 4, 6, K <= 32 / 16 / 10 / 7 / 4 with K (d+1)(d+2)/2 <= 64, about N <= 256 CUs): the restarts still running share the three
+ * launches of an iteration (em_restarts.hip), at most MLHIP_RESTARTS_MAX_BATCH per launch, more in successive groups; a restart
+ * whose closing raises a refinement flag leaves the batch and is run solo from its start. R = 0 is an argument error; other
+ * arguments are checked as by mlhip_em_iterate. */
+#define MLHIP_RESTARTS_MAX_BATCH 32
+#define MLHIP_RESTARTS_BATCH_FROM 4
+int mlhip_em_iterate_restarts(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_type, uint32_t R,
+                              double* mixing, double* means, double* covariances,
+                              uint32_t max_steps, double absolute_tolerance, double relative_tolerance,
+                              uint32_t* steps_done, int* converged, double* log_likelihood, double* log_likelihood_history,
+                              uint32_t* best);
+/* The selection rule of mlhip_em_iterate_restarts as a plain host function (no GPU needed): among the restarts that converged the
+ * greatest final log-likelihood wins, compared with a strict '>' in ascending r -- the first of equals wins; if none converged the
+ * same rule runs over all restarts. A NaN log-likelihood never wins; if every log-likelihood is NaN, restart 0 wins. R >= 1. */
+int mlhip_em_select_restart(uint32_t R, const double* log_likelihood, const int* converged, uint32_t* best);
+/* Which route mlhip_em_iterate_restarts takes for R restarts of K components on `data` (diagnostic, nothing is launched), under the
+ * switches as they are set now: *route is MLHIP_RESTARTS_SEQUENTIAL or MLHIP_RESTARTS_BATCHED, *per_launch the number of restarts one
+ * launch carries (1 on the sequential route). The batch is taken automatically from MLHIP_RESTARTS_BATCH_FROM restarts on (measured:
+ * profiles/em_restarts_timing.txt); MLHIP_EM_RESTARTS=sequential / batch forces either route where the batch exists and is ignored
+ * where it does not. covariance_type as in mlhip_em_iterate. A device group's block always reports SEQUENTIAL. */
+enum { MLHIP_RESTARTS_SEQUENTIAL = 0, MLHIP_RESTARTS_BATCHED = 1 };
+int mlhip_em_restarts_route(const mlhip_data* data, uint32_t K, int covariance_type, uint32_t R, int* route, uint32_t* per_launch);
+
 /* E-step only (ML/EM.cpp:190-219): leaves log-responsibilities on the device, returns the log-likelihood. */
 int mlhip_em_expectation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
                          const double* mixing, const double* means, const double* covariances,

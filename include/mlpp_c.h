@@ -60,6 +60,16 @@ int mlpp_em_set_covariance_type(mlpp_em* h, int covariance_type);
  * non-finite value: MLHIP_E_DOMAIN, the model keeps its value. */
 int mlpp_em_set_covariance_regularisation(mlpp_em* h, double v);
 int mlpp_em_covariance_regularisation(const mlpp_em* h, double* out);
+/* EXTENSION: ml::EM::set_number_initialisations / number_initialisations (restarts; the reference's EM has none, default 1) and what the
+ * last fit recorded per initialisation. 0 initialisations: MLHIP_E_INVALID_ARGUMENT, the model keeps its value. The three per-
+ * initialisation getters write min(capacity, *count) entries to `out` (NULL with capacity 0: ask for the count alone) and the number
+ * of initialisations the last fit ran to *count (0 before any fit; 1 for the exact N == K fit). */
+int mlpp_em_set_number_initialisations(mlpp_em* h, uint32_t v);
+int mlpp_em_number_initialisations(const mlpp_em* h, uint32_t* out);
+int mlpp_em_best_initialisation(const mlpp_em* h, uint32_t* out);
+int mlpp_em_initialisation_log_likelihoods(const mlpp_em* h, double* out, uint32_t capacity, uint32_t* count);
+int mlpp_em_initialisation_steps(const mlpp_em* h, uint32_t* out, uint32_t capacity, uint32_t* count);
+int mlpp_em_initialisation_converged(const mlpp_em* h, int* out, uint32_t capacity, uint32_t* count);
 int mlpp_em_fit(mlpp_em* h, const double* data, uint64_t n, uint32_t d, int* converged);
 /* Extension (ml::EM::fit(data, weights)): the fit of a weighted sample, weights[i] >= 0 the frequency weight of point i (n values). */
 int mlpp_em_fit_weighted(mlpp_em* h, const double* data, const double* weights, uint64_t n, uint32_t d, int* converged);

@@ -91,6 +91,17 @@ def u32ptr(a):
     return a.ctypes.data_as(c_u32p)
 
 
+def em_select_restart(log_likelihood, converged):
+    """The restart mlhip_em_iterate_restarts keeps (mlhip_em_select_restart; no GPU needed): the greatest log-likelihood among the
+    converged restarts, else among all; strict '>', so the first of equals; a NaN never wins, all NaN gives 0."""
+    ll = np.ascontiguousarray(log_likelihood, dtype=np.float64)
+    conv = np.ascontiguousarray(converged, dtype=np.int32)
+    assert ll.shape == conv.shape and ll.ndim == 1
+    best = C.c_uint32()
+    check(lib.mlhip_em_select_restart(C.c_uint32(len(ll)), dptr(ll), conv.ctypes.data_as(C.POINTER(C.c_int)), C.byref(best)))
+    return best.value
+
+
 RCCL_UNIQUE_ID_BYTES = 128
 
 
@@ -431,6 +442,36 @@ class Data:
         check(lib.mlhip_em_iterate(self.ctx.handle, self._h, K, 2 if tied else int(bool(diagonal)), dptr(pi), dptr(mu), dptr(S), C.c_uint32(max_steps),
                                    C.c_double(atol), C.c_double(rtol), C.byref(steps), C.byref(conv), C.byref(ll), dptr(hist)))
         return steps.value, bool(conv.value), ll.value, pi, mu, S, hist[:steps.value]
+
+    def em_iterate_restarts(self, mixing, means, covs, max_steps, atol=0.0, rtol=0.0, diagonal=False, tied=False):
+        """R EM loops from R starts in one call, and the best of them (mlhip_em_iterate_restarts). mixing: R x K, means: R x K x d,
+        covs: R x K x d x d (R x K x d variances with diagonal=True, R x d x d with tied=True). Returns (restarts, best): restarts[r] is
+        restart r's tuple, shaped like em_iterate's -- (steps_done, converged, log_likelihood, mixing, means, covs,
+        log_likelihood_history) --, best the restart mlhip_em_select_restart picks; em_labels / em_responsibilities afterwards
+        are that restart's."""
+        pi = np.array(mixing, dtype=np.float64, order="C")
+        mu = np.array(means, dtype=np.float64, order="C")
+        S = np.array(covs, dtype=np.float64, order="C")
+        assert not (diagonal and tied) and pi.ndim == 2
+        R, K = pi.shape
+        assert mu.shape == (R, K, self.d)
+        assert S.shape == ((R, self.d, self.d) if tied else (R, K, self.d) if diagonal else (R, K, self.d, self.d))
+        steps, conv, ll = np.zeros(R, dtype=np.uint32), np.zeros(R, dtype=np.int32), np.full(R, np.nan)
+        hist = np.full((R, int(max_steps)), np.nan)
+        best = C.c_uint32()
+        check(lib.mlhip_em_iterate_restarts(self.ctx.handle, self._h, C.c_uint32(K), 2 if tied else int(bool(diagonal)), C.c_uint32(R), dptr(pi),
+                                            dptr(mu), dptr(S), C.c_uint32(max_steps), C.c_double(atol), C.c_double(rtol), u32ptr(steps),
+                                            conv.ctypes.data_as(C.POINTER(C.c_int)), dptr(ll), dptr(hist), C.byref(best)))
+        restarts = [(int(steps[r]), bool(conv[r]), float(ll[r]), pi[r], mu[r], S[r], hist[r, :steps[r]]) for r in range(R)]
+        return restarts, best.value
+
+    def em_restarts_route(self, K, R, covariance_type="full"):
+        """The route of mlhip_em_iterate_restarts for R restarts of K components under the switches as they are set now
+        (mlhip_em_restarts_route): ('sequential' | 'batched', restarts one launch carries)."""
+        route, per_launch = C.c_int(), C.c_uint32()
+        check(lib.mlhip_em_restarts_route(self._h, C.c_uint32(K), {"full": 0, "diag": 1, "tied": 2}[covariance_type], C.c_uint32(R),
+                                          C.byref(route), C.byref(per_launch)))
+        return ("sequential", "batched")[route.value], per_launch.value
 
     def em_plan(self, K):
         """Which kernels a full-covariance EM iteration of K components is made of (mlhip_em_plan):

@@ -9,7 +9,9 @@ Conventions kept from the reference:
   * std::invalid_argument / std::domain_error surface as ValueError.
 Extensions (not in the reference surface): `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
-`KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`.
+`KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`, `EM.set_number_initialisations`,
+`EM.number_initialisations`, `EM.best_initialisation`, `EM.initialisation_log_likelihoods`, `EM.initialisation_steps`,
+`EM.initialisation_converged`.
 """
 import ctypes as C
 
@@ -212,6 +214,50 @@ class EM:
         v = C.c_double()
         _check(_l.mlpp_em_covariance_regularisation(self._h, C.byref(v)))
         return v.value
+
+    def set_number_initialisations(self, number_initialisations):
+        """Extension (scikit-learn's `n_init`; the reference's EM has no restarts): `fit` runs this many EM loops on the one
+        uploaded sample and keeps the best. Start r is what a solo fit would begin from, drawn from the seeded PRNG in order -- the
+        starts of that many consecutive `fit` calls on one object after one `set_seed`. Among the loops that converged the greatest
+        log-likelihood wins, the first of equals; if none converged, the same over all. Default 1. ValueError for 0."""
+        _check(_l.mlpp_em_set_number_initialisations(self._h, C.c_uint32(number_initialisations)))
+
+    @property
+    def number_initialisations(self):
+        """Extension: the value set by `set_number_initialisations` (1 unless set)."""
+        v = C.c_uint32()
+        _check(_l.mlpp_em_number_initialisations(self._h, C.byref(v)))
+        return v.value
+
+    @property
+    def best_initialisation(self):
+        """Extension: the initialisation the fitted state (parameters, log-likelihood, labels, responsibilities) belongs to."""
+        v = C.c_uint32()
+        _check(_l.mlpp_em_best_initialisation(self._h, C.byref(v)))
+        return v.value
+
+    def _per_initialisation(self, getter, dtype, ctype):
+        count = C.c_uint32()
+        _check(getter(self._h, None, C.c_uint32(0), C.byref(count)))
+        out = np.empty(count.value, dtype=dtype)
+        if count.value:
+            _check(getter(self._h, out.ctypes.data_as(C.POINTER(ctype)), count, C.byref(count)))
+        return out
+
+    @property
+    def initialisation_log_likelihoods(self):
+        """Extension: the final log-likelihood of every initialisation of the last fit, in order."""
+        return self._per_initialisation(_l.mlpp_em_initialisation_log_likelihoods, np.float64, C.c_double)
+
+    @property
+    def initialisation_steps(self):
+        """Extension: the iterations every initialisation of the last fit ran."""
+        return self._per_initialisation(_l.mlpp_em_initialisation_steps, np.uint32, C.c_uint32)
+
+    @property
+    def initialisation_converged(self):
+        """Extension: whether each initialisation of the last fit converged (bool array)."""
+        return self._per_initialisation(_l.mlpp_em_initialisation_converged, np.int32, C.c_int).astype(bool)
 
     def fit(self, data, sample_weight=None):
         """Fits the components to the data (2D array with data points in rows). Returns True if EM converged.

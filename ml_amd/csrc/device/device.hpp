@@ -193,6 +193,37 @@ size_t em_resident_exchange_doubles(int d, int K, int vgrid);
 bool em_resident_supported(int d, int K, int vgrid, int num_cus);
 bool launch_em_resident(const ResidentArgs& a, hipStream_t stream);
 }
+/// One iteration of SEVERAL independent full-covariance EM loops on one block -- the restarts of mlhip_em_iterate_restarts -- in three
+/// launches however many loops are alive (em_restarts.hip): the vector-unit pass on a grid (grid, count), the fixed-order reduction
+/// and the closing arithmetic, each the text the solo launches run (em_fused_valu_body.hpp, em_reduce_body.hpp, em_close_body.hpp).
+/// Row y of a launch works on restart alive.index[y]; every per-restart array is `*_stride` doubles apart.
+namespace mstats {
+constexpr int kRestartsMaxBatch = 32;                        // restarts one launch carries at most (the index list rides in the kernel arguments)
+}
+struct RestartsAlive {
+    int count;
+    unsigned char index[mstats::kRestartsMaxBatch];          // ascending
+};
+struct RestartsArgs {
+    const double* xt; size_t ldx; uint32_t n; int d; int K;
+    const double* shift;
+    int grid;                                                // workgroups per restart = its partial blocks (em_fused_valu_small_grid)
+    RestartsAlive alive;
+    const double* records_in; double* records_out; size_t records_stride;   // estep_param_stride(d) records: this iteration's, the next one's
+    double* partials; size_t partials_stride;                // [grid][KP][FP] per restart
+    double* ll_partials; size_t ll_stride;                   // [grid] per restart
+    double* stats; size_t stats_stride;                      // [K F + 1] per restart
+    double* mixing; double* means; double* covs; size_t pack_stride;       // the new parameters (device)
+    double* info; size_t info_stride;                        // pinned host memory: [ll_sum | refine flag (K) | max |W (mu - shift)| (K)]
+    double n_global, ridge, refine_limit;                    // as CloseArgs
+};
+namespace mstats {
+/// The three launches, in this order on one stream. d = 1, 2, 3, 4, 6 with K <= valu_max_k(d): the shapes of the vector-unit pass;
+/// false: not built for the shape, nothing was launched.
+bool launch_em_restarts_pass(const RestartsArgs& a, hipStream_t stream);
+bool launch_em_restarts_reduce(const RestartsArgs& a, hipStream_t stream);
+bool launch_em_restarts_close(const RestartsArgs& a, hipStream_t stream);
+}
 /// Diagonal-covariance EM iteration in one kernel (em_diag.hip): params are em_diag_partial_rows(K) records of
 /// diag_param_stride(padded_dim(d)) -- K real ones, then neutral padding (coef = -inf) -- and shift holds padded_dim(d)
 /// doubles (zeros beyond d).

@@ -203,30 +203,10 @@ __global__ __launch_bounds__(256) void em_fused_valu_kernel(
     const double* __restrict__ xt, size_t ldx, uint32_t n, const double* __restrict__ shift, const double* __restrict__ params,
     double* __restrict__ lse_out, double* __restrict__ partials, int KP, int FP, double* __restrict__ ll_partials)
 {
-    using S = ValuShape<D, K>;
-    constexpr int F = S::F, VP = S::VP;
-    __shared__ double fold[4][VP];
+    __shared__ double fold[4][ValuShape<D, K>::VP];
     __shared__ double red[4];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    double acc[VP];                                           // acc[k F + f]
-#pragma unroll
-    for (int e = 0; e < VP; ++e) acc[e] = 0.0;
-    double ll_acc = 0.0;
-    double xn[D];                                             // the NEXT tile's sample, in flight while this one is worked on
-    {
-        const uint32_t n_tiles = (n + TS - 1) / TS, t0 = blockIdx.x * 4 + wave;
-        valu_load_tile<D>(xt, ldx, t0 < n_tiles ? t0 : 0, lane, xn);
-    }
-    valu_tiles<D, K>(xt, ldx, n, shift, params, lse_out, blockIdx.x, gridDim.x, wave, lane, xn, acc, ll_acc);
-    valu_fold<VP>(acc, ll_acc, wave, lane, fold, red);
-    __syncthreads();
-    double* out = partials + (size_t)blockIdx.x * KP * FP;
-    for (int e = tid; e < K * F; e += 256) {
-        const int k = e / F, f = e - k * F;
-        out[(size_t)k * FP + f] = ((fold[0][e] + fold[1][e]) + fold[2][e]) + fold[3][e];
-    }
-    if (tid == 0) ll_partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    valu_pass<D, K>(xt, ldx, n, shift, params, lse_out, partials + (size_t)blockIdx.x * KP * FP, FP, ll_partials + blockIdx.x, blockIdx.x,
+                    gridDim.x, fold, red);
 }
 
 template <int D, int RBW, int CB, bool SFEED = false>

@@ -161,6 +161,38 @@ template <int VP> __device__ __forceinline__ void valu_fold(double (&acc)[VP], d
     if (lane == 0) red[wave] = ll_acc;
 }
 
+/// One workgroup's whole pass as (virtual) workgroup `block` of `grid`: its tiles, the fold over lanes and waves, and its partial
+/// block out[k * FP + f] and log-likelihood partial *ll_out. `fold` / `red`: LDS of the calling workgroup (256 threads). The text of
+/// the one-pass kernel (em_fused_small.hip) and of the restarts' batched pass (em_restarts.hip): one text, the same bits.
+template <int D, int K>
+__device__ __forceinline__ void valu_pass(const double* __restrict__ xt, size_t ldx, uint32_t n, const double* __restrict__ shift,
+                                          const double* __restrict__ params, double* __restrict__ lse_out, double* __restrict__ out, int FP,
+                                          double* __restrict__ ll_out, uint32_t block, uint32_t grid,
+                                          double (*fold)[ValuShape<D, K>::VP], double* red)
+{
+    using S = ValuShape<D, K>;
+    constexpr int F = S::F, VP = S::VP;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    double acc[VP];                                           // acc[k F + f]
+#pragma unroll
+    for (int e = 0; e < VP; ++e) acc[e] = 0.0;
+    double ll_acc = 0.0;
+    double xn[D];                                             // the NEXT tile's sample, in flight while this one is worked on
+    {
+        const uint32_t n_tiles = (n + TS - 1) / TS, t0 = block * 4 + wave;
+        valu_load_tile<D>(xt, ldx, t0 < n_tiles ? t0 : 0, lane, xn);
+    }
+    valu_tiles<D, K>(xt, ldx, n, shift, params, lse_out, block, grid, wave, lane, xn, acc, ll_acc);
+    valu_fold<VP>(acc, ll_acc, wave, lane, fold, red);
+    __syncthreads();
+    for (int e = tid; e < K * F; e += 256) {
+        const int k = e / F, f = e - k * F;
+        out[(size_t)k * FP + f] = ((fold[0][e] + fold[1][e]) + fold[2][e]) + fold[3][e];
+    }
+    if (tid == 0) *ll_out = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 /// Largest K the vector-unit form is built for at dimension d (K F <= ~100 accumulators per lane); 0: not built for d.
 constexpr int valu_max_k(int D) { return D == 1 ? 32 : D == 2 ? 16 : D == 3 ? 10 : D == 4 ? 7 : D == 6 ? 4 : 0; }
 

@@ -18,6 +18,7 @@
 // 16x16 accumulators (8 VGPRs each). Per-workgroup partial sums go to scratch and are combined in a
 // fixed order by em_reduce_kernel (no atomics: bitwise reproducible).
 #include "em_mstats_common.hpp"
+#include "em_reduce_body.hpp"
 
 namespace mlhip {
 namespace {
@@ -34,53 +35,13 @@ __global__ __launch_bounds__(256) void fill_resp_kernel(const uint32_t* __restri
     }
 }
 
-/// stats[k*F + f] = sum_b partials[b][k][f], stats[K*F] = sum of the ll partials. Fixed order, hence reproducible run to run
-/// and identical on every rank: 8 outputs per workgroup, each summed by 32 threads over the block slices b = s, s + 32, ...
-/// (ascending), the 32 slice sums added in ascending s. (One thread per output walking all partial blocks, as in round 1, is
-/// latency-bound: 24 us for the 528 outputs of the diagonal configuration; 8 slices, round 2: 9.6 us with 768 partial blocks --
-/// the chain of dependent loads per thread is what it costs, so round 3 cuts it to a quarter.)
-constexpr int kRedOut = 8, kRedSlices = 32;
+/// The fixed-order combination of the partial blocks (em_reduce_body.hpp), one launch per statistics buffer.
 __global__ __launch_bounds__(256) void em_reduce_kernel(const double* __restrict__ partials, int n_blocks, int KP, int FP,
                                                          int K, int F, const double* __restrict__ ll_partials,
                                                          int n_ll, double* __restrict__ stats)
 {
     __shared__ double red[256];
-    const int total = K * F;
-    if ((int)blockIdx.x * kRedOut < total) {
-        const int o = threadIdx.x & (kRedOut - 1), sl = threadIdx.x / kRedOut;
-        const int e = blockIdx.x * kRedOut + o;
-        double s = 0.0;
-        if (e < total) {
-            const int k = e / F, f = e - k * F;
-            const double* p = partials + (size_t)k * FP + f;
-            int b = sl;
-            for (; b + 3 * kRedSlices < n_blocks; b += 4 * kRedSlices) {          // 4 loads in flight, consumed in order
-                const double v0 = p[(size_t)b * KP * FP], v1 = p[(size_t)(b + kRedSlices) * KP * FP];
-                const double v2 = p[(size_t)(b + 2 * kRedSlices) * KP * FP], v3 = p[(size_t)(b + 3 * kRedSlices) * KP * FP];
-                s += v0; s += v1; s += v2; s += v3;
-            }
-            for (; b < n_blocks; b += kRedSlices) s += p[(size_t)b * KP * FP];
-        }
-        red[threadIdx.x] = s;
-        __syncthreads();
-        if (sl == 0 && e < total) {
-            double t = red[o];
-#pragma unroll
-            for (int q = 1; q < kRedSlices; ++q) t += red[q * kRedOut + o];
-            stats[e] = t;
-        }
-    } else {
-        // one extra block: log-likelihood partials (fixed-order tree)
-        double s = 0.0;
-        for (int b = threadIdx.x; b < n_ll; b += 256) s += ll_partials[b];
-        red[threadIdx.x] = s;
-        __syncthreads();
-        for (int off = 128; off > 0; off >>= 1) {
-            if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) stats[total] = red[0];
-    }
+    em_reduce_body(partials, n_blocks, KP, FP, K, F, ll_partials, n_ll, stats, (int)blockIdx.x, red);
 }
 
 

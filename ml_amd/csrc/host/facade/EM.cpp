@@ -90,6 +90,12 @@ void EM::set_covariance_regularisation(double covariance_regularisation)
     covariance_regularisation_ = covariance_regularisation;
 }
 
+void EM::set_number_initialisations(unsigned int number_initialisations)
+{
+    if (!number_initialisations) throw std::invalid_argument("EM: At least 1 initialisation required");
+    number_initialisations_ = number_initialisations;
+}
+
 void EM::set_maximum_steps(unsigned int maximum_steps)
 {
     if (maximum_steps < 2) throw std::invalid_argument("EM: At least two steps required for convergence test");
@@ -155,6 +161,7 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
 {
     converged_ = false;
     steps_done_ = 0;
+    best_initialisation_ = 0;
     const auto number_dimensions = static_cast<unsigned int>(data.rows());
     const auto sample_size = static_cast<unsigned int>(data.cols());
     const unsigned int K = number_components_;
@@ -190,6 +197,9 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
         }
         log_likelihood_ = std::numeric_limits<double>::infinity();
         converged_ = true;
+        initialisation_log_likelihoods_.assign(1, log_likelihood_);      // (the exact fit ignores number_initialisations(), like KMeans)
+        initialisation_steps_.assign(1, 0);
+        initialisation_converged_.assign(1, 1);
         return converged_;
     }
 
@@ -221,6 +231,9 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
         for (unsigned int k = 0; k < K; ++k) covariances_[k].setZero(number_dimensions, number_dimensions);
         log_likelihood_ = std::numeric_limits<double>::infinity();
         converged_ = true;
+        initialisation_log_likelihoods_.assign(1, log_likelihood_);      // (the exact fit ignores number_initialisations(), like KMeans)
+        initialisation_steps_.assign(1, 0);
+        initialisation_converged_.assign(1, 1);
         return converged_;
     }
 
@@ -236,87 +249,91 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
             std::copy_n(cov_flat.data() + dd * k, dd, covariances_[k].data());
         }
     };
+    std::vector<double> sample_covariance;                                 // formed once, by the first start that needs it
 
-    if (maximise_first_) {
-        // Start from responsibilities, then one M-step (ML/EM.cpp:120-125).
-        const auto* closest = dynamic_cast<const Clustering::ClosestCentroid*>(responsibilities_initialiser_.get());
-        const Clustering::ResponsibilitiesInitialiser& initialiser = *responsibilities_initialiser_;
-        if (closest && typeid(initialiser) == typeid(Clustering::ClosestCentroid)) {
-            // Library ClosestCentroid: draw the centroids on the host exactly as it would, run the nearest-centroid
-            // pass (strict '<', first minimum wins: ML/Clustering.cpp:77-88) on the GPU and accumulate the one-hot
-            // M-step from labels -- no N x K matrix is materialised.
-            MatrixXd centroids(number_dimensions, K);
-            Clustering::detail::init_centroids(*closest->centroids_initialiser(), data, prng_, K, centroids, ctx, dev.h);
-            double inertia = 0;
-            uint64_t changed = 0;
-            check(mlhip_kmeans_assign(ctx, dev.h, K, centroids.data(), &inertia, &changed));
-            std::vector<unsigned int> hard(sample_size);
-            check(mlhip_kmeans_labels(ctx, dev.h, hard.data()));
-            check(mlhip_em_maximisation_from_labels(ctx, dev.h, K, hard.data(), mixing_probabilities_.data(), means_.data(),
-                                                    cov_flat.data()));
+    // Start r -- what a solo fit would begin from, drawn from prng_ in order r = 0, 1, ... -- into mixing_probabilities_, means_ and
+    // cov_flat / var_flat / tied_cov.
+    auto make_start = [&] {
+        mixing_probabilities_.fill(1. / static_cast<double>(K));
+        if (maximise_first_) {
+            // Start from responsibilities, then one M-step (ML/EM.cpp:120-125).
+            const auto* closest = dynamic_cast<const Clustering::ClosestCentroid*>(responsibilities_initialiser_.get());
+            const Clustering::ResponsibilitiesInitialiser& initialiser = *responsibilities_initialiser_;
+            if (closest && typeid(initialiser) == typeid(Clustering::ClosestCentroid)) {
+                // Library ClosestCentroid: draw the centroids on the host exactly as it would, run the nearest-centroid
+                // pass (strict '<', first minimum wins: ML/Clustering.cpp:77-88) on the GPU and accumulate the one-hot
+                // M-step from labels -- no N x K matrix is materialised.
+                MatrixXd centroids(number_dimensions, K);
+                Clustering::detail::init_centroids(*closest->centroids_initialiser(), data, prng_, K, centroids, ctx, dev.h);
+                double inertia = 0;
+                uint64_t changed = 0;
+                check(mlhip_kmeans_assign(ctx, dev.h, K, centroids.data(), &inertia, &changed));
+                std::vector<unsigned int> hard(sample_size);
+                check(mlhip_kmeans_labels(ctx, dev.h, hard.data()));
+                check(mlhip_em_maximisation_from_labels(ctx, dev.h, K, hard.data(), mixing_probabilities_.data(), means_.data(),
+                                                        cov_flat.data()));
+            } else {
+                // User-defined initialiser: it fills a host N x K matrix, which is shipped to the device once.
+                responsibilities_.resize(sample_size, K);
+                responsibilities_initialiser_->init(data, prng_, K, responsibilities_);
+                check(mlhip_em_maximisation_from(ctx, dev.h, K, responsibilities_.data(), responsibilities_.rows(),
+                                                 mixing_probabilities_.data(), means_.data(), cov_flat.data()));
+            }
         } else {
-            // User-defined initialiser: it fills a host N x K matrix, which is shipped to the device once.
-            responsibilities_.resize(sample_size, K);
-            responsibilities_initialiser_->init(data, prng_, K, responsibilities_);
-            check(mlhip_em_maximisation_from(ctx, dev.h, K, responsibilities_.data(), responsibilities_.rows(),
-                                             mixing_probabilities_.data(), means_.data(), cov_flat.data()));
+            // Sensible guesses: initialiser's means, every covariance = sample covariance (ML/EM.cpp:127-135).
+            Clustering::detail::init_centroids(*means_initialiser_, data, prng_, K, means_, ctx, dev.h);   // identical on all ranks
+            if (sample_covariance.empty()) {
+                sample_covariance.resize(dd);
+                check(mlhip_sample_covariance(ctx, dev.h, nullptr, sample_covariance.data()));
+            }
+            for (unsigned int k = 0; k < K; ++k) std::copy_n(sample_covariance.data(), dd, cov_flat.data() + dd * k);
         }
-    } else {
-        // Sensible guesses: initialiser's means, every covariance = sample covariance (ML/EM.cpp:127-135).
-        Clustering::detail::init_centroids(*means_initialiser_, data, prng_, K, means_, ctx, dev.h);   // identical on all ranks
-        std::vector<double> sample_covariance(dd);
-        check(mlhip_sample_covariance(ctx, dev.h, nullptr, sample_covariance.data()));
-        for (unsigned int k = 0; k < K; ++k) std::copy_n(sample_covariance.data(), dd, cov_flat.data() + dd * k);
-    }
 
-    if (diagonal) {
-        // the diagonal of the starting covariances (a one-hot / responsibility-weighted M-step entry by entry, or the
-        // sample variances) is the diagonal-mode start
-        var_flat.resize(static_cast<std::size_t>(number_dimensions) * K);
-        for (unsigned int k = 0; k < K; ++k)
-            for (unsigned int j = 0; j < number_dimensions; ++j)
-                var_flat[static_cast<std::size_t>(k) * number_dimensions + j] = cov_flat[dd * k + static_cast<std::size_t>(j) * number_dimensions + j];
-    }
-
-    if (tied) {
-        // the pooled sum_k pi_k Sigma_k of the starting covariances (ascending k) is the tied start: the tied M-step of the starting
-        // responsibilities, or -- K copies of the sample covariance with pi_k = 1 / K -- the sample covariance itself
-        tied_cov.assign(dd, 0.0);
-        for (std::size_t e = 0; e < dd; ++e)
-            for (unsigned int k = 0; k < K; ++k) tied_cov[e] += mixing_probabilities_[k] * cov_flat[dd * k + e];
-    }
-
-    if (!verbose_) {
-        // The whole loop below in one library call (same steps, same convergence test: ML/EM.cpp:143-170), with the M-step's
-        // closing arithmetic and the K covariance factorizations on the device between two tests.
-        uint32_t steps = 0;
-        int conv = 0;
-        check(mlhip_em_iterate(ctx, dev.h, K, tied ? MLHIP_COVARIANCE_TIED : diagonal ? MLHIP_COVARIANCE_DIAGONAL : MLHIP_COVARIANCE_FULL,
-                               mixing_probabilities_.data(), means_.data(),
-                               tied ? tied_cov.data() : diagonal ? var_flat.data() : cov_flat.data(),
-                               maximum_steps_, absolute_tolerance_, relative_tolerance_, &steps, &conv, &log_likelihood_, nullptr));
-        steps_done_ = steps;
-        if (conv) {
-            check(mlhip_em_labels(ctx, dev.h, K, labels_.data()));   // EM::calculate_labels, on convergence only
-            converged_ = true;
+        if (diagonal) {
+            // the diagonal of the starting covariances (a one-hot / responsibility-weighted M-step entry by entry, or the
+            // sample variances) is the diagonal-mode start
+            var_flat.resize(static_cast<std::size_t>(number_dimensions) * K);
+            for (unsigned int k = 0; k < K; ++k)
+                for (unsigned int j = 0; j < number_dimensions; ++j)
+                    var_flat[static_cast<std::size_t>(k) * number_dimensions + j] = cov_flat[dd * k + static_cast<std::size_t>(j) * number_dimensions + j];
         }
-    }
 
-    double old_log_likelihood = -std::numeric_limits<double>::infinity();
-    for (unsigned int step = 0; verbose_ && step < maximum_steps_; ++step) {
-        // One E-step + M-step on the device; parameters are updated in place (ML/EM.cpp:145-147).
-        if (tied)
-            check(mlhip_em_step_tied(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), tied_cov.data(), &log_likelihood_,
-                                     mixing_probabilities_.data(), means_.data(), tied_cov.data()));
-        else if (diagonal)
-            check(mlhip_em_step_diag(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), var_flat.data(), &log_likelihood_,
-                                     mixing_probabilities_.data(), means_.data(), var_flat.data()));
-        else
-            check(mlhip_em_step(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), cov_flat.data(), &log_likelihood_,
-                                mixing_probabilities_.data(), means_.data(), cov_flat.data()));
-        ++steps_done_;
+        if (tied) {
+            // the pooled sum_k pi_k Sigma_k of the starting covariances (ascending k) is the tied start: the tied M-step of the starting
+            // responsibilities, or -- K copies of the sample covariance with pi_k = 1 / K -- the sample covariance itself
+            tied_cov.assign(dd, 0.0);
+            for (std::size_t e = 0; e < dd; ++e)
+                for (unsigned int k = 0; k < K; ++k) tied_cov[e] += mixing_probabilities_[k] * cov_flat[dd * k + e];
+        }
+    };
+    // the covariance array of the mode in hand (what the loops below update in place)
+    auto mode_covariance = [&]() -> std::vector<double>& { return tied ? tied_cov : diagonal ? var_flat : cov_flat; };
+    const int covariance_code = tied ? MLHIP_COVARIANCE_TIED : diagonal ? MLHIP_COVARIANCE_DIAGONAL : MLHIP_COVARIANCE_FULL;
 
-        if (verbose_) {
+    // The verbose loop of one start: one E-step + M-step per trip through the per-step entry points, printed as the reference prints.
+    // Returns whether it converged; `last_inputs` (may be null) receives the parameters its last E-step ran on.
+    auto run_verbose = [&](std::vector<double>* last_inputs) {
+        bool converged = false;
+        double old_log_likelihood = -std::numeric_limits<double>::infinity();
+        for (unsigned int step = 0; step < maximum_steps_; ++step) {
+            if (last_inputs) {
+                std::vector<double>& cov = mode_covariance();
+                last_inputs->assign(mixing_probabilities_.data(), mixing_probabilities_.data() + K);
+                last_inputs->insert(last_inputs->end(), means_.data(), means_.data() + static_cast<std::size_t>(number_dimensions) * K);
+                last_inputs->insert(last_inputs->end(), cov.begin(), cov.end());
+            }
+            // One E-step + M-step on the device; parameters are updated in place (ML/EM.cpp:145-147).
+            if (tied)
+                check(mlhip_em_step_tied(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), tied_cov.data(), &log_likelihood_,
+                                         mixing_probabilities_.data(), means_.data(), tied_cov.data()));
+            else if (diagonal)
+                check(mlhip_em_step_diag(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), var_flat.data(), &log_likelihood_,
+                                         mixing_probabilities_.data(), means_.data(), var_flat.data()));
+            else
+                check(mlhip_em_step(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), cov_flat.data(), &log_likelihood_,
+                                    mixing_probabilities_.data(), means_.data(), cov_flat.data()));
+            ++steps_done_;
+
             std::cout << "Step " << step << "\n";
             std::cout << "Log-likelihood == " << log_likelihood_ << "\n";
             std::cout << "Mixing probabilities == ";
@@ -336,17 +353,102 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
                 std::cout << "\n";
             }
             std::cout << std::endl;
-        }
 
-        if (step > 0) {
-            const double ll_change = std::abs(log_likelihood_ - old_log_likelihood);
-            if (ll_change < absolute_tolerance_ + relative_tolerance_ * std::max(std::abs(old_log_likelihood), std::abs(log_likelihood_))) {
-                check(mlhip_em_labels(ctx, dev.h, K, labels_.data()));   // EM::calculate_labels, on convergence only
-                converged_ = true;
-                break;
+            if (step > 0) {
+                const double ll_change = std::abs(log_likelihood_ - old_log_likelihood);
+                if (ll_change < absolute_tolerance_ + relative_tolerance_ * std::max(std::abs(old_log_likelihood), std::abs(log_likelihood_))) {
+                    converged = true;
+                    break;
+                }
+            }
+            old_log_likelihood = log_likelihood_;
+        }
+        return converged;
+    };
+
+    const unsigned int R = number_initialisations_;
+    if (R == 1) {
+        make_start();
+        if (!verbose_) {
+            // The whole loop in one library call (same steps, same convergence test: ML/EM.cpp:143-170), with the M-step's
+            // closing arithmetic and the K covariance factorizations on the device between two tests.
+            uint32_t steps = 0;
+            int conv = 0;
+            check(mlhip_em_iterate(ctx, dev.h, K, covariance_code, mixing_probabilities_.data(), means_.data(), mode_covariance().data(),
+                                   maximum_steps_, absolute_tolerance_, relative_tolerance_, &steps, &conv, &log_likelihood_, nullptr));
+            steps_done_ = steps;
+            converged_ = conv != 0;
+        } else {
+            converged_ = run_verbose(nullptr);
+        }
+        if (converged_) check(mlhip_em_labels(ctx, dev.h, K, labels_.data()));   // EM::calculate_labels, on convergence only
+        initialisation_log_likelihoods_.assign(1, log_likelihood_);
+        initialisation_steps_.assign(1, steps_done_);
+        initialisation_converged_.assign(1, converged_ ? 1 : 0);
+    } else {
+        // R starts, drawn one after the other as R consecutive solo fits would draw them (the loops consume no random numbers), then
+        // the R loops on the one resident block: the sample is uploaded once, weights, ridge and sample covariance are set once.
+        const std::size_t kd = static_cast<std::size_t>(number_dimensions) * K;
+        std::vector<double> all_mixing, all_means, all_covariances;
+        for (unsigned int r = 0; r < R; ++r) {
+            make_start();
+            const std::vector<double>& cov = mode_covariance();
+            all_mixing.insert(all_mixing.end(), mixing_probabilities_.data(), mixing_probabilities_.data() + K);
+            all_means.insert(all_means.end(), means_.data(), means_.data() + kd);
+            all_covariances.insert(all_covariances.end(), cov.begin(), cov.end());
+        }
+        const std::size_t n_cov = all_covariances.size() / R;
+        std::vector<uint32_t> steps(R, 0);
+        initialisation_converged_.assign(R, 0);
+        initialisation_log_likelihoods_.assign(R, 0.0);
+        uint32_t best = 0;
+        if (!verbose_) {
+            check(mlhip_em_iterate_restarts(ctx, dev.h, K, covariance_code, R, all_mixing.data(), all_means.data(), all_covariances.data(),
+                                            maximum_steps_, absolute_tolerance_, relative_tolerance_, steps.data(),
+                                            initialisation_converged_.data(), initialisation_log_likelihoods_.data(), nullptr, &best));
+        } else {
+            // one start after the other; the winner's E-step state is put back by one E-step on the inputs of its last one
+            std::vector<double> last_inputs, best_inputs;
+            for (unsigned int r = 0; r < R; ++r) {
+                std::cout << "Initialisation " << r << "\n";
+                std::copy_n(all_mixing.data() + static_cast<std::size_t>(r) * K, K, mixing_probabilities_.data());
+                std::copy_n(all_means.data() + r * kd, kd, means_.data());
+                mode_covariance().assign(all_covariances.begin() + r * n_cov, all_covariances.begin() + (r + 1) * n_cov);
+                steps_done_ = 0;
+                initialisation_converged_[r] = run_verbose(&last_inputs) ? 1 : 0;
+                steps[r] = steps_done_;
+                initialisation_log_likelihoods_[r] = log_likelihood_;
+                std::copy_n(mixing_probabilities_.data(), K, all_mixing.data() + static_cast<std::size_t>(r) * K);
+                std::copy_n(means_.data(), kd, all_means.data() + r * kd);
+                std::copy(mode_covariance().begin(), mode_covariance().end(), all_covariances.begin() + r * n_cov);
+                uint32_t so_far = 0;
+                check(mlhip_em_select_restart(r + 1, initialisation_log_likelihoods_.data(), initialisation_converged_.data(), &so_far));
+                if (so_far == r) best_inputs = last_inputs;
+                best = so_far;
+            }
+            if (best + 1 != R) {
+                std::vector<double> full(dd * K, 0.0);                     // the winner's last E-step again (full covariances of its mode)
+                const double* cov = best_inputs.data() + K + kd;
+                for (unsigned int k = 0; k < K; ++k)
+                    for (unsigned int j = 0; j < number_dimensions; ++j)
+                        for (unsigned int l = 0; l < number_dimensions; ++l)
+                            full[dd * k + static_cast<std::size_t>(j) * number_dimensions + l] =
+                                tied ? cov[static_cast<std::size_t>(j) * number_dimensions + l]
+                                     : diagonal ? (j == l ? cov[static_cast<std::size_t>(k) * number_dimensions + j] : 0.0)
+                                                : cov[dd * k + static_cast<std::size_t>(j) * number_dimensions + l];
+                double ll = 0;
+                check(mlhip_em_expectation(ctx, dev.h, K, best_inputs.data(), best_inputs.data() + K, full.data(), &ll));
             }
         }
-        old_log_likelihood = log_likelihood_;
+        best_initialisation_ = best;
+        initialisation_steps_.assign(steps.begin(), steps.end());
+        std::copy_n(all_mixing.data() + static_cast<std::size_t>(best) * K, K, mixing_probabilities_.data());
+        std::copy_n(all_means.data() + best * kd, kd, means_.data());
+        mode_covariance().assign(all_covariances.begin() + best * n_cov, all_covariances.begin() + (best + 1) * n_cov);
+        log_likelihood_ = initialisation_log_likelihoods_[best];
+        steps_done_ = steps[best];
+        converged_ = initialisation_converged_[best] != 0;
+        if (converged_) check(mlhip_em_labels(ctx, dev.h, K, labels_.data()));   // EM::calculate_labels, on convergence only
     }
 
     if (diagonal) {

@@ -41,6 +41,14 @@ std::default_random_engine make_engine(int seed_set, uint32_t seed)
     if (seed_set) e.seed(seed);
     return e;
 }
+/// min(capacity, v.size()) entries of v to `out`, v.size() to *count (the per-initialisation getters).
+template <class T, class U> void copy_per_initialisation(const std::vector<T>& v, U* out, uint32_t capacity, uint32_t* count)
+{
+    need(count);
+    if (capacity) need(out);
+    *count = static_cast<uint32_t>(v.size());
+    for (uint32_t r = 0; r < capacity && r < v.size(); ++r) out[r] = static_cast<U>(v[r]);
+}
 }  // namespace
 
 extern "C" {
@@ -110,6 +118,21 @@ int mlpp_em_set_absolute_tolerance(mlpp_em* h, double v) { return guarded([&] { 
 int mlpp_em_set_relative_tolerance(mlpp_em* h, double v) { return guarded([&] { need(h); h->em.set_relative_tolerance(v); }); }
 int mlpp_em_set_covariance_regularisation(mlpp_em* h, double v) { return guarded([&] { need(h); h->em.set_covariance_regularisation(v); }); }
 int mlpp_em_covariance_regularisation(const mlpp_em* h, double* out) { return guarded([&] { need(h); need(out); *out = h->em.covariance_regularisation(); }); }
+int mlpp_em_set_number_initialisations(mlpp_em* h, uint32_t v) { return guarded([&] { need(h); h->em.set_number_initialisations(v); }); }
+int mlpp_em_number_initialisations(const mlpp_em* h, uint32_t* out) { return guarded([&] { need(h); need(out); *out = h->em.number_initialisations(); }); }
+int mlpp_em_best_initialisation(const mlpp_em* h, uint32_t* out) { return guarded([&] { need(h); need(out); *out = h->em.best_initialisation(); }); }
+int mlpp_em_initialisation_log_likelihoods(const mlpp_em* h, double* out, uint32_t capacity, uint32_t* count)
+{
+    return guarded([&] { need(h); copy_per_initialisation(h->em.initialisation_log_likelihoods(), out, capacity, count); });
+}
+int mlpp_em_initialisation_steps(const mlpp_em* h, uint32_t* out, uint32_t capacity, uint32_t* count)
+{
+    return guarded([&] { need(h); copy_per_initialisation(h->em.initialisation_steps(), out, capacity, count); });
+}
+int mlpp_em_initialisation_converged(const mlpp_em* h, int* out, uint32_t capacity, uint32_t* count)
+{
+    return guarded([&] { need(h); copy_per_initialisation(h->em.initialisation_converged(), out, capacity, count); });
+}
 int mlpp_em_set_maximum_steps(mlpp_em* h, uint32_t v) { return guarded([&] { need(h); h->em.set_maximum_steps(v); }); }
 int mlpp_em_set_means_initialiser(mlpp_em* h, const mlpp_centroids_initialiser* i) { return guarded([&] { need(h); h->em.set_means_initialiser(i ? i->p : nullptr); }); }
 int mlpp_em_set_responsibilities_initialiser(mlpp_em* h, const mlpp_responsibilities_initialiser* i) { return guarded([&] { need(h); h->em.set_responsibilities_initialiser(i ? i->p : nullptr); }); }

@@ -17,28 +17,6 @@
 namespace mlhip_rt {
 namespace {
 
-/// ML/EM.cpp:161-168: from the second trip on, |ll - ll_old| < atol + rtol max(|ll_old|, |ll|) stops the loop.
-struct ConvergenceTest {
-    double atol, rtol;
-    uint32_t* steps_done;
-    int* converged;
-    double* log_likelihood;
-    double* history;
-    double old_ll = -HUGE_VAL;
-    bool operator()(uint32_t step, double ll)
-    {
-        if (history) history[step] = ll;
-        *log_likelihood = ll;
-        *steps_done = step + 1;
-        if (step > 0) {
-            const double change = std::fabs(ll - old_ll);
-            if (change < atol + rtol * std::max(std::fabs(old_ll), std::fabs(ll))) { *converged = 1; return true; }
-        }
-        old_ll = ll;
-        return false;
-    }
-};
-
 struct EmLoop {
     mlhip_data* data;
     mlhip_ctx* ctx;

@@ -456,6 +456,20 @@ struct EstepState {
     void records_are(int layout, bool fold) { rec_layout = layout; rec_fold = fold; }
     void stats_from(int mode, const double* resp, size_t ld) { stats_mode = mode; stats_resp = resp; stats_ld = ld; }
 
+    /// What a later call needs of this state apart from the record buffer itself (mlhip_em_iterate_restarts keeps the best restart's
+    /// while the next one runs): the N x K block is not part of it -- a state put back is one whose block has to be rebuilt.
+    /// The source of the last statistics pass (stats_mode / stats_resp / stats_ld) is not part of it either: it only serves the
+    /// refinement pass INSIDE the step that ran the statistics, and every step sets it before it reads it (stats_from).
+    struct Small {
+        What what = kNone;
+        int rec_layout = 0;
+        bool rec_fold = false;
+        int n_ll = 0;
+        Kept kept;
+    };
+    Small small() const { return Small{what == kBlock ? kRecords : what, rec_layout, rec_fold, n_ll, kept}; }
+    void put_back(const Small& s) { what = s.what; rec_layout = s.rec_layout; rec_fold = s.rec_fold; n_ll = s.n_ll; kept = s.kept; }
+
     bool on_device() const { return what != kNone; }
     bool needs_rebuild() const { return what == kRecords || what == kDiagRecords || what == kTiedRecords; }
     bool diagonal() const { return what == kDiagRecords; }
@@ -519,6 +533,10 @@ struct mlhip_data {
     PinnedBuf it_info_slot[3] = {PinnedBuf{&pool}, PinnedBuf{&pool}, PinnedBuf{&pool}};
     PinnedBuf it_history{&pool};  // [result words | log-likelihood history] of the resident loop
     hipEvent_t it_event[3] = {nullptr, nullptr, nullptr};
+    // mlhip_em_iterate_restarts (em_restarts.cpp): the records behind the E-step state of the best restart so far while another one
+    // runs; the batched route's per-restart rings, scratch and statistics (one block, carved by the loop) and its pinned info blocks
+    DevBuf rs_kept{&pool}, rs_dev{&pool};
+    PinnedBuf rs_info{&pool};
     DevBuf refine_shift{&pool}, refine_stats{&pool};   // the per-component refinement pass
     // self-normalising statistics passes (run_mstats): both kernels add the number of nonzero responsibilities to nz_dev, which
     // is copied to slot sn_calls % 3 of nz_host; pass t chooses the sparse kernel from the count of pass t - 2 (in hand in every
@@ -633,6 +651,28 @@ struct ScoreRoute {
     uint32_t chunk_rows = 0;           // composed: rows per chunk, a multiple of kSampleTile (MLHIP_SCORE_ROWS, else by kScoreScratchBytes)
 };
 ScoreRoute score_route(const mlhip_data* data, int K);
+
+/// mlhip_em_iterate_restarts: R loops one after the other (every shape and mode), or BATCHED -- the restarts still running share the
+/// three launches of an iteration (em_restarts.hip) -- where the solo iteration is the fused kernel in its vector-unit form on at
+/// most one workgroup per CU: full covariances, an unweighted block, a single rank without an all-reduce hook. The batch is taken from
+/// kRestartsBatchFrom restarts on; MLHIP_EM_RESTARTS=sequential / batch forces either where the batch exists. (mlhip.h names the
+/// routes by these values.)
+enum RestartsKind : int { kRestartsSequential = 0, kRestartsBatched = 1 };
+// Measured (profiles/em_restarts_timing.txt: 50 iterations per restart, one batched call against R solo calls, N = 1 000 / 10 000 /
+// 65 536 at d = 2, K = 3 and N = 10 000 at d = 4, K = 3): at R = 2 the batch loses at three of the four shapes (0.73 - 0.91 of the
+// solo calls' speed: 25 - 26 us per batched iteration against two resident iterations of 9 - 12 us), from R = 4 on it wins at all of
+// them (1.36 - 2.26x at R = 4, 5.4 - 7.0x at R = 32). R = 3 was not measured and stays sequential.
+constexpr uint32_t kRestartsBatchFrom = MLHIP_RESTARTS_BATCH_FROM;
+constexpr size_t kRestartsScratchBytes = size_t(64) << 20;   // the batched route's device block: caps the restarts of one launch
+struct RestartsRoute {
+    int kind = kRestartsSequential;
+    int per_launch = 1;                // restarts one launch carries (<= mstats::kRestartsMaxBatch, and what the scratch holds)
+    int grid = 0;                      // batched: the solo pass's grid for this block (em_fused_valu_small_grid)
+    EmRoute em;                        // the solo route of one restart
+};
+/// Doubles of device memory one restart of the batched route needs (two record slots, a pack, partial blocks, statistics).
+size_t restarts_doubles_per_restart(int d, int K, int grid);
+RestartsRoute restarts_route(const mlhip_data* data, int K, int covariance_type, uint32_t R);
 
 struct KmRoute {
     bool pad = false;                  // the block runs on a copy zero-padded to a multiple of 4 dimensions (km_xt_pad)
@@ -800,6 +840,28 @@ void run_total_scatter(mlhip_data* data);
 void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mixing, const double* means, const double* cov,
                   double* log_likelihood, double* mixing_out, double* means_out, double* cov_out);
 
+/// ML/EM.cpp:161-168: from the second trip on, |ll - ll_old| < atol + rtol max(|ll_old|, |ll|) stops the loop.
+struct ConvergenceTest {
+    double atol, rtol;
+    uint32_t* steps_done;
+    int* converged;
+    double* log_likelihood;
+    double* history;
+    double old_ll = -HUGE_VAL;
+    bool operator()(uint32_t step, double ll)
+    {
+        if (history) history[step] = ll;
+        *log_likelihood = ll;
+        *steps_done = step + 1;
+        if (step > 0) {
+            const double change = std::fabs(ll - old_ll);
+            if (change < atol + rtol * std::max(std::fabs(old_ll), std::fabs(ll))) { *converged = 1; return true; }
+        }
+        old_ll = ll;
+        return false;
+    }
+};
+
 /// The loop of EM::fit (ML/EM.cpp:143-170) with everything between two convergence tests on the device (em_loop.cpp): E-step,
 /// statistics, all-reduce, closing arithmetic + next records (em_close.hip); per iteration the host reads back 1 + 2K doubles (log-
 /// likelihood sum, refinement flags, FOLD criterion) and decides. A flagged component (far, tight cluster) sends that one
@@ -810,6 +872,15 @@ void em_iterate(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mi
 /// The same loop for a tied covariance (covs: d*d doubles): one em_step_tied per trip, closing on the host.
 void em_iterate_tied(mlhip_data* data, const TiedRoute& r, int K, double* mixing, double* means, double* cov, uint32_t max_steps, double atol,
                      double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history);
+
+/// The batched loop of mlhip_em_iterate_restarts (em_restarts.cpp): restarts [0, R) of full-covariance EM on a single rank's block;
+/// arrays as in mlhip.h. Restarts it could not finish itself (a refinement flag) are run through em_iterate from their starts.
+/// Leaves the E-step state of restart *best on the handle.
+void em_iterate_restarts_batched(mlhip_data* data, const RestartsRoute& route, int K, uint32_t R, double* mixing, double* means, double* covs,
+                                 uint32_t max_steps, double atol, double rtol, uint32_t* steps_done, int* converged, double* log_likelihood,
+                                 double* history, uint32_t* best);
+/// The selection rule of mlhip_em_select_restart (mlhip.h).
+uint32_t select_restart(uint32_t R, const double* log_likelihood, const int* converged);
 
 /// The all-reduce hook of a context that owns an RCCL communicator: one ncclAllReduce(double, sum), in place, on the
 /// context's stream -- ordered with the kernels before it and the copies after it, no host synchronisation.

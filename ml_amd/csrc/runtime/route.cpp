@@ -28,6 +28,7 @@ struct Switches {
     bool score_composed;        // MLHIP_SCORE=composed
     long score_rows;            // MLHIP_SCORE_ROWS=n: rows per chunk of the composed scoring route (0: by the scratch bound)
     int tied;                   // MLHIP_TIED=composed / kernel: kTiedComposed / kTiedKernel forced (the kernel: where it exists), -1 automatic
+    int restarts;               // MLHIP_EM_RESTARTS=sequential / batch: kRestartsSequential / kRestartsBatched forced (the batch: where it exists), -1 automatic
 };
 
 Switches read_switches()
@@ -57,6 +58,8 @@ Switches read_switches()
     s.score_rows = rows && *rows ? std::atol(rows) : 0;
     const char* tied = std::getenv("MLHIP_TIED");
     s.tied = !tied ? -1 : std::strcmp(tied, "composed") == 0 ? kTiedComposed : std::strcmp(tied, "kernel") == 0 ? kTiedKernel : -1;
+    const char* restarts = std::getenv("MLHIP_EM_RESTARTS");
+    s.restarts = !restarts ? -1 : std::strcmp(restarts, "sequential") == 0 ? kRestartsSequential : std::strcmp(restarts, "batch") == 0 ? kRestartsBatched : -1;
     return s;
 }
 
@@ -135,6 +138,39 @@ TiedRoute tied_route(const mlhip_data* data, int K)
     // unless MLHIP_TIED=kernel asks for the kernel.
     const bool composed_faster = r.em.fused && r.em.fused_form == kFusedValu;
     if (sw.tied == kTiedKernel || !composed_faster) r.kernel = kTiedKernel;
+    return r;
+}
+
+size_t restarts_doubles_per_restart(int d, int K, int grid)
+{
+    const size_t records = (size_t)K * estep_param_stride(d), pack = (size_t)K * (1 + d + (size_t)d * d);
+    const size_t block = (size_t)mstats::em_fused_partial_rows(K) * mstats::em_fused_partial_cols(d);
+    return 2 * records + pack + (size_t)grid * (block + 1) + (size_t)K * stats_count(d) + 1;
+}
+
+RestartsRoute restarts_route(const mlhip_data* data, int K, int covariance_type, uint32_t R)
+{
+    const Switches sw = read_switches();
+    const mlhip_ctx* ctx = data->ctx;
+    RestartsRoute r;
+    r.em = em_route(data, K, covariance_type == MLHIP_COVARIANCE_DIAGONAL);
+    // Where the batch exists: the solo iteration is the vector-unit pass + reduction + device closing of ONE rank, and its grid is at
+    // most one workgroup per CU (the partial-block scratch and the ll partials never cut such a grid: em_fused_small.hip).
+    if (covariance_type != MLHIP_COVARIANCE_FULL || data->weighted || ctx->reduce_fn || ctx->world_size > 1) return r;
+    if (!r.em.fused || r.em.fused_form != kFusedValu || !r.em.device_close) return r;
+    FusedArgs fa{};
+    fa.n = data->n; fa.d = data->d; fa.K = K; fa.form = r.em.fused_form;
+    fa.n_ll_partials = kMaxLlPartials;
+    fa.partials_capacity = std::max(data->partials.bytes / sizeof(double), em_mstats_scratch_doubles(data->d, K, ctx->num_cus));
+    const int grid = mstats::em_fused_valu_small_grid(fa, ctx->num_cus);
+    if (grid <= 0) return r;
+    const size_t fit = kRestartsScratchBytes / (sizeof(double) * restarts_doubles_per_restart(data->d, K, grid));
+    if (fit < 1) return r;
+    // Automatic: from kRestartsBatchFrom restarts on (the smallest R at which the batch was faster at every measured shape)
+    if (sw.restarts == kRestartsSequential || (sw.restarts < 0 && R < kRestartsBatchFrom)) return r;
+    r.kind = kRestartsBatched;
+    r.grid = grid;
+    r.per_launch = (int)std::min<size_t>(fit, (size_t)mstats::kRestartsMaxBatch);
     return r;
 }
 
