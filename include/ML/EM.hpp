@@ -7,6 +7,7 @@
  * ML/EM.hpp:18-198 (same method names, defaults, exceptions and result semantics), executed on an MI355X:
  * the E-step / M-step loops of ML/EM.cpp:190-263 run as HIP kernels through the C ABI in mlhip.h; this class keeps
  * the driver loop (ML/EM.cpp:91-174), the convergence test and the host-side point query. */
+#include <cstdint>
 #include <memory>
 #include <random>
 #include <vector>
@@ -132,6 +133,16 @@ public:
     /** Extension: the data.cols() x number_components() posteriors of `data` (the batch form of assign_responsibilities, normalised
     in the log domain). This one needs the N x K block: an E-step per row batch on a temporary device block. */
     DLL_DECLSPEC MatrixXd calculate_responsibilities(ConstMatrixRef data) const;
+    /** Extension (scikit-learn's GaussianMixture.sample): `n` points drawn from the fitted mixture on the device, a point in every
+    column (means().rows() x n: what fit takes); `labels`, if given, receives the component every point was drawn from. Point i is
+    a pure function of (seed, i) and the fitted parameters (mlhip_em_sample: Philox4x32-10 counters, Box-Muller normals, the lower
+    Cholesky factors of covariances()): the same seed gives the same points, a longer draw starts with the shorter one, and the
+    result does not depend on the row batches (those of log_densities) or the device group it runs on. The model's own random
+    engine is not touched: a fit after a sample draws what it would have drawn.
+    @throw std::invalid_argument If `n < 0` or the model has not been fitted.
+    @throw std::domain_error If a covariance is not positive definite.
+    @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
+    DLL_DECLSPEC MatrixXd sample(Index n, std::uint64_t seed = 0, std::vector<unsigned int>* labels = nullptr) const;
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }
     /** Extension: number of E-M iterations the last fit() ran. */

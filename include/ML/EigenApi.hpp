@@ -22,6 +22,7 @@
 
 #include <Eigen/Core>
 
+#include <cstdint>
 #include <memory>
 #include <random>
 #include <stdexcept>
@@ -376,6 +377,19 @@ public:
         const detail::Block block(data);
         Eigen::MatrixXd out(data.cols(), static_cast<Eigen::Index>(number_components_));
         detail::check(mlpp_em_predict_proba(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()), out.data()));
+        return out;
+    }
+    /** Extension (ML/EM.hpp): `n` points drawn from the fitted mixture on the device, a point in every column (means().rows() x n);
+    `labels`, if given, receives the components drawn. Point i is a pure function of (seed, i) and the fitted parameters.
+    @throw std::invalid_argument If `n < 0` or the model has not been fitted. */
+    Eigen::MatrixXd sample(Eigen::Index n, std::uint64_t seed = 0, std::vector<unsigned int>* labels = nullptr) const
+    {
+        if (n < 0) throw std::invalid_argument("EM: Negative number of samples");
+        Eigen::MatrixXd out(means_.rows(), n);
+        if (labels) labels->resize(static_cast<std::size_t>(n));
+        static_assert(sizeof(unsigned int) == sizeof(uint32_t), "labels are 32-bit");
+        detail::check(mlpp_em_sample(h_, static_cast<uint64_t>(n), seed, out.data(),
+                                     labels ? reinterpret_cast<uint32_t*>(labels->data()) : nullptr));
         return out;
     }
     const std::vector<unsigned int>& labels() const override { return labels_; }

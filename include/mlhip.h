@@ -303,6 +303,48 @@ int mlhip_em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_
                    const double* mixing, const double* means, const double* covariances,
                    double* log_density, uint32_t* labels);
 
+/* EXTENSION (scikit-learn's GaussianMixture.sample; not in the reference surface): rows [first_row, first_row + n) of THE sample that a
+ * seed and a mixture define, drawn on the device. Row i (its 64-bit global index) is a pure function of (seed, i), so the result does
+ * not depend on the grid, on how a sample is cut into calls (first_row), on the chunks a call runs in or on the shards of a device
+ * group, bit for bit. Definition -- Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl increments 0x9E3779B9, 0xBB67AE85), key
+ * (seed & 0xffffffff, seed >> 32), counter (i & 0xffffffff, i >> 32, block, 0), output words w0..w3, U(lo, hi) = (((hi 2^32 + lo) >> 12)
+ * + 1/2) 2^-52 (exact in fp64, strictly inside (0, 1)):
+ *   label   (block 0): u = U(w0, w1); s_k the sequential fp64 prefix sums of `mixing`, t_k = s_k / s_{K-1}; label = #{k < K-1 : u >= t_k}
+ *           (a component of weight 0 is never drawn, the last component absorbs the rounding);
+ *   normals (block 1 + p, p = 0 .. ceil(d/2) - 1): u1 = U(w0, w1), u2 = U(w2, w3), r = sqrt(-2 log u1), z_2p = r cos(2 pi u2),
+ *           z_2p+1 = r sin(2 pi u2) (for odd d the last value is dropped);
+ *   row:    x_j = mu_kj + sum_{c <= j} L_k[j][c] z_c with L_k the lower Cholesky factor of Sigma_k (mlhip_cholesky_lower), evaluated as
+ *           acc = mu_j, then acc = fma(L_jc, z_c, acc) for c = 0 .. j, on every route.
+ * covariance_type and the layouts of mixing / means / covariances as in mlhip_em_score: diagonal input (L = sqrt(variance)) gives the
+ * bits of the same variances passed as full diagonal matrices, tied input (one factor) those of K copies. A matrix that is not
+ * positive definite: MLHIP_E_DOMAIN. x: n rows of d doubles, `ld` doubles apart; labels: n; either may be NULL, not both. The rows are
+ * generated in chunks into a block from the context's pool (64 MiB; MLHIP_SAMPLE_ROWS=rows overrides) and copied down. A device group:
+ * shard s draws its rows of the balanced split of mlhip_data_upload on its own GPU. The model's own random engine is not involved.
+ * MLHIP_E_INVALID_ARGUMENT, before any device work: null pointers, K = 0, d = 0 or d > 4096, a bad covariance_type, a negative or
+ * non-finite mixing weight or a total that is not positive, non-finite means, first_row + n beyond 64 bits, ld < d. n = 0 succeeds
+ * and writes nothing. */
+int mlhip_em_sample(mlhip_ctx* ctx, uint32_t d, uint32_t K, int covariance_type,
+                    const double* mixing, const double* means, const double* covariances,
+                    uint64_t seed, uint64_t first_row, uint64_t n, double* x, int64_t ld, uint32_t* labels);
+/* The same rows as a resident block: generated sample-major into a pool buffer, they become a handle by the path of
+ * mlhip_data_upload_dev and never leave the device; the handle is what mlhip_data_upload returns for the host copy of the same rows
+ * (a device group's: assembled from the parts its shards drew themselves). labels (n, host) may be NULL. Also
+ * MLHIP_E_INVALID_ARGUMENT: n beyond the per-rank row limit of mlhip_data_upload. n = 0: an empty block, as an empty upload. */
+int mlhip_em_sample_data(mlhip_ctx* ctx, uint32_t d, uint32_t K, int covariance_type,
+                         const double* mixing, const double* means, const double* covariances,
+                         uint64_t seed, uint64_t first_row, uint64_t n, uint32_t* labels, mlhip_data** out);
+/* Host helper, no GPU needed: the lower Cholesky factor the sampler uses (and a fit's records are built from), column-major d x d,
+ * upper triangle zero. 1 <= d <= 4096; MLHIP_E_DOMAIN when the matrix is not positive definite. */
+int mlhip_cholesky_lower(uint32_t d, const double* covariance, double* lower);
+/* Which kernel the sampling calls run for K components in d dimensions (diagnostic, nothing is launched), under the switches as they
+ * are set now. d <= 64: lane = row with the normals in registers, the wave's 64 x d tile staged through LDS and written as contiguous
+ * 16 bytes per lane; the factors and means are read per lane from LDS (MLHIP_SAMPLE_LDS_TABLE) where the K (d (d+1)/2 + d) doubles of a
+ * full model fit into the 64 KiB of a workgroup beside the staging tile (4 / 2 / 1 waves of 64 x (d | 1) doubles at d <= 16 / 32 / 64)
+ * and the K thresholds, else -- and under MLHIP_SAMPLE_TABLE=global -- from global memory (MLHIP_SAMPLE_GLOBAL_TABLE; same bits).
+ * 64 < d <= 4096: the plain tier (MLHIP_SAMPLE_PLAIN), normals into the output row and the product in place there. */
+enum { MLHIP_SAMPLE_LDS_TABLE = 0, MLHIP_SAMPLE_GLOBAL_TABLE = 1, MLHIP_SAMPLE_PLAIN = 2 };
+int mlhip_em_sample_route(uint32_t d, uint32_t K, int* kernel);
+
 /* (X - mean)(X - mean)^T / (N - 1) over ALL ranks' samples (EM::calculate_sample_covariance,
  * ML/EM.cpp:265-272). mean may be NULL. */
 int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance);

@@ -91,6 +91,10 @@ int mlpp_em_assign_responsibilities(const mlpp_em* h, const double* x, uint32_t 
 int mlpp_em_score_samples(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out);
 int mlpp_em_predict(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, uint32_t* out);
 int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out);
+/* Extension: EM::sample -- n points drawn from the fitted mixture on the device, point i a pure function of (seed, i) and the
+ * parameters (mlhip_em_sample). x_out: n x d row-major (a point in every row); labels_out (n, the components drawn) may be NULL.
+ * n = 0 writes nothing. */
+int mlpp_em_sample(const mlpp_em* h, uint64_t n, uint64_t seed, double* x_out, uint32_t* labels_out);
 
 /* ---- KMeans (cppyml/clustering.cpp:148-183) ---- */
 int mlpp_kmeans_create(uint32_t number_clusters, mlpp_kmeans** out);

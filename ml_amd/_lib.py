@@ -263,6 +263,35 @@ class Context:
         check(lib.mlhip_ctx_world(self._h, C.byref(w), C.byref(r)))
         return w.value, r.value
 
+    def _sample_arguments(self, mixing, means, covs, n, seed, first_row, diagonal, tied):
+        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
+        means = np.ascontiguousarray(means, dtype=np.float64)
+        covs = np.ascontiguousarray(covs, dtype=np.float64)
+        assert not (diagonal and tied) and mixing.ndim == 1 and means.ndim == 2
+        K, d = means.shape
+        assert mixing.shape == (K,) and covs.shape == ((d, d) if tied else (K, d) if diagonal else (K, d, d))
+        if n < 0:
+            raise ValueError("the number of rows must not be negative")
+        return (self._h, C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(mixing), dptr(means), dptr(covs),
+                C.c_uint64(seed), C.c_uint64(first_row), C.c_uint64(n)), (mixing, means, covs), d
+
+    def em_sample(self, mixing, means, covs, n, seed=0, first_row=0, diagonal=False, tied=False):
+        """Rows [first_row, first_row + n) of the sample that `seed` and the mixture define, drawn on the device (mlhip_em_sample):
+        (X, labels), X n x d C-contiguous float64, labels uint32. means: K x d; covs: K x d x d (K x d variances with diagonal=True,
+        the one d x d matrix with tied=True). A row depends on (seed, its global index) only."""
+        args, keep, d = self._sample_arguments(mixing, means, covs, n, seed, first_row, diagonal, tied)
+        X, labels = np.empty((n, d)), np.empty(n, dtype=np.uint32)
+        check(lib.mlhip_em_sample(*args, dptr(X), C.c_int64(d), u32ptr(labels)))
+        return X, labels
+
+    def em_sample_data(self, mixing, means, covs, n, seed=0, first_row=0, diagonal=False, tied=False):
+        """The same rows as a resident block that never leaves the device (mlhip_em_sample_data): (Data, labels)."""
+        args, keep, d = self._sample_arguments(mixing, means, covs, n, seed, first_row, diagonal, tied)
+        labels = np.empty(n, dtype=np.uint32)
+        handle = C.c_void_p()
+        check(lib.mlhip_em_sample_data(*args, u32ptr(labels), C.byref(handle)))
+        return Data.adopt(self, handle, n, d), labels
+
     def timing_enable(self, on=True):
         check(lib.mlhip_timing_enable(self._h, int(on)))
 
@@ -313,6 +342,16 @@ class Data:
                                             C.c_int64(d), C.byref(self._h)))
         self.n, self.d = n, d
         ctx._blocks.add(self)
+
+    @classmethod
+    def adopt(cls, ctx, handle, n, d):
+        """Wraps a block the library made itself (Context.em_sample_data): owned from here on, freed by close() like an upload."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+        self.n, self.d = int(n), int(d)
+        ctx._blocks.add(self)
+        return self
 
     def close(self):
         if getattr(self, "_h", None):
@@ -666,6 +705,25 @@ def finalize_statistics_tied(statistics, total_scatter, shift, total_weight, rid
         check(lib.mlhip_em_finalize_statistics_tied_ridge(d, K, dptr(st), dptr(T), dptr(shift), float(total_weight), float(ridge), dptr(pi),
                                                           dptr(mu), dptr(S)))
     return pi, mu, S
+
+
+def cholesky_lower(cov):
+    """The lower Cholesky factor the sampler uses (mlhip_cholesky_lower, no GPU): L with L @ L.T == cov up to rounding, upper
+    triangle zero. ValueError when cov is not positive definite."""
+    cov = np.ascontiguousarray(cov, dtype=np.float64)
+    d = cov.shape[0]
+    assert cov.shape == (d, d)
+    L = np.empty((d, d), order="F")
+    check(lib.mlhip_cholesky_lower(C.c_uint32(d), dptr(cov), dptr(L)))
+    return np.ascontiguousarray(L)
+
+
+def em_sample_route(d, K):
+    """The kernel the sampling calls run for K components in d dimensions under the switches as they are set now
+    (mlhip_em_sample_route): 'lds_table' | 'global_table' | 'plain'."""
+    k = C.c_int()
+    check(lib.mlhip_em_sample_route(C.c_uint32(d), C.c_uint32(K), C.byref(k)))
+    return ("lds_table", "global_table", "plain")[k.value]
 
 
 def process_covariance(cov):

@@ -7,7 +7,7 @@ Conventions kept from the reference:
   * `EM.means` is `d x K` (NOT transposed, clustering.cpp:126), `KMeans.centroids` is `K x d` (clustering.cpp:66-69,172);
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
-Extensions (not in the reference surface): `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
+Extensions (not in the reference surface): `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
 `KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`, `EM.set_number_initialisations`,
 `EM.number_initialisations`, `EM.best_initialisation`, `EM.initialisation_log_likelihoods`, `EM.initialisation_steps`,
@@ -374,6 +374,19 @@ class EM:
         out = np.empty((n, self.number_components), order="F")
         _check(_l.mlpp_em_predict_proba(self._h, _dp(X), C.c_uint64(n), d, _dp(out)))
         return out
+
+    def sample(self, n_samples, seed=0):
+        """Extension (scikit-learn's GaussianMixture.sample): n_samples points drawn from the fitted mixture on the GPU. Returns
+        (X, labels): X (n_samples, d) C-contiguous float64 -- what `fit` takes --, labels the uint32 component of every row. Row i is
+        a pure function of (seed, i) and the fitted parameters: one seed gives one sample, a longer draw starts with the shorter
+        one. The model's own random engine is not touched. ValueError for a negative n_samples or a model that was not fitted."""
+        n = int(n_samples)
+        if n < 0:
+            raise ValueError("sample(): n_samples must not be negative")
+        d, _ = self._dims()
+        X, labels = np.empty((n, d)), np.empty(n, dtype=np.uint32)
+        _check(_l.mlpp_em_sample(self._h, C.c_uint64(n), C.c_uint64(int(seed)), _dp(X), _lib.u32ptr(labels)))
+        return X, labels
 
     @property
     def labels(self):

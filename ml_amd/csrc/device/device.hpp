@@ -96,6 +96,29 @@ int launch_em_score_mfma4(const ScoreArgs& a, int num_cus, hipStream_t stream);
 void launch_em_score_finish(const double* lw, size_t ldr, const double* lse, uint32_t n, int K, double* lse_out, uint32_t* labels_out,
                             hipStream_t stream);
 
+/// Sampling pass (em_sample.hip): rows [first_row, first_row + n) of the sample that (seed, mixture) define, sample-major and
+/// contiguous (row stride d) into x, their components into labels; either may be null. Every row is a pure function of its global
+/// index, so the outputs do not depend on how a sample is cut into launches.
+enum SampleKernel : int {
+    kSampleLdsTable = 0,                       // d <= 64, the factors and means in LDS beside the staging tile
+    kSampleGlobalTable = 1,                    // d <= 64, read per lane from global memory
+    kSamplePlain = 2,                          // 64 < d <= 4096: normals to the output row, product in place there
+};
+struct SampleArgs {
+    int d; uint32_t K;
+    const double* table; size_t table_doubles;               // [factors: packed lower triangles, l_stride apart | means (K x d)]
+    size_t l_stride;                                         // d (d+1)/2, or 0 when all components share one factor (tied)
+    const double* thresholds;                                // K doubles: the normalised prefix sums of the mixing weights
+    uint64_t seed, first_row, n;
+    double* x; uint32_t* labels;                             // out: n x d (16-byte aligned), n
+    int kernel;                                              // SampleKernel (em_sample_route, or the other table form of the same tier)
+};
+/// The kernel for a full model of K components in d dimensions: LDS table where K (d (d+1)/2 + d) doubles fit into the 64 KiB a
+/// workgroup takes beside the staging tile (4 / 2 / 1 waves of 64 x (d | 1) doubles at d <= 16 / 32 / 64) and the K thresholds.
+int em_sample_route(int d, uint32_t K);
+/// Returns the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
+int launch_em_sample(const SampleArgs& a, int num_cus, hipStream_t stream);
+
 enum MstatsMode : int {
     kFromLogResp = 0,   // r = exp(lw - lse)          (after an E-step)
     kFromResp = 1,      // r = lw                     (plain responsibilities: caller-given, one-hot, or all ones)

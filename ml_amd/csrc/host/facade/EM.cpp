@@ -558,6 +558,33 @@ MatrixXd EM::calculate_responsibilities(ConstMatrixRef data) const
     return out;
 }
 
+MatrixXd EM::sample(Index n, std::uint64_t seed, std::vector<unsigned int>* labels) const
+{
+    if (n < 0) throw std::invalid_argument("EM: Negative number of samples");
+    const Index d = means().rows();
+    // (the order of require_fitted_for: the shape, the device, the decompositions)
+    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    (void)device::context();
+    if (inverse_covariances_.empty() || inverse_covariances_[0].rows() != d)
+        throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    MatrixXd out(d, n);
+    if (labels) labels->resize(static_cast<std::size_t>(n));
+    if (!n) return out;
+    const std::size_t dd = static_cast<std::size_t>(d) * d;
+    std::vector<double> cov_flat(dd * number_components_);
+    for (unsigned int k = 0; k < number_components_; ++k) std::copy_n(covariances_[k].data(), dd, cov_flat.data() + dd * k);
+    mlhip_ctx* ctx = device::context();
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "labels are 32-bit");
+    const Index batch = Clustering::detail::score_batch_rows();
+    for (Index first = 0; first < n; first += batch) {
+        const Index rows = std::min(batch, n - first);
+        check(mlhip_em_sample(ctx, static_cast<uint32_t>(d), number_components_, MLHIP_COVARIANCE_FULL, mixing_probabilities_.data(),
+                              means_.data(), cov_flat.data(), seed, static_cast<uint64_t>(first), static_cast<uint64_t>(rows), out.col(first), d,
+                              labels ? reinterpret_cast<uint32_t*>(labels->data()) + first : nullptr));
+    }
+    return out;
+}
+
 void EM::process_covariances(const Index number_dimensions)
 {
     // Inverse and sqrt(det) of every covariance for the host point query (ML/EM.cpp:274-287).

@@ -3,6 +3,7 @@
 #include "mlpp_c.h"
 
 #include <algorithm>
+#include <limits>
 #include <memory>
 #include <random>
 #include <stdexcept>
@@ -204,6 +205,18 @@ int mlpp_em_predict(const mlpp_em* h, const double* data, uint64_t n, uint32_t d
         need(h); need(data); need(out);
         const std::vector<unsigned int> v = h->em.assign_labels(ConstMatrixRef(data, d, static_cast<Index>(n), d));
         std::copy(v.begin(), v.end(), out);
+    });
+}
+int mlpp_em_sample(const mlpp_em* h, uint64_t n, uint64_t seed, double* x_out, uint32_t* labels_out)
+{
+    return guarded([&] {
+        need(h);
+        if (n) need(x_out);
+        if (n > static_cast<uint64_t>(std::numeric_limits<Index>::max())) throw std::invalid_argument("EM: Too many samples");
+        std::vector<unsigned int> labels;
+        const MatrixXd x = h->em.sample(static_cast<Index>(n), seed, labels_out ? &labels : nullptr);
+        std::copy_n(x.data(), x.size(), x_out);
+        if (labels_out) std::copy(labels.begin(), labels.end(), labels_out);
     });
 }
 int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out)

@@ -177,7 +177,20 @@ std::vector<int> distinct_devices(const mlhip_group* g)
     }
 }
 
+std::vector<uint64_t> balanced_rows(uint64_t n, int shards)
+{
+    std::vector<uint64_t> first((size_t)shards + 1, 0);
+    const uint64_t base = n / (uint64_t)shards, rem = n % (uint64_t)shards;
+    for (int s = 0; s < shards; ++s) first[(size_t)s + 1] = first[(size_t)s] + base + ((uint64_t)s < rem ? 1 : 0);
+    return first;
+}
+
 void fan_out(mlhip_ctx* ctx, mlhip_data* data, const std::function<int(Shard&)>& f)
+{
+    fan_out_rows(ctx, data->first_row, data, f);
+}
+
+void fan_out_rows(mlhip_ctx* ctx, const std::vector<uint64_t>& first_row, mlhip_data* data, const std::function<int(Shard&)>& f)
 {
     mlhip_group* g = group_of(ctx);
     std::vector<Shard> view((size_t)g->n);
@@ -185,9 +198,9 @@ void fan_out(mlhip_ctx* ctx, mlhip_data* data, const std::function<int(Shard&)>&
         Shard& sh = view[(size_t)s];
         sh.index = s;
         sh.ctx = g->shard[(size_t)s];
-        sh.part = data->parts[(size_t)s];
-        sh.first_row = data->first_row[(size_t)s];
-        sh.n_rows = data->first_row[(size_t)s + 1] - sh.first_row;
+        sh.part = data ? data->parts[(size_t)s] : nullptr;
+        sh.first_row = first_row[(size_t)s];
+        sh.n_rows = first_row[(size_t)s + 1] - sh.first_row;
         sh.scratch.reserve(8);                                // (so that the shard's thread allocates its outputs only)
         sh.scalars.reserve(4);
     }
@@ -372,6 +385,22 @@ mlhip_data* upload(mlhip_ctx* ctx, const double* x, bool on_device, uint32_t d, 
     require(x != nullptr || n == 0, "null data");
     require(d >= 1, "At least one dimension required");
     require(ld >= (int64_t)d, "ld must be >= d");
+    if (padded_dim((int)d) < 0) throw Unsupported("dimension d > 4096 is not supported");
+    if (on_device && n) {
+        // a block already in device memory must be readable from every shard's GPU: its own GPU, or a peer with access enabled
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, x) != hipSuccess) { (void)hipGetLastError(); throw InvalidArgument("x_dev is not a device pointer"); }
+        enable_peer_access(distinct_devices(g), attr.device, "upload the block from host memory");
+    }
+    return upload_parts(ctx, d, n, [&](mlhip_ctx* shard, uint64_t first_row, uint64_t rows) {
+        return upload_common(shard, x ? x + (int64_t)first_row * ld : nullptr, on_device, d, rows, ld);
+    });
+}
+
+mlhip_data* upload_parts(mlhip_ctx* ctx, uint32_t d, uint64_t n, const PartSource& source)
+{
+    mlhip_group* g = group_of(ctx);
+    require(d >= 1, "At least one dimension required");
     auto* gd = new mlhip_data;
     try {
         gd->ctx = ctx;
@@ -381,20 +410,10 @@ mlhip_data* upload(mlhip_ctx* ctx, const double* x, bool on_device, uint32_t d, 
         gd->n_global = n;
         gd->n = (uint32_t)std::min<uint64_t>(n, 0xffffffffull);
         gd->parts.assign((size_t)g->n, nullptr);
-        // contiguous, balanced row shards that tile [0, n) -- the split of ml_amd.dist.shard_bounds, so that a group reproduces the
-        // multi-process job of the same size
-        gd->first_row.assign((size_t)g->n + 1, 0);
-        const uint64_t base = n / (uint64_t)g->n, rem = n % (uint64_t)g->n;
-        for (int s = 0; s < g->n; ++s) gd->first_row[(size_t)s + 1] = gd->first_row[(size_t)s] + base + ((uint64_t)s < rem ? 1 : 0);
-        if (on_device && n) {
-            // a block already in device memory must be readable from every shard's GPU: its own GPU, or a peer with access enabled
-            hipPointerAttribute_t attr{};
-            if (hipPointerGetAttributes(&attr, x) != hipSuccess) { (void)hipGetLastError(); throw InvalidArgument("x_dev is not a device pointer"); }
-            enable_peer_access(distinct_devices(g), attr.device, "upload the block from host memory");
-        }
+        gd->first_row = balanced_rows(n, g->n);
         run_on_shards(g, [&](int s) {
             const uint64_t lo = gd->first_row[(size_t)s], rows = gd->first_row[(size_t)s + 1] - lo;
-            gd->parts[(size_t)s] = upload_common(g->shard[(size_t)s], x ? x + (int64_t)lo * ld : nullptr, on_device, d, rows, ld);
+            gd->parts[(size_t)s] = source(g->shard[(size_t)s], lo, rows);
         });
         gd->shift = gd->parts[0]->shift;
         require(gd->parts[0]->n_global == n, "device group: the shards disagree on the sample size");

@@ -652,6 +652,17 @@ struct ScoreRoute {
 };
 ScoreRoute score_route(const mlhip_data* data, int K);
 
+/// mlhip_em_sample / _sample_data: the kernel em_sample_route (device/em_sample.hip) names for the shape -- under
+/// MLHIP_SAMPLE_TABLE=global the global-table form where the LDS-table form would run (same bits) -- and the rows the host-output form
+/// generates per chunk: a pool block of at most kSampleChunkBytes, whole 64-row tiles (MLHIP_SAMPLE_ROWS overrides; the rows do not
+/// depend on it). (mlhip.h names the kernels by SampleKernel's values.)
+constexpr uint64_t kSampleChunkBytes = uint64_t(64) << 20;
+struct SampleRoute {
+    int kernel = kSampleLdsTable;
+    uint64_t chunk_rows = 64;
+};
+SampleRoute sample_route(int d, uint32_t K);
+
 /// mlhip_em_iterate_restarts: R loops one after the other (every shape and mode), or BATCHED -- the restarts still running share the
 /// three launches of an iteration (em_restarts.hip) -- where the solo iteration is the fused kernel in its vector-unit form on at
 /// most one workgroup per CU: full covariances, an unweighted block, a single rank without an all-reduce hook. The batch is taken from
@@ -950,6 +961,12 @@ private:
 /// f(shard) on every shard's thread (ShardTeam: a failure of one shard fails the call on the caller's thread, the group recovers
 /// before the next one); f returns the status of the shard's own mlhip_* call.
 void fan_out(mlhip_ctx* ctx, mlhip_data* data, const std::function<int(Shard&)>& f);
+/// The same over a row split given by the caller (first_row: shards + 1 entries) -- a call that has rows but no block yet
+/// (mlhip_em_sample); `data` may be null, the shards' `part` is null then.
+void fan_out_rows(mlhip_ctx* ctx, const std::vector<uint64_t>& first_row, mlhip_data* data, const std::function<int(Shard&)>& f);
+/// The contiguous, balanced row shards that tile [0, n): shard s holds rows [first[s], first[s + 1]) (the split of
+/// ml_amd.dist.shard_bounds, so that a group reproduces the multi-process job of the same size).
+std::vector<uint64_t> balanced_rows(uint64_t n, int shards);
 
 // What is not a plain fan-out:
 namespace grp {
@@ -960,6 +977,11 @@ int shard_count(const mlhip_ctx* ctx);
 mlhip_ctx* shard_context(const mlhip_ctx* ctx, int shard);
 const char* reduce_kind(const mlhip_ctx* ctx);
 mlhip_data* upload(mlhip_ctx* ctx, const double* x, bool on_device, uint32_t d, uint64_t n, int64_t ld);
+/// The group's handle over n rows from parts the shards make themselves: `source` runs on every shard's thread with that shard's
+/// context and its rows [first_row, first_row + rows) of the balanced split and returns the shard's block (upload: upload_common on
+/// its rows of the caller's block; mlhip_em_sample_data: the rows the shard generated on its own GPU).
+using PartSource = std::function<mlhip_data*(mlhip_ctx* shard, uint64_t first_row, uint64_t rows)>;
+mlhip_data* upload_parts(mlhip_ctx* ctx, uint32_t d, uint64_t n, const PartSource& source);
 /// (the shards one after the other: they continue each other's running means)
 void random_partition_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const uint32_t* order, const uint32_t* offsets, double* means,
                             double* sizes);

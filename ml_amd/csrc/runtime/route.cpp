@@ -29,6 +29,8 @@ struct Switches {
     long score_rows;            // MLHIP_SCORE_ROWS=n: rows per chunk of the composed scoring route (0: by the scratch bound)
     int tied;                   // MLHIP_TIED=composed / kernel: kTiedComposed / kTiedKernel forced (the kernel: where it exists), -1 automatic
     int restarts;               // MLHIP_EM_RESTARTS=sequential / batch: kRestartsSequential / kRestartsBatched forced (the batch: where it exists), -1 automatic
+    bool sample_global;         // MLHIP_SAMPLE_TABLE=global: the sampler reads its table from global memory where it would fit LDS
+    long sample_rows;           // MLHIP_SAMPLE_ROWS=n: rows per chunk of the host-output sampler (0: by kSampleChunkBytes)
 };
 
 Switches read_switches()
@@ -60,10 +62,25 @@ Switches read_switches()
     s.tied = !tied ? -1 : std::strcmp(tied, "composed") == 0 ? kTiedComposed : std::strcmp(tied, "kernel") == 0 ? kTiedKernel : -1;
     const char* restarts = std::getenv("MLHIP_EM_RESTARTS");
     s.restarts = !restarts ? -1 : std::strcmp(restarts, "sequential") == 0 ? kRestartsSequential : std::strcmp(restarts, "batch") == 0 ? kRestartsBatched : -1;
+    const char* sample_table = std::getenv("MLHIP_SAMPLE_TABLE");
+    s.sample_global = sample_table && std::strcmp(sample_table, "global") == 0;
+    const char* sample_rows = std::getenv("MLHIP_SAMPLE_ROWS");
+    s.sample_rows = sample_rows && *sample_rows ? std::atol(sample_rows) : 0;
     return s;
 }
 
 }  // namespace
+
+SampleRoute sample_route(int d, uint32_t K)
+{
+    const Switches sw = read_switches();
+    SampleRoute r;
+    r.kernel = em_sample_route(d, K);
+    if (r.kernel == kSampleLdsTable && sw.sample_global) r.kernel = kSampleGlobalTable;
+    const uint64_t rows = sw.sample_rows > 0 ? (uint64_t)sw.sample_rows : (kSampleChunkBytes / (sizeof(double) * (uint64_t)d)) & ~uint64_t(63);
+    r.chunk_rows = std::max<uint64_t>(rows, 64);
+    return r;
+}
 
 EmRoute em_route(const mlhip_data* data, int K, bool diag)
 {
