@@ -181,8 +181,14 @@ private:
     std::vector<unsigned int> initialisation_steps_;
     std::vector<int> initialisation_converged_;
 
+    struct FitJob;                                                   // what the pieces of one fit share (EM.cpp)
+    bool finish_exact_fit(unsigned int number_dimensions);
+    void make_start(FitJob& job, double* covariance);
+    bool run_verbose(const FitJob& job, double* covariance, std::vector<double>* last_inputs);
     void process_covariances(Index number_dimensions);
+    std::vector<double> flat_covariances() const;                    // covariances() as one number_components() x d x d array
     void require_fitted_for(ConstMatrixRef data) const;
+    void require_fitted() const;
     void score(ConstMatrixRef data, double* log_density, unsigned int* labels) const;
 };
 

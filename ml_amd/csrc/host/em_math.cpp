@@ -2,10 +2,12 @@
 
 #include <sched.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <functional>
+#include <stdexcept>
 #include <vector>
 
 #include "../device/layout.hpp"
@@ -375,6 +377,50 @@ void finalize_mstep_tied(int d, int K, const double* stats, const double* total_
 }
 
 void set_host_ranks(int local_ranks) { g_host_threads.store(resolve_host_threads(local_ranks), std::memory_order_relaxed); }
+
+Covariance covariance_from_abi(int covariance_type)
+{
+    if (covariance_type < (int)Covariance::Full || covariance_type > (int)Covariance::Tied) throw std::invalid_argument("bad covariance_type");
+    return (Covariance)covariance_type;
+}
+
+std::size_t covariance_doubles(Covariance mode, int K, int d)
+{
+    const std::size_t k = (std::size_t)K, n = (std::size_t)d;
+    return mode == Covariance::Tied ? n * n : mode == Covariance::Diagonal ? k * n : k * n * n;
+}
+
+void covariances_as_full(Covariance mode, int K, int d, const double* covariance, double* full)
+{
+    const std::size_t dd = (std::size_t)d * d;
+    if (mode == Covariance::Diagonal) {
+        std::fill(full, full + (std::size_t)K * dd, 0.0);
+        for (int k = 0; k < K; ++k)
+            for (int j = 0; j < d; ++j) full[((std::size_t)k * d + j) * d + j] = covariance[(std::size_t)k * d + j];
+        return;
+    }
+    for (int k = 0; k < K; ++k) {
+        const double* from = mode == Covariance::Tied ? covariance : covariance + (std::size_t)k * dd;
+        std::copy(from, from + dd, full + (std::size_t)k * dd);
+    }
+}
+
+void covariances_from_full(Covariance mode, int K, int d, const double* mixing, const double* full, double* covariance)
+{
+    const std::size_t dd = (std::size_t)d * d;
+    if (mode == Covariance::Diagonal) {
+        for (int k = 0; k < K; ++k)
+            for (int j = 0; j < d; ++j) covariance[(std::size_t)k * d + j] = full[((std::size_t)k * d + j) * d + j];
+    } else if (mode == Covariance::Tied) {
+        for (std::size_t e = 0; e < dd; ++e) {
+            double v = 0.0;
+            for (int k = 0; k < K; ++k) v += mixing[k] * full[(std::size_t)k * dd + e];
+            covariance[e] = v;
+        }
+    } else {
+        std::copy(full, full + (std::size_t)K * dd, covariance);
+    }
+}
 
 }  // namespace host
 }  // namespace mlhip

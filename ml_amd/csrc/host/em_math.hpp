@@ -60,6 +60,24 @@ void build_tied_params(int d, int D, int K, int K_padded, const double* mixing, 
 void finalize_mstep_tied(int d, int K, const double* stats, const double* total_scatter, const double* shift, double total_weight,
                          double ridge, double* mixing, double* means, double* covariance);
 
+/// The covariance mode of an EM call: K full matrices (K d d doubles), K diagonals (K d variances) or the one matrix all components
+/// share (d d). The values are mlhip.h's MLHIP_COVARIANCE_* (runtime/internal.hpp checks that).
+enum class Covariance : int { Full = 0, Diagonal = 1, Tied = 2 };
+
+/// The mode an ABI `covariance_type` names; std::invalid_argument("bad covariance_type") for any other value.
+Covariance covariance_from_abi(int covariance_type);
+
+/// Doubles in the covariance array of `mode`.
+std::size_t covariance_doubles(Covariance mode, int K, int d);
+
+/// The covariance array of `mode` as K full d x d matrices in `full`: a diagonal becomes a diagonal matrix (+0.0 elsewhere), the tied
+/// matrix K copies, full matrices a copy.
+void covariances_as_full(Covariance mode, int K, int d, const double* covariance, double* full);
+
+/// K full matrices and the mixing weights pi as the covariance array of `mode`: the diagonals; the pooled sum_k pi_k Sigma_k -- per
+/// entry v = 0, then v += pi_k Sigma_k[e] in ascending k: the order is part of the results' bits --; a copy.
+void covariances_from_full(Covariance mode, int K, int d, const double* mixing, const double* full, double* covariance);
+
 /// Tells the host-side math how many ranks share this node, so that the OpenMP teams of the per-component
 /// factorizations together stay within the host's cores (MLHIP_HOST_THREADS overrides the per-rank thread count).
 void set_host_ranks(int local_ranks);

@@ -12,6 +12,7 @@
 #include "DeviceInit.hpp"
 #include "ML/Device.hpp"
 #include "ML/LinearAlgebra.hpp"
+#include "host/em_math.hpp"
 #include "mlhip.h"
 
 namespace ml {
@@ -19,7 +20,10 @@ namespace ml {
 using device::check;
 
 namespace {
-/// d x K matrix of means -> the ABI wants exactly this memory (column k = mean k).
+namespace host = mlhip::host;
+using host::Covariance;
+
+/// Owns a device block until release(): a fit that throws, and every batch of a query, frees its block.
 struct DataGuard {
     mlhip_data* h = nullptr;
     ~DataGuard() { if (h) mlhip_data_free(h); }
@@ -31,6 +35,17 @@ void print_row(const double* p, Index n, Index stride)
     for (Index j = 0; j < n; ++j) std::cout << (j ? " " : "") << p[j * stride];
 }
 }  // namespace
+
+/// What the pieces of one fit share: the sample, its device block, the shapes and the mode.
+struct EM::FitJob {
+    ConstMatrixRef data;
+    mlhip_ctx* ctx;
+    mlhip_data* dev;
+    unsigned int d, n, K;                        // dimensions, this rank's points, components
+    Covariance mode;
+    std::vector<double> full;                    // K d d doubles: a start's full covariances, in the end the published ones
+    std::vector<double> sample_covariance;       // formed once, by the first start that needs it
+};
 
 EM::EM(const unsigned int number_components)
     : means_initialiser_(std::make_shared<Clustering::Forgy>())
@@ -192,15 +207,9 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
         for (unsigned int i = 0; i < sample_size; ++i) {
             responsibilities_(i, i) = 1;
             std::copy_n(data.col(i), number_dimensions, means_.col(i));
-            covariances_[i].setZero(number_dimensions, number_dimensions);
             labels_[i] = i;
         }
-        log_likelihood_ = std::numeric_limits<double>::infinity();
-        converged_ = true;
-        initialisation_log_likelihoods_.assign(1, log_likelihood_);      // (the exact fit ignores number_initialisations(), like KMeans)
-        initialisation_steps_.assign(1, 0);
-        initialisation_converged_.assign(1, 1);
-        return converged_;
+        return finish_exact_fit(number_dimensions);
     }
 
     // ---- move the sample block to HBM (stays resident for the whole fit) ---------------------------------
@@ -228,244 +237,210 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
             labels_[i] = g;
         }
         Clustering::detail::sum_across_ranks(ctx, means_);
-        for (unsigned int k = 0; k < K; ++k) covariances_[k].setZero(number_dimensions, number_dimensions);
-        log_likelihood_ = std::numeric_limits<double>::infinity();
-        converged_ = true;
-        initialisation_log_likelihoods_.assign(1, log_likelihood_);      // (the exact fit ignores number_initialisations(), like KMeans)
-        initialisation_steps_.assign(1, 0);
-        initialisation_converged_.assign(1, 1);
-        return converged_;
+        return finish_exact_fit(number_dimensions);
     }
 
-    const std::size_t dd = static_cast<std::size_t>(number_dimensions) * number_dimensions;
-    const bool diagonal = covariance_type_ == CovarianceType::Diagonal;   // extension, see ML/EM.hpp
-    std::vector<double> cov_flat(dd * K);
-    const bool tied = covariance_type_ == CovarianceType::Tied;           // extension, see ML/EM.hpp
-    std::vector<double> var_flat;                                          // diagonal mode: K x d variances
-    std::vector<double> tied_cov;                                          // tied mode: the one d x d covariance
-    auto unpack_covariances = [&] {
-        for (unsigned int k = 0; k < K; ++k) {
-            covariances_[k].resize(number_dimensions, number_dimensions);
-            std::copy_n(cov_flat.data() + dd * k, dd, covariances_[k].data());
-        }
-    };
-    std::vector<double> sample_covariance;                                 // formed once, by the first start that needs it
+    // The mode (extension, see ML/EM.hpp) and the parameter set in its form: mixing_probabilities_, means_ and `covariance`.
+    static_assert(static_cast<int>(CovarianceType::Full) == static_cast<int>(Covariance::Full) &&
+                      static_cast<int>(CovarianceType::Diagonal) == static_cast<int>(Covariance::Diagonal) &&
+                      static_cast<int>(CovarianceType::Tied) == static_cast<int>(Covariance::Tied),
+                  "CovarianceType names the modes in host::Covariance's order");
+    FitJob job{data, ctx, dev.h, number_dimensions, sample_size, K, static_cast<Covariance>(covariance_type_), {}, {}};
+    job.full.resize(host::covariance_doubles(Covariance::Full, K, number_dimensions));
+    const std::size_t kd = static_cast<std::size_t>(number_dimensions) * K;
+    const std::size_t n_cov = host::covariance_doubles(job.mode, K, number_dimensions);
+    std::vector<double> covariance(n_cov);
 
-    // Start r -- what a solo fit would begin from, drawn from prng_ in order r = 0, 1, ... -- into mixing_probabilities_, means_ and
-    // cov_flat / var_flat / tied_cov.
-    auto make_start = [&] {
-        mixing_probabilities_.fill(1. / static_cast<double>(K));
-        if (maximise_first_) {
-            // Start from responsibilities, then one M-step (ML/EM.cpp:120-125).
-            const auto* closest = dynamic_cast<const Clustering::ClosestCentroid*>(responsibilities_initialiser_.get());
-            const Clustering::ResponsibilitiesInitialiser& initialiser = *responsibilities_initialiser_;
-            if (closest && typeid(initialiser) == typeid(Clustering::ClosestCentroid)) {
-                // Library ClosestCentroid: draw the centroids on the host exactly as it would, run the nearest-centroid
-                // pass (strict '<', first minimum wins: ML/Clustering.cpp:77-88) on the GPU and accumulate the one-hot
-                // M-step from labels -- no N x K matrix is materialised.
-                MatrixXd centroids(number_dimensions, K);
-                Clustering::detail::init_centroids(*closest->centroids_initialiser(), data, prng_, K, centroids, ctx, dev.h);
-                double inertia = 0;
-                uint64_t changed = 0;
-                check(mlhip_kmeans_assign(ctx, dev.h, K, centroids.data(), &inertia, &changed));
-                std::vector<unsigned int> hard(sample_size);
-                check(mlhip_kmeans_labels(ctx, dev.h, hard.data()));
-                check(mlhip_em_maximisation_from_labels(ctx, dev.h, K, hard.data(), mixing_probabilities_.data(), means_.data(),
-                                                        cov_flat.data()));
-            } else {
-                // User-defined initialiser: it fills a host N x K matrix, which is shipped to the device once.
-                responsibilities_.resize(sample_size, K);
-                responsibilities_initialiser_->init(data, prng_, K, responsibilities_);
-                check(mlhip_em_maximisation_from(ctx, dev.h, K, responsibilities_.data(), responsibilities_.rows(),
-                                                 mixing_probabilities_.data(), means_.data(), cov_flat.data()));
-            }
-        } else {
-            // Sensible guesses: initialiser's means, every covariance = sample covariance (ML/EM.cpp:127-135).
-            Clustering::detail::init_centroids(*means_initialiser_, data, prng_, K, means_, ctx, dev.h);   // identical on all ranks
-            if (sample_covariance.empty()) {
-                sample_covariance.resize(dd);
-                check(mlhip_sample_covariance(ctx, dev.h, nullptr, sample_covariance.data()));
-            }
-            for (unsigned int k = 0; k < K; ++k) std::copy_n(sample_covariance.data(), dd, cov_flat.data() + dd * k);
-        }
-
-        if (diagonal) {
-            // the diagonal of the starting covariances (a one-hot / responsibility-weighted M-step entry by entry, or the
-            // sample variances) is the diagonal-mode start
-            var_flat.resize(static_cast<std::size_t>(number_dimensions) * K);
-            for (unsigned int k = 0; k < K; ++k)
-                for (unsigned int j = 0; j < number_dimensions; ++j)
-                    var_flat[static_cast<std::size_t>(k) * number_dimensions + j] = cov_flat[dd * k + static_cast<std::size_t>(j) * number_dimensions + j];
-        }
-
-        if (tied) {
-            // the pooled sum_k pi_k Sigma_k of the starting covariances (ascending k) is the tied start: the tied M-step of the starting
-            // responsibilities, or -- K copies of the sample covariance with pi_k = 1 / K -- the sample covariance itself
-            tied_cov.assign(dd, 0.0);
-            for (std::size_t e = 0; e < dd; ++e)
-                for (unsigned int k = 0; k < K; ++k) tied_cov[e] += mixing_probabilities_[k] * cov_flat[dd * k + e];
-        }
-    };
-    // the covariance array of the mode in hand (what the loops below update in place)
-    auto mode_covariance = [&]() -> std::vector<double>& { return tied ? tied_cov : diagonal ? var_flat : cov_flat; };
-    const int covariance_code = tied ? MLHIP_COVARIANCE_TIED : diagonal ? MLHIP_COVARIANCE_DIAGONAL : MLHIP_COVARIANCE_FULL;
-
-    // The verbose loop of one start: one E-step + M-step per trip through the per-step entry points, printed as the reference prints.
-    // Returns whether it converged; `last_inputs` (may be null) receives the parameters its last E-step ran on.
-    auto run_verbose = [&](std::vector<double>* last_inputs) {
-        bool converged = false;
-        double old_log_likelihood = -std::numeric_limits<double>::infinity();
-        for (unsigned int step = 0; step < maximum_steps_; ++step) {
-            if (last_inputs) {
-                std::vector<double>& cov = mode_covariance();
-                last_inputs->assign(mixing_probabilities_.data(), mixing_probabilities_.data() + K);
-                last_inputs->insert(last_inputs->end(), means_.data(), means_.data() + static_cast<std::size_t>(number_dimensions) * K);
-                last_inputs->insert(last_inputs->end(), cov.begin(), cov.end());
-            }
-            // One E-step + M-step on the device; parameters are updated in place (ML/EM.cpp:145-147).
-            if (tied)
-                check(mlhip_em_step_tied(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), tied_cov.data(), &log_likelihood_,
-                                         mixing_probabilities_.data(), means_.data(), tied_cov.data()));
-            else if (diagonal)
-                check(mlhip_em_step_diag(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), var_flat.data(), &log_likelihood_,
-                                         mixing_probabilities_.data(), means_.data(), var_flat.data()));
-            else
-                check(mlhip_em_step(ctx, dev.h, K, mixing_probabilities_.data(), means_.data(), cov_flat.data(), &log_likelihood_,
-                                    mixing_probabilities_.data(), means_.data(), cov_flat.data()));
-            ++steps_done_;
-
-            std::cout << "Step " << step << "\n";
-            std::cout << "Log-likelihood == " << log_likelihood_ << "\n";
-            std::cout << "Mixing probabilities == ";
-            print_row(mixing_probabilities_.data(), K, 1);
-            std::cout << "\n";
-            for (unsigned int k = 0; k < K; ++k) {
-                std::cout << "Mean[" << k << "] == ";
-                print_row(means_.col(k), number_dimensions, 1);
-                std::cout << "\n";
-            }
-            std::cout << "Responsibilities (first 10 rows):\n";
-            // (only the rows that are printed cross the bus: ML/EM.cpp:155-156 prints topRows(10))
-            MatrixXd r(std::min(sample_size, 10u), K);
-            check(mlhip_em_responsibilities_rows(ctx, dev.h, K, 0, static_cast<uint64_t>(r.rows()), r.data(), r.rows()));
-            for (unsigned int i = 0; i < std::min(sample_size, 10u); ++i) {
-                print_row(r.data() + i, K, r.rows());
-                std::cout << "\n";
-            }
-            std::cout << std::endl;
-
-            if (step > 0) {
-                const double ll_change = std::abs(log_likelihood_ - old_log_likelihood);
-                if (ll_change < absolute_tolerance_ + relative_tolerance_ * std::max(std::abs(old_log_likelihood), std::abs(log_likelihood_))) {
-                    converged = true;
-                    break;
-                }
-            }
-            old_log_likelihood = log_likelihood_;
-        }
-        return converged;
-    };
-
+    // R starts, drawn one after the other as R consecutive solo fits would draw them (the loops consume no random numbers), then the R
+    // loops on the one resident block: the sample is uploaded once, weights, ridge and sample covariance are set once.
     const unsigned int R = number_initialisations_;
-    if (R == 1) {
-        make_start();
-        if (!verbose_) {
-            // The whole loop in one library call (same steps, same convergence test: ML/EM.cpp:143-170), with the M-step's
-            // closing arithmetic and the K covariance factorizations on the device between two tests.
-            uint32_t steps = 0;
-            int conv = 0;
-            check(mlhip_em_iterate(ctx, dev.h, K, covariance_code, mixing_probabilities_.data(), means_.data(), mode_covariance().data(),
-                                   maximum_steps_, absolute_tolerance_, relative_tolerance_, &steps, &conv, &log_likelihood_, nullptr));
-            steps_done_ = steps;
-            converged_ = conv != 0;
-        } else {
-            converged_ = run_verbose(nullptr);
-        }
-        if (converged_) check(mlhip_em_labels(ctx, dev.h, K, labels_.data()));   // EM::calculate_labels, on convergence only
-        initialisation_log_likelihoods_.assign(1, log_likelihood_);
-        initialisation_steps_.assign(1, steps_done_);
-        initialisation_converged_.assign(1, converged_ ? 1 : 0);
-    } else {
-        // R starts, drawn one after the other as R consecutive solo fits would draw them (the loops consume no random numbers), then
-        // the R loops on the one resident block: the sample is uploaded once, weights, ridge and sample covariance are set once.
-        const std::size_t kd = static_cast<std::size_t>(number_dimensions) * K;
-        std::vector<double> all_mixing, all_means, all_covariances;
-        for (unsigned int r = 0; r < R; ++r) {
-            make_start();
-            const std::vector<double>& cov = mode_covariance();
-            all_mixing.insert(all_mixing.end(), mixing_probabilities_.data(), mixing_probabilities_.data() + K);
-            all_means.insert(all_means.end(), means_.data(), means_.data() + kd);
-            all_covariances.insert(all_covariances.end(), cov.begin(), cov.end());
-        }
-        const std::size_t n_cov = all_covariances.size() / R;
-        std::vector<uint32_t> steps(R, 0);
-        initialisation_converged_.assign(R, 0);
-        initialisation_log_likelihoods_.assign(R, 0.0);
-        uint32_t best = 0;
-        if (!verbose_) {
-            check(mlhip_em_iterate_restarts(ctx, dev.h, K, covariance_code, R, all_mixing.data(), all_means.data(), all_covariances.data(),
-                                            maximum_steps_, absolute_tolerance_, relative_tolerance_, steps.data(),
+    std::vector<double> all_mixing, all_means, all_covariances;
+    for (unsigned int r = 0; r < R; ++r) {
+        make_start(job, covariance.data());
+        all_mixing.insert(all_mixing.end(), mixing_probabilities_.data(), mixing_probabilities_.data() + K);
+        all_means.insert(all_means.end(), means_.data(), means_.data() + kd);
+        all_covariances.insert(all_covariances.end(), covariance.begin(), covariance.end());
+    }
+    std::vector<uint32_t> steps(R, 0);
+    initialisation_converged_.assign(R, 0);
+    initialisation_log_likelihoods_.assign(R, 0.0);
+    uint32_t best = 0;
+    if (!verbose_) {
+        // The whole loop in one library call (same steps, same convergence test: ML/EM.cpp:143-170), with the M-step's closing
+        // arithmetic and the K covariance factorizations on the device between two tests; several starts in one call of their own.
+        if (R == 1)
+            check(mlhip_em_iterate(ctx, dev.h, K, static_cast<int>(job.mode), all_mixing.data(), all_means.data(), all_covariances.data(),
+                                   maximum_steps_, absolute_tolerance_, relative_tolerance_, steps.data(), initialisation_converged_.data(),
+                                   initialisation_log_likelihoods_.data(), nullptr));
+        else
+            check(mlhip_em_iterate_restarts(ctx, dev.h, K, static_cast<int>(job.mode), R, all_mixing.data(), all_means.data(),
+                                            all_covariances.data(), maximum_steps_, absolute_tolerance_, relative_tolerance_, steps.data(),
                                             initialisation_converged_.data(), initialisation_log_likelihoods_.data(), nullptr, &best));
-        } else {
-            // one start after the other; the winner's E-step state is put back by one E-step on the inputs of its last one
-            std::vector<double> last_inputs, best_inputs;
-            for (unsigned int r = 0; r < R; ++r) {
-                std::cout << "Initialisation " << r << "\n";
-                std::copy_n(all_mixing.data() + static_cast<std::size_t>(r) * K, K, mixing_probabilities_.data());
-                std::copy_n(all_means.data() + r * kd, kd, means_.data());
-                mode_covariance().assign(all_covariances.begin() + r * n_cov, all_covariances.begin() + (r + 1) * n_cov);
-                steps_done_ = 0;
-                initialisation_converged_[r] = run_verbose(&last_inputs) ? 1 : 0;
-                steps[r] = steps_done_;
-                initialisation_log_likelihoods_[r] = log_likelihood_;
-                std::copy_n(mixing_probabilities_.data(), K, all_mixing.data() + static_cast<std::size_t>(r) * K);
-                std::copy_n(means_.data(), kd, all_means.data() + r * kd);
-                std::copy(mode_covariance().begin(), mode_covariance().end(), all_covariances.begin() + r * n_cov);
-                uint32_t so_far = 0;
-                check(mlhip_em_select_restart(r + 1, initialisation_log_likelihoods_.data(), initialisation_converged_.data(), &so_far));
-                if (so_far == r) best_inputs = last_inputs;
-                best = so_far;
-            }
-            if (best + 1 != R) {
-                std::vector<double> full(dd * K, 0.0);                     // the winner's last E-step again (full covariances of its mode)
-                const double* cov = best_inputs.data() + K + kd;
-                for (unsigned int k = 0; k < K; ++k)
-                    for (unsigned int j = 0; j < number_dimensions; ++j)
-                        for (unsigned int l = 0; l < number_dimensions; ++l)
-                            full[dd * k + static_cast<std::size_t>(j) * number_dimensions + l] =
-                                tied ? cov[static_cast<std::size_t>(j) * number_dimensions + l]
-                                     : diagonal ? (j == l ? cov[static_cast<std::size_t>(k) * number_dimensions + j] : 0.0)
-                                                : cov[dd * k + static_cast<std::size_t>(j) * number_dimensions + l];
-                double ll = 0;
-                check(mlhip_em_expectation(ctx, dev.h, K, best_inputs.data(), best_inputs.data() + K, full.data(), &ll));
-            }
+    } else {
+        // one start after the other; the winner's E-step state is put back by one E-step on the inputs of its last one
+        std::vector<double> last_inputs, best_inputs;
+        for (unsigned int r = 0; r < R; ++r) {
+            if (R > 1) std::cout << "Initialisation " << r << "\n";
+            std::copy_n(all_mixing.data() + static_cast<std::size_t>(r) * K, K, mixing_probabilities_.data());
+            std::copy_n(all_means.data() + r * kd, kd, means_.data());
+            std::copy_n(all_covariances.data() + r * n_cov, n_cov, covariance.data());
+            steps_done_ = 0;
+            initialisation_converged_[r] = run_verbose(job, covariance.data(), R > 1 ? &last_inputs : nullptr) ? 1 : 0;
+            steps[r] = steps_done_;
+            initialisation_log_likelihoods_[r] = log_likelihood_;
+            std::copy_n(mixing_probabilities_.data(), K, all_mixing.data() + static_cast<std::size_t>(r) * K);
+            std::copy_n(means_.data(), kd, all_means.data() + r * kd);
+            std::copy_n(covariance.data(), n_cov, all_covariances.data() + r * n_cov);
+            uint32_t so_far = 0;
+            check(mlhip_em_select_restart(r + 1, initialisation_log_likelihoods_.data(), initialisation_converged_.data(), &so_far));
+            if (so_far == r) best_inputs = last_inputs;
+            best = so_far;
         }
-        best_initialisation_ = best;
-        initialisation_steps_.assign(steps.begin(), steps.end());
-        std::copy_n(all_mixing.data() + static_cast<std::size_t>(best) * K, K, mixing_probabilities_.data());
-        std::copy_n(all_means.data() + best * kd, kd, means_.data());
-        mode_covariance().assign(all_covariances.begin() + best * n_cov, all_covariances.begin() + (best + 1) * n_cov);
-        log_likelihood_ = initialisation_log_likelihoods_[best];
-        steps_done_ = steps[best];
-        converged_ = initialisation_converged_[best] != 0;
-        if (converged_) check(mlhip_em_labels(ctx, dev.h, K, labels_.data()));   // EM::calculate_labels, on convergence only
+        if (best + 1 != R) {
+            // the winner's last E-step again (full covariances of its mode)
+            host::covariances_as_full(job.mode, K, number_dimensions, best_inputs.data() + K + kd, job.full.data());
+            double ll = 0;
+            check(mlhip_em_expectation(ctx, dev.h, K, best_inputs.data(), best_inputs.data() + K, job.full.data(), &ll));
+        }
     }
 
-    if (diagonal) {
-        std::fill(cov_flat.begin(), cov_flat.end(), 0.0);
-        for (unsigned int k = 0; k < K; ++k)
-            for (unsigned int j = 0; j < number_dimensions; ++j)
-                cov_flat[dd * k + static_cast<std::size_t>(j) * number_dimensions + j] = var_flat[static_cast<std::size_t>(k) * number_dimensions + j];
+    // take the winner
+    best_initialisation_ = best;
+    initialisation_steps_.assign(steps.begin(), steps.end());
+    std::copy_n(all_mixing.data() + static_cast<std::size_t>(best) * K, K, mixing_probabilities_.data());
+    std::copy_n(all_means.data() + best * kd, kd, means_.data());
+    log_likelihood_ = initialisation_log_likelihoods_[best];
+    steps_done_ = steps[best];
+    converged_ = initialisation_converged_[best] != 0;
+    if (converged_) check(mlhip_em_labels(ctx, dev.h, K, labels_.data()));   // EM::calculate_labels, on convergence only
+
+    // publish: every covariances_[k] is a full matrix (diagonal: a diagonal one; tied: each holds Sigma)
+    host::covariances_as_full(job.mode, K, number_dimensions, all_covariances.data() + best * n_cov, job.full.data());
+    const std::size_t dd = static_cast<std::size_t>(number_dimensions) * number_dimensions;
+    for (unsigned int k = 0; k < K; ++k) {
+        covariances_[k].resize(number_dimensions, number_dimensions);
+        std::copy_n(job.full.data() + dd * k, dd, covariances_[k].data());
     }
-    if (tied)
-        for (unsigned int k = 0; k < K; ++k) std::copy_n(tied_cov.data(), dd, cov_flat.data() + dd * k);   // every covariances_[k] holds Sigma
-    unpack_covariances();
     process_covariances(number_dimensions);
     // The responsibilities of the last E-step stay in HBM; responsibilities() allocates and fetches them on demand.
     responsibilities_.resize(0, 0);
     responsibilities_on_device_ = true;
     device_data_ = dev.release();
     return converged_;
+}
+
+bool EM::finish_exact_fit(unsigned int number_dimensions)
+{
+    for (unsigned int k = 0; k < number_components_; ++k) covariances_[k].setZero(number_dimensions, number_dimensions);
+    log_likelihood_ = std::numeric_limits<double>::infinity();
+    converged_ = true;
+    initialisation_log_likelihoods_.assign(1, log_likelihood_);      // (the exact fit ignores number_initialisations(), like KMeans)
+    initialisation_steps_.assign(1, 0);
+    initialisation_converged_.assign(1, 1);
+    return converged_;
+}
+
+// Start r -- what a solo fit would begin from, drawn from prng_ in order r = 0, 1, ... -- into mixing_probabilities_, means_ and
+// `covariance` (the mode's form).
+void EM::make_start(FitJob& job, double* covariance)
+{
+    const unsigned int K = job.K;
+    const std::size_t dd = static_cast<std::size_t>(job.d) * job.d;
+    mixing_probabilities_.fill(1. / static_cast<double>(K));
+    if (maximise_first_) {
+        // Start from responsibilities, then one M-step (ML/EM.cpp:120-125).
+        const auto* closest = dynamic_cast<const Clustering::ClosestCentroid*>(responsibilities_initialiser_.get());
+        const Clustering::ResponsibilitiesInitialiser& initialiser = *responsibilities_initialiser_;
+        if (closest && typeid(initialiser) == typeid(Clustering::ClosestCentroid)) {
+            // Library ClosestCentroid: draw the centroids on the host exactly as it would, run the nearest-centroid
+            // pass (strict '<', first minimum wins: ML/Clustering.cpp:77-88) on the GPU and accumulate the one-hot
+            // M-step from labels -- no N x K matrix is materialised.
+            MatrixXd centroids(job.d, K);
+            Clustering::detail::init_centroids(*closest->centroids_initialiser(), job.data, prng_, K, centroids, job.ctx, job.dev);
+            double inertia = 0;
+            uint64_t changed = 0;
+            check(mlhip_kmeans_assign(job.ctx, job.dev, K, centroids.data(), &inertia, &changed));
+            std::vector<unsigned int> hard(job.n);
+            check(mlhip_kmeans_labels(job.ctx, job.dev, hard.data()));
+            check(mlhip_em_maximisation_from_labels(job.ctx, job.dev, K, hard.data(), mixing_probabilities_.data(), means_.data(),
+                                                    job.full.data()));
+        } else {
+            // User-defined initialiser: it fills a host N x K matrix, which is shipped to the device once.
+            responsibilities_.resize(job.n, K);
+            responsibilities_initialiser_->init(job.data, prng_, K, responsibilities_);
+            check(mlhip_em_maximisation_from(job.ctx, job.dev, K, responsibilities_.data(), responsibilities_.rows(),
+                                             mixing_probabilities_.data(), means_.data(), job.full.data()));
+        }
+    } else {
+        // Sensible guesses: initialiser's means, every covariance = sample covariance (ML/EM.cpp:127-135).
+        Clustering::detail::init_centroids(*means_initialiser_, job.data, prng_, K, means_, job.ctx, job.dev);   // identical on all ranks
+        if (job.sample_covariance.empty()) {
+            job.sample_covariance.resize(dd);
+            check(mlhip_sample_covariance(job.ctx, job.dev, nullptr, job.sample_covariance.data()));
+        }
+        host::covariances_as_full(Covariance::Tied, K, job.d, job.sample_covariance.data(), job.full.data());
+    }
+    // Diagonal: the diagonal of the starting covariances (a one-hot / responsibility-weighted M-step entry by entry, or the sample
+    // variances). Tied: their pooled sum_k pi_k Sigma_k (ascending k) -- the tied M-step of the starting responsibilities, or, from K
+    // copies of the sample covariance with pi_k = 1 / K, that sum of K equal terms.
+    host::covariances_from_full(job.mode, K, job.d, mixing_probabilities_.data(), job.full.data(), covariance);
+}
+
+// The verbose loop of one start: one E-step + M-step per trip through the per-step entry point of the mode, printed as the reference
+// prints. Returns whether it converged; `last_inputs` (may be null) receives the parameters its last E-step ran on.
+bool EM::run_verbose(const FitJob& job, double* covariance, std::vector<double>* last_inputs)
+{
+    const unsigned int K = job.K;
+    const auto step_of_mode = job.mode == Covariance::Tied ? mlhip_em_step_tied : job.mode == Covariance::Diagonal ? mlhip_em_step_diag : mlhip_em_step;
+    const std::size_t n_cov = host::covariance_doubles(job.mode, K, job.d);
+    double old_log_likelihood = -std::numeric_limits<double>::infinity();
+    for (unsigned int step = 0; step < maximum_steps_; ++step) {
+        if (last_inputs) {
+            last_inputs->assign(mixing_probabilities_.data(), mixing_probabilities_.data() + K);
+            last_inputs->insert(last_inputs->end(), means_.data(), means_.data() + static_cast<std::size_t>(job.d) * K);
+            last_inputs->insert(last_inputs->end(), covariance, covariance + n_cov);
+        }
+        // One E-step + M-step on the device; parameters are updated in place (ML/EM.cpp:145-147).
+        check(step_of_mode(job.ctx, job.dev, K, mixing_probabilities_.data(), means_.data(), covariance, &log_likelihood_,
+                           mixing_probabilities_.data(), means_.data(), covariance));
+        ++steps_done_;
+
+        std::cout << "Step " << step << "\n";
+        std::cout << "Log-likelihood == " << log_likelihood_ << "\n";
+        std::cout << "Mixing probabilities == ";
+        print_row(mixing_probabilities_.data(), K, 1);
+        std::cout << "\n";
+        for (unsigned int k = 0; k < K; ++k) {
+            std::cout << "Mean[" << k << "] == ";
+            print_row(means_.col(k), job.d, 1);
+            std::cout << "\n";
+        }
+        std::cout << "Responsibilities (first 10 rows):\n";
+        // (only the rows that are printed cross the bus: ML/EM.cpp:155-156 prints topRows(10))
+        MatrixXd r(std::min(job.n, 10u), K);
+        check(mlhip_em_responsibilities_rows(job.ctx, job.dev, K, 0, static_cast<uint64_t>(r.rows()), r.data(), r.rows()));
+        for (unsigned int i = 0; i < std::min(job.n, 10u); ++i) {
+            print_row(r.data() + i, K, r.rows());
+            std::cout << "\n";
+        }
+        std::cout << std::endl;
+
+        if (step > 0) {
+            const double ll_change = std::abs(log_likelihood_ - old_log_likelihood);
+            if (ll_change < absolute_tolerance_ + relative_tolerance_ * std::max(std::abs(old_log_likelihood), std::abs(log_likelihood_)))
+                return true;
+        }
+        old_log_likelihood = log_likelihood_;
+    }
+    return false;
+}
+
+std::vector<double> EM::flat_covariances() const
+{
+    const std::size_t dd = static_cast<std::size_t>(means_.rows()) * static_cast<std::size_t>(means_.rows());
+    std::vector<double> flat(dd * number_components_);
+    for (unsigned int k = 0; k < number_components_; ++k) std::copy_n(covariances_[k].data(), dd, flat.data() + dd * k);
+    return flat;
 }
 
 void EM::assign_responsibilities(ConstVectorRef x, VectorRef u) const
@@ -489,8 +464,13 @@ void EM::assign_responsibilities(ConstVectorRef x, VectorRef u) const
 void EM::require_fitted_for(ConstMatrixRef data) const
 {
     if (data.rows() != means().rows()) throw std::invalid_argument("Wrong data size");
+    require_fitted();
+}
+
+void EM::require_fitted() const
+{
     (void)device::context();                                 // (no GPU: the "no CPU fallback" error, whatever the model holds)
-    if (inverse_covariances_.empty() || inverse_covariances_[0].rows() != data.rows())
+    if (inverse_covariances_.empty() || inverse_covariances_[0].rows() != means().rows())
         throw std::invalid_argument("EM: model has no fitted covariance decompositions");
 }
 
@@ -499,9 +479,7 @@ void EM::score(ConstMatrixRef data, double* log_density, unsigned int* labels) c
     require_fitted_for(data);
     const Index d = data.rows(), n = data.cols(), batch = Clustering::detail::score_batch_rows();
     if (!n) return;
-    const std::size_t dd = static_cast<std::size_t>(d) * d;
-    std::vector<double> cov_flat(dd * number_components_);
-    for (unsigned int k = 0; k < number_components_; ++k) std::copy_n(covariances_[k].data(), dd, cov_flat.data() + dd * k);
+    const std::vector<double> cov_flat = flat_covariances();
     mlhip_ctx* ctx = device::context();
     for (Index first = 0; first < n; first += batch) {
         const Index rows = std::min(batch, n - first);
@@ -543,9 +521,7 @@ MatrixXd EM::calculate_responsibilities(ConstMatrixRef data) const
     if (!n) return out;
     // (a batch holds its rows x K log-responsibilities on the device: at most 2^27 doubles of them)
     const Index batch = std::max<Index>(256, std::min(Clustering::detail::score_batch_rows(), (Index(1) << 27) / K));
-    const std::size_t dd = static_cast<std::size_t>(d) * d;
-    std::vector<double> cov_flat(dd * K);
-    for (unsigned int k = 0; k < K; ++k) std::copy_n(covariances_[k].data(), dd, cov_flat.data() + dd * k);
+    const std::vector<double> cov_flat = flat_covariances();
     mlhip_ctx* ctx = device::context();
     for (Index first = 0; first < n; first += batch) {
         const Index rows = std::min(batch, n - first);
@@ -562,17 +538,13 @@ MatrixXd EM::sample(Index n, std::uint64_t seed, std::vector<unsigned int>* labe
 {
     if (n < 0) throw std::invalid_argument("EM: Negative number of samples");
     const Index d = means().rows();
-    // (the order of require_fitted_for: the shape, the device, the decompositions)
+    // (the order of require_fitted_for: the shape -- here: that there is one --, the device, the decompositions)
     if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
-    (void)device::context();
-    if (inverse_covariances_.empty() || inverse_covariances_[0].rows() != d)
-        throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    require_fitted();
     MatrixXd out(d, n);
     if (labels) labels->resize(static_cast<std::size_t>(n));
     if (!n) return out;
-    const std::size_t dd = static_cast<std::size_t>(d) * d;
-    std::vector<double> cov_flat(dd * number_components_);
-    for (unsigned int k = 0; k < number_components_; ++k) std::copy_n(covariances_[k].data(), dd, cov_flat.data() + dd * k);
+    const std::vector<double> cov_flat = flat_covariances();
     mlhip_ctx* ctx = device::context();
     static_assert(sizeof(unsigned int) == sizeof(uint32_t), "labels are 32-bit");
     const Index batch = Clustering::detail::score_batch_rows();

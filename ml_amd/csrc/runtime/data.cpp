@@ -167,7 +167,7 @@ void run_total_scatter(mlhip_data* data)
     ensure_em_workspace(data, 1);
     data->estep.invalidate();
     launch_fill_responsibilities(nullptr, data->n, 1, data->lw.as<double>(), data->ldr, data->ctx->stream);
-    run_mstats(data, em_route(data, 1, false), 1, kFromResp, data->lw.as<double>(), data->ldr, false);
+    run_mstats(data, em_route(data, 1, Covariance::Full), 1, kFromResp, data->lw.as<double>(), data->ldr, false);
 }
 
 }  // namespace mlhip_rt
@@ -356,7 +356,7 @@ int mlhip_xxt_xy(mlhip_ctx* ctx, mlhip_data* data, const double* y, double* xxt,
         HIP_CHECK(hipMemsetAsync(w + data->ldr, 0, sizeof(double) * data->ldr, ctx->stream));
         if (data->n)
             HIP_CHECK(hipMemcpyAsync(w + data->ldr, y, sizeof(double) * data->n, hipMemcpyHostToDevice, ctx->stream));
-        run_mstats(data, em_route(data, 2, false), 2, kFromResp, w, data->ldr, false, true, false);
+        run_mstats(data, em_route(data, 2, Covariance::Full), 2, kFromResp, w, data->ldr, false, true, false);
         const int d = data->d, F = stats_count(d);
         const double* s0 = data->stats_host.as<double>();
         const double* s1 = s0 + F;

@@ -131,22 +131,11 @@ void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, co
 }
 
 
-/// K x d variances as K full covariance matrices (zero off the diagonal).
-static std::vector<double> diagonal_as_full(int K, int d, const double* variances)
+/// The covariance array of `mode` as K full covariance matrices (host::covariances_as_full).
+std::vector<double> as_full(Covariance mode, int K, int d, const double* covariance)
 {
-    std::vector<double> covs((size_t)K * d * d, 0.0);
-    for (int k = 0; k < K; ++k)
-        for (int j = 0; j < d; ++j) covs[((size_t)k * d + j) * d + j] = variances[(size_t)k * d + j];
-    return covs;
-}
-
-
-/// One d x d covariance as the covariances of K components that all carry it.
-static std::vector<double> tied_as_full(int K, int d, const double* cov)
-{
-    const size_t dd = (size_t)d * d;
-    std::vector<double> covs((size_t)K * dd);
-    for (int k = 0; k < K; ++k) std::copy(cov, cov + dd, covs.begin() + (size_t)k * dd);
+    std::vector<double> covs(covariance_doubles(Covariance::Full, K, d));
+    host::covariances_as_full(mode, K, d, covariance, covs.data());
     return covs;
 }
 
@@ -156,11 +145,10 @@ static std::vector<double> tied_as_full(int K, int d, const double* cov)
 void ensure_lw(mlhip_data* dt, const EmRoute& r, int K)
 {
     if (!dt->estep.needs_rebuild()) return;
-    if (dt->estep.diagonal() || dt->estep.tied()) {
+    if (dt->estep.mode_records()) {
         // params_dev holds diagonal / tied records: the same parameters as full covariances for the E-step kernel
         const EstepState::Kept& p = dt->estep.kept;
-        const std::vector<double> covs = dt->estep.diagonal() ? diagonal_as_full(K, dt->d, p.covariance.data())
-                                                              : tied_as_full(K, dt->d, p.covariance.data());
+        const std::vector<double> covs = as_full(p.mode, K, dt->d, p.covariance.data());
         prepare_estep(dt, r, K, p.mixing.data(), p.means.data(), covs.data());
     }
     launch_estep(dt, r, K);
@@ -443,7 +431,7 @@ void run_diag_kernel(mlhip_data* dt, const EmRoute& r, int K, const double* shif
     a.exact = r.diag_exact ? 1 : 0;
     const int grid = run_one_pass(dt, a, "em_diag", "diagonal", mstats::em_diag_partial_rows(K), mstats::em_diag_partial_cols(dt->d),
                                   diag_stats_count(dt->d), [&] { return mstats::launch_em_diag(a, ctx->num_cus, ctx->stream); });
-    dt->estep.diag_records_only(grid);
+    dt->estep.mode_records_only(Covariance::Diagonal, grid);
     if (collect) collect_stats(dt, K, (size_t)K * diag_stats_count(dt->d) + 1);
 }
 
@@ -540,16 +528,15 @@ void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixin
         // full-covariance kernels on diagonal matrices -- the E-step's Cholesky of a diagonal matrix is its square root, and
         // the diagonal of the M-step's full covariance IS the diagonal-mode variance (ML/EM.cpp:245-257 entry by entry); the
         // off-diagonal sums are computed and dropped. Slower than it could be, never refused.
-        const std::vector<double> cov = diagonal_as_full(K, d, variances);
-        std::vector<double> cov_out((size_t)K * d * d);
+        const std::vector<double> cov = as_full(Covariance::Diagonal, K, d, variances);
+        std::vector<double> cov_out(cov.size());
         em_step_full(data, r, K, mixing, means, cov.data(), log_likelihood, mixing_out, means_out, cov_out.data());
-        for (int k = 0; k < K; ++k)
-            for (int j = 0; j < d; ++j) variances_out[(size_t)k * d + j] = cov_out[((size_t)k * d + j) * d + j];
+        host::covariances_from_full(Covariance::Diagonal, K, d, mixing_out, cov_out.data(), variances_out);
         return;
     }
     ensure_em_workspace(data, K);
     // keep the input parameters: labels / responsibilities are produced from them on demand (ensure_lw)
-    data->estep.diag_parameters(K, d, mixing, means, variances);
+    data->estep.parameters(Covariance::Diagonal, K, d, mixing, means, variances);
     upload_diag_records(data, K, mixing, means, variances, data->params_dev);
     run_diag_kernel(data, r, K, data->shift_dev.as<double>());
     const int F = diag_stats_count(d);
@@ -570,7 +557,7 @@ static void run_tied_kernel(mlhip_data* dt, int K)
     a.winv = a.params + (size_t)mstats::em_tied_partial_rows(K) * tied_param_stride(dt->D);
     const int grid = run_one_pass(dt, a, "em_tied", "tied", mstats::em_tied_partial_rows(K), mstats::em_tied_partial_cols(dt->d),
                                   tied_stats_count(dt->d), [&] { return mstats::launch_em_tied(a, ctx->num_cus, ctx->stream); });
-    dt->estep.tied_records_only(grid);
+    dt->estep.mode_records_only(Covariance::Tied, grid);
     collect_stats(dt, K, (size_t)K * tied_stats_count(dt->d) + 1);
 }
 
@@ -592,25 +579,20 @@ static void upload_tied_records(mlhip_data* data, int K, const double* mixing, c
 }
 
 
-void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mixing, const double* means, const double* cov,
+void em_step_tied(mlhip_data* data, const ModeRoute& r, int K, const double* mixing, const double* means, const double* cov,
                   double* log_likelihood, double* mixing_out, double* means_out, double* cov_out)
 {
     const int d = data->d;
-    const size_t dd = (size_t)d * d;
-    if (r.kernel != kTiedKernel) {
+    if (r.tied_kernel != kTiedKernel) {
         // COMPOSED: one full-covariance step on K copies of the covariance, on whatever route this shape takes (weights, the
         // refinement pass, big dimensions and the plain tier included), then  Sigma = sum_k pi_k Sigma_k  in ascending k -- the tied
         // M-step, since sum_k S0_k Sigma_k = T - sum_k S1_k S1_k^T / S0_k. Every Sigma_k carries the handle's ridge r I (ML/EM.cpp:252),
         // and sum_k pi_k = 1 up to rounding: the K ridges pool to the one ridge of the tied mode. Nothing is subtracted or re-added.
         // Slower than it could be, never refused.
-        const std::vector<double> covs = tied_as_full(K, d, cov);
-        std::vector<double> covs_out((size_t)K * dd);
+        const std::vector<double> covs = as_full(Covariance::Tied, K, d, cov);
+        std::vector<double> covs_out(covs.size());
         em_step_full(data, r.em, K, mixing, means, covs.data(), log_likelihood, mixing_out, means_out, covs_out.data());
-        for (size_t e = 0; e < dd; ++e) {
-            double v = 0.0;
-            for (int k = 0; k < K; ++k) v += mixing_out[k] * covs_out[(size_t)k * dd + e];
-            cov_out[e] = v;
-        }
+        host::covariances_from_full(Covariance::Tied, K, d, mixing_out, covs_out.data(), cov_out);
         return;
     }
     // T = sum_i xt_i xt_i^T does not depend on the responsibilities: once per handle, all-reduced like the statistics
@@ -621,7 +603,7 @@ void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mix
     }
     ensure_em_workspace(data, K);
     // keep the input parameters: labels / responsibilities are produced from them on demand (ensure_lw)
-    data->estep.tied_parameters(K, d, mixing, means, cov);
+    data->estep.parameters(Covariance::Tied, K, d, mixing, means, cov);
     upload_tied_records(data, K, mixing, means, cov);
     run_tied_kernel(data, K);
     const int F = tied_stats_count(d);
@@ -632,13 +614,24 @@ void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mix
 }
 
 
+void em_step(mlhip_data* data, const ModeRoute& r, int K, const double* mixing, const double* means, const double* covs,
+             double* log_likelihood, double* mixing_out, double* means_out, double* covs_out)
+{
+    switch (r.mode) {
+    case Covariance::Full: em_step_full(data, r.em, K, mixing, means, covs, log_likelihood, mixing_out, means_out, covs_out); break;
+    case Covariance::Diagonal: em_step_diag(data, r.em, K, mixing, means, covs, log_likelihood, mixing_out, means_out, covs_out); break;
+    case Covariance::Tied: em_step_tied(data, r, K, mixing, means, covs, log_likelihood, mixing_out, means_out, covs_out); break;
+    }
+}
+
+
 namespace {
 
 /// mlhip_em_step / mlhip_em_step_diag / mlhip_em_step_tied (`step`) through a device group: the outputs may alias the inputs, so the shards read copies.
-void group_em_step(decltype(&mlhip_em_step) step, mlhip_ctx* ctx, mlhip_data* data, uint32_t K, size_t cov_doubles, const double* mixing,
+void group_em_step(decltype(&mlhip_em_step) step, mlhip_ctx* ctx, mlhip_data* data, uint32_t K, Covariance mode, const double* mixing,
                    const double* means, const double* covs, double* log_likelihood, double* mixing_out, double* means_out, double* covs_out)
 {
-    const size_t kd = (size_t)K * data->d;
+    const size_t kd = (size_t)K * data->d, cov_doubles = covariance_doubles(mode, (int)K, data->d);
     const std::vector<double> pi(mixing, mixing + K), mu(means, means + kd), cv(covs, covs + cov_doubles);
     fan_out(ctx, data, [&](Shard& sh) {
         return step(sh.ctx, sh.part, K, pi.data(), mu.data(), cv.data(), sh.scalar(log_likelihood), sh.replicated(mixing_out, K),
@@ -664,7 +657,7 @@ int mlhip_em_expectation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const dou
             });
             return;
         }
-        run_estep(data, em_route(data, (int)K, false), (int)K, mixing, means, covariances);
+        run_estep(data, em_route(data, (int)K, Covariance::Full), (int)K, mixing, means, covariances);
         double* slot = data->stats_dev.as<double>() + (size_t)K * stats_count(data->d);
         launch_ll_reduce(data->ll_partials.as<double>(), data->estep.n_ll, slot, ctx->stream);
         HIP_CHECK(hipGetLastError());
@@ -691,7 +684,7 @@ int mlhip_em_maximisation(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, double* 
             return;
         }
         require(data->has_estep_results((int)K), "no E-step results on the device for this K");
-        const EmRoute r = em_route(data, (int)K, false);
+        const EmRoute r = em_route(data, (int)K, Covariance::Full);
         ensure_lw(data, r, (int)K);
         run_mstats(data, r, (int)K, kFromLogResp, nullptr, 0, true);
         finalize_out(data, r, (int)K, mixing_out, means_out, covariances_out);
@@ -706,11 +699,11 @@ int mlhip_em_step(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const double* mi
         check_call(ctx, data, K);
         require(mixing && means && covariances && log_likelihood && mixing_out && means_out && covariances_out, "null argument");
         if (ctx->group) {
-            group_em_step(mlhip_em_step, ctx, data, K, (size_t)K * data->d * data->d, mixing, means, covariances, log_likelihood, mixing_out,
+            group_em_step(mlhip_em_step, ctx, data, K, Covariance::Full, mixing, means, covariances, log_likelihood, mixing_out,
                           means_out, covariances_out);
             return;
         }
-        em_step_full(data, em_route(data, (int)K, false), (int)K, mixing, means, covariances, log_likelihood, mixing_out, means_out, covariances_out);
+        em_step(data, mode_route(data, (int)K, Covariance::Full), (int)K, mixing, means, covariances, log_likelihood, mixing_out, means_out, covariances_out);
     });
 }
 
@@ -722,11 +715,11 @@ int mlhip_em_step_diag(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const doubl
         check_call(ctx, data, K);
         require(mixing && means && variances && log_likelihood && mixing_out && means_out && variances_out, "null argument");
         if (ctx->group) {
-            group_em_step(mlhip_em_step_diag, ctx, data, K, (size_t)K * data->d, mixing, means, variances, log_likelihood, mixing_out, means_out,
+            group_em_step(mlhip_em_step_diag, ctx, data, K, Covariance::Diagonal, mixing, means, variances, log_likelihood, mixing_out, means_out,
                           variances_out);
             return;
         }
-        em_step_diag(data, em_route(data, (int)K, true), (int)K, mixing, means, variances, log_likelihood, mixing_out, means_out, variances_out);
+        em_step(data, mode_route(data, (int)K, Covariance::Diagonal), (int)K, mixing, means, variances, log_likelihood, mixing_out, means_out, variances_out);
     });
 }
 
@@ -738,11 +731,11 @@ int mlhip_em_step_tied(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const doubl
         check_call(ctx, data, K);
         require(mixing && means && covariance && log_likelihood && mixing_out && means_out && covariance_out, "null argument");
         if (ctx->group) {
-            group_em_step(mlhip_em_step_tied, ctx, data, K, (size_t)data->d * data->d, mixing, means, covariance, log_likelihood, mixing_out,
+            group_em_step(mlhip_em_step_tied, ctx, data, K, Covariance::Tied, mixing, means, covariance, log_likelihood, mixing_out,
                           means_out, covariance_out);
             return;
         }
-        em_step_tied(data, tied_route(data, (int)K), (int)K, mixing, means, covariance, log_likelihood, mixing_out, means_out, covariance_out);
+        em_step(data, mode_route(data, (int)K, Covariance::Tied), (int)K, mixing, means, covariance, log_likelihood, mixing_out, means_out, covariance_out);
     });
 }
 
@@ -753,14 +746,10 @@ int mlhip_em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covarianc
     return guarded([&] {
         check_call(ctx, data, K);
         require(mixing && means && covariances && steps_done && converged && log_likelihood, "null argument");
-        require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL ||
-                    covariance_type == MLHIP_COVARIANCE_TIED,
-                "bad covariance_type");
+        const Covariance mode = covariance_from_abi(covariance_type);
         require(max_steps >= 1, "at least one step required");
         if (absolute_tolerance < 0 || relative_tolerance < 0) throw DomainError("negative tolerance");
-        const bool diag = covariance_type == MLHIP_COVARIANCE_DIAGONAL;
-        const bool tied = covariance_type == MLHIP_COVARIANCE_TIED;
-        const size_t kd = (size_t)K * data->d, cov_doubles = tied ? (size_t)data->d * data->d : kd * (diag ? 1 : data->d);
+        const size_t kd = (size_t)K * data->d, cov_doubles = covariance_doubles(mode, (int)K, data->d);
         if (ctx->group) {
             // the parameters are in/out: shard 0 updates the caller's, the others copies of their own (the ranks' end-of-fit
             // checksum exchange inside the shards' calls holds them to bit-identical results)
@@ -773,12 +762,8 @@ int mlhip_em_iterate(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covarianc
             });
             return;
         }
-        if (tied)
-            em_iterate_tied(data, tied_route(data, (int)K), (int)K, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance,
-                            steps_done, converged, log_likelihood, log_likelihood_history);
-        else
-            em_iterate(data, em_route(data, (int)K, diag), (int)K, diag, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance, steps_done,
-                       converged, log_likelihood, log_likelihood_history);
+        em_iterate(data, mode, (int)K, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance, steps_done, converged,
+                   log_likelihood, log_likelihood_history);
         ctx->check_ranks_agree("the EM parameters", {{mixing, K}, {means, kd}, {covariances, cov_doubles}, {log_likelihood, 1}});
     });
 }
@@ -804,7 +789,7 @@ int mlhip_em_maximisation_from(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, con
         if (data->n)
             HIP_CHECK(hipMemcpy2DAsync(data->resp_dev.p, sizeof(double) * data->ldr, resp, sizeof(double) * ldr,
                                        sizeof(double) * data->n, K, hipMemcpyHostToDevice, ctx->stream));
-        const EmRoute r = em_route(data, (int)K, false);
+        const EmRoute r = em_route(data, (int)K, Covariance::Full);
         run_mstats(data, r, (int)K, kFromResp, data->resp_dev.as<double>(), data->ldr, false);
         finalize_out(data, r, (int)K, mixing_out, means_out, covariances_out);
     });
@@ -831,7 +816,7 @@ int mlhip_em_maximisation_from_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t
         // One-hot responsibilities are materialised in the (still unused) log-responsibility buffer of the workspace.
         data->estep.invalidate();
         launch_fill_responsibilities(data->labels_dev.as<uint32_t>(), data->n, (int)K, data->lw.as<double>(), data->ldr, ctx->stream);
-        const EmRoute r = em_route(data, (int)K, false);
+        const EmRoute r = em_route(data, (int)K, Covariance::Full);
         run_mstats(data, r, (int)K, kFromResp, data->lw.as<double>(), data->ldr, false);
         finalize_out(data, r, (int)K, mixing_out, means_out, covariances_out);
     });
@@ -849,7 +834,7 @@ int mlhip_em_responsibilities_rows(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
         if (ctx->group) { grp::em_responsibilities(ctx, data, K, resp, ldr, first_row, n_rows); return; }
         require(data->has_estep_results((int)K), "no E-step results on the device for this K");
         if (!n_rows) return;
-        ensure_lw(data, em_route(data, (int)K, false), (int)K);
+        ensure_lw(data, em_route(data, (int)K, Covariance::Full), (int)K);
         const size_t ldo = (size_t)padded_samples(n_rows);
         data->resp_dev.reserve(sizeof(double) * ldo * K);
         RespArgs a{data->lw.as<double>() + first_row, data->ldr, data->lse.as<double>() + first_row, (uint32_t)n_rows, (int)K,
@@ -878,7 +863,7 @@ int mlhip_em_labels(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t* labe
             return;
         }
         require(data->has_estep_results((int)K), "no E-step results on the device for this K");
-        ensure_lw(data, em_route(data, (int)K, false), (int)K);
+        ensure_lw(data, em_route(data, (int)K, Covariance::Full), (int)K);
         data->labels_dev.reserve(sizeof(uint32_t) * data->n_pad);
         RespArgs a{data->lw.as<double>(), data->ldr, data->lse.as<double>(), data->n, (int)K, nullptr, 0,
                    data->labels_dev.as<uint32_t>()};
@@ -937,7 +922,7 @@ int mlhip_em_tied_route(const mlhip_data* data, uint32_t K, int* kernel)
         require(data && kernel && K >= 1, "bad argument");
         if (!data->parts.empty()) data = data->parts[0];        // (a group's block: every shard takes the same route)
         static_assert(kTiedComposed == MLHIP_TIED_COMPOSED && kTiedKernel == MLHIP_TIED_KERNEL, "mlhip.h names the routes by TiedKernel");
-        *kernel = tied_route(data, (int)K).kernel;
+        *kernel = mode_route(data, (int)K, Covariance::Tied).tied_kernel;
     });
 }
 
@@ -954,7 +939,7 @@ int mlhip_em_plan(const mlhip_data* data, uint32_t K, uint32_t* flags)
     return guarded([&] {
         require(data && flags && K >= 1, "null argument");
         if (!data->parts.empty()) data = data->parts[0];        // (a group's block: every shard takes the same plan)
-        const EmRoute r = em_route(data, (int)K, false);
+        const EmRoute r = em_route(data, (int)K, Covariance::Full);
         uint32_t f = 0;
         if (r.fused) f |= MLHIP_PLAN_FUSED;
         else {
@@ -968,10 +953,10 @@ int mlhip_em_plan(const mlhip_data* data, uint32_t K, uint32_t* flags)
 int mlhip_em_route(const mlhip_data* data, uint32_t K, int covariance_type, mlhip_em_route_info* out)
 {
     return guarded([&] {
-        require(data && out && K >= 1 && (covariance_type == 0 || covariance_type == 1), "bad argument");
+        // (the fields describe the full and the diagonal route; the tied one is mlhip_em_tied_route's)
+        require(data && out && K >= 1 && (covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL), "bad argument");
         if (!data->parts.empty()) data = data->parts[0];
-        const bool diag = covariance_type == 1;
-        const EmRoute r = em_route(data, (int)K, diag);
+        const EmRoute r = em_route(data, (int)K, (Covariance)covariance_type);
         out->estep = r.estep == Estep::kScalarFed ? MLHIP_ESTEP_SCALAR_FED : r.estep == Estep::kMatrix4 ? MLHIP_ESTEP_MATRIX4
                    : r.estep == Estep::kBigDim ? MLHIP_ESTEP_BIG_DIM : MLHIP_ESTEP_PLAIN;
         out->fused = r.fused;

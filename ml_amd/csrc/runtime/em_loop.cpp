@@ -22,7 +22,7 @@ struct EmLoop {
     mlhip_ctx* ctx;
     const EmRoute& route;
     const int K, d;
-    const bool diag;
+    const bool diag;                            // diagonal covariances (a tied loop never gets here: em_iterate)
     double *mixing, *means, *covs;              // the caller's arrays (start -> result)
     // ---- plan of an iteration
     bool fused = false, self_norm = false;
@@ -37,8 +37,8 @@ struct EmLoop {
     std::vector<double> shadow[3];              // diagonal mode: host copy of P_i (ensure_lw rebuilds the block from an E-step's inputs)
     uint32_t launched = 0;                      // iterations launched so far
 
-    EmLoop(mlhip_data* dt, const EmRoute& r, int K_, bool diag_, double* mixing_, double* means_, double* covs_)
-        : data(dt), ctx(dt->ctx), route(r), K(K_), d(dt->d), diag(diag_), mixing(mixing_), means(means_), covs(covs_) {}
+    EmLoop(mlhip_data* dt, const ModeRoute& r, int K_, double* mixing_, double* means_, double* covs_)
+        : data(dt), ctx(dt->ctx), route(r.em), K(K_), d(dt->d), diag(r.mode == Covariance::Diagonal), mixing(mixing_), means(means_), covs(covs_) {}
 
     // The closing kernel writes its info block into pinned host memory (it_info_slot); in diagonal mode the whole (small) pack lives there.
     double* pack_base(int slot) const { return diag ? data->it_info_slot[slot].as<double>() : data->it_pack[slot].as<double>(); }
@@ -56,7 +56,7 @@ struct EmLoop {
         if (!diag) {
             prepare_estep(data, route, K, mixing, means, covs);    // -> params_dev and its descriptor
         }
-        n_cov = diag ? (size_t)K * d : (size_t)K * d * d;
+        n_cov = covariance_doubles(diag ? Covariance::Diagonal : Covariance::Full, K, d);
         F = diag ? diag_stats_count(d) : stats_count(d);
         n_info = em_close_info_doubles(K);
         n_pack = n_info + K + (size_t)K * d + n_cov;
@@ -281,7 +281,7 @@ struct EmLoop {
         if (launched > last + 1) data->estep.block_overwritten();
         if (diag) {
             const double* sh = shadow[last % 3].data();
-            data->estep.diag_parameters(K, d, sh, sh + K, sh + K + (size_t)K * d);
+            data->estep.parameters(Covariance::Diagonal, K, d, sh, sh + K, sh + K + (size_t)K * d);
         }
     }
 
@@ -354,40 +354,29 @@ struct EmLoop {
     }
 };
 
-/// No device closing on the route (d > 1024, MLHIP_DEVICE_CLOSE=0): the loop over the per-step functions.
-/// `tied`: a tied-covariance loop (covs: d*d doubles) on that route -- tied iterations are never closed on the device.
-void host_closing_loop(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mixing, double* means, double* covs,
-                       uint32_t max_steps, ConvergenceTest& test, const TiedRoute* tied = nullptr)
+/// No device closing: tied covariances (never closed on the device), d > 1024, MLHIP_DEVICE_CLOSE=0. The loop over em_step.
+void host_closing_loop(mlhip_data* data, const ModeRoute& r, int K, double* mixing, double* means, double* covs, uint32_t max_steps,
+                       ConvergenceTest& test)
 {
     for (uint32_t step = 0; step < max_steps; ++step) {
         double ll = 0;
-        if (tied) em_step_tied(data, *tied, K, mixing, means, covs, &ll, mixing, means, covs);
-        else if (diag) em_step_diag(data, r, K, mixing, means, covs, &ll, mixing, means, covs);
-        else em_step_full(data, r, K, mixing, means, covs, &ll, mixing, means, covs);
+        em_step(data, r, K, mixing, means, covs, &ll, mixing, means, covs);
         if (test(step, ll)) break;
     }
 }
 
 }  // namespace
 
-void em_iterate_tied(mlhip_data* data, const TiedRoute& r, int K, double* mixing, double* means, double* cov, uint32_t max_steps, double atol,
-                     double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history)
+void em_iterate(mlhip_data* data, Covariance mode, int K, double* mixing, double* means, double* covs, uint32_t max_steps, double atol,
+                double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history)
 {
+    const ModeRoute r = mode_route(data, K, mode);
     *steps_done = 0;
     *converged = 0;
     ConvergenceTest test{atol, rtol, steps_done, converged, log_likelihood, history};
-    host_closing_loop(data, r.em, K, false, mixing, means, cov, max_steps, test, &r);
-}
-
-void em_iterate(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps,
-                double atol, double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history)
-{
-    *steps_done = 0;
-    *converged = 0;
-    ConvergenceTest test{atol, rtol, steps_done, converged, log_likelihood, history};
-    EmLoop loop(data, r, K, diag, mixing, means, covs);
-    if (!loop.prepare()) {
-        host_closing_loop(data, r, K, diag, mixing, means, covs, max_steps, test);
+    EmLoop loop(data, r, K, mixing, means, covs);
+    if (mode == Covariance::Tied || !loop.prepare()) {
+        host_closing_loop(data, r, K, mixing, means, covs, max_steps, test);
         return;
     }
     uint32_t first = 0;

@@ -84,7 +84,8 @@ struct BestState {
 /// One solo loop on the handle: restart r of the caller's arrays.
 struct SoloRun {
     mlhip_data* data;
-    int K, covariance_type;
+    int K;
+    Covariance mode;
     size_t kd, n_cov;
     double *mixing, *means, *covs;
     uint32_t max_steps;
@@ -99,13 +100,7 @@ struct SoloRun {
         double* mu = means + (size_t)r * kd;
         double* cv = covs + (size_t)r * n_cov;
         double* hist = history ? history + (size_t)r * max_steps : nullptr;
-        if (covariance_type == MLHIP_COVARIANCE_TIED)
-            em_iterate_tied(data, tied_route(data, K), K, pi, mu, cv, max_steps, atol, rtol, steps_done + r, converged + r, log_likelihood + r, hist);
-        else {
-            const bool diag = covariance_type == MLHIP_COVARIANCE_DIAGONAL;
-            em_iterate(data, em_route(data, K, diag), K, diag, pi, mu, cv, max_steps, atol, rtol, steps_done + r, converged + r,
-                       log_likelihood + r, hist);
-        }
+        em_iterate(data, mode, K, pi, mu, cv, max_steps, atol, rtol, steps_done + r, converged + r, log_likelihood + r, hist);
         data->ctx->check_ranks_agree("the EM parameters", {{pi, (size_t)K}, {mu, kd}, {cv, n_cov}, {log_likelihood + r, 1}});
     }
 };
@@ -236,7 +231,7 @@ void em_iterate_restarts_batched(mlhip_data* data, const RestartsRoute& route, i
 
     // flagged restarts: the solo loop from their (untouched) starts, results and history written anew
     for (uint32_t r : solo_runs) { steps_done[r] = 0; converged[r] = 0; }
-    const SoloRun solo{data, K, MLHIP_COVARIANCE_FULL, kd, n_cov, mixing, means, covs, max_steps, atol, rtol, steps_done, converged,
+    const SoloRun solo{data, K, Covariance::Full, kd, n_cov, mixing, means, covs, max_steps, atol, rtol, steps_done, converged,
                        log_likelihood, history};
     run_sequential(solo, solo_runs, state, have_best, best);
     state.put_back();
@@ -259,16 +254,14 @@ int mlhip_em_restarts_route(const mlhip_data* data, uint32_t K, int covariance_t
 {
     return guarded([&] {
         require(data && route && per_launch && K >= 1 && R >= 1, "bad argument");
-        require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL ||
-                    covariance_type == MLHIP_COVARIANCE_TIED,
-                "bad covariance_type");
+        const Covariance mode = covariance_from_abi(covariance_type);
         static_assert(kRestartsSequential == MLHIP_RESTARTS_SEQUENTIAL && kRestartsBatched == MLHIP_RESTARTS_BATCHED,
                       "mlhip.h names the routes by RestartsKind");
         static_assert(mstats::kRestartsMaxBatch == MLHIP_RESTARTS_MAX_BATCH, "mlhip.h states the cap of one launch");
         *route = MLHIP_RESTARTS_SEQUENTIAL;
         *per_launch = 1;
         if (!data->parts.empty()) return;                       // a group's block: its shards are ranks of an all-reduce
-        const RestartsRoute r = restarts_route(data, (int)K, covariance_type, R);
+        const RestartsRoute r = restarts_route(data, (int)K, mode, R);
         *route = r.kind;
         *per_launch = (uint32_t)r.per_launch;
     });
@@ -281,14 +274,11 @@ int mlhip_em_iterate_restarts(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int 
     return guarded([&] {
         check_call(ctx, data, K);
         require(mixing && means && covariances && steps_done && converged && log_likelihood && best, "null argument");
-        require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL ||
-                    covariance_type == MLHIP_COVARIANCE_TIED,
-                "bad covariance_type");
+        const Covariance mode = covariance_from_abi(covariance_type);
         require(R >= 1, "at least one restart required");
         require(max_steps >= 1, "at least one step required");
         if (absolute_tolerance < 0 || relative_tolerance < 0) throw DomainError("negative tolerance");
-        const bool diag = covariance_type == MLHIP_COVARIANCE_DIAGONAL, tied = covariance_type == MLHIP_COVARIANCE_TIED;
-        const size_t kd = (size_t)K * data->d, n_cov = tied ? (size_t)data->d * data->d : kd * (diag ? 1 : data->d);
+        const size_t kd = (size_t)K * data->d, n_cov = covariance_doubles(mode, (int)K, data->d);
         if (ctx->group) {
             // the parameters are in/out, as in mlhip_em_iterate: shard 0 updates the caller's, the others copies of their own; every
             // shard sees the same all-reduced log-likelihoods and selects the same restart
@@ -303,13 +293,13 @@ int mlhip_em_iterate_restarts(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int 
             });
             return;
         }
-        const RestartsRoute route = restarts_route(data, (int)K, covariance_type, R);
+        const RestartsRoute route = restarts_route(data, (int)K, mode, R);
         if (route.kind == kRestartsBatched) {
             em_iterate_restarts_batched(data, route, (int)K, R, mixing, means, covariances, max_steps, absolute_tolerance, relative_tolerance,
                                         steps_done, converged, log_likelihood, log_likelihood_history, best);
             return;
         }
-        const SoloRun solo{data, (int)K, covariance_type, kd, n_cov, mixing, means, covariances, max_steps, absolute_tolerance,
+        const SoloRun solo{data, (int)K, mode, kd, n_cov, mixing, means, covariances, max_steps, absolute_tolerance,
                            relative_tolerance, steps_done, converged, log_likelihood, log_likelihood_history};
         std::vector<uint32_t> runs(R);
         for (uint32_t r = 0; r < R; ++r) runs[r] = r;

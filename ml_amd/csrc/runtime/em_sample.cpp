@@ -16,16 +16,14 @@ struct SampleModel {
     std::vector<double> table, thresholds;
 };
 
-/// The argument errors of both sampling calls that need no device (mlhip.h).
-void check_sample_arguments(const mlhip_ctx* ctx, uint32_t d, uint32_t K, int covariance_type, const double* mixing, const double* means,
+/// The argument errors of both sampling calls that need no device (mlhip.h); returns the covariance mode.
+Covariance check_sample_arguments(const mlhip_ctx* ctx, uint32_t d, uint32_t K, int covariance_type, const double* mixing, const double* means,
                             const double* covs, uint64_t first_row, uint64_t n)
 {
     require(ctx && mixing && means && covs, "null argument");
     require(K >= 1, "At least one component required");
     require(d >= 1 && d <= (uint32_t)kGenericMaxDim, "the dimension must be 1 .. 4096");
-    require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL ||
-                covariance_type == MLHIP_COVARIANCE_TIED,
-            "bad covariance_type");
+    const Covariance mode = covariance_from_abi(covariance_type);
     double total = 0;
     for (uint32_t k = 0; k < K; ++k) {
         require(std::isfinite(mixing[k]) && mixing[k] >= 0, "mixing weights must be finite and >= 0");
@@ -34,6 +32,7 @@ void check_sample_arguments(const mlhip_ctx* ctx, uint32_t d, uint32_t K, int co
     require(total > 0 && std::isfinite(total), "the mixing weights' total must be positive and finite");
     for (size_t i = 0; i < (size_t)K * d; ++i) require(std::isfinite(means[i]), "means must be finite");
     require(first_row + n >= first_row, "first_row + n must fit 64 bits");
+    return mode;
 }
 
 /// Packs the lower triangle of the column-major factor L row by row; DomainError unless it is a Cholesky factor (finite, positive
@@ -49,17 +48,17 @@ void pack_factor(int d, const double* L, double* packed)
     }
 }
 
-SampleModel build_model(uint32_t d_, uint32_t K, int covariance_type, const double* mixing, const double* means, const double* covs)
+SampleModel build_model(uint32_t d_, uint32_t K, Covariance mode, const double* mixing, const double* means, const double* covs)
 {
     SampleModel m;
     const int d = (int)d_;
     m.d = d;
     m.K = K;
     const size_t tl = (size_t)d * (d + 1) / 2, dd = (size_t)d * d;
-    const size_t factors = covariance_type == MLHIP_COVARIANCE_TIED ? 1 : K;
-    m.l_stride = covariance_type == MLHIP_COVARIANCE_TIED ? 0 : tl;
+    const size_t factors = mode == Covariance::Tied ? 1 : K;
+    m.l_stride = mode == Covariance::Tied ? 0 : tl;
     m.table.assign(factors * tl + (size_t)K * d, 0.0);
-    if (covariance_type == MLHIP_COVARIANCE_DIAGONAL) {
+    if (mode == Covariance::Diagonal) {
         // L = sqrt(variance): the factor host::cholesky_lower gives for the same variances as a diagonal matrix, bit for bit
         for (uint32_t k = 0; k < K; ++k)
             for (int j = 0; j < d; ++j) {
@@ -168,11 +167,11 @@ int mlhip_em_sample(mlhip_ctx* ctx, uint32_t d, uint32_t K, int covariance_type,
                     const double* covariances, uint64_t seed, uint64_t first_row, uint64_t n, double* x, int64_t ld, uint32_t* labels)
 {
     return guarded([&] {
-        check_sample_arguments(ctx, d, K, covariance_type, mixing, means, covariances, first_row, n);
+        const Covariance mode = check_sample_arguments(ctx, d, K, covariance_type, mixing, means, covariances, first_row, n);
         require(x || labels, "null argument: neither x nor labels");
         require(!x || ld >= (int64_t)d, "ld must be >= d");
         if (!n) return;
-        const SampleModel m = build_model(d, K, covariance_type, mixing, means, covariances);
+        const SampleModel m = build_model(d, K, mode, mixing, means, covariances);
         if (ctx->group) {
             // (every shard draws its rows of the balanced split on its own GPU: no collective, nothing to put together but the rows'
             // places in the caller's arrays)
@@ -194,11 +193,11 @@ int mlhip_em_sample_data(mlhip_ctx* ctx, uint32_t d, uint32_t K, int covariance_
 {
     return guarded([&] {
         require(out, "null argument");
-        check_sample_arguments(ctx, d, K, covariance_type, mixing, means, covariances, first_row, n);
+        const Covariance mode = check_sample_arguments(ctx, d, K, covariance_type, mixing, means, covariances, first_row, n);
         int shards = 1;
         if (ctx->group) check_status(mlhip_ctx_shards(ctx, &shards));
         require((n + (uint64_t)shards - 1) / (uint64_t)shards < kMaxBlockRows, "shard too large (n must fit 32 bits, like the reference's unsigned int)");
-        const SampleModel m = build_model(d, K, covariance_type, mixing, means, covariances);
+        const SampleModel m = build_model(d, K, mode, mixing, means, covariances);
         if (ctx->group) {
             *out = grp::upload_parts(ctx, d, n, [&](mlhip_ctx* shard, uint64_t lo, uint64_t rows) {
                 return em_sample_block(shard, m, seed, first_row + lo, rows, labels ? labels + lo : nullptr);

@@ -41,7 +41,7 @@ void score_composed(mlhip_data* dt, const ScoreRoute& r, int K, const DevBuf& re
     ctx->sync();                                         // (the scratch goes back to the pool behind the last kernel)
 }
 
-void em_score(mlhip_data* dt, int K, int covariance_type, const double* mixing, const double* means, const double* covs, double* log_density,
+void em_score(mlhip_data* dt, int K, Covariance mode, const double* mixing, const double* means, const double* covs, double* log_density,
               uint32_t* labels)
 {
     mlhip_ctx* ctx = dt->ctx;
@@ -49,19 +49,12 @@ void em_score(mlhip_data* dt, int K, int covariance_type, const double* mixing, 
     const ScoreRoute r = score_route(dt, K);
     const int d = dt->d;
     std::vector<double> full;
-    if (covariance_type == MLHIP_COVARIANCE_TIED) {
-        // the same kernels on K components that all carry the one covariance; no kernel of its own. The record builders work per
-        // component, so the one matrix is factored K times: K - 1 wasted factorizations, microseconds at d <= 32 but K d^3 / 3 flop
-        // each at large d (on the device above d = 64) -- records derived from one factorization are not built
-        const size_t dd = (size_t)d * d;
-        full.resize((size_t)K * dd);
-        for (int k = 0; k < K; ++k) std::copy(covs, covs + dd, full.begin() + (size_t)k * dd);
-        covs = full.data();
-    } else if (covariance_type == MLHIP_COVARIANCE_DIAGONAL) {
-        // the same kernels on diagonal matrices, as ensure_lw (em.cpp) does after a diagonal step
-        full.assign((size_t)K * d * d, 0.0);
-        for (int k = 0; k < K; ++k)
-            for (int j = 0; j < d; ++j) full[((size_t)k * d + j) * d + j] = covs[(size_t)k * d + j];
+    if (mode != Covariance::Full) {
+        // The same kernels on diagonal matrices, as ensure_lw (em.cpp) does after a diagonal step, or on K components that all carry
+        // the one tied covariance; no kernels of their own. The record builders work per component, so the tied matrix is factored K
+        // times: K - 1 wasted factorizations, microseconds at d <= 32 but K d^3 / 3 flop each at large d (on the device above d = 64)
+        // -- records derived from one factorization are not built
+        full = as_full(mode, K, d, covs);
         covs = full.data();
     }
     DevBuf records{&dt->pool}, work{&dt->pool}, lse_dev{&dt->pool}, labels_dev{&dt->pool};
@@ -104,9 +97,7 @@ int mlhip_em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_
     return guarded([&] {
         check_call(ctx, data, K);
         require(mixing && means && covariances, "null argument");
-        require(covariance_type == MLHIP_COVARIANCE_FULL || covariance_type == MLHIP_COVARIANCE_DIAGONAL ||
-                    covariance_type == MLHIP_COVARIANCE_TIED,
-                "bad covariance_type");
+        const Covariance mode = covariance_from_abi(covariance_type);
         if (ctx->group) {
             // (every shard scores its own rows: no collective, nothing to put together but the rows' places in the caller's arrays)
             fan_out(ctx, data, [&](Shard& sh) {
@@ -114,7 +105,7 @@ int mlhip_em_score(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, int covariance_
             });
             return;
         }
-        em_score(data, (int)K, covariance_type, mixing, means, covariances, log_density, labels);
+        em_score(data, (int)K, mode, mixing, means, covariances, log_density, labels);
     });
 }
 

@@ -44,6 +44,15 @@ struct NoDevice : std::runtime_error { using std::runtime_error::runtime_error; 
 struct Unsupported : std::runtime_error { using std::runtime_error::runtime_error; };
 struct DomainError : std::runtime_error { using std::runtime_error::runtime_error; };
 
+/// The covariance mode of an EM call (host/em_math.hpp). host::covariance_from_abi decodes the ABI's `covariance_type` -- the one place
+/// that refuses a bad one; `guarded` reports its std::invalid_argument as MLHIP_E_INVALID_ARGUMENT.
+using mlhip::host::Covariance;
+using mlhip::host::covariance_doubles;
+using mlhip::host::covariance_from_abi;
+static_assert((int)Covariance::Full == MLHIP_COVARIANCE_FULL && (int)Covariance::Diagonal == MLHIP_COVARIANCE_DIAGONAL &&
+                  (int)Covariance::Tied == MLHIP_COVARIANCE_TIED,
+              "mlhip.h names the covariance types by Covariance");
+
 #define HIP_CHECK(expr)                                                                                   \
     do {                                                                                                  \
         hipError_t e_ = (expr);                                                                           \
@@ -63,6 +72,7 @@ template <class F> int guarded(F&& f)
     g_error.clear();                   // (mlhip_last_error speaks of the LAST call; hook_failure reads what a hook left during this one)
     try { f(); return MLHIP_OK; }
     catch (const InvalidArgument& e) { g_error = e.what(); return MLHIP_E_INVALID_ARGUMENT; }
+    catch (const std::invalid_argument& e) { g_error = e.what(); return MLHIP_E_INVALID_ARGUMENT; }
     catch (const DomainError& e) { g_error = e.what(); return MLHIP_E_DOMAIN; }
     catch (const NoDevice& e) { g_error = e.what(); return MLHIP_E_NO_DEVICE; }
     catch (const Unsupported& e) { g_error = e.what(); return MLHIP_E_UNSUPPORTED; }
@@ -415,11 +425,11 @@ struct mlhip_ctx {
 ///   kBlock       -- lw (and lse, once the E-step or the self-normalising statistics pass wrote it);
 ///   kRecords     -- lse and the full-covariance records in params_dev (after a fused step, the resident loop, a lagged loop that
 ///                   ran one iteration ahead): ensure_lw reruns the E-step kernel on the same records;
-///   kDiagRecords -- lse, diagonal records in params_dev and the parameters' host copy: ensure_lw expands them to full covariances.
-///   kTiedRecords -- the same after a tied-covariance kernel step: ensure_lw replicates the one covariance K times.
+///   kModeRecords -- lse, the records of a diagonal or tied one-kernel pass in params_dev and the parameters' host copy in their
+///                   mode's form (kept): ensure_lw expands them to full covariances (host::covariances_as_full).
 /// Only the members below assign the fields.
 struct EstepState {
-    enum What { kNone, kBlock, kRecords, kDiagRecords, kTiedRecords };
+    enum What { kNone, kBlock, kRecords, kModeRecords };
     What what = kNone;
     int rec_layout = 0;           // record layout currently in params_dev: 0 = valu, 2 = mfma4 (CloseArgs::layout codes)
     bool rec_fold = false;        // mfma4 records in FOLD form (vector slot = -W (mu - shift)): layout.hpp kEstepFoldLimit
@@ -428,10 +438,11 @@ struct EstepState {
     int stats_mode = 0;
     const double* stats_resp = nullptr;
     size_t stats_ld = 0;
-    // kDiagRecords / kTiedRecords: the parameters of that pass (the N x K block is rebuilt from them on demand)
+    // kModeRecords: the mode and the parameters of that pass (the N x K block is rebuilt from them on demand)
     struct Kept {
+        Covariance mode = Covariance::Full;
         std::vector<double> mixing, means;                    // [K], [K][d]
-        std::vector<double> covariance;                       // diagonal: the K x d variances; tied: the one d x d covariance
+        std::vector<double> covariance;                       // covariance_doubles(mode, K, d): the K x d variances / the one d x d covariance
     } kept;
 
     void invalidate() { what = kNone; }
@@ -439,19 +450,17 @@ struct EstepState {
     /// A weighted block: the E-step's log-likelihood partials were replaced by `grid` partials of w_i lse_i (launch_estep).
     void ll_weighted(int grid) { n_ll = grid; }
     void records_only(int grid) { what = kRecords; n_ll = grid; }
-    void diag_records_only(int grid) { what = kDiagRecords; n_ll = grid; }
-    void tied_records_only(int grid) { what = kTiedRecords; n_ll = grid; }
+    /// A one-kernel pass of `mode` (diagonal, tied) left its records and `grid` log-likelihood partials.
+    void mode_records_only(Covariance mode, int grid) { what = kModeRecords; kept.mode = mode; n_ll = grid; }
     /// A later (speculative) pass overwrote lw / lse; the records in params_dev still stand.
     void block_overwritten() { if (what == kBlock) what = kRecords; }
-    /// The parameters behind the diagonal records in params_dev (mlhip_em_iterate: set once, when the loop is over).
-    void diag_parameters(int K, int d, const double* mixing, const double* means, const double* vars)
+    /// The parameters behind the records of `mode` in params_dev (mlhip_em_iterate: set once, when the loop is over).
+    void parameters(Covariance mode, int K, int d, const double* mixing, const double* means, const double* covariance)
     {
-        keep(K, d, mixing, means, vars, (size_t)K * d);
-    }
-    /// The parameters behind the tied records in params_dev.
-    void tied_parameters(int K, int d, const double* mixing, const double* means, const double* cov)
-    {
-        keep(K, d, mixing, means, cov, (size_t)d * d);
+        kept.mode = mode;
+        kept.mixing.assign(mixing, mixing + K);
+        kept.means.assign(means, means + (size_t)K * d);
+        kept.covariance.assign(covariance, covariance + covariance_doubles(mode, K, d));
     }
     void records_are(int layout, bool fold) { rec_layout = layout; rec_fold = fold; }
     void stats_from(int mode, const double* resp, size_t ld) { stats_mode = mode; stats_resp = resp; stats_ld = ld; }
@@ -471,17 +480,8 @@ struct EstepState {
     void put_back(const Small& s) { what = s.what; rec_layout = s.rec_layout; rec_fold = s.rec_fold; n_ll = s.n_ll; kept = s.kept; }
 
     bool on_device() const { return what != kNone; }
-    bool needs_rebuild() const { return what == kRecords || what == kDiagRecords || what == kTiedRecords; }
-    bool diagonal() const { return what == kDiagRecords; }
-    bool tied() const { return what == kTiedRecords; }
-
-private:
-    void keep(int K, int d, const double* mixing, const double* means, const double* covariance, size_t covariance_doubles)
-    {
-        kept.mixing.assign(mixing, mixing + K);
-        kept.means.assign(means, means + (size_t)K * d);
-        kept.covariance.assign(covariance, covariance + covariance_doubles);
-    }
+    bool needs_rebuild() const { return what == kRecords || what == kModeRecords; }
+    bool mode_records() const { return what == kModeRecords; }
 };
 
 struct mlhip_data {
@@ -627,18 +627,21 @@ struct EmRoute {
     /// MstatsArgs::plain: the plain tier above d = 128, whole column blocks per wave at d <= 32.
     int stats_plain(int d) const { return d > kMaxDim ? estep == Estep::kPlain : !balanced; }
 };
-/// `diag`: the call runs the diagonal-covariance kernel where it exists (em_diag.hip), else the full-covariance kernels.
-EmRoute em_route(const mlhip_data* data, int K, bool diag);
+/// The kernels of K components on this block. Diagonal: the diagonal-covariance kernel where it exists (em_diag.hip), else the
+/// full-covariance kernels. Tied: the full-covariance kernels of the composed step, the matrix-core E-step never in its FOLD form.
+EmRoute em_route(const mlhip_data* data, int K, Covariance mode);
 
-/// A tied-covariance step (mlhip_em_step_tied): the one-kernel iteration (em_tied.hip: unweighted blocks, d <= 32, K <= 64, unless
-/// MLHIP_TIED=composed or the composed step was measured faster: route.cpp) or COMPOSED -- one full-covariance step on `em`, the route of K full components on this block, with the
-/// covariance replicated and the result pooled. (mlhip.h names the routes by these values.)
+/// A tied-covariance step: the one-kernel iteration (em_tied.hip: unweighted blocks, d <= 32, K <= 64, unless MLHIP_TIED=composed or
+/// the composed step was measured faster: route.cpp) or COMPOSED -- one full-covariance step on the route of K full components on
+/// this block, with the covariance replicated and the result pooled. (mlhip.h names the routes by these values.)
 enum TiedKernel : int { kTiedComposed = 0, kTiedKernel = 1 };
-struct TiedRoute {
-    int kernel = kTiedComposed;
-    EmRoute em;                        // full-covariance route: the composed step, and the E-step kernel that rebuilds the N x K block
+/// The route of one EM step or loop in a covariance mode: what em_step and em_iterate dispatch on.
+struct ModeRoute {
+    Covariance mode = Covariance::Full;
+    EmRoute em;                        // em_route(data, K, mode)
+    int tied_kernel = kTiedComposed;   // Tied only
 };
-TiedRoute tied_route(const mlhip_data* data, int K);
+ModeRoute mode_route(const mlhip_data* data, int K, Covariance mode);
 
 /// mlhip_em_score: the scalar-fed score kernel (em_score.hip) and the matrix-core E-step's SCORE form (em_estep_mfma4.hip) where the
 /// E-step's route is scalar-fed / matrix-core; composed -- the E-step kernel on row chunks into a bounded scratch block, then
@@ -683,7 +686,7 @@ struct RestartsRoute {
 };
 /// Doubles of device memory one restart of the batched route needs (two record slots, a pack, partial blocks, statistics).
 size_t restarts_doubles_per_restart(int d, int K, int grid);
-RestartsRoute restarts_route(const mlhip_data* data, int K, int covariance_type, uint32_t R);
+RestartsRoute restarts_route(const mlhip_data* data, int K, Covariance mode, uint32_t R);
 
 struct KmRoute {
     bool pad = false;                  // the block runs on a copy zero-padded to a multiple of 4 dimensions (km_xt_pad)
@@ -828,6 +831,9 @@ void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, 
 
 bool mstats_sparse_applies(mlhip_data* dt, const EmRoute& r, int K);
 
+/// The covariance array of `mode` as K full covariance matrices (host::covariances_as_full).
+std::vector<double> as_full(Covariance mode, int K, int d, const double* covariance);
+
 /// One full-covariance EM iteration with the closing arithmetic on the HOST (the body of mlhip_em_step).
 void em_step_full(mlhip_data* data, const EmRoute& r, int K, const double* mixing, const double* means, const double* covariances,
                   double* log_likelihood, double* mixing_out, double* means_out, double* covariances_out);
@@ -848,8 +854,13 @@ void em_step_diag(mlhip_data* data, const EmRoute& r, int K, const double* mixin
 void run_total_scatter(mlhip_data* data);
 
 /// One tied-covariance EM iteration (the body of mlhip_em_step_tied): cov / cov_out hold d*d doubles.
-void em_step_tied(mlhip_data* data, const TiedRoute& r, int K, const double* mixing, const double* means, const double* cov,
+void em_step_tied(mlhip_data* data, const ModeRoute& r, int K, const double* mixing, const double* means, const double* cov,
                   double* log_likelihood, double* mixing_out, double* means_out, double* cov_out);
+
+/// One EM iteration in the mode of `r` with the closing arithmetic on the host: em_step_full, em_step_diag or em_step_tied. The
+/// covariance arrays hold covariance_doubles(r.mode, K, d) doubles.
+void em_step(mlhip_data* data, const ModeRoute& r, int K, const double* mixing, const double* means, const double* covs,
+             double* log_likelihood, double* mixing_out, double* means_out, double* covs_out);
 
 /// ML/EM.cpp:161-168: from the second trip on, |ll - ll_old| < atol + rtol max(|ll_old|, |ll|) stops the loop.
 struct ConvergenceTest {
@@ -877,12 +888,10 @@ struct ConvergenceTest {
 /// statistics, all-reduce, closing arithmetic + next records (em_close.hip); per iteration the host reads back 1 + 2K doubles (log-
 /// likelihood sum, refinement flags, FOLD criterion) and decides. A flagged component (far, tight cluster) sends that one
 /// iteration through the host closing with its refinement pass, exactly as mlhip_em_step would. Without device closing
-/// (r.device_close) the whole loop runs through the per-step functions.
-void em_iterate(mlhip_data* data, const EmRoute& r, int K, bool diag, double* mixing, double* means, double* covs, uint32_t max_steps, double atol,
+/// (the route's device_close; tied covariances always) the whole loop runs through em_step. Resolves mode_route(data, K, mode) itself;
+/// covs: covariance_doubles(mode, K, d) doubles.
+void em_iterate(mlhip_data* data, Covariance mode, int K, double* mixing, double* means, double* covs, uint32_t max_steps, double atol,
                 double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history);
-/// The same loop for a tied covariance (covs: d*d doubles): one em_step_tied per trip, closing on the host.
-void em_iterate_tied(mlhip_data* data, const TiedRoute& r, int K, double* mixing, double* means, double* cov, uint32_t max_steps, double atol,
-                     double rtol, uint32_t* steps_done, int* converged, double* log_likelihood, double* history);
 
 /// The batched loop of mlhip_em_iterate_restarts (em_restarts.cpp): restarts [0, R) of full-covariance EM on a single rank's block;
 /// arrays as in mlhip.h. Restarts it could not finish itself (a refinement flag) are run through em_iterate from their starts.

@@ -82,8 +82,9 @@ SampleRoute sample_route(int d, uint32_t K)
     return r;
 }
 
-EmRoute em_route(const mlhip_data* data, int K, bool diag)
+EmRoute em_route(const mlhip_data* data, int K, Covariance mode)
 {
+    const bool diag = mode == Covariance::Diagonal;
     const Switches sw = read_switches();
     const mlhip_ctx* ctx = data->ctx;
     const int d = data->d, D = data->D;
@@ -119,6 +120,10 @@ EmRoute em_route(const mlhip_data* data, int K, bool diag)
     r.device_close = sw.device_close && em_close_supported(d) && (!diag || diag_kernel);
     // single rank, the vector-unit form (em_loop.cpp checks the grid)
     r.resident = sw.resident && r.fused && r.fused_form == kFusedValu && !ctx->reduce_fn && ctx->world_size <= 1;
+    // The composed route is the tied mode's accurate one (it is where the kernel's weighted, large and ill-conditioned cases go, and
+    // what the kernel is compared with): its matrix-core E-step takes the exact form, never FOLD, whose 1e-13 in a
+    // log-responsibility would be the route's largest error (tests/test_gpu_tied_hp.py, reach 0.9 x 64: 1.1e-14 against 1.9e-15).
+    if (mode == Covariance::Tied) r.fold_allowed = false;
     return r;
 }
 
@@ -126,7 +131,7 @@ ScoreRoute score_route(const mlhip_data* data, int K)
 {
     const Switches sw = read_switches();
     ScoreRoute r;
-    r.em = em_route(data, K, false);
+    r.em = em_route(data, K, Covariance::Full);
     if (sw.score_composed || r.em.estep == Estep::kBigDim || r.em.estep == Estep::kPlain) r.kernel = kScoreComposed;
     else r.kernel = r.em.estep == Estep::kMatrix4 ? kScoreMatrix4 : kScoreScalarFed;
     // the composed route's scratch: the largest whole number of sample tiles whose K x rows doubles stay within kScoreScratchBytes
@@ -138,15 +143,13 @@ ScoreRoute score_route(const mlhip_data* data, int K)
     return r;
 }
 
-TiedRoute tied_route(const mlhip_data* data, int K)
+ModeRoute mode_route(const mlhip_data* data, int K, Covariance mode)
 {
+    ModeRoute r;
+    r.mode = mode;
+    r.em = em_route(data, K, mode);
+    if (mode != Covariance::Tied) return r;
     const Switches sw = read_switches();
-    TiedRoute r;
-    r.em = em_route(data, K, false);
-    // The composed route is the tied mode's accurate one (it is where the kernel's weighted, large and ill-conditioned cases go, and
-    // what the kernel is compared with): its matrix-core E-step takes the exact form, never FOLD, whose 1e-13 in a
-    // log-responsibility would be the route's largest error (tests/test_gpu_tied_hp.py, reach 0.9 x 64: 1.1e-14 against 1.9e-15).
-    r.em.fold_allowed = false;
     // the kernel has no weighted form (like the diagonal one); every other shape, and MLHIP_TIED=composed, takes the composed route
     if (sw.tied == kTiedComposed || data->weighted || !mstats::em_tied_supported(data->d, K)) return r;
     // Measured (profiles/tied_timing.txt): where the full-covariance step is the fused kernel in its vector-unit form -- few components
@@ -154,7 +157,7 @@ TiedRoute tied_route(const mlhip_data* data, int K)
     // against 0.261 ms; the ONE shape of that form that was timed, the rule extends it to the others): those shapes stay composed
     // unless MLHIP_TIED=kernel asks for the kernel.
     const bool composed_faster = r.em.fused && r.em.fused_form == kFusedValu;
-    if (sw.tied == kTiedKernel || !composed_faster) r.kernel = kTiedKernel;
+    if (sw.tied == kTiedKernel || !composed_faster) r.tied_kernel = kTiedKernel;
     return r;
 }
 
@@ -165,15 +168,15 @@ size_t restarts_doubles_per_restart(int d, int K, int grid)
     return 2 * records + pack + (size_t)grid * (block + 1) + (size_t)K * stats_count(d) + 1;
 }
 
-RestartsRoute restarts_route(const mlhip_data* data, int K, int covariance_type, uint32_t R)
+RestartsRoute restarts_route(const mlhip_data* data, int K, Covariance mode, uint32_t R)
 {
     const Switches sw = read_switches();
     const mlhip_ctx* ctx = data->ctx;
     RestartsRoute r;
-    r.em = em_route(data, K, covariance_type == MLHIP_COVARIANCE_DIAGONAL);
+    r.em = em_route(data, K, mode);
     // Where the batch exists: the solo iteration is the vector-unit pass + reduction + device closing of ONE rank, and its grid is at
     // most one workgroup per CU (the partial-block scratch and the ll partials never cut such a grid: em_fused_small.hip).
-    if (covariance_type != MLHIP_COVARIANCE_FULL || data->weighted || ctx->reduce_fn || ctx->world_size > 1) return r;
+    if (mode != Covariance::Full || data->weighted || ctx->reduce_fn || ctx->world_size > 1) return r;
     if (!r.em.fused || r.em.fused_form != kFusedValu || !r.em.device_close) return r;
     FusedArgs fa{};
     fa.n = data->n; fa.d = data->d; fa.K = K; fa.form = r.em.fused_form;

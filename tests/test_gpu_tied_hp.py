@@ -201,7 +201,7 @@ def test_whitening_reach(ctx, monkeypatch, reach, route):
     """Two overlapping components 0.9, 1.1 and 10 x 64 whitened units from the shift (>= 500 rows with responsibilities strictly
     inside (0, 1)): the kernel has no guard on |L^-1 (mu_k - shift)| and no exact form, and is held to its own model at every reach.
 
-    The composed route takes the exact form of the full-covariance E-step at every reach (runtime/route.cpp, tied_route): with the
+    The composed route takes the exact form of the full-covariance E-step at every reach (runtime/route.cpp, em_route for the tied mode): with the
     FOLD form, which the full-covariance mode runs below 64, its responsibilities at reach 0.9 x 64 were 1.10e-14 against a limit of
     9.08e-15 = 4 err_cpu; the exact form gives 1.9e-15."""
     problem, refs = _reach_case(reach)

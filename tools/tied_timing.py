@@ -101,7 +101,7 @@ def main():
                       "kernel" if keeps else "composed: (a) < (b) fails"))
         print(lines[-1], flush=True)
     ctx.close()
-    lines.append("# Routing that follows (runtime/route.cpp tied_route): a shape where (a) < (b) fails takes the composed route by default;")
+    lines.append("# Routing that follows (runtime/route.cpp mode_route): a shape where (a) < (b) fails takes the composed route by default;")
     lines.append("# MLHIP_TIED=kernel still selects the kernel there.")
     for n, d, K, full_route in composed:
         lines.append("#   N=%d d=%d K=%d: composed (its full-covariance step is %s)" % (n, d, K, full_route))
