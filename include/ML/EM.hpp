@@ -143,6 +143,19 @@ public:
     @throw std::domain_error If a covariance is not positive definite.
     @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
     DLL_DECLSPEC MatrixXd sample(Index n, std::uint64_t seed = 0, std::vector<unsigned int>* labels = nullptr) const;
+    /** Extension (Gaussian-mixture regression, imputation): E[x_M | x_O] under the fitted mixture for every column of
+    `data_observed`, on the device. `observed`: distinct coordinates < means().rows() in any order, at least one and not all of them;
+    row c of `data_observed` holds coordinate observed[c] of every point. Returns (number of missing coordinates) x data.cols(): a
+    point in every column, the missing coordinates in ascending order. `log_densities`, if given, receives data.cols() values: the
+    log-density of every x_O under the marginal mixture. The definition and its fixed evaluation order: mlhip_em_condition,
+    mlhip_em_conditional_means. The result does not depend on the row batches (those of log_densities) or the device group it runs on;
+    the model is not changed.
+    @throw std::invalid_argument If the model has not been fitted, `observed` is empty, holds every coordinate, one that is out of
+    range or one twice, or `data_observed.rows() != observed.size()`.
+    @throw std::domain_error If the observed block of a covariance is not positive definite.
+    @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
+    DLL_DECLSPEC MatrixXd conditional_means(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed,
+                                            double* log_densities = nullptr) const;
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }
     /** Extension: number of E-M iterations the last fit() ran. */

@@ -392,6 +392,23 @@ public:
                                      labels ? reinterpret_cast<uint32_t*>(labels->data()) : nullptr));
         return out;
     }
+    /** Extension (ML/EM.hpp): E[x_M | x_O] under the fitted mixture for every column of `data_observed` (row c = coordinate
+    observed[c]); returns (number of missing coordinates) x data_observed.cols(), the missing coordinates ascending. `log_densities`,
+    if given, receives the log-density of every x_O under the marginal mixture.
+    @throw std::invalid_argument If the model has not been fitted, for bad coordinates or `data_observed.rows() != observed.size()`.
+    @throw std::domain_error If the observed block of a covariance is not positive definite. */
+    Eigen::MatrixXd conditional_means(const std::vector<unsigned int>& observed, Eigen::Ref<const Eigen::MatrixXd> data_observed,
+                                      double* log_densities = nullptr) const
+    {
+        if (data_observed.rows() != static_cast<Eigen::Index>(observed.size())) throw std::invalid_argument("Wrong data size");
+        const Eigen::Index missing = means_.rows() > data_observed.rows() ? means_.rows() - data_observed.rows() : 0;
+        const detail::Block block(data_observed);
+        Eigen::MatrixXd out(missing, data_observed.cols());
+        static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+        detail::check(mlpp_em_conditional_means(h_, reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(observed.size()),
+                                                block.p, static_cast<uint64_t>(data_observed.cols()), out.data(), log_densities));
+        return out;
+    }
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }
 

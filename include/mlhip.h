@@ -345,6 +345,45 @@ int mlhip_cholesky_lower(uint32_t d, const double* covariance, double* lower);
 enum { MLHIP_SAMPLE_LDS_TABLE = 0, MLHIP_SAMPLE_GLOBAL_TABLE = 1, MLHIP_SAMPLE_PLAIN = 2 };
 int mlhip_em_sample_route(uint32_t d, uint32_t K, int* kernel);
 
+/* EXTENSION (Gaussian-mixture regression / imputation; not in the reference surface): a mixture over (x_O, x_M) conditioned on the
+ * observed block. Host helper, no GPU needed. `observed`: n_observed distinct coordinates < d in any order, 1 <= n_observed <= d - 1
+ * (column c of an observed row holds coordinate observed[c]); the missing coordinates M are the complement in ascending order, dM =
+ * d - n_observed of them. means: K x d; covariances as in mlhip_em_score (diagonal and tied input count as the full matrices they
+ * stand for). Outputs, per component k:
+ *   means_observed       K x dO                  mu_k[O_c]
+ *   covariances_observed K x dO x dO, full       Sigma_k,OO
+ *   maps                 K x dM x dO, row-major  A_k = Sigma_k,MO Sigma_k,OO^-1, row j = missing coordinate j, computed as
+ *                                                A_k = (L^-T (L^-1 Sigma_k,OM))^T with L L^T = Sigma_k,OO (mlhip_cholesky_lower's factor)
+ *   means_missing        K x dM                  mu_k[M_j]
+ * Diagonal input gives maps of +0.0, tied input K maps with equal bits. MLHIP_E_DOMAIN when a Sigma_k,OO is not positive definite.
+ * MLHIP_E_INVALID_ARGUMENT, before any work: null pointers, K = 0, d = 0 or d > 4096, a bad covariance_type, n_observed = 0 or >= d,
+ * a coordinate >= d, a coordinate given twice. */
+int mlhip_em_condition(uint32_t d, uint32_t K, int covariance_type, const double* means, const double* covariances,
+                       const uint32_t* observed, uint32_t n_observed,
+                       double* means_observed, double* covariances_observed, double* maps, double* means_missing);
+/* E[x_M | x_O] for every row of `data`, a resident block of the OBSERVED coordinates (its d is dO), under the conditioned mixture
+ * mlhip_em_condition returns (mixing: the K weights of the joint model). With lw_k = log pi_k + log N(x_O | mu_k,O, Sigma_k,OO),
+ * lse = log sum_k exp lw_k and r_k = exp(lw_k - lse):   out_j = sum_k r_k (mu_k,M[j] + sum_c A_k[j][c] (x_c - mu_k,O[c])).
+ * The marginal mixture's E-step runs in its exact form on chunks of whole 256-row tiles (the kernels and the chunking of
+ * mlhip_em_score's composed route; MLHIP_CONDITION_ROWS=rows overrides the chunk, rounded up to whole tiles) and the conditioning
+ * kernel finishes each chunk in a fixed order: z_c = x_c - mu_k,O[c]; t_j = mu_k,M[j], t_j = fma(A_k[j][c], z_c, t_j) for ascending
+ * c; y_j = +0.0, y_j = fma(r_k, t_j, y_j) for ascending k over the components with r_k != 0. A row's output is a pure function of
+ * the row and the parameters: chunks, the row's place in the block and the shards of a device group (each conditions its own rows,
+ * no collective) change no bit. out: rows x dM, `ld_out` >= dM doubles apart, host memory. log_density (rows; may be NULL):
+ * lse - dO log(2 pi) / 2, the log-density of x_O under the marginal mixture -- the bits mlhip_em_score gives on its composed route.
+ * Row weights are ignored, as in scoring; nothing the handle holds is changed. n = 0 succeeds and writes nothing. */
+int mlhip_em_conditional_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t dM, const double* mixing,
+                               const double* means_observed, const double* covariances_observed, const double* maps,
+                               const double* means_missing, double* out, int64_t ld_out, double* log_density);
+/* Which conditioning kernel mlhip_em_conditional_means runs behind the E-step for dM missing coordinates on this block (diagnostic,
+ * nothing is launched), under the switches as they are set now. dO <= 32 and dM <= 32: lane = row, x_O and the dM accumulators in
+ * registers, the maps fed as scalar operands, the wave's 64 x dM tile staged through LDS into contiguous 16-byte stores
+ * (MLHIP_CONDITION_REGISTERS); else, up to dO + dM = 4096, and everywhere under MLHIP_CONDITION=plain: table and accumulators in
+ * global memory (MLHIP_CONDITION_PLAIN; same bits). MLHIP_CONDITION_SKIP=0 makes the kernels run the components that no row of a wave
+ * has a share in (same bits). */
+enum { MLHIP_CONDITION_REGISTERS = 0, MLHIP_CONDITION_PLAIN = 1 };
+int mlhip_em_condition_route(const mlhip_data* data, uint32_t K, uint32_t dM, int* kernel);
+
 /* (X - mean)(X - mean)^T / (N - 1) over ALL ranks' samples (EM::calculate_sample_covariance,
  * ML/EM.cpp:265-272). mean may be NULL. */
 int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance);

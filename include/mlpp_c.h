@@ -95,6 +95,12 @@ int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint
  * parameters (mlhip_em_sample). x_out: n x d row-major (a point in every row); labels_out (n, the components drawn) may be NULL.
  * n = 0 writes nothing. */
 int mlpp_em_sample(const mlpp_em* h, uint64_t n, uint64_t seed, double* x_out, uint32_t* labels_out);
+/* Extension: EM::conditional_means -- E[x_M | x_O] under the fitted mixture for n points (mlhip_em_condition,
+ * mlhip_em_conditional_means). observed: n_observed distinct coordinates; data_observed: n x n_observed row-major (column c =
+ * coordinate observed[c]); out: n x (d - n_observed) row-major, the missing coordinates ascending; log_density_out (n) may be NULL.
+ * n = 0 writes nothing. */
+int mlpp_em_conditional_means(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                              double* out, double* log_density_out);
 
 /* ---- KMeans (cppyml/clustering.cpp:148-183) ---- */
 int mlpp_kmeans_create(uint32_t number_clusters, mlpp_kmeans** out);

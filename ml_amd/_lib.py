@@ -561,6 +561,33 @@ class Data:
         check(lib.mlhip_em_score_route(self._h, C.c_uint32(K), C.byref(k)))
         return ("scalar_fed", "matrix4", "composed")[k.value]
 
+    def em_conditional_means(self, mixing, means_observed, covs_observed, maps, means_missing, log_density=False):
+        """E[x_M | x_O] for every row of this block of OBSERVED coordinates under the conditioned mixture em_condition returns
+        (mlhip_em_conditional_means): n x dM C-contiguous float64, and with log_density=True also the n log-densities of the rows
+        under the marginal mixture. means_observed: K x dO; covs_observed: K x dO x dO; maps: K x dM x dO; means_missing: K x dM.
+        Nothing the handle holds is changed."""
+        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
+        means_observed = np.ascontiguousarray(means_observed, dtype=np.float64)
+        covs_observed = np.ascontiguousarray(covs_observed, dtype=np.float64)
+        maps = np.ascontiguousarray(maps, dtype=np.float64)
+        means_missing = np.ascontiguousarray(means_missing, dtype=np.float64)
+        K, dM = means_missing.shape
+        assert mixing.shape == (K,) and means_observed.shape == (K, self.d) and covs_observed.shape == (K, self.d, self.d)
+        assert maps.shape == (K, dM, self.d)
+        out = np.empty((self.n, dM))
+        dens = np.empty(self.n) if log_density else None
+        check(lib.mlhip_em_conditional_means(self.ctx.handle, self._h, C.c_uint32(K), C.c_uint32(dM), dptr(mixing), dptr(means_observed),
+                                             dptr(covs_observed), dptr(maps), dptr(means_missing), dptr(out), C.c_int64(dM),
+                                             dptr(dens) if log_density else None))
+        return (out, dens) if log_density else out
+
+    def em_condition_route(self, K, dM):
+        """The conditioning kernel mlhip_em_conditional_means runs for dM missing coordinates on this block under the switches as they
+        are set now (mlhip_em_condition_route): 'registers' | 'plain'."""
+        k = C.c_int()
+        check(lib.mlhip_em_condition_route(self._h, C.c_uint32(K), C.c_uint32(dM), C.byref(k)))
+        return ("registers", "plain")[k.value]
+
     def em_expectation(self, mixing, means, covs):
         K = len(mixing)
         mixing = np.ascontiguousarray(mixing, dtype=np.float64)
@@ -716,6 +743,25 @@ def cholesky_lower(cov):
     L = np.empty((d, d), order="F")
     check(lib.mlhip_cholesky_lower(C.c_uint32(d), dptr(cov), dptr(L)))
     return np.ascontiguousarray(L)
+
+
+def em_condition(means, covs, observed, diagonal=False, tied=False):
+    """A mixture over (x_O, x_M) conditioned on the coordinates `observed` (mlhip_em_condition, no GPU): (means_observed K x dO,
+    covs_observed K x dO x dO, maps K x dM x dO, means_missing K x dM), the missing coordinates in ascending order. means: K x d;
+    covs: K x d x d (K x d variances with diagonal=True, the one d x d matrix with tied=True). ValueError for bad coordinates or an
+    observed block that is not positive definite."""
+    means = np.ascontiguousarray(means, dtype=np.float64)
+    covs = np.ascontiguousarray(covs, dtype=np.float64)
+    assert not (diagonal and tied) and means.ndim == 2
+    K, d = means.shape
+    assert covs.shape == ((d, d) if tied else (K, d) if diagonal else (K, d, d))
+    observed = np.ascontiguousarray(observed, dtype=np.uint32).ravel()
+    dO = len(observed)
+    dM = max(d - dO, 0)
+    mu_o, S_oo, A, mu_m = np.empty((K, dO)), np.empty((K, dO, dO)), np.empty((K, dM, dO)), np.empty((K, dM))
+    check(lib.mlhip_em_condition(C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(means), dptr(covs), u32ptr(observed),
+                                 C.c_uint32(dO), dptr(mu_o), dptr(S_oo), dptr(A), dptr(mu_m)))
+    return mu_o, S_oo, A, mu_m
 
 
 def em_sample_route(d, K):

@@ -7,7 +7,7 @@ Conventions kept from the reference:
   * `EM.means` is `d x K` (NOT transposed, clustering.cpp:126), `KMeans.centroids` is `K x d` (clustering.cpp:66-69,172);
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
-Extensions (not in the reference surface): `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
+Extensions (not in the reference surface): `EM.conditional_mean`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
 `KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`, `EM.set_number_initialisations`,
 `EM.number_initialisations`, `EM.best_initialisation`, `EM.initialisation_log_likelihoods`, `EM.initialisation_steps`,
@@ -387,6 +387,38 @@ class EM:
         X, labels = np.empty((n, d)), np.empty(n, dtype=np.uint32)
         _check(_l.mlpp_em_sample(self._h, C.c_uint64(n), C.c_uint64(int(seed)), _dp(X), _lib.u32ptr(labels)))
         return X, labels
+
+    def conditional_mean(self, X_observed, observed, return_log_density=False):
+        """Extension (Gaussian-mixture regression, imputation): E[x_M | x_O] under the fitted mixture for every row of X_observed, on
+        the GPU. `observed`: distinct coordinate indices in any order, at least one and not all of them; column c of X_observed
+        (N x len(observed), C-contiguous float64 like what `fit` takes) holds coordinate observed[c]. Returns an (N, d - len(observed))
+        C-contiguous float64 array, the missing coordinates in ascending order -- with return_log_density=True a pair of it and the N
+        log-densities of the rows under the marginal mixture. TypeError / ValueError before any device work."""
+        X = _require_data(X_observed)
+        try:
+            coordinates = [int(c) for c in observed]
+        except TypeError:
+            raise TypeError("conditional_mean(): observed must be a sequence of coordinate indices") from None
+        if any(c != o for c, o in zip(coordinates, observed)):
+            raise TypeError("conditional_mean(): observed must hold integers")
+        d, _ = self._dims()
+        if d == 0:
+            raise ValueError("conditional_mean(): the model has not been fitted")
+        if not 1 <= len(coordinates) <= d - 1:
+            raise ValueError("conditional_mean(): between 1 and d - 1 coordinates must be observed")
+        if min(coordinates) < 0 or max(coordinates) >= d:
+            raise ValueError("conditional_mean(): observed coordinate out of range")
+        if len(set(coordinates)) != len(coordinates):
+            raise ValueError("conditional_mean(): observed coordinate given twice")
+        n, columns = X.shape
+        if columns != len(coordinates):
+            raise ValueError("conditional_mean(): X_observed must have one column per observed coordinate")
+        index = np.array(coordinates, dtype=np.uint32)
+        out = np.empty((n, d - len(coordinates)))
+        dens = np.empty(n) if return_log_density else None
+        _check(_l.mlpp_em_conditional_means(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n), _dp(out),
+                                            _dp(dens) if return_log_density else None))
+        return (out, dens) if return_log_density else out
 
     @property
     def labels(self):

@@ -119,8 +119,37 @@ int em_sample_route(int d, uint32_t K);
 /// Returns the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
 int launch_em_sample(const SampleArgs& a, int num_cus, hipStream_t stream);
 
+/// Conditioning pass (em_condition.hip): E[x_M | x_O] of the n rows of a chunk from the log-responsibilities lw [K][ldr] / lse an
+/// E-step kernel wrote for the marginal mixture over the observed coordinates (with_lse = 1, fold = 0) -- the composed route's
+/// finishing kernel where em_score_finish_kernel stands in scoring. Row i's output is a pure function of row i and the parameters.
+enum ConditionKernel : int {
+    kConditionRegisters = 0,                   // dO <= 32 and dM <= 32: lane = row, x_O and the accumulators in registers
+    kConditionPlain = 1,                       // up to d = 4096: table and accumulators in global memory
+};
+struct ConditionArgs {
+    const double* xt; size_t ldx; uint32_t n;                // the observed coordinates, feature-major: row c = coordinate observed[c]
+    int dO, dM, K;
+    const double* lw; size_t ldr; const double* lse;         // K x ldr log-responsibilities and their log-sum-exp
+    const double* table;                                     // K records of condition_record_doubles(kernel, dO, dM)
+    double* out;                                             // n x dM, row-major and contiguous (16-byte aligned)
+    int skip;                                                // 1: a wave passes over a component none of its rows has a share in
+    int kernel;                                              // ConditionKernel
+};
+/// kConditionRegisters where both paddings exist, else kConditionPlain.
+int em_condition_route(int dO, int dM);
+/// The paddings the record of `kernel` is laid out for: [mu_O (PO) | mu_M (PM) | A^T (PO x PM: row c = observed coordinate c)], +0.0
+/// beyond dO / dM except the rows c >= dO of A^T, which hold -0.0 (an identity in the kernel's fma chain). The register tier pads to 4 / 8 / 16 / 32 each, the plain tier not at all.
+int condition_pad(int kernel, int n);
+inline size_t condition_record_doubles(int kernel, int dO, int dM)
+{
+    const size_t po = (size_t)condition_pad(kernel, dO), pm = (size_t)condition_pad(kernel, dM);
+    return po + pm + po * pm;
+}
+/// Returns the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
+int launch_em_condition(const ConditionArgs& a, int num_cus, hipStream_t stream);
+
 enum MstatsMode : int {
-    kFromLogResp = 0,   // r = exp(lw - lse)          (after an E-step)
+    kFromLogResp = 0,  // r = exp(lw - lse)          (after an E-step)
     kFromResp = 1,      // r = lw                     (plain responsibilities: caller-given, one-hot, or all ones)
     kFromLogRespSelfNorm = 2   // r = e_k / sum_k e_k with the normalisation done by the statistics kernel itself (wide kernel, one
                                // row-block group); launch_em_reduce then also finishes lse = max + log(sum) and the ll partials

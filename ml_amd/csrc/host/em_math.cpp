@@ -422,5 +422,54 @@ void covariances_from_full(Covariance mode, int K, int d, const double* mixing, 
     }
 }
 
+void condition(Covariance mode, int K, int d, const double* means, const double* covariance, const unsigned int* observed, int n_observed,
+               double* means_observed, double* covariances_observed, double* maps, double* means_missing)
+{
+    const int dO = n_observed, dM = d - n_observed;
+    const std::size_t dd = (std::size_t)d * d, oo = (std::size_t)dO * dO, mo = (std::size_t)dM * dO;
+    std::vector<char> is_observed(d, 0);
+    for (int c = 0; c < dO; ++c) is_observed[observed[c]] = 1;
+    std::vector<unsigned int> missing;
+    for (int j = 0; j < d; ++j)
+        if (!is_observed[j]) missing.push_back((unsigned int)j);
+    for (int k = 0; k < K; ++k) {
+        for (int c = 0; c < dO; ++c) means_observed[(std::size_t)k * dO + c] = means[(std::size_t)k * d + observed[c]];
+        for (int j = 0; j < dM; ++j) means_missing[(std::size_t)k * dM + j] = means[(std::size_t)k * d + missing[j]];
+    }
+    // (the tied matrix is conditioned once: its K maps are copies, equal bit for bit)
+    const int factored = mode == Covariance::Tied ? 1 : K;
+    std::vector<double> full(dd), L(oo), y(dO);
+    for (int k = 0; k < factored; ++k) {
+        covariances_as_full(mode, 1, d, covariance + (mode == Covariance::Diagonal ? (std::size_t)k * d : (std::size_t)k * dd), full.data());
+        double* Soo = covariances_observed + (std::size_t)k * oo;
+        for (int b = 0; b < dO; ++b)
+            for (int a = 0; a < dO; ++a) Soo[(std::size_t)b * dO + a] = full[(std::size_t)observed[b] * d + observed[a]];
+        cholesky_lower(dO, Soo, L.data());
+        for (int c = 0; c < dO; ++c)
+            for (int i = c; i < dO; ++i) {
+                const double v = L[(std::size_t)c * dO + i];
+                if (!std::isfinite(v) || (i == c && !(v > 0))) throw std::domain_error("observed covariance block is not positive definite");
+            }
+        for (int j = 0; j < dM; ++j) {
+            double* a_j = maps + (std::size_t)k * mo + (std::size_t)j * dO;
+            const double* s = full.data() + (std::size_t)missing[j] * d;      // column M_j of Sigma_k: s[O_a] = Sigma_k[O_a][M_j]
+            for (int i = 0; i < dO; ++i) {
+                double t = s[observed[i]];
+                for (int l = 0; l < i; ++l) t -= L[(std::size_t)l * dO + i] * y[l];
+                y[i] = t / L[(std::size_t)i * dO + i];
+            }
+            for (int i = dO - 1; i >= 0; --i) {
+                double t = y[i];
+                for (int l = i + 1; l < dO; ++l) t -= L[(std::size_t)i * dO + l] * a_j[l];
+                a_j[i] = t / L[(std::size_t)i * dO + i];
+            }
+        }
+    }
+    for (int k = factored; k < K; ++k) {
+        std::copy(covariances_observed, covariances_observed + oo, covariances_observed + (std::size_t)k * oo);
+        std::copy(maps, maps + mo, maps + (std::size_t)k * mo);
+    }
+}
+
 }  // namespace host
 }  // namespace mlhip

@@ -78,6 +78,16 @@ void covariances_as_full(Covariance mode, int K, int d, const double* covariance
 /// entry v = 0, then v += pi_k Sigma_k[e] in ascending k: the order is part of the results' bits --; a copy.
 void covariances_from_full(Covariance mode, int K, int d, const double* mixing, const double* full, double* covariance);
 
+/// Conditioning of a mixture over (x_O, x_M) on the observed block (mlhip_em_condition, mlhip.h). `observed`: n_observed distinct
+/// coordinates < d in any order (column c of an observed row holds coordinate observed[c]); the missing ones are the complement, ascending.
+/// Per component, on the covariance as a full matrix (covariances_as_full: a diagonal gives maps of +0.0, the tied matrix K equal maps):
+///   means_observed[k][c] = mu_k[O_c]; covariances_observed[k] = Sigma_k,OO (dO x dO, always full); means_missing[k][j] = mu_k[M_j];
+///   maps[k] = A_k = Sigma_k,MO Sigma_k,OO^-1 (dM x dO, row j = missing coordinate j), row j solved as L y = Sigma_k,O M_j (forward),
+///   L^T a = y (backward) with L = cholesky_lower(Sigma_k,OO) -- the substitutions of process_covariance.
+/// std::domain_error when a Sigma_k,OO is not positive definite (a factor with a non-finite entry or a diagonal that is not > 0).
+void condition(Covariance mode, int K, int d, const double* means, const double* covariance, const unsigned int* observed, int n_observed,
+               double* means_observed, double* covariances_observed, double* maps, double* means_missing);
+
 /// Tells the host-side math how many ranks share this node, so that the OpenMP teams of the per-component
 /// factorizations together stay within the host's cores (MLHIP_HOST_THREADS overrides the per-rank thread count).
 void set_host_ranks(int local_ranks);

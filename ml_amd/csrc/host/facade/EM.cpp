@@ -557,6 +557,46 @@ MatrixXd EM::sample(Index n, std::uint64_t seed, std::vector<unsigned int>* labe
     return out;
 }
 
+MatrixXd EM::conditional_means(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, double* log_densities) const
+{
+    const Index d = means().rows();
+    // (the order of sample: that there is a shape, the arguments against it, the device, the decompositions)
+    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    if (observed.empty() || static_cast<Index>(observed.size()) >= d)
+        throw std::invalid_argument("EM: between 1 and d - 1 coordinates must be observed");
+    std::vector<char> seen(static_cast<std::size_t>(d), 0);
+    for (const unsigned int c : observed) {
+        if (static_cast<Index>(c) >= d) throw std::invalid_argument("EM: observed coordinate out of range");
+        if (seen[c]) throw std::invalid_argument("EM: observed coordinate given twice");
+        seen[c] = 1;
+    }
+    const Index d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed, n = data_observed.cols();
+    if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
+    require_fitted();
+    const unsigned int K = number_components_;
+    const std::vector<double> cov_flat = flat_covariances();
+    std::vector<double> means_observed(static_cast<std::size_t>(K * d_observed)), covariances_observed(static_cast<std::size_t>(K * d_observed * d_observed)),
+        maps(static_cast<std::size_t>(K * d_missing * d_observed)), means_missing(static_cast<std::size_t>(K * d_missing));
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+    check(mlhip_em_condition(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, means_.data(), cov_flat.data(),
+                             reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(d_observed), means_observed.data(),
+                             covariances_observed.data(), maps.data(), means_missing.data()));
+    MatrixXd out(d_missing, n);
+    if (!n) return out;
+    mlhip_ctx* ctx = device::context();
+    const Index batch = Clustering::detail::score_batch_rows();
+    for (Index first = 0; first < n; first += batch) {
+        const Index rows = std::min(batch, n - first);
+        DataGuard dev;
+        check(mlhip_data_upload(ctx, data_observed.col(first), static_cast<uint32_t>(d_observed), static_cast<uint64_t>(rows),
+                                data_observed.outerStride(), &dev.h));
+        check(mlhip_em_conditional_means(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
+                                         covariances_observed.data(), maps.data(), means_missing.data(), out.col(first), d_missing,
+                                         log_densities ? log_densities + first : nullptr));
+    }
+    return out;
+}
+
 void EM::process_covariances(const Index number_dimensions)
 {
     // Inverse and sqrt(det) of every covariance for the host point query (ML/EM.cpp:274-287).

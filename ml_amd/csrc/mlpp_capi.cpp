@@ -219,6 +219,20 @@ int mlpp_em_sample(const mlpp_em* h, uint64_t n, uint64_t seed, double* x_out, u
         if (labels_out) std::copy(labels.begin(), labels.end(), labels_out);
     });
 }
+int mlpp_em_conditional_means(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                              double* out, double* log_density_out)
+{
+    return guarded([&] {
+        need(h);
+        if (n_observed) need(observed);
+        if (n && n_observed) { need(data_observed); need(out); }
+        if (n > static_cast<uint64_t>(std::numeric_limits<Index>::max())) throw std::invalid_argument("EM: Too many samples");
+        const std::vector<unsigned int> coordinates(observed, observed + n_observed);
+        const MatrixXd y = h->em.conditional_means(coordinates, ConstMatrixRef(data_observed, n_observed, static_cast<Index>(n), n_observed),
+                                                   log_density_out);
+        std::copy_n(y.data(), y.size(), out);
+    });
+}
 int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out)
 {
     return guarded([&] {

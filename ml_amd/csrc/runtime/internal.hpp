@@ -666,6 +666,20 @@ struct SampleRoute {
 };
 SampleRoute sample_route(int d, uint32_t K);
 
+/// mlhip_em_conditional_means: the E-step tier of the observed block's shape (em_route, full covariances, exact form), the finishing
+/// kernel em_condition_route (device/em_condition.hip) names for (dO, dM) -- MLHIP_CONDITION=plain: the plain tier everywhere -- and the
+/// rows per chunk: the largest whole number of sample tiles whose K + dM doubles per row (log-responsibilities and output) stay within
+/// kScoreScratchBytes (MLHIP_CONDITION_ROWS=n overrides, rounded UP to whole tiles; the rows do not depend on it). `skip`: the
+/// kernel passes over components no row of a wave has a share in (MLHIP_CONDITION_SKIP=0: it runs them all; same bits).
+/// (mlhip.h names the kernels by ConditionKernel's values.)
+struct ConditionRoute {
+    EmRoute em;
+    int kernel = kConditionRegisters;
+    uint32_t chunk_rows = 0;
+    bool skip = true;
+};
+ConditionRoute condition_route(const mlhip_data* data, int K, int dM);
+
 /// mlhip_em_iterate_restarts: R loops one after the other (every shape and mode), or BATCHED -- the restarts still running share the
 /// three launches of an iteration (em_restarts.hip) -- where the solo iteration is the fused kernel in its vector-unit form on at
 /// most one workgroup per CU: full covariances, an unweighted block, a single rank without an all-reduce hook. The batch is taken from

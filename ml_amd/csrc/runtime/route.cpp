@@ -31,6 +31,9 @@ struct Switches {
     int restarts;               // MLHIP_EM_RESTARTS=sequential / batch: kRestartsSequential / kRestartsBatched forced (the batch: where it exists), -1 automatic
     bool sample_global;         // MLHIP_SAMPLE_TABLE=global: the sampler reads its table from global memory where it would fit LDS
     long sample_rows;           // MLHIP_SAMPLE_ROWS=n: rows per chunk of the host-output sampler (0: by kSampleChunkBytes)
+    bool condition_plain;       // MLHIP_CONDITION=plain: the conditioning pass takes its plain tier at every shape
+    long condition_rows;        // MLHIP_CONDITION_ROWS=n: rows per chunk of the conditioning pass (0: by the scratch bound)
+    bool condition_skip;        // on unless MLHIP_CONDITION_SKIP=0: components without a share in a wave's rows are passed over
 };
 
 Switches read_switches()
@@ -66,6 +69,11 @@ Switches read_switches()
     s.sample_global = sample_table && std::strcmp(sample_table, "global") == 0;
     const char* sample_rows = std::getenv("MLHIP_SAMPLE_ROWS");
     s.sample_rows = sample_rows && *sample_rows ? std::atol(sample_rows) : 0;
+    const char* condition = std::getenv("MLHIP_CONDITION");
+    s.condition_plain = condition && std::strcmp(condition, "plain") == 0;
+    const char* condition_rows = std::getenv("MLHIP_CONDITION_ROWS");
+    s.condition_rows = condition_rows && *condition_rows ? std::atol(condition_rows) : 0;
+    s.condition_skip = env_char("MLHIP_CONDITION_SKIP") != '0';
     return s;
 }
 
@@ -138,6 +146,22 @@ ScoreRoute score_route(const mlhip_data* data, int K)
     uint64_t rows = sw.score_rows > 0 ? (uint64_t)sw.score_rows : kScoreScratchBytes / (sizeof(double) * (uint64_t)K);
     rows = rows / kSampleTile * kSampleTile;
     if (rows < (uint64_t)kSampleTile) rows = kSampleTile;
+    if (rows > data->n_pad) rows = data->n_pad;
+    r.chunk_rows = (uint32_t)rows;
+    return r;
+}
+
+ConditionRoute condition_route(const mlhip_data* data, int K, int dM)
+{
+    const Switches sw = read_switches();
+    ConditionRoute r;
+    r.em = em_route(data, K, Covariance::Full);
+    r.kernel = sw.condition_plain ? kConditionPlain : em_condition_route(data->d, dM);
+    r.skip = sw.condition_skip;
+    const uint64_t tile = kSampleTile;
+    uint64_t rows = sw.condition_rows > 0 ? (uint64_t)sw.condition_rows : kScoreScratchBytes / (sizeof(double) * ((uint64_t)K + (uint64_t)dM));
+    rows = sw.condition_rows > 0 ? (rows + tile - 1) / tile * tile : rows / tile * tile;
+    if (rows < tile) rows = tile;
     if (rows > data->n_pad) rows = data->n_pad;
     r.chunk_rows = (uint32_t)rows;
     return r;
