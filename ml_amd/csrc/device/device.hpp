@@ -68,6 +68,7 @@ struct EstepArgs {
     const double* shift;                                    // device, D doubles (zero-padded): the fold's centre
     int fold;                                               // records carry -W (mu - shift) instead of the mean (d <= 32)
     int with_lse;                                           // 0: write lw only (the statistics kernel normalises)
+    int row_major;                                          // fold && !with_lse: the blocks in row-quad-major order where that form is built (estep_mfma4_row_major_built)
     int num_cus;                                            // compute units of the context's device (0: ask the current device)
     double* scratch; size_t scratch_doubles;                // a block free for the launch (the statistics partials): the big tier's q parts
     int plain;                                              // d > kMaxDim: 1 = the plain tier even where big_dim.hip applies

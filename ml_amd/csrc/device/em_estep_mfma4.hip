@@ -24,7 +24,10 @@
 //   !LSE  no online log-sum-exp, only lw is written: the statistics kernel normalises a sample's K log-responsibilities
 //         itself while staging its tile (em_mstats_wide.hip, one exp per (sample, component) instead of one in each
 //         kernel) and produces lse and the log-likelihood sum. Used whenever K fits one row-block group of that kernel.
-// A third option makes the scoring pass (mlhip_em_score) out of the same kernel:
+// A third halves the LDS operand reads and barriers per sample:
+//   ROWS  (with FOLD and !LSE, D = 24 and 32) the blocks row-quad major and 128 samples per wave instead of column-quad major
+//         and 64: see the kernel's comment. Same bits; MLHIP_ESTEP_ORDER=column keeps the column order.
+// A fourth makes the scoring pass (mlhip_em_score) out of the same kernel:
 //   SCORE the LSE epilogue without the lw store and without the log-likelihood partials; the label argmax_k lw (first maximum
 //         wins) is carried next to m / ssum in the owner lanes -- the running maximum of the log-sum-exp is the running best lw,
 //         both move on the strict lw > m -- and lw_out points at the labels. Exact form only. Its instantiations are part 2 of
@@ -45,6 +48,11 @@ template <int D> struct Blocks {
     static constexpr int C(int t) { int c = 0; while (c + 1 < Q && start_of(c + 1) <= t) ++c; return c; }
     static constexpr int R(int t) { return C(t) + (t - start_of(C(t))); }
     static constexpr bool first_of_C(int t) { return t == start_of(C(t)); }
+    // step u (row-quad major, the ROWS form): u -> (R, C), C = 0..R; slot(R, C) = the block's step in the record's column-quad-major order
+    static constexpr int row_of(int u) { int r = 0; while ((r + 1) * (r + 2) / 2 <= u) ++r; return r; }
+    static constexpr int col_of(int u) { return u - row_of(u) * (row_of(u) + 1) / 2; }
+    static constexpr int slot(int R, int C) { return start_of(C) + (R - C); }
+    static constexpr int slot_of_row_step(int u) { return slot(row_of(u), col_of(u)); }
     // rolling prefetch window: the largest divisor of NB that is <= 9
     static constexpr int window() { for (int w = 9; w > 1; --w) if (NB % w == 0) return w; return 1; }
 };
@@ -82,20 +90,34 @@ __device__ __forceinline__ double reduce_scatter_groups(double v0, double v1, do
 
 /// SB = 16-sample blocks per wave (4: 64 samples per wave, 4 waves per workgroup, 2 waves per SIMD -- d <= 32; 2: 32
 /// samples per wave, 8 waves per workgroup, half the coordinate/accumulator registers -- 32 < d <= 64, or
-/// MLHIP_ESTEP_SB=2; 1: 16 samples per wave, 8 waves of 512 threads -- 64 < d <= 128). A workgroup covers 256 samples
-/// per component sweep for SB = 4 and 2 (128 for SB = 1); the component record is staged once per sweep.
+/// MLHIP_ESTEP_SB=2; 1: 16 samples per wave, 8 waves of 512 threads -- 64 < d <= 128; 8: 128 samples per wave, 2 waves per
+/// workgroup -- the row-major form below). A workgroup covers 256 samples per component sweep for SB = 8, 4 and 2 (128 for
+/// SB = 1); the component record is staged once per sweep.
 template <int SB> constexpr int default_waves() { return SB == 1 ? 8 : 16 / SB; }
 
 template <bool SCORE> struct BlockOut { using type = double; };       // lw_out: the log-responsibility block ...
 template <> struct BlockOut<true> { using type = uint32_t; };         // ... or, in the SCORE form, the labels
 
-template <int D, int SB, bool FOLD, bool LSE, int NW = default_waves<SB>(), bool SCORE = false>
-__global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_kernel(
+/// ROWS != 0 (FOLD and !LSE, SB = 8, D = 24 and 32): the blocks in ROW-quad-major order, 128 samples per wave in 2-wave workgroups
+/// (a sweep is still 256 samples), four workgroups per CU = two waves per SIMD. In the FOLD form the B operand is x - s itself, the
+/// same for every component, so nothing ties the blocks to the column order: with R outer and C = 0..R inner a row quad of y is
+/// complete after its last column, its squares go into q at once and its accumulators are free again -- ROWS x SB accumulators live
+/// instead of Q x SB, which is what lets 8 sample blocks and their 128 coordinate registers fit two waves per SIMD. Every read of a W
+/// block, of an accumulator initialiser and of coef, and every barrier, then serves 128 samples instead of 64. ROWS is the number of
+/// row quads whose squares are taken in one cluster of vector instructions (row_cluster<D>(), measured). Every accumulator still
+/// receives its products in ascending C and q its squares in ascending R through the same fma chain: lw has the bits of the column
+/// order. The record is unchanged, the blocks are read from their column-major slots.
+template <int D> constexpr int row_cluster() { return D == 32 ? 4 : 2; }
+
+template <int D, int SB, bool FOLD, bool LSE, int NW = default_waves<SB>(), bool SCORE = false, int ROWS = 0>
+__global__ __launch_bounds__(64 * NW, (SB == 8 ? 2 : D <= 32 ? 8 / SB : 2)) void em_estep_mfma4_kernel(
     const double* __restrict__ xt, size_t ldx, uint32_t n, uint32_t n_groups, const double* __restrict__ params, int K,
     const double* __restrict__ shift, typename BlockOut<SCORE>::type* __restrict__ lw_out, size_t ldr, double* __restrict__ lse_out,
     double* __restrict__ ll_partials)
 {
     static_assert(!SCORE || (LSE && !FOLD), "the SCORE form is the exact LSE form");
+    static_assert(!ROWS || (FOLD && !LSE), "the row-major order needs a B operand that does not depend on the component");
+    static_assert((SB == 8) == (ROWS != 0) && (SB != 8 || NW == 2), "8 sample blocks per wave: the row-major form, and only it");
     using B = Blocks<D>;
     constexpr int Q = B::Q, NB = B::NB, PS = B::PS;
     constexpr int NT = 64 * NW, NWV = NW;          // threads / waves per workgroup
@@ -157,51 +179,90 @@ __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_
             for (int it = 0; it < NLD; ++it) stage[it] = nxt[min(tid + NT * it, PS - 1)];
 
             const double coef = rec[NB * 16 + 2 * D];
-            double aw[W], acc[SB][Q], z[SB];
-#pragma unroll
-            for (int t = 0; t < W && t < NB; ++t) aw[t] = rec[t * 16 + aoff];
-            // Nested static loops (column quad C, then row quad R >= C): every index below is a compile-time constant
-            // after unrolling, so the accumulators and the window stay in registers.
-            // The wave in its matrix phase gets the issue priority over the SIMD's other wave, which is in its VALU phase
-            // (squares, reduce-scatter, epilogue) or waiting at the barrier: the MFMA stream is not broken up by the
-            // neighbour's VALU instructions, which fit into its shadow instead. Measured: d = 32, K = 64 12.35 -> 12.0 ms;
-            // -1.5 % at d = 24 / 28, neutral at d = 20 and from d = 48 on, but +3 .. 4 % at d = 12 / 16, where the matrix phase of a
-            // component is 6 - 10 blocks short and the neighbour's epilogue is most of the work: not used there.
+            double aw[W], qs[SB];
             constexpr bool kPrioritise = D >= 20;
-            if constexpr (kPrioritise) __builtin_amdgcn_s_setprio(kMatrixPhasePriority);
+            if constexpr (ROWS != 0) {
+                constexpr int kRowCluster = ROWS;
+                double acc[SB][kRowCluster];
 #pragma unroll
-            for (int C = 0; C < Q; ++C) {
-                // the record's two vectors: the mean (exact form) / -W (mu - shift) (FOLD: the accumulator initialiser)
-                const double mu = FOLD ? 0.0 : rec[NB * 16 + 4 * C + g];
+                for (int sb = 0; sb < SB; ++sb) qs[sb] = 0.0;
 #pragma unroll
-                for (int R = C; R < Q; ++R) {
-                    const int t = C * Q - C * (C - 1) / 2 + (R - C);     // step index in column-quad-major order
-                    const double a = aw[t % W];
-                    if (R == C) {
+                for (int u = 0; u < W && u < NB; ++u) aw[u] = rec[B::slot_of_row_step(u) * 16 + aoff];
+                if constexpr (kPrioritise) __builtin_amdgcn_s_setprio(kMatrixPhasePriority);
 #pragma unroll
-                        for (int sb = 0; sb < SB; ++sb) z[sb] = FOLD ? xb[C][sb] : xb[C][sb] - mu;
+                for (int R = 0; R < Q; ++R) {
+                    const double init = rec[NB * 16 + D + 4 * R + g];      // -W (mu - shift), rows 4R .. 4R + 3
+#pragma unroll
+                    for (int C = 0; C <= R; ++C) {
+                        const int u = R * (R + 1) / 2 + C;                 // step index in row-quad-major order
+                        const double a = aw[u % W];
+                        if (u + W < NB) aw[u % W] = rec[B::slot_of_row_step(u + W) * 16 + aoff];
+#pragma unroll
+                        for (int sb = 0; sb < SB; ++sb)
+                            acc[sb][R % kRowCluster] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xb[C][sb], C == 0 ? init : acc[sb][R % kRowCluster], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-                    if (t + W < NB) aw[t % W] = rec[(t + W) * 16 + aoff];   // refill the slot (LDS broadcast read)
-                    double init = 0.0;
-                    if constexpr (FOLD) { if (C == 0) init = rec[NB * 16 + D + 4 * R + g]; }
+                    // the squares of the finished rows, in ONE cluster (a vector instruction between two matrix instructions costs
+                    // the pipe 12 cycles, in a cluster 5), oldest row first: its products have long left the pipe
+                    if ((R + 1) % kRowCluster == 0 || R == Q - 1) {
 #pragma unroll
-                    for (int sb = 0; sb < SB; ++sb)
-                        acc[sb][R] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, z[sb], C == 0 ? init : acc[sb][R], 0, 0, 0);
-                    // Pin the block order (column-quad major, the sample blocks back to back).
-                    __builtin_amdgcn_sched_barrier(0);
+                        for (int r = R - R % kRowCluster; r <= R; ++r)
+#pragma unroll
+                            for (int sb = 0; sb < SB; ++sb) qs[sb] = __builtin_fma(acc[sb][r % kRowCluster], acc[sb][r % kRowCluster], qs[sb]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                if constexpr (kPrioritise) __builtin_amdgcn_s_setprio(0);
+            } else {   // the column-quad-major order
+                double acc[SB][Q], z[SB];
+#pragma unroll
+                for (int t = 0; t < W && t < NB; ++t) aw[t] = rec[t * 16 + aoff];
+                // Nested static loops (column quad C, then row quad R >= C): every index below is a compile-time constant
+                // after unrolling, so the accumulators and the window stay in registers.
+                // The wave in its matrix phase gets the issue priority over the SIMD's other wave, which is in its VALU phase
+                // (squares, reduce-scatter, epilogue) or waiting at the barrier: the MFMA stream is not broken up by the
+                // neighbour's VALU instructions, which fit into its shadow instead. Measured: d = 32, K = 64 12.35 -> 12.0 ms;
+                // -1.5 % at d = 24 / 28, neutral at d = 20 and from d = 48 on, but +3 .. 4 % at d = 12 / 16, where the matrix phase of a
+                // component is 6 - 10 blocks short and the neighbour's epilogue is most of the work: not used there.
+                if constexpr (kPrioritise) __builtin_amdgcn_s_setprio(kMatrixPhasePriority);
+#pragma unroll
+                for (int C = 0; C < Q; ++C) {
+                    // the record's two vectors: the mean (exact form) / -W (mu - shift) (FOLD: the accumulator initialiser)
+                    const double mu = FOLD ? 0.0 : rec[NB * 16 + 4 * C + g];
+#pragma unroll
+                    for (int R = C; R < Q; ++R) {
+                        const int t = C * Q - C * (C - 1) / 2 + (R - C);     // step index in column-quad-major order
+                        const double a = aw[t % W];
+                        if (R == C) {
+#pragma unroll
+                            for (int sb = 0; sb < SB; ++sb) z[sb] = FOLD ? xb[C][sb] : xb[C][sb] - mu;
+                        }
+                        if (t + W < NB) aw[t % W] = rec[(t + W) * 16 + aoff];   // refill the slot (LDS broadcast read)
+                        double init = 0.0;
+                        if constexpr (FOLD) { if (C == 0) init = rec[NB * 16 + D + 4 * R + g]; }
+#pragma unroll
+                        for (int sb = 0; sb < SB; ++sb)
+                            acc[sb][R] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, z[sb], C == 0 ? init : acc[sb][R], 0, 0, 0);
+                        // Pin the block order (column-quad major, the sample blocks back to back).
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                if constexpr (kPrioritise) __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+                for (int sb = 0; sb < SB; ++sb) {
+                    double t2 = 0.0;
+#pragma unroll
+                    for (int R = 0; R < Q; ++R) t2 = __builtin_fma(acc[sb][R], acc[sb][R], t2);
+                    qs[sb] = t2;
                 }
             }
-            if constexpr (kPrioritise) __builtin_amdgcn_s_setprio(0);
-            double qs[SB];
-#pragma unroll
-            for (int sb = 0; sb < SB; ++sb) {
-                double t2 = 0.0;
-#pragma unroll
-                for (int R = 0; R < Q; ++R) t2 = __builtin_fma(acc[sb][R], acc[sb][R], t2);
-                qs[sb] = t2;
-            }
             double q;
-            if constexpr (SB == 1) {
+            if constexpr (SB == 8) {
+                // two 64-sample halves: lane (g, s) gets sample 16g + s of blocks 0-3 and sample 64 + 16g + s of blocks 4-7
+                q = reduce_scatter_groups(qs[0], qs[1], qs[2], qs[3]);
+                const double q_hi = reduce_scatter_groups(qs[4], qs[5], qs[6], qs[7]);
+                lw_out[(size_t)k * ldr + base + 64 + lane] = __builtin_fma(-0.5, q_hi, coef);
+            } else if constexpr (SB == 1) {
                 // one block: the four lane groups hold the four row residues of the same 16 samples
                 const double t = qs[0] + __shfl_xor(qs[0], 16, 64);
                 q = t + __shfl_xor(t, 32, 64);
@@ -282,7 +343,7 @@ __global__ __launch_bounds__(64 * NW, D <= 32 ? 8 / SB : 2) void em_estep_mfma4_
     }
 }
 
-template <int D, int SB, bool FOLD, bool LSE, int NW = default_waves<SB>(), bool SCORE = false>
+template <int D, int SB, bool FOLD, bool LSE, int NW = default_waves<SB>(), bool SCORE = false, int ROWS = 0>
 int launch_sb(const EstepArgs& a, int num_cus, hipStream_t stream)
 {
     // the waves of a workgroup share barriers inside the component loop: a workgroup sweep must cover a whole number of
@@ -296,13 +357,14 @@ int launch_sb(const EstepArgs& a, int num_cus, hipStream_t stream)
     const uint32_t n_groups = n_pad / GS;
     uint32_t grid = (n_groups + NWV - 1) / NWV;
     uint32_t per_cu = 2 * default_waves<SB>() / NW;                          // the CU's resident workgroups, persistent
+    if constexpr (ROWS != 0) per_cu = 4;                                     // two waves per SIMD
     if constexpr (SB == 4 && D <= 20) {
         // small d: a component is 6 - 21 blocks short, the per-component barrier and the epilogue weigh more, and the kernel needs
         // few registers (92 - 138): as many workgroups per CU as fit, up to 4 [r3] (at d = 24 three fit, the E-step gains 1 % and the
         // statistics kernel behind it loses 2 %: not used there)
         static const int fit = [] {
             int blocks = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, em_estep_mfma4_kernel<D, SB, FOLD, LSE, NW, SCORE>, NT, sizeof(double) * 2 * NLD * NT) != hipSuccess) blocks = 2;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, em_estep_mfma4_kernel<D, SB, FOLD, LSE, NW, SCORE, ROWS>, NT, sizeof(double) * 2 * NLD * NT) != hipSuccess) blocks = 2;
             return blocks < 2 ? 2 : (blocks > 4 ? 4 : blocks);
         }();
         if ((uint32_t)fit > per_cu) per_cu = (uint32_t)fit;
@@ -312,7 +374,7 @@ int launch_sb(const EstepArgs& a, int num_cus, hipStream_t stream)
     if (grid > (uint32_t)a.n_ll_partials) grid = (uint32_t)a.n_ll_partials;
     typename BlockOut<SCORE>::type* block_out;
     if constexpr (SCORE) block_out = a.labels; else block_out = a.lw;
-    hipLaunchKernelGGL((em_estep_mfma4_kernel<D, SB, FOLD, LSE, NW, SCORE>), dim3(grid), dim3(NT), smem, stream, a.xt, a.ldx, a.n, n_groups,
+    hipLaunchKernelGGL((em_estep_mfma4_kernel<D, SB, FOLD, LSE, NW, SCORE, ROWS>), dim3(grid), dim3(NT), smem, stream, a.xt, a.ldx, a.n, n_groups,
                        a.params, a.K, a.shift, block_out, a.ldr, a.lse, a.ll_partials);
     return (int)grid;
 }
@@ -323,6 +385,9 @@ int launch_v(const EstepArgs& a, int num_cus, hipStream_t stream)
 #if MLHIP_PART == 2
     return launch_sb<D, SB, false, true, default_waves<SB>(), true>(a, num_cus, stream);
 #else
+    if constexpr (D == 24 || D == 32) {   // (layout.hpp estep_mfma4_row_major_built)
+        if (a.fold && !a.with_lse && a.row_major) return launch_sb<D, 8, true, false, 2, false, row_cluster<D>()>(a, num_cus, stream);
+    }
     if constexpr (D <= kRegDim) {
         if (a.fold) return a.with_lse ? launch_sb<D, SB, true, true>(a, num_cus, stream) : launch_sb<D, SB, true, false>(a, num_cus, stream);
     }

@@ -56,6 +56,9 @@ inline int estep_param_stride(int D) { return D + D * (D + 1) / 2 + 1; }
 /// unless two responsibilities already agree to 1e-13.
 constexpr double kEstepFoldLimit = 64.0;
 inline bool estep_mfma4_supported(int D) { return D >= 12 && D <= kMaxDim && D % 4 == 0; }
+/// The FOLD, lw-only form of that kernel also exists with its blocks in row-quad-major order (128 samples per wave) here: the
+/// dimensions at which it was measured faster by the margin DESIGN.md 3.3b asks for (at D = 28 it missed that margin).
+inline bool estep_mfma4_row_major_built(int D) { return D == 24 || D == 32; }
 inline int estep_mfma4_block_count(int D) { const int q = D / 4; return q * (q + 1) / 2; }
 inline int estep_mfma4_param_stride(int D) { return estep_mfma4_block_count(D) * 16 + 2 * D + 1; }
 

@@ -103,6 +103,7 @@ void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const 
     a.ll_partials = dt->ll_partials.as<double>(); a.n_ll_partials = kMaxLlPartials;
     a.shift = dt->shift_dev.as<double>(); a.fold = (fold < 0 ? dt->estep.rec_fold : fold != 0) ? 1 : 0;
     a.with_lse = (with_lse || dt->estep.rec_layout != 2) ? 1 : 0;
+    a.row_major = r.estep_rows ? 1 : 0;
     a.num_cus = ctx->num_cus;
     a.scratch = dt->partials.as<double>(); a.scratch_doubles = dt->partials.bytes / sizeof(double);   // (written by the statistics kernel AFTER the E-step, on the same stream)
     a.plain = r.estep == Estep::kPlain;

@@ -615,6 +615,7 @@ struct EmRoute {
     Estep estep = Estep::kScalarFed;
     bool records_on_device = false;    // d > 64: a fit's first records are factored by the closing kernels (em_close_big.hip)
     bool fold_allowed = false;         // d <= 32: the matrix-core E-step may take its FOLD form (kEstepFoldLimit)
+    bool estep_rows = false;           // D = 24, 32: the matrix-core E-step's FOLD, lw-only launches walk their blocks row-quad major
     bool fused = false;                // E-step + statistics in one kernel (em_fused_small.hip)
     int fused_form = kFusedLdsFeed;    // FusedArgs::form
     bool self_norm = false;            // the matrix-core E-step writes lw only, the statistics kernel normalises it

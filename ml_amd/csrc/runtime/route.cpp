@@ -21,6 +21,7 @@ int env_force(const char* name)
 
 struct Switches {
     bool estep_valu;            // MLHIP_ESTEP=valu
+    bool estep_rows;            // off under MLHIP_ESTEP_ORDER=column
     bool fold, self_norm, balanced, fused, diag_ab, big_dim, device_close, records, resident;   // on unless "0"
     int sparse, sfeed;          // MLHIP_MSTATS_SPARSE, MLHIP_FUSED_SFEED: 0 / 1 forced, -1 automatic
     int fused_valu;             // MLHIP_FUSED_VALU: 0 never, 2 wherever built, -1 by shape
@@ -42,6 +43,8 @@ Switches read_switches()
     const char* estep = std::getenv("MLHIP_ESTEP");
     s.estep_valu = estep && std::strcmp(estep, "valu") == 0;
     s.fold = env_char("MLHIP_ESTEP_FOLD") != '0';
+    const char* order = std::getenv("MLHIP_ESTEP_ORDER");
+    s.estep_rows = !(order && std::strcmp(order, "column") == 0);
     s.self_norm = env_char("MLHIP_SELF_NORM") != '0';
     s.balanced = env_char("MLHIP_MSTATS_BALANCED") != '0';
     s.fused = env_char("MLHIP_FUSED") != '0';
@@ -108,6 +111,7 @@ EmRoute em_route(const mlhip_data* data, int K, Covariance mode)
     else r.estep = sw.big_dim && big_dim_applies(D) ? Estep::kBigDim : Estep::kPlain;
     r.records_on_device = sw.records && em_close_big_supported(d);
     r.fold_allowed = sw.fold && D <= kRegDim;
+    r.estep_rows = sw.estep_rows && r.estep == Estep::kMatrix4 && estep_mfma4_row_major_built(D);
     // (the fused kernel reads the scalar-fed E-step's records)
     r.fused = !diag_kernel && !weighted && sw.fused && r.estep == Estep::kScalarFed && mstats::em_fused_supported(d, K);
     if (r.fused) {
