@@ -1,6 +1,7 @@
 """Inputs shared by tests/test_hp_reference.py (CPU) and tests/test_gpu_hp_error.py / test_gpu_hp_edges.py (GPU): mixture problems,
 the oracle's step in the reference's output form, the problems that sit just below / above a guard of DESIGN.md section 4, and the
-inputs no plain sample holds -- a component without mass, rows far in a tail (test infrastructure)."""
+inputs no plain sample holds -- a component without mass, rows far in a tail --, and the ill-conditioned mixtures of
+tests/test_gpu_hp_ill.py with the fp64 restatement of the whitening form that is their yardstick (test infrastructure)."""
 import importlib.util
 import math
 import os
@@ -405,3 +406,121 @@ def tied_grid(d, K, n, num_cus):
 def tied_many_tiles_rows(d, K, num_cus):
     """N at which every wave of the launch takes two whole tiles and the first ones a third, ragged one."""
     return 64 * 4 * tied_grid(d, K, 2 ** 31, num_cus) * 2 + 37
+
+
+# ---- ill-conditioned covariances (DESIGN.md section 4): tests/test_gpu_hp_ill.py on the GPU, the data conditions and the constants in
+# ---- tests/test_hp_reference.py ----------------------------------------------------------------------------------------------------
+
+ILL_CONDS = (1e6, 1e8)
+# (d, K, N): every E-step / statistics family, the closings (registers to d = 32, LDS to 64, panelled above) and the tiers above d = 128
+ILL_SHAPES = [(2, 3, 3001), (3, 4, 3001), (8, 5, 3001), (6, 8, 3001), (16, 8, 4001), (24, 6, 3001), (32, 16, 6001), (33, 4, 3001),
+              (64, 4, 3001), (72, 3, 2501), (128, 3, 2001), (136, 3, 2001)]
+# seed 7 unless the case needs another one for max |W (mu - shift)| to stay 5 % clear of the FOLD guard (tests/test_hp_reference.py)
+ILL_SEEDS = {(16, 8, 4001, 1e8): 8, (33, 4, 3001, 1e8): 8}          # (seed 7 gives 63.6 and 65.0)
+# The whitening model's constants (section 4): per output 4 x the largest constant whitened_step_fp64() needs over ILL_SHAPES x
+# ILL_CONDS in units of sqrt(N_k) 2^-53 kappa_k (tests/test_hp_reference.step_errors; an entry below the floor of its limit --
+# tests/hp_limits.ill_limits -- needs none). `lse`: the per-row log-density, absolute, in the responsibilities' unit -- far above
+# `resp`, because the light components share W and x, so that most of a row's error in y is common to their log-weights and
+# leaves the responsibilities, yet stays in the density; `ll2`: the log-likelihood of a second E-step on the restatement's own new
+# parameters (+ the ridge), in units of sqrt(N) 2^-53 max kappa(new covariances). Measured on this CPU restatement (largest values:
+# ll 0.040, resp 0.964, mixing 0.008, means 0.072, covs 0.233, lse 27.5, ll2 0.0092; tests/test_hp_reference.py asserts them,
+# `python tests/test_hp_reference.py` prints them, oracle/README.md holds the per-case figures), never on a kernel.
+C_ILL = {"ll": 4 * 0.05, "resp": 4 * 1.0, "mixing": 4 * 0.01, "means": 4 * 0.08, "covs": 4 * 0.3, "lse": 4 * 30.0, "ll2": 4 * 0.01}
+
+
+def ill_seed(d, K, n, cond):
+    return ILL_SEEDS.get((d, K, n, cond), 7)
+
+
+def ill_problem(d, K, n, cond, seed=7, sep=1.0, offset=1.5):
+    """A heavy, well conditioned component 0 (60 % of the rows, S = A A^T / d + I / 2, centred at the origin) and K - 1 light ones
+    that share S1 = Q diag(logspace(0, -log10 cond, d)) Q^T (condition number `cond`, kappa ~ sqrt(cond)) and OVERLAP: centres
+    3 Q[:, 0] + j sep L1 u, j = 0 .. K - 2, u a random unit vector -- a chain `sep` whitened units apart, responsibilities strictly
+    inside (0, 1) on their rows. Rows shuffled, everything moved by `offset`, the starting parameters the clusters' own. One
+    default_rng(seed), drawn in the order Q, A, u, heavy rows, light rows, permutation. Returns (X, pi0, mu0, S0)."""
+    rng = np.random.default_rng(seed)
+    Q, _ = np.linalg.qr(rng.standard_normal((d, d)))
+    A = rng.standard_normal((d, d))
+    u = rng.standard_normal(d)
+    u /= np.linalg.norm(u)
+    S_heavy = A @ A.T / d + 0.5 * np.eye(d)
+    S1 = (Q * np.logspace(0, -math.log10(cond), d)) @ Q.T
+    S1 = (S1 + S1.T) / 2
+    L0, L1 = np.linalg.cholesky(S_heavy), np.linalg.cholesky(S1)
+    n1 = int(0.4 * n / (K - 1))
+    n0 = n - (K - 1) * n1
+    centres = np.vstack([np.zeros(d)] + [3 * Q[:, 0] + j * sep * (L1 @ u) for j in range(K - 1)])
+    blocks = [rng.standard_normal((n0, d)) @ L0.T]
+    for j in range(1, K):
+        blocks.append(rng.standard_normal((n1, d)) @ L1.T + centres[j])
+    X = np.vstack(blocks)[rng.permutation(n)]
+    pi0 = np.array([n0 / n] + [n1 / n] * (K - 1))
+    return np.ascontiguousarray(X + offset), pi0, centres + offset, np.stack([S_heavy] + [S1] * (K - 1))
+
+
+def _whitening_fp64(S):
+    """(L, W = L^-1) of one covariance in fp64: the left-looking Cholesky loops and the forward substitution of host/em_math.cpp
+    -- every entry receives its terms in ascending l, one product and one subtraction at a time --, vectorised over the row index
+    (the factor) and over the column of W."""
+    d = S.shape[0]
+    L = np.zeros((d, d))
+    for j in range(d):
+        col = S[j:, j].copy()
+        for l in range(j):
+            col -= L[j:, l] * L[j, l]
+        L[j, j] = math.sqrt(col[0])
+        L[j + 1:, j] = col[1:] / L[j, j]
+    W = np.zeros((d, d))
+    for i in range(d):
+        t = np.zeros(d)
+        t[i] = 1.0
+        for l in range(i):
+            t -= L[i, l] * W[l]
+        W[i] = t / L[i, i]
+    return L, np.tril(W)
+
+
+def _whitened_log_weights_fp64(X, pi, mu, S):
+    n, d = X.shape
+    lw = np.empty((n, len(pi)))
+    for k in range(len(pi)):
+        L, W = _whitening_fp64(S[k])
+        c = X - mu[k]
+        q = np.zeros(n)
+        for i in range(d):
+            y = W[i, 0] * c[:, 0]
+            for j in range(1, i + 1):
+                y = y + W[i, j] * c[:, j]
+            q = q + y * y
+        lw[:, k] = -0.5 * q + math.log(pi[k]) - np.log(np.diag(L)).sum() - 0.5 * d * math.log(2 * math.pi)
+    top = lw.max(axis=1)
+    return lw, top + np.log(np.exp(lw - top[:, None]).sum(axis=1))
+
+
+def whitened_log_likelihood_fp64(X, pi, mu, S):
+    """The density part of whitened_step_fp64 alone: (mean log-likelihood, the per-row log-sum-exp)."""
+    lse = _whitened_log_weights_fp64(X, pi, mu, S)[1]
+    return lse.mean(), lse
+
+
+def whitened_step_fp64(X, pi0, mu0, S0):
+    """The kernels' algorithm restated in fp64 numpy, in no kernel's operation order (the whitening model's yardstick, as
+    tied_kernel_log_resp is the tied kernel's): L by the host's Cholesky loops and W = L^-1 by forward substitution,
+    y = W (x - mu) accumulated by ascending column, q = sum_j y_j^2, lw = -q / 2 + log pi - sum_j log L_jj - d log(2 pi) / 2, the
+    log-sum-exp about the maximum, then the shared-shift statistics s0 = sum r, s1 = sum r x~, S2 = sum r x~ x~^T about the data
+    mean (x~ = x - shift) closed as host::finalize_mstep closes them -- m = s1 / s0, mu = shift + m, Sigma = (S2 - s1 m^T) / s0 --
+    without the ridge. Returns (ll, responsibilities N x K, mixing, means, covariances, the per-row log-sum-exp)."""
+    n, d = X.shape
+    lw, lse = _whitened_log_weights_fp64(X, pi0, mu0, S0)
+    R = np.exp(lw - lse[:, None])
+    shift = X.mean(axis=0)
+    Xt = X - shift
+    s0 = R.sum(axis=0)
+    s1 = R.T @ Xt
+    m = s1 / s0[:, None]
+    covs = np.empty((len(pi0), d, d))
+    for k in range(len(pi0)):
+        S2 = (Xt * R[:, k][:, None]).T @ Xt
+        covs[k] = (S2 - np.outer(s1[k], m[k])) / s0[k]
+        covs[k] = np.tril(covs[k]) + np.tril(covs[k], -1).T
+    return lse.mean(), R, s0 / n, shift + m, covs, lse

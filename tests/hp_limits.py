@@ -56,6 +56,121 @@ def _report_and_check(name, e_gpu, e_cpu, ratio, estep_model=None, model_name=""
     assert not failures, (name, failures)
 
 
+# ---- ill-conditioned covariances: tests/test_gpu_hp_ill.py -----------------------------------------------------------------------
+
+def ill_errors(got, ref):
+    """_errors with the means per component too (the whitening model's unit sqrt(N_k) 2^-53 kappa_k differs by orders of magnitude
+    between a well and an ill conditioned component of one mixture)."""
+    e = _errors(got, ref)
+    e["means"] = np.array([hp.rel_err(got[3][k], ref[3][k]) for k in range(len(ref[3]))])
+    return e
+
+
+def ill_limits(ref, kappa, ratio, n, fold_ran):
+    """The whitening model's limits: y = W (x - mu) loses kappa = |L|_inf |L^-1|_inf roundings, N_k samples
+    add up like a random walk -- C_ILL[o] sqrt(N_k) 2^-53 kappa_k per component for means and covariances (never below the limits
+    the well conditioned suites hold them to: 4 FLOOR, 4 * 3e-15 max(1, ratio_k)), C_ILL[o] sqrt(N) 2^-53 max kappa for the
+    log-likelihood, the responsibilities and the mixing weights (never below 4 FLOOR), to which the FOLD form, where it ran, adds its
+    own 4 FOLD_BOUND, scaled as _report_and_check scales it. The constants come from the fp64 restatement
+    hp_cases.whitened_step_fp64 on the CPU; the oracle's error is no part of any limit."""
+    n_k = n * np.asarray(ref[2], dtype=np.float64)
+    whole = float(np.sqrt(n) * hp.EPS64 * np.max(kappa))
+    per = np.sqrt(n_k) * hp.EPS64 * np.asarray(kappa)
+    scale = {"ll": abs(float(ref[0])), "resp": 1.0, "mixing": float(np.max(ref[2]))}
+    limits = {key: max(hp_cases.C_ILL[key] * whole, 4 * FLOOR) + (4 * FOLD_BOUND / scale[key] if fold_ran else 0.0) for key in scale}
+    limits["means"] = np.maximum(hp_cases.C_ILL["means"] * per, 4 * FLOOR)
+    limits["covs"] = np.maximum(hp_cases.C_ILL["covs"] * per, 4 * 3e-15 * np.maximum(1.0, ratio))
+    return limits
+
+
+def ill_needed(e, ref, kappa, ratio, n):
+    """The constant each output of an ill_errors() dict needs under ill_limits() without FOLD: its error in the model's unit, 0 for
+    an entry that its limit's floor already covers; means and covariances at their worst component."""
+    n_k = n * np.asarray(ref[2], dtype=np.float64)
+    whole = float(np.sqrt(n) * hp.EPS64 * np.max(kappa))
+    per = np.sqrt(n_k) * hp.EPS64 * np.asarray(kappa)
+    out = {key: (e[key] / whole if e[key] > 4 * FLOOR else 0.0) for key in ("ll", "resp", "mixing")}
+    out["means"] = float(np.where(e["means"] > 4 * FLOOR, e["means"] / per, 0.0).max())
+    out["covs"] = float(np.where(e["covs"] > 4 * 3e-15 * np.maximum(1.0, ratio), e["covs"] / per, 0.0).max())
+    return out
+
+
+def ill_references(d, K, n, cond):
+    """Everything a case of tests/test_gpu_hp_ill.py compares with, from the CPU alone -> dict: the input (X, pi0, mu0, S0), lw (the
+    reference's K x N log-weights), lse, ref (the reference step), old / new (conditioning of the input / of the reference's new
+    parameters about the data mean), white (hp_cases.whitened_step_fp64's 6-tuple), e_white and e_oracle (their ill_errors)."""
+    from oracle import oracle_ctypes as orc
+    X, pi0, mu0, S0 = hp_cases.ill_problem(d, K, n, cond, seed=hp_cases.ill_seed(d, K, n, cond))
+    lw = hp.log_weights(X, pi0, mu0, S0)
+    resp, lse = hp._normalise(lw)
+    ref = (lse.sum() / n, resp.T) + hp._close(hp._ld(X), resp, False)            # (hp.em_step, the log-weights kept)
+    shift = X.astype(LD).mean(axis=0)
+    white = hp_cases.whitened_step_fp64(X, pi0, mu0, S0)
+    return {"X": X, "pi0": pi0, "mu0": mu0, "S0": S0, "lw": lw, "lse": lse, "ref": ref, "white": white,
+            "old": hp.conditioning(shift, mu0, covs=S0), "new": hp.conditioning(shift, ref[3], covs=ref[4]),
+            "e_white": ill_errors(white[:5], ref), "e_oracle": ill_errors(hp_cases.oracle_step(orc, X, pi0, mu0, S0), ref)}
+
+
+def ill_failures(e, limits):
+    """The outputs of an ill_errors() dict that lie over ill_limits(), as strings (resp may be None: not compared)."""
+    failures = []
+    for key in ("ll", "resp", "mixing"):
+        if e[key] is not None and not e[key] <= limits[key]:
+            failures.append(f"{key}: {e[key]:.2e} > {limits[key]:.2e}")
+    for key in ("means", "covs"):
+        for k in np.nonzero(~(e[key] <= limits[key]))[0]:
+            failures.append(f"{key}[{k}]: {e[key][k]:.2e} > {limits[key][k]:.2e}")
+    return failures
+
+
+def check_ill(name, e_gpu, ref, kappa, ratio, n, fold_ran, e_white=None, e_oracle=None):
+    """Prints the case's line -- per output err_gpu / err_whitened_fp64 / err_oracle, means and covariances at the component where
+    the kernel is nearest to its limit --, then asserts ill_limits()."""
+    limits = ill_limits(ref, kappa, ratio, n, fold_ran)
+    fmt = lambda v: "-" if v is None else f"{v:.1e}"   # noqa: E731
+    pick = lambda e, key, k: None if e is None or e[key] is None else (e[key] if k is None else e[key][k])   # noqa: E731
+    parts = []
+    for key in ("ll", "resp", "mixing", "means", "covs"):
+        k = None if key in ("ll", "resp", "mixing") else int(np.argmax(e_gpu[key] / limits[key]))
+        parts.append(f"{key}{'' if k is None else f'[{k}]'} {fmt(pick(e_gpu, key, k))} / {fmt(pick(e_white, key, k))} / {fmt(pick(e_oracle, key, k))}"
+                     f" (limit {fmt(limits[key] if k is None else limits[key][k])})")
+    print(f"HPERR {name} | kappa {np.max(kappa):.3g} | " + " | ".join(parts) + (" | FOLD ran" if fold_ran else ""), flush=True)
+    failures = ill_failures(e_gpu, limits)
+    assert not failures, (name, failures)
+
+
+def ill_ll2_limit(n, kappa_new):
+    """A second E-step's log-likelihood against the reference on the very fp64 parameters the library returned (ridge included):
+    only the factorization of the NEW covariances and the density enter."""
+    return max(hp_cases.C_ILL["ll2"] * float(np.sqrt(n) * hp.EPS64 * np.max(kappa_new)), 4 * FLOOR)
+
+
+def ill_row_limit(n, kappa):
+    """The per-row constant of a log-density (absolute), in the responsibilities' unit."""
+    return max(hp_cases.C_ILL["lse"] * float(np.sqrt(n) * hp.EPS64 * np.max(kappa)), 4 * FLOOR)
+
+
+def ill_decided_rows(lw, limit):
+    """The rows of a K x N block of reference log-weights whose runner-up lies more than `limit` below the winner: an error of
+    limit / 2 in each of the two cannot change their label."""
+    order = np.sort(lw, axis=0)
+    return np.asarray((order[-1] - order[-2]) > limit)
+
+
+def check_ill_rows(name, dens, labels, lw, n, kappa):
+    """em_score's per-row log-densities within ill_row_limit() of the reference's log-sum-exp, its labels the reference's on every
+    decided row; at most 0.1 % of the rows may be undecided. Prints the case's line first."""
+    limit = ill_row_limit(n, kappa)
+    err = hp.abs_err(dens, hp._normalise(lw)[1])
+    decided = ill_decided_rows(lw, limit)
+    wrong = int((np.asarray(labels)[decided] != lw.argmax(axis=0)[decided]).sum())
+    print(f"HPERR {name} | kappa {np.max(kappa):.3g} | per-row log-density {err:.1e} (limit {limit:.1e}) | undecided rows "
+          f"{int((~decided).sum())} of {len(decided)} | wrong labels on decided rows {wrong}", flush=True)
+    assert decided.mean() >= 0.999, (name, decided.mean())
+    assert wrong == 0, (name, wrong)
+    assert err <= limit, (name, err, limit)
+
+
 # ---- the inputs of tests/test_gpu_hp_edges.py ----------------------------------------------------------------------------------
 
 def finite_errors(e):

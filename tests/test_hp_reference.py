@@ -6,6 +6,7 @@ reference in section 4's norms (max-norm relative; per component for means and c
 |L_k|_inf |L_k^-1|_inf of the component's input covariance; N and the largest kappa for the log-likelihood, the mixing weights
 and the responsibilities). C_ORACLE is 4 x the largest constant the oracle needed over CASES / DIAG_CASES in one CPU run
 (the per-case figures are in DESIGN.md section 5 and oracle/README.md); `python tests/test_hp_reference.py` prints them."""
+import functools
 import os
 import sys
 
@@ -555,6 +556,91 @@ def test_edge_checkers_reject_fabricated_results():
         check_tail("a moved row with another label", tuple(fp64()), other, refs, rows, comps, 0)
 
 
+# ---- ill-conditioned covariances: the inputs of tests/test_gpu_hp_ill.py, the whitening model's constants, the limit rule -------
+
+ILL_CASES = [(shape, cond) for shape in hp_cases.ILL_SHAPES for cond in hp_cases.ILL_CONDS]
+ILL_IDS = [f"d={s[0]}-K={s[1]}-cond={c:g}" for s, c in ILL_CASES]
+
+
+@functools.lru_cache(maxsize=None)
+def _ill_case(shape, cond):
+    """The case's references (hp_limits.ill_references) and what the fp64 restatement needs on it: `needed`, the constant per output
+    of one step, the per-row log-density (`lse`) and the second E-step's log-likelihood on its own new parameters (`ll2`)."""
+    import hp_limits
+    d, K, n = shape
+    c = hp_limits.ill_references(d, K, n, cond)
+    X, white = c["X"], c["white"]
+    needed = hp_limits.ill_needed(c["e_white"], c["ref"], c["old"]["kappa"], c["new"]["ratio"], n)
+    whole = np.sqrt(n) * hp.EPS64 * c["old"]["kappa"].max()
+    e_lse = hp.abs_err(white[5], c["lse"])
+    needed["lse"] = float(e_lse / whole) if e_lse > 4 * hp_limits.FLOOR else 0.0
+    pi1, mu1, S1 = white[2], white[3], white[4] + 1e-15 * np.eye(d)             # (what the library hands to its next E-step)
+    ref2 = hp._normalise(hp.log_weights(X, pi1, mu1, S1))[1].sum() / n
+    e_ll2 = abs(float((LD(hp_cases.whitened_log_likelihood_fp64(X, pi1, mu1, S1)[0]) - ref2) / ref2))
+    kappa1 = hp.conditioning(X.astype(LD).mean(axis=0), mu1, covs=S1)["kappa"]
+    needed["ll2"] = float(e_ll2 / (np.sqrt(n) * hp.EPS64 * kappa1.max())) if e_ll2 > 4 * hp_limits.FLOOR else 0.0
+    return dict(c, needed=needed, kappa1=kappa1)
+
+
+def _ill_line(shape, cond, c):
+    o = _ill_oracle_needed(c, shape[2])
+    return (f"ill {shape} cond {cond:g} seed {hp_cases.ill_seed(*shape, cond)}: kappa {c['old']['kappa'].max():.3g}, max abs W(mu-s) "
+            f"{c['old']['fold'].max():.4g}, new ratio {c['new']['ratio'].max():.3g} | units needed, whitening fp64 (oracle): "
+            + ", ".join(f"{k} {v:.4f}" + (f" ({o[k]:.2f})" if k in o else "") for k, v in c["needed"].items()))
+
+
+def _ill_oracle_needed(c, n):
+    import hp_limits
+    return hp_limits.ill_needed(c["e_oracle"], c["ref"], c["old"]["kappa"], c["new"]["ratio"], n)
+
+
+@pytest.mark.parametrize("shape,cond", ILL_CASES, ids=ILL_IDS)
+def test_ill_problems_hold_what_they_are_built_for_and_the_restatement_keeps_its_constants(shape, cond):
+    """What tests/test_gpu_hp_ill.py needs of each input -- kappa ~ sqrt(cond), hundreds of rows with responsibilities strictly
+    inside (0, 1), new covariances that factor and stay far below the refinement guard, max |W (mu - shift)| 5 % clear of the FOLD
+    guard, at most 0.1 % of the rows too close for a label --, and what pins C_ILL: the fp64 restatement of the whitening form
+    within C_ILL / 4 units on every output."""
+    import hp_limits
+    d, K, n = shape
+    c = _ill_case(shape, cond)
+    print(_ill_line(shape, cond, c))
+    kappa = c["old"]["kappa"].max()
+    assert np.sqrt(cond) / 2 <= kappa <= 40 * np.sqrt(cond), kappa
+    resp = c["ref"][1].astype(np.float64)
+    assert ((resp > 1e-3) & (resp < 1 - 1e-3)).any(axis=1).sum() >= 500
+    for k in range(K):
+        hp.cholesky(c["ref"][4][k])                                              # (raises where a new covariance does not factor)
+    assert c["new"]["ratio"].max() < 1e3, c["new"]["ratio"]
+    assert abs(c["old"]["fold"].max() / 64 - 1) > 0.05, c["old"]["fold"]
+    assert hp_limits.ill_decided_rows(c["lw"], hp_limits.ill_row_limit(n, c["old"]["kappa"])).mean() >= 0.999
+    for key, value in c["needed"].items():
+        assert value <= hp_cases.C_ILL[key] / 4, (key, value)
+    hp_limits.check_ill("the restatement", c["e_white"], c["ref"], c["old"]["kappa"], c["new"]["ratio"], n, False, c["e_white"], c["e_oracle"])
+
+
+def test_ill_constants_are_the_restatement_s_and_the_limit_rejects_the_explicit_inverse_form():
+    """C_ILL is 4 x the restatement's largest need, rounded up by no more than a third; and the limit has the teeth the oracle-relative
+    rule lacks: with the oracle's step (explicit inverse covariance, error ~ cond * eps) in a kernel's place the responsibilities
+    exceed it at cond = 1e8 on at least half of the shapes with d >= 6."""
+    import hp_limits
+    worst = {key: max(_ill_case(s, c)["needed"][key] for s, c in ILL_CASES) for key in hp_cases.C_ILL}
+    print("largest constants the restatement needs:", ", ".join(f"{k} {v:.4f}" for k, v in worst.items()))
+    for key, value in worst.items():
+        assert 0.75 * hp_cases.C_ILL[key] / 4 <= value <= hp_cases.C_ILL[key] / 4, (key, value)
+    shapes = [s for s in hp_cases.ILL_SHAPES if s[0] >= 6]
+    rejected = []
+    for shape in shapes:
+        c = _ill_case(shape, 1e8)
+        limits = hp_limits.ill_limits(c["ref"], c["old"]["kappa"], c["new"]["ratio"], shape[2], False)
+        if c["e_oracle"]["resp"] > limits["resp"]:
+            rejected.append(shape)
+    print(f"the oracle's responsibilities exceed the limit on {len(rejected)} of {len(shapes)} shapes: {rejected}")
+    assert 2 * len(rejected) >= len(shapes)
+    with pytest.raises(AssertionError):
+        c = _ill_case(rejected[0], 1e8)
+        hp_limits.check_ill("the oracle in a kernel's place", c["e_oracle"], c["ref"], c["old"]["kappa"], c["new"]["ratio"], rejected[0][2], False)
+
+
 # ---- the comparison helper ------------------------------------------------------------------------------------------------
 
 def test_comparison_helper_tells_a_lost_digit_from_rounding_noise():
@@ -587,3 +673,7 @@ if __name__ == "__main__":
             res = _oracle_case(*case, diagonal)
             print(("diag " if diagonal else "full ") + str(case), "%.1fs" % (time.time() - t),
                   " ".join(f"{k} {e:.1e} ({e / u:.3f})" for k, (e, u) in res.items()), flush=True)
+    for shape, cond in ILL_CASES:
+        print(_ill_line(shape, cond, _ill_case(shape, cond)), flush=True)
+    print("C_ILL / 4:", {k: v / 4 for k, v in hp_cases.C_ILL.items()}, "largest needed:",
+          {k: round(max(_ill_case(s, c)["needed"][k] for s, c in ILL_CASES), 4) for k in hp_cases.C_ILL})
