@@ -556,6 +556,12 @@ int mlhip_em_score_route(const mlhip_data* data, uint32_t K, int* kernel);
 enum { MLHIP_TIED_COMPOSED = 0, MLHIP_TIED_KERNEL = 1 };
 int mlhip_em_tied_route(const mlhip_data* data, uint32_t K, int* kernel);
 int mlhip_kmeans_route(const mlhip_data* data, uint32_t K, mlhip_kmeans_route_info* out);
+/* The screened E-step (MLHIP_ESTEP_SCREEN; full covariances, 12 <= d <= 32, K <= 64, unweighted blocks) is chosen pass by pass at
+ * launch. What the E-step passes of the fits on `data` did since the block was uploaded (diagnostic; tests assert the route a case
+ * takes), summed over the shards of a device group: counts[0] passes that ran screened, counts[1] passes of the screened kernel's
+ * domain that ran dense, counts[2] those among counts[1] that asked for the screened kernel and were sent back because a component's
+ * bound carried no information, counts[3] the candidates (pairs evaluated) of the last screened pass. Waits for the stream. */
+int mlhip_em_screen_counts(mlhip_ctx* ctx, mlhip_data* data, uint64_t counts[4]);
 
 #ifdef __cplusplus
 }

@@ -519,6 +519,13 @@ class Data:
         check(lib.mlhip_em_plan(self._h, C.c_uint32(K), C.byref(f)))
         return {"fused": bool(f.value & 1), "matrix_estep": bool(f.value & 2), "self_norm": bool(f.value & 4)}
 
+    def em_screen_counts(self):
+        """What the E-step passes of the fits on this block did (mlhip_em_screen_counts): {'screened', 'dense', 'no_information',
+        'candidates'} -> int; 'candidates' is the number of pairs the last screened pass evaluated."""
+        c = (C.c_uint64 * 4)()
+        check(lib.mlhip_em_screen_counts(self.ctx.handle, self._h, c))
+        return {"screened": int(c[0]), "dense": int(c[1]), "no_information": int(c[2]), "candidates": int(c[3])}
+
     def em_route(self, K, covariance_type="full"):
         """The whole route of an EM call of K components under the switches as they are set now (mlhip_em_route): a dict of
         the fields of mlhip_em_route_info, `estep` / `fused_form` by name, the flags as bool, `sparse` as None (by the call

@@ -81,6 +81,28 @@ int launch_em_estep_generic(const EstepArgs& a, hipStream_t stream);
 /// 4x4-block triangular variant (em_estep_mfma4.hip); params use the estep_mfma4_param_stride(D) record layout.
 int launch_em_estep_mfma4(const EstepArgs& a, int num_cus, hipStream_t stream);
 
+/// Screened E-step (em_estep_screen.hip; FOLD records, lw only, 12 <= D <= 32, K <= 64): rewrites the block lw that an earlier pass
+/// left, evaluating only the pairs the bound constants cannot prove zero. exact: padded_samples(n) words, bit k of word i = "lw[k][i]
+/// is an evaluated value" (read unless all_exact, always rewritten). consts: 4 doubles per component (em_screen_bound.hpp).
+struct ScreenArgs {
+    const double* xt; size_t ldx; uint32_t n; int D;
+    const double* params; int K;                            // the NEW records, estep_mfma4_param_stride(D) each
+    const double* shift;                                    // device, D doubles (zero-padded)
+    const double* consts;
+    double* lw; size_t ldr;
+    unsigned long long* exact; int all_exact;
+    unsigned long long* cand_count;                         // += candidates among the n rows (may be null)
+};
+bool em_estep_screen_supported(int D, int K);
+/// The shapes at which the runtime takes the screened pass by itself (measured faster than the dense kernel there).
+bool em_estep_screen_preferred(int D, int K);
+/// Returns the grid, or < 0 where the kernel is not instantiated.
+int launch_em_estep_screen(const ScreenArgs& a, int num_cus, hipStream_t stream);
+/// The constants of K components from the records the block belongs to and the new ones (both in FOLD form); *no_info += components
+/// whose bound carries no information.
+void launch_em_screen_constants(const double* rec_old, const double* rec_new, int K, int d, int D, double* consts,
+                                unsigned* no_info, hipStream_t stream);
+
 /// Scoring pass (em_score.hip; em_estep_mfma4.hip's SCORE form): per sample the log-sum-exp of the K log-densities-times-weights and
 /// the label argmax_k lw (first maximum wins; 0xffffffff where lse is NaN) -- no N x K block. Both outputs hold padded_samples(n)
 /// entries; either may be null.

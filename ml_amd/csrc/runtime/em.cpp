@@ -91,9 +91,67 @@ RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* 
 }
 
 
+/// Largest number of nonzero responsibilities (sparse statistics kernel) / candidates (screened E-step) per sample up to which the
+/// kernels whose cost grows with them are taken.
+constexpr double kSparseMaxPairs = 16.0;
+constexpr double kScreenMaxPairs = kSparseMaxPairs;
+
+
+/// Whether pass t of a fit -- an E-step pass of the screened kernel's domain, launch_estep -- is asked to run screened
+/// (em_estep_screen.hip). The block must be one the screened kernel may start from (EstepState::screenable: written by such a pass
+/// of this handle with this K and untouched since, its records in scr_rec). By call history: the sparse-statistics rule holds for
+/// pass t - 2 (the last whose counts every loop has in hand), and where pass t - 2 was itself screened it had at most
+/// kScreenMaxPairs candidates per sample -- and only at the shapes where the screened pass was measured faster
+/// (em_estep_screen_preferred). The route may force either (r.screen). The bound constants have the last word: launch_screened.
+static bool screen_wanted(const mlhip_data* dt, const EmRoute& r, int K)
+{
+    if (r.screen == 0 || !dt->estep.screenable) return false;
+    if (r.screen == 1) return true;
+    if (!em_estep_screen_preferred(dt->D, K)) return false;
+    if (dt->sn_K != K || dt->sn_calls < 2 || dt->scr_passes < 2) return false;
+    const unsigned long long nz = dt->nz_host.as<unsigned long long>()[(dt->sn_calls - 2) % 3];
+    if ((double)nz > kSparseMaxPairs * (double)dt->n) return false;
+    const int back = (int)((dt->scr_passes - 2) % 3);
+    if (dt->scr_was[back] && (double)dt->scr_host.as<unsigned long long>()[1 + back] > kScreenMaxPairs * (double)dt->n) return false;
+    return true;
+}
+
+
+/// The screened pass: the constants of the step from the block's records (scr_rec) to `a.params`, then -- when every component's
+/// bound carries information -- the screened kernel. Returns its grid, or 0 when the dense kernel has to run (the decision is the
+/// host's: it waits for the constants kernel's count, a few microseconds on a stream that has just been waited for).
+static int launch_screened(mlhip_data* dt, const EstepArgs& a, int K)
+{
+    mlhip_ctx* ctx = dt->ctx;
+    unsigned long long* dev = dt->scr_dev.as<unsigned long long>();
+    unsigned long long* host = dt->scr_host.as<unsigned long long>();
+    HIP_CHECK(hipMemsetAsync(dev, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    launch_em_screen_constants(dt->scr_rec.as<double>(), a.params, K, dt->d, dt->D, dt->scr_consts.as<double>(),
+                               reinterpret_cast<unsigned*>(dev), ctx->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    if (host[0] != 0) {
+        dt->scr_n_no_info++;
+        return 0;
+    }
+    ScreenArgs sa{};
+    sa.xt = a.xt; sa.ldx = a.ldx; sa.n = a.n; sa.D = a.D;
+    sa.params = a.params; sa.K = K; sa.shift = a.shift; sa.consts = dt->scr_consts.as<double>();
+    sa.lw = a.lw; sa.ldr = a.ldr;
+    sa.exact = dt->scr_exact.as<unsigned long long>(); sa.all_exact = dt->scr_all_exact ? 1 : 0;
+    sa.cand_count = dev + 1;
+    const int grid = launch_em_estep_screen(sa, ctx->num_cus, ctx->stream);
+    if (grid <= 0) throw Unsupported("screened E-step kernel not instantiated for this dimension");
+    HIP_CHECK(hipMemcpyAsync(host + 1 + dt->scr_passes % 3, dev + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    return grid;
+}
+
+
 /// E-step kernel on the records in params_dev: fills lw and -- unless the statistics kernel is going to normalise the
 /// log-responsibilities itself (`with_lse` false, matrix-core kernel only) -- lse and the log-likelihood partials.
-void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const DevBuf* records, int fold)
+/// This is the one place where a pass of a fit (`may_screen`) is routed to the dense or the screened kernel.
+void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const DevBuf* records, int fold, bool may_screen)
 {
     mlhip_ctx* ctx = dt->ctx;
     EstepArgs a{};
@@ -107,13 +165,46 @@ void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const 
     a.num_cus = ctx->num_cus;
     a.scratch = dt->partials.as<double>(); a.scratch_doubles = dt->partials.bytes / sizeof(double);   // (written by the statistics kernel AFTER the E-step, on the same stream)
     a.plain = r.estep == Estep::kPlain;
+    // the screened kernel's domain: the FOLD, lw-only matrix-core pass of an unweighted block where the sparse statistics kernel exists
+    const bool domain = may_screen && dt->estep.rec_layout == 2 && a.fold && !a.with_lse && !dt->weighted && r.estep == Estep::kMatrix4 &&
+                        em_estep_screen_supported(dt->D, K) && em_mstats_sparse_supported(dt->d, K, ctx->num_cus);
+    // ... and whether this pass may screen or leave a block a later pass may screen from: only then the state below is kept
+    const bool tracked = domain && (r.screen == 1 || (r.screen < 0 && em_estep_screen_preferred(dt->D, K)));
+    const size_t rec_bytes = sizeof(double) * estep_mfma4_param_stride(dt->D) * K;
+    if (tracked) {
+        if (dt->scr_K != K) {
+            dt->scr_K = K;
+            dt->scr_passes = 0;
+            dt->estep.screenable = false;
+        }
+        dt->scr_rec.reserve(rec_bytes);
+        dt->scr_exact.reserve(sizeof(unsigned long long) * dt->n_pad);
+        dt->scr_consts.reserve(sizeof(double) * 4 * K);
+        dt->scr_dev.reserve(2 * sizeof(unsigned long long));
+        dt->scr_host.reserve(4 * sizeof(unsigned long long));
+    }
     int grid = 0;
+    bool screened = false;
     ctx->timed("em_estep", [&] {
-        grid = dt->estep.rec_layout == 2 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
+        if (tracked && screen_wanted(dt, r, K)) {
+            grid = launch_screened(dt, a, K);
+            screened = grid > 0;
+        }
+        if (!screened)
+            grid = dt->estep.rec_layout == 2 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
     });
     if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
     HIP_CHECK(hipGetLastError());
     dt->estep.block_written(grid);
+    if (domain) (screened ? dt->scr_n_screened : dt->scr_n_dense)++;
+    if (tracked) {
+        // the block now belongs to these records: the next pass of the fit may start from it
+        HIP_CHECK(hipMemcpyAsync(dt->scr_rec.p, a.params, rec_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        dt->scr_all_exact = !screened;
+        dt->scr_was[dt->scr_passes % 3] = screened;
+        dt->scr_passes++;
+        dt->estep.block_screenable();
+    }
     if (dt->weighted && a.with_lse) {
         // the log-likelihood of a weighted block is sum_i w_i lse_i: its partials replace the E-step's, lse itself stays per row
         // (without lse the weighted self-normalising statistics pass finishes both: launch_em_reduce)
@@ -125,10 +216,11 @@ void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const 
 }
 
 
-void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs, bool with_lse)
+void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs, bool with_lse,
+               bool may_screen)
 {
     prepare_estep(dt, r, K, mixing, means, covs);
-    launch_estep(dt, r, K, with_lse);
+    launch_estep(dt, r, K, with_lse, nullptr, -1, may_screen);
 }
 
 
@@ -445,7 +537,6 @@ void run_diag_kernel(mlhip_data* dt, const EmRoute& r, int K, const double* shif
 /// sparse kernel exists).
 bool mstats_sparse_applies(mlhip_data* dt, const EmRoute& r, int K)
 {
-    constexpr double kSparseMaxPairs = 16.0;
     if (dt->sn_K != K) {
         dt->sn_K = K;
         dt->sn_calls = 0;
@@ -468,7 +559,7 @@ void em_step_full(mlhip_data* data, const EmRoute& r, int K, const double* mixin
     if (run_fused_step(data, r, K, mixing, means, covariances)) {
         tr.mark("fused E+M launch+sync+D2H");
     } else {
-        run_estep(data, r, K, mixing, means, covariances, !r.self_norm);
+        run_estep(data, r, K, mixing, means, covariances, !r.self_norm, true);
         tr.mark("params+launch E");
         run_mstats(data, r, K, r.self_norm ? kFromLogRespSelfNorm : kFromLogResp, nullptr, 0, true);
         tr.mark("M launch+sync+D2H");
@@ -948,6 +1039,28 @@ int mlhip_em_plan(const mlhip_data* data, uint32_t K, uint32_t* flags)
             if (r.self_norm) f |= MLHIP_PLAN_SELF_NORM;
         }
         *flags = f;
+    });
+}
+
+int mlhip_em_screen_counts(mlhip_ctx* ctx, mlhip_data* data, uint64_t counts[4])
+{
+    return guarded([&] {
+        require(ctx && data && counts, "null argument");
+        require(data->ctx == ctx, "data belongs to another context");
+        for (int j = 0; j < 4; ++j) counts[j] = 0;
+        auto add = [&](mlhip_data* dt) {
+            dt->ctx->use();
+            dt->ctx->sync();
+            counts[0] += dt->scr_n_screened; counts[1] += dt->scr_n_dense; counts[2] += dt->scr_n_no_info;
+            for (uint64_t back = 1; back <= 3 && back <= dt->scr_passes; ++back) {      // the newest screened pass among the last three
+                const int slot = (int)((dt->scr_passes - back) % 3);
+                if (!dt->scr_was[slot]) continue;
+                counts[3] += dt->scr_host.as<unsigned long long>()[1 + slot];
+                break;
+            }
+        };
+        if (data->parts.empty()) add(data);
+        else for (mlhip_data* part : data->parts) add(part);
     });
 }
 

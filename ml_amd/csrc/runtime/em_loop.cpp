@@ -101,7 +101,7 @@ struct EmLoop {
         } else if (fused) {
             launch_fused_step(data, route, K, false, rec[in]);
         } else {
-            launch_estep(data, route, K, !self_norm, rec[in], fold[in] ? 1 : 0);
+            launch_estep(data, route, K, !self_norm, rec[in], fold[in] ? 1 : 0, true);
             run_mstats(data, route, K, self_norm ? kFromLogRespSelfNorm : kFromLogResp, nullptr, 0, true, false);
         }
         ctx->reduce_in_place(data->stats_dev.as<double>(), data->stats_host.as<double>(), (size_t)K * F + 1);

@@ -445,15 +445,20 @@ struct EstepState {
         std::vector<double> covariance;                       // covariance_doubles(mode, K, d): the K x d variances / the one d x d covariance
     } kept;
 
-    void invalidate() { what = kNone; }
-    void block_written(int grid) { what = kBlock; n_ll = grid; }
+    // The block is one the screened E-step may start from (launch_estep): every entry an evaluated value or an upper bound of one, under
+    // the records kept in mlhip_data::scr_rec. Every member that changes what the block is clears it.
+    bool screenable = false;
+
+    void invalidate() { what = kNone; screenable = false; }
+    void block_written(int grid) { what = kBlock; n_ll = grid; screenable = false; }
+    void block_screenable() { screenable = what == kBlock; }
     /// A weighted block: the E-step's log-likelihood partials were replaced by `grid` partials of w_i lse_i (launch_estep).
     void ll_weighted(int grid) { n_ll = grid; }
-    void records_only(int grid) { what = kRecords; n_ll = grid; }
+    void records_only(int grid) { what = kRecords; n_ll = grid; screenable = false; }
     /// A one-kernel pass of `mode` (diagonal, tied) left its records and `grid` log-likelihood partials.
-    void mode_records_only(Covariance mode, int grid) { what = kModeRecords; kept.mode = mode; n_ll = grid; }
+    void mode_records_only(Covariance mode, int grid) { what = kModeRecords; kept.mode = mode; n_ll = grid; screenable = false; }
     /// A later (speculative) pass overwrote lw / lse; the records in params_dev still stand.
-    void block_overwritten() { if (what == kBlock) what = kRecords; }
+    void block_overwritten() { if (what == kBlock) what = kRecords; screenable = false; }
     /// The parameters behind the records of `mode` in params_dev (mlhip_em_iterate: set once, when the loop is over).
     void parameters(Covariance mode, int K, int d, const double* mixing, const double* means, const double* covariance)
     {
@@ -477,7 +482,7 @@ struct EstepState {
         Kept kept;
     };
     Small small() const { return Small{what == kBlock ? kRecords : what, rec_layout, rec_fold, n_ll, kept}; }
-    void put_back(const Small& s) { what = s.what; rec_layout = s.rec_layout; rec_fold = s.rec_fold; n_ll = s.n_ll; kept = s.kept; }
+    void put_back(const Small& s) { what = s.what; rec_layout = s.rec_layout; rec_fold = s.rec_fold; n_ll = s.n_ll; kept = s.kept; screenable = false; }
 
     bool on_device() const { return what != kNone; }
     bool needs_rebuild() const { return what == kRecords || what == kModeRecords; }
@@ -545,6 +550,19 @@ struct mlhip_data {
     PinnedBuf nz_host{&pool};
     uint64_t sn_calls = 0;
     int sn_K = 0;
+    // screened E-step (em.cpp launch_estep, em_estep_screen.hip), kept only for passes that may screen: scr_rec -- the records the
+    // N x K block belongs to (a copy: the ring of mlhip_em_iterate and params_dev move on); scr_exact -- one word per sample, bit k =
+    // "the stored value of component k is an evaluated one" (scr_all_exact: a dense pass wrote the block, the words are not read);
+    // scr_consts -- 4 doubles per component; scr_dev -- [components without information (32 bits), padding | candidates]; scr_host --
+    // its pinned copy: [0] the first word, [1 + t % 3] the candidates of tracked pass t. scr_was[t % 3]: whether tracked pass t ran
+    // screened (t counts the passes that kept this state with this K: scr_passes). The last three: mlhip_em_screen_counts.
+    DevBuf scr_rec{&pool}, scr_exact{&pool}, scr_consts{&pool}, scr_dev{&pool};
+    PinnedBuf scr_host{&pool};
+    bool scr_all_exact = true;
+    int scr_K = 0;
+    uint64_t scr_passes = 0;
+    bool scr_was[3] = {false, false, false};
+    uint64_t scr_n_screened = 0, scr_n_dense = 0, scr_n_no_info = 0;
     // K-means workspace
     DevBuf km_labels[2] = {DevBuf{&pool}, DevBuf{&pool}};
     DevBuf km_cent{&pool}, km_cent_next{&pool}, km_partials{&pool}, km_out{&pool}, km_mind{&pool}, km_probe{&pool}, km_scale{&pool},
@@ -620,6 +638,7 @@ struct EmRoute {
     int fused_form = kFusedLdsFeed;    // FusedArgs::form
     bool self_norm = false;            // the matrix-core E-step writes lw only, the statistics kernel normalises it
     int sparse = -1;                   // self-normalising statistics: 1 the sparse kernel, 0 the dense one, -1 by call history
+    int screen = -1;                   // E-step passes of a fit: 1 screened wherever the block allows, 0 dense, -1 by call history
     bool balanced = true;              // d <= 32: the wide statistics kernel deals balanced (column block, row block) units
     bool diag_exact = false;           // diagonal mode: the exact density form always
     bool diag_kernel = false;          // diagonal mode: the one-kernel iteration (em_diag.hip), else the full-covariance kernels
@@ -749,10 +768,13 @@ RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* 
 /// log-responsibilities itself (`with_lse` false, matrix-core kernel only) -- lse and the log-likelihood partials.
 /// `records` / `fold`: another record buffer than params_dev and its form (mlhip_em_iterate keeps a ring of them); default: params_dev
 /// and its form.
-void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse = true, const DevBuf* records = nullptr, int fold = -1);
+/// `may_screen`: a pass of a fit (mlhip_em_step, mlhip_em_iterate) -- the only ones that may take the screened kernel instead
+/// (em_estep_screen.hip; the rule is launch_estep's); rebuilds for labels / responsibilities, scoring, conditioning and restarts never do.
+void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse = true, const DevBuf* records = nullptr, int fold = -1,
+                  bool may_screen = false);
 
 void run_estep(mlhip_data* dt, const EmRoute& r, int K, const double* mixing, const double* means, const double* covs,
-               bool with_lse = true);
+               bool with_lse = true, bool may_screen = false);
 
 /// After a fused step only lse exists on the device; whoever needs the log-responsibility block (labels,
 /// responsibilities, a separate M-step, the refinement pass) gets it rebuilt from the same parameter records.

@@ -24,6 +24,7 @@ struct Switches {
     bool estep_rows;            // off under MLHIP_ESTEP_ORDER=column
     bool fold, self_norm, balanced, fused, diag_ab, big_dim, device_close, records, resident;   // on unless "0"
     int sparse, sfeed;          // MLHIP_MSTATS_SPARSE, MLHIP_FUSED_SFEED: 0 / 1 forced, -1 automatic
+    int screen;                 // MLHIP_ESTEP_SCREEN: 0 / 1 forced, -1 automatic
     int fused_valu;             // MLHIP_FUSED_VALU: 0 never, 2 wherever built, -1 by shape
     int kmeans;                 // MLHIP_KMEANS=valu / mfma: kKmDirect / kKmMatrix forced, -1 automatic
     bool score_composed;        // MLHIP_SCORE=composed
@@ -56,6 +57,7 @@ Switches read_switches()
     s.resident = env_char("MLHIP_RESIDENT") != '0';
     s.sparse = env_force("MLHIP_MSTATS_SPARSE");
     s.sfeed = env_force("MLHIP_FUSED_SFEED");
+    s.screen = env_force("MLHIP_ESTEP_SCREEN");
     const char valu = env_char("MLHIP_FUSED_VALU");
     s.fused_valu = valu == '0' ? 0 : valu == '2' ? 2 : -1;
     const char km = env_char("MLHIP_KMEANS");
@@ -127,6 +129,7 @@ EmRoute em_route(const mlhip_data* data, int K, Covariance mode)
     r.self_norm = !diag_kernel && !r.fused && sw.self_norm && !sw.estep_valu && r.estep == Estep::kMatrix4 &&
                   em_mstats_self_norm_supported(d, K, ctx->num_cus);
     r.sparse = weighted ? 0 : sw.sparse;
+    r.screen = weighted ? 0 : sw.screen;
     r.balanced = sw.balanced;
     r.diag_exact = !sw.diag_ab;
     r.device_close = sw.device_close && em_close_supported(d) && (!diag || diag_kernel);
