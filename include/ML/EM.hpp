@@ -156,6 +156,22 @@ public:
     @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
     DLL_DECLSPEC MatrixXd conditional_means(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed,
                                             double* log_densities = nullptr) const;
+    /** Extension: the covariances Sigma_k,M|O of the conditioned components, K matrices of (number of missing coordinates)^2, the
+    missing coordinates in ascending order (mlhip_em_condition_covariances; host only, no device). `observed` as for conditional_means.
+    @throw std::invalid_argument If the model has not been fitted or for bad coordinates.
+    @throw std::domain_error If the observed block of a covariance, or a conditioned covariance, is not positive definite. */
+    DLL_DECLSPEC std::vector<MatrixXd> conditional_covariances(const std::vector<unsigned int>& observed) const;
+    /** Extension (multiple imputation, predictive intervals): `n_draws` draws from p(x_M | x_O) under the fitted mixture for every
+    column of `data_observed`, on the device. Arguments as for conditional_means. Returns (number of missing coordinates) x
+    (n_draws * data.cols()): draw q of point i in column q * data.cols() + i. `labels`, if given, receives n_draws * data.cols()
+    components, in the same order. Draw q of point i is a pure function of (seed, i, q), the point's observed coordinates and the
+    parameters (mlhip_em_conditional_samples holds the definition): it does not depend on the row batches or the device group, and a
+    seed shared with sample() shares no random word with it. The model and its random engine are not changed.
+    @throw std::invalid_argument As conditional_means, or if n_draws < 0 or n_draws > 2^32 - 1.
+    @throw std::domain_error If the observed block of a covariance, or a conditioned covariance, is not positive definite.
+    @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
+    DLL_DECLSPEC MatrixXd conditional_samples(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, Index n_draws,
+                                              std::uint64_t seed = 0, std::vector<unsigned int>* labels = nullptr) const;
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }
     /** Extension: number of E-M iterations the last fit() ran. */

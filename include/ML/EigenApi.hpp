@@ -22,6 +22,7 @@
 
 #include <Eigen/Core>
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <random>
@@ -407,6 +408,45 @@ public:
         static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
         detail::check(mlpp_em_conditional_means(h_, reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(observed.size()),
                                                 block.p, static_cast<uint64_t>(data_observed.cols()), out.data(), log_densities));
+        return out;
+    }
+    /** Extension (ML/EM.hpp): the covariances of the conditioned components, K matrices of (number of missing coordinates)^2. Host only.
+    @throw std::invalid_argument If the model has not been fitted or for bad coordinates.
+    @throw std::domain_error If a block is not positive definite. */
+    std::vector<Eigen::MatrixXd> conditional_covariances(const std::vector<unsigned int>& observed) const
+    {
+        const Eigen::Index d = means_.rows(), dO = static_cast<Eigen::Index>(observed.size()), missing = d > dO ? d - dO : 0;
+        const Eigen::Index K = means_.cols();
+        std::vector<double> flat(static_cast<std::size_t>(K * missing * missing) + 1);
+        static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+        detail::check(mlpp_em_conditional_covariances(h_, reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(observed.size()),
+                                                      flat.data()));
+        std::vector<Eigen::MatrixXd> out;
+        for (Eigen::Index k = 0; k < K; ++k) {
+            Eigen::MatrixXd c(missing, missing);
+            std::copy_n(flat.data() + k * missing * missing, missing * missing, c.data());
+            out.push_back(c);
+        }
+        return out;
+    }
+    /** Extension (ML/EM.hpp): `n_draws` draws from p(x_M | x_O) under the fitted mixture for every column of `data_observed`; returns
+    (number of missing coordinates) x (n_draws * data_observed.cols()), draw q of point i in column q * data_observed.cols() + i.
+    `labels`, if given, receives the components drawn, in the same order.
+    @throw std::invalid_argument As conditional_means, or if n_draws < 0 or n_draws > 2^32 - 1.
+    @throw std::domain_error If a block is not positive definite. */
+    Eigen::MatrixXd conditional_samples(const std::vector<unsigned int>& observed, Eigen::Ref<const Eigen::MatrixXd> data_observed,
+                                        Eigen::Index n_draws, std::uint64_t seed = 0, std::vector<unsigned int>* labels = nullptr) const
+    {
+        if (data_observed.rows() != static_cast<Eigen::Index>(observed.size())) throw std::invalid_argument("Wrong data size");
+        if (n_draws < 0) throw std::invalid_argument("EM: n_draws must be 0 .. 2^32 - 1");
+        const Eigen::Index missing = means_.rows() > data_observed.rows() ? means_.rows() - data_observed.rows() : 0;
+        const detail::Block block(data_observed);
+        Eigen::MatrixXd out(missing, n_draws * data_observed.cols());
+        if (labels) labels->assign(static_cast<std::size_t>(n_draws * data_observed.cols()), 0u);
+        static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+        detail::check(mlpp_em_conditional_samples(h_, reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(observed.size()),
+                                                  block.p, static_cast<uint64_t>(data_observed.cols()), static_cast<uint64_t>(n_draws), seed,
+                                                  out.data(), labels ? reinterpret_cast<uint32_t*>(labels->data()) : nullptr));
         return out;
     }
     const std::vector<unsigned int>& labels() const override { return labels_; }

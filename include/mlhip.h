@@ -384,6 +384,50 @@ int mlhip_em_conditional_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uin
 enum { MLHIP_CONDITION_REGISTERS = 0, MLHIP_CONDITION_PLAIN = 1 };
 int mlhip_em_condition_route(const mlhip_data* data, uint32_t K, uint32_t dM, int* kernel);
 
+/* EXTENSION (multiple imputation, predictive intervals; not in the reference surface): the covariances of the conditioned
+ * components. Host helper, no GPU needed; d, K, covariance_type, covariances, observed, n_observed as in mlhip_em_condition, whose
+ * argument checks are made here too, before any work. Per component k, with L L^T = Sigma_k,OO (the factor mlhip_em_condition uses)
+ * and Y = L^-1 Sigma_k,OM (its forward substitution):
+ *   covariances_missing  K x dM x dM             C_k = Sigma_k,M|O = Sigma_k,MM - Y^T Y; entry (a, b), b <= a, is Sigma_k[M_a][M_b] less
+ *                                                Y[l][a] Y[l][b] for ascending l, and (b, a) a copy of it: symmetric by construction
+ *   factors              K x dM x dM, row-major  G_k = the lower Cholesky factor of C_k (mlhip_cholesky_lower's), row j, column c at
+ *                                                j dM + c, +0.0 above the diagonal; may be NULL
+ * Diagonal input gives C_k = diag(sigma^2_M) and G_k = diag(sqrt(sigma^2_M)) exactly, tied input K copies with equal bits.
+ * MLHIP_E_DOMAIN when a Sigma_k,OO or a C_k is not positive definite. */
+int mlhip_em_condition_covariances(uint32_t d, uint32_t K, int covariance_type, const double* covariances, const uint32_t* observed,
+                                   uint32_t n_observed, double* covariances_missing, double* factors);
+/* Draws from p(x_M | x_O) for every row of `data`, a resident block of the OBSERVED coordinates (its d is dO), under the conditioned
+ * mixture of mlhip_em_condition (mixing: the K weights of the joint model) and the factors G_k of mlhip_em_condition_covariances,
+ * for the draws q = first_draw .. first_draw + n_draws - 1. Row i below is the row's GLOBAL index: first_row + its index in the block.
+ *   Responsibilities  r_k = exp(lw_k - lse) from the marginal mixture's exact E-step, the values mlhip_em_conditional_means weights with.
+ *   Label             Philox4x32-10 as in mlhip_em_sample, the same key, counter (i lo, i hi, 0, 1 + q); u = U(w0, w1); s_k the
+ *                     sequential fp64 prefix sums of r_k for ascending k, S = s_{K-1}; label = the smallest k with u S < s_k (one
+ *                     fp64 product); if there is none, the largest k with r_k != 0. A component with r_k = 0 has s_k = s_{k-1} and
+ *                     is never drawn. A row whose S is a NaN gives a NaN in every coordinate and the label 0xFFFFFFFF.
+ *   Normals           counter (i lo, i hi, 1 + p, 1 + q), p = 0 .. ceil(dM / 2) - 1; Box-Muller exactly as in mlhip_em_sample gives
+ *                     zeta_0 .. zeta_{dM-1}.
+ *   Row               with k = label: z_c = x_c - mu_k,O[c]; t_j = mu_k,M[j], t_j = fma(A_k[j][c], z_c, t_j) for ascending c (the
+ *                     chain of mlhip_em_conditional_means); then t_j = fma(G_k[j][c], zeta_c, t_j) for c = 0 .. j; x~_j = t_j.
+ * The fourth counter word is 1 + q and never 0, the word of mlhip_em_sample: data generated with a seed and imputed with the same
+ * seed share no random word. Hence first_draw + n_draws <= 2^32 - 1. Row (i, q) is a pure function of (seed, i, q), the row's x_O
+ * and the parameters: the grid, the chunks (those of mlhip_em_conditional_means: whole 256-row tiles, MLHIP_CONDITION_ROWS=rows
+ * overrides; the draws go through in groups so that a chunk's scratch keeps that call's bound), the row's place in the block, how a
+ * call is split over first_row or first_draw, the shards of a device group (each draws for its own rows under their global indices,
+ * no collective) and the kernel tier change no bit.
+ * out: n_draws blocks of rows x dM, draw-major, a row `ld_out` >= dM doubles after the one before and a block rows x ld_out doubles
+ * after the one before, host memory. labels (n_draws x rows, may be NULL): the component every row was drawn from. Row weights are
+ * ignored, as in scoring; nothing the handle holds is changed. n = 0 or n_draws = 0 succeeds and writes nothing. */
+int mlhip_em_conditional_samples(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t dM, const double* mixing,
+                                 const double* means_observed, const double* covariances_observed, const double* maps,
+                                 const double* means_missing, const double* factors, uint64_t seed, uint64_t first_row,
+                                 uint32_t first_draw, uint32_t n_draws, double* out, int64_t ld_out, uint32_t* labels);
+/* Which kernel mlhip_em_conditional_samples runs behind the E-step for dM missing coordinates on this block (diagnostic, nothing is
+ * launched), under the switches as they are set now: the tiers of mlhip_em_condition_route. MLHIP_CONDITION_REGISTERS (dO <= 32 and
+ * dM <= 32): lane = row, x_O, the chain and the normals in registers, maps and factor fed as scalar operands, only the components
+ * some row of a wave drew are run, the wave's 64 x dM tile staged through LDS into contiguous 16-byte stores; MLHIP_CONDITION_PLAIN
+ * (else, up to dO + dM = 4096, and everywhere under MLHIP_CONDITION=plain): thread = row, table from global memory; same bits. */
+int mlhip_em_conditional_sample_route(const mlhip_data* data, uint32_t K, uint32_t dM, int* kernel);
+
 /* (X - mean)(X - mean)^T / (N - 1) over ALL ranks' samples (EM::calculate_sample_covariance,
  * ML/EM.cpp:265-272). mean may be NULL. */
 int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance);

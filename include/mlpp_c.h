@@ -101,6 +101,14 @@ int mlpp_em_sample(const mlpp_em* h, uint64_t n, uint64_t seed, double* x_out, u
  * n = 0 writes nothing. */
 int mlpp_em_conditional_means(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
                               double* out, double* log_density_out);
+/* Extension: EM::conditional_covariances -- the covariances of the conditioned components (mlhip_em_condition_covariances; host
+ * only). out: K x dM x dM, dM = d - n_observed. */
+int mlpp_em_conditional_covariances(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, double* out);
+/* Extension: EM::conditional_samples -- n_draws draws from p(x_M | x_O) under the fitted mixture for n points
+ * (mlhip_em_conditional_samples). observed, data_observed as for mlpp_em_conditional_means; out: n_draws x n x (d - n_observed)
+ * row-major, draw-major; labels_out (n_draws x n, the components drawn) may be NULL. n = 0 or n_draws = 0 writes nothing. */
+int mlpp_em_conditional_samples(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                                uint64_t n_draws, uint64_t seed, double* out, uint32_t* labels_out);
 
 /* ---- KMeans (cppyml/clustering.cpp:148-183) ---- */
 int mlpp_kmeans_create(uint32_t number_clusters, mlpp_kmeans** out);

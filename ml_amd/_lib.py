@@ -595,6 +595,38 @@ class Data:
         check(lib.mlhip_em_condition_route(self._h, C.c_uint32(K), C.c_uint32(dM), C.byref(k)))
         return ("registers", "plain")[k.value]
 
+    def em_conditional_samples(self, mixing, means_observed, covs_observed, maps, means_missing, factors, n_draws=1, seed=0, first_row=0,
+                               first_draw=0, labels=False):
+        """Draws from p(x_M | x_O) for every row of this block of OBSERVED coordinates under the conditioned mixture em_condition and
+        em_condition_covariances return (mlhip_em_conditional_samples): n_draws x n x dM C-contiguous float64, and with labels=True
+        also the n_draws x n components drawn (uint32). factors: K x dM x dM lower Cholesky factors; first_row: the global index of
+        the block's row 0; the draws are first_draw .. first_draw + n_draws - 1. Nothing the handle holds is changed."""
+        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
+        means_observed = np.ascontiguousarray(means_observed, dtype=np.float64)
+        covs_observed = np.ascontiguousarray(covs_observed, dtype=np.float64)
+        maps = np.ascontiguousarray(maps, dtype=np.float64)
+        means_missing = np.ascontiguousarray(means_missing, dtype=np.float64)
+        factors = np.ascontiguousarray(factors, dtype=np.float64)
+        K, dM = means_missing.shape
+        assert mixing.shape == (K,) and means_observed.shape == (K, self.d) and covs_observed.shape == (K, self.d, self.d)
+        assert maps.shape == (K, dM, self.d) and factors.shape == (K, dM, dM)
+        if n_draws < 0 or first_draw < 0 or first_draw + n_draws > 2 ** 32 - 1:
+            raise ValueError("the draws must lie in 0 .. 2^32 - 2")
+        out = np.empty((n_draws, self.n, dM))
+        lab = np.empty((n_draws, self.n), dtype=np.uint32) if labels else None
+        check(lib.mlhip_em_conditional_samples(self.ctx.handle, self._h, C.c_uint32(K), C.c_uint32(dM), dptr(mixing), dptr(means_observed),
+                                               dptr(covs_observed), dptr(maps), dptr(means_missing), dptr(factors), C.c_uint64(int(seed)),
+                                               C.c_uint64(int(first_row)), C.c_uint32(int(first_draw)), C.c_uint32(int(n_draws)), dptr(out),
+                                               C.c_int64(dM), u32ptr(lab) if labels else None))
+        return (out, lab) if labels else out
+
+    def em_conditional_sample_route(self, K, dM):
+        """The kernel mlhip_em_conditional_samples runs for dM missing coordinates on this block under the switches as they are set
+        now (mlhip_em_conditional_sample_route): 'registers' | 'plain'."""
+        k = C.c_int()
+        check(lib.mlhip_em_conditional_sample_route(self._h, C.c_uint32(K), C.c_uint32(dM), C.byref(k)))
+        return ("registers", "plain")[k.value]
+
     def em_expectation(self, mixing, means, covs):
         K = len(mixing)
         mixing = np.ascontiguousarray(mixing, dtype=np.float64)
@@ -769,6 +801,27 @@ def em_condition(means, covs, observed, diagonal=False, tied=False):
     check(lib.mlhip_em_condition(C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(means), dptr(covs), u32ptr(observed),
                                  C.c_uint32(dO), dptr(mu_o), dptr(S_oo), dptr(A), dptr(mu_m)))
     return mu_o, S_oo, A, mu_m
+
+
+def em_condition_covariances(covs, observed, diagonal=False, tied=False, K=None):
+    """The covariances of the components of a mixture conditioned on the coordinates `observed` and their lower Cholesky factors
+    (mlhip_em_condition_covariances, no GPU): (covariances_missing K x dM x dM, factors K x dM x dM, zero above the diagonal), the
+    missing coordinates in ascending order. covs as for em_condition (tied=True: the one d x d matrix, and K components). ValueError for
+    bad coordinates or a block that is not positive definite."""
+    covs = np.ascontiguousarray(covs, dtype=np.float64)
+    assert not (diagonal and tied)
+    if tied:
+        assert covs.ndim == 2 and covs.shape[0] == covs.shape[1] and K is not None
+        d = covs.shape[0]
+    else:
+        assert covs.ndim == (2 if diagonal else 3) and (diagonal or covs.shape[1] == covs.shape[2])
+        K, d = covs.shape[0], covs.shape[1]
+    observed = np.ascontiguousarray(observed, dtype=np.uint32).ravel()
+    dM = max(d - len(observed), 0)
+    C_m, G = np.empty((K, dM, dM)), np.empty((K, dM, dM))
+    check(lib.mlhip_em_condition_covariances(C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(covs), u32ptr(observed),
+                                             C.c_uint32(len(observed)), dptr(C_m), dptr(G)))
+    return C_m, G
 
 
 def em_sample_route(d, K):

@@ -7,7 +7,7 @@ Conventions kept from the reference:
   * `EM.means` is `d x K` (NOT transposed, clustering.cpp:126), `KMeans.centroids` is `K x d` (clustering.cpp:66-69,172);
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
-Extensions (not in the reference surface): `EM.conditional_mean`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
+Extensions (not in the reference surface): `EM.conditional_mean`, `EM.conditional_sample`, `EM.conditional_covariances`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
 `KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`, `EM.set_number_initialisations`,
 `EM.number_initialisations`, `EM.best_initialisation`, `EM.initialisation_log_likelihoods`, `EM.initialisation_steps`,
@@ -388,6 +388,25 @@ class EM:
         _check(_l.mlpp_em_sample(self._h, C.c_uint64(n), C.c_uint64(int(seed)), _dp(X), _lib.u32ptr(labels)))
         return X, labels
 
+    def _observed(self, observed, name):
+        """The checks of `observed` that conditional_mean, conditional_sample and conditional_covariances share -> (coordinates, d)."""
+        try:
+            coordinates = [int(c) for c in observed]
+        except TypeError:
+            raise TypeError(name + "(): observed must be a sequence of coordinate indices") from None
+        if any(c != o for c, o in zip(coordinates, observed)):
+            raise TypeError(name + "(): observed must hold integers")
+        d, _ = self._dims()
+        if d == 0:
+            raise ValueError(name + "(): the model has not been fitted")
+        if not 1 <= len(coordinates) <= d - 1:
+            raise ValueError(name + "(): between 1 and d - 1 coordinates must be observed")
+        if min(coordinates) < 0 or max(coordinates) >= d:
+            raise ValueError(name + "(): observed coordinate out of range")
+        if len(set(coordinates)) != len(coordinates):
+            raise ValueError(name + "(): observed coordinate given twice")
+        return coordinates, d
+
     def conditional_mean(self, X_observed, observed, return_log_density=False):
         """Extension (Gaussian-mixture regression, imputation): E[x_M | x_O] under the fitted mixture for every row of X_observed, on
         the GPU. `observed`: distinct coordinate indices in any order, at least one and not all of them; column c of X_observed
@@ -395,21 +414,7 @@ class EM:
         C-contiguous float64 array, the missing coordinates in ascending order -- with return_log_density=True a pair of it and the N
         log-densities of the rows under the marginal mixture. TypeError / ValueError before any device work."""
         X = _require_data(X_observed)
-        try:
-            coordinates = [int(c) for c in observed]
-        except TypeError:
-            raise TypeError("conditional_mean(): observed must be a sequence of coordinate indices") from None
-        if any(c != o for c, o in zip(coordinates, observed)):
-            raise TypeError("conditional_mean(): observed must hold integers")
-        d, _ = self._dims()
-        if d == 0:
-            raise ValueError("conditional_mean(): the model has not been fitted")
-        if not 1 <= len(coordinates) <= d - 1:
-            raise ValueError("conditional_mean(): between 1 and d - 1 coordinates must be observed")
-        if min(coordinates) < 0 or max(coordinates) >= d:
-            raise ValueError("conditional_mean(): observed coordinate out of range")
-        if len(set(coordinates)) != len(coordinates):
-            raise ValueError("conditional_mean(): observed coordinate given twice")
+        coordinates, d = self._observed(observed, "conditional_mean")
         n, columns = X.shape
         if columns != len(coordinates):
             raise ValueError("conditional_mean(): X_observed must have one column per observed coordinate")
@@ -419,6 +424,44 @@ class EM:
         _check(_l.mlpp_em_conditional_means(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n), _dp(out),
                                             _dp(dens) if return_log_density else None))
         return (out, dens) if return_log_density else out
+
+    def conditional_covariances(self, observed):
+        """Extension: the covariances of the conditioned components, Sigma_k,M|O = Sigma_k,MM - Sigma_k,MO Sigma_k,OO^-1 Sigma_k,OM, as a
+        (K, dM, dM) float64 array, the missing coordinates in ascending order. `observed` as for conditional_mean. Host only: no GPU."""
+        coordinates, d = self._observed(observed, "conditional_covariances")
+        index = np.array(coordinates, dtype=np.uint32)
+        dM = d - len(coordinates)
+        out = np.empty((self.number_components, dM, dM))
+        _check(_l.mlpp_em_conditional_covariances(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(out)))
+        return out
+
+    def conditional_sample(self, X_observed, observed, n_draws=1, seed=0, return_labels=False):
+        """Extension (multiple imputation, predictive intervals): n_draws draws from p(x_M | x_O) under the fitted mixture for every
+        row of X_observed, on the GPU. X_observed and `observed` as for conditional_mean. Returns an (n_draws, N, d - len(observed))
+        C-contiguous float64 array, the missing coordinates in ascending order -- with return_labels=True a pair of it and the
+        (n_draws, N) uint32 components the rows were drawn from. Draw q of row i is a pure function of (seed, i, q), the row and the
+        parameters; a seed shared with `sample` shares no random number with it, and the model's own random engine is not touched.
+        TypeError / ValueError before any device work."""
+        X = _require_data(X_observed)
+        coordinates, d = self._observed(observed, "conditional_sample")
+        n, columns = X.shape
+        if columns != len(coordinates):
+            raise ValueError("conditional_sample(): X_observed must have one column per observed coordinate")
+        if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)):
+            raise TypeError("conditional_sample(): n_draws must be an integer")
+        if n_draws < 0 or n_draws > 2 ** 32 - 1:
+            raise ValueError("conditional_sample(): n_draws must lie in 0 .. 2^32 - 1")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+            raise TypeError("conditional_sample(): seed must be an integer")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("conditional_sample(): seed must lie in 0 .. 2^64 - 1")
+        index = np.array(coordinates, dtype=np.uint32)
+        out = np.empty((int(n_draws), n, d - len(coordinates)))
+        labels = np.empty((int(n_draws), n), dtype=np.uint32) if return_labels else None
+        _check(_l.mlpp_em_conditional_samples(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n),
+                                              C.c_uint64(int(n_draws)), C.c_uint64(int(seed)), _dp(out),
+                                              _lib.u32ptr(labels) if return_labels else None))
+        return (out, labels) if return_labels else out
 
     @property
     def labels(self):

@@ -171,6 +171,30 @@ inline size_t condition_record_doubles(int kernel, int dO, int dM)
 /// Returns the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
 int launch_em_condition(const ConditionArgs& a, int num_cus, hipStream_t stream);
 
+/// Conditional draws (em_condition_sample.hip): x_M | x_O of the n rows of a chunk for the draws first_draw .. first_draw + n_draws - 1,
+/// from the same lw / lse as the conditioning pass. Row (i, q) is a pure function of (seed, first_row + i, q), the row and the
+/// parameters. The tiers and paddings are ConditionKernel's and condition_pad's; the record is the conditioning pass's with the
+/// factor behind it: [mu_O | mu_M | A^T | G, the lower triangle packed row by row: (j, c) at j (j+1)/2 + c, for the PADDED dM].
+struct ConditionSampleArgs {
+    const double* xt; size_t ldx; uint32_t n;                // the observed coordinates, feature-major
+    int dO, dM, K;
+    const double* lw; size_t ldr; const double* lse;         // K x ldr log-responsibilities and their log-sum-exp
+    const double* table;                                     // K records of condition_sample_record_doubles(kernel, dO, dM)
+    uint64_t seed, first_row;                                // first_row: the global index of the chunk's row 0
+    uint32_t first_draw, n_draws;                            // (first_draw + n_draws <= 2^32 - 1: draw q is generator stream 1 + q)
+    double* out; size_t ldq;                                 // n_draws blocks of n x dM (row-major), ldq doubles apart: even, 16-byte aligned
+    uint32_t* labels;                                        // n_draws x n, or null
+    int kernel;                                              // ConditionKernel
+};
+constexpr uint32_t kConditionSampleNoLabel = 0xFFFFFFFFu;    // the label of a row whose shares do not sum to a number
+inline size_t condition_sample_record_doubles(int kernel, int dO, int dM)
+{
+    const size_t pm = (size_t)condition_pad(kernel, dM);
+    return condition_record_doubles(kernel, dO, dM) + pm * (pm + 1) / 2;
+}
+/// Returns the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
+int launch_em_condition_sample(const ConditionSampleArgs& a, int num_cus, hipStream_t stream);
+
 enum MstatsMode : int {
     kFromLogResp = 0,  // r = exp(lw - lse)          (after an E-step)
     kFromResp = 1,      // r = lw                     (plain responsibilities: caller-given, one-hot, or all ones)

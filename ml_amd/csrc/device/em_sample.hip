@@ -10,8 +10,10 @@
 //                                      j = d-1 down, the wave's 64 x d tile through LDS (odd row stride: conflict-free writes) and out
 //                                      as contiguous 16 bytes per lane. L_k / mu_k per lane from LDS (LdsTable) or global memory.
 //   em_sample_plain_kernel             64 < d <= 4096: the normals go to the output row, the product runs there in place.
+// The generator: philox.hpp, on its stream 0.
 // Table: [L of component 0 .. (packed lower triangle, row by row: (j, c) at j (j+1)/2 + c) | mu (K x d)]; a tied model holds ONE L.
 #include "device.hpp"
+#include "philox.hpp"
 
 namespace mlhip {
 namespace {
@@ -19,52 +21,13 @@ namespace {
 constexpr int kSampleLdsBytes = 64 * 1024;       // what one workgroup takes at most (as every kernel of this library)
 constexpr uint32_t kSampleLdsThresholds = 2048;  // K up to which the label thresholds sit in LDS
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&w)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
-/// (((hi 2^32 + lo) >> 12) + 1/2) 2^-52: every step exact in fp64, strictly inside (0, 1).
-__device__ __forceinline__ double unit_uniform(uint32_t lo, uint32_t hi)
-{
-    const uint64_t v = (((uint64_t)hi << 32) | lo) >> 12;
-    return ((double)v + 0.5) * 0x1p-52;
-}
-
 /// Row i's component: block 0 against the thresholds (ascending, so the count is the first k with u < t_k).
 __device__ __forceinline__ uint32_t draw_label(uint64_t i, uint64_t seed, const double* thresholds, uint32_t K)
 {
-    uint32_t w[4];
-    philox4x32_10((uint32_t)i, (uint32_t)(i >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    const double u = unit_uniform(w[0], w[1]);
+    const double u = draw_uniform(i, seed, 0u);
     uint32_t label = 0;
     while (label + 1 < K && u >= thresholds[label]) ++label;
     return label;
-}
-
-/// Normals z_2p, z_2p+1 of row i.
-__device__ __forceinline__ void draw_pair(uint64_t i, uint64_t seed, uint32_t p, double& z0, double& z1)
-{
-    uint32_t w[4];
-    philox4x32_10((uint32_t)i, (uint32_t)(i >> 32), 1u + p, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    const double u1 = unit_uniform(w[0], w[1]), u2 = unit_uniform(w[2], w[3]);
-    const double r = sqrt(-2.0 * log(u1));
-    double s, c;
-    sincospi(2.0 * u2, &s, &c);
-    z0 = r * c;
-    z1 = r * s;
 }
 
 template <int DP, int W, bool LdsTable>
@@ -98,7 +61,7 @@ __global__ __launch_bounds__(64 * W) void em_sample_kernel(SampleArgs a)
         double z[DP + 1];
 #pragma unroll
         for (int p = 0; p < (DP + 1) / 2; ++p)
-            if (2 * p < d) draw_pair(i, a.seed, (uint32_t)p, z[2 * p], z[2 * p + 1]);
+            if (2 * p < d) draw_pair(i, a.seed, (uint32_t)p, 0u, z[2 * p], z[2 * p + 1]);
 
         const double* Lk;
         const double* mu;
@@ -159,7 +122,7 @@ __global__ __launch_bounds__(256) void em_sample_plain_kernel(SampleArgs a)
         double* row = a.x + local * (uint64_t)d;
         for (int p = 0; 2 * p < d; ++p) {
             double z0, z1;
-            draw_pair(i, a.seed, (uint32_t)p, z0, z1);
+            draw_pair(i, a.seed, (uint32_t)p, 0u, z0, z1);
             row[2 * p] = z0;
             if (2 * p + 1 < d) row[2 * p + 1] = z1;
         }

@@ -471,5 +471,62 @@ void condition(Covariance mode, int K, int d, const double* means, const double*
     }
 }
 
+void condition_covariances(Covariance mode, int K, int d, const double* covariance, const unsigned int* observed, int n_observed,
+                           double* covariances_missing, double* factors)
+{
+    const int dO = n_observed, dM = d - n_observed;
+    const std::size_t dd = (std::size_t)d * d, oo = (std::size_t)dO * dO, mm = (std::size_t)dM * dM;
+    std::vector<char> is_observed(d, 0);
+    for (int c = 0; c < dO; ++c) is_observed[observed[c]] = 1;
+    std::vector<unsigned int> missing;
+    for (int j = 0; j < d; ++j)
+        if (!is_observed[j]) missing.push_back((unsigned int)j);
+    // (the tied matrix is conditioned once: its K results are copies, equal bit for bit)
+    const int factored = mode == Covariance::Tied ? 1 : K;
+    std::vector<double> full(dd), Soo(oo), L(oo), Y((std::size_t)dO * dM), G(mm);
+    for (int k = 0; k < factored; ++k) {
+        covariances_as_full(mode, 1, d, covariance + (mode == Covariance::Diagonal ? (std::size_t)k * d : (std::size_t)k * dd), full.data());
+        for (int b = 0; b < dO; ++b)
+            for (int a = 0; a < dO; ++a) Soo[(std::size_t)b * dO + a] = full[(std::size_t)observed[b] * d + observed[a]];
+        cholesky_lower(dO, Soo.data(), L.data());
+        for (int c = 0; c < dO; ++c)
+            for (int i = c; i < dO; ++i) {
+                const double v = L[(std::size_t)c * dO + i];
+                if (!std::isfinite(v) || (i == c && !(v > 0))) throw std::domain_error("observed covariance block is not positive definite");
+            }
+        // Y = L^-1 Sigma_OM, column j by the forward substitution of condition()
+        for (int j = 0; j < dM; ++j) {
+            const double* s = full.data() + (std::size_t)missing[j] * d;
+            for (int i = 0; i < dO; ++i) {
+                double t = s[observed[i]];
+                for (int l = 0; l < i; ++l) t -= L[(std::size_t)l * dO + i] * Y[(std::size_t)l * dM + j];
+                Y[(std::size_t)i * dM + j] = t / L[(std::size_t)i * dO + i];
+            }
+        }
+        // C = Sigma_MM - Y^T Y: the lower triangle, l ascending, mirrored -- symmetric by construction
+        double* C = covariances_missing + (std::size_t)k * mm;
+        for (int a = 0; a < dM; ++a)
+            for (int b = 0; b <= a; ++b) {
+                double t = full[(std::size_t)missing[b] * d + missing[a]];
+                for (int l = 0; l < dO; ++l) t -= Y[(std::size_t)l * dM + a] * Y[(std::size_t)l * dM + b];
+                C[(std::size_t)a * dM + b] = t;
+                C[(std::size_t)b * dM + a] = t;
+            }
+        cholesky_lower(dM, C, G.data());
+        for (int c = 0; c < dM; ++c)
+            for (int j = c; j < dM; ++j) {
+                const double v = G[(std::size_t)c * dM + j];
+                if (!std::isfinite(v) || (j == c && !(v > 0))) throw std::domain_error("conditioned covariance is not positive definite");
+            }
+        if (factors)
+            for (int j = 0; j < dM; ++j)
+                for (int c = 0; c < dM; ++c) factors[(std::size_t)k * mm + (std::size_t)j * dM + c] = G[(std::size_t)c * dM + j];
+    }
+    for (int k = factored; k < K; ++k) {
+        std::copy(covariances_missing, covariances_missing + mm, covariances_missing + (std::size_t)k * mm);
+        if (factors) std::copy(factors, factors + mm, factors + (std::size_t)k * mm);
+    }
+}
+
 }  // namespace host
 }  // namespace mlhip

@@ -88,6 +88,15 @@ void covariances_from_full(Covariance mode, int K, int d, const double* mixing, 
 void condition(Covariance mode, int K, int d, const double* means, const double* covariance, const unsigned int* observed, int n_observed,
                double* means_observed, double* covariances_observed, double* maps, double* means_missing);
 
+/// The covariances of the conditioned components (mlhip_em_condition_covariances, mlhip.h), `observed` as for condition(). Per
+/// component, with L = cholesky_lower(Sigma_k,OO) (condition()'s factor) and Y = L^-1 Sigma_k,OM (its forward substitution):
+///   covariances_missing[k] = C_k = Sigma_k,MM - Y^T Y (dM x dM; entry (a, b), b <= a: t = Sigma[M_a][M_b], t -= Y[l][a] Y[l][b] for
+///   ascending l; mirrored, so symmetric by construction); factors[k] = G_k = cholesky_lower(C_k), row-major (row j, column c at
+///   j dM + c), +0.0 above the diagonal; `factors` may be null. A diagonal gives C_k = diag(sigma^2_M) and G_k = diag(sqrt) exactly,
+/// the tied matrix K copies. std::domain_error when a Sigma_k,OO or a C_k is not positive definite.
+void condition_covariances(Covariance mode, int K, int d, const double* covariance, const unsigned int* observed, int n_observed,
+                           double* covariances_missing, double* factors);
+
 /// Tells the host-side math how many ranks share this node, so that the OpenMP teams of the per-component
 /// factorizations together stay within the host's cores (MLHIP_HOST_THREADS overrides the per-rank thread count).
 void set_host_ranks(int local_ranks);

@@ -557,11 +557,10 @@ MatrixXd EM::sample(Index n, std::uint64_t seed, std::vector<unsigned int>* labe
     return out;
 }
 
-MatrixXd EM::conditional_means(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, double* log_densities) const
+namespace {
+/// The checks of `observed` that the conditional calls share, against the model's dimension d (> 0).
+void check_observed(const std::vector<unsigned int>& observed, Index d)
 {
-    const Index d = means().rows();
-    // (the order of sample: that there is a shape, the arguments against it, the device, the decompositions)
-    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
     if (observed.empty() || static_cast<Index>(observed.size()) >= d)
         throw std::invalid_argument("EM: between 1 and d - 1 coordinates must be observed");
     std::vector<char> seen(static_cast<std::size_t>(d), 0);
@@ -570,6 +569,15 @@ MatrixXd EM::conditional_means(const std::vector<unsigned int>& observed, ConstM
         if (seen[c]) throw std::invalid_argument("EM: observed coordinate given twice");
         seen[c] = 1;
     }
+}
+}  // namespace
+
+MatrixXd EM::conditional_means(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, double* log_densities) const
+{
+    const Index d = means().rows();
+    // (the order of sample: that there is a shape, the arguments against it, the device, the decompositions)
+    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    check_observed(observed, d);
     const Index d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed, n = data_observed.cols();
     if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
     require_fitted();
@@ -593,6 +601,80 @@ MatrixXd EM::conditional_means(const std::vector<unsigned int>& observed, ConstM
         check(mlhip_em_conditional_means(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
                                          covariances_observed.data(), maps.data(), means_missing.data(), out.col(first), d_missing,
                                          log_densities ? log_densities + first : nullptr));
+    }
+    return out;
+}
+
+std::vector<MatrixXd> EM::conditional_covariances(const std::vector<unsigned int>& observed) const
+{
+    const Index d = means().rows();
+    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    check_observed(observed, d);
+    require_fitted();
+    const unsigned int K = number_components_;
+    const Index d_missing = d - static_cast<Index>(observed.size());
+    const std::vector<double> cov_flat = flat_covariances();
+    std::vector<double> flat(static_cast<std::size_t>(K * d_missing * d_missing));
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+    check(mlhip_em_condition_covariances(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, cov_flat.data(),
+                                         reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(observed.size()),
+                                         flat.data(), nullptr));
+    std::vector<MatrixXd> out;
+    for (unsigned int k = 0; k < K; ++k) {
+        MatrixXd c(d_missing, d_missing);
+        std::copy_n(flat.data() + static_cast<std::size_t>(k) * d_missing * d_missing, d_missing * d_missing, c.data());   // (symmetric)
+        out.push_back(std::move(c));
+    }
+    return out;
+}
+
+MatrixXd EM::conditional_samples(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, Index n_draws, std::uint64_t seed,
+                                 std::vector<unsigned int>* labels) const
+{
+    const Index d = means().rows();
+    // (the order of conditional_means: that there is a shape, the arguments against it, the device, the decompositions)
+    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    check_observed(observed, d);
+    const Index d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed, n = data_observed.cols();
+    if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
+    if (n_draws < 0 || static_cast<std::uint64_t>(n_draws) > 0xFFFFFFFFull) throw std::invalid_argument("EM: n_draws must be 0 .. 2^32 - 1");
+    require_fitted();
+    const unsigned int K = number_components_;
+    const std::vector<double> cov_flat = flat_covariances();
+    std::vector<double> means_observed(static_cast<std::size_t>(K * d_observed)), covariances_observed(static_cast<std::size_t>(K * d_observed * d_observed)),
+        maps(static_cast<std::size_t>(K * d_missing * d_observed)), means_missing(static_cast<std::size_t>(K * d_missing)),
+        covariances_missing(static_cast<std::size_t>(K * d_missing * d_missing)), factors(static_cast<std::size_t>(K * d_missing * d_missing));
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+    const uint32_t* coordinates = reinterpret_cast<const uint32_t*>(observed.data());
+    check(mlhip_em_condition(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, means_.data(), cov_flat.data(), coordinates,
+                             static_cast<uint32_t>(d_observed), means_observed.data(), covariances_observed.data(), maps.data(),
+                             means_missing.data()));
+    check(mlhip_em_condition_covariances(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, cov_flat.data(), coordinates,
+                                         static_cast<uint32_t>(d_observed), covariances_missing.data(), factors.data()));
+    MatrixXd out(d_missing, n_draws * n);
+    if (labels) labels->assign(static_cast<std::size_t>(n_draws * n), 0u);
+    if (!n || !n_draws) return out;
+    mlhip_ctx* ctx = device::context();
+    const Index batch = Clustering::detail::score_batch_rows();
+    std::vector<double> block;                                   // (a batch's draws lie batch rows apart, the result's n: one copy per draw)
+    std::vector<uint32_t> block_labels;
+    for (Index first = 0; first < n; first += batch) {
+        const Index rows = std::min(batch, n - first);
+        DataGuard dev;
+        check(mlhip_data_upload(ctx, data_observed.col(first), static_cast<uint32_t>(d_observed), static_cast<uint64_t>(rows),
+                                data_observed.outerStride(), &dev.h));
+        const bool whole = rows == n;                          // (one batch: the call writes the result in place)
+        if (!whole) block.resize(static_cast<std::size_t>(n_draws * rows * d_missing));
+        if (!whole && labels) block_labels.resize(static_cast<std::size_t>(n_draws * rows));
+        check(mlhip_em_conditional_samples(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
+                                           covariances_observed.data(), maps.data(), means_missing.data(), factors.data(), seed,
+                                           static_cast<uint64_t>(first), 0u, static_cast<uint32_t>(n_draws), whole ? out.data() : block.data(),
+                                           d_missing, !labels ? nullptr : whole ? labels->data() : block_labels.data()));
+        if (whole) break;
+        for (Index q = 0; q < n_draws; ++q) {
+            std::copy_n(block.data() + static_cast<std::size_t>(q * rows * d_missing), rows * d_missing, out.col(q * n + first));
+            if (labels) std::copy_n(block_labels.data() + static_cast<std::size_t>(q * rows), rows, labels->data() + q * n + first);
+        }
     }
     return out;
 }

@@ -233,6 +233,34 @@ int mlpp_em_conditional_means(const mlpp_em* h, const uint32_t* observed, uint32
         std::copy_n(y.data(), y.size(), out);
     });
 }
+int mlpp_em_conditional_covariances(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, double* out)
+{
+    return guarded([&] {
+        need(h);
+        if (n_observed) need(observed);
+        need(out);
+        const std::vector<unsigned int> coordinates(observed, observed + n_observed);
+        for (const MatrixXd& c : h->em.conditional_covariances(coordinates)) out = std::copy_n(c.data(), c.size(), out);
+    });
+}
+int mlpp_em_conditional_samples(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                                uint64_t n_draws, uint64_t seed, double* out, uint32_t* labels_out)
+{
+    return guarded([&] {
+        need(h);
+        if (n_observed) need(observed);
+        if (n && n_observed) need(data_observed);
+        if (n && n_observed && n_draws) need(out);
+        if (n > static_cast<uint64_t>(std::numeric_limits<Index>::max())) throw std::invalid_argument("EM: Too many samples");
+        if (n_draws > 0xFFFFFFFFull) throw std::invalid_argument("EM: n_draws must be 0 .. 2^32 - 1");
+        const std::vector<unsigned int> coordinates(observed, observed + n_observed);
+        std::vector<unsigned int> labels;
+        const MatrixXd x = h->em.conditional_samples(coordinates, ConstMatrixRef(data_observed, n_observed, static_cast<Index>(n), n_observed),
+                                                     static_cast<Index>(n_draws), seed, labels_out ? &labels : nullptr);
+        std::copy_n(x.data(), x.size(), out);
+        if (labels_out) std::copy(labels.begin(), labels.end(), labels_out);
+    });
+}
 int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out)
 {
     return guarded([&] {

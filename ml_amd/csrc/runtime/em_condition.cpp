@@ -6,16 +6,15 @@
 #include "internal.hpp"
 
 namespace mlhip_rt {
-namespace {
 
-/// The kernel's table on the host: K records [mu_O | mu_M | A^T] in the paddings of `kernel` (device.hpp condition_pad): +0.0, and
-/// -0.0 in the rows of A^T beyond dO.
-std::vector<double> build_table(int kernel, int K, int dO, int dM, const double* means_observed, const double* maps, const double* means_missing)
+std::vector<double> condition_table(int kernel, int K, int dO, int dM, const double* means_observed, const double* maps,
+                                    const double* means_missing, const double* factors)
 {
     const size_t po = (size_t)condition_pad(kernel, dO), pm = (size_t)condition_pad(kernel, dM), ps = condition_record_doubles(kernel, dO, dM);
-    std::vector<double> table(ps * K, 0.0);
+    const size_t stride = factors ? condition_sample_record_doubles(kernel, dO, dM) : ps;
+    std::vector<double> table(stride * K, 0.0);
     for (int k = 0; k < K; ++k) {
-        double* rec = table.data() + ps * k;
+        double* rec = table.data() + stride * k;
         std::copy_n(means_observed + (size_t)k * dO, dO, rec);
         std::copy_n(means_missing + (size_t)k * dM, dM, rec + po);
         const double* A = maps + (size_t)k * dM * dO;
@@ -23,9 +22,31 @@ std::vector<double> build_table(int kernel, int K, int dO, int dM, const double*
             for (int j = 0; j < dM; ++j) rec[po + pm + (size_t)c * pm + j] = A[(size_t)j * dO + c];
         // (a padded coordinate's term is fma(-0.0, +0.0, t) = t for every t, a t of -0.0 included: device/em_condition.hip)
         std::fill(rec + po + pm + (size_t)dO * pm, rec + ps, -0.0);
+        if (!factors) continue;
+        const double* G = factors + (size_t)k * dM * dM;
+        for (int j = 0; j < dM; ++j)
+            for (int c = 0; c <= j; ++c) rec[ps + (size_t)j * (j + 1) / 2 + c] = G[(size_t)j * dM + c];
     }
     return table;
 }
+
+Covariance check_condition_arguments(uint32_t d, uint32_t K, int covariance_type, const uint32_t* observed, uint32_t n_observed)
+{
+    require(K >= 1, "At least one component required");
+    require(d >= 1 && d <= (uint32_t)kGenericMaxDim, "the dimension must be 1 .. 4096");
+    const Covariance mode = covariance_from_abi(covariance_type);
+    require(n_observed >= 1 && n_observed < d, "between 1 and d - 1 coordinates must be observed");
+    std::vector<char> seen(d, 0);
+    for (uint32_t c = 0; c < n_observed; ++c) {
+        require(observed[c] < d, "observed coordinate out of range");
+        require(!seen[observed[c]], "observed coordinate given twice");
+        seen[observed[c]] = 1;
+    }
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+    return mode;
+}
+
+namespace {
 
 void em_conditional_means(mlhip_data* dt, int K, int dM, const double* mixing, const double* means_observed, const double* covs_observed,
                           const double* maps, const double* means_missing, double* out, int64_t ld_out, double* log_density)
@@ -39,7 +60,7 @@ void em_conditional_means(mlhip_data* dt, int K, int dM, const double* mixing, c
     DevBuf records{&dt->pool}, work{&dt->pool}, table{&dt->pool}, lw{&dt->pool}, lse{&dt->pool}, ll{&dt->pool}, y{&dt->pool};
     PinnedBuf staging{&dt->pool};
     build_records(dt, r.em, K, mixing, means_observed, covs_observed, false, records, staging, work);   // (always the exact form: no FOLD)
-    const std::vector<double> host_table = build_table(r.kernel, K, dO, dM, means_observed, maps, means_missing);
+    const std::vector<double> host_table = condition_table(r.kernel, K, dO, dM, means_observed, maps, means_missing, nullptr);
     table.reserve(sizeof(double) * host_table.size());
     HIP_CHECK(hipMemcpyAsync(table.p, host_table.data(), sizeof(double) * host_table.size(), hipMemcpyHostToDevice, ctx->stream));
     lw.reserve(sizeof(double) * (size_t)chunk * K);
@@ -96,17 +117,7 @@ int mlhip_em_condition(uint32_t d, uint32_t K, int covariance_type, const double
 {
     return guarded([&] {
         require(means && covariances && observed && means_observed && covariances_observed && maps && means_missing, "null argument");
-        require(K >= 1, "At least one component required");
-        require(d >= 1 && d <= (uint32_t)kGenericMaxDim, "the dimension must be 1 .. 4096");
-        const Covariance mode = covariance_from_abi(covariance_type);
-        require(n_observed >= 1 && n_observed < d, "between 1 and d - 1 coordinates must be observed");
-        std::vector<char> seen(d, 0);
-        for (uint32_t c = 0; c < n_observed; ++c) {
-            require(observed[c] < d, "observed coordinate out of range");
-            require(!seen[observed[c]], "observed coordinate given twice");
-            seen[observed[c]] = 1;
-        }
-        static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+        const Covariance mode = check_condition_arguments(d, K, covariance_type, observed, n_observed);
         try {
             host::condition(mode, (int)K, (int)d, means, covariances, observed, (int)n_observed, means_observed, covariances_observed, maps,
                             means_missing);

@@ -699,6 +699,24 @@ struct ConditionRoute {
     bool skip = true;
 };
 ConditionRoute condition_route(const mlhip_data* data, int K, int dM);
+/// mlhip_em_conditional_samples: condition_route's E-step tier and kernel tier (the same switches), and the rows per chunk sized so
+/// that the K log-responsibilities and the output of min(n_draws, kConditionSampleDraws) draws per row stay within kScoreScratchBytes
+/// (MLHIP_CONDITION_ROWS=n overrides, rounded UP to whole tiles). `draws`: how many draws one launch behind a chunk's E-step takes --
+/// as many of n_draws as fit the same bound beside the chunk's log-responsibilities, at least 1. No row depends on either.
+constexpr uint32_t kConditionSampleDraws = 8;
+struct ConditionSampleRoute {
+    EmRoute em;
+    int kernel = kConditionRegisters;
+    uint32_t chunk_rows = 0, draws = 1;
+};
+ConditionSampleRoute condition_sample_route(const mlhip_data* data, int K, int dM, uint32_t n_draws);
+/// The conditioning kernels' table on the host: K records [mu_O | mu_M | A^T] in the paddings of `kernel` (device.hpp condition_pad):
+/// +0.0, and -0.0 in the rows of A^T beyond dO. With `factors` (K x dM x dM row-major lower factors; mlhip_em_conditional_samples) every
+/// record carries its factor behind it, the lower triangle packed row by row in the padded dM (condition_sample_record_doubles).
+std::vector<double> condition_table(int kernel, int K, int dO, int dM, const double* means_observed, const double* maps,
+                                    const double* means_missing, const double* factors);
+/// The argument checks of mlhip_em_condition and mlhip_em_condition_covariances behind their null checks; returns the covariance mode.
+Covariance check_condition_arguments(uint32_t d, uint32_t K, int covariance_type, const uint32_t* observed, uint32_t n_observed);
 
 /// mlhip_em_iterate_restarts: R loops one after the other (every shape and mode), or BATCHED -- the restarts still running share the
 /// three launches of an iteration (em_restarts.hip) -- where the solo iteration is the fused kernel in its vector-unit form on at

@@ -174,6 +174,25 @@ ConditionRoute condition_route(const mlhip_data* data, int K, int dM)
     return r;
 }
 
+ConditionSampleRoute condition_sample_route(const mlhip_data* data, int K, int dM, uint32_t n_draws)
+{
+    const Switches sw = read_switches();
+    ConditionSampleRoute r;
+    r.em = em_route(data, K, Covariance::Full);
+    r.kernel = sw.condition_plain ? kConditionPlain : em_condition_route(data->d, dM);
+    const uint64_t tile = kSampleTile, budget = kScoreScratchBytes / sizeof(double);
+    const uint64_t sized_for = std::max<uint64_t>(1, std::min<uint64_t>(n_draws, kConditionSampleDraws));
+    uint64_t rows = sw.condition_rows > 0 ? (uint64_t)sw.condition_rows : budget / ((uint64_t)K + sized_for * (uint64_t)dM);
+    rows = sw.condition_rows > 0 ? (rows + tile - 1) / tile * tile : rows / tile * tile;
+    if (rows < tile) rows = tile;
+    if (rows > data->n_pad) rows = data->n_pad;
+    r.chunk_rows = (uint32_t)rows;
+    const uint64_t per_row = budget / rows;
+    const uint64_t fit = per_row > (uint64_t)K ? (per_row - (uint64_t)K) / (uint64_t)dM : 0;
+    r.draws = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fit, n_draws));
+    return r;
+}
+
 ModeRoute mode_route(const mlhip_data* data, int K, Covariance mode)
 {
     ModeRoute r;
