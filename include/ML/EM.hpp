@@ -172,6 +172,18 @@ public:
     @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
     DLL_DECLSPEC MatrixXd conditional_samples(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, Index n_draws,
                                               std::uint64_t seed = 0, std::vector<unsigned int>* labels = nullptr) const;
+    /** Extension (error bars on an imputed value, heteroscedastic regression bands): the predictive covariance Var[x_M | x_O] =
+    sum_k r_k (Sigma_k,M|O + (t_k - y)(t_k - y)^T) of every column of `data_observed` under the fitted mixture, on the device; t_k the
+    component predictions, r_k the marginal responsibilities, y = conditional_means. Arguments as for conditional_means. Returns
+    (number of missing coordinates) x data.cols(), the variances of point i in column i -- with `full_covariance` (dM * dM) x
+    data.cols(), column i holding the (symmetric) matrix of point i, whose diagonal has the bits of the default form. `means`, if
+    given, receives conditional_means' result, bit for bit. The definition and its fixed evaluation order:
+    mlhip_em_conditional_variances. The result does not depend on the row batches or the device group; the model is not changed.
+    @throw std::invalid_argument As conditional_means.
+    @throw std::domain_error If the observed block of a covariance, or a conditioned covariance, is not positive definite.
+    @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
+    DLL_DECLSPEC MatrixXd conditional_variances(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed,
+                                                bool full_covariance = false, MatrixXd* means = nullptr) const;
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }
     /** Extension: number of E-M iterations the last fit() ran. */

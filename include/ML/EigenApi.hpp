@@ -449,6 +449,25 @@ public:
                                                   out.data(), labels ? reinterpret_cast<uint32_t*>(labels->data()) : nullptr));
         return out;
     }
+    /** Extension (ML/EM.hpp): the predictive covariance Var[x_M | x_O] of every column of `data_observed` under the fitted mixture;
+    returns (number of missing coordinates) x data_observed.cols(), or with `full_covariance` its square x data_observed.cols(), column
+    i holding the matrix of point i. `means`, if given, receives conditional_means' result.
+    @throw std::invalid_argument As conditional_means.
+    @throw std::domain_error If a block is not positive definite. */
+    Eigen::MatrixXd conditional_variances(const std::vector<unsigned int>& observed, Eigen::Ref<const Eigen::MatrixXd> data_observed,
+                                          bool full_covariance = false, Eigen::MatrixXd* means = nullptr) const
+    {
+        if (data_observed.rows() != static_cast<Eigen::Index>(observed.size())) throw std::invalid_argument("Wrong data size");
+        const Eigen::Index missing = means_.rows() > data_observed.rows() ? means_.rows() - data_observed.rows() : 0;
+        const detail::Block block(data_observed);
+        Eigen::MatrixXd out(full_covariance ? missing * missing : missing, data_observed.cols());
+        if (means) means->resize(missing, data_observed.cols());
+        static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+        detail::check(mlpp_em_conditional_variances(h_, reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(observed.size()),
+                                                    block.p, static_cast<uint64_t>(data_observed.cols()), full_covariance ? 1 : 0, out.data(),
+                                                    means ? means->data() : nullptr));
+        return out;
+    }
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }
 

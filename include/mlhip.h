@@ -428,6 +428,46 @@ int mlhip_em_conditional_samples(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, u
  * (else, up to dO + dM = 4096, and everywhere under MLHIP_CONDITION=plain): thread = row, table from global memory; same bits. */
 int mlhip_em_conditional_sample_route(const mlhip_data* data, uint32_t K, uint32_t dM, int* kernel);
 
+/* EXTENSION (error bars on an imputed value, heteroscedastic regression bands; not in the reference surface): the PER-ROW predictive
+ * covariance Var[x_M | x_O] for every row of `data`, a resident block of the OBSERVED coordinates (its d is dO), under the conditioned
+ * mixture of mlhip_em_condition (mixing: the K weights of the joint model) and covariances_missing = the C_k of
+ * mlhip_em_condition_covariances (K x dM x dM; only the lower triangle and the diagonal are read):
+ *     Var[x_M | x_O] = sum_k r_k (C_k + (t_k - y)(t_k - y)^T),   t_k = mu_k,M + A_k (x_O - mu_k,O),   y = sum_k r_k t_k.
+ * Per row, on every tier, with r_k = exp(lw_k - lse) from the marginal mixture's exact E-step (the values, the chunks and the switches
+ * of mlhip_em_conditional_means), in this fixed order:
+ *   Pass 1  steps 1 - 4 of mlhip_em_conditional_means unchanged: z_c = x_c - mu_k,O[c]; t_j = mu_k,M[j], t_j = fma(A_k[j][c], z_c, t_j)
+ *           for ascending c; y_j = +0.0, y_j = fma(r_k, t_j, y_j) for ascending k over the components with r_k != 0. y_j has the bits
+ *           mlhip_em_conditional_means gives.
+ *   Pass 2  for ascending k, ONLY where r_k != 0: t_j by the same chain (the same bits as in pass 1); u_j = t_j - y_j; then
+ *             diagonal form (full = 0)  s_j = fma(u_j, u_j, C_k[j][j]);           v_j  = fma(r_k, s_j, v_j),  from v_j  = +0.0;
+ *             full form     (full = 1)  s = fma(u_a, u_b, C_k[a][b]) for b <= a;  V_ab = fma(r_k, s, V_ab),   from V_ab = +0.0;
+ *                                       V_ba is a copy of V_ab.
+ * Consequences: the diagonal of the full form has the bits of the diagonal form; the full form is exactly symmetric; the centred sum
+ * cannot go below zero on the diagonal (it does not cancel the way sum_k r_k (C_k + t_k t_k^T) - y y^T does); a component with r_k = 0
+ * leaves v as it is, as step 4 of the mean does, so the kernels' wave-level skip changes no bit (MLHIP_CONDITION_SKIP=0: same bits).
+ * sum_k r_k is whatever the E-step gives: NOTHING IS RENORMALISED, in y or in v. A row's result is a pure function of the row and the
+ * parameters: the chunks (whole 256-row tiles sized for the K log-responsibilities plus this call's outputs per row;
+ * MLHIP_CONDITION_ROWS=rows overrides), the row's place in the block, a prefix of a longer block, the shards of a device group (each
+ * conditions its own rows, no collective), the skip and the kernel tier change no bit.
+ * variances: rows x dM doubles, or with full = 1 rows x dM*dM (row i holds V row-major), a row `ld_variances` >= dM (dM*dM) doubles
+ * after the one before, host memory. means_out (rows x dM, `ld_means` >= dM apart; may be NULL) and log_density (rows; may be NULL)
+ * carry the bits of mlhip_em_conditional_means' out and log_density. Row weights are ignored, as in scoring; nothing the handle holds
+ * is changed (the call's own device scratch is at least 256 rows of K + its outputs per row: dM * dM doubles a row in the full form).
+ * n = 0 succeeds and writes nothing. MLHIP_E_INVALID_ARGUMENT, before any device work: null pointers, K = 0, dM = 0, dO + dM > 4096,
+ * full other than 0 / 1, a leading dimension below its row. */
+int mlhip_em_conditional_variances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t dM, const double* mixing,
+                                   const double* means_observed, const double* covariances_observed, const double* maps,
+                                   const double* means_missing, const double* covariances_missing, int full, double* variances,
+                                   int64_t ld_variances, double* means_out, int64_t ld_means, double* log_density);
+/* Which kernel mlhip_em_conditional_variances runs behind the E-step for dM missing coordinates on this block in the form asked for
+ * (diagnostic, nothing is launched), under the switches as they are set now. MLHIP_CONDITION_REGISTERS: lane = row, x_O, t, y and the
+ * accumulators in registers, mu, A and C fed as scalar operands, the wave's output staged through LDS into contiguous 16-byte stores
+ * -- the diagonal form at dO <= 32 and dM <= 32, the full form at dO <= 32 up to the largest dM whose dM (dM + 1) / 2 accumulators the
+ * compiler keeps in registers without scratch (this function is where that bound is read; profiles/condition_variance_registers.txt
+ * holds the report). MLHIP_CONDITION_PLAIN (else, up to dO + dM = 4096, and everywhere under MLHIP_CONDITION=plain): thread = row, the
+ * output row is the accumulator, table from global memory; same bits. */
+int mlhip_em_condition_variance_route(const mlhip_data* data, uint32_t K, uint32_t dM, int full, int* kernel);
+
 /* (X - mean)(X - mean)^T / (N - 1) over ALL ranks' samples (EM::calculate_sample_covariance,
  * ML/EM.cpp:265-272). mean may be NULL. */
 int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance);

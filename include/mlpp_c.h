@@ -109,6 +109,12 @@ int mlpp_em_conditional_covariances(const mlpp_em* h, const uint32_t* observed, 
  * row-major, draw-major; labels_out (n_draws x n, the components drawn) may be NULL. n = 0 or n_draws = 0 writes nothing. */
 int mlpp_em_conditional_samples(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
                                 uint64_t n_draws, uint64_t seed, double* out, uint32_t* labels_out);
+/* Extension: EM::conditional_variances -- the per-row predictive covariance Var[x_M | x_O] under the fitted mixture for n points
+ * (mlhip_em_conditional_variances). observed, data_observed as for mlpp_em_conditional_means; out: n x dM row-major, dM =
+ * d - n_observed, or with full != 0 n x dM x dM (the matrix of point i in row i); means_out (n x dM, the bits of
+ * mlpp_em_conditional_means) may be NULL. n = 0 writes nothing. */
+int mlpp_em_conditional_variances(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                                  int full, double* out, double* means_out);
 
 /* ---- KMeans (cppyml/clustering.cpp:148-183) ---- */
 int mlpp_kmeans_create(uint32_t number_clusters, mlpp_kmeans** out);

@@ -824,6 +824,41 @@ def em_condition_covariances(covs, observed, diagonal=False, tied=False, K=None)
     return C_m, G
 
 
+def em_conditional_variances(data, mixing, means_observed, covs_observed, maps, means_missing, covs_missing, full=False, means=False,
+                             log_density=False):
+    """Var[x_M | x_O] for every row of `data`, a Data block of OBSERVED coordinates, under the conditioned mixture em_condition and
+    em_condition_covariances return (mlhip_em_conditional_variances): n x dM C-contiguous float64, or n x dM x dM with full=True. With
+    means=True and / or log_density=True a tuple of it, E[x_M | x_O] (n x dM) and the n log-densities of the rows under the marginal
+    mixture, in that order -- the bits of Data.em_conditional_means. covs_missing: K x dM x dM, the other parameters as for
+    Data.em_conditional_means. A function of the module, not a method of Data; nothing the handle holds is changed."""
+    mixing = np.ascontiguousarray(mixing, dtype=np.float64)
+    means_observed = np.ascontiguousarray(means_observed, dtype=np.float64)
+    covs_observed = np.ascontiguousarray(covs_observed, dtype=np.float64)
+    maps = np.ascontiguousarray(maps, dtype=np.float64)
+    means_missing = np.ascontiguousarray(means_missing, dtype=np.float64)
+    covs_missing = np.ascontiguousarray(covs_missing, dtype=np.float64)
+    K, dM = means_missing.shape
+    assert mixing.shape == (K,) and means_observed.shape == (K, data.d) and covs_observed.shape == (K, data.d, data.d)
+    assert maps.shape == (K, dM, data.d) and covs_missing.shape == (K, dM, dM)
+    out = np.empty((data.n, dM, dM) if full else (data.n, dM))
+    y = np.empty((data.n, dM)) if means else None
+    dens = np.empty(data.n) if log_density else None
+    check(lib.mlhip_em_conditional_variances(data.ctx.handle, data._h, C.c_uint32(K), C.c_uint32(dM), dptr(mixing), dptr(means_observed),
+                                             dptr(covs_observed), dptr(maps), dptr(means_missing), dptr(covs_missing), C.c_int(int(bool(full))),
+                                             dptr(out), C.c_int64(dM * dM if full else dM), dptr(y) if means else None, C.c_int64(dM),
+                                             dptr(dens) if log_density else None))
+    extra = ([y] if means else []) + ([dens] if log_density else [])
+    return (out, *extra) if extra else out
+
+
+def em_condition_variance_route(data, K, dM, full=False):
+    """The kernel mlhip_em_conditional_variances runs for dM missing coordinates on the Data block `data` in the form asked for, under
+    the switches as they are set now (mlhip_em_condition_variance_route): 'registers' | 'plain'."""
+    k = C.c_int()
+    check(lib.mlhip_em_condition_variance_route(data._h, C.c_uint32(K), C.c_uint32(dM), C.c_int(int(bool(full))), C.byref(k)))
+    return ("registers", "plain")[k.value]
+
+
 def em_sample_route(d, K):
     """The kernel the sampling calls run for K components in d dimensions under the switches as they are set now
     (mlhip_em_sample_route): 'lds_table' | 'global_table' | 'plain'."""

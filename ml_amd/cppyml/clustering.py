@@ -7,7 +7,7 @@ Conventions kept from the reference:
   * `EM.means` is `d x K` (NOT transposed, clustering.cpp:126), `KMeans.centroids` is `K x d` (clustering.cpp:66-69,172);
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
-Extensions (not in the reference surface): `EM.conditional_mean`, `EM.conditional_sample`, `EM.conditional_covariances`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
+Extensions (not in the reference surface): `EM.conditional_mean`, `EM.conditional_variance`, `EM.conditional_sample`, `EM.conditional_covariances`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
 `KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`, `EM.set_number_initialisations`,
 `EM.number_initialisations`, `EM.best_initialisation`, `EM.initialisation_log_likelihoods`, `EM.initialisation_steps`,
@@ -389,7 +389,7 @@ class EM:
         return X, labels
 
     def _observed(self, observed, name):
-        """The checks of `observed` that conditional_mean, conditional_sample and conditional_covariances share -> (coordinates, d)."""
+        """The checks of `observed` that conditional_mean, conditional_variance, conditional_sample and conditional_covariances share -> (coordinates, d)."""
         try:
             coordinates = [int(c) for c in observed]
         except TypeError:
@@ -424,6 +424,26 @@ class EM:
         _check(_l.mlpp_em_conditional_means(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n), _dp(out),
                                             _dp(dens) if return_log_density else None))
         return (out, dens) if return_log_density else out
+
+    def conditional_variance(self, X_observed, observed, covariance=False, return_mean=False):
+        """Extension (error bars on an imputed value, heteroscedastic regression bands): the predictive variance Var[x_M | x_O] under
+        the fitted mixture for every row of X_observed, on the GPU: sum_k r_k (Sigma_k,M|O + (t_k - y)(t_k - y)^T) with y =
+        conditional_mean. X_observed and `observed` as for conditional_mean. Returns an (N, d - len(observed)) C-contiguous float64
+        array, the missing coordinates in ascending order -- with covariance=True the (N, dM, dM) symmetric matrices, whose diagonal
+        has the bits of the default form; with return_mean=True a pair of that and conditional_mean's (N, dM) result, bit for bit.
+        TypeError / ValueError before any device work."""
+        X = _require_data(X_observed)
+        coordinates, d = self._observed(observed, "conditional_variance")
+        n, columns = X.shape
+        if columns != len(coordinates):
+            raise ValueError("conditional_variance(): X_observed must have one column per observed coordinate")
+        index = np.array(coordinates, dtype=np.uint32)
+        dM = d - len(coordinates)
+        out = np.empty((n, dM, dM) if covariance else (n, dM))
+        mean = np.empty((n, dM)) if return_mean else None
+        _check(_l.mlpp_em_conditional_variances(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n),
+                                                C.c_int(int(bool(covariance))), _dp(out), _dp(mean) if return_mean else None))
+        return (out, mean) if return_mean else out
 
     def conditional_covariances(self, observed):
         """Extension: the covariances of the conditioned components, Sigma_k,M|O = Sigma_k,MM - Sigma_k,MO Sigma_k,OO^-1 Sigma_k,OM, as a

@@ -195,6 +195,33 @@ inline size_t condition_sample_record_doubles(int kernel, int dO, int dM)
 /// Returns the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
 int launch_em_condition_sample(const ConditionSampleArgs& a, int num_cus, hipStream_t stream);
 
+/// Conditional variance (em_condition_variance.hip): Var[x_M | x_O] of the n rows of a chunk from the same lw / lse as the conditioning
+/// pass, whose steps it runs first. Row i's output is a pure function of row i and the parameters. The tiers and paddings are
+/// ConditionKernel's and condition_pad's; the record is the conditioning pass's with c behind it: diag(C_k) (the padded dM doubles),
+/// or with `full` the lower triangle of C_k packed row by row, (a, b) at a (a + 1) / 2 + b, for the PADDED dM.
+struct ConditionVarianceArgs {
+    const double* xt; size_t ldx; uint32_t n;                // the observed coordinates, feature-major
+    int dO, dM, K;
+    const double* lw; size_t ldr; const double* lse;         // K x ldr log-responsibilities and their log-sum-exp
+    const double* table;                                     // K records of condition_variance_record_doubles(kernel, dO, dM, full)
+    double* out;                                             // n x dM, or n x dM x dM with `full`: row-major and contiguous (16-byte aligned)
+    double* means;                                           // n x dM (16-byte aligned): E[x_M | x_O], the conditioning pass's bits; or null
+    double* work;                                            // kConditionPlain: n x 2 dM doubles of the call's own; else unused
+    int full;
+    int skip;                                                // 1: a wave passes over a component none of its rows has a share in
+    int kernel;                                              // ConditionKernel
+};
+/// kConditionRegisters where the register tier is built for (dO, dM) in this form -- the diagonal form to 32 x 32, the full form to
+/// the dM its accumulators fit the register file at (em_condition_variance.hip states the bound) --, else kConditionPlain.
+int em_condition_variance_route(int dO, int dM, int full);
+inline size_t condition_variance_record_doubles(int kernel, int dO, int dM, int full)
+{
+    const size_t pm = (size_t)condition_pad(kernel, dM);
+    return condition_record_doubles(kernel, dO, dM) + (full ? pm * (pm + 1) / 2 : pm);
+}
+/// Returns the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
+int launch_em_condition_variance(const ConditionVarianceArgs& a, int num_cus, hipStream_t stream);
+
 enum MstatsMode : int {
     kFromLogResp = 0,  // r = exp(lw - lse)          (after an E-step)
     kFromResp = 1,      // r = lw                     (plain responsibilities: caller-given, one-hot, or all ones)

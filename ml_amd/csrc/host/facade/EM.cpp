@@ -679,6 +679,47 @@ MatrixXd EM::conditional_samples(const std::vector<unsigned int>& observed, Cons
     return out;
 }
 
+MatrixXd EM::conditional_variances(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, bool full_covariance,
+                                   MatrixXd* means) const
+{
+    const Index d = means_.rows();
+    // (the order of conditional_means: that there is a shape, the arguments against it, the device, the decompositions)
+    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    check_observed(observed, d);
+    const Index d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed, n = data_observed.cols();
+    if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
+    require_fitted();
+    const unsigned int K = number_components_;
+    const std::vector<double> cov_flat = flat_covariances();
+    std::vector<double> means_observed(static_cast<std::size_t>(K * d_observed)), covariances_observed(static_cast<std::size_t>(K * d_observed * d_observed)),
+        maps(static_cast<std::size_t>(K * d_missing * d_observed)), means_missing(static_cast<std::size_t>(K * d_missing)),
+        covariances_missing(static_cast<std::size_t>(K * d_missing * d_missing));
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+    const uint32_t* coordinates = reinterpret_cast<const uint32_t*>(observed.data());
+    check(mlhip_em_condition(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, means_.data(), cov_flat.data(), coordinates,
+                             static_cast<uint32_t>(d_observed), means_observed.data(), covariances_observed.data(), maps.data(),
+                             means_missing.data()));
+    check(mlhip_em_condition_covariances(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, cov_flat.data(), coordinates,
+                                         static_cast<uint32_t>(d_observed), covariances_missing.data(), nullptr));
+    const Index width = full_covariance ? d_missing * d_missing : d_missing;
+    MatrixXd out(width, n);
+    if (means) means->resize(d_missing, n);
+    if (!n) return out;
+    mlhip_ctx* ctx = device::context();
+    const Index batch = Clustering::detail::score_batch_rows();
+    for (Index first = 0; first < n; first += batch) {
+        const Index rows = std::min(batch, n - first);
+        DataGuard dev;
+        check(mlhip_data_upload(ctx, data_observed.col(first), static_cast<uint32_t>(d_observed), static_cast<uint64_t>(rows),
+                                data_observed.outerStride(), &dev.h));
+        check(mlhip_em_conditional_variances(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
+                                             covariances_observed.data(), maps.data(), means_missing.data(), covariances_missing.data(),
+                                             full_covariance ? 1 : 0, out.col(first), width, means ? means->col(first) : nullptr, d_missing,
+                                             nullptr));
+    }
+    return out;
+}
+
 void EM::process_covariances(const Index number_dimensions)
 {
     // Inverse and sqrt(det) of every covariance for the host point query (ML/EM.cpp:274-287).

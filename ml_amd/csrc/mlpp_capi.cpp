@@ -261,6 +261,22 @@ int mlpp_em_conditional_samples(const mlpp_em* h, const uint32_t* observed, uint
         if (labels_out) std::copy(labels.begin(), labels.end(), labels_out);
     });
 }
+int mlpp_em_conditional_variances(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                                  int full, double* out, double* means_out)
+{
+    return guarded([&] {
+        need(h);
+        if (n_observed) need(observed);
+        if (n && n_observed) { need(data_observed); need(out); }
+        if (n > static_cast<uint64_t>(std::numeric_limits<Index>::max())) throw std::invalid_argument("EM: Too many samples");
+        const std::vector<unsigned int> coordinates(observed, observed + n_observed);
+        MatrixXd means;
+        const MatrixXd v = h->em.conditional_variances(coordinates, ConstMatrixRef(data_observed, n_observed, static_cast<Index>(n), n_observed),
+                                                       full != 0, means_out ? &means : nullptr);
+        std::copy_n(v.data(), v.size(), out);
+        if (means_out) std::copy_n(means.data(), means.size(), means_out);
+    });
+}
 int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out)
 {
     return guarded([&] {

@@ -710,6 +710,11 @@ struct ConditionSampleRoute {
     uint32_t chunk_rows = 0, draws = 1;
 };
 ConditionSampleRoute condition_sample_route(const mlhip_data* data, int K, int dM, uint32_t n_draws);
+/// mlhip_em_conditional_variances: condition_route's E-step tier, switches and chunking, with the kernel tier
+/// em_condition_variance_route (device/em_condition_variance.hip) names for (dO, dM) in the form asked for, and the rows per chunk
+/// sized for the K log-responsibilities plus `out_doubles` per row: the call's outputs (dM or dM^2, dM more with the mean) and, on
+/// the plain tier, that kernel's 2 dM doubles of work. No row depends on the chunk.
+ConditionRoute condition_variance_route(const mlhip_data* data, int K, int dM, bool full, bool with_means);
 /// The conditioning kernels' table on the host: K records [mu_O | mu_M | A^T] in the paddings of `kernel` (device.hpp condition_pad):
 /// +0.0, and -0.0 in the rows of A^T beyond dO. With `factors` (K x dM x dM row-major lower factors; mlhip_em_conditional_samples) every
 /// record carries its factor behind it, the lower triangle packed row by row in the padded dM (condition_sample_record_doubles).

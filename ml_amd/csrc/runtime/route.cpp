@@ -174,6 +174,24 @@ ConditionRoute condition_route(const mlhip_data* data, int K, int dM)
     return r;
 }
 
+ConditionRoute condition_variance_route(const mlhip_data* data, int K, int dM, bool full, bool with_means)
+{
+    const Switches sw = read_switches();
+    ConditionRoute r;
+    r.em = em_route(data, K, Covariance::Full);
+    r.kernel = sw.condition_plain ? kConditionPlain : em_condition_variance_route(data->d, dM, full);
+    r.skip = sw.condition_skip;
+    const uint64_t tile = kSampleTile;
+    const uint64_t per_row = (uint64_t)K + (full ? (uint64_t)dM * dM : (uint64_t)dM) + (with_means ? (uint64_t)dM : 0) +
+                             (r.kernel == kConditionPlain ? 2 * (uint64_t)dM : 0);
+    uint64_t rows = sw.condition_rows > 0 ? (uint64_t)sw.condition_rows : kScoreScratchBytes / (sizeof(double) * per_row);
+    rows = sw.condition_rows > 0 ? (rows + tile - 1) / tile * tile : rows / tile * tile;
+    if (rows < tile) rows = tile;
+    if (rows > data->n_pad) rows = data->n_pad;
+    r.chunk_rows = (uint32_t)rows;
+    return r;
+}
+
 ConditionSampleRoute condition_sample_route(const mlhip_data* data, int K, int dM, uint32_t n_draws)
 {
     const Switches sw = read_switches();
