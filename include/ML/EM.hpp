@@ -184,6 +184,27 @@ public:
     @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
     DLL_DECLSPEC MatrixXd conditional_variances(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed,
                                                 bool full_covariance = false, MatrixXd* means = nullptr) const;
+    /** Extension (exceedance probabilities, the probability integral transform, p-values of an observed value): the predictive CDF
+    P(x_j <= v | x_O) of every missing coordinate j under the fitted mixture, on the device, for every column of `data_observed` at
+    that point's own values: `values` is (number of missing coordinates) x data.cols(), the missing coordinates in ascending order.
+    Arguments as for conditional_means; returns a matrix of the shape of `values`. Given x_O, coordinate j follows the
+    one-dimensional mixture sum_k r_k N(t_kj, Sigma_k,M|O[j][j]); the definition and its fixed evaluation order:
+    mlhip_em_conditional_cdfs. The result does not depend on the row batches or the device group; the model is not changed.
+    @throw std::invalid_argument As conditional_means, or if `values` has another shape.
+    @throw std::domain_error If the observed block of a covariance, or a conditioned covariance, is not positive definite.
+    @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
+    DLL_DECLSPEC MatrixXd conditional_cdfs(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, ConstMatrixRef values) const;
+    /** Extension (exact predictive intervals and medians): the quantiles of the same one-dimensional mixtures, the inverse of
+    conditional_cdfs, at every probability of `probabilities` (each strictly inside (0, 1)). Returns (number of missing coordinates) x
+    (probabilities.size() * data.cols()): the quantiles at probability q of point i in column q * data.cols() + i, as conditional_samples
+    lays out its draws. A safeguarded Newton search per (point, coordinate) inside the bracket of the components' own quantiles, with a
+    fixed start, stopping rule and trip cap (mlhip_em_conditional_quantiles holds the definition): a pure function of the point, the
+    parameters and the probability.
+    @throw std::invalid_argument As conditional_means, or for a probability that is a NaN or not strictly inside (0, 1).
+    @throw std::domain_error If the observed block of a covariance, or a conditioned covariance, is not positive definite.
+    @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
+    DLL_DECLSPEC MatrixXd conditional_quantiles(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed,
+                                                const std::vector<double>& probabilities) const;
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }
     /** Extension: number of E-M iterations the last fit() ran. */
@@ -230,6 +251,9 @@ private:
     std::vector<double> flat_covariances() const;                    // covariances() as one number_components() x d x d array
     void require_fitted_for(ConstMatrixRef data) const;
     void require_fitted() const;
+    /// conditional_cdfs (`values` given) and conditional_quantiles (`probabilities` given) behind their own argument checks.
+    MatrixXd conditional_distribution(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, const ConstMatrixRef* values,
+                                      const std::vector<double>* probabilities) const;
     void score(ConstMatrixRef data, double* log_density, unsigned int* labels) const;
 };
 

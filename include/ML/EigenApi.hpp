@@ -468,6 +468,42 @@ public:
                                                     means ? means->data() : nullptr));
         return out;
     }
+    /** Extension (ML/EM.hpp): the predictive CDF P(x_j <= v | x_O) per missing coordinate of every column of `data_observed` at that
+    point's own `values` ((number of missing coordinates) x data_observed.cols()); returns a matrix of that shape.
+    @throw std::invalid_argument As conditional_means, or if `values` has another shape.
+    @throw std::domain_error If a block is not positive definite. */
+    Eigen::MatrixXd conditional_cdfs(const std::vector<unsigned int>& observed, Eigen::Ref<const Eigen::MatrixXd> data_observed,
+                                     Eigen::Ref<const Eigen::MatrixXd> values) const
+    {
+        if (data_observed.rows() != static_cast<Eigen::Index>(observed.size())) throw std::invalid_argument("Wrong data size");
+        const Eigen::Index missing = means_.rows() > data_observed.rows() ? means_.rows() - data_observed.rows() : 0;
+        if (values.rows() != missing || values.cols() != data_observed.cols())
+            throw std::invalid_argument("EM: values must hold one row per missing coordinate and one column per point");
+        const detail::Block block(data_observed), at(values);
+        Eigen::MatrixXd out(missing, data_observed.cols());
+        static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+        detail::check(mlpp_em_conditional_cdfs(h_, reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(observed.size()), block.p,
+                                               static_cast<uint64_t>(data_observed.cols()), at.p, out.data()));
+        return out;
+    }
+    /** Extension (ML/EM.hpp): the quantiles of the same one-dimensional mixtures at every probability (each strictly inside (0, 1));
+    returns (number of missing coordinates) x (probabilities.size() * data_observed.cols()), probability q of point i in column
+    q * data_observed.cols() + i.
+    @throw std::invalid_argument As conditional_means, or for a probability that is a NaN or not strictly inside (0, 1).
+    @throw std::domain_error If a block is not positive definite. */
+    Eigen::MatrixXd conditional_quantiles(const std::vector<unsigned int>& observed, Eigen::Ref<const Eigen::MatrixXd> data_observed,
+                                          const std::vector<double>& probabilities) const
+    {
+        if (data_observed.rows() != static_cast<Eigen::Index>(observed.size())) throw std::invalid_argument("Wrong data size");
+        const Eigen::Index missing = means_.rows() > data_observed.rows() ? means_.rows() - data_observed.rows() : 0;
+        const detail::Block block(data_observed);
+        Eigen::MatrixXd out(missing, static_cast<Eigen::Index>(probabilities.size()) * data_observed.cols());
+        static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+        detail::check(mlpp_em_conditional_quantiles(h_, reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(observed.size()),
+                                                    block.p, static_cast<uint64_t>(data_observed.cols()), probabilities.data(),
+                                                    static_cast<uint64_t>(probabilities.size()), out.data()));
+        return out;
+    }
     const std::vector<unsigned int>& labels() const override { return labels_; }
     bool converged() const override { return converged_; }
 

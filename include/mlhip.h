@@ -468,6 +468,84 @@ int mlhip_em_conditional_variances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
  * output row is the accumulator, table from global memory; same bits. */
 int mlhip_em_condition_variance_route(const mlhip_data* data, uint32_t K, uint32_t dM, int full, int* kernel);
 
+/* EXTENSION (exact predictive intervals, medians, exceedance probabilities, the probability integral transform; not in the reference
+ * surface). Host helpers, no GPU needed: the standard normal CDF the kernels below use (device/normal_cdf.hpp, the same text on host
+ * and device: Phi(-t) = exp(-t^2/2) y P(s), one form for every argument, no table and no library call; relative error <= 6.01e-16
+ * against a 40-digit reference wherever the result is a normal number, <= 1.84 spacings of the subnormals below; Phi(-inf) = 0,
+ * Phi(+inf) = 1, Phi(0) = 0.5, NaN -> NaN; n values each) and its inverse (a rational start and four Halley steps on that CDF; odd
+ * about 0.5 wherever 1 - p is a double; mlhip_normal_quantile(0.5) = +0.0; MLHIP_E_INVALID_ARGUMENT for a probability that is a
+ * NaN or not strictly inside (0, 1)). */
+int mlhip_normal_cdf(const double* a, uint64_t n, double* out);
+int mlhip_normal_quantile(const double* p, uint64_t n, double* out);
+/* Host helper, no GPU needed: from covariances_missing = the C_k of mlhip_em_condition_covariances (K x dM x dM; only the diagonal is
+ * read) the two K x dM arrays the calls below take: scales s_kj = sqrt(C_k[j][j]) and inverse_scales w_kj = 1.0 / s_kj (one fp64
+ * sqrt, one fp64 division). Diagonal input to mlhip_em_condition_covariances gives sqrt(sigma^2_M) exactly. MLHIP_E_DOMAIN where a
+ * C_k[j][j] is <= 0 or not finite. */
+int mlhip_em_condition_scales(uint32_t K, uint32_t dM, const double* covariances_missing, double* scales, double* inverse_scales);
+/* Under the conditioned mixture of mlhip_em_condition (mixing: the K weights of the joint model), coordinate j of x_M given x_O follows
+ * the ONE-DIMENSIONAL mixture sum_k r_k N(t_kj, s_kj^2): t_k = mu_k,M + A_k (x_O - mu_k,O), r_k = exp_nonpos(lw_k - lse) from the
+ * marginal mixture's exact E-step (the values, the chunks and the switches of mlhip_em_conditional_means), s and w from
+ * mlhip_em_condition_scales. `data` is a resident block of the OBSERVED coordinates (its d is dO). Per row, on every tier, with t_kj by
+ * the chain of mlhip_em_conditional_means (z_c = x_c - mu_k,O[c]; t_j = mu_k,M[j], t_j = fma(A_k[j][c], z_c, t_j) for ascending c):
+ *   mlhip_em_conditional_cdfs   P(x_j <= v_j | x_O) at the row's own value v_j per missing coordinate (values: rows x dM, `ld_values`
+ *       apart): for ascending k, ONLY where r_k != 0:  a = (v_j - t_kj) * w_kj;  F_j = fma(r_k, normal_cdf(a), F_j), from F_j = +0.0.
+ *       A NaN row or a NaN value gives NaN. out: rows x dM, `ld_out` >= dM apart.
+ *   mlhip_em_conditional_quantiles   the v with F_j(v) = p S for every probability p (n_probabilities of them, each strictly inside
+ *       (0, 1)); z = mlhip_normal_quantile(p) on the host. S = the sequential fp64 sum of r_k for ascending k from +0.0 (the s_{K-1} of
+ *       mlhip_em_conditional_samples); T = p * S. Over the components with r_k != 0, ascending k: q_k = fma(s_kj, z, t_kj); lo = min
+ *       q_k, hi = max q_k (the mixture's quantile lies between its components'; a NaN q_k makes both NaN); g = fma(r_k, q_k, g) from
+ *       +0.0. Start: v = g / S clamped into [lo, hi] (the weighted mean of the q_k leaves it only by rounding) -- the ends included: a
+ *       row with one dominant component has its answer ON an end (g / S is that component's own quantile), and an end is not
+ *       evaluated otherwise. Where lo == hi -- K = 1, a row with one share, p = 0.5 with equal t_kj -- the result is lo and no trip is
+ *       made; it is NaN where lo or T is a NaN or no component has a share. Else the bracket is widened to [lo - e, hi + e],
+ *       e = 2^-50 max(|lo|, |hi|) (a candidate on an end, or a few roundings beyond it, is strictly inside), and trips n = 1, 2, ...:
+ *         F = F_j(v) as above, f = sum_k fma(r_k, w_kj * normal_pdf(a), f) from +0.0, normal_pdf(a) = exp_nonpos(-0.5 * (t * t)) *
+ *         3.98942280401432677940e-01 with t = min(|a|, 40) (a product by the rounded 1 / sqrt(2 pi), no division; NaN for a NaN);
+ *         if F < T then lo = v else hi = v;
+ *         the Newton candidate, taken on the logarithm of the nearer tail (near the root it is the plain Newton step; far out in a
+ *         tail it neither creeps nor flies off):  c = v + log(T / F) * (F / f) if T + T < S (or T + T == S and F < T), else
+ *         c = v - log((S - T) / (S - F)) * ((S - F) / f)   (log: the device library's);
+ *         next = c if n <= 24 and lo < c < hi, else lo + (hi - lo) / 2;
+ *         STOP with the result v (the last point evaluated) if |F - T| <= 2^-50 T, or |c - v| <= 2^-51 |v|, or next is not strictly
+ *         inside (lo, hi), or n == MLHIP_QUANTILE_MAX_TRIPS; else v = next.
+ *       The cap holds whatever the data: from trip 25 on every trip is a bisection, so the last 60 trips alone cut the bracket to 2^-60
+ *       of its width, below the rounding of the q_k that span it; the first stop rule says F is within the accuracy of a sum of
+ *       normal_cdf values, the second that the step is below v's own rounding, the third that the bracket has no double left to try. p = 0.5 gives z = +0.0 and q_k = t_kj exactly, so K
+ *       = 1 returns the bits of mlhip_em_conditional_means there. A coordinate's search is a pure function of (row, parameters, p); the
+ *       kernels run the dM coordinates of 64 rows in lock-step until none is left, and a coordinate that has stopped is not written
+ *       again. out: n_probabilities blocks of rows x dM, probability-major, a row `ld_out` >= dM doubles after the one before and a
+ *       block rows x ld_out doubles after the one before (the layout of mlhip_em_conditional_samples' draws). iterations (may be NULL):
+ *       n_probabilities x rows x dM uint32, contiguous: the trips every output took (0 where no search ran). The probabilities go
+ *       through in groups so that a chunk's scratch keeps the call's bound (MLHIP_CONDITION_GROUP=n: at most n per group): one launch per
+ *       chunk and group.
+ * means_out (rows x dM, `ld_means` >= dM apart; may be NULL) and log_density (rows; may be NULL) carry the bits of
+ * mlhip_em_conditional_means' out and log_density. sum_k r_k is whatever the E-step gives: NOTHING IS RENORMALISED. A component with
+ * r_k = 0 leaves every sum as it is, so the kernels' wave-level skip changes no bit (MLHIP_CONDITION_SKIP=0: same bits). A row's result
+ * is a pure function of the row and the parameters: the chunks (whole 256-row tiles sized for the K log-responsibilities plus this
+ * call's inputs and outputs per row; MLHIP_CONDITION_ROWS=rows overrides), the row's place in the block, a prefix of a longer block,
+ * the shards of a device group (each handles its own rows, no collective), how the probabilities are grouped or split over calls, the
+ * skip and the kernel tier change no bit. Row weights are ignored, as in scoring; nothing the handle holds is changed. n = 0 or
+ * n_probabilities = 0 succeeds and writes nothing. MLHIP_E_INVALID_ARGUMENT, before any device work: null pointers, K = 0, dM = 0,
+ * dO + dM > 4096, a leading dimension below its row, a probability that is a NaN or not strictly inside (0, 1). */
+enum { MLHIP_QUANTILE_NEWTON_TRIPS = 24, MLHIP_QUANTILE_MAX_TRIPS = 84 };
+int mlhip_em_conditional_cdfs(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t dM, const double* mixing, const double* means_observed,
+                              const double* covariances_observed, const double* maps, const double* means_missing, const double* scales,
+                              const double* inverse_scales, const double* values, int64_t ld_values, double* out, int64_t ld_out,
+                              double* means_out, int64_t ld_means, double* log_density);
+int mlhip_em_conditional_quantiles(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t dM, const double* mixing,
+                                   const double* means_observed, const double* covariances_observed, const double* maps,
+                                   const double* means_missing, const double* scales, const double* inverse_scales,
+                                   const double* probabilities, uint32_t n_probabilities, double* out, int64_t ld_out, double* means_out,
+                                   int64_t ld_means, double* log_density, uint32_t* iterations);
+/* Which kernel mlhip_em_conditional_cdfs (quantile = 0) or mlhip_em_conditional_quantiles (quantile = 1) runs behind the E-step for dM
+ * missing coordinates on this block (diagnostic, nothing is launched), under the switches as they are set now.
+ * MLHIP_CONDITION_REGISTERS: lane = row, x_O, t and the per-coordinate state in registers, mu, A, s and w fed as scalar operands,
+ * values in and results out through LDS as contiguous 16 bytes per lane -- the CDF at dO <= 32 and dM <= 32, the quantile search at
+ * dO <= 32 up to the largest dM whose state (lo, hi, v, F, f and t per coordinate) the compiler keeps in registers without scratch
+ * at every dO: dM <= 16 (profiles/condition_quantile_registers.txt holds the report). MLHIP_CONDITION_PLAIN (else, up to dO + dM =
+ * 4096, and everywhere under MLHIP_CONDITION=plain): thread = row, table from global memory; same bits. */
+int mlhip_em_condition_quantile_route(const mlhip_data* data, uint32_t K, uint32_t dM, int quantile, int* kernel);
+
 /* (X - mean)(X - mean)^T / (N - 1) over ALL ranks' samples (EM::calculate_sample_covariance,
  * ML/EM.cpp:265-272). mean may be NULL. */
 int mlhip_sample_covariance(mlhip_ctx* ctx, mlhip_data* data, double* mean, double* covariance);

@@ -115,6 +115,16 @@ int mlpp_em_conditional_samples(const mlpp_em* h, const uint32_t* observed, uint
  * mlpp_em_conditional_means) may be NULL. n = 0 writes nothing. */
 int mlpp_em_conditional_variances(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
                                   int full, double* out, double* means_out);
+/* Extension: EM::conditional_cdfs -- P(x_j <= v | x_O) per missing coordinate under the fitted mixture for n points
+ * (mlhip_em_conditional_cdfs). observed, data_observed as for mlpp_em_conditional_means; values and out: n x dM row-major, dM =
+ * d - n_observed, the missing coordinates in ascending order. n = 0 writes nothing. */
+int mlpp_em_conditional_cdfs(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                             const double* values, double* out);
+/* Extension: EM::conditional_quantiles -- the inverse of mlpp_em_conditional_cdfs at n_probabilities probabilities, each strictly
+ * inside (0, 1) (mlhip_em_conditional_quantiles). out: n_probabilities x n x dM row-major, probability-major. n = 0 or
+ * n_probabilities = 0 writes nothing. */
+int mlpp_em_conditional_quantiles(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                                  const double* probabilities, uint64_t n_probabilities, double* out);
 
 /* ---- KMeans (cppyml/clustering.cpp:148-183) ---- */
 int mlpp_kmeans_create(uint32_t number_clusters, mlpp_kmeans** out);

@@ -859,6 +859,96 @@ def em_condition_variance_route(data, K, dM, full=False):
     return ("registers", "plain")[k.value]
 
 
+def normal_cdf(a):
+    """The standard normal CDF the conditional CDF / quantile kernels use (mlhip_normal_cdf, device/normal_cdf.hpp compiled for the
+    host; no GPU), elementwise: float64, the shape of `a`."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    out = np.empty_like(a)
+    check(lib.mlhip_normal_cdf(dptr(a), C.c_uint64(a.size), dptr(out)))
+    return out
+
+
+def normal_quantile(p):
+    """The inverse of normal_cdf (mlhip_normal_quantile, no GPU), elementwise; ValueError for a probability that is a NaN or not
+    strictly inside (0, 1)."""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    out = np.empty_like(p)
+    check(lib.mlhip_normal_quantile(dptr(p), C.c_uint64(p.size), dptr(out)))
+    return out
+
+
+QUANTILE_MAX_TRIPS = 84      # MLHIP_QUANTILE_MAX_TRIPS: the trip cap of the quantile search
+
+
+def em_condition_scales(covs_missing):
+    """(scales, inverse_scales), K x dM each: s_kj = sqrt(C_k[j][j]) and w_kj = 1.0 / s_kj from the K x dM x dM conditioned covariances
+    of em_condition_covariances (mlhip_em_condition_scales, no GPU). ValueError where a C_k[j][j] is <= 0 or not finite."""
+    covs_missing = np.ascontiguousarray(covs_missing, dtype=np.float64)
+    assert covs_missing.ndim == 3 and covs_missing.shape[1] == covs_missing.shape[2]
+    K, dM = covs_missing.shape[:2]
+    s, w = np.empty((K, dM)), np.empty((K, dM))
+    check(lib.mlhip_em_condition_scales(C.c_uint32(K), C.c_uint32(dM), dptr(covs_missing), dptr(s), dptr(w)))
+    return s, w
+
+
+def _conditioned_arguments(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales):
+    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales)]
+    K, dM = arrays[4].shape
+    assert arrays[0].shape == (K,) and arrays[1].shape == (K, data.d) and arrays[2].shape == (K, data.d, data.d)
+    assert arrays[3].shape == (K, dM, data.d) and arrays[5].shape == (K, dM) and arrays[6].shape == (K, dM)
+    return K, dM, arrays
+
+
+def em_conditional_cdfs(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales, values, means=False,
+                        log_density=False):
+    """P(x_j <= values[i, j] | x_O) per missing coordinate for every row of `data`, a Data block of OBSERVED coordinates, under the
+    conditioned mixture em_condition returns and the scales of em_condition_scales (mlhip_em_conditional_cdfs): n x dM C-contiguous
+    float64. With means=True and / or log_density=True a tuple of it, E[x_M | x_O] (n x dM) and the n log-densities of the rows under
+    the marginal mixture, in that order -- the bits of Data.em_conditional_means. A function of the module, not a method of Data;
+    nothing the handle holds is changed."""
+    K, dM, arrays = _conditioned_arguments(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales)
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    assert values.shape == (data.n, dM)
+    out = np.empty((data.n, dM))
+    y = np.empty((data.n, dM)) if means else None
+    dens = np.empty(data.n) if log_density else None
+    check(lib.mlhip_em_conditional_cdfs(data.ctx.handle, data._h, C.c_uint32(K), C.c_uint32(dM), *[dptr(a) for a in arrays], dptr(values),
+                                        C.c_int64(dM), dptr(out), C.c_int64(dM), dptr(y) if means else None, C.c_int64(dM),
+                                        dptr(dens) if log_density else None))
+    extra = ([y] if means else []) + ([dens] if log_density else [])
+    return (out, *extra) if extra else out
+
+
+def em_conditional_quantiles(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales, probabilities,
+                             iterations=False, means=False, log_density=False):
+    """The quantiles of x_j | x_O per missing coordinate at every probability (each strictly inside (0, 1)) for every row of `data`
+    (mlhip_em_conditional_quantiles): P x n x dM C-contiguous float64, probability-major. With iterations=True, means=True and / or
+    log_density=True a tuple of it, the trips every output took (P x n x dM uint32), E[x_M | x_O] and the log-densities, in that
+    order. Arguments as for em_conditional_cdfs. ValueError for a bad probability, before any device work."""
+    K, dM, arrays = _conditioned_arguments(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales)
+    probabilities = np.ascontiguousarray(probabilities, dtype=np.float64)
+    assert probabilities.ndim == 1
+    P = len(probabilities)
+    out = np.empty((P, data.n, dM))
+    trips = np.zeros((P, data.n, dM), dtype=np.uint32) if iterations else None
+    y = np.empty((data.n, dM)) if means else None
+    dens = np.empty(data.n) if log_density else None
+    check(lib.mlhip_em_conditional_quantiles(data.ctx.handle, data._h, C.c_uint32(K), C.c_uint32(dM), *[dptr(a) for a in arrays],
+                                             dptr(probabilities), C.c_uint32(P), dptr(out), C.c_int64(dM), dptr(y) if means else None,
+                                             C.c_int64(dM), dptr(dens) if log_density else None, u32ptr(trips) if iterations else None))
+    extra = ([trips] if iterations else []) + ([y] if means else []) + ([dens] if log_density else [])
+    return (out, *extra) if extra else out
+
+
+def em_condition_quantile_route(data, K, dM, quantile=True):
+    """The kernel mlhip_em_conditional_quantiles (quantile=True) or mlhip_em_conditional_cdfs (quantile=False) runs for dM missing
+    coordinates on the Data block `data`, under the switches as they are set now (mlhip_em_condition_quantile_route): 'registers' |
+    'plain'."""
+    k = C.c_int()
+    check(lib.mlhip_em_condition_quantile_route(data._h, C.c_uint32(K), C.c_uint32(dM), C.c_int(int(bool(quantile))), C.byref(k)))
+    return ("registers", "plain")[k.value]
+
+
 def em_sample_route(d, K):
     """The kernel the sampling calls run for K components in d dimensions under the switches as they are set now
     (mlhip_em_sample_route): 'lds_table' | 'global_table' | 'plain'."""

@@ -7,7 +7,7 @@ Conventions kept from the reference:
   * `EM.means` is `d x K` (NOT transposed, clustering.cpp:126), `KMeans.centroids` is `K x d` (clustering.cpp:66-69,172);
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
-Extensions (not in the reference surface): `EM.conditional_mean`, `EM.conditional_variance`, `EM.conditional_sample`, `EM.conditional_covariances`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
+Extensions (not in the reference surface): `EM.conditional_mean`, `EM.conditional_variance`, `EM.conditional_cdf`, `EM.conditional_quantile`, `EM.conditional_sample`, `EM.conditional_covariances`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
 `KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`, `EM.set_number_initialisations`,
 `EM.number_initialisations`, `EM.best_initialisation`, `EM.initialisation_log_likelihoods`, `EM.initialisation_steps`,
@@ -389,7 +389,7 @@ class EM:
         return X, labels
 
     def _observed(self, observed, name):
-        """The checks of `observed` that conditional_mean, conditional_variance, conditional_sample and conditional_covariances share -> (coordinates, d)."""
+        """The checks of `observed` that conditional_mean, conditional_variance, conditional_cdf, conditional_quantile, conditional_sample and conditional_covariances share -> (coordinates, d)."""
         try:
             coordinates = [int(c) for c in observed]
         except TypeError:
@@ -444,6 +444,51 @@ class EM:
         _check(_l.mlpp_em_conditional_variances(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n),
                                                 C.c_int(int(bool(covariance))), _dp(out), _dp(mean) if return_mean else None))
         return (out, mean) if return_mean else out
+
+    def conditional_cdf(self, X_observed, observed, values):
+        """Extension (exceedance probabilities, the probability integral transform, p-values of an observed value): the predictive
+        CDF P(x_j <= values[i, j] | x_O) of every missing coordinate under the fitted mixture for every row of X_observed, on the
+        GPU. Given x_O, coordinate j follows the one-dimensional mixture sum_k r_k N(t_kj, Sigma_k,M|O[j][j]). X_observed and
+        `observed` as for conditional_mean; `values`: a C-contiguous float64 (N, d - len(observed)) array, the missing coordinates in
+        ascending order. Returns an array of that shape. TypeError / ValueError before any device work."""
+        X = _require_data(X_observed)
+        coordinates, d = self._observed(observed, "conditional_cdf")
+        n, columns = X.shape
+        if columns != len(coordinates):
+            raise ValueError("conditional_cdf(): X_observed must have one column per observed coordinate")
+        dM = d - len(coordinates)
+        if not (isinstance(values, np.ndarray) and values.dtype == np.float64 and values.ndim == 2 and values.flags.c_contiguous):
+            raise TypeError("conditional_cdf(): values must be a C-contiguous float64 array of shape (N, dM)")
+        if values.shape != (n, dM):
+            raise ValueError("conditional_cdf(): values must have one row per row of X_observed and one column per missing coordinate")
+        index = np.array(coordinates, dtype=np.uint32)
+        out = np.empty((n, dM))
+        _check(_l.mlpp_em_conditional_cdfs(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n), _dp(values), _dp(out)))
+        return out
+
+    def conditional_quantile(self, X_observed, observed, probabilities):
+        """Extension (exact predictive intervals and medians): the quantiles of x_j | x_O, the inverse of conditional_cdf, for every
+        row of X_observed at every probability, on the GPU -- exact where mean +- z sqrt(variance) is wrong (a mixture's conditional
+        is skewed or multimodal) and without the 1 / sqrt(n_draws) error of quantiles taken from conditional_sample draws.
+        `probabilities`: a 1-D sequence of floats strictly inside (0, 1). Returns a (len(probabilities), N, d - len(observed))
+        C-contiguous float64 array, the missing coordinates in ascending order. A pure function of the row, the parameters and the
+        probability. TypeError / ValueError before any device work."""
+        X = _require_data(X_observed)
+        coordinates, d = self._observed(observed, "conditional_quantile")
+        n, columns = X.shape
+        if columns != len(coordinates):
+            raise ValueError("conditional_quantile(): X_observed must have one column per observed coordinate")
+        try:
+            p = np.array([float(q) for q in probabilities], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("conditional_quantile(): probabilities must be a 1-D sequence of floats") from None
+        if not np.all((p > 0.0) & (p < 1.0)):
+            raise ValueError("conditional_quantile(): every probability must lie strictly inside (0, 1)")
+        index = np.array(coordinates, dtype=np.uint32)
+        out = np.empty((len(p), n, d - len(coordinates)))
+        _check(_l.mlpp_em_conditional_quantiles(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n), _dp(p),
+                                                C.c_uint64(len(p)), _dp(out)))
+        return out
 
     def conditional_covariances(self, observed):
         """Extension: the covariances of the conditioned components, Sigma_k,M|O = Sigma_k,MM - Sigma_k,MO Sigma_k,OO^-1 Sigma_k,OM, as a

@@ -222,6 +222,36 @@ inline size_t condition_variance_record_doubles(int kernel, int dO, int dM, int 
 /// Returns the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
 int launch_em_condition_variance(const ConditionVarianceArgs& a, int num_cus, hipStream_t stream);
 
+/// Conditional CDF and quantiles (em_condition_quantile.hip): per missing coordinate j the one-dimensional mixture sum_k r_k N(t_kj,
+/// s_kj^2) of the n rows of a chunk, from the same lw / lse as the conditioning pass -- its CDF at a value per (row, coordinate), or
+/// its quantiles at n_prob probabilities. Row i's output is a pure function of row i and the parameters. The tiers and paddings are
+/// ConditionKernel's and condition_pad's; the record is the conditioning pass's with [s (the padded dM) | w = 1 / s (the same)] behind it.
+struct ConditionQuantileArgs {
+    const double* xt; size_t ldx; uint32_t n;                // the observed coordinates, feature-major
+    int dO, dM, K;
+    const double* lw; size_t ldr; const double* lse;         // K x ldr log-responsibilities and their log-sum-exp
+    const double* table;                                     // K records of condition_quantile_record_doubles(kernel, dO, dM)
+    const double* values;                                    // CDF: n x dM, row-major and contiguous (16-byte aligned); quantile: unused
+    const double* probabilities; const double* z;            // quantile: n_prob probabilities and their normal quantiles (device memory)
+    uint32_t n_prob;
+    double* out;                                             // n x dM row-major (16-byte aligned); quantile: n_prob such blocks, ldq doubles apart
+    uint32_t* iterations;                                    // quantile: trips per output, in out's layout (blocks ldq apart); or null
+    size_t ldq;                                              // even
+    double* means;                                           // n x dM (16-byte aligned): E[x_M | x_O], the conditioning pass's bits; or null
+    int skip;                                                // 1: a wave passes over a component none of its rows has a share in
+    int kernel;                                              // ConditionKernel
+};
+/// kConditionRegisters where the register tier is built for (dO, dM) -- the CDF to 32 x 32, the quantile search to the dM its state
+/// fits the register file at (em_condition_quantile.hip states the bound) --, else kConditionPlain.
+int em_condition_quantile_route(int dO, int dM, int quantile);
+inline size_t condition_quantile_record_doubles(int kernel, int dO, int dM)
+{
+    return condition_record_doubles(kernel, dO, dM) + 2 * (size_t)condition_pad(kernel, dM);
+}
+/// Return the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
+int launch_em_condition_cdf(const ConditionQuantileArgs& a, int num_cus, hipStream_t stream);
+int launch_em_condition_quantile(const ConditionQuantileArgs& a, int num_cus, hipStream_t stream);
+
 enum MstatsMode : int {
     kFromLogResp = 0,  // r = exp(lw - lse)          (after an E-step)
     kFromResp = 1,      // r = lw                     (plain responsibilities: caller-given, one-hot, or all ones)

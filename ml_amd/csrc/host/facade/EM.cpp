@@ -720,6 +720,77 @@ MatrixXd EM::conditional_variances(const std::vector<unsigned int>& observed, Co
     return out;
 }
 
+MatrixXd EM::conditional_distribution(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, const ConstMatrixRef* values,
+                                      const std::vector<double>* probabilities) const
+{
+    const Index d = means_.rows();
+    // (the order of conditional_means: that there is a shape, the arguments against it, the device, the decompositions)
+    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    check_observed(observed, d);
+    const Index d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed, n = data_observed.cols();
+    if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
+    if (values && (values->rows() != d_missing || values->cols() != n)) throw std::invalid_argument("EM: values must hold one row per missing coordinate and one column per point");
+    const Index n_probabilities = probabilities ? static_cast<Index>(probabilities->size()) : 1;
+    if (probabilities) {
+        if (static_cast<std::uint64_t>(n_probabilities) > 0xFFFFFFFFull) throw std::invalid_argument("EM: too many probabilities");
+        for (const double p : *probabilities)
+            if (!(p > 0.0 && p < 1.0)) throw std::invalid_argument("EM: a probability must lie strictly inside (0, 1)");
+    }
+    require_fitted();
+    const unsigned int K = number_components_;
+    const std::vector<double> cov_flat = flat_covariances();
+    std::vector<double> means_observed(static_cast<std::size_t>(K * d_observed)), covariances_observed(static_cast<std::size_t>(K * d_observed * d_observed)),
+        maps(static_cast<std::size_t>(K * d_missing * d_observed)), means_missing(static_cast<std::size_t>(K * d_missing)),
+        covariances_missing(static_cast<std::size_t>(K * d_missing * d_missing)), scales(static_cast<std::size_t>(K * d_missing)),
+        inverse_scales(static_cast<std::size_t>(K * d_missing));
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+    const uint32_t* coordinates = reinterpret_cast<const uint32_t*>(observed.data());
+    check(mlhip_em_condition(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, means_.data(), cov_flat.data(), coordinates,
+                             static_cast<uint32_t>(d_observed), means_observed.data(), covariances_observed.data(), maps.data(),
+                             means_missing.data()));
+    check(mlhip_em_condition_covariances(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, cov_flat.data(), coordinates,
+                                         static_cast<uint32_t>(d_observed), covariances_missing.data(), nullptr));
+    check(mlhip_em_condition_scales(K, static_cast<uint32_t>(d_missing), covariances_missing.data(), scales.data(), inverse_scales.data()));
+    MatrixXd out(d_missing, n_probabilities * n);
+    if (!n || !n_probabilities) return out;
+    mlhip_ctx* ctx = device::context();
+    const Index batch = Clustering::detail::score_batch_rows();
+    std::vector<double> block;                                   // (a batch's quantiles lie batch rows apart, the result's n: one copy per probability)
+    for (Index first = 0; first < n; first += batch) {
+        const Index rows = std::min(batch, n - first);
+        DataGuard dev;
+        check(mlhip_data_upload(ctx, data_observed.col(first), static_cast<uint32_t>(d_observed), static_cast<uint64_t>(rows),
+                                data_observed.outerStride(), &dev.h));
+        if (values) {
+            check(mlhip_em_conditional_cdfs(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
+                                            covariances_observed.data(), maps.data(), means_missing.data(), scales.data(), inverse_scales.data(),
+                                            values->col(first), values->outerStride(), out.col(first), d_missing, nullptr, d_missing, nullptr));
+            continue;
+        }
+        const bool whole = rows == n;                          // (one batch: the call writes the result in place)
+        if (!whole) block.resize(static_cast<std::size_t>(n_probabilities * rows * d_missing));
+        check(mlhip_em_conditional_quantiles(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
+                                             covariances_observed.data(), maps.data(), means_missing.data(), scales.data(), inverse_scales.data(),
+                                             probabilities->data(), static_cast<uint32_t>(n_probabilities), whole ? out.data() : block.data(),
+                                             d_missing, nullptr, d_missing, nullptr, nullptr));
+        if (whole) break;
+        for (Index q = 0; q < n_probabilities; ++q)
+            std::copy_n(block.data() + static_cast<std::size_t>(q * rows * d_missing), rows * d_missing, out.col(q * n + first));
+    }
+    return out;
+}
+
+MatrixXd EM::conditional_cdfs(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, ConstMatrixRef values) const
+{
+    return conditional_distribution(observed, data_observed, &values, nullptr);
+}
+
+MatrixXd EM::conditional_quantiles(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed,
+                                   const std::vector<double>& probabilities) const
+{
+    return conditional_distribution(observed, data_observed, nullptr, &probabilities);
+}
+
 void EM::process_covariances(const Index number_dimensions)
 {
     // Inverse and sqrt(det) of every covariance for the host point query (ML/EM.cpp:274-287).

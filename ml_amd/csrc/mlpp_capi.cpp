@@ -277,6 +277,38 @@ int mlpp_em_conditional_variances(const mlpp_em* h, const uint32_t* observed, ui
         if (means_out) std::copy_n(means.data(), means.size(), means_out);
     });
 }
+int mlpp_em_conditional_cdfs(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                             const double* values, double* out)
+{
+    return guarded([&] {
+        need(h);
+        if (n_observed) need(observed);
+        if (n && n_observed) { need(data_observed); need(values); need(out); }
+        if (n > static_cast<uint64_t>(std::numeric_limits<Index>::max())) throw std::invalid_argument("EM: Too many samples");
+        const std::vector<unsigned int> coordinates(observed, observed + n_observed);
+        const Index d = h->em.means().rows(), missing = d > static_cast<Index>(n_observed) ? d - static_cast<Index>(n_observed) : 0;
+        const MatrixXd v = h->em.conditional_cdfs(coordinates, ConstMatrixRef(data_observed, n_observed, static_cast<Index>(n), n_observed),
+                                                  ConstMatrixRef(values, missing, static_cast<Index>(n), missing));
+        std::copy_n(v.data(), v.size(), out);
+    });
+}
+int mlpp_em_conditional_quantiles(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
+                                  const double* probabilities, uint64_t n_probabilities, double* out)
+{
+    return guarded([&] {
+        need(h);
+        if (n_observed) need(observed);
+        if (n_probabilities) need(probabilities);
+        if (n && n_observed) need(data_observed);
+        if (n && n_observed && n_probabilities) need(out);
+        if (n > static_cast<uint64_t>(std::numeric_limits<Index>::max())) throw std::invalid_argument("EM: Too many samples");
+        if (n_probabilities > 0xFFFFFFFFull) throw std::invalid_argument("EM: too many probabilities");
+        const std::vector<unsigned int> coordinates(observed, observed + n_observed);
+        const std::vector<double> p(probabilities, probabilities + n_probabilities);
+        const MatrixXd v = h->em.conditional_quantiles(coordinates, ConstMatrixRef(data_observed, n_observed, static_cast<Index>(n), n_observed), p);
+        std::copy_n(v.data(), v.size(), out);
+    });
+}
 int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out)
 {
     return guarded([&] {

@@ -715,6 +715,21 @@ ConditionSampleRoute condition_sample_route(const mlhip_data* data, int K, int d
 /// sized for the K log-responsibilities plus `out_doubles` per row: the call's outputs (dM or dM^2, dM more with the mean) and, on
 /// the plain tier, that kernel's 2 dM doubles of work. No row depends on the chunk.
 ConditionRoute condition_variance_route(const mlhip_data* data, int K, int dM, bool full, bool with_means);
+/// mlhip_em_conditional_cdfs / mlhip_em_conditional_quantiles: condition_route's E-step tier, switches and chunking, with the kernel
+/// tier em_condition_quantile_route (device/em_condition_quantile.hip) names for (dO, dM) and the call, and the rows per chunk sized so
+/// that the K log-responsibilities, the mean if asked for, and the CDF's values and output -- or the blocks (and trip counts) of
+/// min(n_prob, kConditionQuantileGroup) probabilities -- stay within kScoreScratchBytes (MLHIP_CONDITION_ROWS=n overrides, rounded UP
+/// to whole tiles). `group`: how many probabilities one launch behind a chunk's E-step takes -- as many as fit the same bound, at
+/// least 1, and at most MLHIP_CONDITION_GROUP=n where that is set. No row depends on either.
+constexpr uint32_t kConditionQuantileGroup = 8;
+struct ConditionQuantileRoute {
+    EmRoute em;
+    int kernel = kConditionRegisters;
+    uint32_t chunk_rows = 0, group = 1;
+    bool skip = true;
+};
+ConditionQuantileRoute condition_quantile_route(const mlhip_data* data, int K, int dM, bool quantile, uint32_t n_prob, bool with_means,
+                                                bool with_iterations);
 /// The conditioning kernels' table on the host: K records [mu_O | mu_M | A^T] in the paddings of `kernel` (device.hpp condition_pad):
 /// +0.0, and -0.0 in the rows of A^T beyond dO. With `factors` (K x dM x dM row-major lower factors; mlhip_em_conditional_samples) every
 /// record carries its factor behind it, the lower triangle packed row by row in the padded dM (condition_sample_record_doubles).

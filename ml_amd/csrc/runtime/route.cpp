@@ -36,6 +36,7 @@ struct Switches {
     bool condition_plain;       // MLHIP_CONDITION=plain: the conditioning pass takes its plain tier at every shape
     long condition_rows;        // MLHIP_CONDITION_ROWS=n: rows per chunk of the conditioning pass (0: by the scratch bound)
     bool condition_skip;        // on unless MLHIP_CONDITION_SKIP=0: components without a share in a wave's rows are passed over
+    long condition_group;       // MLHIP_CONDITION_GROUP=n: at most n probabilities per launch of the quantile search (0: as many as fit the scratch bound)
 };
 
 Switches read_switches()
@@ -79,6 +80,8 @@ Switches read_switches()
     const char* condition_rows = std::getenv("MLHIP_CONDITION_ROWS");
     s.condition_rows = condition_rows && *condition_rows ? std::atol(condition_rows) : 0;
     s.condition_skip = env_char("MLHIP_CONDITION_SKIP") != '0';
+    const char* condition_group = std::getenv("MLHIP_CONDITION_GROUP");
+    s.condition_group = condition_group && *condition_group ? std::atol(condition_group) : 0;
     return s;
 }
 
@@ -189,6 +192,32 @@ ConditionRoute condition_variance_route(const mlhip_data* data, int K, int dM, b
     if (rows < tile) rows = tile;
     if (rows > data->n_pad) rows = data->n_pad;
     r.chunk_rows = (uint32_t)rows;
+    return r;
+}
+
+ConditionQuantileRoute condition_quantile_route(const mlhip_data* data, int K, int dM, bool quantile, uint32_t n_prob, bool with_means,
+                                                bool with_iterations)
+{
+    const Switches sw = read_switches();
+    ConditionQuantileRoute r;
+    r.em = em_route(data, K, Covariance::Full);
+    r.kernel = sw.condition_plain ? kConditionPlain : em_condition_quantile_route(data->d, dM, quantile);
+    r.skip = sw.condition_skip;
+    const uint64_t tile = kSampleTile, budget = kScoreScratchBytes / sizeof(double);
+    // per row: the K log-responsibilities and the mean; the CDF's values and its output, or the blocks of a group of probabilities
+    // (with the trip counts: a uint32 each, counted as a double)
+    const uint64_t fixed = (uint64_t)K + (with_means ? (uint64_t)dM : 0) + (quantile ? 0 : (uint64_t)dM);
+    const uint64_t block = (uint64_t)dM * (quantile && with_iterations ? 2 : 1);
+    const uint64_t sized_for = quantile ? std::max<uint64_t>(1, std::min<uint64_t>(n_prob, kConditionQuantileGroup)) : 1;
+    uint64_t rows = sw.condition_rows > 0 ? (uint64_t)sw.condition_rows : budget / (fixed + sized_for * block);
+    rows = sw.condition_rows > 0 ? (rows + tile - 1) / tile * tile : rows / tile * tile;
+    if (rows < tile) rows = tile;
+    if (rows > data->n_pad) rows = data->n_pad;
+    r.chunk_rows = (uint32_t)rows;
+    const uint64_t per_row = budget / rows;
+    const uint64_t fit = per_row > fixed ? (per_row - fixed) / block : 0;
+    r.group = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fit, std::max<uint32_t>(n_prob, 1)));
+    if (sw.condition_group > 0 && (uint64_t)sw.condition_group < r.group) r.group = (uint32_t)sw.condition_group;   // (no bit depends on it)
     return r;
 }
 
