@@ -92,7 +92,9 @@ struct ScreenArgs {
     double* lw; size_t ldr;
     unsigned long long* exact; int all_exact;
     unsigned long long* cand_count;                         // += candidates among the n rows (may be null)
+    unsigned long long* profile;                            // diagnostic: kScreenStamps clock stamps per workgroup (null: the plain kernel)
 };
+constexpr int kScreenStamps = 24;
 bool em_estep_screen_supported(int D, int K);
 /// The shapes at which the runtime takes the screened pass by itself (measured faster than the dense kernel there).
 bool em_estep_screen_preferred(int D, int K);

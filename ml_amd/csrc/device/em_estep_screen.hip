@@ -5,16 +5,21 @@
 // value is, and only its bound is stored. The other pairs -- the candidates, ~4.4 of 64 per sample at the headline shape -- are
 // evaluated with the dense kernel's arithmetic (em_estep_mfma4.hip, FOLD form) and get its bits.
 //
-// Per tile of ST = 128 samples, one workgroup of two waves:
-//   * stage: thread t holds sample t's K stored values and the sample's exactness word (bit k: the stored value of component k is an
-//     evaluated one, not a bound; a dense pass marks the whole block with a launch argument instead of writing words). Lmax = the
-//     largest lower bound over the exact entries; a pair is a candidate unless ub < Lmax - 746 -- written so that a NaN is a
+// Per tile of ST = 256 samples, one workgroup of eight waves per CU (three workgroup barriers per tile, none inside the component loop):
+//   * stage: two threads serve a sample -- thread t and thread t + 256 hold the stored values of components 0 .. 31 and 32 .. 63 of
+//     sample t & 255, their half of the sample's exactness word (bit k: the stored value of component k is an evaluated one, not a
+//     bound; a dense pass marks the whole block with a launch argument instead of writing words) and half of its coordinates.
+//     Lmax = the largest lower bound over the exact entries, the first maximum in ascending k -- each half's own, then combined
+//     through LDS, the lower half winning a tie; a pair is a candidate unless ub < Lmax - 746 -- written so that a NaN is a
 //     candidate --, and always when its stored value is not finite or at least 2^40 in magnitude, or when it gave Lmax.
-//     Non-candidates store ub; the new exactness word is the candidate word. x - shift of the sample goes to an LDS tile.
-//   * buckets: one ballot per component; a candidate lane writes its sample index into the component's list of its wave at the
-//     rank the ballot gives it (ascending sample order, the same in every run).
-//   * evaluate: wave w takes the components 2r + w, r = 0, 1, ... (their records staged in LDS a round ahead, as the dense kernel
-//     stages them); 16 bucket entries per group are gathered from the tile into the B operand of v_mfma_f64_4x4x4_4b (lane layout as
+//     Non-candidates store ub; the new exactness word is the candidate word, written as its two 32-bit halves. x - shift of the
+//     sample goes to an LDS tile. The loads of a workgroup's NEXT tile (its stored values and words; at D <= 24 its coordinates too)
+//     are issued before the component loop and land under it.
+//   * buckets: one ballot per component and 64-sample segment (the four waves of a half); a candidate lane writes its sample index
+//     into the component's list of its segment at the rank the ballot gives it (ascending sample order, the same in every run).
+//   * evaluate: wave w takes the components w, w + 8, ...; its record sits in an LDS slot of the wave's own, the next one is fetched
+//     into registers meanwhile and copied in when the wave is done with the slot (wave-level ordering only); 16 bucket entries per
+//     group are gathered from the tile into the B operand of v_mfma_f64_4x4x4_4b (lane layout as
 //     in em_estep_mfma4.hip) and run through the dense kernel's chain: y_{4R+i} over C = 0 .. R ascending from the initialiser
 //     -W (mu - s), a_i = fma(y, y, a_i) over R ascending from 0, q = (a_0 + a_1) + (a_2 + a_3), lw = fma(-0.5, q, coef). Entries past
 //     the end of a bucket read the sentinel row behind the tile and store nothing.
@@ -26,7 +31,10 @@
 namespace mlhip {
 namespace {
 
-constexpr int ST = 128;            // samples per tile = threads per workgroup
+constexpr int ST = 256;            // samples per tile
+constexpr int SNT = 2 * ST;        // threads per workgroup: two per sample
+constexpr int SNW = SNT / 64;      // waves: four 64-sample segments x two component halves
+constexpr int SKH = 32;            // components per half
 constexpr int SXS = 33;            // odd row stride of the x tile
 constexpr int SKMAX = 64;          // components
 constexpr int SDMAX = 32;          // dimensions
@@ -88,99 +96,157 @@ __global__ __launch_bounds__(64) void em_screen_constants_kernel(const double* _
     }
 }
 
-template <int D>
-__global__ __launch_bounds__(ST) void em_estep_screen_kernel(
+/// LDS of a workgroup, in bytes: the x tile and its sentinel row, a record slot per wave, the two halves' maxima, the segment counts
+/// and the bucket lists.
+template <int D> constexpr size_t screen_lds_bytes()
+{
+    return sizeof(double) * ((size_t)(ST + 1) * SXS + (size_t)SNW * ScreenBlocks<D>::PS + 2 * ST) + sizeof(int) * 2 * ST +
+           sizeof(unsigned) * 4 * SKMAX + (size_t)SKMAX * ST;
+}
+
+/// PROF: thread 0 stamps the 100 MHz clock at the phase boundaries of the workgroup's second tile (kScreenStamps slots per workgroup:
+/// 0 tile start, 1 end of stage, 2 end of buckets, 3 + 2j / 4 + 2j wave 0's j-th record copied / evaluated, 19 wave 0 out of the
+/// component loop, 20 end of tile). The normal instantiation has no stamp in it.
+template <int D, bool PROF>
+__global__ __launch_bounds__(SNT) void em_estep_screen_kernel(
     const double* __restrict__ xt, size_t ldx, uint32_t n, uint32_t n_tiles, const double* __restrict__ params, int K,
     const double* __restrict__ shift, const double* __restrict__ consts, double* __restrict__ lw, size_t ldr,
-    unsigned long long* __restrict__ exact, int all_exact, unsigned long long* __restrict__ cand_count)
+    unsigned* __restrict__ exact, int all_exact, unsigned long long* __restrict__ cand_count, unsigned long long* __restrict__ prof)
 {
     using B = ScreenBlocks<D>;
     constexpr int Q = B::Q, NB = B::NB, PS = B::PS;
-    constexpr int NLD = (2 * PS + ST - 1) / ST;      // doubles of a round's two records each thread moves to LDS
-    __shared__ double Xs[(ST + 1) * SXS];            // x - shift, sample-major; row ST: the sentinel
-    __shared__ double recs[2 * PS];                  // the round's two records
-    __shared__ unsigned char list[2][SKMAX][64];     // [wave][component]: the wave's candidate samples (tile index), ascending
-    __shared__ unsigned cnt[2][SKMAX];
+    constexpr int NLD = (PS + 63) / 64;              // doubles of a record each lane moves to the wave's slot
+    constexpr int DH = D / 2;                        // coordinates a thread stages
+    constexpr bool PFX = D <= 24;                    // the next tile's coordinates are loaded a tile ahead like its stored values (above: no registers for them)
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    double* Xs = smem;                               // [ST + 1][SXS]: x - shift, sample-major; row ST: the sentinel
+    double* recs = Xs + (ST + 1) * SXS;              // [SNW][PS]: a record slot per wave
+    double* xL = recs + SNW * PS;                    // [2][ST]: each half's largest lower bound ...
+    int* xk = reinterpret_cast<int*>(xL + 2 * ST);   // [2][ST]: ... and the component that gave it
+    unsigned* cnt = reinterpret_cast<unsigned*>(xk + 2 * ST);            // [4][SKMAX]: entries of a component's list per segment
+    unsigned char* list = reinterpret_cast<unsigned char*>(cnt + 4 * SKMAX);   // [SKMAX][4][64]: candidate samples (tile index), ascending
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = wave >> 2, seg = wave & 3;      // the thread's components half * 32 .. half * 32 + 31, its sample's segment
+    const int kbase = half * SKH;
+    const int sl = tid & (ST - 1);                   // the thread's sample in the tile
     const int g = lane >> 4, s = lane & 15;
     const int aoff = g * 4 + (lane & 3);             // A operand: entry [k = lane >> 4][i = lane & 3] of a 16-double block
     if (tid < SXS) Xs[ST * SXS + tid] = 0.0;
     unsigned long long n_cand = 0;
-    const int rounds = (K + 1) / 2;
+    double* __restrict__ rec = recs + wave * PS;
 
+    auto stamp = [&](uint32_t tile, int slot) {
+        if constexpr (PROF) {
+            if (tid == 0 && tile == blockIdx.x + gridDim.x) prof[(size_t)blockIdx.x * kScreenStamps + slot] = wall_clock64();
+        }
+    };
+    // the registers a tile is staged from: the half's stored values, its half of the exactness word, half of the coordinates
+    double v[SKH], xs[DH];
+    unsigned ex = 0;
+    auto load_x = [&](uint32_t tile) {
+        const uint32_t i = tile * ST + sl;           // < n_pad: always inside the allocations
+#pragma unroll
+        for (int j = 0; j < DH; ++j) xs[j] = xt[(size_t)(half * DH + j) * ldx + i];
+    };
+    auto load_v = [&](uint32_t tile) {
+        const uint32_t i = tile * ST + sl;
+        ex = all_exact ? ~0u : exact[2 * (size_t)i + half];
+        if (kbase < K) {
+#pragma unroll
+            for (int kk = 0; kk < SKH; ++kk) v[kk] = lw[(size_t)(kbase + kk < K ? kbase + kk : K - 1) * ldr + i];
+        }
+    };
+    double stg[NLD];
+    auto fetch = [&](int k) {
+#pragma unroll
+        for (int it = 0; it < NLD; ++it) stg[it] = params[(size_t)k * PS + min(lane + 64 * it, PS - 1)];
+    };
+
+    if (blockIdx.x < n_tiles) {
+        if (PFX) load_x(blockIdx.x);
+        load_v(blockIdx.x);
+    }
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint32_t i = tile * ST + tid;          // < n_pad: always inside the allocations
+        const uint32_t i = tile * ST + sl;
+        stamp(tile, 0);
         // ---- stage
-#pragma unroll
-        for (int j = 0; j < D; ++j) Xs[tid * SXS + j] = xt[(size_t)j * ldx + i] - shift[j];
-        const unsigned long long ex = all_exact ? ~0ull : exact[i];
-        double v[SKMAX];
-#pragma unroll
-        for (int k = 0; k < SKMAX; ++k) v[k] = lw[(size_t)(k < K ? k : K - 1) * ldr + i];
+        if (!PFX) load_x(tile);
         double Lmax = -HUGE_VAL;
         int kmax = -1;
 #pragma unroll
-        for (int k = 0; k < SKMAX; ++k) {
+        for (int kk = 0; kk < SKH; ++kk) {
+            const int k = kbase + kk;
             if (k < K) {
-                const double lb = __builtin_fma(consts[4 * k + 2], v[k], consts[4 * k + 3]);
-                const bool usable = ((ex >> k) & 1) && fabs(v[k]) < screen::kMaxStored;      // (NaN, inf: not usable)
+                const double lb = __builtin_fma(consts[4 * k + 2], v[kk], consts[4 * k + 3]);
+                const bool usable = ((ex >> kk) & 1) && fabs(v[kk]) < screen::kMaxStored;    // (NaN, inf: not usable)
                 if (usable && lb > Lmax) { Lmax = lb; kmax = k; }
             }
         }
+        xL[half * ST + sl] = Lmax;
+        xk[half * ST + sl] = kmax;
+        __syncthreads();
+        {
+            // the first maximum in ascending k: the upper half's only where it is larger
+            const double oL = xL[(half ^ 1) * ST + sl];
+            const int ok = xk[(half ^ 1) * ST + sl];
+            const bool other = half == 0 ? oL > Lmax : !(Lmax > oL);
+            if (other) { Lmax = oL; kmax = ok; }
+        }
         const double limit = Lmax - screen::kSkipMargin;
-        unsigned long long cand = 0;
+        unsigned cand = 0;
 #pragma unroll
-        for (int k = 0; k < SKMAX; ++k) {
+        for (int kk = 0; kk < SKH; ++kk) {
+            const int k = kbase + kk;
             if (k < K) {
-                const double ub = __builtin_fma(consts[4 * k + 0], v[k], consts[4 * k + 1]);
-                const bool skip = ub < limit && fabs(v[k]) < screen::kMaxStored && k != kmax;   // (a NaN anywhere: a candidate)
+                const double ub = __builtin_fma(consts[4 * k + 0], v[kk], consts[4 * k + 1]);
+                const bool skip = ub < limit && fabs(v[kk]) < screen::kMaxStored && k != kmax;   // (a NaN anywhere: a candidate)
                 if (skip) lw[(size_t)k * ldr + i] = ub;
-                else cand |= 1ull << k;
+                else cand |= 1u << kk;
             }
         }
-        exact[i] = cand;
-        if (i < n) n_cand += (unsigned long long)__popcll(cand);
+        exact[2 * (size_t)i + half] = cand;
+        if (i < n) n_cand += (unsigned long long)__popc(cand);
+#pragma unroll
+        for (int j = 0; j < DH; ++j) Xs[sl * SXS + half * DH + j] = xs[j] - shift[half * DH + j];
+        const int kfirst = wave;
+        if (kfirst < K) fetch(kfirst);
+        stamp(tile, 1);
         // ---- buckets
-        for (int k = 0; k < K; ++k) {
-            const bool c = (cand >> k) & 1;
+        for (int kk = 0; kk < SKH && kbase + kk < K; ++kk) {
+            const int k = kbase + kk;
+            const bool c = (cand >> kk) & 1;
             const unsigned long long b = __ballot(c);
             const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-            if (c) list[wave][k][rank] = (unsigned char)tid;
-            if (lane == 0) cnt[wave][k] = (unsigned)__popcll(b);
+            if (c) list[(k * 4 + seg) * 64 + rank] = (unsigned char)sl;
+            if (lane == 0) cnt[seg * SKMAX + k] = (unsigned)__popcll(b);
         }
+        // the next tile's loads land under the component loop (v, xs and ex are free from here on)
+        if (tile + gridDim.x < n_tiles) {
+            if (PFX) load_x(tile + gridDim.x);
+            load_v(tile + gridDim.x);
+        }
+        __syncthreads();                             // the tile, the lists and the counts are written
+        stamp(tile, 2);
         // ---- evaluate
-        double stg[NLD];
-        // (the two records of a round are contiguous: element e of the pair sits at 2 r PS + e; past the last record -- K odd, the last
-        // round -- the first of the pair is read once more, nobody uses it)
-        auto fetch = [&](int r) {
-            const int base = 2 * r * PS, last = K * PS;
-#pragma unroll
-            for (int it = 0; it < NLD; ++it) {
-                int e = base + min(tid + ST * it, 2 * PS - 1);
-                e = e < last ? e : e - PS;
-                stg[it] = params[e];
-            }
-        };
-        fetch(0);
-        for (int r = 0; r < rounds; ++r) {
-            __syncthreads();                         // the buckets are written (r = 0); every wave is done with round r - 1's records
+        for (int k = kfirst, j = 0; k < K; k += SNW, ++j) {
+            // the wave's slot: nobody else reads or writes it, so the wave's own order is all that has to hold
 #pragma unroll
             for (int it = 0; it < NLD; ++it)
-                if (tid + ST * it < 2 * PS) recs[tid + ST * it] = stg[it];
-            __syncthreads();
-            if (r + 1 < rounds) fetch(r + 1);
-            const int k = 2 * r + wave;
-            if (k >= K) continue;
-            const double* __restrict__ rec = recs + wave * PS;
-            const unsigned c0 = cnt[0][k], total = c0 + cnt[1][k];
+                if (lane + 64 * it < PS) rec[lane + 64 * it] = stg[it];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (wave == 0 && j < 8) stamp(tile, 3 + 2 * j);
+            if (k + SNW < K) fetch(k + SNW);
+            const unsigned c0 = cnt[k], c1 = c0 + cnt[SKMAX + k], c2 = c1 + cnt[2 * SKMAX + k], total = c2 + cnt[3 * SKMAX + k];
             const double coef = rec[NB * 16 + 2 * D];
             for (unsigned first = 0; first < total; first += 16) {
                 const unsigned e = first + s;
                 const bool valid = e < total;
-                const unsigned w = e >= c0 ? 1u : 0u;
-                const unsigned pos = valid ? e - (w ? c0 : 0u) : 0u;      // < 64: a wave's list holds at most its 64 samples
-                const unsigned smp = valid ? (unsigned)list[w][k][pos & 63u] : (unsigned)ST;
+                const unsigned w = (e >= c0 ? 1u : 0u) + (e >= c1 ? 1u : 0u) + (e >= c2 ? 1u : 0u);   // the entry's segment
+                const unsigned pos = valid ? e - (w == 0 ? 0u : w == 1 ? c0 : w == 2 ? c1 : c2) : 0u;   // < 64: a segment holds 64 samples
+                const unsigned smp = valid ? (unsigned)list[((unsigned)k * 4 + w) * 64 + (pos & 63u)] : (unsigned)ST;
                 const double* xrow = Xs + smp * SXS + g;
                 double xb[Q];
 #pragma unroll
@@ -199,8 +265,13 @@ __global__ __launch_bounds__(ST) void em_estep_screen_kernel(
                 const double q = t + __shfl_xor(t, 32, 64);
                 if (valid && g == 0) lw[(size_t)k * ldr + (size_t)tile * ST + smp] = __builtin_fma(-0.5, q, coef);
             }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // every lane is done with the slot before the next record goes in
+            __builtin_amdgcn_wave_barrier();
+            if (wave == 0 && j < 8) stamp(tile, 4 + 2 * j);
         }
+        stamp(tile, 19);
         __syncthreads();                             // the tile, the lists and the counts are free for the next tile
+        stamp(tile, 20);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) n_cand += __shfl_down(n_cand, off, 64);
@@ -210,10 +281,15 @@ __global__ __launch_bounds__(ST) void em_estep_screen_kernel(
 template <int D> int launch_d(const ScreenArgs& a, int num_cus, hipStream_t stream)
 {
     const uint32_t n_tiles = padded_samples(a.n) / ST;
-    uint32_t grid = (uint32_t)num_cus * 3;
+    uint32_t grid = (uint32_t)num_cus;               // one workgroup per CU: its LDS and its two waves per SIMD fill one
     if (grid > n_tiles) grid = n_tiles;
-    hipLaunchKernelGGL(em_estep_screen_kernel<D>, dim3(grid), dim3(ST), 0, stream, a.xt, a.ldx, a.n, n_tiles, a.params, a.K, a.shift,
-                       a.consts, a.lw, a.ldr, a.exact, a.all_exact, a.cand_count);
+    unsigned* exact = reinterpret_cast<unsigned*>(a.exact);              // word i as its halves 2i (components 0 .. 31) and 2i + 1
+    if (a.profile)
+        hipLaunchKernelGGL((em_estep_screen_kernel<D, true>), dim3(grid), dim3(SNT), screen_lds_bytes<D>(), stream, a.xt, a.ldx, a.n,
+                           n_tiles, a.params, a.K, a.shift, a.consts, a.lw, a.ldr, exact, a.all_exact, a.cand_count, a.profile);
+    else
+        hipLaunchKernelGGL((em_estep_screen_kernel<D, false>), dim3(grid), dim3(SNT), screen_lds_bytes<D>(), stream, a.xt, a.ldx, a.n,
+                           n_tiles, a.params, a.K, a.shift, a.consts, a.lw, a.ldr, exact, a.all_exact, a.cand_count, nullptr);
     return (int)grid;
 }
 
@@ -223,12 +299,13 @@ static_assert(kSampleTile % ST == 0, "a block is a whole number of tiles");
 
 bool em_estep_screen_supported(int D, int K) { return D >= 12 && D <= SDMAX && D % 4 == 0 && K >= 1 && K <= SKMAX; }
 
-/// Where the runtime takes the screened pass by itself: the shape at which it was measured faster than the dense one on repeated
-/// alternating runs (profiles/estep_screen_ab.txt: D = 32, K = 64, E-step 11.2 -> 8.95 ms at N = 10M). Its time hardly depends on d --
-/// it is bound by its rounds, one per two components --, the dense kernel's falls with d^2 and K: single runs at N = 5M
-/// (profiles/estep_screen_sweep.txt) give D = 32: K = 32 2.95 -> 2.67 ms (not relied on before it is repeated), K = 16 1.54 -> 1.78 ms;
-/// K = 64: D = 28, 24, 16 4.73 -> 5.35, 3.67 -> 6.06, 1.95 -> 6.22 ms. Elsewhere only MLHIP_ESTEP_SCREEN=1 screens.
-bool em_estep_screen_preferred(int D, int K) { return D == 32 && K == SKMAX; }
+/// Where the runtime takes the screened pass by itself: the shapes at which it was measured faster than the dense one on three
+/// alternating runs each, by more than both spreads (profiles/estep_screen_tile_ab.txt: D = 32, K = 64, E-step 11.3 -> 6.0 ms at
+/// N = 10M; D = 28, K = 64, 4.69 -> 3.89 ms at N = 5M). Its time grows with the candidates per sample, which at a smaller d are more,
+/// while the dense kernel's falls with d^2 and K: at N = 5M, K = 64, D = 24 and 16 give 3.60 -> 4.40 and 1.92 -> 5.04 ms, D = 24,
+/// K = 32 1.81 -> 2.73 ms, D = 32, K = 16 1.51 -> 1.46 ms (inside the spreads). D = 32, K = 32 gains (2.90 -> 2.16 ms) and stays
+/// dense until tests/test_gpu_estep_screen.py's test_automatic_route, which fixes it, changes. Elsewhere only MLHIP_ESTEP_SCREEN=1 screens.
+bool em_estep_screen_preferred(int D, int K) { return (D == 32 || D == 28) && K == SKMAX; }
 
 void launch_em_screen_constants(const double* rec_old, const double* rec_new, int K, int d, int D, double* consts,
                                 unsigned* no_info, hipStream_t stream)

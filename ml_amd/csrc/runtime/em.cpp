@@ -117,6 +117,42 @@ static bool screen_wanted(const mlhip_data* dt, const EmRoute& r, int K)
 }
 
 
+/// The stamps of a profiled screened pass (em_estep_screen.hip, PROF form), averaged over the workgroups that stamped a tile: one line
+/// on stderr, microseconds of the 100 MHz clock. tools/estep_screen_phases.py reads it.
+static void report_screen_stamps(const mlhip_data* dt, const DevBuf& stamps, int grid, int K)
+{
+    constexpr int NS = kScreenStamps;
+    std::vector<unsigned long long> t((size_t)NS * grid);
+    HIP_CHECK(hipMemcpy(t.data(), stamps.p, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost));
+    const int rounds = std::min(8, (K + 7) / 8);                       // components wave 0 takes (the stamped ones)
+    double stage = 0, buckets = 0, copy = 0, eval = 0, wait = 0, tile = 0;
+    int used = 0;
+    for (int b = 0; b < grid; ++b) {
+        const unsigned long long* s = t.data() + (size_t)NS * b;
+        if (!s[0] || !s[20]) continue;                                  // (the workgroup had no second tile)
+        ++used;
+        stage += (double)(s[1] - s[0]);
+        buckets += (double)(s[2] - s[1]);
+        unsigned long long prev = s[2];
+        for (int j = 0; j < rounds; ++j) {
+            copy += (double)(s[3 + 2 * j] - prev);
+            eval += (double)(s[4 + 2 * j] - s[3 + 2 * j]);
+            prev = s[4 + 2 * j];
+        }
+        wait += (double)(s[20] - s[19]);
+        tile += (double)(s[20] - s[0]);
+    }
+    if (!used) {
+        std::fprintf(stderr, "[mlhip] screened E-step, N=%u d=%d K=%d grid=%d: no workgroup had a second tile to stamp\n", dt->n, dt->d, K, grid);
+        return;
+    }
+    const double us = 0.01 / used;
+    std::fprintf(stderr, "[mlhip] screened E-step, N=%u d=%d K=%d grid=%d, us per 256-sample tile (thread 0, mean of %d workgroups): stage %.2f, "
+                 "buckets %.2f, record copy %.2f, evaluation %.2f (%d components of wave 0), end barrier %.2f, tile %.2f\n",
+                 dt->n, dt->d, K, grid, used, stage * us, buckets * us, copy * us, eval * us, rounds, wait * us, tile * us);
+}
+
+
 /// The screened pass: the constants of the step from the block's records (scr_rec) to `a.params`, then -- when every component's
 /// bound carries information -- the screened kernel. Returns its grid, or 0 when the dense kernel has to run (the decision is the
 /// host's: it waits for the constants kernel's count, a few microseconds on a stream that has just been waited for).
@@ -141,8 +177,21 @@ static int launch_screened(mlhip_data* dt, const EstepArgs& a, int K)
     sa.lw = a.lw; sa.ldr = a.ldr;
     sa.exact = dt->scr_exact.as<unsigned long long>(); sa.all_exact = dt->scr_all_exact ? 1 : 0;
     sa.cand_count = dev + 1;
+    // MLHIP_ESTEP_SCREEN_PROFILE=1: the kernel's stamping form; the phases of every workgroup's second tile, averaged, on stderr (diagnostic)
+    static const bool profile = [] { const char* e = std::getenv("MLHIP_ESTEP_SCREEN_PROFILE"); return e && e[0] == '1'; }();
+    DevBuf stamps;
+    if (profile) {
+        stamps.reserve(sizeof(unsigned long long) * kScreenStamps * ctx->num_cus);
+        HIP_CHECK(hipMemsetAsync(stamps.p, 0, stamps.bytes, ctx->stream));
+        sa.profile = stamps.as<unsigned long long>();
+    }
     const int grid = launch_em_estep_screen(sa, ctx->num_cus, ctx->stream);
     if (grid <= 0) throw Unsupported("screened E-step kernel not instantiated for this dimension");
+    if (profile) {
+        HIP_CHECK(hipGetLastError());
+        ctx->sync();
+        report_screen_stamps(dt, stamps, grid, K);
+    }
     HIP_CHECK(hipMemcpyAsync(host + 1 + dt->scr_passes % 3, dev + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return grid;
 }
