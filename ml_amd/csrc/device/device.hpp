@@ -94,8 +94,16 @@ struct ScreenArgs {
     unsigned long long* cand_count;                         // += candidates among the n rows (may be null)
     unsigned long long* profile;                            // diagnostic: kScreenStamps clock stamps per workgroup (null: the plain kernel)
 };
-constexpr int kScreenStamps = 24;
+/// Stamp slots of a workgroup: 0 tile start, 1 end of stage (the maxima combined), 2 end of buckets, 3 + 2j / 4 + 2j wave 0's j-th record copied /
+/// evaluated (j < kScreenStampRounds: wave 0's components at K = 64 in the four-wave form), then the two below.
+constexpr int kScreenStampRounds = 16;
+constexpr int kScreenStampLoopEnd = 3 + 2 * kScreenStampRounds;        // wave 0 out of the component loop
+constexpr int kScreenStampTileEnd = kScreenStampLoopEnd + 1;           // behind the tile's last barrier
+constexpr int kScreenStamps = 40;
 bool em_estep_screen_supported(int D, int K);
+/// Samples per tile of the form instantiated for D (128 or 256; < 0: not instantiated). A workgroup has tile / 32 waves, 256 / tile
+/// workgroups share a CU, and the grid is at most that many per CU.
+int em_estep_screen_tile(int D);
 /// The shapes at which the runtime takes the screened pass by itself (measured faster than the dense kernel there).
 bool em_estep_screen_preferred(int D, int K);
 /// Returns the grid, or < 0 where the kernel is not instantiated.

@@ -5,7 +5,11 @@
 // value is, and only its bound is stored. The other pairs -- the candidates, ~4.4 of 64 per sample at the headline shape -- are
 // evaluated with the dense kernel's arithmetic (em_estep_mfma4.hip, FOLD form) and get its bits.
 //
-// Per tile of ST = 256 samples, one workgroup of eight waves per CU (three workgroup barriers per tile, none inside the component loop):
+// The tile size ST is a template parameter next to D (screen_tile<D>: one form per D, no switch at run time). ST = 256, one workgroup
+// of eight waves per CU, is what every D is instantiated with; ST = 128 -- four waves, two 64-sample segments, wave w taking the
+// components w, w + 4, ..., two workgroups per CU so that one's stage runs under the other's evaluation -- passes the same tests and
+// was measured slower at D = 28 and 32 (DESIGN 3.3p "The pair": a record fetched twice as often, emptier groups, and no phase got
+// shorter). Per tile of ST samples (three workgroup barriers per tile, none inside the component loop; written for ST = 256):
 //   * stage: two threads serve a sample -- thread t and thread t + 256 hold the stored values of components 0 .. 31 and 32 .. 63 of
 //     sample t & 255, their half of the sample's exactness word (bit k: the stored value of component k is an evaluated one, not a
 //     bound; a dense pass marks the whole block with a launch argument instead of writing words) and half of its coordinates.
@@ -15,8 +19,10 @@
 //     Non-candidates store ub; the new exactness word is the candidate word, written as its two 32-bit halves. x - shift of the
 //     sample goes to an LDS tile. The loads of a workgroup's NEXT tile (its stored values and words; at D <= 24 its coordinates too)
 //     are issued before the component loop and land under it.
-//   * buckets: one ballot per component and 64-sample segment (the four waves of a half); a candidate lane writes its sample index
-//     into the component's list of its segment at the rank the ballot gives it (ascending sample order, the same in every run).
+//   * buckets, in the loop that decides the candidates: one ballot per component and 64-sample segment (the four waves of a half);
+//     a candidate lane writes its sample index into the component's list of its segment at the rank the ballot gives it (ascending
+//     sample order, the same in every run); lane kk of the wave collects component kk's count and the wave stores its <= 32 counts
+//     with one LDS write.
 //   * evaluate: wave w takes the components w, w + 8, ...; its record sits in an LDS slot of the wave's own, the next one is fetched
 //     into registers meanwhile and copied in when the wave is done with the slot (wave-level ordering only); 16 bucket entries per
 //     group are gathered from the tile into the B operand of v_mfma_f64_4x4x4_4b (lane layout as
@@ -31,9 +37,15 @@
 namespace mlhip {
 namespace {
 
-constexpr int ST = 256;            // samples per tile
-constexpr int SNT = 2 * ST;        // threads per workgroup: two per sample
-constexpr int SNW = SNT / 64;      // waves: four 64-sample segments x two component halves
+/// The tile: ST samples, two threads per sample, ST / 64 segments of 64 samples x two component halves = ST / 32 waves. 256 / ST
+/// workgroups share a CU (two waves per SIMD in either form); screen_tile<D> below picks the form per dimension.
+template <int ST> struct ScreenTile {
+    static_assert(ST == 128 || ST == 256, "one or two workgroups per CU");
+    static constexpr int NT = 2 * ST;        // threads per workgroup: two per sample
+    static constexpr int NSEG = ST / 64;     // 64-sample segments
+    static constexpr int NW = NT / 64;       // waves
+    static constexpr int PER_CU = 256 / ST;  // workgroups resident on a CU
+};
 constexpr int SKH = 32;            // components per half
 constexpr int SXS = 33;            // odd row stride of the x tile
 constexpr int SKMAX = 64;          // components
@@ -98,23 +110,29 @@ __global__ __launch_bounds__(64) void em_screen_constants_kernel(const double* _
 
 /// LDS of a workgroup, in bytes: the x tile and its sentinel row, a record slot per wave, the two halves' maxima, the segment counts
 /// and the bucket lists.
-template <int D> constexpr size_t screen_lds_bytes()
+template <int D, int ST> constexpr size_t screen_lds_bytes()
 {
-    return sizeof(double) * ((size_t)(ST + 1) * SXS + (size_t)SNW * ScreenBlocks<D>::PS + 2 * ST) + sizeof(int) * 2 * ST +
-           sizeof(unsigned) * 4 * SKMAX + (size_t)SKMAX * ST;
+    using T = ScreenTile<ST>;
+    return sizeof(double) * ((size_t)(ST + 1) * SXS +(size_t)T::NW * ScreenBlocks<D>::PS + 2 * ST) + sizeof(int) * 2 * ST +
+           sizeof(unsigned) * T::NSEG * SKMAX + (size_t)SKMAX * ST;
 }
+static_assert(2 * screen_lds_bytes<SDMAX, 128>() <= 160 * 1024, "two 128-sample workgroups share a CU's LDS");
 
 /// PROF: thread 0 stamps the 100 MHz clock at the phase boundaries of the workgroup's second tile (kScreenStamps slots per workgroup:
-/// 0 tile start, 1 end of stage, 2 end of buckets, 3 + 2j / 4 + 2j wave 0's j-th record copied / evaluated, 19 wave 0 out of the
-/// component loop, 20 end of tile). The normal instantiation has no stamp in it.
-template <int D, bool PROF>
-__global__ __launch_bounds__(SNT) void em_estep_screen_kernel(
+/// 0 tile start, 1 end of stage -- the sample's maximum is known --, 2 end of the candidate-and-bucket loop, the tile's stores and their barrier, 3 + 2j / 4 + 2j wave 0's j-th record copied / evaluated (j < kScreenStampRounds),
+/// kScreenStampLoopEnd wave 0 out of the component loop, kScreenStampTileEnd end of tile). The normal instantiation has no stamp in it.
+/// The second launch bound pins two waves per SIMD (256 registers a lane) in either form: a 256-thread workgroup alone would be
+/// given 512, and a second workgroup would then not fit next to it.
+template <int D, int ST, bool PROF>
+__global__ __launch_bounds__(2 * ST, 2) void em_estep_screen_kernel(
     const double* __restrict__ xt, size_t ldx, uint32_t n, uint32_t n_tiles, const double* __restrict__ params, int K,
     const double* __restrict__ shift, const double* __restrict__ consts, double* __restrict__ lw, size_t ldr,
     unsigned* __restrict__ exact, int all_exact, unsigned long long* __restrict__ cand_count, unsigned long long* __restrict__ prof)
 {
     using B = ScreenBlocks<D>;
+    using T = ScreenTile<ST>;
     constexpr int Q = B::Q, NB = B::NB, PS = B::PS;
+    constexpr int SNW = T::NW, NSEG = T::NSEG;
     constexpr int NLD = (PS + 63) / 64;              // doubles of a record each lane moves to the wave's slot
     constexpr int DH = D / 2;                        // coordinates a thread stages
     constexpr bool PFX = D <= 24;                    // the next tile's coordinates are loaded a tile ahead like its stored values (above: no registers for them)
@@ -123,11 +141,11 @@ __global__ __launch_bounds__(SNT) void em_estep_screen_kernel(
     double* recs = Xs + (ST + 1) * SXS;              // [SNW][PS]: a record slot per wave
     double* xL = recs + SNW * PS;                    // [2][ST]: each half's largest lower bound ...
     int* xk = reinterpret_cast<int*>(xL + 2 * ST);   // [2][ST]: ... and the component that gave it
-    unsigned* cnt = reinterpret_cast<unsigned*>(xk + 2 * ST);            // [4][SKMAX]: entries of a component's list per segment
-    unsigned char* list = reinterpret_cast<unsigned char*>(cnt + 4 * SKMAX);   // [SKMAX][4][64]: candidate samples (tile index), ascending
+    unsigned* cnt = reinterpret_cast<unsigned*>(xk + 2 * ST);            // [NSEG][SKMAX]: entries of a component's list per segment
+    unsigned char* list = reinterpret_cast<unsigned char*>(cnt + NSEG * SKMAX);   // [SKMAX][NSEG][64]: candidate samples (tile index), ascending
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = wave >> 2, seg = wave & 3;      // the thread's components half * 32 .. half * 32 + 31, its sample's segment
+    const int half = wave / NSEG, seg = wave % NSEG; // the thread's components half * 32 .. half * 32 + 31, its sample's segment
     const int kbase = half * SKH;
     const int sl = tid & (ST - 1);                   // the thread's sample in the tile
     const int g = lane >> 4, s = lane & 15;
@@ -144,17 +162,23 @@ __global__ __launch_bounds__(SNT) void em_estep_screen_kernel(
     // the registers a tile is staged from: the half's stored values, its half of the exactness word, half of the coordinates
     double v[SKH], xs[DH];
     unsigned ex = 0;
+    // (rows are addressed by a pointer that moves a row on, one 64-bit add each: a row offset formed per component is a scalar
+    // product kept in a lane of a spill register and read back for every use)
     auto load_x = [&](uint32_t tile) {
-        const uint32_t i = tile * ST + sl;           // < n_pad: always inside the allocations
+        const double* p = xt + (size_t)(half * DH) * ldx + (tile * ST + sl);   // sample < n_pad: always inside the allocations
 #pragma unroll
-        for (int j = 0; j < DH; ++j) xs[j] = xt[(size_t)(half * DH + j) * ldx + i];
+        for (int j = 0; j < DH; ++j, p += ldx) xs[j] = *p;
     };
     auto load_v = [&](uint32_t tile) {
         const uint32_t i = tile * ST + sl;
         ex = all_exact ? ~0u : exact[2 * (size_t)i + half];
         if (kbase < K) {
+            const double* p = lw + (size_t)kbase * ldr + i;              // components past K - 1 read row K - 1 again (never used)
 #pragma unroll
-            for (int kk = 0; kk < SKH; ++kk) v[kk] = lw[(size_t)(kbase + kk < K ? kbase + kk : K - 1) * ldr + i];
+            for (int kk = 0; kk < SKH; ++kk) {
+                v[kk] = *p;
+                if (kbase + kk + 1 < K) p += ldr;
+            }
         }
     };
     double stg[NLD];
@@ -194,33 +218,37 @@ __global__ __launch_bounds__(SNT) void em_estep_screen_kernel(
             if (other) { Lmax = oL; kmax = ok; }
         }
         const double limit = Lmax - screen::kSkipMargin;
-        unsigned cand = 0;
+        stamp(tile, 1);
+        // ---- candidates and buckets, one loop: the component's candidate lanes are balloted where they are decided
+        unsigned cand = 0, counts = 0;               // counts: lane kk holds the entries of component kbase + kk in this segment
+        // what the wave shares, kept per lane (from tid, not from the wave's scalars): the unrolled loop then compares and addresses
+        // with immediates off one register each, where a scalar per component would sit in a lane of a spill register
+        const int krel = kmax - (tid / ST) * SKH;    // the maximum's component relative to the half (never a kk when it is the other half's, or none)
+        const unsigned lbase = (unsigned)(((tid / ST) * SKH * NSEG + (tid >> 6) % NSEG) * 64);   // list of component kbase, this segment
+        double* ps = lw + (size_t)kbase * ldr + i;   // the sample's stored value of component kbase + kk
 #pragma unroll
         for (int kk = 0; kk < SKH; ++kk) {
             const int k = kbase + kk;
             if (k < K) {
                 const double ub = __builtin_fma(consts[4 * k + 0], v[kk], consts[4 * k + 1]);
-                const bool skip = ub < limit && fabs(v[kk]) < screen::kMaxStored && k != kmax;   // (a NaN anywhere: a candidate)
-                if (skip) lw[(size_t)k * ldr + i] = ub;
-                else cand |= 1u << kk;
+                const bool skip = ub < limit && fabs(v[kk]) < screen::kMaxStored && kk != krel;   // (a NaN anywhere: a candidate)
+                if (skip) *ps = ub;
+                ps += ldr;
+                cand |= (skip ? 0u : 1u) << kk;
+                const unsigned long long b = __builtin_amdgcn_ballot_w64(!skip);
+                // the candidate's place: the list's offset plus its rank among the segment's candidates (ascending sample order)
+                const unsigned at = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, lbase));
+                if (!skip) list[kk * NSEG * 64 + at] = (unsigned char)sl;   // < (k * NSEG + seg) * 64 + 64
+                counts = lane == kk ? (unsigned)__popcll(b) : counts;
             }
         }
+        if (lane < SKH && kbase + lane < K) cnt[seg * SKMAX + kbase + lane] = counts;   // the wave's counts in one write
         exact[2 * (size_t)i + half] = cand;
         if (i < n) n_cand += (unsigned long long)__popc(cand);
 #pragma unroll
         for (int j = 0; j < DH; ++j) Xs[sl * SXS + half * DH + j] = xs[j] - shift[half * DH + j];
         const int kfirst = wave;
         if (kfirst < K) fetch(kfirst);
-        stamp(tile, 1);
-        // ---- buckets
-        for (int kk = 0; kk < SKH && kbase + kk < K; ++kk) {
-            const int k = kbase + kk;
-            const bool c = (cand >> kk) & 1;
-            const unsigned long long b = __ballot(c);
-            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-            if (c) list[(k * 4 + seg) * 64 + rank] = (unsigned char)sl;
-            if (lane == 0) cnt[seg * SKMAX + k] = (unsigned)__popcll(b);
-        }
         // the next tile's loads land under the component loop (v, xs and ex are free from here on)
         if (tile + gridDim.x < n_tiles) {
             if (PFX) load_x(tile + gridDim.x);
@@ -237,16 +265,18 @@ __global__ __launch_bounds__(SNT) void em_estep_screen_kernel(
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (wave == 0 && j < 8) stamp(tile, 3 + 2 * j);
+            if (wave == 0 && j < kScreenStampRounds) stamp(tile, 3 + 2 * j);
             if (k + SNW < K) fetch(k + SNW);
-            const unsigned c0 = cnt[k], c1 = c0 + cnt[SKMAX + k], c2 = c1 + cnt[2 * SKMAX + k], total = c2 + cnt[3 * SKMAX + k];
+            // the ends of the segment lists in the component's bucket (NSEG = 2: c1 and c2 are the total, no entry reaches them)
+            const unsigned c0 = cnt[k], c1 = c0 + cnt[SKMAX + k];
+            const unsigned c2 = NSEG == 4 ? c1 + cnt[(NSEG - 2) * SKMAX + k] : c1, total = NSEG == 4 ? c2 + cnt[(NSEG - 1) * SKMAX + k] : c1;
             const double coef = rec[NB * 16 + 2 * D];
             for (unsigned first = 0; first < total; first += 16) {
                 const unsigned e = first + s;
                 const bool valid = e < total;
-                const unsigned w = (e >= c0 ? 1u : 0u) + (e >= c1 ? 1u : 0u) + (e >= c2 ? 1u : 0u);   // the entry's segment
+                const unsigned w = valid ? (e >= c0 ? 1u : 0u) + (e >= c1 ? 1u : 0u) + (e >= c2 ? 1u : 0u) : 0u;   // the entry's segment, < NSEG
                 const unsigned pos = valid ? e - (w == 0 ? 0u : w == 1 ? c0 : w == 2 ? c1 : c2) : 0u;   // < 64: a segment holds 64 samples
-                const unsigned smp = valid ? (unsigned)list[((unsigned)k * 4 + w) * 64 + (pos & 63u)] : (unsigned)ST;
+                const unsigned smp = valid ? (unsigned)list[((unsigned)k * NSEG + w) * 64 + (pos & 63u)] : (unsigned)ST;
                 const double* xrow = Xs + smp * SXS + g;
                 double xb[Q];
 #pragma unroll
@@ -267,35 +297,43 @@ __global__ __launch_bounds__(SNT) void em_estep_screen_kernel(
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // every lane is done with the slot before the next record goes in
             __builtin_amdgcn_wave_barrier();
-            if (wave == 0 && j < 8) stamp(tile, 4 + 2 * j);
+            if (wave == 0 && j < kScreenStampRounds) stamp(tile, 4 + 2 * j);
         }
-        stamp(tile, 19);
+        stamp(tile, kScreenStampLoopEnd);
         __syncthreads();                             // the tile, the lists and the counts are free for the next tile
-        stamp(tile, 20);
+        stamp(tile, kScreenStampTileEnd);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) n_cand += __shfl_down(n_cand, off, 64);
     if (cand_count && lane == 0) atomicAdd(cand_count, n_cand);          // (an integer sum: order-free)
 }
 
+/// The tile each dimension is instantiated with -- one form per D, no switch at run time (the measurements: DESIGN 3.3p, "The pair").
+template <int D> constexpr int screen_tile = 256;
+
 template <int D> int launch_d(const ScreenArgs& a, int num_cus, hipStream_t stream)
 {
+    constexpr int ST = screen_tile<D>;
+    using T = ScreenTile<ST>;
+    static_assert(kSampleTile % ST == 0, "a block is a whole number of tiles");
+    static_assert(T::PER_CU * screen_lds_bytes<D, ST>() <= 160 * 1024, "the CU's workgroups share its LDS");
     const uint32_t n_tiles = padded_samples(a.n) / ST;
-    uint32_t grid = (uint32_t)num_cus;               // one workgroup per CU: its LDS and its two waves per SIMD fill one
+    uint32_t grid = (uint32_t)(T::PER_CU * num_cus); // what is resident at once: two waves per SIMD, the CU's LDS
     if (grid > n_tiles) grid = n_tiles;
     unsigned* exact = reinterpret_cast<unsigned*>(a.exact);              // word i as its halves 2i (components 0 .. 31) and 2i + 1
+    constexpr size_t lds = screen_lds_bytes<D, ST>();
     if (a.profile)
-        hipLaunchKernelGGL((em_estep_screen_kernel<D, true>), dim3(grid), dim3(SNT), screen_lds_bytes<D>(), stream, a.xt, a.ldx, a.n,
-                           n_tiles, a.params, a.K, a.shift, a.consts, a.lw, a.ldr, exact, a.all_exact, a.cand_count, a.profile);
+        hipLaunchKernelGGL((em_estep_screen_kernel<D, ST, true>), dim3(grid), dim3(T::NT), lds, stream, a.xt, a.ldx,
+                           a.n, n_tiles, a.params, a.K, a.shift, a.consts, a.lw, a.ldr, exact, a.all_exact, a.cand_count, a.profile);
     else
-        hipLaunchKernelGGL((em_estep_screen_kernel<D, false>), dim3(grid), dim3(SNT), screen_lds_bytes<D>(), stream, a.xt, a.ldx, a.n,
-                           n_tiles, a.params, a.K, a.shift, a.consts, a.lw, a.ldr, exact, a.all_exact, a.cand_count, nullptr);
+        hipLaunchKernelGGL((em_estep_screen_kernel<D, ST, false>), dim3(grid), dim3(T::NT), lds, stream, a.xt, a.ldx,
+                           a.n, n_tiles, a.params, a.K, a.shift, a.consts, a.lw, a.ldr, exact, a.all_exact, a.cand_count, nullptr);
     return (int)grid;
 }
 
-}  // namespace
+template <int D> int tile_d() { return screen_tile<D>; }
 
-static_assert(kSampleTile % ST == 0, "a block is a whole number of tiles");
+}  // namespace
 
 bool em_estep_screen_supported(int D, int K) { return D >= 12 && D <= SDMAX && D % 4 == 0 && K >= 1 && K <= SKMAX; }
 
@@ -305,6 +343,8 @@ bool em_estep_screen_supported(int D, int K) { return D >= 12 && D <= SDMAX && D
 /// while the dense kernel's falls with d^2 and K: at N = 5M, K = 64, D = 24 and 16 give 3.60 -> 4.40 and 1.92 -> 5.04 ms, D = 24,
 /// K = 32 1.81 -> 2.73 ms, D = 32, K = 16 1.51 -> 1.46 ms (inside the spreads). D = 32, K = 32 gains (2.90 -> 2.16 ms) and stays
 /// dense until tests/test_gpu_estep_screen.py's test_automatic_route, which fixes it, changes. Elsewhere only MLHIP_ESTEP_SCREEN=1 screens.
+/// With the merged candidate and bucket loop (profiles/estep_screen_pair_ab.txt) D = 32, K = 16 meets the criterion too (1.53 -> 1.31 ms);
+/// it is not routed yet.
 bool em_estep_screen_preferred(int D, int K) { return (D == 32 || D == 28) && K == SKMAX; }
 
 void launch_em_screen_constants(const double* rec_old, const double* rec_new, int K, int d, int D, double* consts,
@@ -323,6 +363,19 @@ int launch_em_estep_screen(const ScreenArgs& a, int num_cus, hipStream_t stream)
     case 24: return launch_d<24>(a, num_cus, stream);
     case 28: return launch_d<28>(a, num_cus, stream);
     case 32: return launch_d<32>(a, num_cus, stream);
+    default: return -1;
+    }
+}
+
+int em_estep_screen_tile(int D)
+{
+    switch (D) {
+    case 12: return tile_d<12>();
+    case 16: return tile_d<16>();
+    case 20: return tile_d<20>();
+    case 24: return tile_d<24>();
+    case 28: return tile_d<28>();
+    case 32: return tile_d<32>();
     default: return -1;
     }
 }

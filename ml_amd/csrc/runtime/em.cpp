@@ -124,12 +124,13 @@ static void report_screen_stamps(const mlhip_data* dt, const DevBuf& stamps, int
     constexpr int NS = kScreenStamps;
     std::vector<unsigned long long> t((size_t)NS * grid);
     HIP_CHECK(hipMemcpy(t.data(), stamps.p, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost));
-    const int rounds = std::min(8, (K + 7) / 8);                       // components wave 0 takes (the stamped ones)
+    const int tile_samples = em_estep_screen_tile(dt->D), waves = tile_samples / 32;
+    const int rounds = std::min(kScreenStampRounds, (K + waves - 1) / waves);   // components wave 0 takes (the stamped ones)
     double stage = 0, buckets = 0, copy = 0, eval = 0, wait = 0, tile = 0;
     int used = 0;
     for (int b = 0; b < grid; ++b) {
         const unsigned long long* s = t.data() + (size_t)NS * b;
-        if (!s[0] || !s[20]) continue;                                  // (the workgroup had no second tile)
+        if (!s[0] || !s[kScreenStampTileEnd]) continue;                                  // (the workgroup had no second tile)
         ++used;
         stage += (double)(s[1] - s[0]);
         buckets += (double)(s[2] - s[1]);
@@ -139,17 +140,17 @@ static void report_screen_stamps(const mlhip_data* dt, const DevBuf& stamps, int
             eval += (double)(s[4 + 2 * j] - s[3 + 2 * j]);
             prev = s[4 + 2 * j];
         }
-        wait += (double)(s[20] - s[19]);
-        tile += (double)(s[20] - s[0]);
+        wait += (double)(s[kScreenStampTileEnd] - s[kScreenStampLoopEnd]);
+        tile += (double)(s[kScreenStampTileEnd] - s[0]);
     }
     if (!used) {
         std::fprintf(stderr, "[mlhip] screened E-step, N=%u d=%d K=%d grid=%d: no workgroup had a second tile to stamp\n", dt->n, dt->d, K, grid);
         return;
     }
     const double us = 0.01 / used;
-    std::fprintf(stderr, "[mlhip] screened E-step, N=%u d=%d K=%d grid=%d, us per 256-sample tile (thread 0, mean of %d workgroups): stage %.2f, "
+    std::fprintf(stderr, "[mlhip] screened E-step, N=%u d=%d K=%d grid=%d, us per %d-sample tile (thread 0, mean of %d workgroups): stage %.2f, "
                  "buckets %.2f, record copy %.2f, evaluation %.2f (%d components of wave 0), end barrier %.2f, tile %.2f\n",
-                 dt->n, dt->d, K, grid, used, stage * us, buckets * us, copy * us, eval * us, rounds, wait * us, tile * us);
+                 dt->n, dt->d, K, grid, tile_samples, used, stage * us, buckets * us, copy * us, eval * us, rounds, wait * us, tile * us);
 }
 
 
@@ -181,7 +182,7 @@ static int launch_screened(mlhip_data* dt, const EstepArgs& a, int K)
     static const bool profile = [] { const char* e = std::getenv("MLHIP_ESTEP_SCREEN_PROFILE"); return e && e[0] == '1'; }();
     DevBuf stamps;
     if (profile) {
-        stamps.reserve(sizeof(unsigned long long) * kScreenStamps * ctx->num_cus);
+        stamps.reserve(sizeof(unsigned long long) * kScreenStamps * (256 / em_estep_screen_tile(dt->D)) * ctx->num_cus);   // (a slot set per workgroup of the grid)
         HIP_CHECK(hipMemsetAsync(stamps.p, 0, stamps.bytes, ctx->stream));
         sa.profile = stamps.as<unsigned long long>();
     }

@@ -4,8 +4,13 @@ stamping form -- thread 0 of every workgroup stamps the 100 MHz clock at the pha
 runtime prints the spans, averaged over the workgroups, on stderr. This tool runs a few passes of one shape in a child process with
 the switch set, reads those lines and prints each span in microseconds, in shader cycles (at --mhz) and as a share of the tile.
 The stamping form's fences forbid overlaps the plain kernel has: read the shares, not the length.
+The five spans, whatever the tile size the dimension is instantiated with (the line names it): "stage" ends when the sample's
+maximum is known (loads, lower bounds, the barrier that joins the halves); "buckets" is the loop that decides the candidates and
+ballots them into the lists, the tile's stores, the issue of the next tile's loads and the barrier that closes them; "record copy" and
+"evaluation" are wave 0's components (tile / 32 waves share the K components: eight of 64 in the 256-sample form, sixteen in the
+128-sample one); "end barrier" is wave 0's wait for the other waves.
 
-    python tools/estep_screen_phases.py [N d K] [--mhz 2400] > profiles/estep_screen_phases.txt
+    python tools/estep_screen_phases.py [N d K] [--mhz 2400] > profiles/estep_screen_pair_phases.txt
 """
 import os
 import re
