@@ -143,5 +143,20 @@ private:
     std::shared_ptr<const CentroidsInitialiser> centroids_initialiser_;
 };
 
+/** @brief Extension (not in the reference; scikit-learn's silhouette_samples): the exact silhouette value of points of `data` (d x N,
+a point in every column) under `labels` (one per point; `KMeans::labels()` or `EM::labels()` go straight in), Euclidean distance, on
+the device: with D_ic the sum of the distances of point i to the points labelled c,
+a_i = D_i,own / (n_own - 1), b_i = the smallest D_ic / n_c over the other non-empty clusters (the first minimum), s_i = (b_i - a_i) /
+max(a_i, b_i); 0 for a point alone in its cluster and where max(a_i, b_i) = 0; labels no point carries are ignored. `rows`: the
+points to evaluate, in any order, repeats allowed (empty: all, in order); every one is scored against ALL N points. The block is
+uploaded once: every point meets every other, so there are no row batches. The arithmetic and the order of every sum are fixed
+(mlhip_silhouette): no expansion of the squared distance, so data far from the origin lose nothing.
+@throw std::invalid_argument If `labels.size() != data.cols()`, a row index is out of range, or fewer than two clusters are non-empty.
+@throw std::runtime_error On device failures (no GPU: there is no CPU fallback; a context with a caller's all-reduce hook or RCCL
+ranks, whose ranks hold only their own points). */
+DLL_DECLSPEC VectorXd silhouette_samples(ConstMatrixRef data, const std::vector<unsigned int>& labels, const std::vector<Index>& rows = {});
+/** Extension: the mean of silhouette_samples(data, labels, rows), summed sequentially in row order. */
+DLL_DECLSPEC double silhouette_score(ConstMatrixRef data, const std::vector<unsigned int>& labels, const std::vector<Index>& rows = {});
+
 }  // namespace Clustering
 }  // namespace ml

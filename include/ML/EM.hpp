@@ -128,6 +128,16 @@ public:
     /** Extension: the mean of log_densities(data), summed sequentially in row order (comparable with log_likelihood()); NaN for an
     empty block (the other batch queries return empty results for one). */
     DLL_DECLSPEC double mean_log_density(ConstMatrixRef data) const;
+    /** Extension (model selection; scikit-learn's `_n_parameters`): the free parameters of the fitted mixture in the covariance mode
+    it was FITTED in -- K d(d+1)/2 for Full, K d for Diagonal, d(d+1)/2 for Tied --, plus K d for the means and K - 1 for the mixing
+    probabilities. Host only. @throw std::invalid_argument If the model has not been fitted. */
+    DLL_DECLSPEC std::size_t number_parameters() const;
+    /** Extension: the Bayesian information criterion of the fitted model on `data`, -2 N mean_log_density(data) +
+    number_parameters() log N with N = data.cols(), as scikit-learn defines it (lower is better); the scoring pass of log_densities,
+    no kernel of its own. Weights play no part. Throws like log_densities; an empty block gives NaN. */
+    DLL_DECLSPEC double bic(ConstMatrixRef data) const;
+    /** Extension: the Akaike information criterion, -2 N mean_log_density(data) + 2 number_parameters(). */
+    DLL_DECLSPEC double aic(ConstMatrixRef data) const;
     /** Extension: argmax_k of every point's log-responsibilities, first maximum wins (the same pass as log_densities). */
     DLL_DECLSPEC std::vector<unsigned int> assign_labels(ConstMatrixRef data) const;
     /** Extension: the data.cols() x number_components() posteriors of `data` (the batch form of assign_responsibilities, normalised
@@ -235,6 +245,7 @@ private:
     bool maximise_first_;
     bool converged_;
     CovarianceType covariance_type_ = CovarianceType::Full;
+    CovarianceType fitted_covariance_type_ = CovarianceType::Full;   // the mode of the last fit(): number_parameters()
     mlhip_data* device_data_ = nullptr;
     double covariance_regularisation_ = 1e-15;   // MLHIP_DEFAULT_COVARIANCE_RIDGE
     unsigned int number_initialisations_ = 1;

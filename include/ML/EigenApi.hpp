@@ -192,6 +192,36 @@ private:
     bool converged_ = false;
 };
 
+/** Extension: the exact silhouette value (Euclidean) of points of `data` (a point in every column) under `labels`, on the device;
+`rows`: the points to evaluate, in any order (empty: all). The definition, its fixed arithmetic and the exceptions: the function of
+the same name in ML/Clustering.hpp. silhouette_score: their mean, summed in row order. */
+inline Eigen::VectorXd silhouette_samples(Eigen::Ref<const Eigen::MatrixXd> data, const std::vector<unsigned int>& labels,
+                                          const std::vector<Eigen::Index>& rows = {})
+{
+    if (labels.size() != static_cast<std::size_t>(data.cols())) throw std::invalid_argument("silhouette: one label per data point required");
+    unsigned int top = 0;
+    for (const unsigned int l : labels) top = l > top ? l : top;
+    if (top == static_cast<unsigned int>(-1)) throw std::invalid_argument("silhouette: a label is too large");
+    std::vector<uint64_t> index;
+    for (const Eigen::Index r : rows) {
+        if (r < 0 || r >= data.cols()) throw std::invalid_argument("silhouette: a row index is out of range");
+        index.push_back(static_cast<uint64_t>(r));
+    }
+    const detail::Block block(data);
+    Eigen::VectorXd out(rows.empty() ? data.cols() : static_cast<Eigen::Index>(rows.size()));
+    detail::check(mlpp_silhouette_samples(block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()), labels.data(),
+                                          top + 1, rows.empty() ? nullptr : index.data(), index.size(), out.data()));
+    return out;
+}
+inline double silhouette_score(Eigen::Ref<const Eigen::MatrixXd> data, const std::vector<unsigned int>& labels,
+                               const std::vector<Eigen::Index>& rows = {})
+{
+    const Eigen::VectorXd v = silhouette_samples(data, labels, rows);
+    double sum = 0;
+    for (Eigen::Index i = 0; i < v.size(); ++i) sum += v[i];
+    return sum / static_cast<double>(v.size());
+}
+
 }  // namespace Clustering
 
 /** Gaussian-mixture EM (ML/EM.hpp:18-198). */
@@ -364,6 +394,28 @@ public:
         double sum = 0;
         for (Eigen::Index i = 0; i < v.size(); ++i) sum += v[i];
         return sum / static_cast<double>(v.size());
+    }
+    /** Extensions (model selection): the free parameters of the fitted mixture in the mode it was fitted in, and scikit-learn's
+    BIC / AIC of the fitted model on `data`: -2 N mean_log_density(data) + number_parameters() log N, and + 2 number_parameters(). */
+    std::size_t number_parameters() const
+    {
+        uint64_t p = 0;
+        detail::check(mlpp_em_number_parameters(h_, &p));
+        return static_cast<std::size_t>(p);
+    }
+    double bic(Eigen::Ref<const Eigen::MatrixXd> data) const
+    {
+        const detail::Block block(data);
+        double out = 0;
+        detail::check(mlpp_em_bic(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()), &out));
+        return out;
+    }
+    double aic(Eigen::Ref<const Eigen::MatrixXd> data) const
+    {
+        const detail::Block block(data);
+        double out = 0;
+        detail::check(mlpp_em_aic(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()), &out));
+        return out;
     }
     std::vector<unsigned int> assign_labels(Eigen::Ref<const Eigen::MatrixXd> data) const
     {

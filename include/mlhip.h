@@ -663,6 +663,39 @@ int mlhip_min_squared_distances(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, co
 int mlhip_random_partition_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const uint32_t* order, const uint32_t* offsets,
                                  double* means, double* sizes);
 
+/* ---- silhouette -------------------------------------------------------------------------------------- */
+/* Exact silhouette values of rows of the resident block under `labels` (Euclidean distance; every evaluated row against ALL rows of
+ * the block): with n_c the rows labelled c and D_ic = sum_{j: l_j = c} |x_i - x_j| (j = i included: +0),
+ *     a_i = D_{i,l_i} / (n_{l_i} - 1),   b_i = min over c != l_i with n_c > 0 of D_ic / n_c (the first minimum),
+ *     s_i = (b_i - a_i) / max(a_i, b_i);
+ * s_i = 0 and a_i = 0 for a row alone in its cluster, s_i = 0 where max(a_i, b_i) = 0 (scikit-learn's conventions); labels no row
+ * carries are ignored. labels: one per row of the block, each < K -- this rank's rows; ALL rows of the sample on a device group.
+ * rows: n_rows global row indices, in any order, repeats allowed; NULL: all rows in order (n_rows is then ignored). a_out / b_out /
+ * s_out: one double per evaluated row, each may be NULL. Weights attached to the block play no part; coordinates that are not
+ * finite are not looked for and come out as NaN wherever they enter.
+ * The arithmetic is fixed: z = x_i - x_j (one rounding per coordinate), q = z_0 z_0, q = fma(z_j, z_j, q) for ascending j, the
+ * distance sqrt(q) correctly rounded -- no expansion of the square, no matrix-core product. The columns j are taken cluster-sorted (a
+ * stable counting sort of the rows by label), every cluster's run is cut into chunks of 256 columns, the distances of a chunk are
+ * added one after the other and the chunk sums of a cluster in ascending order. A row's values are therefore a function of the data,
+ * the labels and the block's shard layout alone: not of `rows`, the row blocks the call walks (sized so that the chunk sums stay
+ * within the scoring routes' scratch bound; MLHIP_SILHOUETTE_ROWS=n overrides), the grid (MLHIP_SILHOUETTE_GRID=n), the tier
+ * (MLHIP_SILHOUETTE=plain: the plain tier at every d) or the column feed (MLHIP_SILHOUETTE_FEED=lds / scalar).
+ * Device group: every shard forms D_ic over its OWN columns by these rules (the evaluated rows' coordinates are collected from their
+ * shards and given to all), the host adds the shards' sums in ascending shard order and closes; the values then depend on the shard
+ * layout within rounding. A context that reduces through a caller's hook or RCCL ranks: MLHIP_E_UNSUPPORTED (a rank holds only its
+ * own columns). MLHIP_E_INVALID_ARGUMENT, before any launch: null data or labels, a label >= K, a row index >= the sample's rows, or
+ * fewer than two non-empty clusters. */
+int mlhip_silhouette(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, const uint32_t* labels, const uint64_t* rows, uint64_t n_rows,
+                     double* a_out, double* b_out, double* s_out);
+/* Which tier mlhip_silhouette runs on `data` under the switches as they are set now (diagnostic, nothing is launched): the register
+ * tier for d <= 32, the plain tier above and under MLHIP_SILHOUETTE=plain. */
+enum { MLHIP_SILHOUETTE_REGISTERS = 0, MLHIP_SILHOUETTE_PLAIN = 1 };
+int mlhip_silhouette_route(const mlhip_data* data, int* tier);
+/* The closing arithmetic of mlhip_silhouette for ONE row on the host (no GPU): counts: K cluster sizes, own_label < K the row's
+ * label, D: its K sums of distances; a / b / s each may be NULL. MLHIP_E_INVALID_ARGUMENT: null counts or D, own_label >= K,
+ * counts[own_label] = 0, or no other non-empty cluster. */
+int mlhip_silhouette_finish(uint32_t K, const uint64_t* counts, uint32_t own_label, const double* D, double* a, double* b, double* s);
+
 /* ---- timing (for bench.py / profiling) -------------------------------------------------------------- */
 /* Average device time in ms of the named kernel family over its launches since the last reset, measured with
  * HIP events on the context's stream. name: "em_estep", "em_mstats", "em_score", "kmeans_assign", ... Returns count in *launches.

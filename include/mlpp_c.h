@@ -91,6 +91,17 @@ int mlpp_em_assign_responsibilities(const mlpp_em* h, const double* x, uint32_t 
 int mlpp_em_score_samples(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out);
 int mlpp_em_predict(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, uint32_t* out);
 int mlpp_em_predict_proba(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out);
+/* Extensions (model selection): EM::number_parameters (host only; the mode the model was fitted in), EM::bic and EM::aic on N x d
+ * row-major data -- -2 N (mean log-density) + p log N and + 2 p, scikit-learn's definitions; the scoring pass of mlpp_em_score_samples. */
+int mlpp_em_number_parameters(const mlpp_em* h, uint64_t* out);
+int mlpp_em_bic(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out);
+int mlpp_em_aic(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out);
+/* Extension: Clustering::silhouette_samples -- exact silhouette values (Euclidean) of rows of x (n x d row-major) under `labels`
+ * (n labels, each < K), on the device (mlhip_silhouette holds the definition and the fixed arithmetic). rows: n_rows row indices in
+ * any order, repeats allowed; NULL: all n rows in order. s_out: one double per evaluated row. Every row meets every other, so there
+ * are no row batches: the block is uploaded once, and a block that does not fit the device is refused. */
+int mlpp_silhouette_samples(const double* x, uint64_t n, uint32_t d, const uint32_t* labels, uint32_t K, const uint64_t* rows, uint64_t n_rows,
+                            double* s_out);
 /* Extension: EM::sample -- n points drawn from the fitted mixture on the device, point i a pure function of (seed, i) and the
  * parameters (mlhip_em_sample). x_out: n x d row-major (a point in every row); labels_out (n, the components drawn) may be NULL.
  * n = 0 writes nothing. */

@@ -730,6 +730,80 @@ class Data:
         return out
 
 
+def silhouette(data, labels, K=None, rows=None, parts=False):
+    """Exact silhouette values (Euclidean) of the rows of the Data block `data` under `labels` (mlhip_silhouette): one float64 per
+    row, or per entry of `rows` (row indices, any order, repeats allowed), every one scored against ALL rows of the block.
+    parts=True: the tuple (a, b, s) -- mean distance to the row's own cluster, to the nearest other cluster, and the silhouette value.
+    labels: one integer in [0, K) per row (K: max + 1 unless given). Weights attached to the block play no part. TypeError /
+    ValueError before any device work: see silhouette_arguments. A function of the module, not a method of Data; nothing the handle
+    holds is changed."""
+    labels, K, rows = silhouette_arguments(data.n, labels, rows, K)
+    m = data.n if rows is None else len(rows)
+    s = np.empty(m)
+    a = np.empty(m) if parts else None
+    b = np.empty(m) if parts else None
+    check(lib.mlhip_silhouette(data.ctx.handle, data._h, C.c_uint32(K), u32ptr(labels),
+                               None if rows is None else rows.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_uint64(m),
+                               dptr(a) if parts else None, dptr(b) if parts else None, dptr(s)))
+    return (a, b, s) if parts else s
+
+
+def silhouette_route(data):
+    """The tier mlhip_silhouette runs on the Data block `data` under the switches as they are set now (mlhip_silhouette_route):
+    'registers' | 'plain'."""
+    tier = C.c_int()
+    check(lib.mlhip_silhouette_route(data._h, C.byref(tier)))
+    return ("registers", "plain")[tier.value]
+
+
+def silhouette_arguments(n, labels, rows=None, K=None):
+    """The argument checks of the silhouette calls, before any device work: returns (labels as a C-contiguous uint32 array of length
+    n, K, rows as a C-contiguous uint64 array or None). labels: a 1-D integer array or a list of n integers >= 0 (K: max + 1 unless
+    given, then every label < K), at least two distinct values among them; rows: None or 1-D integers in [0, n). TypeError for
+    another type or dtype, ValueError for a wrong length or refused values."""
+    def integers(v, what):
+        arr = np.asarray(v)
+        if arr.dtype == object or not (np.issubdtype(arr.dtype, np.integer) or (arr.size == 0 and isinstance(v, (list, tuple)))):
+            raise TypeError(f"{what} must be integers (a 1-D integer array or a list of them)")
+        if arr.ndim != 1:
+            raise ValueError(f"{what} must be one-dimensional")
+        return arr
+    labels = integers(labels, "labels")
+    if len(labels) != n:
+        raise ValueError(f"labels has {len(labels)} entries for {n} rows")
+    if n and labels.min() < 0:
+        raise ValueError("labels must be >= 0")
+    top = int(labels.max()) + 1 if n else 0
+    if K is None:
+        K = top
+    K = int(K)
+    if top > K:
+        raise ValueError("a label is not below K")
+    if K > 0xffffffff:
+        raise ValueError("labels must be below 2^32")
+    if n == 0 or len(np.unique(labels)) < 2:
+        raise ValueError("the silhouette needs at least two non-empty clusters")
+    if rows is not None:
+        rows = integers(rows, "rows")
+        if len(rows) and (rows.min() < 0 or rows.max() >= n):
+            raise ValueError("a row index is outside [0, N)")
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    return np.ascontiguousarray(labels, dtype=np.uint32), K, rows
+
+
+def silhouette_finish(counts, own_label, sums):
+    """The closing arithmetic of the silhouette for one row on the host (mlhip_silhouette_finish, device/silhouette_finish.hpp
+    compiled for the host; no GPU): counts -- the K cluster sizes, own_label -- the row's label, sums -- its K sums of distances.
+    Returns (a, b, s)."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    assert counts.ndim == 1 and sums.shape == counts.shape
+    a, b, s = C.c_double(), C.c_double(), C.c_double()
+    check(lib.mlhip_silhouette_finish(C.c_uint32(len(counts)), counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_uint32(int(own_label)),
+                                      dptr(sums), C.byref(a), C.byref(b), C.byref(s)))
+    return a.value, b.value, s.value
+
+
 def calculate_XXt_beta(X, y, lam):
     """ml::LinearRegression::calculate_XXt_beta on an N x q float64 C-contiguous X: returns (XXt + diag(lam), beta)."""
     if not (isinstance(X, np.ndarray) and X.dtype == np.float64 and X.ndim == 2 and X.flags.c_contiguous):

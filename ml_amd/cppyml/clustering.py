@@ -7,13 +7,15 @@ Conventions kept from the reference:
   * `EM.means` is `d x K` (NOT transposed, clustering.cpp:126), `KMeans.centroids` is `K x d` (clustering.cpp:66-69,172);
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
-Extensions (not in the reference surface): `EM.conditional_mean`, `EM.conditional_variance`, `EM.conditional_cdf`, `EM.conditional_quantile`, `EM.conditional_sample`, `EM.conditional_covariances`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
+Extensions (not in the reference surface): `silhouette_samples`, `silhouette_score` (module level: exact silhouette values on the GPU,
+for the labels of either model), `EM.number_parameters`, `EM.bic`, `EM.aic`, `EM.conditional_mean`, `EM.conditional_variance`, `EM.conditional_cdf`, `EM.conditional_quantile`, `EM.conditional_sample`, `EM.conditional_covariances`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
 `KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`, `EM.set_number_initialisations`,
 `EM.number_initialisations`, `EM.best_initialisation`, `EM.initialisation_log_likelihoods`, `EM.initialisation_steps`,
 `EM.initialisation_converged`.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -546,6 +548,69 @@ class EM:
         v = C.c_uint32()
         _check(_l.mlpp_em_steps_done(self._h, C.byref(v)))
         return v.value
+
+    @property
+    def number_parameters(self):
+        """Extension (model selection; scikit-learn's `_n_parameters`): the free parameters of the fitted mixture in the covariance
+        mode it was fitted in -- full K d (d + 1) / 2, diag K d, tied d (d + 1) / 2, each plus K d + K - 1. No GPU needed.
+        ValueError for a model that was not fitted."""
+        v = C.c_uint64()
+        _check(_l.mlpp_em_number_parameters(self._h, C.byref(v)))
+        return v.value
+
+    def bic(self, X):
+        """Extension: the Bayesian information criterion of the fitted model on X (N x d, what `fit` takes), as scikit-learn defines
+        it: -2 N score(X) + number_parameters log N (lower is better). Runs the scoring pass of score_samples."""
+        n = len(_require_data(X))
+        p = self.number_parameters
+        return -2.0 * n * self.score(X) + p * math.log(n) if n else float("nan")
+
+    def aic(self, X):
+        """Extension: the Akaike information criterion on X: -2 N score(X) + 2 number_parameters."""
+        n = len(_require_data(X))
+        p = self.number_parameters
+        return -2.0 * n * self.score(X) + 2.0 * p
+
+
+def silhouette_samples(X, labels, rows=None):
+    """Extension (scikit-learn's silhouette_samples): the exact silhouette value of every row of X (N x d, what `fit` takes) under
+    `labels`, Euclidean distance, computed on the GPU -- or of the rows listed in `rows` (any order, repeats allowed), each scored
+    against ALL N rows. Returns float64 values, N or len(rows) of them. labels: a 1-D integer array or a list (`KMeans.labels`,
+    `EM.labels` go straight in), K = max + 1; a label no row carries is ignored; a row alone in its cluster scores 0.
+    s = (b - a) / max(a, b) with a the mean distance to the other rows of the own cluster and b the smallest mean distance to
+    another cluster. The distances are formed directly, sqrt(sum (x - y)^2), never from |x|^2 + |y|^2 - 2 x.y, so data far from the
+    origin lose no accuracy; the order of every sum is fixed (include/mlhip.h, mlhip_silhouette).
+    TypeError / ValueError before any device work: X or labels of a wrong type, a wrong number of labels, a negative label, fewer
+    than two clusters, a row index outside [0, N)."""
+    X = _require_data(X)
+    n, d = X.shape
+    labels, K, rows = _lib.silhouette_arguments(n, labels, rows)
+    out = np.empty(n if rows is None else len(rows))
+    _check(_l.mlpp_silhouette_samples(_dp(X), C.c_uint64(n), C.c_uint32(d), _lib.u32ptr(labels), C.c_uint32(K),
+                                      None if rows is None else rows.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      C.c_uint64(0 if rows is None else len(rows)), _dp(out)))
+    return out
+
+
+def silhouette_score(X, labels, sample_size=None, seed=0):
+    """Extension (scikit-learn's silhouette_score): the mean of silhouette_samples, summed sequentially in row order. With
+    sample_size = m the rows are np.sort(np.random.default_rng(seed).choice(N, m, replace=False)) and those m rows are scored
+    against ALL N rows: exact silhouette values of a subsample. (scikit-learn scores the subsample against ITSELF, an estimate
+    from m^2 pairs; here the m values are the ones the full computation gives.) ValueError for a sample_size outside 1 .. N."""
+    X = _require_data(X)
+    n = len(X)
+    rows = None
+    if sample_size is not None:
+        m = int(sample_size)
+        if not 1 <= m <= n:
+            raise ValueError("silhouette_score(): sample_size must lie in 1 .. N")
+        _lib.silhouette_arguments(n, labels)
+        rows = np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+    total = 0.0
+    values = silhouette_samples(X, labels, rows)
+    for v in values.tolist():
+        total += v
+    return total / len(values)
 
 
 class KMeans:

@@ -57,6 +57,51 @@ constexpr int kGroupMaxShards = 64;
 struct GroupSumSlots { const double* p[kGroupMaxShards]; };
 void launch_group_sum(const GroupSumSlots& slots, int n, double* out, size_t count, hipStream_t stream);
 
+// ---- silhouette (silhouette.hip) -------------------------------------------------------------------
+/// Columns per chunk of a cluster's run of sorted columns: with the sorted order it fixes the order of every sum (mlhip.h).
+constexpr uint32_t kSilhouetteChunk = 256;
+/// Evaluated rows one workgroup holds (one per lane); the runtime sizes its row blocks in whole tiles.
+constexpr uint32_t kSilhouetteRowTile = 256;
+constexpr int kSilhouetteMaxRegisters = 32;
+enum SilhouetteKernel : int {
+    kSilhouetteRegisters = 0,                  // d <= 32: lane = evaluated row, its coordinates in registers
+    kSilhouettePlain = 1,                      // up to d = 4096: a lane walks its coordinates from memory (same operations, same bits)
+};
+enum SilhouetteFeed : int {
+    kSilhouetteScalarFeed = 0,                 // columns as wave-uniform scalar loads from the sorted copy
+    kSilhouetteLdsFeed = 1,                    // the chunk staged in LDS, read as same-address broadcasts (register tier only)
+};
+/// kSilhouetteRegisters for d <= 32, else kSilhouettePlain.
+int silhouette_tier(int d);
+/// Doubles per column of the sorted copy: the register tier's padding of d (2, 4, 8, 16, 32; zeros beyond d), d itself on the plain tier.
+int silhouette_pad(int kernel, int d);
+/// cols[c * stride + j] = xt[j * ldx + order[c]] for c < n, j < d, and +0.0 for d <= j < stride.
+void launch_silhouette_gather_columns(const double* xt, size_t ldx, int d, const uint32_t* order, uint32_t n, double* cols, int stride,
+                                      hipStream_t stream);
+/// rows[j * ldm + r] = xt[j * ldx + index[r]] for r < m, j < d, and +0.0 for d <= j < pad.
+void launch_silhouette_gather_rows(const double* xt, size_t ldx, int d, const uint32_t* index, uint32_t m, double* rows, size_t ldm, int pad,
+                                   hipStream_t stream);
+struct SilhouetteArgs {
+    const double* rows; size_t ldm; uint32_t m;              // evaluated rows, dimension-major, silhouette_pad(kernel, d) rows of ldm
+    const double* cols; int d;                               // the sorted copy, silhouette_pad(kernel, d) doubles per column
+    const uint32_t* chunk_first; const uint32_t* chunk_len; uint32_t n_chunks;   // device: first sorted column and length of every chunk
+    double* partials; size_t ldp;                            // out: partials[t * ldp + r], chunk t's sum for row r
+    int kernel, feed;
+    int grid;                                                // > 0: workgroups (a test's override; no bit depends on it)
+};
+/// Returns the workgroups launched (0: nothing to do), < 0: not built for the shape.
+int launch_silhouette(const SilhouetteArgs& a, int num_cus, hipStream_t stream);
+/// The chunk sums of every cluster added in ascending order (cluster c owns chunks cluster_chunks[c] .. cluster_chunks[c + 1]), then
+/// either the sums themselves, sums[c * lds + r] (a device group's shard), or the closing arithmetic of silhouette_finish.hpp with the
+/// cluster sizes `counts` and the rows' own labels: a_out / b_out / s_out, each may be null.
+struct SilhouetteFoldArgs {
+    const double* partials; size_t ldp; uint32_t m; uint32_t K;
+    const uint32_t* cluster_chunks; const uint32_t* counts; const uint32_t* own;
+    double* a_out; double* b_out; double* s_out;
+    double* sums; size_t lds;
+};
+void launch_silhouette_fold(const SilhouetteFoldArgs& a, hipStream_t stream);
+
 // ---- EM ----------------------------------------------------------------------------------------------
 struct EstepArgs {
     const double* xt; size_t ldx; uint32_t n; int D;      // D = padded dimension

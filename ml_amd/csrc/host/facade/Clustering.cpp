@@ -9,7 +9,9 @@
 #include <numeric>
 #include <stdexcept>
 
+#include "ML/Device.hpp"
 #include "device/fixed_point.hpp"
+#include "mlhip.h"
 
 namespace ml {
 namespace Clustering {
@@ -154,6 +156,46 @@ void ClosestCentroid::init(ConstMatrixRef data, std::default_random_engine& prng
         }
         responsibilities(i, arg) = 1;
     }
+}
+
+VectorXd silhouette_samples(ConstMatrixRef data, const std::vector<unsigned int>& labels, const std::vector<Index>& rows)
+{
+    const Index d = data.rows(), n = data.cols();
+    if (labels.size() != static_cast<std::size_t>(n)) throw std::invalid_argument("silhouette: one label per data point required");
+    if (d < 1) throw std::invalid_argument("silhouette: At least one dimension required");
+    unsigned int K = 0;
+    for (const unsigned int l : labels) K = std::max(K, l);
+    std::vector<char> seen(static_cast<std::size_t>(K) + 1, 0);
+    std::size_t distinct = 0;
+    for (const unsigned int l : labels)
+        if (!seen[l]) { seen[l] = 1; ++distinct; }
+    if (distinct < 2) throw std::invalid_argument("silhouette: at least two non-empty clusters required");
+    if (K == std::numeric_limits<unsigned int>::max()) throw std::invalid_argument("silhouette: a label is too large");
+    K += 1;
+    std::vector<uint64_t> index(rows.size());
+    for (std::size_t r = 0; r < rows.size(); ++r) {
+        if (rows[r] < 0 || rows[r] >= n) throw std::invalid_argument("silhouette: a row index is out of range");
+        index[r] = static_cast<uint64_t>(rows[r]);
+    }
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "labels go to the C ABI as they are");
+    mlhip_ctx* ctx = device::context();
+    struct Guard {
+        mlhip_data* h = nullptr;
+        ~Guard() { if (h) mlhip_data_free(h); }
+    } dev;
+    device::check(mlhip_data_upload(ctx, data.data(), static_cast<uint32_t>(d), static_cast<uint64_t>(n), data.outerStride(), &dev.h));
+    VectorXd out(rows.empty() ? n : static_cast<Index>(rows.size()));
+    device::check(mlhip_silhouette(ctx, dev.h, K, labels.data(), rows.empty() ? nullptr : index.data(), index.size(), nullptr, nullptr,
+                                   out.data()));
+    return out;
+}
+
+double silhouette_score(ConstMatrixRef data, const std::vector<unsigned int>& labels, const std::vector<Index>& rows)
+{
+    const VectorXd v = silhouette_samples(data, labels, rows);
+    double sum = 0;
+    for (Index i = 0; i < v.size(); ++i) sum += v[i];
+    return sum / static_cast<double>(v.size());
 }
 
 }  // namespace Clustering

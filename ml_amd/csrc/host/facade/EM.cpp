@@ -181,6 +181,7 @@ bool EM::fit_weighted(ConstMatrixRef data, const double* weights)
     const auto sample_size = static_cast<unsigned int>(data.cols());
     const unsigned int K = number_components_;
     if (!number_dimensions) throw std::invalid_argument("EM: At least one dimension required");
+    fitted_covariance_type_ = covariance_type_;
 
     // A previous fit's device block is no longer needed (its responsibilities are superseded).
     responsibilities_on_device_ = false;
@@ -503,6 +504,31 @@ double EM::mean_log_density(ConstMatrixRef data) const
     double sum = 0;
     for (Index i = 0; i < v.size(); ++i) sum += v[i];
     return sum / static_cast<double>(v.size());
+}
+
+std::size_t EM::number_parameters() const
+{
+    // (the exact N == K fit counts too: its parameters exist, though its zero covariances have no decompositions)
+    if (means().rows() == 0 || means().cols() != static_cast<Index>(number_components_))
+        throw std::invalid_argument("EM: the model has not been fitted");
+    const std::size_t d = static_cast<std::size_t>(means().rows()), K = number_components_;
+    const std::size_t triangle = d * (d + 1) / 2;
+    const std::size_t covariance = fitted_covariance_type_ == CovarianceType::Full       ? K * triangle
+                                   : fitted_covariance_type_ == CovarianceType::Diagonal ? K * d
+                                                                                         : triangle;
+    return covariance + K * d + K - 1;
+}
+
+double EM::bic(ConstMatrixRef data) const
+{
+    const double n = static_cast<double>(data.cols()), p = static_cast<double>(number_parameters());
+    return -2.0 * n * mean_log_density(data) + p * std::log(n);
+}
+
+double EM::aic(ConstMatrixRef data) const
+{
+    const double n = static_cast<double>(data.cols()), p = static_cast<double>(number_parameters());
+    return -2.0 * n * mean_log_density(data) + 2.0 * p;
 }
 
 std::vector<unsigned int> EM::assign_labels(ConstMatrixRef data) const

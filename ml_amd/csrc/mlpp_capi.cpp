@@ -207,6 +207,40 @@ int mlpp_em_predict(const mlpp_em* h, const double* data, uint64_t n, uint32_t d
         std::copy(v.begin(), v.end(), out);
     });
 }
+int mlpp_em_number_parameters(const mlpp_em* h, uint64_t* out)
+{
+    return guarded([&] { need(h); need(out); *out = h->em.number_parameters(); });
+}
+int mlpp_em_bic(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out)
+{
+    return guarded([&] { need(h); need(data); need(out); *out = h->em.bic(ConstMatrixRef(data, d, static_cast<Index>(n), d)); });
+}
+int mlpp_em_aic(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out)
+{
+    return guarded([&] { need(h); need(data); need(out); *out = h->em.aic(ConstMatrixRef(data, d, static_cast<Index>(n), d)); });
+}
+int mlpp_silhouette_samples(const double* x, uint64_t n, uint32_t d, const uint32_t* labels, uint32_t K, const uint64_t* rows, uint64_t n_rows,
+                            double* s_out)
+{
+    return guarded([&] {
+        need(x); need(labels); need(s_out);
+        if (n > static_cast<uint64_t>(std::numeric_limits<Index>::max())) throw std::invalid_argument("silhouette: Too many samples");
+        std::vector<unsigned int> l(labels, labels + n);
+        for (const unsigned int v : l)
+            if (v >= K) throw std::invalid_argument("silhouette: a label is not below K");
+        std::vector<Index> r;
+        if (rows) {
+            if (!n_rows) return;
+            r.reserve(n_rows);
+            for (uint64_t i = 0; i < n_rows; ++i) {
+                if (rows[i] >= n) throw std::invalid_argument("silhouette: a row index is out of range");
+                r.push_back(static_cast<Index>(rows[i]));
+            }
+        }
+        const VectorXd s = Clustering::silhouette_samples(ConstMatrixRef(x, d, static_cast<Index>(n), d), l, r);
+        std::copy_n(s.data(), s.size(), s_out);
+    });
+}
 int mlpp_em_sample(const mlpp_em* h, uint64_t n, uint64_t seed, double* x_out, uint32_t* labels_out)
 {
     return guarded([&] {

@@ -730,6 +730,18 @@ struct ConditionQuantileRoute {
 };
 ConditionQuantileRoute condition_quantile_route(const mlhip_data* data, int K, int dM, bool quantile, uint32_t n_prob, bool with_means,
                                                 bool with_iterations);
+/// mlhip_silhouette: the tier silhouette_tier (device/silhouette.hip) names for d -- MLHIP_SILHOUETTE=plain: the plain tier at every
+/// d --, the register tier's column feed (scalar loads; MLHIP_SILHOUETTE_FEED=lds: the LDS feed), the pair kernel's grid where
+/// MLHIP_SILHOUETTE_GRID=n gives one, and the evaluated rows per block: the largest whole number of row tiles whose chunk sums (one
+/// double per chunk and row) stay within kScoreScratchBytes, at least one tile (MLHIP_SILHOUETTE_ROWS=n overrides, rounded UP to whole
+/// tiles). No bit depends on any of them. (mlhip.h names the tiers by SilhouetteKernel's values.)
+struct SilhouetteRoute {
+    int kernel = kSilhouetteRegisters, feed = kSilhouetteScalarFeed;
+    uint32_t rows_override = 0;
+    int grid = 0;
+    uint32_t block_rows(uint64_t n_chunks, uint64_t m) const;
+};
+SilhouetteRoute silhouette_route(const mlhip_data* data);
 /// The conditioning kernels' table on the host: K records [mu_O | mu_M | A^T] in the paddings of `kernel` (device.hpp condition_pad):
 /// +0.0, and -0.0 in the rows of A^T beyond dO. With `factors` (K x dM x dM row-major lower factors; mlhip_em_conditional_samples) every
 /// record carries its factor behind it, the lower triangle packed row by row in the padded dM (condition_sample_record_doubles).

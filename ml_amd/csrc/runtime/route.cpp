@@ -37,6 +37,10 @@ struct Switches {
     long condition_rows;        // MLHIP_CONDITION_ROWS=n: rows per chunk of the conditioning pass (0: by the scratch bound)
     bool condition_skip;        // on unless MLHIP_CONDITION_SKIP=0: components without a share in a wave's rows are passed over
     long condition_group;       // MLHIP_CONDITION_GROUP=n: at most n probabilities per launch of the quantile search (0: as many as fit the scratch bound)
+    bool silhouette_plain;      // MLHIP_SILHOUETTE=plain: the silhouette takes its plain tier at every d
+    int silhouette_feed;        // MLHIP_SILHOUETTE_FEED=scalar / lds: kSilhouetteScalarFeed / kSilhouetteLdsFeed forced, -1 automatic
+    long silhouette_rows;       // MLHIP_SILHOUETTE_ROWS=n: evaluated rows per block (0: by the scratch bound)
+    long silhouette_grid;       // MLHIP_SILHOUETTE_GRID=n: workgroups of the pair kernel (0: by the CU count)
 };
 
 Switches read_switches()
@@ -82,6 +86,14 @@ Switches read_switches()
     s.condition_skip = env_char("MLHIP_CONDITION_SKIP") != '0';
     const char* condition_group = std::getenv("MLHIP_CONDITION_GROUP");
     s.condition_group = condition_group && *condition_group ? std::atol(condition_group) : 0;
+    const char* silhouette = std::getenv("MLHIP_SILHOUETTE");
+    s.silhouette_plain = silhouette && std::strcmp(silhouette, "plain") == 0;
+    const char* feed = std::getenv("MLHIP_SILHOUETTE_FEED");
+    s.silhouette_feed = !feed ? -1 : std::strcmp(feed, "scalar") == 0 ? kSilhouetteScalarFeed : std::strcmp(feed, "lds") == 0 ? kSilhouetteLdsFeed : -1;
+    const char* silhouette_rows = std::getenv("MLHIP_SILHOUETTE_ROWS");
+    s.silhouette_rows = silhouette_rows && *silhouette_rows ? std::atol(silhouette_rows) : 0;
+    const char* silhouette_grid = std::getenv("MLHIP_SILHOUETTE_GRID");
+    s.silhouette_grid = silhouette_grid && *silhouette_grid ? std::atol(silhouette_grid) : 0;
     return s;
 }
 
@@ -238,6 +250,28 @@ ConditionSampleRoute condition_sample_route(const mlhip_data* data, int K, int d
     const uint64_t fit = per_row > (uint64_t)K ? (per_row - (uint64_t)K) / (uint64_t)dM : 0;
     r.draws = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fit, n_draws));
     return r;
+}
+
+SilhouetteRoute silhouette_route(const mlhip_data* data)
+{
+    const Switches sw = read_switches();
+    SilhouetteRoute r;
+    r.kernel = sw.silhouette_plain ? (int)kSilhouettePlain : silhouette_tier(data->d);
+    // The column feed of the register tier: scalar loads unless MLHIP_SILHOUETTE_FEED=lds (profiles/silhouette_timing.txt).
+    r.feed = r.kernel == kSilhouetteRegisters && sw.silhouette_feed == kSilhouetteLdsFeed ? kSilhouetteLdsFeed : kSilhouetteScalarFeed;
+    r.rows_override = sw.silhouette_rows > 0 ? (uint32_t)std::min<long>(sw.silhouette_rows, 1l << 30) : 0;
+    r.grid = sw.silhouette_grid > 0 ? (int)std::min<long>(sw.silhouette_grid, 1l << 20) : 0;
+    return r;
+}
+
+uint32_t SilhouetteRoute::block_rows(uint64_t n_chunks, uint64_t m) const
+{
+    const uint64_t tile = kSilhouetteRowTile, budget = kScoreScratchBytes / sizeof(double);
+    uint64_t rows = rows_override ? (uint64_t)rows_override : budget / std::max<uint64_t>(n_chunks, 1);
+    rows = rows_override ? (rows + tile - 1) / tile * tile : rows / tile * tile;
+    if (rows < tile) rows = tile;
+    const uint64_t all = (std::max<uint64_t>(m, 1) + tile - 1) / tile * tile;
+    return (uint32_t)std::min(rows, all);
 }
 
 ModeRoute mode_route(const mlhip_data* data, int K, Covariance mode)
