@@ -262,6 +262,14 @@ private:
     std::vector<double> flat_covariances() const;                    // covariances() as one number_components() x d x d array
     void require_fitted_for(ConstMatrixRef data) const;
     void require_fitted() const;
+    struct ConditionDims;                                            // the dimensions of a conditional call (EM.cpp)
+    struct Conditioned;                                              // the model conditioned on observed coordinates (EM.cpp)
+    /// The argument checks every conditional call on data opens with: a fitted shape, `observed` against it, the data's rows.
+    ConditionDims check_conditional_call(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed) const;
+    /// What condition() adds to the marginal parts and the regression maps: nothing, the missing coordinates' covariances, those and
+    /// their factors, or those and their scales.
+    enum class ConditionParts { Marginal, Covariances, Factors, Scales };
+    Conditioned condition(const std::vector<unsigned int>& observed, ConditionParts parts) const;
     /// conditional_cdfs (`values` given) and conditional_quantiles (`probabilities` given) behind their own argument checks.
     MatrixXd conditional_distribution(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, const ConstMatrixRef* values,
                                       const std::vector<double>* probabilities) const;

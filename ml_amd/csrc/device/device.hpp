@@ -204,14 +204,17 @@ enum ConditionKernel : int {
     kConditionRegisters = 0,                   // dO <= 32 and dM <= 32: lane = row, x_O and the accumulators in registers
     kConditionPlain = 1,                       // up to d = 4096: table and accumulators in global memory
 };
-struct ConditionArgs {
+/// What every conditioning kernel reads of a chunk: the rows, the log-responsibilities an E-step kernel wrote for them and the table.
+struct ConditionChunk {
     const double* xt; size_t ldx; uint32_t n;                // the observed coordinates, feature-major: row c = coordinate observed[c]
     int dO, dM, K;
     const double* lw; size_t ldr; const double* lse;         // K x ldr log-responsibilities and their log-sum-exp
-    const double* table;                                     // K records of condition_record_doubles(kernel, dO, dM)
+    const double* table;                                     // K records of the kernel's *_record_doubles(kernel, dO, dM)
+    int kernel;                                              // ConditionKernel
+};
+struct ConditionArgs : ConditionChunk {
     double* out;                                             // n x dM, row-major and contiguous (16-byte aligned)
     int skip;                                                // 1: a wave passes over a component none of its rows has a share in
-    int kernel;                                              // ConditionKernel
 };
 /// kConditionRegisters where both paddings exist, else kConditionPlain.
 int em_condition_route(int dO, int dM);
@@ -230,16 +233,11 @@ int launch_em_condition(const ConditionArgs& a, int num_cus, hipStream_t stream)
 /// from the same lw / lse as the conditioning pass. Row (i, q) is a pure function of (seed, first_row + i, q), the row and the
 /// parameters. The tiers and paddings are ConditionKernel's and condition_pad's; the record is the conditioning pass's with the
 /// factor behind it: [mu_O | mu_M | A^T | G, the lower triangle packed row by row: (j, c) at j (j+1)/2 + c, for the PADDED dM].
-struct ConditionSampleArgs {
-    const double* xt; size_t ldx; uint32_t n;                // the observed coordinates, feature-major
-    int dO, dM, K;
-    const double* lw; size_t ldr; const double* lse;         // K x ldr log-responsibilities and their log-sum-exp
-    const double* table;                                     // K records of condition_sample_record_doubles(kernel, dO, dM)
+struct ConditionSampleArgs : ConditionChunk {
     uint64_t seed, first_row;                                // first_row: the global index of the chunk's row 0
     uint32_t first_draw, n_draws;                            // (first_draw + n_draws <= 2^32 - 1: draw q is generator stream 1 + q)
     double* out; size_t ldq;                                 // n_draws blocks of n x dM (row-major), ldq doubles apart: even, 16-byte aligned
     uint32_t* labels;                                        // n_draws x n, or null
-    int kernel;                                              // ConditionKernel
 };
 constexpr uint32_t kConditionSampleNoLabel = 0xFFFFFFFFu;    // the label of a row whose shares do not sum to a number
 inline size_t condition_sample_record_doubles(int kernel, int dO, int dM)
@@ -254,17 +252,12 @@ int launch_em_condition_sample(const ConditionSampleArgs& a, int num_cus, hipStr
 /// pass, whose steps it runs first. Row i's output is a pure function of row i and the parameters. The tiers and paddings are
 /// ConditionKernel's and condition_pad's; the record is the conditioning pass's with c behind it: diag(C_k) (the padded dM doubles),
 /// or with `full` the lower triangle of C_k packed row by row, (a, b) at a (a + 1) / 2 + b, for the PADDED dM.
-struct ConditionVarianceArgs {
-    const double* xt; size_t ldx; uint32_t n;                // the observed coordinates, feature-major
-    int dO, dM, K;
-    const double* lw; size_t ldr; const double* lse;         // K x ldr log-responsibilities and their log-sum-exp
-    const double* table;                                     // K records of condition_variance_record_doubles(kernel, dO, dM, full)
+struct ConditionVarianceArgs : ConditionChunk {
     double* out;                                             // n x dM, or n x dM x dM with `full`: row-major and contiguous (16-byte aligned)
     double* means;                                           // n x dM (16-byte aligned): E[x_M | x_O], the conditioning pass's bits; or null
     double* work;                                            // kConditionPlain: n x 2 dM doubles of the call's own; else unused
     int full;
-    int skip;                                                // 1: a wave passes over a component none of its rows has a share in
-    int kernel;                                              // ConditionKernel
+    int skip;                                                // as ConditionArgs'
 };
 /// kConditionRegisters where the register tier is built for (dO, dM) in this form -- the diagonal form to 32 x 32, the full form to
 /// the dM its accumulators fit the register file at (em_condition_variance.hip states the bound) --, else kConditionPlain.
@@ -281,11 +274,7 @@ int launch_em_condition_variance(const ConditionVarianceArgs& a, int num_cus, hi
 /// s_kj^2) of the n rows of a chunk, from the same lw / lse as the conditioning pass -- its CDF at a value per (row, coordinate), or
 /// its quantiles at n_prob probabilities. Row i's output is a pure function of row i and the parameters. The tiers and paddings are
 /// ConditionKernel's and condition_pad's; the record is the conditioning pass's with [s (the padded dM) | w = 1 / s (the same)] behind it.
-struct ConditionQuantileArgs {
-    const double* xt; size_t ldx; uint32_t n;                // the observed coordinates, feature-major
-    int dO, dM, K;
-    const double* lw; size_t ldr; const double* lse;         // K x ldr log-responsibilities and their log-sum-exp
-    const double* table;                                     // K records of condition_quantile_record_doubles(kernel, dO, dM)
+struct ConditionQuantileArgs : ConditionChunk {
     const double* values;                                    // CDF: n x dM, row-major and contiguous (16-byte aligned); quantile: unused
     const double* probabilities; const double* z;            // quantile: n_prob probabilities and their normal quantiles (device memory)
     uint32_t n_prob;
@@ -293,8 +282,7 @@ struct ConditionQuantileArgs {
     uint32_t* iterations;                                    // quantile: trips per output, in out's layout (blocks ldq apart); or null
     size_t ldq;                                              // even
     double* means;                                           // n x dM (16-byte aligned): E[x_M | x_O], the conditioning pass's bits; or null
-    int skip;                                                // 1: a wave passes over a component none of its rows has a share in
-    int kernel;                                              // ConditionKernel
+    int skip;                                                // as ConditionArgs'
 };
 /// kConditionRegisters where the register tier is built for (dO, dM) -- the CDF to 32 x 32, the quantile search to the dM its state
 /// fits the register file at (em_condition_quantile.hip states the bound) --, else kConditionPlain.

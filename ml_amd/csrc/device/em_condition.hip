@@ -23,7 +23,7 @@
 //   em_condition_plain_kernel       any dO + dM <= 4096: thread = row, the output row is the accumulator, table from global memory.
 // Record: [mu_O (PO) | mu_M (PM) | A^T (PO x PM: row c = observed coordinate c, so the PM maps of one z_c are contiguous)]; padding
 // +0.0, except the rows c >= dO of A^T: -0.0.
-#include "device.hpp"
+#include "em_condition_common.hpp"
 #include "exp_nonpos.hpp"
 
 namespace mlhip {
@@ -60,6 +60,10 @@ __global__ __launch_bounds__(64 * W) void em_condition_kernel(const double* __re
             if (skip && __ballot(share) == 0) continue;
             const double* __restrict__ rec = table + (size_t)k * PS;   // wave-uniform -> scalar loads
             double tj[PM];
+            // Steps 1 - 2 and the tile store below are written out here, not taken from em_condition_common.hpp (component_prediction,
+            // move_staged<false>, which state the same text for the other kernels): either call moves this kernel's instructions, and
+            // with the calls the 16 x 16 padding ran up to 3.5 % slower at unchanged register counts
+            // (profiles/condition_shared_timing.txt). As written, this file compiles to the instructions it had before the header.
 #pragma unroll
             for (int j = 0; j < PM; ++j) tj[j] = rec[PO + j];
 #pragma unroll
@@ -82,8 +86,7 @@ __global__ __launch_bounds__(64 * W) void em_condition_kernel(const double* __re
 #pragma unroll
         for (int j = 0; j < PM; ++j)
             if (j < dM) stage[lane * S + j] = y[j];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_sync();
 
         // the tile is rows * dM contiguous doubles of the output: two per lane and trip, (row, col) carried along without a division
         const uint32_t rows = n - t * 64 < 64 ? n - t * 64 : 64;
@@ -105,8 +108,7 @@ __global__ __launch_bounds__(64 * W) void em_condition_kernel(const double* __re
             col += step_cols;
             if (col >= (uint32_t)dM) { col -= (uint32_t)dM; ++row; }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();                         // (the next tile's stores wait for these reads)
+        wave_sync();                                             // (the next tile's stores wait for these reads)
     }
 }
 
@@ -134,36 +136,6 @@ __global__ __launch_bounds__(256) void em_condition_plain_kernel(const double* _
     }
 }
 
-constexpr int waves_for(int PM) { return PM <= 16 ? 4 : 2; }
-
-int pad_registers(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= kConditionMaxRegisters ? 32 : -1; }
-
-template <int PO, int PM>
-int launch_t(const ConditionArgs& a, int num_cus, hipStream_t stream)
-{
-    constexpr int W = waves_for(PM);
-    const uint32_t tiles = (a.n + 63) / 64;
-    uint32_t grid = (tiles + W - 1) / W;
-    const uint32_t cap = (uint32_t)(num_cus > 0 ? num_cus : 256) * 4;
-    if (grid > cap) grid = cap;
-    const size_t bytes = sizeof(double) * (size_t)W * 64 * (size_t)(a.dM | 1);
-    hipLaunchKernelGGL((em_condition_kernel<PO, PM, W>), dim3(grid), dim3(64 * W), bytes, stream, a.xt, a.ldx, a.n, a.dO, a.dM, a.K, a.lw,
-                       a.ldr, a.lse, a.table, a.out, a.skip);
-    return (int)grid;
-}
-
-template <int PO>
-int launch_o(const ConditionArgs& a, int num_cus, hipStream_t stream)
-{
-    switch (pad_registers(a.dM)) {
-    case 4: return launch_t<PO, 4>(a, num_cus, stream);
-    case 8: return launch_t<PO, 8>(a, num_cus, stream);
-    case 16: return launch_t<PO, 16>(a, num_cus, stream);
-    case 32: return launch_t<PO, 32>(a, num_cus, stream);
-    default: return -1;
-    }
-}
-
 }  // namespace
 
 int em_condition_route(int dO, int dM)
@@ -171,27 +143,30 @@ int em_condition_route(int dO, int dM)
     return dO <= kConditionMaxRegisters && dM <= kConditionMaxRegisters ? kConditionRegisters : kConditionPlain;
 }
 
-int condition_pad(int kernel, int n) { return kernel == kConditionRegisters ? pad_registers(n) : n; }
+int condition_pad(int kernel, int n)
+{
+    if (kernel != kConditionRegisters) return n;
+    return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= kConditionMaxRegisters ? 32 : -1;
+}
 
 int launch_em_condition(const ConditionArgs& a, int num_cus, hipStream_t stream)
 {
     if (a.dO < 1 || a.dM < 1 || a.dO + a.dM > kGenericMaxDim || a.K < 1) return -1;
     if (a.n == 0) return 0;
     if (a.kernel == kConditionPlain) {
-        uint32_t grid = (a.n + 255) / 256;
-        const uint32_t cap = (uint32_t)(num_cus > 0 ? num_cus : 256) * 8;
-        if (grid > cap) grid = cap;
+        const uint32_t grid = row_grid(a.n, num_cus);
         hipLaunchKernelGGL(em_condition_plain_kernel, dim3(grid), dim3(256), 0, stream, a.xt, a.ldx, a.n, a.dO, a.dM, a.K, a.lw, a.ldr, a.lse,
                            a.table, a.out);
         return (int)grid;
     }
-    switch (pad_registers(a.dO)) {
-    case 4: return launch_o<4>(a, num_cus, stream);
-    case 8: return launch_o<8>(a, num_cus, stream);
-    case 16: return launch_o<16>(a, num_cus, stream);
-    case 32: return launch_o<32>(a, num_cus, stream);
-    default: return -1;
-    }
+    return dispatch_paddings<32>(a.dO, a.dM, [&](auto po, auto pm) {
+        constexpr int PO = decltype(po)::value, PM = decltype(pm)::value, W = condition_waves(PM);
+        const uint32_t grid = tile_grid(a.n, W, num_cus);
+        const size_t bytes = sizeof(double) * (size_t)W * 64 * (size_t)(a.dM | 1);
+        hipLaunchKernelGGL((em_condition_kernel<PO, PM, W>), dim3(grid), dim3(64 * W), bytes, stream, a.xt, a.ldx, a.n, a.dO, a.dM, a.K, a.lw,
+                           a.ldr, a.lse, a.table, a.out, a.skip);
+        return (int)grid;
+    });
 }
 
 }  // namespace mlhip

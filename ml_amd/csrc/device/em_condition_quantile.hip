@@ -2,8 +2,8 @@
 // one-dimensional mixture sum_k r_k N(t_kj, s_kj^2). From the log-responsibilities lw / lse an E-step kernel wrote for the MARGINAL
 // mixture over the observed coordinates (exact form, with_lse = 1, fold = 0) and the table [mu_k,O | mu_k,M | A_k^T | s_k | w_k] per
 // component -- the record of em_condition.hip with s_kj = sqrt(C_k[j][j]) and w_kj = 1 / s_kj behind it -- per row, on every tier:
-//   both    z_c = x_c - mu_k,O[c]; t_j = mu_k,M[j], t_j = fma(A_k[j][c], z_c, t_j) for ascending c (em_condition_kernel's chain, text
-//           for text); r_k = exp_nonpos(lw_k - lse); a component takes part ONLY where r_k != 0.
+//   both    z_c = x_c - mu_k,O[c]; t_j = mu_k,M[j], t_j = fma(A_k[j][c], z_c, t_j) for ascending c (component_prediction);
+//           r_k = exp_nonpos(lw_k - lse); a component takes part ONLY where r_k != 0.
 //   CDF     a = (v_j - t_kj) * w_kj;  F_j = fma(r_k, normal_cdf(a), F_j) for ascending k from F_j = +0.0.
 //   quantile at probability p, z = normal_quantile(p) from the host:
 //           S = the sequential sum of r_k for ascending k from +0.0 (em_condition_sample.hip's s_{K-1}); T = p * S;
@@ -32,7 +32,7 @@
 //   em_condition_cdf_plain_kernel, em_condition_quantile_plain_kernel   any dO + dM <= 4096: thread = row, table from global memory,
 //                                   unpadded; the CDF accumulates in its output row, the search runs one coordinate at a time in
 //                                   registers (it needs no work array: its state is five doubles). Same order, same bits.
-#include "device.hpp"
+#include "em_condition_common.hpp"
 #include "mlhip.h"               // MLHIP_QUANTILE_NEWTON_TRIPS, MLHIP_QUANTILE_MAX_TRIPS: the header states the search's constants
 #pragma clang fp contract(off)   // every fused multiply-add below is written out: both tiers and the host's restatement round alike
 #include "exp_nonpos.hpp"
@@ -50,28 +50,8 @@ constexpr int kQuantileMaxTrips = MLHIP_QUANTILE_MAX_TRIPS;  // the cap (mlhip.h
 constexpr double kQuantileTolerance = 0x1p-50;      // |F - T| <= this * T: F is as close as a sum of normal_cdf values can tell
 constexpr double kQuantileResolution = 0x1p-51;     // |candidate - v| <= this * |v|: the step is below v's own rounding
 
-constexpr int cdf_waves(int PM) { return PM <= 16 ? 4 : 2; }
 constexpr int quantile_waves(int PM) { return PM <= 4 ? 4 : PM <= 8 ? 2 : 1; }
 __host__ __device__ constexpr size_t stage_doubles(int dM) { return (size_t)64 * ((size_t)dM | 1); }
-
-/// em_condition_kernel's chain, text for text.
-template <int PO, int PM>
-__device__ __forceinline__ void component_prediction(const double* __restrict__ rec, const double (&x)[PO], int dO, double (&tj)[PM])
-{
-#pragma unroll
-    for (int j = 0; j < PM; ++j) tj[j] = rec[PO + j];
-#pragma unroll
-    for (int c0 = 0; c0 < PO; c0 += 4) {
-        if (c0 < dO) {                                           // (wave-uniform: a group of four coordinates beyond dO is not run at all)
-#pragma unroll
-            for (int c = c0; c < c0 + 4; ++c) {
-                const double z = x[c] - rec[c];
-#pragma unroll
-                for (int j = 0; j < PM; ++j) tj[j] = __builtin_fma(rec[PO + PM + c * PM + j], z, tj[j]);
-            }
-        }
-    }
-}
 
 /// The start of a coordinate's search. True: a search runs from v inside [lo, hi], widened here; false: v is the result. The start is
 /// the weighted mean of the component quantiles CLAMPED into [lo, hi] -- it leaves it only by rounding --, so it may sit ON an end: a
@@ -107,41 +87,6 @@ __device__ __forceinline__ bool quantile_step(double F, double f, double S, doub
     const bool stop = converged || !(lo < next && next < hi) || trip >= kQuantileMaxTrips;
     v = stop ? v : next;
     return stop;
-}
-
-/// `rows` x `width` contiguous doubles between global memory and the staging tile (row stride S), two per lane and trip, (row, col)
-/// carried along without a division. The global pointer is 16-byte aligned.
-template <bool LOAD>
-__device__ __forceinline__ void move_staged(double* stage, int S, uint32_t rows, uint32_t width, double* __restrict__ mem, int lane)
-{
-    const uint32_t total = rows * width;
-    const uint32_t step_rows = 128u / width, step_cols = 128u % width;
-    uint32_t row = (2u * lane) / width, col = (2u * lane) % width;
-    for (uint32_t e = 2u * lane; e < total; e += 128u) {
-        uint32_t row1 = row, col1 = col + 1;
-        if (col1 == width) { col1 = 0; ++row1; }
-        if (e + 1 < total) {
-            if constexpr (LOAD) {
-                const double2 v = *reinterpret_cast<const double2*>(mem + e);
-                stage[row * S + col] = v.x;
-                stage[row1 * S + col1] = v.y;
-            } else {
-                *reinterpret_cast<double2*>(mem + e) = make_double2(stage[row * S + col], stage[row1 * S + col1]);
-            }
-        } else {
-            if constexpr (LOAD) stage[row * S + col] = mem[e];
-            else mem[e] = stage[row * S + col];
-        }
-        row += step_rows;
-        col += step_cols;
-        if (col >= width) { col -= width; ++row; }
-    }
-}
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
 }
 
 /// A lane's PM registers out as the wave's rows x dM tile at dst.
@@ -195,7 +140,7 @@ __global__ __launch_bounds__(64 * W) void em_condition_cdf_kernel(const double* 
             const double* __restrict__ rec = table + (size_t)k * PS;   // wave-uniform -> scalar loads
             const double* __restrict__ wk = rec + PO + PM + PO * PM + PM;
             double tj[PM];
-            component_prediction<PO, PM>(rec, x, dO, tj);
+            component_prediction(rec, x, dO, tj, PO, PM);
             if (means) {                                         // (wave-uniform)
 #pragma unroll
                 for (int j = 0; j < PM; ++j) {
@@ -261,7 +206,7 @@ __global__ __launch_bounds__(64 * W) void em_condition_quantile_kernel(const dou
                 const double* __restrict__ rec = table + (size_t)k * PS;
                 const double* __restrict__ sk = rec + PO + PM + PO * PM;
                 double tj[PM];
-                component_prediction<PO, PM>(rec, x, dO, tj);
+                component_prediction(rec, x, dO, tj, PO, PM);
                 if (with_mean) {
 #pragma unroll
                     for (int j = 0; j < PM; ++j) {
@@ -300,7 +245,7 @@ __global__ __launch_bounds__(64 * W) void em_condition_quantile_kernel(const dou
                     const double* __restrict__ rec = table + (size_t)k * PS;
                     const double* __restrict__ wk = rec + PO + PM + PO * PM + PM;
                     double tj[PM];
-                    component_prediction<PO, PM>(rec, x, dO, tj);
+                    component_prediction(rec, x, dO, tj, PO, PM);
 #pragma unroll
                     for (int j = 0; j < PM; ++j) {
                         const double a = (v[j] - tj[j]) * wk[j];
@@ -348,12 +293,9 @@ __global__ __launch_bounds__(256) void em_condition_cdf_plain_kernel(const doubl
             const double r = exp_nonpos(lw[(size_t)k * ldr + i] - l);
             if (!(r != 0.0)) continue;
             const double* rec = table + (size_t)k * PS;
-            const double* mu_m = rec + dO;
-            const double* at = rec + dO + dM;
-            const double* wk = at + (size_t)dO * dM + dM;
+            const double* wk = rec + dO + dM + (size_t)dO * dM + dM;
             for (int j = 0; j < dM; ++j) {
-                double tj = mu_m[j];
-                for (int c = 0; c < dO; ++c) tj = __builtin_fma(at[(size_t)c * dM + j], xt[(size_t)c * ldx + i] - rec[c], tj);
+                const double tj = plain_prediction(rec, dO, dM, j, xt, ldx, i);
                 if (y) y[j] = __builtin_fma(r, tj, y[j]);
                 const double a = (values[(size_t)i * dM + j] - tj) * wk[j];
                 F[j] = __builtin_fma(r, normal_cdf(a), F[j]);
@@ -376,13 +318,7 @@ __global__ __launch_bounds__(256) void em_condition_quantile_plain_kernel(const 
         double S = 0.0;
         for (int k = 0; k < K; ++k) S = S + exp_nonpos(lw[(size_t)k * ldr + i] - l);
         for (int j = 0; j < dM; ++j) {
-            // t_kj by the chain, for the component k's record
-            auto prediction = [&](const double* rec) {
-                const double* at = rec + dO + dM;
-                double tj = rec[dO + j];
-                for (int c = 0; c < dO; ++c) tj = __builtin_fma(at[(size_t)c * dM + j], xt[(size_t)c * ldx + i] - rec[c], tj);
-                return tj;
-            };
+            auto prediction = [&](const double* rec) { return plain_prediction(rec, dO, dM, j, xt, ldx, i); };
             if (means) {
                 double y = 0.0;
                 for (int k = 0; k < K; ++k) {
@@ -431,64 +367,12 @@ __global__ __launch_bounds__(256) void em_condition_quantile_plain_kernel(const 
     }
 }
 
-int pad_registers(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : -1; }
-
-uint32_t capped_grid(uint32_t blocks, int num_cus, int per_cu)
-{
-    const uint32_t cap = (uint32_t)(num_cus > 0 ? num_cus : 256) * per_cu;
-    return blocks > cap ? cap : blocks;
-}
-
-template <int PO, int PM>
-int launch_cdf_t(const ConditionQuantileArgs& a, int num_cus, hipStream_t stream)
-{
-    constexpr int W = cdf_waves(PM);
-    const uint32_t tiles = (a.n + 63) / 64;
-    const uint32_t grid = capped_grid((tiles + W - 1) / W, num_cus, 4);
-    hipLaunchKernelGGL((em_condition_cdf_kernel<PO, PM, W>), dim3(grid), dim3(64 * W), sizeof(double) * W * stage_doubles(a.dM), stream, a.xt, a.ldx,
-                       a.n, a.dO, a.dM, a.K, a.lw, a.ldr, a.lse, a.table, a.values, a.out, a.means, a.skip);
-    return (int)grid;
-}
-
-template <int PO, int PM>
-int launch_quantile_t(const ConditionQuantileArgs& a, int num_cus, hipStream_t stream)
-{
-    constexpr int W = quantile_waves(PM);
-    const uint32_t tiles = (a.n + 63) / 64;
-    const uint32_t grid = capped_grid((tiles + W - 1) / W, num_cus, 4);
-    hipLaunchKernelGGL((em_condition_quantile_kernel<PO, PM, W>), dim3(grid), dim3(64 * W), sizeof(double) * W * stage_doubles(a.dM), stream, a.xt,
-                       a.ldx, a.n, a.dO, a.dM, a.K, a.lw, a.ldr, a.lse, a.table, a.probabilities, a.z, a.n_prob, a.out, a.ldq, a.iterations, a.means,
-                       a.skip);
-    return (int)grid;
-}
-
-template <int PO>
-int launch_o(const ConditionQuantileArgs& a, bool quantile, int num_cus, hipStream_t stream)
-{
-    const int pm = pad_registers(a.dM);
-    if (quantile) {
-        switch (pm) {
-        case 4: return launch_quantile_t<PO, 4>(a, num_cus, stream);
-        case 8: return launch_quantile_t<PO, 8>(a, num_cus, stream);
-        case 16: return launch_quantile_t<PO, 16>(a, num_cus, stream);
-        default: return -1;
-        }
-    }
-    switch (pm) {
-    case 4: return launch_cdf_t<PO, 4>(a, num_cus, stream);
-    case 8: return launch_cdf_t<PO, 8>(a, num_cus, stream);
-    case 16: return launch_cdf_t<PO, 16>(a, num_cus, stream);
-    case 32: return launch_cdf_t<PO, 32>(a, num_cus, stream);
-    default: return -1;
-    }
-}
-
 int launch(const ConditionQuantileArgs& a, bool quantile, int num_cus, hipStream_t stream)
 {
     if (a.dO < 1 || a.dM < 1 || a.dO + a.dM > kGenericMaxDim || a.K < 1) return -1;
     if (a.n == 0 || (quantile && a.n_prob == 0)) return 0;
     if (a.kernel == kConditionPlain) {
-        const uint32_t grid = capped_grid((a.n + 255) / 256, num_cus, 8);
+        const uint32_t grid = row_grid(a.n, num_cus);
         if (quantile)
             hipLaunchKernelGGL(em_condition_quantile_plain_kernel, dim3(grid), dim3(256), 0, stream, a.xt, a.ldx, a.n, a.dO, a.dM, a.K, a.lw, a.ldr,
                                a.lse, a.table, a.probabilities, a.z, a.n_prob, a.out, a.ldq, a.iterations, a.means);
@@ -498,13 +382,22 @@ int launch(const ConditionQuantileArgs& a, bool quantile, int num_cus, hipStream
         return (int)grid;
     }
     if (em_condition_quantile_route(a.dO, a.dM, quantile) != kConditionRegisters) return -1;
-    switch (pad_registers(a.dO)) {
-    case 4: return launch_o<4>(a, quantile, num_cus, stream);
-    case 8: return launch_o<8>(a, quantile, num_cus, stream);
-    case 16: return launch_o<16>(a, quantile, num_cus, stream);
-    case 32: return launch_o<32>(a, quantile, num_cus, stream);
-    default: return -1;
-    }
+    if (quantile)
+        return dispatch_paddings<kQuantileMaxRegisters>(a.dO, a.dM, [&](auto po, auto pm) {
+            constexpr int PO = decltype(po)::value, PM = decltype(pm)::value, W = quantile_waves(PM);
+            const uint32_t grid = tile_grid(a.n, W, num_cus);
+            hipLaunchKernelGGL((em_condition_quantile_kernel<PO, PM, W>), dim3(grid), dim3(64 * W), sizeof(double) * W * stage_doubles(a.dM), stream,
+                               a.xt, a.ldx, a.n, a.dO, a.dM, a.K, a.lw, a.ldr, a.lse, a.table, a.probabilities, a.z, a.n_prob, a.out, a.ldq,
+                               a.iterations, a.means, a.skip);
+            return (int)grid;
+        });
+    return dispatch_paddings<kCdfMaxRegisters>(a.dO, a.dM, [&](auto po, auto pm) {
+        constexpr int PO = decltype(po)::value, PM = decltype(pm)::value, W = condition_waves(PM);
+        const uint32_t grid = tile_grid(a.n, W, num_cus);
+        hipLaunchKernelGGL((em_condition_cdf_kernel<PO, PM, W>), dim3(grid), dim3(64 * W), sizeof(double) * W * stage_doubles(a.dM), stream, a.xt,
+                           a.ldx, a.n, a.dO, a.dM, a.K, a.lw, a.ldr, a.lse, a.table, a.values, a.out, a.means, a.skip);
+        return (int)grid;
+    });
 }
 
 }  // namespace

@@ -27,7 +27,7 @@
 //   em_condition_sample_plain_kernel  any dO + dM <= 4096: thread = row, the normals go into the output row, the chain and the product
 //                                   run there in place from j = dM-1 down, table from global memory. The same order: the same bits.
 // Record: [mu_O (PO) | mu_M (PM) | A^T (PO x PM) | G (PM (PM+1) / 2: (j, c) at j (j+1)/2 + c)]; padding as em_condition.hip, +0.0 in G.
-#include "device.hpp"
+#include "em_condition_common.hpp"
 #include "exp_nonpos.hpp"
 #include "philox.hpp"
 
@@ -111,19 +111,7 @@ __global__ __launch_bounds__(64 * W) void em_condition_sample_kernel(const doubl
                     if (__ballot(run) == 0) continue;
                     const double* __restrict__ rec = table + (size_t)k * PS;   // wave-uniform -> scalar loads
                     double tj[PM];
-#pragma unroll
-                    for (int j = 0; j < PM; ++j) tj[j] = rec[PO + j];
-#pragma unroll
-                    for (int c0 = 0; c0 < PO; c0 += 4) {
-                        if (c0 < dO) {                           // (wave-uniform: a group of four coordinates beyond dO is not run at all)
-#pragma unroll
-                            for (int c = c0; c < c0 + 4; ++c) {
-                                const double zc = x[c] - rec[c];
-#pragma unroll
-                                for (int j = 0; j < PM; ++j) tj[j] = __builtin_fma(rec[PO + PM + c * PM + j], zc, tj[j]);
-                            }
-                        }
-                    }
+                    component_prediction(rec, x, dO, tj, PO, PM);
 #pragma unroll
                     for (int j = 0; j < PM; ++j) {
                         if (j < dM) {                            // (wave-uniform)
@@ -133,31 +121,10 @@ __global__ __launch_bounds__(64 * W) void em_condition_sample_kernel(const doubl
                         }
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-
-                // the tile is rows * dM contiguous doubles of the draw's block: two per lane and trip, (row, col) carried along
+                wave_sync();
                 const uint32_t rows = a.n - t * 64 < 64 ? a.n - t * 64 : 64;
-                const uint32_t count = rows * (uint32_t)dM;
-                double* dst = out + (size_t)(q0 + g) * a.ldq + (size_t)t * 64 * (size_t)dM;
-                const uint32_t step_rows = 128u / (uint32_t)dM, step_cols = 128u % (uint32_t)dM;
-                uint32_t row = (2u * lane) / (uint32_t)dM, col = (2u * lane) % (uint32_t)dM;
-                for (uint32_t e = 2u * lane; e < count; e += 128u) {
-                    const double v0 = stage[row * S + col];
-                    uint32_t row1 = row, col1 = col + 1;
-                    if (col1 == (uint32_t)dM) { col1 = 0; ++row1; }
-                    if (e + 1 < count) {
-                        const double v1 = stage[row1 * S + col1];
-                        *reinterpret_cast<double2*>(dst + e) = make_double2(v0, v1);
-                    } else {
-                        dst[e] = v0;
-                    }
-                    row += step_rows;
-                    col += step_cols;
-                    if (col >= (uint32_t)dM) { col -= (uint32_t)dM; ++row; }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();                 // (the next draw's stores wait for these reads)
+                move_staged<false>(stage, S, rows, (uint32_t)dM, out + (size_t)(q0 + g) * a.ldq + (size_t)t * 64 * (size_t)dM, lane);
+                wave_sync();                                     // (the next draw's stores wait for these reads)
             }
         }
     }
@@ -198,45 +165,14 @@ __global__ __launch_bounds__(256) void em_condition_sample_plain_kernel(Conditio
                 if (2 * p + 1 < dM) row[2 * p + 1] = z1;
             }
             const double* rec = a.table + (size_t)label * PS;
-            const double* mu_m = rec + dO;
-            const double* at = rec + dO + dM;
-            const double* G = at + (size_t)dO * dM;
+            const double* G = rec + dO + dM + (size_t)dO * dM;
             for (int j = dM - 1; j >= 0; --j) {
-                double tj = mu_m[j];
-                for (int c = 0; c < dO; ++c) tj = __builtin_fma(at[(size_t)c * dM + j], a.xt[(size_t)c * a.ldx + local] - rec[c], tj);
+                double tj = plain_prediction(rec, dO, dM, j, a.xt, a.ldx, local);
                 const double* Gj = G + (size_t)j * (j + 1) / 2;
                 for (int c = 0; c <= j; ++c) tj = __builtin_fma(Gj[c], row[c], tj);
                 row[j] = tj;                                     // (zeta_j is not read again: the rows below j are done)
             }
         }
-    }
-}
-
-constexpr int waves_for(int PM) { return PM <= 16 ? 4 : 2; }
-
-template <int PO, int PM>
-int launch_t(const ConditionSampleArgs& a, int num_cus, hipStream_t stream)
-{
-    constexpr int W = waves_for(PM);
-    const uint32_t tiles = (a.n + 63) / 64;
-    uint32_t grid = (tiles + W - 1) / W;
-    const uint32_t cap = (uint32_t)(num_cus > 0 ? num_cus : 256) * 4;
-    if (grid > cap) grid = cap;
-    const size_t bytes = sizeof(double) * (size_t)W * 64 * (size_t)(a.dM | 1) + sizeof(uint32_t) * (size_t)W * 64 * kDrawGroup;
-    // (the pointers once more as parameters of their own: __restrict__ there is what lets the table come in through scalar loads)
-    hipLaunchKernelGGL((em_condition_sample_kernel<PO, PM, W>), dim3(grid), dim3(64 * W), bytes, stream, a.xt, a.lw, a.lse, a.table, a.out, a.labels, a);
-    return (int)grid;
-}
-
-template <int PO>
-int launch_o(const ConditionSampleArgs& a, int num_cus, hipStream_t stream)
-{
-    switch (condition_pad(kConditionRegisters, a.dM)) {
-    case 4: return launch_t<PO, 4>(a, num_cus, stream);
-    case 8: return launch_t<PO, 8>(a, num_cus, stream);
-    case 16: return launch_t<PO, 16>(a, num_cus, stream);
-    case 32: return launch_t<PO, 32>(a, num_cus, stream);
-    default: return -1;
     }
 }
 
@@ -248,19 +184,18 @@ int launch_em_condition_sample(const ConditionSampleArgs& a, int num_cus, hipStr
     if ((a.ldq & 1) || a.ldq < (size_t)a.n * (size_t)a.dM) return -1;
     if (a.n == 0 || a.n_draws == 0) return 0;
     if (a.kernel == kConditionPlain) {
-        uint32_t grid = (a.n + 255) / 256;
-        const uint32_t cap = (uint32_t)(num_cus > 0 ? num_cus : 256) * 8;
-        if (grid > cap) grid = cap;
+        const uint32_t grid = row_grid(a.n, num_cus);
         hipLaunchKernelGGL(em_condition_sample_plain_kernel, dim3(grid), dim3(256), 0, stream, a);
         return (int)grid;
     }
-    switch (condition_pad(kConditionRegisters, a.dO)) {
-    case 4: return launch_o<4>(a, num_cus, stream);
-    case 8: return launch_o<8>(a, num_cus, stream);
-    case 16: return launch_o<16>(a, num_cus, stream);
-    case 32: return launch_o<32>(a, num_cus, stream);
-    default: return -1;
-    }
+    return dispatch_paddings<32>(a.dO, a.dM, [&](auto po, auto pm) {
+        constexpr int PO = decltype(po)::value, PM = decltype(pm)::value, W = condition_waves(PM);
+        const uint32_t grid = tile_grid(a.n, W, num_cus);
+        const size_t bytes = sizeof(double) * (size_t)W * 64 * (size_t)(a.dM | 1) + sizeof(uint32_t) * (size_t)W * 64 * kDrawGroup;
+        // (the pointers once more as parameters of their own: __restrict__ there is what lets the table come in through scalar loads)
+        hipLaunchKernelGGL((em_condition_sample_kernel<PO, PM, W>), dim3(grid), dim3(64 * W), bytes, stream, a.xt, a.lw, a.lse, a.table, a.out, a.labels, a);
+        return (int)grid;
+    });
 }
 
 }  // namespace mlhip

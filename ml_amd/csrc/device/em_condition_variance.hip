@@ -25,7 +25,7 @@
 //                                   a work array of the call, table from global memory, unpadded. Same order, same bits.
 // Record: [mu_O (PO) | mu_M (PM) | A^T (PO x PM) | c]: c = diag(C_k) (PM) in the diagonal form, the lower triangle of C_k packed row by
 // row ((a, b) at a (a + 1) / 2 + b, for the PADDED dM) in the full form; padding +0.0, except the rows c >= dO of A^T: -0.0.
-#include "device.hpp"
+#include "em_condition_common.hpp"
 #include "exp_nonpos.hpp"
 
 namespace mlhip {
@@ -48,55 +48,7 @@ __host__ __device__ constexpr size_t stage_doubles(int rows, int dM, bool full)
     return out > mean ? out : mean;
 }
 
-constexpr int variance_waves(int PM, bool full) { return full ? (PM <= 4 ? 4 : PM <= 8 ? 2 : 1) : (PM <= 16 ? 4 : 2); }
-
-/// Steps 1 - 2 of the definition: em_condition_kernel's chain, text for text.
-template <int PO, int PM>
-__device__ __forceinline__ void component_prediction(const double* __restrict__ rec, const double (&x)[PO], int dO, double (&tj)[PM])
-{
-#pragma unroll
-    for (int j = 0; j < PM; ++j) tj[j] = rec[PO + j];
-#pragma unroll
-    for (int c0 = 0; c0 < PO; c0 += 4) {
-        if (c0 < dO) {                                           // (wave-uniform: a group of four coordinates beyond dO is not run at all)
-#pragma unroll
-            for (int c = c0; c < c0 + 4; ++c) {
-                const double z = x[c] - rec[c];
-#pragma unroll
-                for (int j = 0; j < PM; ++j) tj[j] = __builtin_fma(rec[PO + PM + c * PM + j], z, tj[j]);
-            }
-        }
-    }
-}
-
-/// `rows` x `width` contiguous doubles of the output from the staging tile (row stride S), two per lane and trip, (row, col) carried
-/// along without a division. dst is 16-byte aligned.
-__device__ __forceinline__ void store_staged(const double* stage, int S, uint32_t rows, uint32_t width, double* __restrict__ dst, int lane)
-{
-    const uint32_t total = rows * width;
-    const uint32_t step_rows = 128u / width, step_cols = 128u % width;
-    uint32_t row = (2u * lane) / width, col = (2u * lane) % width;
-    for (uint32_t e = 2u * lane; e < total; e += 128u) {
-        const double v0 = stage[row * S + col];
-        uint32_t row1 = row, col1 = col + 1;
-        if (col1 == width) { col1 = 0; ++row1; }
-        if (e + 1 < total) {
-            const double v1 = stage[row1 * S + col1];
-            *reinterpret_cast<double2*>(dst + e) = make_double2(v0, v1);
-        } else {
-            dst[e] = v0;
-        }
-        row += step_rows;
-        col += step_cols;
-        if (col >= width) { col -= width; ++row; }
-    }
-}
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
+constexpr int variance_waves(int PM, bool full) { return full ? (PM <= 4 ? 4 : PM <= 8 ? 2 : 1) : condition_waves(PM); }
 
 template <int PO, int PM, int W, bool FULL>
 __global__ __launch_bounds__(64 * W) void em_condition_variance_kernel(const double* __restrict__ xt, size_t ldx, uint32_t n, int dO, int dM,
@@ -125,14 +77,14 @@ __global__ __launch_bounds__(64 * W) void em_condition_variance_kernel(const dou
 #pragma unroll
         for (int j = 0; j < PM; ++j) y[j] = 0.0;
 
-        // pass 1: em_condition_kernel's loop
+        // pass 1
         for (int k = 0; k < K; ++k) {
             const double r = live ? exp_nonpos(lw[(size_t)k * ldr + i] - l) : 0.0;
             const bool share = r != 0.0;                         // (a NaN has one: it reaches the output)
             if (skip && __ballot(share) == 0) continue;
             const double* __restrict__ rec = table + (size_t)k * PS;   // wave-uniform -> scalar loads
             double tj[PM];
-            component_prediction<PO, PM>(rec, x, dO, tj);
+            component_prediction(rec, x, dO, tj, PO, PM);
 #pragma unroll
             for (int j = 0; j < PM; ++j) {
                 const double v = __builtin_fma(r, tj[j], y[j]);
@@ -151,7 +103,7 @@ __global__ __launch_bounds__(64 * W) void em_condition_variance_kernel(const dou
             const double* __restrict__ rec = table + (size_t)k * PS;
             const double* __restrict__ ck = rec + PO + PM + PO * PM;
             double u[PM];
-            component_prediction<PO, PM>(rec, x, dO, u);
+            component_prediction(rec, x, dO, u, PO, PM);
 #pragma unroll
             for (int j = 0; j < PM; ++j) u[j] = u[j] - y[j];
             if constexpr (FULL) {
@@ -179,7 +131,7 @@ __global__ __launch_bounds__(64 * W) void em_condition_variance_kernel(const dou
             for (int j = 0; j < PM; ++j)
                 if (j < dM) stage[lane * SY + j] = y[j];
             wave_sync();
-            store_staged(stage, SY, rows, (uint32_t)dM, means + (size_t)t * 64 * (size_t)dM, lane);
+            move_staged<false>(stage, SY, rows, (uint32_t)dM, means + (size_t)t * 64 * (size_t)dM, lane);
             wave_sync();                                         // (the next stores to the tile wait for these reads)
         }
 #pragma unroll 1
@@ -200,7 +152,7 @@ __global__ __launch_bounds__(64 * W) void em_condition_variance_kernel(const dou
             }
             wave_sync();
             const uint32_t now = rows - first < (uint32_t)kRows ? rows - first : (uint32_t)kRows;
-            store_staged(stage, S, now, (uint32_t)width, out + ((size_t)t * 64 + first) * (size_t)width, lane);
+            move_staged<false>(stage, S, now, (uint32_t)width, out + ((size_t)t * 64 + first) * (size_t)width, lane);
             wave_sync();
         }
     }
@@ -225,13 +177,7 @@ __global__ __launch_bounds__(256) void em_condition_variance_plain_kernel(const 
             const double r = exp_nonpos(lw[(size_t)k * ldr + i] - l);
             if (!(r != 0.0)) continue;
             const double* rec = table + (size_t)k * PS;
-            const double* mu_m = rec + dO;
-            const double* at = rec + dO + dM;
-            for (int j = 0; j < dM; ++j) {
-                double tj = mu_m[j];
-                for (int c = 0; c < dO; ++c) tj = __builtin_fma(at[(size_t)c * dM + j], xt[(size_t)c * ldx + i] - rec[c], tj);
-                y[j] = __builtin_fma(r, tj, y[j]);
-            }
+            for (int j = 0; j < dM; ++j) y[j] = __builtin_fma(r, plain_prediction(rec, dO, dM, j, xt, ldx, i), y[j]);
         }
         if (full) {
             for (int a = 0; a < dM; ++a)
@@ -243,13 +189,9 @@ __global__ __launch_bounds__(256) void em_condition_variance_plain_kernel(const 
             const double r = exp_nonpos(lw[(size_t)k * ldr + i] - l);
             if (!(r != 0.0)) continue;
             const double* rec = table + (size_t)k * PS;
-            const double* mu_m = rec + dO;
-            const double* at = rec + dO + dM;
-            const double* ck = at + (size_t)dO * dM;
+            const double* ck = rec + dO + dM + (size_t)dO * dM;
             for (int j = 0; j < dM; ++j) {
-                double tj = mu_m[j];
-                for (int c = 0; c < dO; ++c) tj = __builtin_fma(at[(size_t)c * dM + j], xt[(size_t)c * ldx + i] - rec[c], tj);
-                const double uj = tj - y[j];
+                const double uj = plain_prediction(rec, dO, dM, j, xt, ldx, i) - y[j];
                 if (full) u[j] = uj;
                 else v[j] = __builtin_fma(r, __builtin_fma(uj, uj, ck[j]), v[j]);
             }
@@ -268,43 +210,6 @@ __global__ __launch_bounds__(256) void em_condition_variance_plain_kernel(const 
     }
 }
 
-int pad_registers(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= kVarianceMaxRegisters ? 32 : -1; }
-
-template <int PO, int PM, bool FULL>
-int launch_t(const ConditionVarianceArgs& a, int num_cus, hipStream_t stream)
-{
-    constexpr int W = variance_waves(PM, FULL);
-    const uint32_t tiles = (a.n + 63) / 64;
-    uint32_t grid = (tiles + W - 1) / W;
-    const uint32_t cap = (uint32_t)(num_cus > 0 ? num_cus : 256) * 4;
-    if (grid > cap) grid = cap;
-    const size_t bytes = sizeof(double) * (size_t)W * stage_doubles(stage_rows(PM, FULL), a.dM, FULL);
-    hipLaunchKernelGGL((em_condition_variance_kernel<PO, PM, W, FULL>), dim3(grid), dim3(64 * W), bytes, stream, a.xt, a.ldx, a.n, a.dO, a.dM, a.K,
-                       a.lw, a.ldr, a.lse, a.table, a.out, a.means, a.skip);
-    return (int)grid;
-}
-
-template <int PO>
-int launch_o(const ConditionVarianceArgs& a, int num_cus, hipStream_t stream)
-{
-    const int pm = pad_registers(a.dM);
-    if (a.full) {
-        switch (pm) {
-        case 4: return launch_t<PO, 4, true>(a, num_cus, stream);
-        case 8: return launch_t<PO, 8, true>(a, num_cus, stream);
-        case 16: return launch_t<PO, 16, true>(a, num_cus, stream);
-        default: return -1;
-        }
-    }
-    switch (pm) {
-    case 4: return launch_t<PO, 4, false>(a, num_cus, stream);
-    case 8: return launch_t<PO, 8, false>(a, num_cus, stream);
-    case 16: return launch_t<PO, 16, false>(a, num_cus, stream);
-    case 32: return launch_t<PO, 32, false>(a, num_cus, stream);
-    default: return -1;
-    }
-}
-
 }  // namespace
 
 int em_condition_variance_route(int dO, int dM, int full)
@@ -319,21 +224,24 @@ int launch_em_condition_variance(const ConditionVarianceArgs& a, int num_cus, hi
     if (a.n == 0) return 0;
     if (a.kernel == kConditionPlain) {
         if (!a.work) return -1;
-        uint32_t grid = (a.n + 255) / 256;
-        const uint32_t cap = (uint32_t)(num_cus > 0 ? num_cus : 256) * 8;
-        if (grid > cap) grid = cap;
+        const uint32_t grid = row_grid(a.n, num_cus);
         hipLaunchKernelGGL(em_condition_variance_plain_kernel, dim3(grid), dim3(256), 0, stream, a.xt, a.ldx, a.n, a.dO, a.dM, a.K, a.lw, a.ldr,
                            a.lse, a.table, a.out, a.means, a.work, a.full);
         return (int)grid;
     }
     if (em_condition_variance_route(a.dO, a.dM, a.full) != kConditionRegisters) return -1;
-    switch (pad_registers(a.dO)) {
-    case 4: return launch_o<4>(a, num_cus, stream);
-    case 8: return launch_o<8>(a, num_cus, stream);
-    case 16: return launch_o<16>(a, num_cus, stream);
-    case 32: return launch_o<32>(a, num_cus, stream);
-    default: return -1;
-    }
+    const auto launch = [&](auto po, auto pm, auto full) {
+        constexpr int PO = decltype(po)::value, PM = decltype(pm)::value;
+        constexpr bool FULL = decltype(full)::value;
+        constexpr int W = variance_waves(PM, FULL);
+        const uint32_t grid = tile_grid(a.n, W, num_cus);
+        const size_t bytes = sizeof(double) * (size_t)W * stage_doubles(stage_rows(PM, FULL), a.dM, FULL);
+        hipLaunchKernelGGL((em_condition_variance_kernel<PO, PM, W, FULL>), dim3(grid), dim3(64 * W), bytes, stream, a.xt, a.ldx, a.n, a.dO, a.dM,
+                           a.K, a.lw, a.ldr, a.lse, a.table, a.out, a.means, a.skip);
+        return (int)grid;
+    };
+    if (a.full) return dispatch_paddings<kVarianceMaxRegistersFull>(a.dO, a.dM, [&](auto po, auto pm) { return launch(po, pm, std::true_type{}); });
+    return dispatch_paddings<kVarianceMaxRegisters>(a.dO, a.dM, [&](auto po, auto pm) { return launch(po, pm, std::false_type{}); });
 }
 
 }  // namespace mlhip

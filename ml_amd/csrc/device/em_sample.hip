@@ -12,7 +12,7 @@
 //   em_sample_plain_kernel             64 < d <= 4096: the normals go to the output row, the product runs there in place.
 // The generator: philox.hpp, on its stream 0.
 // Table: [L of component 0 .. (packed lower triangle, row by row: (j, c) at j (j+1)/2 + c) | mu (K x d)]; a tied model holds ONE L.
-#include "device.hpp"
+#include "em_condition_common.hpp"   // the staged tile store
 #include "philox.hpp"
 
 namespace mlhip {
@@ -82,31 +82,10 @@ __global__ __launch_bounds__(64 * W) void em_sample_kernel(SampleArgs a)
                 stage[lane * S + j] = acc;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-
-        // the tile is rows * d contiguous doubles of the output: two per lane and trip, (row, col) carried along without a division
+        wave_sync();
         const uint64_t rows = a.n - t * 64 < 64 ? a.n - t * 64 : 64;
-        const uint32_t total = (uint32_t)rows * (uint32_t)d;
-        double* out = a.x + t * 64 * (uint64_t)d;
-        const uint32_t step_rows = 128u / (uint32_t)d, step_cols = 128u % (uint32_t)d;
-        uint32_t row = (2u * lane) / (uint32_t)d, col = (2u * lane) % (uint32_t)d;
-        for (uint32_t e = 2u * lane; e < total; e += 128u) {
-            const double v0 = stage[row * S + col];
-            uint32_t row1 = row, col1 = col + 1;
-            if (col1 == (uint32_t)d) { col1 = 0; ++row1; }
-            if (e + 1 < total) {
-                const double v1 = stage[row1 * S + col1];
-                *reinterpret_cast<double2*>(out + e) = make_double2(v0, v1);
-            } else {
-                out[e] = v0;
-            }
-            row += step_rows;
-            col += step_cols;
-            if (col >= (uint32_t)d) { col -= (uint32_t)d; ++row; }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();                         // (the next tile's stores wait for these reads)
+        move_staged<false>(stage, S, (uint32_t)rows, (uint32_t)d, a.x + t * 64 * (uint64_t)d, lane);
+        wave_sync();                                             // (the next tile's stores wait for these reads)
     }
 }
 

@@ -596,38 +596,103 @@ void check_observed(const std::vector<unsigned int>& observed, Index d)
         seen[c] = 1;
     }
 }
-}  // namespace
 
-MatrixXd EM::conditional_means(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, double* log_densities) const
+/// f(context, handle, first, rows) for every batch of columns [first, first + rows) of `data_observed`, uploaded for the call.
+template <class F> void for_each_batch(ConstMatrixRef data_observed, F&& f)
 {
-    const Index d = means().rows();
-    // (the order of sample: that there is a shape, the arguments against it, the device, the decompositions)
-    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
-    check_observed(observed, d);
-    const Index d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed, n = data_observed.cols();
-    if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
-    require_fitted();
-    const unsigned int K = number_components_;
-    const std::vector<double> cov_flat = flat_covariances();
-    std::vector<double> means_observed(static_cast<std::size_t>(K * d_observed)), covariances_observed(static_cast<std::size_t>(K * d_observed * d_observed)),
-        maps(static_cast<std::size_t>(K * d_missing * d_observed)), means_missing(static_cast<std::size_t>(K * d_missing));
-    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
-    check(mlhip_em_condition(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, means_.data(), cov_flat.data(),
-                             reinterpret_cast<const uint32_t*>(observed.data()), static_cast<uint32_t>(d_observed), means_observed.data(),
-                             covariances_observed.data(), maps.data(), means_missing.data()));
-    MatrixXd out(d_missing, n);
-    if (!n) return out;
     mlhip_ctx* ctx = device::context();
-    const Index batch = Clustering::detail::score_batch_rows();
+    const Index n = data_observed.cols(), batch = Clustering::detail::score_batch_rows();
     for (Index first = 0; first < n; first += batch) {
         const Index rows = std::min(batch, n - first);
         DataGuard dev;
-        check(mlhip_data_upload(ctx, data_observed.col(first), static_cast<uint32_t>(d_observed), static_cast<uint64_t>(rows),
+        check(mlhip_data_upload(ctx, data_observed.col(first), static_cast<uint32_t>(data_observed.rows()), static_cast<uint64_t>(rows),
                                 data_observed.outerStride(), &dev.h));
-        check(mlhip_em_conditional_means(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
-                                         covariances_observed.data(), maps.data(), means_missing.data(), out.col(first), d_missing,
-                                         log_densities ? log_densities + first : nullptr));
+        f(ctx, dev.h, first, rows);
     }
+}
+
+/// A result of `blocks` blocks (one per draw or probability) of n points x `width` values, block q of point i at (q * n + i) * width.
+/// A batch's call writes its blocks batch rows apart, the result's lie n apart: target() is where the call writes -- the result
+/// itself where the batch is all n points, else a buffer --, and scatter() then copies the buffer's blocks to their places.
+template <class T> struct BlockScatter {
+    T* out;                                                      // (null: the result is not asked for)
+    Index width, blocks, n;
+    std::vector<T> block;
+    T* target(Index rows)
+    {
+        if (!out || rows == n) return out;
+        block.resize(static_cast<std::size_t>(blocks * rows * width));
+        return block.data();
+    }
+    void scatter(Index first, Index rows) const
+    {
+        if (!out || rows == n) return;
+        for (Index q = 0; q < blocks; ++q)
+            std::copy_n(block.data() + static_cast<std::size_t>(q * rows * width), rows * width, out + (q * n + first) * width);
+    }
+};
+}  // namespace
+
+struct EM::ConditionDims {
+    Index d, d_observed, d_missing, n;
+};
+
+/// The model conditioned on the observed coordinates, as the mlhip_em_conditional_* calls take it.
+struct EM::Conditioned {
+    std::vector<double> means_observed, covariances_observed, maps, means_missing, covariances_missing, factors, scales, inverse_scales;
+};
+
+EM::ConditionDims EM::check_conditional_call(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed) const
+{
+    const Index d = means_.rows();
+    // (the order of sample: that there is a shape, the arguments against it; then, in condition(), the device and the decompositions)
+    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    check_observed(observed, d);
+    const Index d_observed = static_cast<Index>(observed.size());
+    if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
+    return {d, d_observed, d - d_observed, data_observed.cols()};
+}
+
+EM::Conditioned EM::condition(const std::vector<unsigned int>& observed, ConditionParts parts) const
+{
+    require_fitted();
+    const unsigned int K = number_components_;
+    const Index d = means_.rows(), d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed;
+    const std::vector<double> cov_flat = flat_covariances();
+    Conditioned c;
+    c.means_observed.resize(static_cast<std::size_t>(K * d_observed));
+    c.covariances_observed.resize(static_cast<std::size_t>(K * d_observed * d_observed));
+    c.maps.resize(static_cast<std::size_t>(K * d_missing * d_observed));
+    c.means_missing.resize(static_cast<std::size_t>(K * d_missing));
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
+    const uint32_t* coordinates = reinterpret_cast<const uint32_t*>(observed.data());
+    check(mlhip_em_condition(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, means_.data(), cov_flat.data(), coordinates,
+                             static_cast<uint32_t>(d_observed), c.means_observed.data(), c.covariances_observed.data(), c.maps.data(),
+                             c.means_missing.data()));
+    if (parts == ConditionParts::Marginal) return c;
+    c.covariances_missing.resize(static_cast<std::size_t>(K * d_missing * d_missing));
+    if (parts == ConditionParts::Factors) c.factors.resize(c.covariances_missing.size());
+    check(mlhip_em_condition_covariances(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, cov_flat.data(), coordinates,
+                                         static_cast<uint32_t>(d_observed), c.covariances_missing.data(),
+                                         c.factors.empty() ? nullptr : c.factors.data()));
+    if (parts != ConditionParts::Scales) return c;
+    c.scales.resize(static_cast<std::size_t>(K * d_missing));
+    c.inverse_scales.resize(c.scales.size());
+    check(mlhip_em_condition_scales(K, static_cast<uint32_t>(d_missing), c.covariances_missing.data(), c.scales.data(), c.inverse_scales.data()));
+    return c;
+}
+
+MatrixXd EM::conditional_means(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, double* log_densities) const
+{
+    const ConditionDims s = check_conditional_call(observed, data_observed);
+    const Conditioned c = condition(observed, ConditionParts::Marginal);
+    MatrixXd out(s.d_missing, s.n);
+    if (!s.n) return out;
+    for_each_batch(data_observed, [&](mlhip_ctx* ctx, mlhip_data* block, Index first, Index) {
+        check(mlhip_em_conditional_means(ctx, block, number_components_, static_cast<uint32_t>(s.d_missing), mixing_probabilities_.data(),
+                                         c.means_observed.data(), c.covariances_observed.data(), c.maps.data(), c.means_missing.data(),
+                                         out.col(first), s.d_missing, log_densities ? log_densities + first : nullptr));
+    });
     return out;
 }
 
@@ -657,152 +722,73 @@ std::vector<MatrixXd> EM::conditional_covariances(const std::vector<unsigned int
 MatrixXd EM::conditional_samples(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, Index n_draws, std::uint64_t seed,
                                  std::vector<unsigned int>* labels) const
 {
-    const Index d = means().rows();
-    // (the order of conditional_means: that there is a shape, the arguments against it, the device, the decompositions)
-    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
-    check_observed(observed, d);
-    const Index d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed, n = data_observed.cols();
-    if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
+    const ConditionDims s = check_conditional_call(observed, data_observed);
     if (n_draws < 0 || static_cast<std::uint64_t>(n_draws) > 0xFFFFFFFFull) throw std::invalid_argument("EM: n_draws must be 0 .. 2^32 - 1");
-    require_fitted();
-    const unsigned int K = number_components_;
-    const std::vector<double> cov_flat = flat_covariances();
-    std::vector<double> means_observed(static_cast<std::size_t>(K * d_observed)), covariances_observed(static_cast<std::size_t>(K * d_observed * d_observed)),
-        maps(static_cast<std::size_t>(K * d_missing * d_observed)), means_missing(static_cast<std::size_t>(K * d_missing)),
-        covariances_missing(static_cast<std::size_t>(K * d_missing * d_missing)), factors(static_cast<std::size_t>(K * d_missing * d_missing));
-    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
-    const uint32_t* coordinates = reinterpret_cast<const uint32_t*>(observed.data());
-    check(mlhip_em_condition(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, means_.data(), cov_flat.data(), coordinates,
-                             static_cast<uint32_t>(d_observed), means_observed.data(), covariances_observed.data(), maps.data(),
-                             means_missing.data()));
-    check(mlhip_em_condition_covariances(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, cov_flat.data(), coordinates,
-                                         static_cast<uint32_t>(d_observed), covariances_missing.data(), factors.data()));
-    MatrixXd out(d_missing, n_draws * n);
-    if (labels) labels->assign(static_cast<std::size_t>(n_draws * n), 0u);
-    if (!n || !n_draws) return out;
-    mlhip_ctx* ctx = device::context();
-    const Index batch = Clustering::detail::score_batch_rows();
-    std::vector<double> block;                                   // (a batch's draws lie batch rows apart, the result's n: one copy per draw)
-    std::vector<uint32_t> block_labels;
-    for (Index first = 0; first < n; first += batch) {
-        const Index rows = std::min(batch, n - first);
-        DataGuard dev;
-        check(mlhip_data_upload(ctx, data_observed.col(first), static_cast<uint32_t>(d_observed), static_cast<uint64_t>(rows),
-                                data_observed.outerStride(), &dev.h));
-        const bool whole = rows == n;                          // (one batch: the call writes the result in place)
-        if (!whole) block.resize(static_cast<std::size_t>(n_draws * rows * d_missing));
-        if (!whole && labels) block_labels.resize(static_cast<std::size_t>(n_draws * rows));
-        check(mlhip_em_conditional_samples(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
-                                           covariances_observed.data(), maps.data(), means_missing.data(), factors.data(), seed,
-                                           static_cast<uint64_t>(first), 0u, static_cast<uint32_t>(n_draws), whole ? out.data() : block.data(),
-                                           d_missing, !labels ? nullptr : whole ? labels->data() : block_labels.data()));
-        if (whole) break;
-        for (Index q = 0; q < n_draws; ++q) {
-            std::copy_n(block.data() + static_cast<std::size_t>(q * rows * d_missing), rows * d_missing, out.col(q * n + first));
-            if (labels) std::copy_n(block_labels.data() + static_cast<std::size_t>(q * rows), rows, labels->data() + q * n + first);
-        }
-    }
+    const Conditioned c = condition(observed, ConditionParts::Factors);
+    MatrixXd out(s.d_missing, n_draws * s.n);
+    if (labels) labels->assign(static_cast<std::size_t>(n_draws * s.n), 0u);
+    if (!s.n || !n_draws) return out;
+    BlockScatter<double> draws{out.data(), s.d_missing, n_draws, s.n, {}};
+    BlockScatter<uint32_t> draw_labels{labels ? labels->data() : nullptr, 1, n_draws, s.n, {}};
+    for_each_batch(data_observed, [&](mlhip_ctx* ctx, mlhip_data* block, Index first, Index rows) {
+        check(mlhip_em_conditional_samples(ctx, block, number_components_, static_cast<uint32_t>(s.d_missing), mixing_probabilities_.data(),
+                                           c.means_observed.data(), c.covariances_observed.data(), c.maps.data(), c.means_missing.data(),
+                                           c.factors.data(), seed, static_cast<uint64_t>(first), 0u, static_cast<uint32_t>(n_draws),
+                                           draws.target(rows), s.d_missing, draw_labels.target(rows)));
+        draws.scatter(first, rows);
+        draw_labels.scatter(first, rows);
+    });
     return out;
 }
 
 MatrixXd EM::conditional_variances(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, bool full_covariance,
                                    MatrixXd* means) const
 {
-    const Index d = means_.rows();
-    // (the order of conditional_means: that there is a shape, the arguments against it, the device, the decompositions)
-    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
-    check_observed(observed, d);
-    const Index d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed, n = data_observed.cols();
-    if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
-    require_fitted();
-    const unsigned int K = number_components_;
-    const std::vector<double> cov_flat = flat_covariances();
-    std::vector<double> means_observed(static_cast<std::size_t>(K * d_observed)), covariances_observed(static_cast<std::size_t>(K * d_observed * d_observed)),
-        maps(static_cast<std::size_t>(K * d_missing * d_observed)), means_missing(static_cast<std::size_t>(K * d_missing)),
-        covariances_missing(static_cast<std::size_t>(K * d_missing * d_missing));
-    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
-    const uint32_t* coordinates = reinterpret_cast<const uint32_t*>(observed.data());
-    check(mlhip_em_condition(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, means_.data(), cov_flat.data(), coordinates,
-                             static_cast<uint32_t>(d_observed), means_observed.data(), covariances_observed.data(), maps.data(),
-                             means_missing.data()));
-    check(mlhip_em_condition_covariances(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, cov_flat.data(), coordinates,
-                                         static_cast<uint32_t>(d_observed), covariances_missing.data(), nullptr));
-    const Index width = full_covariance ? d_missing * d_missing : d_missing;
-    MatrixXd out(width, n);
-    if (means) means->resize(d_missing, n);
-    if (!n) return out;
-    mlhip_ctx* ctx = device::context();
-    const Index batch = Clustering::detail::score_batch_rows();
-    for (Index first = 0; first < n; first += batch) {
-        const Index rows = std::min(batch, n - first);
-        DataGuard dev;
-        check(mlhip_data_upload(ctx, data_observed.col(first), static_cast<uint32_t>(d_observed), static_cast<uint64_t>(rows),
-                                data_observed.outerStride(), &dev.h));
-        check(mlhip_em_conditional_variances(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
-                                             covariances_observed.data(), maps.data(), means_missing.data(), covariances_missing.data(),
-                                             full_covariance ? 1 : 0, out.col(first), width, means ? means->col(first) : nullptr, d_missing,
-                                             nullptr));
-    }
+    const ConditionDims s = check_conditional_call(observed, data_observed);
+    const Conditioned c = condition(observed, ConditionParts::Covariances);
+    const Index width = full_covariance ? s.d_missing * s.d_missing : s.d_missing;
+    MatrixXd out(width, s.n);
+    if (means) means->resize(s.d_missing, s.n);
+    if (!s.n) return out;
+    for_each_batch(data_observed, [&](mlhip_ctx* ctx, mlhip_data* block, Index first, Index) {
+        check(mlhip_em_conditional_variances(ctx, block, number_components_, static_cast<uint32_t>(s.d_missing), mixing_probabilities_.data(),
+                                             c.means_observed.data(), c.covariances_observed.data(), c.maps.data(), c.means_missing.data(),
+                                             c.covariances_missing.data(), full_covariance ? 1 : 0, out.col(first), width,
+                                             means ? means->col(first) : nullptr, s.d_missing, nullptr));
+    });
     return out;
 }
 
 MatrixXd EM::conditional_distribution(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed, const ConstMatrixRef* values,
                                       const std::vector<double>* probabilities) const
 {
-    const Index d = means_.rows();
-    // (the order of conditional_means: that there is a shape, the arguments against it, the device, the decompositions)
-    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
-    check_observed(observed, d);
-    const Index d_observed = static_cast<Index>(observed.size()), d_missing = d - d_observed, n = data_observed.cols();
-    if (data_observed.rows() != d_observed) throw std::invalid_argument("Wrong data size");
-    if (values && (values->rows() != d_missing || values->cols() != n)) throw std::invalid_argument("EM: values must hold one row per missing coordinate and one column per point");
+    const ConditionDims s = check_conditional_call(observed, data_observed);
+    if (values && (values->rows() != s.d_missing || values->cols() != s.n)) throw std::invalid_argument("EM: values must hold one row per missing coordinate and one column per point");
     const Index n_probabilities = probabilities ? static_cast<Index>(probabilities->size()) : 1;
     if (probabilities) {
         if (static_cast<std::uint64_t>(n_probabilities) > 0xFFFFFFFFull) throw std::invalid_argument("EM: too many probabilities");
         for (const double p : *probabilities)
             if (!(p > 0.0 && p < 1.0)) throw std::invalid_argument("EM: a probability must lie strictly inside (0, 1)");
     }
-    require_fitted();
-    const unsigned int K = number_components_;
-    const std::vector<double> cov_flat = flat_covariances();
-    std::vector<double> means_observed(static_cast<std::size_t>(K * d_observed)), covariances_observed(static_cast<std::size_t>(K * d_observed * d_observed)),
-        maps(static_cast<std::size_t>(K * d_missing * d_observed)), means_missing(static_cast<std::size_t>(K * d_missing)),
-        covariances_missing(static_cast<std::size_t>(K * d_missing * d_missing)), scales(static_cast<std::size_t>(K * d_missing)),
-        inverse_scales(static_cast<std::size_t>(K * d_missing));
-    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "coordinates are 32-bit");
-    const uint32_t* coordinates = reinterpret_cast<const uint32_t*>(observed.data());
-    check(mlhip_em_condition(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, means_.data(), cov_flat.data(), coordinates,
-                             static_cast<uint32_t>(d_observed), means_observed.data(), covariances_observed.data(), maps.data(),
-                             means_missing.data()));
-    check(mlhip_em_condition_covariances(static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, cov_flat.data(), coordinates,
-                                         static_cast<uint32_t>(d_observed), covariances_missing.data(), nullptr));
-    check(mlhip_em_condition_scales(K, static_cast<uint32_t>(d_missing), covariances_missing.data(), scales.data(), inverse_scales.data()));
-    MatrixXd out(d_missing, n_probabilities * n);
-    if (!n || !n_probabilities) return out;
-    mlhip_ctx* ctx = device::context();
-    const Index batch = Clustering::detail::score_batch_rows();
-    std::vector<double> block;                                   // (a batch's quantiles lie batch rows apart, the result's n: one copy per probability)
-    for (Index first = 0; first < n; first += batch) {
-        const Index rows = std::min(batch, n - first);
-        DataGuard dev;
-        check(mlhip_data_upload(ctx, data_observed.col(first), static_cast<uint32_t>(d_observed), static_cast<uint64_t>(rows),
-                                data_observed.outerStride(), &dev.h));
+    const Conditioned c = condition(observed, ConditionParts::Scales);
+    MatrixXd out(s.d_missing, n_probabilities * s.n);
+    if (!s.n || !n_probabilities) return out;
+    BlockScatter<double> quantiles{out.data(), s.d_missing, n_probabilities, s.n, {}};
+    for_each_batch(data_observed, [&](mlhip_ctx* ctx, mlhip_data* block, Index first, Index rows) {
         if (values) {
-            check(mlhip_em_conditional_cdfs(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
-                                            covariances_observed.data(), maps.data(), means_missing.data(), scales.data(), inverse_scales.data(),
-                                            values->col(first), values->outerStride(), out.col(first), d_missing, nullptr, d_missing, nullptr));
-            continue;
+            check(mlhip_em_conditional_cdfs(ctx, block, number_components_, static_cast<uint32_t>(s.d_missing), mixing_probabilities_.data(),
+                                            c.means_observed.data(), c.covariances_observed.data(), c.maps.data(), c.means_missing.data(),
+                                            c.scales.data(), c.inverse_scales.data(), values->col(first), values->outerStride(), out.col(first),
+                                            s.d_missing, nullptr, s.d_missing, nullptr));
+            return;
         }
-        const bool whole = rows == n;                          // (one batch: the call writes the result in place)
-        if (!whole) block.resize(static_cast<std::size_t>(n_probabilities * rows * d_missing));
-        check(mlhip_em_conditional_quantiles(ctx, dev.h, K, static_cast<uint32_t>(d_missing), mixing_probabilities_.data(), means_observed.data(),
-                                             covariances_observed.data(), maps.data(), means_missing.data(), scales.data(), inverse_scales.data(),
-                                             probabilities->data(), static_cast<uint32_t>(n_probabilities), whole ? out.data() : block.data(),
-                                             d_missing, nullptr, d_missing, nullptr, nullptr));
-        if (whole) break;
-        for (Index q = 0; q < n_probabilities; ++q)
-            std::copy_n(block.data() + static_cast<std::size_t>(q * rows * d_missing), rows * d_missing, out.col(q * n + first));
-    }
+        check(mlhip_em_conditional_quantiles(ctx, block, number_components_, static_cast<uint32_t>(s.d_missing), mixing_probabilities_.data(),
+                                             c.means_observed.data(), c.covariances_observed.data(), c.maps.data(), c.means_missing.data(),
+                                             c.scales.data(), c.inverse_scales.data(), probabilities->data(),
+                                             static_cast<uint32_t>(n_probabilities), quantiles.target(rows), s.d_missing, nullptr, s.d_missing,
+                                             nullptr, nullptr));
+        quantiles.scatter(first, rows);
+    });
     return out;
 }
 

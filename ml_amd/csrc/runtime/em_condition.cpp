@@ -1,33 +1,104 @@
 // mlhip_em_condition / mlhip_em_conditional_means: E[x_M | x_O] of every row of a resident block of OBSERVED coordinates under a
-// mixture conditioned on them (the definition: mlhip.h; the kernels: device/em_condition.hip). The host conditions the model
-// (host::condition: marginal parameters and the regression maps A_k); the device runs the marginal mixture's E-step in its exact form
-// on chunks of whole tiles, as mlhip_em_score's composed route does, and the conditioning kernel behind every chunk. Every buffer is
-// the call's own, taken from the context's pool: the handle's E-step state, weights, ridge and label history stay as they were.
+// mixture conditioned on them (the definition: mlhip.h; the kernels: device/em_condition.hip) -- and the chunked pass every
+// conditioning call runs (ConditionPass, internal.hpp). The host conditions the model (host::condition: marginal parameters and the
+// regression maps A_k); the device runs the marginal mixture's E-step in its exact form on chunks of whole tiles, as mlhip_em_score's
+// composed route does, and the call's own kernel behind every chunk.
 #include "internal.hpp"
 
 namespace mlhip_rt {
 
-std::vector<double> condition_table(int kernel, int K, int dO, int dM, const double* means_observed, const double* maps,
-                                    const double* means_missing, const double* factors)
+void ChunkEstep::reserve(int K, uint32_t chunk_rows)
 {
+    chunk = chunk_rows;
+    lw.reserve(sizeof(double) * (size_t)chunk * K);
+    lse.reserve(sizeof(double) * chunk);
+    ll.reserve(sizeof(double) * kMaxLlPartials);
+}
+
+void ChunkEstep::launch(mlhip_data* dt, const EmRoute& em, int K, const DevBuf& records, uint32_t row, uint32_t rows)
+{
+    mlhip_ctx* ctx = dt->ctx;
+    EstepArgs a{};
+    a.xt = dt->xt.as<double>() + row; a.ldx = dt->ldx; a.n = rows; a.D = dt->D;
+    a.params = records.as<double>(); a.K = K;
+    a.lw = lw.as<double>(); a.ldr = chunk; a.lse = lse.as<double>();
+    a.ll_partials = ll.as<double>(); a.n_ll_partials = kMaxLlPartials;
+    a.shift = dt->shift_dev.as<double>(); a.fold = 0; a.with_lse = 1;
+    a.num_cus = ctx->num_cus;
+    a.plain = em.estep == Estep::kPlain;
+    int grid = 0;
+    ctx->timed("em_estep", [&] {
+        grid = em.estep == Estep::kMatrix4 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
+    });
+    if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
+}
+
+std::vector<double> condition_table(int kernel, const ConditionedModel& m, int dO, size_t tail, const ConditionTail& fill)
+{
+    const int K = m.K, dM = m.dM;
     const size_t po = (size_t)condition_pad(kernel, dO), pm = (size_t)condition_pad(kernel, dM), ps = condition_record_doubles(kernel, dO, dM);
-    const size_t stride = factors ? condition_sample_record_doubles(kernel, dO, dM) : ps;
+    const size_t stride = ps + tail;
     std::vector<double> table(stride * K, 0.0);
     for (int k = 0; k < K; ++k) {
         double* rec = table.data() + stride * k;
-        std::copy_n(means_observed + (size_t)k * dO, dO, rec);
-        std::copy_n(means_missing + (size_t)k * dM, dM, rec + po);
-        const double* A = maps + (size_t)k * dM * dO;
+        std::copy_n(m.means_observed + (size_t)k * dO, dO, rec);
+        std::copy_n(m.means_missing + (size_t)k * dM, dM, rec + po);
+        const double* A = m.maps + (size_t)k * dM * dO;
         for (int c = 0; c < dO; ++c)
             for (int j = 0; j < dM; ++j) rec[po + pm + (size_t)c * pm + j] = A[(size_t)j * dO + c];
-        // (a padded coordinate's term is fma(-0.0, +0.0, t) = t for every t, a t of -0.0 included: device/em_condition.hip)
         std::fill(rec + po + pm + (size_t)dO * pm, rec + ps, -0.0);
-        if (!factors) continue;
-        const double* G = factors + (size_t)k * dM * dM;
-        for (int j = 0; j < dM; ++j)
-            for (int c = 0; c <= j; ++c) rec[ps + (size_t)j * (j + 1) / 2 + c] = G[(size_t)j * dM + c];
+        if (tail) fill(k, rec + ps);
     }
     return table;
+}
+
+ConditionPass::ConditionPass(mlhip_data* dt, const ConditionedModel& m, const EmRoute& em, int kernel, uint32_t chunk_rows, size_t tail,
+                             const ConditionTail& fill, const char* unsupported)
+    : dt_(dt), em_(em), records_(&dt->pool), work_(&dt->pool), table_(&dt->pool), staging_(&dt->pool), estep_(dt)
+{
+    const int dO = dt->d;
+    if (condition_pad(kernel, dO) < 0 || condition_pad(kernel, m.dM) < 0) throw Unsupported(unsupported);
+    build_records(dt, em, m.K, m.mixing, m.means_observed, m.covs_observed, false, records_, staging_, work_);
+    host_table_ = condition_table(kernel, m, dO, tail, fill);
+    table_.reserve(sizeof(double) * host_table_.size());
+    HIP_CHECK(hipMemcpyAsync(table_.p, host_table_.data(), sizeof(double) * host_table_.size(), hipMemcpyHostToDevice, dt->ctx->stream));
+    estep_.reserve(m.K, chunk_rows);
+    c_.ldx = dt->ldx; c_.dO = dO; c_.dM = m.dM; c_.K = m.K;
+    c_.lw = estep_.lw.as<double>(); c_.ldr = chunk_rows; c_.lse = estep_.lse.as<double>();
+    c_.table = table_.as<double>(); c_.kernel = kernel;
+}
+
+void ConditionPass::run(double* log_density, const std::function<void(const ConditionChunk& c, uint32_t row)>& behind)
+{
+    // (ML/EM.cpp:197-198 applies the constant to the mean)
+    const double offset = (double)c_.dO * log_two_pi() / 2;
+    for (uint32_t row = 0; row < dt_->n; row += estep_.chunk) {
+        const uint32_t rows = std::min(estep_.chunk, dt_->n - row);
+        estep_.launch(dt_, em_, c_.K, records_, row, rows);
+        c_.xt = dt_->xt.as<double>() + row; c_.n = rows;
+        behind(c_, row);
+        if (!log_density) continue;
+        download_rows(log_density + row, 1, estep_.lse.p, rows, 1);
+        for (uint32_t i = 0; i < rows; ++i) log_density[row + i] -= offset;
+    }
+    dt_->ctx->sync();
+}
+
+void on_block_or_shards(mlhip_ctx* ctx, mlhip_data* data, const std::function<void(Shard&)>& f)
+{
+    if (!ctx->group) {
+        Shard whole;
+        whole.ctx = ctx; whole.part = data; whole.n_rows = data->n;
+        f(whole);
+        return;
+    }
+    // (every shard works on its own rows: no collective, nothing to put together but the rows' places in the caller's arrays)
+    fan_out(ctx, data, [&](Shard& sh) {
+        return guarded([&] {
+            sh.ctx->use();
+            f(sh);
+        });
+    });
 }
 
 Covariance check_condition_arguments(uint32_t d, uint32_t K, int covariance_type, const uint32_t* observed, uint32_t n_observed)
@@ -48,63 +119,24 @@ Covariance check_condition_arguments(uint32_t d, uint32_t K, int covariance_type
 
 namespace {
 
-void em_conditional_means(mlhip_data* dt, int K, int dM, const double* mixing, const double* means_observed, const double* covs_observed,
-                          const double* maps, const double* means_missing, double* out, int64_t ld_out, double* log_density)
+void em_conditional_means(mlhip_data* dt, const ConditionedModel& m, double* out, int64_t ld_out, double* log_density)
 {
     mlhip_ctx* ctx = dt->ctx;
     if (!dt->n) return;
-    const int dO = dt->d;
-    const ConditionRoute r = condition_route(dt, K, dM);
-    if (condition_pad(r.kernel, dO) < 0 || condition_pad(r.kernel, dM) < 0) throw Unsupported("conditioning kernel not instantiated for this shape");
-    const uint32_t chunk = r.chunk_rows;
-    DevBuf records{&dt->pool}, work{&dt->pool}, table{&dt->pool}, lw{&dt->pool}, lse{&dt->pool}, ll{&dt->pool}, y{&dt->pool};
-    PinnedBuf staging{&dt->pool};
-    build_records(dt, r.em, K, mixing, means_observed, covs_observed, false, records, staging, work);   // (always the exact form: no FOLD)
-    const std::vector<double> host_table = condition_table(r.kernel, K, dO, dM, means_observed, maps, means_missing, nullptr);
-    table.reserve(sizeof(double) * host_table.size());
-    HIP_CHECK(hipMemcpyAsync(table.p, host_table.data(), sizeof(double) * host_table.size(), hipMemcpyHostToDevice, ctx->stream));
-    lw.reserve(sizeof(double) * (size_t)chunk * K);
-    lse.reserve(sizeof(double) * chunk);
-    ll.reserve(sizeof(double) * kMaxLlPartials);
-    y.reserve(sizeof(double) * (size_t)chunk * dM);
-    std::vector<double> packed;                                 // ld_out > dM: a chunk comes down contiguous and is spread by the CPU
-    if (ld_out != (int64_t)dM) packed.resize((size_t)std::min(chunk, dt->n) * dM);
-    // the kernels' lw leave the density's constant out, like the E-step's (ML/EM.cpp:197-198 applies it to the mean)
-    const double offset = (double)dO * log_two_pi() / 2;
-    for (uint32_t row = 0; row < dt->n; row += chunk) {
-        const uint32_t rows = std::min(chunk, dt->n - row);   // (padded_samples(rows) <= chunk: the chunk is whole tiles)
-        EstepArgs a{};
-        a.xt = dt->xt.as<double>() + row; a.ldx = dt->ldx; a.n = rows; a.D = dt->D;
-        a.params = records.as<double>(); a.K = K;
-        a.lw = lw.as<double>(); a.ldr = chunk; a.lse = lse.as<double>();
-        a.ll_partials = ll.as<double>(); a.n_ll_partials = kMaxLlPartials;
-        a.shift = dt->shift_dev.as<double>(); a.fold = 0; a.with_lse = 1;
-        a.num_cus = ctx->num_cus;
-        a.plain = r.em.estep == Estep::kPlain;
-        int grid = 0;
-        ctx->timed("em_estep", [&] {
-            grid = r.em.estep == Estep::kMatrix4 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
-        });
-        if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
+    const ConditionRoute r = condition_route(dt, m.K, m.dM);
+    ConditionPass pass(dt, m, r.em, r.kernel, r.chunk_rows, 0, {}, "conditioning kernel not instantiated for this shape");
+    DevBuf y{&dt->pool};
+    y.reserve(sizeof(double) * (size_t)r.chunk_rows * m.dM);
+    pass.run(log_density, [&](const ConditionChunk& chunk, uint32_t row) {
         ConditionArgs c{};
-        c.xt = a.xt; c.ldx = a.ldx; c.n = rows; c.dO = dO; c.dM = dM; c.K = K;
-        c.lw = a.lw; c.ldr = a.ldr; c.lse = a.lse;
-        c.table = table.as<double>(); c.out = y.as<double>();
-        c.skip = r.skip; c.kernel = r.kernel;
+        static_cast<ConditionChunk&>(c) = chunk;
+        c.out = y.as<double>(); c.skip = r.skip;
+        int grid = 0;
         ctx->timed("em_condition", [&] { grid = launch_em_condition(c, ctx->num_cus, ctx->stream); });
         if (grid < 0) throw Unsupported("conditioning kernel not instantiated for this shape");
         HIP_CHECK(hipGetLastError());
-        // (the copies wait for the stream: the scratch is free for the next chunk, and host_table for the end of the call)
-        double* dst = out + (int64_t)row * ld_out;
-        download_columns(ctx, reinterpret_cast<char*>(packed.empty() ? dst : packed.data()), 0, y.as<char>(), 0, sizeof(double) * dM * rows, 1);
-        if (!packed.empty())
-            for (uint32_t i = 0; i < rows; ++i) std::memcpy(dst + (int64_t)i * ld_out, packed.data() + (size_t)i * dM, sizeof(double) * dM);
-        if (log_density) {
-            download_columns(ctx, reinterpret_cast<char*>(log_density + row), 0, lse.as<char>(), 0, sizeof(double) * rows, 1);
-            for (uint32_t i = 0; i < rows; ++i) log_density[row + i] -= offset;
-        }
-    }
-    ctx->sync();
+        pass.download_rows(out + (int64_t)row * ld_out, ld_out, y.p, chunk.n, (size_t)m.dM);
+    });
 }
 
 }  // namespace
@@ -137,15 +169,8 @@ int mlhip_em_conditional_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uin
         const uint32_t dO = (uint32_t)(data->parts.empty() ? data->d : data->parts[0]->d);
         require(dM >= 1 && dO + dM <= (uint32_t)kGenericMaxDim, "observed and missing coordinates together must be 2 .. 4096");
         require(ld_out >= (int64_t)dM, "ld_out must be >= dM");
-        if (ctx->group) {
-            // (every shard conditions its own rows: no collective, nothing to put together but the rows' places in the caller's arrays)
-            fan_out(ctx, data, [&](Shard& sh) {
-                return mlhip_em_conditional_means(sh.ctx, sh.part, K, dM, mixing, means_observed, covariances_observed, maps, means_missing,
-                                                  sh.rows(out, ld_out), ld_out, sh.rows(log_density));
-            });
-            return;
-        }
-        em_conditional_means(data, (int)K, (int)dM, mixing, means_observed, covariances_observed, maps, means_missing, out, ld_out, log_density);
+        const ConditionedModel m{(int)K, (int)dM, mixing, means_observed, covariances_observed, maps, means_missing};
+        on_block_or_shards(ctx, data, [&](Shard& sh) { em_conditional_means(sh.part, m, sh.rows(out, ld_out), ld_out, sh.rows(log_density)); });
     });
 }
 

@@ -1,22 +1,17 @@
 // mlhip_em_conditional_cdfs / mlhip_em_conditional_quantiles: the per-coordinate predictive CDF P(x_j <= v | x_O) and its inverse for
 // every row of a resident block of OBSERVED coordinates under a mixture conditioned on them (the definitions: mlhip.h; the kernels:
 // device/em_condition_quantile.hip; Phi: device/normal_cdf.hpp). The host conditions the model (host::condition,
-// host::condition_covariances, mlhip_em_condition_scales); the device runs the marginal mixture's E-step in its exact form on chunks of
-// whole tiles, exactly as mlhip_em_conditional_means does (runtime/em_condition.cpp), and behind every chunk ONE launch of the CDF
-// kernel, or one launch of the quantile kernel per group of probabilities. Every buffer is the call's own, taken from the context's
-// pool: the handle's E-step state, weights, ridge and label history stay as they were.
+// host::condition_covariances, mlhip_em_condition_scales); the device runs the conditioning pass (ConditionPass,
+// runtime/em_condition.cpp) and behind every chunk ONE launch of the CDF kernel, or one launch of the quantile kernel per group of
+// probabilities.
 #include "internal.hpp"
 #include "../device/normal_cdf.hpp"
 
 namespace mlhip_rt {
 namespace {
 
-struct ConditionedModel {
-    int K, dM;
-    const double *mixing, *means_observed, *covs_observed, *maps, *means_missing, *scales, *inverse_scales;
-};
-
 struct QuantileCall {
+    const double *scales, *inverse_scales;                      // K x dM: s_kj = sqrt(C_k[j][j]) and 1 / s_kj
     bool quantile;
     const double* values; int64_t ld_values;                    // CDF
     const double *probabilities, *z; uint32_t n_prob;           // quantile: the probabilities and their normal quantiles
@@ -27,101 +22,52 @@ struct QuantileCall {
     uint32_t* iterations;
 };
 
-/// The conditioning kernels' records (condition_table) with [s | w] behind each, in the padded dM (+0.0 beyond dM).
-std::vector<double> quantile_table(int kernel, const ConditionedModel& m, int dO)
-{
-    const int K = m.K, dM = m.dM;
-    const std::vector<double> base = condition_table(kernel, K, dO, dM, m.means_observed, m.maps, m.means_missing, nullptr);
-    const size_t ps = condition_record_doubles(kernel, dO, dM), stride = condition_quantile_record_doubles(kernel, dO, dM);
-    const size_t pm = (size_t)condition_pad(kernel, dM);
-    std::vector<double> table(stride * K, 0.0);
-    for (int k = 0; k < K; ++k) {
-        double* rec = table.data() + stride * k;
-        std::copy_n(base.data() + ps * k, ps, rec);
-        std::copy_n(m.scales + (size_t)k * dM, dM, rec + ps);
-        std::copy_n(m.inverse_scales + (size_t)k * dM, dM, rec + ps + pm);
-    }
-    return table;
-}
-
-/// A chunk's rows x width elements from the device to rows `ld` elements apart on the host.
-template <class T>
-void download_rows(mlhip_ctx* ctx, std::vector<T>& packed, T* dst, int64_t ld, const char* src, uint32_t rows, size_t width)
-{
-    const bool spread = ld != (int64_t)width;
-    if (spread) packed.resize((size_t)rows * width);
-    download_columns(ctx, reinterpret_cast<char*>(spread ? packed.data() : dst), 0, src, 0, sizeof(T) * width * rows, 1);
-    if (spread)
-        for (uint32_t i = 0; i < rows; ++i) std::memcpy(dst + (int64_t)i * ld, packed.data() + (size_t)i * width, sizeof(T) * width);
-}
-
 void em_conditional_quantiles(mlhip_data* dt, const ConditionedModel& m, const QuantileCall& q)
 {
     mlhip_ctx* ctx = dt->ctx;
     if (!dt->n || (q.quantile && !q.n_prob)) return;
-    const int dO = dt->d, K = m.K, dM = m.dM;
-    const ConditionQuantileRoute r = condition_quantile_route(dt, K, dM, q.quantile, q.n_prob, q.means_out != nullptr, q.iterations != nullptr);
-    if (condition_pad(r.kernel, dO) < 0 || condition_pad(r.kernel, dM) < 0) throw Unsupported("conditional quantile kernel not instantiated for this shape");
+    const int dO = dt->d, dM = m.dM;
+    const ConditionQuantileRoute r = condition_quantile_route(dt, m.K, dM, q.quantile, q.n_prob, q.means_out != nullptr, q.iterations != nullptr);
     const uint32_t chunk = r.chunk_rows, group = q.quantile ? r.group : 1;
     const size_t ldq = ((size_t)chunk * dM + 1) & ~(size_t)1;   // (even: every probability's block starts 16-byte aligned)
-    DevBuf records{&dt->pool}, work{&dt->pool}, table{&dt->pool}, lw{&dt->pool}, lse{&dt->pool}, ll{&dt->pool}, out{&dt->pool}, y{&dt->pool},
-        vals{&dt->pool}, its{&dt->pool}, pz{&dt->pool};
-    PinnedBuf staging{&dt->pool};
-    build_records(dt, r.em, K, m.mixing, m.means_observed, m.covs_observed, false, records, staging, work);   // (always the exact form: no FOLD)
-    const std::vector<double> host_table = quantile_table(r.kernel, m, dO);
-    table.reserve(sizeof(double) * host_table.size());
-    HIP_CHECK(hipMemcpyAsync(table.p, host_table.data(), sizeof(double) * host_table.size(), hipMemcpyHostToDevice, ctx->stream));
+    // the record's tail: [s | w], each in the padded dM (+0.0 beyond dM)
+    const size_t tail = condition_quantile_record_doubles(r.kernel, dO, dM) - condition_record_doubles(r.kernel, dO, dM);
+    ConditionPass pass(dt, m, r.em, r.kernel, chunk, tail, [&](int k, double* sw) {
+        std::copy_n(q.scales + (size_t)k * dM, dM, sw);
+        std::copy_n(q.inverse_scales + (size_t)k * dM, dM, sw + tail / 2);
+    }, "conditional quantile kernel not instantiated for this shape");
+    DevBuf out{&dt->pool}, y{&dt->pool}, vals{&dt->pool}, its{&dt->pool}, pz{&dt->pool};
     if (q.quantile) {                                            // [probabilities | their normal quantiles]
         pz.reserve(sizeof(double) * 2 * q.n_prob);
         HIP_CHECK(hipMemcpyAsync(pz.p, q.probabilities, sizeof(double) * q.n_prob, hipMemcpyHostToDevice, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(pz.as<double>() + q.n_prob, q.z, sizeof(double) * q.n_prob, hipMemcpyHostToDevice, ctx->stream));
     }
-    lw.reserve(sizeof(double) * (size_t)chunk * K);
-    lse.reserve(sizeof(double) * chunk);
-    ll.reserve(sizeof(double) * kMaxLlPartials);
     out.reserve(sizeof(double) * ldq * group);
     if (q.means_out) y.reserve(sizeof(double) * (size_t)chunk * dM);
     if (!q.quantile) vals.reserve(sizeof(double) * (size_t)chunk * dM);
     if (q.iterations) its.reserve(sizeof(uint32_t) * ldq * group);
-    std::vector<double> packed;                                 // a leading dimension above dM: a chunk goes up / comes down contiguous, the CPU gathers / spreads
-    std::vector<uint32_t> packed_trips;
-    // the kernels' lw leave the density's constant out, like the E-step's (ML/EM.cpp:197-198 applies it to the mean)
-    const double offset = (double)dO * log_two_pi() / 2;
-    for (uint32_t row = 0; row < dt->n; row += chunk) {
-        const uint32_t rows = std::min(chunk, dt->n - row);   // (padded_samples(rows) <= chunk: the chunk is whole tiles)
-        EstepArgs a{};
-        a.xt = dt->xt.as<double>() + row; a.ldx = dt->ldx; a.n = rows; a.D = dt->D;
-        a.params = records.as<double>(); a.K = K;
-        a.lw = lw.as<double>(); a.ldr = chunk; a.lse = lse.as<double>();
-        a.ll_partials = ll.as<double>(); a.n_ll_partials = kMaxLlPartials;
-        a.shift = dt->shift_dev.as<double>(); a.fold = 0; a.with_lse = 1;
-        a.num_cus = ctx->num_cus;
-        a.plain = r.em.estep == Estep::kPlain;
-        int grid = 0;
-        ctx->timed("em_estep", [&] {
-            grid = r.em.estep == Estep::kMatrix4 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
-        });
-        if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
+    std::vector<double> gathered;                               // ld_values > dM: the CPU gathers a chunk's values before they go up
+    pass.run(q.log_density, [&](const ConditionChunk& chunk_args, uint32_t row) {
+        const uint32_t rows = chunk_args.n;
         ConditionQuantileArgs c{};
-        c.xt = a.xt; c.ldx = a.ldx; c.n = rows; c.dO = dO; c.dM = dM; c.K = K;
-        c.lw = a.lw; c.ldr = a.ldr; c.lse = a.lse;
-        c.table = table.as<double>(); c.out = out.as<double>(); c.ldq = ldq;
-        c.skip = r.skip; c.kernel = r.kernel;
+        static_cast<ConditionChunk&>(c) = chunk_args;
+        c.out = out.as<double>(); c.ldq = ldq; c.skip = r.skip;
+        int grid = 0;
         if (!q.quantile) {
             const double* src = q.values + (int64_t)row * q.ld_values;
             if (q.ld_values != (int64_t)dM) {
-                packed.resize((size_t)rows * dM);
-                for (uint32_t i = 0; i < rows; ++i) std::memcpy(packed.data() + (size_t)i * dM, src + (int64_t)i * q.ld_values, sizeof(double) * dM);
-                src = packed.data();
+                gathered.resize((size_t)rows * dM);
+                for (uint32_t i = 0; i < rows; ++i) std::memcpy(gathered.data() + (size_t)i * dM, src + (int64_t)i * q.ld_values, sizeof(double) * dM);
+                src = gathered.data();
             }
-            // (`packed` is not touched again before the download below has waited for the stream, this copy included)
+            // (`gathered` is not touched again before the download below has waited for the stream, this copy included)
             HIP_CHECK(hipMemcpyAsync(vals.p, src, sizeof(double) * (size_t)rows * dM, hipMemcpyHostToDevice, ctx->stream));
             c.values = vals.as<double>();
             c.means = q.means_out ? y.as<double>() : nullptr;
             ctx->timed("em_condition_cdf", [&] { grid = launch_em_condition_cdf(c, ctx->num_cus, ctx->stream); });
             if (grid < 0) throw Unsupported("conditional CDF kernel not instantiated for this shape");
             HIP_CHECK(hipGetLastError());
-            download_rows(ctx, packed, q.out + (int64_t)row * q.ld_out, q.ld_out, out.as<char>(), rows, (size_t)dM);
+            pass.download_rows(q.out + (int64_t)row * q.ld_out, q.ld_out, out.p, rows, (size_t)dM);
         }
         for (uint32_t q0 = 0; q.quantile && q0 < q.n_prob; q0 += group) {
             const uint32_t nq = std::min(group, q.n_prob - q0);
@@ -131,30 +77,22 @@ void em_conditional_quantiles(mlhip_data* dt, const ConditionedModel& m, const Q
             ctx->timed("em_condition_quantile", [&] { grid = launch_em_condition_quantile(c, ctx->num_cus, ctx->stream); });
             if (grid < 0) throw Unsupported("conditional quantile kernel not instantiated for this shape");
             HIP_CHECK(hipGetLastError());
-            // (the copies wait for the stream: the scratch is free for the next launch, and host_table for the end of the call)
             for (uint32_t g = 0; g < nq; ++g) {
                 const int64_t at = (int64_t)((uint64_t)(q0 + g) * q.block_rows + row);
-                download_rows(ctx, packed, q.out + at * q.ld_out, q.ld_out, out.as<char>() + sizeof(double) * ldq * g, rows, (size_t)dM);
-                if (q.iterations)
-                    download_rows(ctx, packed_trips, q.iterations + at * (int64_t)dM, (int64_t)dM, its.as<char>() + sizeof(uint32_t) * ldq * g, rows,
-                                  (size_t)dM);
+                pass.download_rows(q.out + at * q.ld_out, q.ld_out, out.as<double>() + ldq * g, rows, (size_t)dM);
+                if (q.iterations) pass.download_rows(q.iterations + at * (int64_t)dM, (int64_t)dM, its.as<uint32_t>() + ldq * g, rows, (size_t)dM);
             }
         }
-        if (q.means_out) download_rows(ctx, packed, q.means_out + (int64_t)row * q.ld_means, q.ld_means, y.as<char>(), rows, (size_t)dM);
-        if (q.log_density) {
-            download_columns(ctx, reinterpret_cast<char*>(q.log_density + row), 0, lse.as<char>(), 0, sizeof(double) * rows, 1);
-            for (uint32_t i = 0; i < rows; ++i) q.log_density[row + i] -= offset;
-        }
-    }
-    ctx->sync();
+        if (q.means_out) pass.download_rows(q.means_out + (int64_t)row * q.ld_means, q.ld_means, y.p, rows, (size_t)dM);
+    });
 }
 
 /// The checks both calls share, before any device work; returns dO.
-uint32_t check_quantile_call(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t dM, const ConditionedModel& m, int64_t ld_out, bool with_means,
-                             int64_t ld_means)
+uint32_t check_quantile_call(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint32_t dM, const ConditionedModel& m, const double* scales,
+                             const double* inverse_scales, int64_t ld_out, bool with_means, int64_t ld_means)
 {
     check_call(ctx, data, K);
-    require(m.mixing && m.means_observed && m.covs_observed && m.maps && m.means_missing && m.scales && m.inverse_scales, "null argument");
+    require(m.mixing && m.means_observed && m.covs_observed && m.maps && m.means_missing && scales && inverse_scales, "null argument");
     const uint32_t dO = (uint32_t)(data->parts.empty() ? data->d : data->parts[0]->d);
     require(dM >= 1 && dO + dM <= (uint32_t)kGenericMaxDim, "observed and missing coordinates together must be 2 .. 4096");
     require(ld_out >= (int64_t)dM, "ld_out must be >= dM");
@@ -162,25 +100,17 @@ uint32_t check_quantile_call(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint3
     return dO;
 }
 
-/// One call on a single context's block, or on every shard of a group's: each shard handles its own rows, no collective, nothing to
-/// put together but the rows' places in the caller's arrays.
+/// The call on the block, or on every shard's rows of it.
 void run(mlhip_ctx* ctx, mlhip_data* data, const ConditionedModel& m, const QuantileCall& q)
 {
-    if (!ctx->group) {
-        em_conditional_quantiles(data, m, q);
-        return;
-    }
-    fan_out(ctx, data, [&](Shard& sh) {
-        return guarded([&] {
-            sh.ctx->use();
-            QuantileCall part = q;
-            part.values = q.values ? sh.rows(q.values, q.ld_values) : nullptr;
-            part.out = sh.rows(q.out, q.ld_out);
-            part.means_out = sh.rows(q.means_out, q.ld_means);
-            part.log_density = sh.rows(q.log_density);
-            part.iterations = sh.rows(q.iterations, (int64_t)m.dM);
-            em_conditional_quantiles(sh.part, m, part);
-        });
+    on_block_or_shards(ctx, data, [&](Shard& sh) {
+        QuantileCall part = q;
+        part.values = sh.rows(q.values, q.ld_values);
+        part.out = sh.rows(q.out, q.ld_out);
+        part.means_out = sh.rows(q.means_out, q.ld_means);
+        part.log_density = sh.rows(q.log_density);
+        part.iterations = sh.rows(q.iterations, (int64_t)m.dM);
+        em_conditional_quantiles(sh.part, m, part);
     });
 }
 
@@ -228,12 +158,13 @@ int mlhip_em_conditional_cdfs(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uint
                               double* means_out, int64_t ld_means, double* log_density)
 {
     return guarded([&] {
-        const ConditionedModel m{(int)K, (int)dM, mixing, means_observed, covariances_observed, maps, means_missing, scales, inverse_scales};
-        check_quantile_call(ctx, data, K, dM, m, ld_out, means_out != nullptr, ld_means);
+        const ConditionedModel m{(int)K, (int)dM, mixing, means_observed, covariances_observed, maps, means_missing};
+        check_quantile_call(ctx, data, K, dM, m, scales, inverse_scales, ld_out, means_out != nullptr, ld_means);
         require(ld_values >= (int64_t)dM, "ld_values must be >= dM");
         if (!data->rows()) return;
         require(values && out, "null argument");
         QuantileCall q{};
+        q.scales = scales; q.inverse_scales = inverse_scales;
         q.quantile = false; q.values = values; q.ld_values = ld_values; q.out = out; q.ld_out = ld_out;
         q.means_out = means_out; q.ld_means = ld_means; q.log_density = log_density;
         run(ctx, data, m, q);
@@ -246,8 +177,8 @@ int mlhip_em_conditional_quantiles(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
                                    int64_t ld_out, double* means_out, int64_t ld_means, double* log_density, uint32_t* iterations)
 {
     return guarded([&] {
-        const ConditionedModel m{(int)K, (int)dM, mixing, means_observed, covariances_observed, maps, means_missing, scales, inverse_scales};
-        check_quantile_call(ctx, data, K, dM, m, ld_out, means_out != nullptr, ld_means);
+        const ConditionedModel m{(int)K, (int)dM, mixing, means_observed, covariances_observed, maps, means_missing};
+        check_quantile_call(ctx, data, K, dM, m, scales, inverse_scales, ld_out, means_out != nullptr, ld_means);
         require(n_probabilities == 0 || probabilities, "null argument");
         for (uint32_t i = 0; i < n_probabilities; ++i)
             require(probabilities[i] > 0.0 && probabilities[i] < 1.0, "a probability must lie strictly inside (0, 1)");   // (a NaN fails both)
@@ -256,6 +187,7 @@ int mlhip_em_conditional_quantiles(mlhip_ctx* ctx, mlhip_data* data, uint32_t K,
         std::vector<double> z(n_probabilities);
         for (uint32_t i = 0; i < n_probabilities; ++i) z[i] = mlhip::normal_quantile(probabilities[i]);
         QuantileCall q{};
+        q.scales = scales; q.inverse_scales = inverse_scales;
         q.quantile = true; q.probabilities = probabilities; q.z = z.data(); q.n_prob = n_probabilities; q.out = out; q.ld_out = ld_out;
         q.block_rows = data->rows(); q.means_out = means_out; q.ld_means = ld_means; q.log_density = log_density; q.iterations = iterations;
         run(ctx, data, m, q);

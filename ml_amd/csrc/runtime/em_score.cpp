@@ -12,29 +12,14 @@ namespace {
 void score_composed(mlhip_data* dt, const ScoreRoute& r, int K, const DevBuf& records, double* lse_out, uint32_t* labels_out)
 {
     mlhip_ctx* ctx = dt->ctx;
-    const uint32_t chunk = r.chunk_rows;
-    DevBuf lw{&dt->pool}, lse{&dt->pool}, ll{&dt->pool};
-    lw.reserve(sizeof(double) * (size_t)chunk * K);
-    lse.reserve(sizeof(double) * chunk);
-    ll.reserve(sizeof(double) * kMaxLlPartials);
-    for (uint32_t row = 0; row < dt->n; row += chunk) {
-        const uint32_t rows = std::min(chunk, dt->n - row);   // (padded_samples(rows) <= chunk: the chunk is whole tiles)
-        EstepArgs a{};
-        a.xt = dt->xt.as<double>() + row; a.ldx = dt->ldx; a.n = rows; a.D = dt->D;
-        a.params = records.as<double>(); a.K = K;
-        a.lw = lw.as<double>(); a.ldr = chunk; a.lse = lse.as<double>();
-        a.ll_partials = ll.as<double>(); a.n_ll_partials = kMaxLlPartials;
-        a.shift = dt->shift_dev.as<double>(); a.fold = 0; a.with_lse = 1;
-        a.num_cus = ctx->num_cus;
-        a.plain = r.em.estep == Estep::kPlain;
-        int grid = 0;
-        ctx->timed("em_estep", [&] {
-            grid = r.em.estep == Estep::kMatrix4 ? launch_em_estep_mfma4(a, ctx->num_cus, ctx->stream) : launch_em_estep(a, ctx->stream);
-        });
-        if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
+    ChunkEstep estep(dt);
+    estep.reserve(K, r.chunk_rows);
+    for (uint32_t row = 0; row < dt->n; row += estep.chunk) {
+        const uint32_t rows = std::min(estep.chunk, dt->n - row);   // (padded_samples(rows) <= chunk: the chunk is whole tiles)
+        estep.launch(dt, r.em, K, records, row, rows);
         ctx->timed("em_score", [&] {
-            launch_em_score_finish(a.lw, a.ldr, a.lse, rows, K, lse_out ? lse_out + row : nullptr, labels_out ? labels_out + row : nullptr,
-                                   ctx->stream);
+            launch_em_score_finish(estep.lw.as<double>(), estep.chunk, estep.lse.as<double>(), rows, K, lse_out ? lse_out + row : nullptr,
+                                   labels_out ? labels_out + row : nullptr, ctx->stream);
         });
         HIP_CHECK(hipGetLastError());
     }

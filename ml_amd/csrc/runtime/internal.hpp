@@ -742,11 +742,6 @@ struct SilhouetteRoute {
     uint32_t block_rows(uint64_t n_chunks, uint64_t m) const;
 };
 SilhouetteRoute silhouette_route(const mlhip_data* data);
-/// The conditioning kernels' table on the host: K records [mu_O | mu_M | A^T] in the paddings of `kernel` (device.hpp condition_pad):
-/// +0.0, and -0.0 in the rows of A^T beyond dO. With `factors` (K x dM x dM row-major lower factors; mlhip_em_conditional_samples) every
-/// record carries its factor behind it, the lower triangle packed row by row in the padded dM (condition_sample_record_doubles).
-std::vector<double> condition_table(int kernel, int K, int dO, int dM, const double* means_observed, const double* maps,
-                                    const double* means_missing, const double* factors);
 /// The argument checks of mlhip_em_condition and mlhip_em_condition_covariances behind their null checks; returns the covariance mode.
 Covariance check_condition_arguments(uint32_t d, uint32_t K, int covariance_type, const uint32_t* observed, uint32_t n_observed);
 
@@ -1063,6 +1058,72 @@ void fan_out_rows(mlhip_ctx* ctx, const std::vector<uint64_t>& first_row, mlhip_
 /// The contiguous, balanced row shards that tile [0, n): shard s holds rows [first[s], first[s + 1]) (the split of
 /// ml_amd.dist.shard_bounds, so that a group reproduces the multi-process job of the same size).
 std::vector<uint64_t> balanced_rows(uint64_t n, int shards);
+/// f on the block itself -- a "shard" that is the whole of it: the caller's context, its block, first row 0 --, or, with a group's
+/// context, on every shard's part on that shard's thread with its device made current. f throws as an entry point's body does.
+/// (A shard's checks are the outer call's: check_call and the argument checks that passed for the group hold for each of its parts.)
+void on_block_or_shards(mlhip_ctx* ctx, mlhip_data* data, const std::function<void(Shard&)>& f);
+
+// ---- the chunked pass of the conditioning calls (em_condition.cpp): mlhip_em_conditional_means / _samples / _variances / _cdfs /
+// _quantiles all run the marginal mixture's E-step in its exact form on chunks of whole tiles and their own kernel behind every chunk.
+
+/// The scratch of an exact-form, LSE-writing E-step on chunks of at most `chunk` rows (whole tiles) of a block, and its launch: what
+/// the conditioning pass and the composed route of mlhip_em_score run. The buffers are the call's own, from the handle's pool.
+struct ChunkEstep {
+    DevBuf lw, lse, ll;                                          // K x chunk log-responsibilities, their log-sum-exp, the partials
+    uint32_t chunk = 0;
+    explicit ChunkEstep(mlhip_data* dt) : lw(&dt->pool), lse(&dt->pool), ll(&dt->pool) {}
+    void reserve(int K, uint32_t chunk_rows);
+    /// The E-step kernel of `em` (fold = 0, with_lse = 1) for rows [row, row + rows) of the block on `records`; rows <= chunk.
+    void launch(mlhip_data* dt, const EmRoute& em, int K, const DevBuf& records, uint32_t row, uint32_t rows);
+};
+
+/// A mixture conditioned on observed coordinates as every conditioning call takes it (mlhip_em_condition's outputs): the marginal
+/// mixture over x_O and, per component, the regression of x_M on x_O.
+struct ConditionedModel {
+    int K, dM;
+    const double *mixing, *means_observed, *covs_observed, *maps, *means_missing;
+};
+/// Writes the `tail` doubles (+0.0 as given) behind record k's [mu_O | mu_M | A^T].
+using ConditionTail = std::function<void(int k, double* tail)>;
+/// The conditioning kernels' table on the host: K records [mu_O | mu_M | A^T | tail] in the paddings of `kernel` (device.hpp
+/// condition_pad): +0.0, and -0.0 in the rows of A^T beyond dO (a padded coordinate's term is fma(-0.0, +0.0, t) = t for every t, a t
+/// of -0.0 included: device/em_condition_common.hpp). `fill` may be empty where `tail` is 0.
+std::vector<double> condition_table(int kernel, const ConditionedModel& m, int dO, size_t tail, const ConditionTail& fill);
+
+/// One conditioning call on one block. The constructor builds the marginal mixture's E-step records (always the exact form: no FOLD),
+/// uploads the table and reserves the E-step's scratch; run() walks the chunks. Every buffer is the call's own, taken from the
+/// handle's pool: the handle's E-step state, weights, ridge and label history stay as they were.
+class ConditionPass {
+public:
+    /// `unsupported`: what to say where `kernel` has no padding for (dO, dM).
+    ConditionPass(mlhip_data* dt, const ConditionedModel& m, const EmRoute& em, int kernel, uint32_t chunk_rows, size_t tail,
+                  const ConditionTail& fill, const char* unsupported);
+    /// Per chunk of rows: the E-step, then behind(c, row) with c the chunk that starts at `row` (c.n rows; padded_samples(c.n) <=
+    /// chunk: the chunk is whole tiles) -- the caller launches its kernel and downloads what it wrote --, then log_density's rows where
+    /// that is not null: lse less dO log(2 pi) / 2, the constant the kernels' lw leave out. Ends with the call's one ctx->sync().
+    void run(double* log_density, const std::function<void(const ConditionChunk& c, uint32_t row)>& behind);
+    /// rows x width elements at `src` on the device to rows `ld` elements apart on the host (a leading dimension above the width: the
+    /// rows come down contiguous and are spread by the CPU). The copy waits for the stream: the source is free for the next launch.
+    template <class T> void download_rows(T* dst, int64_t ld, const void* src, uint32_t rows, size_t width)
+    {
+        const bool spread = ld != (int64_t)width;
+        if (spread) packed_.resize(sizeof(T) * rows * width);
+        char* to = spread ? packed_.data() : reinterpret_cast<char*>(dst);
+        download_columns(dt_->ctx, to, 0, static_cast<const char*>(src), 0, sizeof(T) * width * rows, 1);
+        if (spread)
+            for (uint32_t i = 0; i < rows; ++i) std::memcpy(dst + (int64_t)i * ld, to + sizeof(T) * width * i, sizeof(T) * width);
+    }
+
+private:
+    mlhip_data* dt_;
+    EmRoute em_;
+    ConditionChunk c_{};
+    DevBuf records_, work_, table_;
+    PinnedBuf staging_;
+    std::vector<double> host_table_;                             // (the upload reads it until the stream has been waited for)
+    ChunkEstep estep_;
+    std::vector<char> packed_;
+};
 
 // What is not a plain fan-out:
 namespace grp {

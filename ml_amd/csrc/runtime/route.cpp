@@ -173,6 +173,22 @@ ScoreRoute score_route(const mlhip_data* data, int K)
     return r;
 }
 
+namespace {
+
+/// Rows per chunk of a conditioning call whose scratch takes `per_row` doubles a row: the largest whole number of sample tiles within
+/// kScoreScratchBytes -- MLHIP_CONDITION_ROWS=n overrides, rounded UP to whole tiles --, at least one tile and at most the block.
+uint32_t condition_chunk_rows(const Switches& sw, const mlhip_data* data, uint64_t per_row)
+{
+    const uint64_t tile = kSampleTile;
+    uint64_t rows = sw.condition_rows > 0 ? (uint64_t)sw.condition_rows : kScoreScratchBytes / sizeof(double) / per_row;
+    rows = sw.condition_rows > 0 ? (rows + tile - 1) / tile * tile : rows / tile * tile;
+    if (rows < tile) rows = tile;
+    if (rows > data->n_pad) rows = data->n_pad;
+    return (uint32_t)rows;
+}
+
+}  // namespace
+
 ConditionRoute condition_route(const mlhip_data* data, int K, int dM)
 {
     const Switches sw = read_switches();
@@ -180,12 +196,7 @@ ConditionRoute condition_route(const mlhip_data* data, int K, int dM)
     r.em = em_route(data, K, Covariance::Full);
     r.kernel = sw.condition_plain ? kConditionPlain : em_condition_route(data->d, dM);
     r.skip = sw.condition_skip;
-    const uint64_t tile = kSampleTile;
-    uint64_t rows = sw.condition_rows > 0 ? (uint64_t)sw.condition_rows : kScoreScratchBytes / (sizeof(double) * ((uint64_t)K + (uint64_t)dM));
-    rows = sw.condition_rows > 0 ? (rows + tile - 1) / tile * tile : rows / tile * tile;
-    if (rows < tile) rows = tile;
-    if (rows > data->n_pad) rows = data->n_pad;
-    r.chunk_rows = (uint32_t)rows;
+    r.chunk_rows = condition_chunk_rows(sw, data, (uint64_t)K + (uint64_t)dM);
     return r;
 }
 
@@ -196,14 +207,9 @@ ConditionRoute condition_variance_route(const mlhip_data* data, int K, int dM, b
     r.em = em_route(data, K, Covariance::Full);
     r.kernel = sw.condition_plain ? kConditionPlain : em_condition_variance_route(data->d, dM, full);
     r.skip = sw.condition_skip;
-    const uint64_t tile = kSampleTile;
     const uint64_t per_row = (uint64_t)K + (full ? (uint64_t)dM * dM : (uint64_t)dM) + (with_means ? (uint64_t)dM : 0) +
                              (r.kernel == kConditionPlain ? 2 * (uint64_t)dM : 0);
-    uint64_t rows = sw.condition_rows > 0 ? (uint64_t)sw.condition_rows : kScoreScratchBytes / (sizeof(double) * per_row);
-    rows = sw.condition_rows > 0 ? (rows + tile - 1) / tile * tile : rows / tile * tile;
-    if (rows < tile) rows = tile;
-    if (rows > data->n_pad) rows = data->n_pad;
-    r.chunk_rows = (uint32_t)rows;
+    r.chunk_rows = condition_chunk_rows(sw, data, per_row);
     return r;
 }
 
@@ -215,18 +221,13 @@ ConditionQuantileRoute condition_quantile_route(const mlhip_data* data, int K, i
     r.em = em_route(data, K, Covariance::Full);
     r.kernel = sw.condition_plain ? kConditionPlain : em_condition_quantile_route(data->d, dM, quantile);
     r.skip = sw.condition_skip;
-    const uint64_t tile = kSampleTile, budget = kScoreScratchBytes / sizeof(double);
     // per row: the K log-responsibilities and the mean; the CDF's values and its output, or the blocks of a group of probabilities
     // (with the trip counts: a uint32 each, counted as a double)
     const uint64_t fixed = (uint64_t)K + (with_means ? (uint64_t)dM : 0) + (quantile ? 0 : (uint64_t)dM);
     const uint64_t block = (uint64_t)dM * (quantile && with_iterations ? 2 : 1);
     const uint64_t sized_for = quantile ? std::max<uint64_t>(1, std::min<uint64_t>(n_prob, kConditionQuantileGroup)) : 1;
-    uint64_t rows = sw.condition_rows > 0 ? (uint64_t)sw.condition_rows : budget / (fixed + sized_for * block);
-    rows = sw.condition_rows > 0 ? (rows + tile - 1) / tile * tile : rows / tile * tile;
-    if (rows < tile) rows = tile;
-    if (rows > data->n_pad) rows = data->n_pad;
-    r.chunk_rows = (uint32_t)rows;
-    const uint64_t per_row = budget / rows;
+    r.chunk_rows = condition_chunk_rows(sw, data, fixed + sized_for * block);
+    const uint64_t per_row = kScoreScratchBytes / sizeof(double) / r.chunk_rows;
     const uint64_t fit = per_row > fixed ? (per_row - fixed) / block : 0;
     r.group = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fit, std::max<uint32_t>(n_prob, 1)));
     if (sw.condition_group > 0 && (uint64_t)sw.condition_group < r.group) r.group = (uint32_t)sw.condition_group;   // (no bit depends on it)
@@ -239,14 +240,9 @@ ConditionSampleRoute condition_sample_route(const mlhip_data* data, int K, int d
     ConditionSampleRoute r;
     r.em = em_route(data, K, Covariance::Full);
     r.kernel = sw.condition_plain ? kConditionPlain : em_condition_route(data->d, dM);
-    const uint64_t tile = kSampleTile, budget = kScoreScratchBytes / sizeof(double);
     const uint64_t sized_for = std::max<uint64_t>(1, std::min<uint64_t>(n_draws, kConditionSampleDraws));
-    uint64_t rows = sw.condition_rows > 0 ? (uint64_t)sw.condition_rows : budget / ((uint64_t)K + sized_for * (uint64_t)dM);
-    rows = sw.condition_rows > 0 ? (rows + tile - 1) / tile * tile : rows / tile * tile;
-    if (rows < tile) rows = tile;
-    if (rows > data->n_pad) rows = data->n_pad;
-    r.chunk_rows = (uint32_t)rows;
-    const uint64_t per_row = budget / rows;
+    r.chunk_rows = condition_chunk_rows(sw, data, (uint64_t)K + sized_for * (uint64_t)dM);
+    const uint64_t per_row = kScoreScratchBytes / sizeof(double) / r.chunk_rows;
     const uint64_t fit = per_row > (uint64_t)K ? (per_row - (uint64_t)K) / (uint64_t)dM : 0;
     r.draws = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fit, n_draws));
     return r;
