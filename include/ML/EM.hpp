@@ -166,6 +166,18 @@ public:
     @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
     DLL_DECLSPEC MatrixXd conditional_means(const std::vector<unsigned int>& observed, ConstMatrixRef data_observed,
                                             double* log_densities = nullptr) const;
+    /** Extension (imputation of a table with gaps): `data` (means().rows() x N, a point in every column) with every NaN replaced by
+    its conditional expectation under the fitted mixture given the coordinates THAT point has -- every point its own pattern of
+    NaNs -- on the device. Observed entries keep their bits; a complete point comes back as it is, a point of all NaN as the
+    mixture's mean. `log_densities`, if given, receives data.cols() values: the log-density of every point's observed coordinates
+    under the marginal mixture (0 for a point of all NaN). `responsibilities`, if given, is resized to number_components() x
+    data.cols(): the posterior membership of every point given what it has. The definition and its fixed evaluation order:
+    mlhip_em_impute. A point's results do not depend on the other points, their order, the row batches (those of log_densities)
+    or the device group it runs on; the model is not changed.
+    @throw std::invalid_argument If the model has not been fitted or `data.rows() != means().rows()`.
+    @throw std::domain_error If the observed block of a covariance is not positive definite for some point's pattern.
+    @throw std::runtime_error On device failures (no GPU: there is no CPU fallback). */
+    DLL_DECLSPEC MatrixXd impute(ConstMatrixRef data, double* log_densities = nullptr, MatrixXd* responsibilities = nullptr) const;
     /** Extension: the covariances Sigma_k,M|O of the conditioned components, K matrices of (number of missing coordinates)^2, the
     missing coordinates in ascending order (mlhip_em_condition_covariances; host only, no device). `observed` as for conditional_means.
     @throw std::invalid_argument If the model has not been fitted or for bad coordinates.

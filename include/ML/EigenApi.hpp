@@ -462,6 +462,22 @@ public:
                                                 block.p, static_cast<uint64_t>(data_observed.cols()), out.data(), log_densities));
         return out;
     }
+    /** Extension (ML/EM.hpp): `data` (a point in every column) with every NaN replaced by its conditional expectation under the fitted
+    mixture given the coordinates that point has. `log_densities`, if given, receives the log-density of every point's observed
+    coordinates under the marginal mixture; `responsibilities`, if given, is resized to number_components() x data.cols().
+    @throw std::invalid_argument If the model has not been fitted or `data.rows() != means().rows()`.
+    @throw std::domain_error If the observed block of a covariance is not positive definite for some point's pattern. */
+    Eigen::MatrixXd impute(Eigen::Ref<const Eigen::MatrixXd> data, double* log_densities = nullptr,
+                           Eigen::MatrixXd* responsibilities = nullptr) const
+    {
+        if (data.rows() != means_.rows()) throw std::invalid_argument("Wrong data size");
+        const detail::Block block(data);
+        Eigen::MatrixXd out(data.rows(), data.cols());
+        if (responsibilities) responsibilities->resize(means_.cols(), data.cols());
+        detail::check(mlpp_em_impute(h_, block.p, static_cast<uint64_t>(data.cols()), static_cast<uint32_t>(data.rows()), out.data(), log_densities,
+                                     responsibilities ? responsibilities->data() : nullptr));
+        return out;
+    }
     /** Extension (ML/EM.hpp): the covariances of the conditioned components, K matrices of (number of missing coordinates)^2. Host only.
     @throw std::invalid_argument If the model has not been fitted or for bad coordinates.
     @throw std::domain_error If a block is not positive definite. */

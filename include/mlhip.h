@@ -384,6 +384,69 @@ int mlhip_em_conditional_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uin
 enum { MLHIP_CONDITION_REGISTERS = 0, MLHIP_CONDITION_PLAIN = 1 };
 int mlhip_em_condition_route(const mlhip_data* data, uint32_t K, uint32_t dM, int* kernel);
 
+/* EXTENSION (imputation of a table with gaps; not in the reference surface): every NaN of x replaced by its conditional expectation
+ * under the mixture, every row conditioned on the coordinates IT has. x: n rows of d doubles, contiguous, HOST memory (a block with
+ * NaNs has no usable shift, so it is no mlhip_data); a NaN of any sign and payload marks a missing coordinate. mixing, means,
+ * covariances, covariance_type as in mlhip_em_score (diagonal and tied input count as the full matrices they stand for). out: n x d,
+ * contiguous, host memory; log_density (n) and responsibilities (n x K, row-major) may be NULL.
+ * Row i has the observed coordinates O ascending (c = 0 .. dO - 1) and the missing ones M ascending. For component k, L L^T = Sigma_k,OO,
+ * W = L^-1 and A_k = Sigma_k,MO Sigma_k,OO^-1 (mlhip_em_condition's). Then
+ *   1. z_c = x_c - mu_k,O[c];
+ *   2. y_j = W[j][0] z_0, then fma over l = 1 .. j ascending; q = +0.0, then fma(y_j, y_j, q) for ascending j;
+ *   3. lw_k = fma(-0.5, q, coef_k), coef_k = log pi_k - sum_j log L_jj;
+ *   4. lse = the online log-sum-exp over ascending k of the E-step kernel; log_density = lse - dO log(2 pi) / 2;
+ *   5. r_k = exp(lw_k - lse) (the E-step's exp of a non-positive argument): the responsibilities;
+ *   6. t_j = mu_k,M[j], then fma(A_k[j][c], z_c, t_j) for ascending c; out_j = +0.0, then fma(r_k, t_j, out_j) for ascending k, ONLY
+ *      where r_k != 0.
+ * -- the exact E-step of the marginal mixture over x_O and the conditioning chain of mlhip_em_conditional_means, with the parameters
+ * of the row's own pattern. An observed entry keeps its bits. A complete row: out is the input, log_density has the bits of
+ * mlhip_em_score, the responsibilities are those of the exact E-step. A row of all NaN: out_j = +0.0, then fma(pi_k, mu_k[j], out_j) for
+ * ascending k where pi_k != 0; log_density = 0; responsibilities = pi.
+ * Row i's results are a pure function of row i and the parameters: the other rows, their order, how a table is cut into calls, the
+ * row chunk (MLHIP_IMPUTE_ROWS=n), the pattern chunk (MLHIP_IMPUTE_PATTERNS=n), the shards of a device group (each imputes its own
+ * rows, no collective; with an all-reduce hook installed every rank imputes its own rows, and no collective is made either) and
+ * MLHIP_CONDITION_SKIP change no bit on a route. The rows are grouped by pattern on the host (mlhip_em_impute_plan); the complete rows
+ * go through mlhip_em_score, the rows of all NaN are formed on the host. The others:
+ *   COMPOSED (MLHIP_IMPUTE_COMPOSED), every d up to 4096: every group goes through the pass of mlhip_em_conditional_means with
+ *            `observed` ascending and the model conditioned on the host -- bit for bit what that call gives for the group's rows, output
+ *            and log-density. Its cost grows with the number of patterns: one upload, one host conditioning and two launches each.
+ *   KERNEL   (MLHIP_IMPUTE_KERNEL), 2 <= d <= 32 and any K, the default there (MLHIP_IMPUTE=composed: COMPOSED): the records
+ *            [mu_O | mu_M | A^T | W | coef] of the patterns are built on the device, one wave per (pattern, component)
+ *            (device/em_impute_records.hip), for as many patterns at a time as 256 MiB hold; the evaluation kernel
+ *            (device/em_impute.hip) then runs steps 1 - 6 with lane = row on 64-row tiles of ONE pattern each, one launch per pair
+ *            of register paddings (4 / 8 / 16 / 32 for dO and dM) present in a chunk of rows: the launches do not grow with the
+ *            patterns. The device's factorization is not the host's: the two routes agree within the sum of their error limits
+ *            (DESIGN.md), not bit for bit.
+ * MLHIP_E_DOMAIN where the Sigma_k,OO of some pattern of the block is not positive definite (mlhip_em_condition's error): NO output
+ * is written, and the context stays usable. MLHIP_E_INVALID_ARGUMENT, before any device work: null pointers, K = 0, d = 0 or
+ * d > 4096, a bad covariance_type, n >= 2^32 - 256. n = 0 succeeds and writes nothing. */
+enum { MLHIP_IMPUTE_COMPOSED = 0, MLHIP_IMPUTE_KERNEL = 1 };
+int mlhip_em_impute(mlhip_ctx* ctx, uint32_t d, uint32_t K, int covariance_type, const double* mixing, const double* means,
+                    const double* covariances, const double* x, uint64_t n, double* out, double* log_density,
+                    double* responsibilities);
+/* The pattern grouping of a block, as mlhip_em_impute makes it (host only, no GPU): *n_patterns distinct patterns of observed
+ * coordinates; order (n; may be NULL): the rows in a stable order in which the rows of one pattern are contiguous and ascending;
+ * bounds (room for n + 1, *n_patterns + 1 written; may be NULL): pattern p holds order[bounds[p] .. bounds[p + 1]); n_observed (room
+ * for n, *n_patterns written; may be NULL): the observed coordinates of pattern p. The patterns stand in ascending order of their masks
+ * (bit c set: coordinate c observed; 64-bit words compared from coordinates 0 .. 63 on). */
+int mlhip_em_impute_plan(const double* x, uint64_t n, uint32_t d, uint32_t* n_patterns, uint32_t* order, uint32_t* bounds,
+                         uint32_t* n_observed);
+/* The route mlhip_em_impute takes for a d-dimensional model of K components under the switches as they are set now, and -- launches
+ * not NULL -- the kernel launches it makes behind the uploads for the block x (diagnostic, host only, nothing is launched). COMPOSED:
+ * per group of at most MLHIP_IMPUTE_ROWS rows of one pattern one E-step and one conditioning kernel (a group larger than the
+ * conditioning pass's scratch bound takes more). KERNEL: one records launch per pattern chunk and, per chunk of rows, one evaluation
+ * launch per pair of paddings present -- the same count for 3 and for 300 patterns of the same paddings. Both: one scoring kernel per
+ * group of complete rows. x may be NULL where launches is. */
+int mlhip_em_impute_route(uint32_t d, uint32_t K, const double* x, uint64_t n, int* route, uint64_t* launches);
+/* The records the KERNEL route builds on the device for ONE pattern, downloaded in mlhip_em_condition's layout (diagnostic; d <= 32,
+ * a single context): observed: n_observed ASCENDING coordinates, 1 <= n_observed <= d - 1. means_observed K x dO; whitening K x dO x dO
+ * row-major, W_k = L^-1 with L L^T = Sigma_k,OO, zero above the diagonal; coefficients K, log pi_k - sum_j log L_jj; maps K x dM x dO
+ * row-major, A_k; means_missing K x dM. MLHIP_E_DOMAIN where a Sigma_k,OO is not positive definite (the kernel's flag word);
+ * mlhip_em_condition's argument errors. */
+int mlhip_em_impute_condition(mlhip_ctx* ctx, uint32_t d, uint32_t K, int covariance_type, const double* mixing, const double* means,
+                              const double* covariances, const uint32_t* observed, uint32_t n_observed, double* means_observed,
+                              double* whitening, double* coefficients, double* maps, double* means_missing);
+
 /* EXTENSION (multiple imputation, predictive intervals; not in the reference surface): the covariances of the conditioned
  * components. Host helper, no GPU needed; d, K, covariance_type, covariances, observed, n_observed as in mlhip_em_condition, whose
  * argument checks are made here too, before any work. Per component k, with L L^T = Sigma_k,OO (the factor mlhip_em_condition uses)

@@ -112,6 +112,11 @@ int mlpp_em_sample(const mlpp_em* h, uint64_t n, uint64_t seed, double* x_out, u
  * n = 0 writes nothing. */
 int mlpp_em_conditional_means(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, const double* data_observed, uint64_t n,
                               double* out, double* log_density_out);
+/* Extension: EM::impute -- every NaN of n points replaced by its conditional expectation under the fitted mixture given the
+ * coordinates that point has (mlhip_em_impute). data and out: n x d row-major; log_density_out (n) and responsibilities_out (n x K
+ * row-major) may be NULL. n = 0 writes nothing. */
+int mlpp_em_impute(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out, double* log_density_out,
+                   double* responsibilities_out);
 /* Extension: EM::conditional_covariances -- the covariances of the conditioned components (mlhip_em_condition_covariances; host
  * only). out: K x dM x dM, dM = d - n_observed. */
 int mlpp_em_conditional_covariances(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, double* out);

@@ -877,6 +877,84 @@ def em_condition(means, covs, observed, diagonal=False, tied=False):
     return mu_o, S_oo, A, mu_m
 
 
+def _impute_block(x, d=None):
+    if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.ndim == 2 and x.flags.c_contiguous):
+        raise TypeError("x must be a C-contiguous float64 N x d numpy array")
+    if d is not None and x.shape[1] != d:
+        raise ValueError(f"x must have one column per coordinate of the model ({d})")
+    return x
+
+
+def em_impute(ctx, mixing, means, covs, x, diagonal=False, tied=False, log_density=False, responsibilities=False):
+    """x (N x d C-contiguous float64, NaN = missing, every row its own pattern) with every NaN replaced by its conditional expectation
+    under the mixture given the coordinates the row has (mlhip_em_impute): a new N x d array, observed entries bit for bit -- with
+    log_density=True and / or responsibilities=True a tuple of it, the N log-densities of the rows' observed coordinates under the
+    marginal mixture and the N x K marginal responsibilities (C-contiguous), in that order. ctx: a Context or a device group (every
+    shard imputes its own rows). means: K x d; covs as for Data.em_score. TypeError / ValueError before any device work; ValueError
+    where the observed block of a covariance is not positive definite for some row's pattern (nothing is returned)."""
+    mixing = np.ascontiguousarray(mixing, dtype=np.float64)
+    means = np.ascontiguousarray(means, dtype=np.float64)
+    covs = np.ascontiguousarray(covs, dtype=np.float64)
+    assert not (diagonal and tied) and mixing.ndim == 1 and means.ndim == 2
+    K, d = means.shape
+    assert mixing.shape == (K,) and covs.shape == ((d, d) if tied else (K, d) if diagonal else (K, d, d))
+    x = _impute_block(x, d)
+    n = x.shape[0]
+    out = np.empty((n, d))
+    dens = np.empty(n) if log_density else None
+    resp = np.empty((n, K)) if responsibilities else None
+    check(lib.mlhip_em_impute(ctx.handle, C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(mixing), dptr(means),
+                              dptr(covs), dptr(x), C.c_uint64(n), dptr(out), dptr(dens) if log_density else None,
+                              dptr(resp) if responsibilities else None))
+    extra = tuple(v for v in (dens, resp) if v is not None)
+    return (out,) + extra if extra else out
+
+
+def em_impute_plan(x):
+    """The pattern grouping mlhip_em_impute makes of x (mlhip_em_impute_plan, no GPU): (order, bounds, n_observed) -- the rows in a
+    stable order in which the rows of one pattern of NaNs are contiguous and ascending (uint32, N), the P + 1 group bounds into it and
+    the number of observed coordinates of each of the P patterns."""
+    x = _impute_block(x)
+    n, d = x.shape
+    order, bounds, n_obs = np.empty(n, dtype=np.uint32), np.empty(n + 1, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+    p = C.c_uint32()
+    check(lib.mlhip_em_impute_plan(dptr(x), C.c_uint64(n), C.c_uint32(d), C.byref(p), u32ptr(order), u32ptr(bounds), u32ptr(n_obs)))
+    return order, bounds[:p.value + 1].copy(), n_obs[:p.value].copy()
+
+
+def em_impute_route(d, K, x=None):
+    """The route mlhip_em_impute takes for a d-dimensional model of K components under the switches as they are set now
+    (mlhip_em_impute_route, no GPU, nothing is launched): 'composed' | 'kernel' -- with a block x a pair of it and the kernel launches
+    the call makes for that block."""
+    route, launches = C.c_int(), C.c_uint64()
+    if x is None:
+        check(lib.mlhip_em_impute_route(C.c_uint32(d), C.c_uint32(K), None, C.c_uint64(0), C.byref(route), None))
+        return ("composed", "kernel")[route.value]
+    x = _impute_block(x, d)
+    check(lib.mlhip_em_impute_route(C.c_uint32(d), C.c_uint32(K), dptr(x), C.c_uint64(x.shape[0]), C.byref(route), C.byref(launches)))
+    return ("composed", "kernel")[route.value], launches.value
+
+
+def em_impute_condition(ctx, mixing, means, covs, observed, diagonal=False, tied=False):
+    """The records the kernel route of mlhip_em_impute builds ON THE DEVICE for the pattern that observes the ascending coordinates
+    `observed` (mlhip_em_impute_condition; d <= 32): (means_observed K x dO, whitening K x dO x dO -- W_k = L^-1, L L^T = Sigma_k,OO --,
+    coefficients K -- log pi_k - sum_j log L_jj --, maps K x dM x dO, means_missing K x dM). ValueError for bad coordinates or an
+    observed block that is not positive definite."""
+    mixing = np.ascontiguousarray(mixing, dtype=np.float64)
+    means = np.ascontiguousarray(means, dtype=np.float64)
+    covs = np.ascontiguousarray(covs, dtype=np.float64)
+    assert not (diagonal and tied) and means.ndim == 2
+    K, d = means.shape
+    assert mixing.shape == (K,) and covs.shape == ((d, d) if tied else (K, d) if diagonal else (K, d, d))
+    observed = np.ascontiguousarray(observed, dtype=np.uint32).ravel()
+    dO = len(observed)
+    dM = max(d - dO, 0)
+    mu_o, W, coef, A, mu_m = np.empty((K, dO)), np.empty((K, dO, dO)), np.empty(K), np.empty((K, dM, dO)), np.empty((K, dM))
+    check(lib.mlhip_em_impute_condition(ctx.handle, C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(mixing), dptr(means),
+                                        dptr(covs), u32ptr(observed), C.c_uint32(dO), dptr(mu_o), dptr(W), dptr(coef), dptr(A), dptr(mu_m)))
+    return mu_o, W, coef, A, mu_m
+
+
 def em_condition_covariances(covs, observed, diagonal=False, tied=False, K=None):
     """The covariances of the components of a mixture conditioned on the coordinates `observed` and their lower Cholesky factors
     (mlhip_em_condition_covariances, no GPU): (covariances_missing K x dM x dM, factors K x dM x dM, zero above the diagonal), the

@@ -8,7 +8,7 @@ Conventions kept from the reference:
   * `KMeans.labels` is a Python list (pybind11/stl.h conversion, clustering.cpp:173);
   * std::invalid_argument / std::domain_error surface as ValueError.
 Extensions (not in the reference surface): `silhouette_samples`, `silhouette_score` (module level: exact silhouette values on the GPU,
-for the labels of either model), `EM.number_parameters`, `EM.bic`, `EM.aic`, `EM.conditional_mean`, `EM.conditional_variance`, `EM.conditional_cdf`, `EM.conditional_quantile`, `EM.conditional_sample`, `EM.conditional_covariances`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
+for the labels of either model), `EM.number_parameters`, `EM.bic`, `EM.aic`, `EM.impute`, `EM.conditional_mean`, `EM.conditional_variance`, `EM.conditional_cdf`, `EM.conditional_quantile`, `EM.conditional_sample`, `EM.conditional_covariances`, `EM.sample`, `EM.score_samples`, `EM.score`, `EM.predict`, `EM.predict_proba`, `KMeans.predict`, `EM.labels`, `EM.converged`, `EM.steps_done`, `EM.responsibilities_rows`, `KMeans.converged`,
 `KMeans.steps_done`, `KMeans.labels_array`, `FixedCentroids`, `FixedPointKPP`, `EM.fit(..., sample_weight=)`,
 `KMeans.fit(..., sample_weight=)`, `EM.set_covariance_regularisation`, `EM.covariance_regularisation`, `EM.set_number_initialisations`,
 `EM.number_initialisations`, `EM.best_initialisation`, `EM.initialisation_log_likelihoods`, `EM.initialisation_steps`,
@@ -426,6 +426,29 @@ class EM:
         _check(_l.mlpp_em_conditional_means(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n), _dp(out),
                                             _dp(dens) if return_log_density else None))
         return (out, dens) if return_log_density else out
+
+    def impute(self, X, return_log_density=False, return_responsibilities=False):
+        """Extension (imputation of a table with gaps): a copy of X (N x d, C-contiguous float64 like what `fit` takes) in which every
+        NaN is replaced by E[x_j | the coordinates that row has] under the fitted mixture, on the GPU. Every row has its own pattern
+        of NaNs; observed entries keep their bits, a complete row comes back as it is, a row of all NaN as the mixture's mean. With
+        return_log_density=True and / or return_responsibilities=True a tuple of the array, the N log-densities of the rows' observed
+        coordinates under the marginal mixture, and the (N, K) C-contiguous posterior memberships given what each row has -- what
+        predict_proba cannot give for an incomplete row --, in that order. A row's results do not depend on the other rows or their
+        order. TypeError / ValueError before any device work."""
+        X = _require_data(X)
+        d, _ = self._dims()
+        if d == 0:
+            raise ValueError("impute(): the model has not been fitted")
+        n, columns = X.shape
+        if columns != d:
+            raise ValueError("impute(): X must have one column per coordinate of the model")
+        out = np.empty((n, d))
+        dens = np.empty(n) if return_log_density else None
+        resp = np.empty((n, self.number_components)) if return_responsibilities else None
+        _check(_l.mlpp_em_impute(self._h, _dp(X), C.c_uint64(n), C.c_uint32(d), _dp(out), _dp(dens) if return_log_density else None,
+                                 _dp(resp) if return_responsibilities else None))
+        extra = tuple(v for v in (dens, resp) if v is not None)
+        return (out,) + extra if extra else out
 
     def conditional_variance(self, X_observed, observed, covariance=False, return_mean=False):
         """Extension (error bars on an imputed value, heteroscedastic regression bands): the predictive variance Var[x_M | x_O] under

@@ -229,6 +229,57 @@ inline size_t condition_record_doubles(int kernel, int dO, int dM)
 /// Returns the grid (0: nothing to do), or < 0 where the kernel asked for is not built for the shape.
 int launch_em_condition(const ConditionArgs& a, int num_cus, hipStream_t stream);
 
+/// Imputation with a pattern per row (em_impute_records.hip, em_impute.hip; the definition: mlhip.h, mlhip_em_impute), d <= 32.
+/// A pattern's K records stand one after the other from `rec_base` (in doubles) of the record buffer, each
+///   [mu_O (PO) | mu_M (PM) | A^T (PO x PM: row c = observed coordinate c) | W (PO (PO + 1) / 2: the packed lower triangle of L^-1,
+///    row j from j (j + 1) / 2) | coef]
+/// in the paddings of condition_pad(kConditionRegisters, .): +0.0, except the rows c >= dO of A^T: -0.0 (a padded coordinate has
+/// x_c = mu_c = +0.0, so its term of the map chain is fma(-0.0, +0.0, t) = t and its row of W adds fma(+0.0, +0.0, q) = q: identities
+/// bit for bit).
+constexpr int kImputeMaxDim = 32;
+struct ImputePattern {
+    uint32_t dO, dM, po, pm, rec_base;                           // po / pm: condition_pad(kConditionRegisters, dO / dM)
+    uint32_t observed[kImputeMaxDim];                            // ascending; beyond dO: 0 (never read)
+    uint32_t missing[kImputeMaxDim];                             // ascending; beyond dM: 0 (never read)
+};
+inline size_t impute_record_doubles(int po, int pm) { return (size_t)po + pm + (size_t)po * pm + (size_t)po * (po + 1) / 2 + 1; }
+/// The records of `n_patterns` patterns x K components, one wave each: Sigma_k,OO gathered by the pattern's coordinates into LDS and
+/// factored there (L L^T, the column-by-column form), W = L^-1, coef_k = log_mixing[k] - sum_j log L_jj, A_k = Sigma_k,MO Sigma_k,OO^-1
+/// by a forward and a backward substitution per missing coordinate. A pivot that is not > 0 or not finite is an ordinary value here:
+/// the wave stores 1 to *flag (a plain vector store; the host zeroes it before the launch), takes 1.0 for the pivot and goes on.
+struct ImputeRecordsArgs {
+    int d, K;
+    const double* means;                                         // K x d
+    const double* covs;                                          // K x d x d, full
+    const double* log_mixing;                                    // K
+    const ImputePattern* patterns; uint32_t n_patterns;
+    double* records;                                             // out
+    uint32_t* flag;                                              // out
+};
+void launch_em_impute_records(const ImputeRecordsArgs& a, hipStream_t stream);
+/// One tile of the evaluation kernel: rows [first, first + rows) of the chunk's row block, all of pattern `pattern` (an index into
+/// ImputeArgs::patterns), rows <= 64; their rows x dM results go to y + out_base (out_base even: 16-byte aligned), row-major.
+struct ImputeTile {
+    uint32_t pattern, first, rows, out_base;
+};
+/// The evaluation kernel on the tiles of ONE padding class (po, pm): lane = row, per row the steps 1 - 6 of the definition with the
+/// record of the tile's pattern. Returns the grid (0: nothing to do), < 0 where the class is not instantiated. `grid_cap` > 0: at
+/// most that many workgroups (the tests' way to make a wave take a second tile on a small block).
+struct ImputeArgs {
+    const double* x; int d;                                      // the chunk's rows, row-major and contiguous, NaNs and all
+    int K;
+    const ImputePattern* patterns;
+    const double* records;
+    const ImputeTile* tiles; uint32_t n_tiles;
+    int po, pm;
+    double* y;                                                   // out: per tile rows x dM
+    double* lse;                                                 // out: per row of the chunk, the log-sum-exp of step 4
+    double* resp; size_t ldr;                                    // out (may be null): resp[k * ldr + row]
+    int skip;                                                    // 1: a wave passes over a component none of its rows has a share in
+    int grid_cap;
+};
+int launch_em_impute(const ImputeArgs& a, int num_cus, hipStream_t stream);
+
 /// Conditional draws (em_condition_sample.hip): x_M | x_O of the n rows of a chunk for the draws first_draw .. first_draw + n_draws - 1,
 /// from the same lw / lse as the conditioning pass. Row (i, q) is a pure function of (seed, first_row + i, q), the row and the
 /// parameters. The tiers and paddings are ConditionKernel's and condition_pad's; the record is the conditioning pass's with the

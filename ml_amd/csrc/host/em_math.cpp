@@ -116,6 +116,8 @@ int resolve_host_threads(int local_ranks)
 /// A thread team costs 10-20 us to wake: only worth it when the K factorizations (~2.3 d^3 flop each) are more than that.
 inline bool worth_threads(int K, int d) { return (double)K * d * d * d >= 4.0e5; }
 
+}  // namespace
+
 int host_threads()
 {
     int t = g_host_threads.load(std::memory_order_relaxed);
@@ -125,6 +127,8 @@ int host_threads()
     }
     return t;
 }
+
+namespace {
 
 /// fn(k, L, W) for the K components, L and W two d x d scratch matrices of the thread that runs k: on this thread's team
 /// (host/team.hpp) when the K factorizations are worth waking it, else a plain loop. Every k is handled by exactly one thread and

@@ -100,6 +100,8 @@ void condition_covariances(Covariance mode, int K, int d, const double* covarian
 /// Tells the host-side math how many ranks share this node, so that the OpenMP teams of the per-component
 /// factorizations together stay within the host's cores (MLHIP_HOST_THREADS overrides the per-rank thread count).
 void set_host_ranks(int local_ranks);
+/// The threads a host-side region of this process may use (what set_host_ranks or MLHIP_HOST_THREADS left; at most 8 by default).
+int host_threads();
 
 }  // namespace host
 }  // namespace mlhip

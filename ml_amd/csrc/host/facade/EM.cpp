@@ -696,6 +696,36 @@ MatrixXd EM::conditional_means(const std::vector<unsigned int>& observed, ConstM
     return out;
 }
 
+MatrixXd EM::impute(ConstMatrixRef data, double* log_densities, MatrixXd* responsibilities) const
+{
+    const Index d = means_.rows(), n = data.cols();
+    // (the order of sample: that there is a shape, the arguments against it, then the device and the decompositions)
+    if (d == 0) throw std::invalid_argument("EM: model has no fitted covariance decompositions");
+    if (data.rows() != d) throw std::invalid_argument("Wrong data size");
+    require_fitted();
+    const unsigned int K = number_components_;
+    MatrixXd out(d, n);
+    if (responsibilities) responsibilities->resize(K, n);
+    if (!n) return out;
+    const std::vector<double> cov_flat = flat_covariances();
+    mlhip_ctx* ctx = device::context();
+    const Index batch = Clustering::detail::score_batch_rows();
+    std::vector<double> packed;                                  // (mlhip_em_impute takes contiguous points)
+    for (Index first = 0; first < n; first += batch) {
+        const Index rows = std::min(batch, n - first);
+        const double* x = data.col(first);
+        if (data.outerStride() != d) {
+            packed.resize(static_cast<std::size_t>(rows * d));
+            for (Index i = 0; i < rows; ++i) std::copy_n(data.col(first + i), d, packed.data() + i * d);
+            x = packed.data();
+        }
+        check(mlhip_em_impute(ctx, static_cast<uint32_t>(d), K, MLHIP_COVARIANCE_FULL, mixing_probabilities_.data(), means_.data(),
+                              cov_flat.data(), x, static_cast<uint64_t>(rows), out.col(first), log_densities ? log_densities + first : nullptr,
+                              responsibilities ? responsibilities->col(first) : nullptr));
+    }
+    return out;
+}
+
 std::vector<MatrixXd> EM::conditional_covariances(const std::vector<unsigned int>& observed) const
 {
     const Index d = means().rows();

@@ -267,6 +267,18 @@ int mlpp_em_conditional_means(const mlpp_em* h, const uint32_t* observed, uint32
         std::copy_n(y.data(), y.size(), out);
     });
 }
+int mlpp_em_impute(const mlpp_em* h, const double* data, uint64_t n, uint32_t d, double* out, double* log_density_out, double* responsibilities_out)
+{
+    return guarded([&] {
+        need(h);
+        if (n && d) { need(data); need(out); }
+        if (n > static_cast<uint64_t>(std::numeric_limits<Index>::max())) throw std::invalid_argument("EM: Too many samples");
+        MatrixXd shares;
+        const MatrixXd y = h->em.impute(ConstMatrixRef(data, d, static_cast<Index>(n), d), log_density_out, responsibilities_out ? &shares : nullptr);
+        std::copy_n(y.data(), y.size(), out);
+        if (responsibilities_out) std::copy_n(shares.data(), shares.size(), responsibilities_out);
+    });
+}
 int mlpp_em_conditional_covariances(const mlpp_em* h, const uint32_t* observed, uint32_t n_observed, double* out)
 {
     return guarded([&] {

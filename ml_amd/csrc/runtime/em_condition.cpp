@@ -117,16 +117,17 @@ Covariance check_condition_arguments(uint32_t d, uint32_t K, int covariance_type
     return mode;
 }
 
-namespace {
-
-void em_conditional_means(mlhip_data* dt, const ConditionedModel& m, double* out, int64_t ld_out, double* log_density)
+void em_conditional_means(mlhip_data* dt, const ConditionedModel& m, double* out, int64_t ld_out, double* log_density, double* resp,
+                          int64_t ld_resp)
 {
     mlhip_ctx* ctx = dt->ctx;
     if (!dt->n) return;
     const ConditionRoute r = condition_route(dt, m.K, m.dM);
     ConditionPass pass(dt, m, r.em, r.kernel, r.chunk_rows, 0, {}, "conditioning kernel not instantiated for this shape");
-    DevBuf y{&dt->pool};
+    DevBuf y{&dt->pool}, shares{&dt->pool};
     y.reserve(sizeof(double) * (size_t)r.chunk_rows * m.dM);
+    std::vector<double> columns;
+    if (resp) shares.reserve(sizeof(double) * (size_t)r.chunk_rows * m.K);
     pass.run(log_density, [&](const ConditionChunk& chunk, uint32_t row) {
         ConditionArgs c{};
         static_cast<ConditionChunk&>(c) = chunk;
@@ -136,10 +137,18 @@ void em_conditional_means(mlhip_data* dt, const ConditionedModel& m, double* out
         if (grid < 0) throw Unsupported("conditioning kernel not instantiated for this shape");
         HIP_CHECK(hipGetLastError());
         pass.download_rows(out + (int64_t)row * ld_out, ld_out, y.p, chunk.n, (size_t)m.dM);
+        if (!resp) return;
+        // the shares the kernel above weighted with: em_resp_kernel's exp_nonpos(lw_k - lse) on the same block, component-major
+        RespArgs a{chunk.lw, chunk.ldr, chunk.lse, chunk.n, m.K, shares.as<double>(), chunk.n, nullptr};
+        ctx->timed("em_responsibilities", [&] { launch_em_responsibilities(a, ctx->stream); });
+        HIP_CHECK(hipGetLastError());
+        columns.resize((size_t)chunk.n * m.K);
+        pass.download_rows(columns.data(), (int64_t)chunk.n * m.K, shares.p, 1, (size_t)chunk.n * m.K);
+        for (uint32_t i = 0; i < chunk.n; ++i)
+            for (int k = 0; k < m.K; ++k) resp[(int64_t)(row + i) * ld_resp + k] = columns[(size_t)k * chunk.n + i];
     });
 }
 
-}  // namespace
 }  // namespace mlhip_rt
 
 extern "C" {
@@ -170,7 +179,7 @@ int mlhip_em_conditional_means(mlhip_ctx* ctx, mlhip_data* data, uint32_t K, uin
         require(dM >= 1 && dO + dM <= (uint32_t)kGenericMaxDim, "observed and missing coordinates together must be 2 .. 4096");
         require(ld_out >= (int64_t)dM, "ld_out must be >= dM");
         const ConditionedModel m{(int)K, (int)dM, mixing, means_observed, covariances_observed, maps, means_missing};
-        on_block_or_shards(ctx, data, [&](Shard& sh) { em_conditional_means(sh.part, m, sh.rows(out, ld_out), ld_out, sh.rows(log_density)); });
+        on_block_or_shards(ctx, data, [&](Shard& sh) { em_conditional_means(sh.part, m, sh.rows(out, ld_out), ld_out, sh.rows(log_density), nullptr, 0); });
     });
 }
 

@@ -742,6 +742,25 @@ struct SilhouetteRoute {
     uint32_t block_rows(uint64_t n_chunks, uint64_t m) const;
 };
 SilhouetteRoute silhouette_route(const mlhip_data* data);
+/// mlhip_em_impute, the rows grouped by their pattern of NaNs (host/impute_plan.hpp); on either route the complete rows go through
+/// mlhip_em_score and the rows of all NaN are formed on the host.
+///   COMPOSED  every group of at most `rows` rows of one pattern through the conditional-means pass of that pattern (condition_route:
+///             its kernels, chunks and switches) with the model conditioned on the host: every shape, launches grow with the patterns;
+///   KERNEL    2 <= d <= 32 (MLHIP_IMPUTE=composed: COMPOSED there too): the records of at most `patterns` patterns at a time built on
+///             the device (em_impute_records.hip; 0: as many as kImputeRecordBytes hold), then per chunk of `rows` rows one launch of
+///             the evaluation kernel (em_impute.hip) per padding class present.
+/// `rows`: MLHIP_IMPUTE_ROWS=n, else kImputeRows (composed) / the rows whose coordinates fill kImputeRowBytes (kernel). `grid_cap`:
+/// MLHIP_IMPUTE_GRID=n. No row depends on any of them. (mlhip.h names the routes by ImputeKind's values.)
+enum ImputeKind : int { kImputeComposed = 0, kImputeKernel = 1 };
+constexpr uint32_t kImputeRows = uint32_t(1) << 20;
+constexpr uint64_t kImputeRowBytes = uint64_t(64) << 20, kImputeRecordBytes = uint64_t(256) << 20;
+struct ImputeRoute {
+    int kind = kImputeComposed;
+    uint32_t rows = kImputeRows, patterns = 0;
+    int grid_cap = 0;
+    bool skip = true;
+};
+ImputeRoute impute_route(int d, int K);
 /// The argument checks of mlhip_em_condition and mlhip_em_condition_covariances behind their null checks; returns the covariance mode.
 Covariance check_condition_arguments(uint32_t d, uint32_t K, int covariance_type, const uint32_t* observed, uint32_t n_observed);
 
@@ -1124,6 +1143,12 @@ private:
     ChunkEstep estep_;
     std::vector<char> packed_;
 };
+
+/// The body of mlhip_em_conditional_means on one block (em_condition.cpp). `resp` (rows x K, `ld_resp` >= K doubles apart; may be null):
+/// the shares r_k = exp_nonpos(lw_k - lse) the conditioning kernel weights with, formed by em_resp_kernel from the same chunk's lw / lse
+/// (mlhip_em_impute's composed route asks for them).
+void em_conditional_means(mlhip_data* dt, const ConditionedModel& m, double* out, int64_t ld_out, double* log_density, double* resp,
+                          int64_t ld_resp);
 
 // What is not a plain fan-out:
 namespace grp {

@@ -41,6 +41,10 @@ struct Switches {
     int silhouette_feed;        // MLHIP_SILHOUETTE_FEED=scalar / lds: kSilhouetteScalarFeed / kSilhouetteLdsFeed forced, -1 automatic
     long silhouette_rows;       // MLHIP_SILHOUETTE_ROWS=n: evaluated rows per block (0: by the scratch bound)
     long silhouette_grid;       // MLHIP_SILHOUETTE_GRID=n: workgroups of the pair kernel (0: by the CU count)
+    int impute;                 // MLHIP_IMPUTE=composed / kernel: kImputeComposed / kImputeKernel forced where it exists, -1 automatic
+    long impute_rows;           // MLHIP_IMPUTE_ROWS=n: rows per chunk of mlhip_em_impute (0: by the route's bound)
+    long impute_patterns;       // MLHIP_IMPUTE_PATTERNS=n: patterns whose records the kernel route builds at a time (0: by the scratch bound)
+    long impute_grid;           // MLHIP_IMPUTE_GRID=n: at most n workgroups per evaluation launch (0: by the CU count; the tests' switch)
 };
 
 Switches read_switches()
@@ -94,6 +98,14 @@ Switches read_switches()
     s.silhouette_rows = silhouette_rows && *silhouette_rows ? std::atol(silhouette_rows) : 0;
     const char* silhouette_grid = std::getenv("MLHIP_SILHOUETTE_GRID");
     s.silhouette_grid = silhouette_grid && *silhouette_grid ? std::atol(silhouette_grid) : 0;
+    const char* impute = std::getenv("MLHIP_IMPUTE");
+    s.impute = !impute ? -1 : std::strcmp(impute, "composed") == 0 ? kImputeComposed : std::strcmp(impute, "kernel") == 0 ? kImputeKernel : -1;
+    const char* impute_rows = std::getenv("MLHIP_IMPUTE_ROWS");
+    s.impute_rows = impute_rows && *impute_rows ? std::atol(impute_rows) : 0;
+    const char* impute_patterns = std::getenv("MLHIP_IMPUTE_PATTERNS");
+    s.impute_patterns = impute_patterns && *impute_patterns ? std::atol(impute_patterns) : 0;
+    const char* impute_grid = std::getenv("MLHIP_IMPUTE_GRID");
+    s.impute_grid = impute_grid && *impute_grid ? std::atol(impute_grid) : 0;
     return s;
 }
 
@@ -245,6 +257,22 @@ ConditionSampleRoute condition_sample_route(const mlhip_data* data, int K, int d
     const uint64_t per_row = kScoreScratchBytes / sizeof(double) / r.chunk_rows;
     const uint64_t fit = per_row > (uint64_t)K ? (per_row - (uint64_t)K) / (uint64_t)dM : 0;
     r.draws = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fit, n_draws));
+    return r;
+}
+
+ImputeRoute impute_route(int d, int K)
+{
+    const Switches sw = read_switches();
+    ImputeRoute r;
+    // the kernel route exists where a row can have both kinds of coordinates and the register tier's paddings hold them
+    const bool kernel_exists = d >= 2 && d <= kImputeMaxDim;
+    r.kind = kernel_exists && sw.impute != kImputeComposed ? kImputeKernel : kImputeComposed;
+    // rows per chunk: a pattern's rows per conditioning pass (composed), the rows whose d coordinates stay within kImputeRowBytes (kernel)
+    const uint32_t bound = r.kind == kImputeKernel ? (uint32_t)std::max<uint64_t>(64, kImputeRowBytes / (sizeof(double) * (uint64_t)d) / 64 * 64) : kImputeRows;
+    r.rows = sw.impute_rows > 0 ? (uint32_t)std::min<long>(sw.impute_rows, (long)bound) : bound;
+    r.patterns = sw.impute_patterns > 0 ? (uint32_t)std::min<long>(sw.impute_patterns, 1l << 30) : 0;
+    r.grid_cap = sw.impute_grid > 0 ? (int)std::min<long>(sw.impute_grid, 1l << 20) : 0;
+    r.skip = sw.condition_skip;
     return r;
 }
 
