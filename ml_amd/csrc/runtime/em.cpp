@@ -91,113 +91,6 @@ RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* 
 }
 
 
-/// Largest number of nonzero responsibilities (sparse statistics kernel) / candidates (screened E-step) per sample up to which the
-/// kernels whose cost grows with them are taken.
-constexpr double kSparseMaxPairs = 16.0;
-constexpr double kScreenMaxPairs = kSparseMaxPairs;
-
-
-/// Whether pass t of a fit -- an E-step pass of the screened kernel's domain, launch_estep -- is asked to run screened
-/// (em_estep_screen.hip). The block must be one the screened kernel may start from (EstepState::screenable: written by such a pass
-/// of this handle with this K and untouched since, its records in scr_rec). By call history: the sparse-statistics rule holds for
-/// pass t - 2 (the last whose counts every loop has in hand), and where pass t - 2 was itself screened it had at most
-/// kScreenMaxPairs candidates per sample -- and only at the shapes where the screened pass was measured faster
-/// (em_estep_screen_preferred). The route may force either (r.screen). The bound constants have the last word: launch_screened.
-static bool screen_wanted(const mlhip_data* dt, const EmRoute& r, int K)
-{
-    if (r.screen == 0 || !dt->estep.screenable) return false;
-    if (r.screen == 1) return true;
-    if (!em_estep_screen_preferred(dt->D, K)) return false;
-    if (dt->sn_K != K || dt->sn_calls < 2 || dt->scr_passes < 2) return false;
-    const unsigned long long nz = dt->nz_host.as<unsigned long long>()[(dt->sn_calls - 2) % 3];
-    if ((double)nz > kSparseMaxPairs * (double)dt->n) return false;
-    const int back = (int)((dt->scr_passes - 2) % 3);
-    if (dt->scr_was[back] && (double)dt->scr_host.as<unsigned long long>()[1 + back] > kScreenMaxPairs * (double)dt->n) return false;
-    return true;
-}
-
-
-/// The stamps of a profiled screened pass (em_estep_screen.hip, PROF form), averaged over the workgroups that stamped a tile: one line
-/// on stderr, microseconds of the 100 MHz clock. tools/estep_screen_phases.py reads it.
-static void report_screen_stamps(const mlhip_data* dt, const DevBuf& stamps, int grid, int K)
-{
-    constexpr int NS = kScreenStamps;
-    std::vector<unsigned long long> t((size_t)NS * grid);
-    HIP_CHECK(hipMemcpy(t.data(), stamps.p, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost));
-    const int tile_samples = em_estep_screen_tile(dt->D), waves = tile_samples / 32;
-    const int rounds = std::min(kScreenStampRounds, (K + waves - 1) / waves);   // components wave 0 takes (the stamped ones)
-    double stage = 0, buckets = 0, copy = 0, eval = 0, wait = 0, tile = 0;
-    int used = 0;
-    for (int b = 0; b < grid; ++b) {
-        const unsigned long long* s = t.data() + (size_t)NS * b;
-        if (!s[0] || !s[kScreenStampTileEnd]) continue;                                  // (the workgroup had no second tile)
-        ++used;
-        stage += (double)(s[1] - s[0]);
-        buckets += (double)(s[2] - s[1]);
-        unsigned long long prev = s[2];
-        for (int j = 0; j < rounds; ++j) {
-            copy += (double)(s[3 + 2 * j] - prev);
-            eval += (double)(s[4 + 2 * j] - s[3 + 2 * j]);
-            prev = s[4 + 2 * j];
-        }
-        wait += (double)(s[kScreenStampTileEnd] - s[kScreenStampLoopEnd]);
-        tile += (double)(s[kScreenStampTileEnd] - s[0]);
-    }
-    if (!used) {
-        std::fprintf(stderr, "[mlhip] screened E-step, N=%u d=%d K=%d grid=%d: no workgroup had a second tile to stamp\n", dt->n, dt->d, K, grid);
-        return;
-    }
-    const double us = 0.01 / used;
-    std::fprintf(stderr, "[mlhip] screened E-step, N=%u d=%d K=%d grid=%d, us per %d-sample tile (thread 0, mean of %d workgroups): stage %.2f, "
-                 "buckets %.2f, record copy %.2f, evaluation %.2f (%d components of wave 0), end barrier %.2f, tile %.2f\n",
-                 dt->n, dt->d, K, grid, tile_samples, used, stage * us, buckets * us, copy * us, eval * us, rounds, wait * us, tile * us);
-}
-
-
-/// The screened pass: the constants of the step from the block's records (scr_rec) to `a.params`, then -- when every component's
-/// bound carries information -- the screened kernel. Returns its grid, or 0 when the dense kernel has to run (the decision is the
-/// host's: it waits for the constants kernel's count, a few microseconds on a stream that has just been waited for).
-static int launch_screened(mlhip_data* dt, const EstepArgs& a, int K)
-{
-    mlhip_ctx* ctx = dt->ctx;
-    unsigned long long* dev = dt->scr_dev.as<unsigned long long>();
-    unsigned long long* host = dt->scr_host.as<unsigned long long>();
-    HIP_CHECK(hipMemsetAsync(dev, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    launch_em_screen_constants(dt->scr_rec.as<double>(), a.params, K, dt->d, dt->D, dt->scr_consts.as<double>(),
-                               reinterpret_cast<unsigned*>(dev), ctx->stream);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-    if (host[0] != 0) {
-        dt->scr_n_no_info++;
-        return 0;
-    }
-    ScreenArgs sa{};
-    sa.xt = a.xt; sa.ldx = a.ldx; sa.n = a.n; sa.D = a.D;
-    sa.params = a.params; sa.K = K; sa.shift = a.shift; sa.consts = dt->scr_consts.as<double>();
-    sa.lw = a.lw; sa.ldr = a.ldr;
-    sa.exact = dt->scr_exact.as<unsigned long long>(); sa.all_exact = dt->scr_all_exact ? 1 : 0;
-    sa.cand_count = dev + 1;
-    // MLHIP_ESTEP_SCREEN_PROFILE=1: the kernel's stamping form; the phases of every workgroup's second tile, averaged, on stderr (diagnostic)
-    static const bool profile = [] { const char* e = std::getenv("MLHIP_ESTEP_SCREEN_PROFILE"); return e && e[0] == '1'; }();
-    DevBuf stamps;
-    if (profile) {
-        stamps.reserve(sizeof(unsigned long long) * kScreenStamps * (256 / em_estep_screen_tile(dt->D)) * ctx->num_cus);   // (a slot set per workgroup of the grid)
-        HIP_CHECK(hipMemsetAsync(stamps.p, 0, stamps.bytes, ctx->stream));
-        sa.profile = stamps.as<unsigned long long>();
-    }
-    const int grid = launch_em_estep_screen(sa, ctx->num_cus, ctx->stream);
-    if (grid <= 0) throw Unsupported("screened E-step kernel not instantiated for this dimension");
-    if (profile) {
-        HIP_CHECK(hipGetLastError());
-        ctx->sync();
-        report_screen_stamps(dt, stamps, grid, K);
-    }
-    HIP_CHECK(hipMemcpyAsync(host + 1 + dt->scr_passes % 3, dev + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    return grid;
-}
-
-
 /// E-step kernel on the records in params_dev: fills lw and -- unless the statistics kernel is going to normalise the
 /// log-responsibilities itself (`with_lse` false, matrix-core kernel only) -- lse and the log-likelihood partials.
 /// This is the one place where a pass of a fit (`may_screen`) is routed to the dense or the screened kernel.
@@ -218,26 +111,14 @@ void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const 
     // the screened kernel's domain: the FOLD, lw-only matrix-core pass of an unweighted block where the sparse statistics kernel exists
     const bool domain = may_screen && dt->estep.rec_layout == 2 && a.fold && !a.with_lse && !dt->weighted && r.estep == Estep::kMatrix4 &&
                         em_estep_screen_supported(dt->D, K) && em_mstats_sparse_supported(dt->d, K, ctx->num_cus);
-    // ... and whether this pass may screen or leave a block a later pass may screen from: only then the state below is kept
+    // ... and whether this pass may screen or leave a block a later pass may screen from: only then ScreenState keeps its history
     const bool tracked = domain && (r.screen == 1 || (r.screen < 0 && em_estep_screen_preferred(dt->D, K)));
-    const size_t rec_bytes = sizeof(double) * estep_mfma4_param_stride(dt->D) * K;
-    if (tracked) {
-        if (dt->scr_K != K) {
-            dt->scr_K = K;
-            dt->scr_passes = 0;
-            dt->estep.screenable = false;
-        }
-        dt->scr_rec.reserve(rec_bytes);
-        dt->scr_exact.reserve(sizeof(unsigned long long) * dt->n_pad);
-        dt->scr_consts.reserve(sizeof(double) * 4 * K);
-        dt->scr_dev.reserve(2 * sizeof(unsigned long long));
-        dt->scr_host.reserve(4 * sizeof(unsigned long long));
-    }
+    if (tracked) dt->screen.track(dt, K);
     int grid = 0;
     bool screened = false;
     ctx->timed("em_estep", [&] {
-        if (tracked && screen_wanted(dt, r, K)) {
-            grid = launch_screened(dt, a, K);
+        if (tracked) {
+            grid = dt->screen.run(dt, a, r.screen);
             screened = grid > 0;
         }
         if (!screened)
@@ -246,15 +127,7 @@ void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse, const 
     if (grid < 0) throw Unsupported("E-step kernel not instantiated for this dimension");
     HIP_CHECK(hipGetLastError());
     dt->estep.block_written(grid);
-    if (domain) (screened ? dt->scr_n_screened : dt->scr_n_dense)++;
-    if (tracked) {
-        // the block now belongs to these records: the next pass of the fit may start from it
-        HIP_CHECK(hipMemcpyAsync(dt->scr_rec.p, a.params, rec_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        dt->scr_all_exact = !screened;
-        dt->scr_was[dt->scr_passes % 3] = screened;
-        dt->scr_passes++;
-        dt->estep.block_screenable();
-    }
+    if (domain) dt->screen.pass_done(dt, a, tracked, screened);
     if (dt->weighted && a.with_lse) {
         // the log-likelihood of a weighted block is sum_i w_i lse_i: its partials replace the E-step's, lse itself stays per row
         // (without lse the weighted self-normalising statistics pass finishes both: launch_em_reduce)
@@ -426,16 +299,13 @@ void run_mstats(mlhip_data* dt, const EmRoute& r, int K, int mode, const double*
     dt->estep.stats_from(self_norm ? (int)kFromLogResp : mode, a.lw, a.ldr);
     int rc = 0;
     if (self_norm) {
-        const bool sparse = mstats_sparse_applies(dt, r, K);
-        const int slot = (int)(dt->sn_calls % 3);
-        dt->sn_calls++;
-        a.nz_count = dt->nz_dev.as<unsigned long long>();
-        HIP_CHECK(hipMemsetAsync(dt->nz_dev.p, 0, sizeof(unsigned long long), ctx->stream));
+        // the sparse kernel (em_mstats_sparse.hip) or the dense one, by the counts of the handle's earlier passes (sparse_stats_wanted)
+        a.nz_count = dt->stats_history.begin(K, ctx->stream);
+        const bool sparse = dt->stats_history.sparse_wanted(dt->n, r.sparse, em_mstats_sparse_supported(dt->d, K, ctx->num_cus));
         ctx->timed("em_mstats", [&] {
             rc = sparse ? launch_em_mstats_sparse(a, ctx->num_cus, ctx->stream) : launch_em_mstats(a, ctx->num_cus, ctx->stream);
         });
-        HIP_CHECK(hipMemcpyAsync(dt->nz_host.as<unsigned long long>() + slot, dt->nz_dev.p, sizeof(unsigned long long),
-                                 hipMemcpyDeviceToHost, ctx->stream));
+        dt->stats_history.end(ctx->stream);
     } else {
         ctx->timed("em_mstats", [&] { rc = launch_em_mstats(a, ctx->num_cus, ctx->stream); });
     }
@@ -576,28 +446,6 @@ void run_diag_kernel(mlhip_data* dt, const EmRoute& r, int K, const double* shif
                                   diag_stats_count(dt->d), [&] { return mstats::launch_em_diag(a, ctx->num_cus, ctx->stream); });
     dt->estep.mode_records_only(Covariance::Diagonal, grid);
     if (collect) collect_stats(dt, K, (size_t)K * diag_stats_count(dt->d) + 1);
-}
-
-
-/// Whether the next self-normalising statistics pass of `dt` runs the sparse kernel (em_mstats_sparse.hip) instead of the dense
-/// one. The sparse kernel's cost grows with the nonzero responsibilities, the dense kernel's does not: sparse while the pass two
-/// passes back (the last whose count every loop has in hand) had at most kSparseMaxPairs nonzero pairs per sample. The first two
-/// passes with a K are dense. The choice depends only on the handle's call history, so a loop of mlhip_em_step and
-/// mlhip_em_iterate take the same kernels in the same order. The route may force the sparse / dense kernel (r.sparse; where the
-/// sparse kernel exists).
-bool mstats_sparse_applies(mlhip_data* dt, const EmRoute& r, int K)
-{
-    if (dt->sn_K != K) {
-        dt->sn_K = K;
-        dt->sn_calls = 0;
-    }
-    dt->nz_dev.reserve(sizeof(unsigned long long));
-    dt->nz_host.reserve(3 * sizeof(unsigned long long));
-    if (!em_mstats_sparse_supported(dt->d, K, dt->ctx->num_cus)) return false;
-    if (r.sparse >= 0) return r.sparse == 1;
-    if (dt->sn_calls < 2) return false;
-    const unsigned long long nz = dt->nz_host.as<unsigned long long>()[(dt->sn_calls - 2) % 3];
-    return (double)nz <= kSparseMaxPairs * (double)dt->n;
 }
 
 
@@ -1089,28 +937,6 @@ int mlhip_em_plan(const mlhip_data* data, uint32_t K, uint32_t* flags)
             if (r.self_norm) f |= MLHIP_PLAN_SELF_NORM;
         }
         *flags = f;
-    });
-}
-
-int mlhip_em_screen_counts(mlhip_ctx* ctx, mlhip_data* data, uint64_t counts[4])
-{
-    return guarded([&] {
-        require(ctx && data && counts, "null argument");
-        require(data->ctx == ctx, "data belongs to another context");
-        for (int j = 0; j < 4; ++j) counts[j] = 0;
-        auto add = [&](mlhip_data* dt) {
-            dt->ctx->use();
-            dt->ctx->sync();
-            counts[0] += dt->scr_n_screened; counts[1] += dt->scr_n_dense; counts[2] += dt->scr_n_no_info;
-            for (uint64_t back = 1; back <= 3 && back <= dt->scr_passes; ++back) {      // the newest screened pass among the last three
-                const int slot = (int)((dt->scr_passes - back) % 3);
-                if (!dt->scr_was[slot]) continue;
-                counts[3] += dt->scr_host.as<unsigned long long>()[1 + slot];
-                break;
-            }
-        };
-        if (data->parts.empty()) add(data);
-        else for (mlhip_data* part : data->parts) add(part);
     });
 }
 

@@ -34,6 +34,7 @@
 
 #include "device/device.hpp"
 #include "host/em_math.hpp"
+#include "runtime/pass_history.hpp"
 
 namespace mlhip_rt {
 
@@ -446,12 +447,14 @@ struct EstepState {
     } kept;
 
     // The block is one the screened E-step may start from (launch_estep): every entry an evaluated value or an upper bound of one, under
-    // the records kept in mlhip_data::scr_rec. Every member that changes what the block is clears it.
+    // the records ScreenState keeps. Every member that changes what the block is clears it.
     bool screenable = false;
 
     void invalidate() { what = kNone; screenable = false; }
     void block_written(int grid) { what = kBlock; n_ll = grid; screenable = false; }
     void block_screenable() { screenable = what == kBlock; }
+    /// The records ScreenState keeps are no longer the block's (its history starts again with another K).
+    void block_not_screenable() { screenable = false; }
     /// A weighted block: the E-step's log-likelihood partials were replaced by `grid` partials of w_i lse_i (launch_estep).
     void ll_weighted(int grid) { n_ll = grid; }
     void records_only(int grid) { what = kRecords; n_ll = grid; screenable = false; }
@@ -487,6 +490,68 @@ struct EstepState {
     bool on_device() const { return what != kNone; }
     bool needs_rebuild() const { return what == kRecords || what == kModeRecords; }
     bool mode_records() const { return what == kModeRecords; }
+};
+
+/// The history of the self-normalising statistics passes of a data handle (run_mstats): both kernels add the number of nonzero
+/// responsibilities to a device word, which is copied to the pass's slot of a pinned ring (PassRing: its counts are read without a
+/// wait). Only the members below assign the fields.
+class StatsHistory {
+public:
+    explicit StatsHistory(BufferPool* const* pool) : nz_dev_(pool), nz_host_(pool) {}
+    /// A pass with K begins: the device word the kernel counts into, cleared on the stream.
+    unsigned long long* begin(int K, hipStream_t stream)
+    {
+        ring_.begin(K);
+        nz_dev_.reserve(sizeof(unsigned long long));
+        nz_host_.reserve(3 * sizeof(unsigned long long));
+        HIP_CHECK(hipMemsetAsync(nz_dev_.p, 0, sizeof(unsigned long long), stream));
+        return nz_dev_.as<unsigned long long>();
+    }
+    /// Whether the pass that has begun runs the sparse kernel (sparse_stats_wanted).
+    bool sparse_wanted(uint32_t n, int force, bool supported) const { return sparse_stats_wanted(ring_, counts(), n, force, supported); }
+    /// The kernel is on the stream: its count goes to the pass's slot.
+    void end(hipStream_t stream)
+    {
+        HIP_CHECK(hipMemcpyAsync(nz_host_.as<unsigned long long>() + ring_.slot(), nz_dev_.p, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                 stream));
+        ring_.finish(true);
+    }
+    const PassRing& ring() const { return ring_; }
+    const unsigned long long* counts() const { return nz_host_.as<unsigned long long>(); }
+
+private:
+    DevBuf nz_dev_;
+    PinnedBuf nz_host_;
+    PassRing ring_;
+};
+
+/// What the screened E-step (em_screen.cpp, em_estep_screen.hip) keeps on a data handle. Passes of the screened kernel's DOMAIN
+/// (launch_estep) are counted; the TRACKED ones among them -- those that may screen or leave a block a later pass may screen from --
+/// keep the rest: the records the N x K block belongs to, which of its values are evaluated ones, and the ring of their candidate
+/// counts. A tracked pass that runs dense -- one sent back for want of information included -- leaves no count and a block of
+/// evaluated values only. Only the members below assign the fields; EstepState::screenable says whether the block is still theirs.
+class ScreenState {
+public:
+    explicit ScreenState(BufferPool* const* pool) : rec_(pool), exact_(pool), consts_(pool), dev_(pool), host_(pool) {}
+    /// This pass of `dt` is tracked with K: the buffers, and the history from its start with another K than the last tracked pass's.
+    void track(mlhip_data* dt, int K);
+    /// The tracked pass on `a`, where it is wanted (screen_wanted; `force`: EmRoute::screen) and every component's bound carries
+    /// information: the screened kernel's grid. 0: the dense kernel has to run.
+    int run(mlhip_data* dt, const mlhip::EstepArgs& a, int force);
+    /// A pass of the domain is on the stream, screened or dense; a tracked one leaves the block with its records (`a.params`) for the next.
+    void pass_done(mlhip_data* dt, const mlhip::EstepArgs& a, bool tracked, bool screened);
+    /// mlhip_em_screen_counts, added to `counts`; the caller has waited for the stream.
+    void add_counts(uint64_t counts[4]) const;
+
+private:
+    DevBuf rec_;                  // the records the block belongs to (a copy: the ring of mlhip_em_iterate and params_dev move on)
+    DevBuf exact_;                // one word per sample, bit k = "the stored value of component k is an evaluated one"
+    DevBuf consts_;               // 4 doubles per component: the bound constants of the step from rec_ to the pass's records
+    DevBuf dev_;                  // [components without information (32 bits), padding | candidates]: one memset clears both
+    PinnedBuf host_;              // [the tracked ring's three candidate counts | the first word of dev_]
+    bool all_exact_ = true;       // a dense pass wrote the block: exact_ is not read
+    PassRing tracked_;
+    uint64_t n_screened_ = 0, n_dense_ = 0, n_no_info_ = 0;   // passes of the domain, tracked or not; send-backs (those count as dense too)
 };
 
 struct mlhip_data {
@@ -543,26 +608,11 @@ struct mlhip_data {
     DevBuf rs_kept{&pool}, rs_dev{&pool};
     PinnedBuf rs_info{&pool};
     DevBuf refine_shift{&pool}, refine_stats{&pool};   // the per-component refinement pass
-    // self-normalising statistics passes (run_mstats): both kernels add the number of nonzero responsibilities to nz_dev, which
-    // is copied to slot sn_calls % 3 of nz_host; pass t chooses the sparse kernel from the count of pass t - 2 (in hand in every
-    // loop: mlhip_em_iterate has waited for iteration t - 2 before it launches t)
-    DevBuf nz_dev{&pool};
-    PinnedBuf nz_host{&pool};
-    uint64_t sn_calls = 0;
-    int sn_K = 0;
-    // screened E-step (em.cpp launch_estep, em_estep_screen.hip), kept only for passes that may screen: scr_rec -- the records the
-    // N x K block belongs to (a copy: the ring of mlhip_em_iterate and params_dev move on); scr_exact -- one word per sample, bit k =
-    // "the stored value of component k is an evaluated one" (scr_all_exact: a dense pass wrote the block, the words are not read);
-    // scr_consts -- 4 doubles per component; scr_dev -- [components without information (32 bits), padding | candidates]; scr_host --
-    // its pinned copy: [0] the first word, [1 + t % 3] the candidates of tracked pass t. scr_was[t % 3]: whether tracked pass t ran
-    // screened (t counts the passes that kept this state with this K: scr_passes). The last three: mlhip_em_screen_counts.
-    DevBuf scr_rec{&pool}, scr_exact{&pool}, scr_consts{&pool}, scr_dev{&pool};
-    PinnedBuf scr_host{&pool};
-    bool scr_all_exact = true;
-    int scr_K = 0;
-    uint64_t scr_passes = 0;
-    bool scr_was[3] = {false, false, false};
-    uint64_t scr_n_screened = 0, scr_n_dense = 0, scr_n_no_info = 0;
+    // The pass history behind the two history-dependent route choices of a fit (pass_history.hpp): both keep running across calls,
+    // and so across the restarts of mlhip_em_iterate_restarts, and start again only with another K; a weighted block enters neither
+    // (route.cpp forces both choices off).
+    StatsHistory stats_history{&pool};
+    ScreenState screen{&pool};
     // K-means workspace
     DevBuf km_labels[2] = {DevBuf{&pool}, DevBuf{&pool}};
     DevBuf km_cent{&pool}, km_cent_next{&pool}, km_partials{&pool}, km_out{&pool}, km_mind{&pool}, km_probe{&pool}, km_scale{&pool},
@@ -833,7 +883,7 @@ RecordForm prepare_estep(mlhip_data* dt, const EmRoute& r, int K, const double* 
 /// `records` / `fold`: another record buffer than params_dev and its form (mlhip_em_iterate keeps a ring of them); default: params_dev
 /// and its form.
 /// `may_screen`: a pass of a fit (mlhip_em_step, mlhip_em_iterate) -- the only ones that may take the screened kernel instead
-/// (em_estep_screen.hip; the rule is launch_estep's); rebuilds for labels / responsibilities, scoring, conditioning and restarts never do.
+/// (em_estep_screen.hip; the rule is screen_wanted's, pass_history.hpp); rebuilds for labels / responsibilities, scoring, conditioning and restarts never do.
 void launch_estep(mlhip_data* dt, const EmRoute& r, int K, bool with_lse = true, const DevBuf* records = nullptr, int fold = -1,
                   bool may_screen = false);
 
@@ -929,8 +979,6 @@ void km_close_host(const double* r, int K, int d, double* counts, double* centro
 /// `weighted`: every trip is a weighted step (km_launch); never the resident one-launch loop.
 void km_iterate(mlhip_data* dt, const KmRoute& route, int K, double* centroids, double* old_centroids, uint32_t max_steps, double atol,
                 uint32_t* steps_done, int* converged, double* inertia, double* counts, bool weighted = false);
-
-bool mstats_sparse_applies(mlhip_data* dt, const EmRoute& r, int K);
 
 /// The covariance array of `mode` as K full covariance matrices (host::covariances_as_full).
 std::vector<double> as_full(Covariance mode, int K, int d, const double* covariance);

@@ -6,9 +6,9 @@ library itself on a handle without a past, which the extended-precision suites h
 "call name [output index]" strings are collected and asserted once at the end of a case.
 
 What outlives a call on a handle (runtime/internal.hpp, mlhip_data and EstepState) and could leak into the
-next one: estep.what / kept / screenable, the screened E-step's records and pass history (scr_rec, scr_exact, scr_all_exact, scr_K,
-scr_passes, scr_was), the statistics pass's history (sn_calls, sn_K, nz_host), total_scatter, km_wfactors_valid / km_colmax, weighted /
-weight_sum / ridge, rs_kept and the params_dev / params_next / params_prev ring.
+next one: estep.what / kept / screenable, the screened E-step's records and pass history (screen: ScreenState), the statistics
+pass's history (stats_history: StatsHistory), total_scatter, km_wfactors_valid / km_colmax, weighted / weight_sum / ridge, rs_kept and
+the params_dev / params_next / params_prev ring.
 
 Settings that are MEANT to persist. Weights and ridge are handle settings, not leaks: every compared call declares the weights (None
 or a named vector) and the ridge (None: the default) it runs under. The fresh handle is always given them; the used handle only when

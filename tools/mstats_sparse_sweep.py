@@ -3,7 +3,7 @@
 nonzero responsibilities per sample go from ~2 up to 64. For each mixture one forced-sparse and one forced-dense statistics pass
 (MLHIP_MSTATS_SPARSE=1 / 0), timed by the library's own `em_mstats` timer (Context.timing_get), and the nonzero count of the
 pass from the responsibilities themselves. Prints nonzeros per sample against both times; the crossover is where the threshold
-kSparseMaxPairs (runtime/em.cpp) belongs, just below.
+kSparseMaxPairs (runtime/pass_history.hpp) belongs, just below.
     usage: python tools/mstats_sparse_sweep.py [--n 2500000] [--repeats 3] > profiles/mstats_sparse3_sweep.txt"""
 import argparse
 import os
