@@ -28,11 +28,17 @@
 //     group are gathered from the tile into the B operand of v_mfma_f64_4x4x4_4b (lane layout as
 //     in em_estep_mfma4.hip) and run through the dense kernel's chain: y_{4R+i} over C = 0 .. R ascending from the initialiser
 //     -W (mu - s), a_i = fma(y, y, a_i) over R ascending from 0, q = (a_0 + a_1) + (a_2 + a_3), lw = fma(-0.5, q, coef). Entries past
-//     the end of a bucket read the sentinel row behind the tile and store nothing.
+//     the end of a bucket read the sentinel row behind the tile and store nothing. A step takes 32 entries of the bucket as TWO
+//     groups that share each read of the record and run as two accumulator chains; a step with at most 16 entries left runs one
+//     group. The record's reads of row quad R + 1 are issued before the matrix instructions of row quad R (scheduling fences keep
+//     them there), an entry's segment is found without a branch, and the two cross-lane adds of q are v_permlane16_swap and
+//     v_permlane32_swap, not trips through LDS. The next tile's coordinates a tile ahead at D = 28 and 32 fit the registers in this
+//     form and were measured slower; they stay loaded at the head of their own tile (DESIGN 3.3p "Two groups a step").
 // The constants kernel (one wave per component) also counts the components whose bound carries no information; the runtime reads the
 // count and runs the dense kernel instead when it is not 0 (runtime/em.cpp).
 #include "device.hpp"
 #include "em_screen_bound.hpp"
+#include <type_traits>
 
 namespace mlhip {
 namespace {
@@ -57,6 +63,25 @@ template <int D> struct ScreenBlocks {
     static constexpr int PS = NB * 16 + 2 * D + 1;                       // layout.hpp estep_mfma4_param_stride
     static constexpr int slot(int R, int C) { return C * Q - C * (C - 1) / 2 + (R - C); }   // column-quad major
 };
+
+/// v + (v of lane ^ 16) on every lane, without a trip through LDS: v_permlane16_swap leaves rows 0, 0, 2, 2 of v in one register and
+/// rows 1, 1, 3, 3 in the other (a row: 16 lanes). The even row's value is the left operand, as in v + __shfl_xor(v, 16) on an even row.
+__device__ inline double rows_sum(double v)
+{
+    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+    const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+}
+
+/// v + (v of lane ^ 32) on every lane: v_permlane32_swap leaves the lower half of v twice in one register, the upper half in the other.
+__device__ inline double halves_sum(double v)
+{
+    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+    const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+}
 
 /// One wave per component: the dense lower triangles of W (old) and W' (new) out of the two records, row i of M = W' L on lane i.
 __global__ __launch_bounds__(64) void em_screen_constants_kernel(const double* __restrict__ rec_old, const double* __restrict__ rec_new,
@@ -135,7 +160,7 @@ __global__ __launch_bounds__(2 * ST, 2) void em_estep_screen_kernel(
     constexpr int SNW = T::NW, NSEG = T::NSEG;
     constexpr int NLD = (PS + 63) / 64;              // doubles of a record each lane moves to the wave's slot
     constexpr int DH = D / 2;                        // coordinates a thread stages
-    constexpr bool PFX = D <= 24;                    // the next tile's coordinates are loaded a tile ahead like its stored values (above: no registers for them)
+    constexpr bool PFX = D <= 24;                    // the next tile's coordinates are loaded a tile ahead like its stored values (at D = 28, 32 measured slower: DESIGN 3.3p)
     extern __shared__ __attribute__((aligned(16))) double smem[];
     double* Xs = smem;                               // [ST + 1][SXS]: x - shift, sample-major; row ST: the sentinel
     double* recs = Xs + (ST + 1) * SXS;              // [SNW][PS]: a record slot per wave
@@ -271,29 +296,65 @@ __global__ __launch_bounds__(2 * ST, 2) void em_estep_screen_kernel(
             const unsigned c0 = cnt[k], c1 = c0 + cnt[SKMAX + k];
             const unsigned c2 = NSEG == 4 ? c1 + cnt[(NSEG - 2) * SKMAX + k] : c1, total = NSEG == 4 ? c2 + cnt[(NSEG - 1) * SKMAX + k] : c1;
             const double coef = rec[NB * 16 + 2 * D];
-            for (unsigned first = 0; first < total; first += 16) {
-                const unsigned e = first + s;
-                const bool valid = e < total;
-                const unsigned w = valid ? (e >= c0 ? 1u : 0u) + (e >= c1 ? 1u : 0u) + (e >= c2 ? 1u : 0u) : 0u;   // the entry's segment, < NSEG
-                const unsigned pos = valid ? e - (w == 0 ? 0u : w == 1 ? c0 : w == 2 ? c1 : c2) : 0u;   // < 64: a segment holds 64 samples
-                const unsigned smp = valid ? (unsigned)list[((unsigned)k * NSEG + w) * 64 + (pos & 63u)] : (unsigned)ST;
-                const double* xrow = Xs + smp * SXS + g;
-                double xb[Q];
+            // A step of NG groups: lane s of lane group g serves the entries first + 16 i + s, i < NG. The groups share every read of the
+            // record and run as NG accumulator chains. The record's reads run one row quad ahead of the matrix instructions that use
+            // them, between scheduling fences: left to itself the compiler reads the whole record first, and two groups' operands
+            // beside it do not fit the registers (DESIGN 3.3p "Two groups a step").
+            auto step = [&](unsigned first, auto groups) {
+                constexpr int NG = decltype(groups)::value;
+                double a[Q][Q], ini[Q];
+                auto load_quad = [&](int R) {
+                    ini[R] = rec[NB * 16 + D + 4 * R + g];               // -W (mu - shift), rows 4R .. 4R + 3
 #pragma unroll
-                for (int C = 0; C < Q; ++C) xb[C] = xrow[4 * C];
-                double qs = 0.0;
+                    for (int C = 0; C <= R; ++C) a[R][C] = rec[B::slot(R, C) * 16 + aoff];
+                };
+                load_quad(0);
+                bool valid[NG];
+                unsigned smp[NG];
+                double xb[NG][Q], qs[NG];
+#pragma unroll
+                for (int i = 0; i < NG; ++i) {
+                    const unsigned e = first + 16u * i + s;
+                    valid[i] = e < total;
+                    // the entry's segment (< NSEG when valid) and where that segment starts in the bucket, without a branch
+                    const unsigned w = (e >= c0 ? 1u : 0u) + (e >= c1 ? 1u : 0u) + (e >= c2 ? 1u : 0u);
+                    unsigned base = e >= c0 ? c0 : 0u;
+                    base = e >= c1 ? c1 : base;
+                    base = e >= c2 ? c2 : base;
+                    const unsigned at = ((unsigned)k * NSEG + (w & (NSEG - 1))) * 64 + ((e - base) & 63u);   // inside the component's lists
+                    smp[i] = valid[i] ? (unsigned)list[at] : (unsigned)ST;
+                    const double* xrow = Xs + smp[i] * SXS + g;
+#pragma unroll
+                    for (int C = 0; C < Q; ++C) xb[i][C] = xrow[4 * C];
+                    qs[i] = 0.0;
+                }
 #pragma unroll
                 for (int R = 0; R < Q; ++R) {
-                    double acc = rec[NB * 16 + D + 4 * R + g];            // -W (mu - shift), rows 4R .. 4R + 3
+                    if (R + 1 < Q) load_quad(R + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    double acc[NG];
+#pragma unroll
+                    for (int i = 0; i < NG; ++i) acc[i] = ini[R];
 #pragma unroll
                     for (int C = 0; C <= R; ++C)
-                        acc = __builtin_amdgcn_mfma_f64_4x4x4f64(rec[B::slot(R, C) * 16 + aoff], xb[C], acc, 0, 0, 0);
-                    qs = __builtin_fma(acc, acc, qs);
+#pragma unroll
+                        for (int i = 0; i < NG; ++i) acc[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[R][C], xb[i][C], acc[i], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < NG; ++i) qs[i] = __builtin_fma(acc[i], acc[i], qs[i]);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-                // the four lane groups hold the four row residues a_0 .. a_3 of the same 16 samples: q = (a_0 + a_1) + (a_2 + a_3)
-                const double t = qs + __shfl_xor(qs, 16, 64);
-                const double q = t + __shfl_xor(t, 32, 64);
-                if (valid && g == 0) lw[(size_t)k * ldr + (size_t)tile * ST + smp] = __builtin_fma(-0.5, q, coef);
+#pragma unroll
+                for (int i = 0; i < NG; ++i) {
+                    // the four lane groups hold the four row residues a_0 .. a_3 of the same 16 samples: q = (a_0 + a_1) + (a_2 + a_3)
+                    const double q = halves_sum(rows_sum(qs[i]));
+                    if (valid[i] && g == 0) lw[(size_t)k * ldr + (size_t)tile * ST + smp[i]] = __builtin_fma(-0.5, q, coef);
+                }
+            };
+            for (unsigned first = 0; first < total; first += 32) {
+                if (total - first <= 16)                                 // (wave-uniform)
+                    step(first, std::integral_constant<int, 1>{});       // a lone group: a second chain would be matrix work for nothing
+                else
+                    step(first, std::integral_constant<int, 2>{});
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // every lane is done with the slot before the next record goes in
             __builtin_amdgcn_wave_barrier();
