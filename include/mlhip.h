@@ -161,11 +161,12 @@ int mlhip_data_weight_sum(const mlhip_data* data, double* total);
  * _maximisation_from_labels and the refinement pass about a component's own mean: one plain fp64 add per diagonal entry on every
  * route, so two routes that agree bit for bit at the default agree bit for bit at any r. r finite and >= 0 (-0.0 counts as 0; r = 0 adds
  * 0.0); NaN, an infinity or a negative value: MLHIP_E_INVALID_ARGUMENT and the handle keeps its ridge. The default keeps the
- * reference's bits. NOT touched: parameters a caller GIVES (the first E-step, mlhip_em_expectation, mlhip_em_score use them as they
- * are), mlhip_sample_covariance, the kernel routes (mlhip_em_route / _tied_route / _score_route report what they reported). Setting
- * the ridge drops nothing the handle holds: E-step results stay valid. A device group's handle passes the value to every shard's
- * part and mirrors it. In a multi-process job every rank sets its own handle; nothing is all-reduced (ranks that disagree fail the
- * end-of-fit checksum exchange of mlhip_em_iterate). */
+ * reference's bits. The ridge is ABSOLUTE, in squared data units (at a uniform data scale of 2^-30 the default dominates every
+ * variance): where that matters the caller scales it with the data. NOT touched: parameters a caller GIVES (the first E-step,
+ * mlhip_em_expectation, mlhip_em_score use them as they are), mlhip_sample_covariance, the kernel routes (mlhip_em_route / _tied_route /
+ * _score_route report what they reported). Setting the ridge drops nothing the handle holds: E-step results stay valid. A device group's
+ * handle passes the value to every shard's part and mirrors it. In a multi-process job every rank sets its own handle; nothing is
+ * all-reduced (ranks that disagree fail the end-of-fit checksum exchange of mlhip_em_iterate). */
 #define MLHIP_DEFAULT_COVARIANCE_RIDGE 1e-15
 int mlhip_data_set_covariance_ridge(mlhip_ctx* ctx, mlhip_data* data, double ridge);
 int mlhip_data_covariance_ridge(const mlhip_data* data, double* ridge);

@@ -572,7 +572,7 @@ void launch_em_responsibilities(const RespArgs& a, hipStream_t stream);
 struct KmeansArgs {
     const double* xt; size_t ldx; uint32_t n; int D; int d;
     const double* centroids; int K;            // device, [K][D] (padded coordinates zero)
-    const double* scale;                       // device, d doubles: per-dimension power-of-two scale of the exact sums
+    const double* scale;                       // device, 2 d doubles: per-dimension power-of-two scale of the exact sums, as two factors [f1 (d) | f2 (d)]
     uint32_t* labels; const uint32_t* old_labels; int have_old;
     double* min_dist;                          // out (may be null): per-sample min squared distance
     int accumulate;                            // also accumulate per-cluster sums / counts
@@ -598,7 +598,7 @@ constexpr int kKmResidentMaxN = 4096, kKmResidentMaxK = 32;
 struct KmResidentArgs {
     const double* xt; size_t ldx; uint32_t n; int D, d, K;
     double* cent;                              // device, [K][D]: the starting table in, the final one out
-    const double* scale;                       // device, d doubles (as KmeansArgs)
+    const double* scale;                       // device, 2 d doubles (as KmeansArgs)
     uint32_t* labels[2]; int label_buf, have_old;   // the two label buffers, which one holds the assignment before, whether it does
     double* min_dist;
     uint32_t max_steps; double atol;

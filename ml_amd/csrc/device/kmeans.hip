@@ -10,7 +10,8 @@
 // used: its cancellation can flip labels of nearly equidistant samples.
 //
 // Update statistics (per-cluster coordinate sums and counts) are accumulated EXACTLY: every coordinate is scaled by a
-// per-dimension power of two (chosen at upload from max|x_j| so that |t| < 2^94), cut into three 32-bit limbs and added
+// per-dimension power of two (chosen at upload from max|x_j| so that |t| < 2^94, and applied as two factors so that a column of
+// any finite magnitude, subnormal included, has a finite scale: KmeansArgs::scale), cut into three 32-bit limbs and added
 // with 64-bit INTEGER atomics (ds_add_u64 on workgroup-private LDS accumulators, or global atomics when K*(3d+1)
 // words do not fit). Integer addition is associative, so the sums do not depend on the order in which lanes, waves,
 // workgroups or GPUs contribute: the update step is bitwise reproducible run to run (floating-point atomics are not),
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(BS) void kmeans_assign_kernel(
             u64* row = (USE_LDS ? acc_lds + (size_t)(tid & (copies - 1)) * K * W : my_words) + (size_t)arg * W;
 #pragma unroll
             for (int j = 0; j < D; ++j) {
-                if (j < d) add_limbs(row, j, x[j] * sc[j]);
+                if (j < d) add_limbs(row, j, (x[j] * sc[j]) * scale[d + j]);   // (the second factor: wave-uniform index, scalar load)
             }
             atomicAdd(row + 3 * d, (u64)1);
         }
@@ -200,7 +201,7 @@ __global__ __launch_bounds__(BSU) void kmeans_update_kernel(
                             const double p = wi * x;
                             add_limbs(row, j, (p * scale[j0 + j]) * scale2[j0 + j]);
                         } else {
-                            add_limbs(row, j, x * scale[j0 + j]);
+                            add_limbs(row, j, (x * scale[j0 + j]) * scale2[j0 + j]);
                         }
                     }
                     if (j0 == 0) {
@@ -243,7 +244,8 @@ inline SweepChunks sweep_chunks(int K, int d, size_t budget, int count_words)
 /// One output element of [inertia, n_changed, counts(K), sums(K*d)] by one wave, the lanes striding over the per-workgroup partial blocks
 /// four at a time (round 5: the loads of a trip in flight together -- 11.8 -> ... us at K = 256, d = 8 over 512 blocks). inertia / changed:
 /// lane-strided partial sums combined by a shuffle tree (a fixed order for a given number of partials); counts and coordinate sums:
-/// exact integer sums of the limb words (order-free), converted to double once and divided by their scale.
+/// exact integer sums of the limb words (order-free), converted to double once and divided by their scale (its two factors: the
+/// second, then the first).
 /// WEIGHTED: the blocks of the weighted sweep -- the count is three limbs like a sum, `scale` holds the two factors of every scale
 /// (divided out in that order: the second, then the first), and out[1] (n_changed: a count of rows, written by the assignment's own
 /// reduction) is left alone.
@@ -303,7 +305,7 @@ __device__ __forceinline__ void kmeans_reduce_element(const double* __restrict__
             if (lane == 0) {
                 const double v = limbs_to_double(w0, w1, w2);
                 double* sum = j == d ? out + 2 + k : out + 2 + K + (size_t)k * d + j;
-                if (!WEIGHTED) *sum = v / scale[j];
+                if (!WEIGHTED) *sum = (v / scale[d + j]) / scale[j];
                 else *sum = (v / scale[(j == d ? 2 * d + 1 : d + j)]) / scale[(j == d ? 2 * d : j)];
             }
         }

@@ -33,8 +33,10 @@ namespace {
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr int BSM = 512;   // threads per workgroup (8 waves; two workgroups per CU)
-/// Score of the rows that pad K to a multiple of 16: finite (a tag inserted into -inf's mantissa would make it a NaN),
-/// below every real score (|score| <= |x|^2 + max|c|^2 overflows long before it gets here).
+/// Score of the rows that pad K to a multiple of 16: finite (a tag inserted into -inf's mantissa would make it a NaN) and below
+/// every real score of data whose squares are of ordinary size. It is NOT below every real score: x . c - |c|^2 / 2 reaches
+/// -2^1021 while every direct-form distance is still finite (|c_k|^2 up to 2^1022), so a padding row can hold the best score with a
+/// clear gap. The exact phase therefore calls a winner with index >= K ambiguous, and the full scan decides.
 constexpr double kPadScore = -0x1p1020;
 constexpr int kQuadFactor = 16;   // quad tracking for K >= kQuadFactor * D (and D <= kRegDim)
 
@@ -403,7 +405,8 @@ __global__ __launch_bounds__(BSM, (D <= 16) ? 4 : 2) void kmeans_mfma_kernel(
                     const double t = v - c[j];
                     dist = __builtin_fma(t, t, dist);
                 }
-                certain = (my_best - my_second) > err_unit * (xn + cmax2);          // false for NaN / inf as well
+                // (false for NaN / inf as well; a padding row that won -- see kPadScore -- is never certain)
+                certain = (uint32_t)my_idx < (uint32_t)K && (my_best - my_second) > err_unit * (xn + cmax2);
             }
             if (!certain) {
                 // ambiguous: the reference's own loop (ML/KMeans.cpp:155-163)
@@ -430,7 +433,7 @@ __global__ __launch_bounds__(BSM, (D <= 16) ? 4 : 2) void kmeans_mfma_kernel(
                 u64* row = (USE_LDS ? acc_lds : my_words) + (size_t)arg * W;
 #pragma unroll kExactUnroll
                 for (int j = 0; j < D; ++j) {
-                    if (j < d) add_limbs(row, j, x(j) * scale[j]);   // wave-uniform index: scalar load
+                    if (j < d) add_limbs(row, j, (x(j) * scale[j]) * scale[d + j]);   // wave-uniform indices: scalar loads
                 }
                 atomicAdd(row + 3 * d, (u64)1);
             }

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(RBS) void kmeans_resident_kernel(KmResidentArgs a)
                     u64* row = acc_lds + (size_t)(tid & (copies - 1)) * K * W + (size_t)arg * W;
 #pragma unroll
                     for (int j = 0; j < D; ++j) {
-                        if (j < d) add_limbs(row, j, x[b][j] * sc[j]);
+                        if (j < d) add_limbs(row, j, (x[b][j] * sc[j]) * a.scale[d + j]);
                     }
                     atomicAdd(row + 3 * d, (u64)1);
                 }
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(RBS) void kmeans_resident_kernel(KmResidentArgs a)
                     w1 += p[1];
                     w2 += p[2];
                 }
-                const double sum = limbs_to_double(w0, w1, w2) / a.scale[j];
+                const double sum = (limbs_to_double(w0, w1, w2) / a.scale[d + j]) / a.scale[j];
                 const double c = cnt[k];
                 v = c > 0 ? sum / c : 0.0;                  // (empty cluster -> origin, ML/KMeans.cpp:184)
             }

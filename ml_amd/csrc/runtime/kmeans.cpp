@@ -14,7 +14,9 @@ void ensure_km_workspace(mlhip_data* dt, int K)
     for (int b = 0; b < 2; ++b) dt->km_labels[b].reserve(sizeof(uint32_t) * dt->n_pad);
     dt->km_mind.reserve(sizeof(double) * dt->n_pad);
     if (!dt->km_scale.p) {
-        // Per-dimension power-of-two scale of the exact fixed-point sums: |x_j| * scale_j < 2^94 (device/kmeans.hip).
+        // Per-dimension power-of-two scale of the exact fixed-point sums: |x_j| * 2^(94 - e_j) < 2^94 (device/kmeans.hip), applied
+        // as two powers of two [f1 (d) | f2 (d)] so that neither step leaves the normal range whatever the column's magnitude is
+        // (94 - e_j reaches 1167 on a column of subnormals: one factor would be +inf from max|x_j| < 2^-929 down).
         DevBuf scratch, mx;
         scratch.reserve(sizeof(double) * 1024 * dt->d);
         mx.reserve(sizeof(double) * dt->d);
@@ -31,15 +33,18 @@ void ensure_km_workspace(mlhip_data* dt, int K)
             if (!(v <= mj)) mj = v;                                        // (keeps a NaN / inf of any rank)
         }
         dt->km_colmax = m;                                       // (the weighted sums' overflow test: ensure_km_weighted)
+        std::vector<double> f(2 * (size_t)dt->d);
         for (int j = 0; j < dt->d; ++j) {
             if (!std::isfinite(m[j]))
                 throw DomainError("K-means: the data contain non-finite values (the exact fixed-point update sums need finite coordinates)");
             int e = 0;
             if (m[j] > 0) (void)std::frexp(m[j], &e);   // m < 2^e
-            m[j] = std::ldexp(1.0, 94 - e);
+            const int E = 94 - e, h = E >= 0 ? E / 2 : -((-E) / 2);
+            f[j] = std::ldexp(1.0, h);
+            f[(size_t)dt->d + j] = std::ldexp(1.0, E - h);
         }
-        dt->km_scale.reserve(sizeof(double) * dt->d);
-        HIP_CHECK(hipMemcpyAsync(dt->km_scale.p, m.data(), sizeof(double) * dt->d, hipMemcpyHostToDevice, ctx->stream));
+        dt->km_scale.reserve(sizeof(double) * f.size());
+        HIP_CHECK(hipMemcpyAsync(dt->km_scale.p, f.data(), sizeof(double) * f.size(), hipMemcpyHostToDevice, ctx->stream));
         ctx->sync();
     }
     const int Dp = (dt->D + 3) & ~3;                              // (the K-means kernels may run on a zero-padded copy)

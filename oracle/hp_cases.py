@@ -458,7 +458,7 @@ def ill_problem(d, K, n, cond, seed=7, sep=1.0, offset=1.5):
     return np.ascontiguousarray(X + offset), pi0, centres + offset, np.stack([S_heavy] + [S1] * (K - 1))
 
 
-def _whitening_fp64(S):
+def whitening_fp64(S):
     """(L, W = L^-1) of one covariance in fp64: the left-looking Cholesky loops and the forward substitution of host/em_math.cpp
     -- every entry receives its terms in ascending l, one product and one subtraction at a time --, vectorised over the row index
     (the factor) and over the column of W."""
@@ -484,7 +484,7 @@ def _whitened_log_weights_fp64(X, pi, mu, S):
     n, d = X.shape
     lw = np.empty((n, len(pi)))
     for k in range(len(pi)):
-        L, W = _whitening_fp64(S[k])
+        L, W = whitening_fp64(S[k])
         c = X - mu[k]
         q = np.zeros(n)
         for i in range(d):

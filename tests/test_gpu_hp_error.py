@@ -23,7 +23,7 @@ import pytest
 
 from oracle import hp_reference as hp
 from oracle.hp_cases import KMEANS_SHAPES, edge_problem, oracle_step, problem, refinement_problem
-from hp_limits import FLOOR, FOLD_BOUND, _errors, _report_and_check, _ridge_off
+from hp_limits import FLOOR, FOLD_BOUND, _check_kmeans, _errors, _fsum_centroids, _report_and_check, _ridge_off
 
 pytestmark = pytest.mark.gpu
 
@@ -324,40 +324,6 @@ def test_diag_guard_sweep(ctx, oracle, monkeypatch, factor):
 
 
 # ---- K-means ---------------------------------------------------------------------------------------------------------------
-
-def _fsum_centroids(X, labels, K):
-    out = np.zeros((K, X.shape[1]))
-    for k in range(K):
-        sel = X[labels == k]
-        if len(sel):
-            out[k] = [math.fsum(sel[:, j]) / len(sel) for j in range(X.shape[1])]
-    return out
-
-
-def _check_kmeans(name, X, C0, got, labels, dists, ref, km):
-    """Labels on every row the reference separates by more than 64 * 2^-53 * dist (the oracle is held to the same); distances and
-    centroids against the reference at the rounding level, the inertia with the oracle's error as the yardstick; the update sums
-    against math.fsum over the GPU's own labels."""
-    inertia, _, counts, C1 = got
-    dist, label, margin, ref_inertia, ref_counts, ref_new = ref
-    safe = margin > 64 * hp.EPS64 * dist
-    assert safe.mean() >= 0.999, safe.mean()                         # (a condition on the data, checked on the CPU too)
-    assert np.array_equal(labels[safe], label[safe])
-    assert np.array_equal(km.labels[safe], label[safe])
-    same = np.array_equal(labels, label)
-    e_dist = hp.rel_err(dists[safe], dist[safe])
-    e_in, c_in = abs(float((LD(inertia) - ref_inertia) / ref_inertia)), abs(float((LD(km.inertia) - ref_inertia) / ref_inertia))
-    K = C0.shape[0]
-    exact = _fsum_centroids(X, labels, K)
-    e_sum = float(np.max(np.abs(C1 - exact) / np.maximum(np.abs(exact), 1e-300)))       # per entry: the sums are exact
-    print(f"HPERR {name} | left out {int((~safe).sum())} of {len(safe)} rows | labels == reference on all rows: {same} | "
-          f"distances {e_dist:.1e} | inertia {e_in:.1e} / {c_in:.1e} | centroids vs fsum {e_sum:.1e}", flush=True)
-    assert np.array_equal(counts, np.bincount(labels, minlength=K).astype(float))
-    assert e_dist <= 4 * FLOOR and e_in <= 4 * max(c_in, FLOOR)
-    assert e_sum <= 4e-16                                            # (the existing exactness test's bound)
-    if same:
-        assert np.array_equal(counts, ref_counts.astype(float)) and hp.rel_err(C1, ref_new) <= 4 * FLOOR
-
 
 def _scaled(X):
     """Columns of different scale and offset (as test_kmeans_update_is_bitwise_reproducible_and_exact)."""
