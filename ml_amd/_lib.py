@@ -1,7 +1,8 @@
 """ctypes binding of the C ABI (include/mlhip.h). Loads ml_amd/libmlhip.so; never falls back to anything else."""
 import ctypes as C
-import weakref
 import os
+import re
+import weakref
 
 import numpy as np
 
@@ -46,20 +47,65 @@ c_dp = C.POINTER(C.c_double)
 c_u32p = C.POINTER(C.c_uint32)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
-lib.mlhip_last_error.restype = C.c_char_p
-lib.mlhip_version.restype = C.c_char_p
-
 DEFAULT_COVARIANCE_RIDGE = 1e-15      # MLHIP_DEFAULT_COVARIANCE_RIDGE
-# the covariance ridge's entry points take doubles by value: prototypes, so that a Python float converts by itself
-lib.mlhip_data_set_covariance_ridge.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
-lib.mlhip_data_covariance_ridge.argtypes = [C.c_void_p, c_dp]
-lib.mlhip_em_finalize_statistics_ridge.argtypes = [C.c_uint32, C.c_uint32, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp, c_dp]
-lib.mlhip_em_finalize_statistics_tied_ridge.argtypes = [C.c_uint32, C.c_uint32, c_dp, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp, c_dp]
-lib.mlpp_em_set_covariance_regularisation.argtypes = [C.c_void_p, C.c_double]
-lib.mlpp_em_covariance_regularisation.argtypes = [C.c_void_p, c_dp]
-for _name in ("mlhip_data_set_covariance_ridge", "mlhip_data_covariance_ridge", "mlhip_em_finalize_statistics_ridge",
-              "mlhip_em_finalize_statistics_tied_ridge", "mlpp_em_set_covariance_regularisation", "mlpp_em_covariance_regularisation"):
-    getattr(lib, _name).restype = C.c_int
+
+
+class EmRouteInfo(C.Structure):
+    """mlhip_em_route_info"""
+    _fields_ = [(name, C.c_int32) for name in ("estep", "fused", "fused_form", "self_norm", "sparse", "balanced", "fold_allowed",
+                                               "diag_kernel", "diag_exact", "device_close", "records_on_device", "resident")]
+
+
+class KmeansRouteInfo(C.Structure):
+    """mlhip_kmeans_route_info"""
+    _fields_ = [(name, C.c_int32) for name in ("kernel", "pad", "resident")]
+
+
+# ---- prototypes: read from the headers, so that every call converts its arguments as the C declaration says ----------------
+_SCALARS = {"int": C.c_int, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "int64_t": C.c_int64, "size_t": C.c_size_t,
+            "double": C.c_double}
+_OPAQUE = ("void", "mlhip_ctx", "mlhip_data", "mlpp_em", "mlpp_kmeans", "mlpp_centroids_initialiser", "mlpp_responsibilities_initialiser")
+_STRUCTS = {"mlhip_em_route_info": EmRouteInfo, "mlhip_kmeans_route_info": KmeansRouteInfo}
+_RETURNS = {"int": C.c_int, "const char*": C.c_char_p}
+
+
+def _ctype(spelling):
+    """The ctypes type of a parameter type as the headers spell it ('const double*', 'uint64_t[4]'); None outside their vocabulary."""
+    if spelling in ("const char*", "const char**"):
+        return C.c_char_p if spelling.endswith("r*") else C.POINTER(C.c_char_p)
+    base = re.sub(r"\[\d+\]$", "*", spelling.replace("const ", "").replace("struct ", ""))
+    base, stars = base.rstrip("*"), len(base) - len(base.rstrip("*"))
+    if base in _SCALARS and stars <= 1:
+        return C.POINTER(_SCALARS[base]) if stars else _SCALARS[base]
+    if base in _OPAQUE and 1 <= stars <= 2:
+        return C.c_void_p
+    if base in _STRUCTS and stars == 1:
+        return C.POINTER(_STRUCTS[base])
+    return ALLREDUCE_FN if spelling == "mlhip_allreduce_fn" else None
+
+
+def _prototypes(text):
+    """{function: (restype, argtypes)} for every function a header's text declares. ImportError for a type outside the table above:
+    no declaration is passed over, so no function goes without a prototype."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                                    # comments
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)                               # preprocessor lines
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;|typedef[^;{]*;", "", text, flags=re.S)   # the structs, the hook's type
+    found = {}
+    for returns, name, parameters in re.findall(r"([\w \t*]+?)\s*\b(ml(?:hip|pp)_\w+)\s*\(([^()]*)\)\s*;", text):
+        spellings = [returns] + ([] if parameters.strip() == "void" else parameters.split(","))
+        spellings = [re.sub(r"\s*\*", "*", " ".join(s.split())) for s in spellings]
+        spellings[1:] = [re.sub(r"\s*\b\w+(\[\d+\])?$", r"\1", s) for s in spellings[1:]]   # without the parameter's name
+        types = [_RETURNS.get(spellings[0])] + [_ctype(s) for s in spellings[1:]]
+        if None in types:
+            raise ImportError(f"{name}: no ctypes type for '{spellings[types.index(None)]}' (ml_amd/_lib.py, _ctype)")
+        found[name] = (types[0], types[1:])
+    return found
+
+
+for _header in ("mlhip.h", "mlpp_c.h"):
+    with open(os.path.join(os.path.dirname(_HERE), "include", _header)) as _f:
+        for _name, (_restype, _argtypes) in _prototypes(_f.read()).items():
+            getattr(lib, _name).restype, getattr(lib, _name).argtypes = _restype, _argtypes
 
 
 class MlhipError(RuntimeError):
@@ -84,11 +130,107 @@ def check(rc):
 
 
 def dptr(a):
-    return a.ctypes.data_as(c_dp)
+    """The array's memory as double* (None, an output not asked for, stays None: NULL)."""
+    return None if a is None else a.ctypes.data_as(c_dp)
 
 
 def u32ptr(a):
-    return a.ctypes.data_as(c_u32p)
+    return None if a is None else a.ctypes.data_as(c_u32p)
+
+
+def _float64_copy(a, dtype=np.float64):
+    return np.array(a, dtype=dtype, order="C")
+
+
+def _float64(a, copy=False):
+    return _float64_copy(a) if copy else np.ascontiguousarray(a, np.float64)
+
+
+def _shape_error(name, a, shape):
+    return ValueError(f"{name} has shape {a.shape}, expected {shape}")
+
+
+def _require_shape(name, a, *shape):
+    if a.shape != shape:
+        raise _shape_error(name, a, shape)
+
+
+def _is_block(x):
+    """What every call that takes rows of data accepts as they are: a C-contiguous float64 N x d numpy array, never converted."""
+    return isinstance(x, np.ndarray) and x.dtype == np.float64 and x.ndim == 2 and x.flags.c_contiguous
+
+
+def _covariance_shape(K, d, diagonal, tied):
+    if diagonal and tied:
+        raise ValueError("diagonal and tied exclude each other")
+    return (d, d) if tied else (K, d) if diagonal else (K, d, d)
+
+
+def mixture_arguments(mixing, means, covs, diagonal=False, tied=False, d=None, copy=False, restarts=False):
+    """The parameters of a mixture as the library takes them, checked before any call: (K, d, covariance_type, mixing, means, covs),
+    the arrays C-contiguous float64 (copy=True: fresh copies, for the calls that update them in place), covariance_type 0 full /
+    1 diagonal / 2 tied. mixing: K (None for a call that takes none: K is then the number of rows of means); means: K x d; covs:
+    K x d x d, K x d with diagonal=True, d x d with tied=True; restarts=True: each under one leading axis R. d: the dimension they
+    must have (a block's). ValueError names the array, its shape and the shape expected."""
+    convert = _float64_copy if copy else np.ascontiguousarray           # (kept lean: this runs before every step call)
+    means, covs = convert(means, np.float64), convert(covs, np.float64)
+    if mixing is None:
+        head = means.shape[:-1]
+    else:
+        mixing = convert(mixing, np.float64)
+        head = mixing.shape                                             # (K,), or (R, K) with restarts
+    if len(head) != (2 if restarts else 1):
+        lead = "(R, K" if restarts else "(K"
+        raise ValueError(f"means has shape {means.shape}, expected {lead}, d)" if mixing is None else
+                         f"mixing has shape {head}, expected {lead}{')' if restarts else ',)'}")
+    K = head[-1]
+    if d is None:
+        d = means.shape[-1] if means.ndim else 0
+    if means.shape != head + (d,):
+        raise _shape_error("means", means, head + (d,))
+    expected = head[:-1] + _covariance_shape(K, d, diagonal, tied)
+    if covs.shape != expected:
+        raise _shape_error("covs", covs, expected)
+    return K, d, 2 if tied else 1 if diagonal else 0, mixing, means, covs
+
+
+def conditioned_arguments(d_observed, mixing, means_observed, covs_observed, maps, means_missing, **extra):
+    """A conditioned mixture (what em_condition returns) as the five conditioning calls take it, checked before any call: (K, dM,
+    arrays), arrays the five and then `extra` in the order given, C-contiguous float64. d_observed: the dimension of the block of
+    observed coordinates. extra: factors, covs_missing (K x dM x dM), scales, inverse_scales (K x dM). ValueError names the array,
+    its shape and the shape expected."""
+    arrays = {name: _float64(a) for name, a in dict(mixing=mixing, means_observed=means_observed, covs_observed=covs_observed, maps=maps,
+                                                    means_missing=means_missing, **extra).items()}
+    if arrays["means_missing"].ndim != 2:
+        raise ValueError(f"means_missing has shape {arrays['means_missing'].shape}, expected (K, dM)")
+    K, dM = arrays["means_missing"].shape
+    shapes = dict(mixing=(K,), means_observed=(K, d_observed), covs_observed=(K, d_observed, d_observed), maps=(K, dM, d_observed),
+                  means_missing=(K, dM), factors=(K, dM, dM), covs_missing=(K, dM, dM), scales=(K, dM), inverse_scales=(K, dM))
+    if set(extra) - set(shapes):
+        raise TypeError(f"conditioned_arguments() got an unexpected keyword argument {sorted(set(extra) - set(shapes))[0]!r}")
+    for name, a in arrays.items():
+        _require_shape(name, a, *shapes[name])
+    return K, dM, list(arrays.values())
+
+
+def _route_name(fn, names, *args, after=()):
+    """The name of the route a `*_route` entry point reports: fn(*args, &route, *after)."""
+    route = C.c_int()
+    check(fn(*args, C.byref(route), *after))
+    return names[route.value]
+
+
+def _with_optional(out, *optional):
+    """`out`, or the tuple of it and the optional outputs that were asked for (not None), in the order given."""
+    extra = [v for v in optional if v is not None]
+    return (out, *extra) if extra else out
+
+
+def _get(fn, handle, ctype):
+    """A scalar the library returns through an out-pointer: fn(handle, &value)."""
+    v = ctype()
+    check(fn(handle, C.byref(v)))
+    return v.value
 
 
 def em_select_restart(log_likelihood, converged):
@@ -96,9 +238,11 @@ def em_select_restart(log_likelihood, converged):
     converged restarts, else among all; strict '>', so the first of equals; a NaN never wins, all NaN gives 0."""
     ll = np.ascontiguousarray(log_likelihood, dtype=np.float64)
     conv = np.ascontiguousarray(converged, dtype=np.int32)
-    assert ll.shape == conv.shape and ll.ndim == 1
+    if ll.ndim != 1:
+        raise ValueError(f"log_likelihood has shape {ll.shape}, expected (R,)")
+    _require_shape("converged", conv, *ll.shape)
     best = C.c_uint32()
-    check(lib.mlhip_em_select_restart(C.c_uint32(len(ll)), dptr(ll), conv.ctypes.data_as(C.POINTER(C.c_int)), C.byref(best)))
+    check(lib.mlhip_em_select_restart(len(ll), dptr(ll), conv.ctypes.data_as(C.POINTER(C.c_int)), C.byref(best)))
     return best.value
 
 
@@ -128,11 +272,16 @@ class Context:
     which Data uploads row-shard the caller's block and every call fans out (mlhip_ctx_create_group)."""
 
     def __init__(self, device_id=-1):
-        self._h = C.c_void_p()
+        self._fill(C.c_void_p(), True)
         check(lib.mlhip_ctx_create(int(device_id), C.byref(self._h)))
+
+    def _fill(self, handle, owned):
+        """The fields of a context, set here and nowhere else (__init__, group, borrow)."""
+        self._h = handle
         self._hook = None
-        self._owned = True
+        self._owned = owned
         self._blocks = weakref.WeakSet()      # live Data objects: they hold a pointer to this context
+        return self
 
     @classmethod
     def group(cls, n_shards=None, device_ids=None):
@@ -147,19 +296,13 @@ class Context:
         else:
             n_shards = device_count() if n_shards is None else int(n_shards)
             arr = None
-        self = cls.__new__(cls)
-        self._h = C.c_void_p()
-        self._hook = None
-        self._owned = True
-        self._blocks = weakref.WeakSet()
+        self = cls.__new__(cls)._fill(C.c_void_p(), True)
         check(lib.mlhip_ctx_create_group(n_shards, arr, C.byref(self._h)))
         return self
 
     @property
     def shards(self):
-        n = C.c_int()
-        check(lib.mlhip_ctx_shards(self._h, C.byref(n)))
-        return n.value
+        return _get(lib.mlhip_ctx_shards, self._h, C.c_int)
 
     @property
     def shard_devices(self):
@@ -173,19 +316,12 @@ class Context:
     @property
     def reduce_kind(self):
         """How the statistics are summed: none / hook-host / hook-device / rccl / group-rccl / group-direct."""
-        k = C.c_char_p()
-        check(lib.mlhip_ctx_reduce_kind(self._h, C.byref(k)))
-        return k.value.decode()
+        return _get(lib.mlhip_ctx_reduce_kind, self._h, C.c_char_p).decode()
 
     @classmethod
     def borrow(cls, handle):
         """Wraps a context owned by someone else (the C++ facade's process-wide one): close() leaves it alive."""
-        self = cls.__new__(cls)
-        self._h = C.c_void_p(handle) if not isinstance(handle, C.c_void_p) else handle
-        self._hook = None
-        self._owned = False
-        self._blocks = weakref.WeakSet()
-        return self
+        return cls.__new__(cls)._fill(handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle), False)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -204,15 +340,11 @@ class Context:
 
     @property
     def device(self):
-        d = C.c_int()
-        check(lib.mlhip_ctx_device(self._h, C.byref(d)))
-        return d.value
+        return _get(lib.mlhip_ctx_device, self._h, C.c_int)
 
     @property
     def stream(self):
-        s = C.c_void_p()
-        check(lib.mlhip_ctx_stream(self._h, C.byref(s)))
-        return s.value or 0
+        return _get(lib.mlhip_ctx_stream, self._h, C.c_void_p) or 0
 
     def synchronize(self):
         check(lib.mlhip_ctx_synchronize(self._h))
@@ -250,9 +382,7 @@ class Context:
     @property
     def rccl_ranks(self):
         """Ranks of the library-owned communicator as RCCL counts them (0: none)."""
-        n = C.c_int()
-        check(lib.mlhip_ctx_rccl_ranks(self._h, C.byref(n)))
-        return n.value
+        return _get(lib.mlhip_ctx_rccl_ranks, self._h, C.c_int)
 
     def finalize_rccl(self):
         check(lib.mlhip_ctx_finalize_rccl(self._h))
@@ -264,16 +394,10 @@ class Context:
         return w.value, r.value
 
     def _sample_arguments(self, mixing, means, covs, n, seed, first_row, diagonal, tied):
-        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-        means = np.ascontiguousarray(means, dtype=np.float64)
-        covs = np.ascontiguousarray(covs, dtype=np.float64)
-        assert not (diagonal and tied) and mixing.ndim == 1 and means.ndim == 2
-        K, d = means.shape
-        assert mixing.shape == (K,) and covs.shape == ((d, d) if tied else (K, d) if diagonal else (K, d, d))
+        K, d, mode, *keep = mixture_arguments(mixing, means, covs, diagonal, tied)
         if n < 0:
             raise ValueError("the number of rows must not be negative")
-        return (self._h, C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(mixing), dptr(means), dptr(covs),
-                C.c_uint64(seed), C.c_uint64(first_row), C.c_uint64(n)), (mixing, means, covs), d
+        return (self._h, d, K, mode, *map(dptr, keep), seed, first_row, n), keep, d
 
     def em_sample(self, mixing, means, covs, n, seed=0, first_row=0, diagonal=False, tied=False):
         """Rows [first_row, first_row + n) of the sample that `seed` and the mixture define, drawn on the device (mlhip_em_sample):
@@ -281,7 +405,7 @@ class Context:
         the one d x d matrix with tied=True). A row depends on (seed, its global index) only."""
         args, keep, d = self._sample_arguments(mixing, means, covs, n, seed, first_row, diagonal, tied)
         X, labels = np.empty((n, d)), np.empty(n, dtype=np.uint32)
-        check(lib.mlhip_em_sample(*args, dptr(X), C.c_int64(d), u32ptr(labels)))
+        check(lib.mlhip_em_sample(*args, dptr(X), d, u32ptr(labels)))
         return X, labels
 
     def em_sample_data(self, mixing, means, covs, n, seed=0, first_row=0, diagonal=False, tied=False):
@@ -314,17 +438,6 @@ def require_weights(w, n):
     return w
 
 
-class EmRouteInfo(C.Structure):
-    """mlhip_em_route_info"""
-    _fields_ = [(name, C.c_int32) for name in ("estep", "fused", "fused_form", "self_norm", "sparse", "balanced", "fold_allowed",
-                                               "diag_kernel", "diag_exact", "device_close", "records_on_device", "resident")]
-
-
-class KmeansRouteInfo(C.Structure):
-    """mlhip_kmeans_route_info"""
-    _fields_ = [(name, C.c_int32) for name in ("kernel", "pad", "resident")]
-
-
 class Data:
     """A d x N sample block resident in HBM (mlhip_data). `x` is N x d float64 C-contiguous."""
 
@@ -332,14 +445,13 @@ class Data:
         self.ctx = ctx
         self._h = C.c_void_p()
         if x is not None:
-            if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.ndim == 2 and x.flags.c_contiguous):
+            if not _is_block(x):
                 raise TypeError("data must be a C-contiguous float64 N x d numpy array")
             n, d = x.shape
-            check(lib.mlhip_data_upload(ctx.handle, dptr(x), d, C.c_uint64(n), C.c_int64(d), C.byref(self._h)))
+            check(lib.mlhip_data_upload(ctx.handle, dptr(x), d, n, d, C.byref(self._h)))
         else:
             n, d = shape
-            check(lib.mlhip_data_upload_dev(ctx.handle, C.cast(C.c_void_p(device_ptr), c_dp), d, C.c_uint64(n),
-                                            C.c_int64(d), C.byref(self._h)))
+            check(lib.mlhip_data_upload_dev(ctx.handle, C.cast(C.c_void_p(device_ptr), c_dp), d, n, d, C.byref(self._h)))
         self.n, self.d = n, d
         ctx._blocks.add(self)
 
@@ -392,34 +504,27 @@ class Data:
         with weighted=True."""
         if w is not None:
             w = require_weights(w, self.n)
-        check(lib.mlhip_data_set_weights(self.ctx.handle, self._h, None if w is None else dptr(w)))
+        check(lib.mlhip_data_set_weights(self.ctx.handle, self._h, dptr(w)))
 
     @property
     def weight_sum(self):
         """W, the all-reduced total of the attached weights (the row count of an unweighted block)."""
-        total = C.c_double()
-        check(lib.mlhip_data_weight_sum(self._h, C.byref(total)))
-        return total.value
+        return _get(lib.mlhip_data_weight_sum, self._h, C.c_double)
 
     def set_covariance_ridge(self, ridge):
         """The covariance ridge of the handle (mlhip_data_set_covariance_ridge): what every M-step on it adds to the diagonal of each
         covariance it forms. Finite and >= 0; ValueError otherwise (the handle keeps its ridge). E-step results stay valid."""
-        check(lib.mlhip_data_set_covariance_ridge(self.ctx.handle, self._h, float(ridge)))
+        check(lib.mlhip_data_set_covariance_ridge(self.ctx.handle, self._h, ridge))
 
     @property
     def covariance_ridge(self):
         """The handle's covariance ridge (DEFAULT_COVARIANCE_RIDGE = 1e-15 unless set)."""
-        ridge = C.c_double()
-        check(lib.mlhip_data_covariance_ridge(self._h, C.byref(ridge)))
-        return ridge.value
+        return _get(lib.mlhip_data_covariance_ridge, self._h, C.c_double)
 
     # ---- EM -----------------------------------------------------------------------------------------------
     # Parameter conventions (Python side): means K x d, covariances K x d x d, mixing K.
     def em_step(self, mixing, means, covs):
-        K = len(mixing)
-        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-        means = np.ascontiguousarray(means, dtype=np.float64)
-        covs = np.ascontiguousarray(covs, dtype=np.float64)
+        K, _, _, mixing, means, covs = mixture_arguments(mixing, means, covs, d=self.d)
         ll = C.c_double()
         pi1, mu1, S1 = np.empty(K), np.empty((K, self.d)), np.empty((K, self.d, self.d))
         check(lib.mlhip_em_step(self.ctx.handle, self._h, K, dptr(mixing), dptr(means), dptr(covs), C.byref(ll),
@@ -429,14 +534,11 @@ class Data:
     def em_step_diag(self, mixing, means, variances):
         """Diagonal-covariance extension. variances: K x d (a K x d x d stack of diagonal matrices is accepted too and
         returned in the same form)."""
-        K = len(mixing)
-        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-        means = np.ascontiguousarray(means, dtype=np.float64)
         v = np.asarray(variances, dtype=np.float64)
         stacked = v.ndim == 3
         if stacked:
             v = np.stack([np.diag(m) for m in v])
-        v = np.ascontiguousarray(v)
+        K, _, _, mixing, means, v = mixture_arguments(mixing, means, v, diagonal=True, d=self.d)
         ll = C.c_double()
         pi1, mu1, v1 = np.empty(K), np.empty((K, self.d)), np.empty((K, self.d))
         check(lib.mlhip_em_step_diag(self.ctx.handle, self._h, K, dptr(mixing), dptr(means), dptr(v), C.byref(ll),
@@ -448,11 +550,7 @@ class Data:
     def em_step_tied(self, mixing, means, cov):
         """Tied-covariance extension (mlhip_em_step_tied). cov: the one d x d matrix shared by all components.
         Returns (log_likelihood, mixing, means, cov)."""
-        K = len(mixing)
-        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-        means = np.ascontiguousarray(means, dtype=np.float64)
-        cov = np.ascontiguousarray(cov, dtype=np.float64)
-        assert means.shape == (K, self.d) and cov.shape == (self.d, self.d)
+        K, _, _, mixing, means, cov = mixture_arguments(mixing, means, cov, tied=True, d=self.d)
         ll = C.c_double()
         pi1, mu1, S1 = np.empty(K), np.empty((K, self.d)), np.empty((self.d, self.d))
         check(lib.mlhip_em_step_tied(self.ctx.handle, self._h, K, dptr(mixing), dptr(means), dptr(cov), C.byref(ll),
@@ -462,24 +560,17 @@ class Data:
     def em_tied_route(self, K):
         """The route of a tied-covariance step of K components under the switches as they are set now (mlhip_em_tied_route):
         'composed' | 'kernel'."""
-        k = C.c_int()
-        check(lib.mlhip_em_tied_route(self._h, C.c_uint32(K), C.byref(k)))
-        return ("composed", "kernel")[k.value]
+        return _route_name(lib.mlhip_em_tied_route, ("composed", "kernel"), self._h, K)
 
     def em_iterate(self, mixing, means, covs, max_steps, atol=0.0, rtol=0.0, diagonal=False, tied=False):
         """The EM loop in one call (mlhip_em_iterate): up to max_steps iterations with the reference's convergence test, the
         closing arithmetic on the device. covs: K x d x d (or K x d variances with diagonal=True, the one d x d matrix with tied=True).
         Returns (steps_done, converged, log_likelihood, mixing, means, covs, log_likelihood_history)."""
-        K = len(mixing)
-        pi = np.array(mixing, dtype=np.float64, order="C")
-        mu = np.array(means, dtype=np.float64, order="C")
-        S = np.array(covs, dtype=np.float64, order="C")
-        assert not (diagonal and tied)
-        assert mu.shape == (K, self.d) and S.shape == ((self.d, self.d) if tied else (K, self.d) if diagonal else (K, self.d, self.d))
+        K, _, mode, pi, mu, S = mixture_arguments(mixing, means, covs, diagonal, tied, d=self.d, copy=True)
         steps, conv, ll = C.c_uint32(), C.c_int(), C.c_double()
         hist = np.full(int(max_steps), np.nan)
-        check(lib.mlhip_em_iterate(self.ctx.handle, self._h, K, 2 if tied else int(bool(diagonal)), dptr(pi), dptr(mu), dptr(S), C.c_uint32(max_steps),
-                                   C.c_double(atol), C.c_double(rtol), C.byref(steps), C.byref(conv), C.byref(ll), dptr(hist)))
+        check(lib.mlhip_em_iterate(self.ctx.handle, self._h, K, mode, dptr(pi), dptr(mu), dptr(S), max_steps, atol, rtol,
+                                   C.byref(steps), C.byref(conv), C.byref(ll), dptr(hist)))
         return steps.value, bool(conv.value), ll.value, pi, mu, S, hist[:steps.value]
 
     def em_iterate_restarts(self, mixing, means, covs, max_steps, atol=0.0, rtol=0.0, diagonal=False, tied=False):
@@ -488,35 +579,29 @@ class Data:
         restart r's tuple, shaped like em_iterate's -- (steps_done, converged, log_likelihood, mixing, means, covs,
         log_likelihood_history) --, best the restart mlhip_em_select_restart picks; em_labels / em_responsibilities afterwards
         are that restart's."""
-        pi = np.array(mixing, dtype=np.float64, order="C")
-        mu = np.array(means, dtype=np.float64, order="C")
-        S = np.array(covs, dtype=np.float64, order="C")
-        assert not (diagonal and tied) and pi.ndim == 2
-        R, K = pi.shape
-        assert mu.shape == (R, K, self.d)
-        assert S.shape == ((R, self.d, self.d) if tied else (R, K, self.d) if diagonal else (R, K, self.d, self.d))
+        K, _, mode, pi, mu, S = mixture_arguments(mixing, means, covs, diagonal, tied, d=self.d, copy=True, restarts=True)
+        R = len(pi)
         steps, conv, ll = np.zeros(R, dtype=np.uint32), np.zeros(R, dtype=np.int32), np.full(R, np.nan)
         hist = np.full((R, int(max_steps)), np.nan)
         best = C.c_uint32()
-        check(lib.mlhip_em_iterate_restarts(self.ctx.handle, self._h, C.c_uint32(K), 2 if tied else int(bool(diagonal)), C.c_uint32(R), dptr(pi),
-                                            dptr(mu), dptr(S), C.c_uint32(max_steps), C.c_double(atol), C.c_double(rtol), u32ptr(steps),
-                                            conv.ctypes.data_as(C.POINTER(C.c_int)), dptr(ll), dptr(hist), C.byref(best)))
+        check(lib.mlhip_em_iterate_restarts(self.ctx.handle, self._h, K, mode, R, dptr(pi), dptr(mu), dptr(S), max_steps, atol, rtol,
+                                            u32ptr(steps), conv.ctypes.data_as(C.POINTER(C.c_int)), dptr(ll), dptr(hist), C.byref(best)))
         restarts = [(int(steps[r]), bool(conv[r]), float(ll[r]), pi[r], mu[r], S[r], hist[r, :steps[r]]) for r in range(R)]
         return restarts, best.value
 
     def em_restarts_route(self, K, R, covariance_type="full"):
         """The route of mlhip_em_iterate_restarts for R restarts of K components under the switches as they are set now
         (mlhip_em_restarts_route): ('sequential' | 'batched', restarts one launch carries)."""
-        route, per_launch = C.c_int(), C.c_uint32()
-        check(lib.mlhip_em_restarts_route(self._h, C.c_uint32(K), {"full": 0, "diag": 1, "tied": 2}[covariance_type], C.c_uint32(R),
-                                          C.byref(route), C.byref(per_launch)))
-        return ("sequential", "batched")[route.value], per_launch.value
+        per_launch = C.c_uint32()
+        route = _route_name(lib.mlhip_em_restarts_route, ("sequential", "batched"), self._h, K, {"full": 0, "diag": 1, "tied": 2}[covariance_type], R,
+                            after=(C.byref(per_launch),))
+        return route, per_launch.value
 
     def em_plan(self, K):
         """Which kernels a full-covariance EM iteration of K components is made of (mlhip_em_plan):
         {'fused', 'matrix_estep', 'self_norm'} -> bool."""
         f = C.c_uint32()
-        check(lib.mlhip_em_plan(self._h, C.c_uint32(K), C.byref(f)))
+        check(lib.mlhip_em_plan(self._h, K, C.byref(f)))
         return {"fused": bool(f.value & 1), "matrix_estep": bool(f.value & 2), "self_norm": bool(f.value & 4)}
 
     def em_screen_counts(self):
@@ -531,7 +616,7 @@ class Data:
         the fields of mlhip_em_route_info, `estep` / `fused_form` by name, the flags as bool, `sparse` as None (by the call
         history), False or True."""
         info = EmRouteInfo()
-        check(lib.mlhip_em_route(self._h, C.c_uint32(K), {"full": 0, "diag": 1}[covariance_type], C.byref(info)))
+        check(lib.mlhip_em_route(self._h, K, {"full": 0, "diag": 1}[covariance_type], C.byref(info)))
         out = {name: bool(getattr(info, name)) for name, _ in EmRouteInfo._fields_}
         out["estep"] = ("scalar_fed", "matrix4", "big_dim", "plain")[info.estep]
         out["fused_form"] = ("lds_feed", "scalar_feed", "valu")[info.fused_form] if info.fused else None
@@ -542,58 +627,39 @@ class Data:
         """The route of a K-means call of K clusters (mlhip_kmeans_route): {'kernel': 'direct' | 'matrix' | 'big_dim' | 'plain',
         'pad': bool, 'resident': bool}."""
         info = KmeansRouteInfo()
-        check(lib.mlhip_kmeans_route(self._h, C.c_uint32(K), C.byref(info)))
+        check(lib.mlhip_kmeans_route(self._h, K, C.byref(info)))
         return {"kernel": ("direct", "matrix", "big_dim", "plain")[info.kernel], "pad": bool(info.pad), "resident": bool(info.resident)}
 
     def em_score(self, mixing, means, covs, diagonal=False, densities=True, labels=True, tied=False):
         """Per-row log-density and label under the given mixture (mlhip_em_score): (log_density, labels), None for the one not
         asked for. covs: K x d x d (or K x d variances with diagonal=True, the one d x d matrix with tied=True). Nothing the handle
         holds is changed."""
-        K = len(mixing)
-        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-        means = np.ascontiguousarray(means, dtype=np.float64)
-        covs = np.ascontiguousarray(covs, dtype=np.float64)
-        assert not (diagonal and tied)
-        assert means.shape == (K, self.d) and covs.shape == ((self.d, self.d) if tied else (K, self.d) if diagonal else (K, self.d, self.d))
+        K, _, mode, mixing, means, covs = mixture_arguments(mixing, means, covs, diagonal, tied, d=self.d)
         dens = np.empty(self.n) if densities else None
         lab = np.empty(self.n, dtype=np.uint32) if labels else None
-        check(lib.mlhip_em_score(self.ctx.handle, self._h, K, 2 if tied else int(bool(diagonal)), dptr(mixing), dptr(means), dptr(covs),
-                                 dptr(dens) if densities else None, u32ptr(lab) if labels else None))
+        check(lib.mlhip_em_score(self.ctx.handle, self._h, K, mode, dptr(mixing), dptr(means), dptr(covs), dptr(dens), u32ptr(lab)))
         return dens, lab
 
     def em_score_route(self, K):
         """The kernel mlhip_em_score runs for K components under the switches as they are set now (mlhip_em_score_route):
         'scalar_fed' | 'matrix4' | 'composed'."""
-        k = C.c_int()
-        check(lib.mlhip_em_score_route(self._h, C.c_uint32(K), C.byref(k)))
-        return ("scalar_fed", "matrix4", "composed")[k.value]
+        return _route_name(lib.mlhip_em_score_route, ("scalar_fed", "matrix4", "composed"), self._h, K)
 
     def em_conditional_means(self, mixing, means_observed, covs_observed, maps, means_missing, log_density=False):
         """E[x_M | x_O] for every row of this block of OBSERVED coordinates under the conditioned mixture em_condition returns
         (mlhip_em_conditional_means): n x dM C-contiguous float64, and with log_density=True also the n log-densities of the rows
         under the marginal mixture. means_observed: K x dO; covs_observed: K x dO x dO; maps: K x dM x dO; means_missing: K x dM.
         Nothing the handle holds is changed."""
-        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-        means_observed = np.ascontiguousarray(means_observed, dtype=np.float64)
-        covs_observed = np.ascontiguousarray(covs_observed, dtype=np.float64)
-        maps = np.ascontiguousarray(maps, dtype=np.float64)
-        means_missing = np.ascontiguousarray(means_missing, dtype=np.float64)
-        K, dM = means_missing.shape
-        assert mixing.shape == (K,) and means_observed.shape == (K, self.d) and covs_observed.shape == (K, self.d, self.d)
-        assert maps.shape == (K, dM, self.d)
+        K, dM, arrays = conditioned_arguments(self.d, mixing, means_observed, covs_observed, maps, means_missing)
         out = np.empty((self.n, dM))
         dens = np.empty(self.n) if log_density else None
-        check(lib.mlhip_em_conditional_means(self.ctx.handle, self._h, C.c_uint32(K), C.c_uint32(dM), dptr(mixing), dptr(means_observed),
-                                             dptr(covs_observed), dptr(maps), dptr(means_missing), dptr(out), C.c_int64(dM),
-                                             dptr(dens) if log_density else None))
-        return (out, dens) if log_density else out
+        check(lib.mlhip_em_conditional_means(self.ctx.handle, self._h, K, dM, *map(dptr, arrays), dptr(out), dM, dptr(dens)))
+        return _with_optional(out, dens)
 
     def em_condition_route(self, K, dM):
         """The conditioning kernel mlhip_em_conditional_means runs for dM missing coordinates on this block under the switches as they
         are set now (mlhip_em_condition_route): 'registers' | 'plain'."""
-        k = C.c_int()
-        check(lib.mlhip_em_condition_route(self._h, C.c_uint32(K), C.c_uint32(dM), C.byref(k)))
-        return ("registers", "plain")[k.value]
+        return _route_name(lib.mlhip_em_condition_route, ("registers", "plain"), self._h, K, dM)
 
     def em_conditional_samples(self, mixing, means_observed, covs_observed, maps, means_missing, factors, n_draws=1, seed=0, first_row=0,
                                first_draw=0, labels=False):
@@ -601,37 +667,22 @@ class Data:
         em_condition_covariances return (mlhip_em_conditional_samples): n_draws x n x dM C-contiguous float64, and with labels=True
         also the n_draws x n components drawn (uint32). factors: K x dM x dM lower Cholesky factors; first_row: the global index of
         the block's row 0; the draws are first_draw .. first_draw + n_draws - 1. Nothing the handle holds is changed."""
-        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-        means_observed = np.ascontiguousarray(means_observed, dtype=np.float64)
-        covs_observed = np.ascontiguousarray(covs_observed, dtype=np.float64)
-        maps = np.ascontiguousarray(maps, dtype=np.float64)
-        means_missing = np.ascontiguousarray(means_missing, dtype=np.float64)
-        factors = np.ascontiguousarray(factors, dtype=np.float64)
-        K, dM = means_missing.shape
-        assert mixing.shape == (K,) and means_observed.shape == (K, self.d) and covs_observed.shape == (K, self.d, self.d)
-        assert maps.shape == (K, dM, self.d) and factors.shape == (K, dM, dM)
+        K, dM, arrays = conditioned_arguments(self.d, mixing, means_observed, covs_observed, maps, means_missing, factors=factors)
         if n_draws < 0 or first_draw < 0 or first_draw + n_draws > 2 ** 32 - 1:
             raise ValueError("the draws must lie in 0 .. 2^32 - 2")
         out = np.empty((n_draws, self.n, dM))
         lab = np.empty((n_draws, self.n), dtype=np.uint32) if labels else None
-        check(lib.mlhip_em_conditional_samples(self.ctx.handle, self._h, C.c_uint32(K), C.c_uint32(dM), dptr(mixing), dptr(means_observed),
-                                               dptr(covs_observed), dptr(maps), dptr(means_missing), dptr(factors), C.c_uint64(int(seed)),
-                                               C.c_uint64(int(first_row)), C.c_uint32(int(first_draw)), C.c_uint32(int(n_draws)), dptr(out),
-                                               C.c_int64(dM), u32ptr(lab) if labels else None))
-        return (out, lab) if labels else out
+        check(lib.mlhip_em_conditional_samples(self.ctx.handle, self._h, K, dM, *map(dptr, arrays), int(seed), int(first_row),
+                                               int(first_draw), int(n_draws), dptr(out), dM, u32ptr(lab)))
+        return _with_optional(out, lab)
 
     def em_conditional_sample_route(self, K, dM):
         """The kernel mlhip_em_conditional_samples runs for dM missing coordinates on this block under the switches as they are set
         now (mlhip_em_conditional_sample_route): 'registers' | 'plain'."""
-        k = C.c_int()
-        check(lib.mlhip_em_conditional_sample_route(self._h, C.c_uint32(K), C.c_uint32(dM), C.byref(k)))
-        return ("registers", "plain")[k.value]
+        return _route_name(lib.mlhip_em_conditional_sample_route, ("registers", "plain"), self._h, K, dM)
 
     def em_expectation(self, mixing, means, covs):
-        K = len(mixing)
-        mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-        means = np.ascontiguousarray(means, dtype=np.float64)
-        covs = np.ascontiguousarray(covs, dtype=np.float64)
+        K, _, _, mixing, means, covs = mixture_arguments(mixing, means, covs, d=self.d)
         ll = C.c_double()
         check(lib.mlhip_em_expectation(self.ctx.handle, self._h, K, dptr(mixing), dptr(means), dptr(covs), C.byref(ll)))
         return ll.value
@@ -643,27 +694,29 @@ class Data:
 
     def em_maximisation_from(self, resp):
         resp = np.asfortranarray(resp, dtype=np.float64)
+        if resp.ndim != 2 or len(resp) != self.n:
+            raise ValueError(f"resp has shape {resp.shape}, expected one row per row of the block: ({self.n}, K)")
         n, K = resp.shape
         pi1, mu1, S1 = np.empty(K), np.empty((K, self.d)), np.empty((K, self.d, self.d))
-        check(lib.mlhip_em_maximisation_from(self.ctx.handle, self._h, K, dptr(resp), C.c_int64(n), dptr(pi1), dptr(mu1), dptr(S1)))
+        check(lib.mlhip_em_maximisation_from(self.ctx.handle, self._h, K, dptr(resp), n, dptr(pi1), dptr(mu1), dptr(S1)))
         return pi1, mu1, S1
 
     def em_maximisation_from_labels(self, labels, K):
         labels = np.ascontiguousarray(labels, dtype=np.uint32)
+        _require_shape("labels", labels, self.n)
         pi1, mu1, S1 = np.empty(K), np.empty((K, self.d)), np.empty((K, self.d, self.d))
         check(lib.mlhip_em_maximisation_from_labels(self.ctx.handle, self._h, K, u32ptr(labels), dptr(pi1), dptr(mu1), dptr(S1)))
         return pi1, mu1, S1
 
     def em_responsibilities(self, K):
         out = np.empty((self.n, K), order="F")
-        check(lib.mlhip_em_responsibilities(self.ctx.handle, self._h, K, dptr(out), C.c_int64(self.n)))
+        check(lib.mlhip_em_responsibilities(self.ctx.handle, self._h, K, dptr(out), self.n))
         return out
 
     def em_responsibilities_rows(self, K, first, count):
         """Rows [first, first + count) of the responsibilities only (mlhip_em_responsibilities_rows)."""
         out = np.empty((count, K), order="F")
-        check(lib.mlhip_em_responsibilities_rows(self.ctx.handle, self._h, K, C.c_uint64(first), C.c_uint64(count), dptr(out),
-                                                 C.c_int64(max(count, 1))))
+        check(lib.mlhip_em_responsibilities_rows(self.ctx.handle, self._h, K, first, count, dptr(out), max(count, 1)))
         return out
 
     def em_labels(self, K):
@@ -677,35 +730,39 @@ class Data:
         return mean, cov
 
     # ---- K-means --------------------------------------------------------------------------------------------
+    def _centroids(self, centroids, copy=False):
+        c = _float64(centroids, copy)
+        if c.ndim != 2 or c.shape[1] != self.d:
+            raise ValueError(f"centroids has shape {c.shape}, expected (K, {self.d})")
+        return c
+
     def kmeans_step(self, centroids, weighted=False):
         """One Lloyd step: (inertia, n_changed, counts, centroids). weighted=True: mlhip_kmeans_step_weighted on the attached
         weights (set_weights) -- weighted inertia, counts and means; n_changed, labels and distances stay per row."""
-        centroids = np.ascontiguousarray(centroids, dtype=np.float64)
+        centroids = self._centroids(centroids)
         K = centroids.shape[0]
         inertia, changed = C.c_double(), C.c_uint64()
         counts, cout = np.empty(K), np.empty((K, self.d))
         step = lib.mlhip_kmeans_step_weighted if weighted else lib.mlhip_kmeans_step
-        check(step(self.ctx.handle, self._h, K, dptr(centroids), C.byref(inertia), C.byref(changed),
-                                    dptr(counts), dptr(cout)))
+        check(step(self.ctx.handle, self._h, K, dptr(centroids), C.byref(inertia), C.byref(changed), dptr(counts), dptr(cout)))
         return inertia.value, changed.value, counts, cout
 
     def kmeans_iterate(self, centroids, max_steps, atol=0.0, weighted=False):
         """The step loop of KMeans::fit_once in one call (mlhip_kmeans_iterate): the centroid table stays on the device
         between steps. Returns (steps_done, converged, inertia, counts, centroids, old_centroids). weighted=True: the loop of
         weighted steps (mlhip_kmeans_iterate_weighted)."""
-        cur = np.array(centroids, dtype=np.float64, order="C")
+        cur = self._centroids(centroids, copy=True)
         K = cur.shape[0]
-        assert cur.shape == (K, self.d)
         old, counts = np.zeros((K, self.d)), np.zeros(K)
         steps, conv, inertia = C.c_uint32(), C.c_int(), C.c_double()
         iterate = lib.mlhip_kmeans_iterate_weighted if weighted else lib.mlhip_kmeans_iterate
-        check(iterate(self.ctx.handle, self._h, K, dptr(cur), dptr(old), C.c_uint32(max_steps), C.c_double(atol),
-                      C.byref(steps), C.byref(conv), C.byref(inertia), dptr(counts)))
+        check(iterate(self.ctx.handle, self._h, K, dptr(cur), dptr(old), max_steps, atol, C.byref(steps), C.byref(conv), C.byref(inertia),
+                      dptr(counts)))
         return steps.value, bool(conv.value), inertia.value, counts, cur, old
 
     def kmeans_assign(self, centroids, weighted=False):
         """Assignment only: (inertia, n_changed). weighted=True: the weighted inertia (mlhip_kmeans_assign_weighted)."""
-        centroids = np.ascontiguousarray(centroids, dtype=np.float64)
+        centroids = self._centroids(centroids)
         K = centroids.shape[0]
         inertia, changed = C.c_double(), C.c_uint64()
         assign = lib.mlhip_kmeans_assign_weighted if weighted else lib.mlhip_kmeans_assign
@@ -724,7 +781,7 @@ class Data:
         return out
 
     def min_squared_distances(self, centroids):
-        centroids = np.ascontiguousarray(centroids, dtype=np.float64)
+        centroids = self._centroids(centroids)
         out = np.empty(self.n)
         check(lib.mlhip_min_squared_distances(self.ctx.handle, self._h, centroids.shape[0], dptr(centroids), dptr(out)))
         return out
@@ -742,18 +799,15 @@ def silhouette(data, labels, K=None, rows=None, parts=False):
     s = np.empty(m)
     a = np.empty(m) if parts else None
     b = np.empty(m) if parts else None
-    check(lib.mlhip_silhouette(data.ctx.handle, data._h, C.c_uint32(K), u32ptr(labels),
-                               None if rows is None else rows.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_uint64(m),
-                               dptr(a) if parts else None, dptr(b) if parts else None, dptr(s)))
+    check(lib.mlhip_silhouette(data.ctx.handle, data._h, K, u32ptr(labels), None if rows is None else rows.ctypes.data_as(C.POINTER(C.c_uint64)),
+                               m, dptr(a), dptr(b), dptr(s)))
     return (a, b, s) if parts else s
 
 
 def silhouette_route(data):
     """The tier mlhip_silhouette runs on the Data block `data` under the switches as they are set now (mlhip_silhouette_route):
     'registers' | 'plain'."""
-    tier = C.c_int()
-    check(lib.mlhip_silhouette_route(data._h, C.byref(tier)))
-    return ("registers", "plain")[tier.value]
+    return _route_name(lib.mlhip_silhouette_route, ("registers", "plain"), data._h)
 
 
 def silhouette_arguments(n, labels, rows=None, K=None):
@@ -797,23 +851,24 @@ def silhouette_finish(counts, own_label, sums):
     Returns (a, b, s)."""
     counts = np.ascontiguousarray(counts, dtype=np.uint64)
     sums = np.ascontiguousarray(sums, dtype=np.float64)
-    assert counts.ndim == 1 and sums.shape == counts.shape
+    if counts.ndim != 1:
+        raise ValueError(f"counts has shape {counts.shape}, expected (K,)")
+    _require_shape("sums", sums, *counts.shape)
     a, b, s = C.c_double(), C.c_double(), C.c_double()
-    check(lib.mlhip_silhouette_finish(C.c_uint32(len(counts)), counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_uint32(int(own_label)),
-                                      dptr(sums), C.byref(a), C.byref(b), C.byref(s)))
+    check(lib.mlhip_silhouette_finish(len(counts), counts.ctypes.data_as(C.POINTER(C.c_uint64)), int(own_label), dptr(sums), C.byref(a),
+                                      C.byref(b), C.byref(s)))
     return a.value, b.value, s.value
 
 
 def calculate_XXt_beta(X, y, lam):
     """ml::LinearRegression::calculate_XXt_beta on an N x q float64 C-contiguous X: returns (XXt + diag(lam), beta)."""
-    if not (isinstance(X, np.ndarray) and X.dtype == np.float64 and X.ndim == 2 and X.flags.c_contiguous):
+    if not _is_block(X):
         raise TypeError("X must be a C-contiguous float64 N x q numpy array")
     y = np.ascontiguousarray(y, dtype=np.float64)
     lam = np.ascontiguousarray(lam, dtype=np.float64)
     n, q = X.shape
     XXt, beta = np.empty((q, q)), np.empty(q)
-    check(lib.mlpp_calculate_XXt_beta(dptr(X), C.c_uint64(n), q, dptr(y), C.c_uint64(y.size), dptr(lam), lam.size,
-                                      dptr(XXt), dptr(beta)))
+    check(lib.mlpp_calculate_XXt_beta(dptr(X), n, q, dptr(y), y.size, dptr(lam), lam.size, dptr(XXt), dptr(beta)))
     return XXt, beta
 
 
@@ -823,9 +878,9 @@ def finalize_statistics_ridge(statistics, shift, n_global, ridge):
     st = np.ascontiguousarray(statistics, dtype=np.float64)
     shift = np.ascontiguousarray(shift, dtype=np.float64)
     K, d = st.shape[0], shift.shape[0]
-    assert st.shape == (K, (d + 1) * (d + 2) // 2)
+    _require_shape("statistics", st, K, (d + 1) * (d + 2) // 2)
     pi, mu, S = np.empty(K), np.empty((K, d)), np.empty((K, d, d))
-    check(lib.mlhip_em_finalize_statistics_ridge(d, K, dptr(st), dptr(shift), float(n_global), float(ridge), dptr(pi), dptr(mu), dptr(S)))
+    check(lib.mlhip_em_finalize_statistics_ridge(d, K, dptr(st), dptr(shift), n_global, ridge, dptr(pi), dptr(mu), dptr(S)))
     return pi, mu, S
 
 
@@ -837,13 +892,13 @@ def finalize_statistics_tied(statistics, total_scatter, shift, total_weight, rid
     K, d = st.shape[0], st.shape[1] - 1
     T = np.ascontiguousarray(total_scatter, dtype=np.float64)
     shift = np.ascontiguousarray(shift, dtype=np.float64)
-    assert T.shape == ((d + 1) * (d + 2) // 2,) and shift.shape == (d,)
+    _require_shape("total_scatter", T, (d + 1) * (d + 2) // 2)
+    _require_shape("shift", shift, d)
     pi, mu, S = np.empty(K), np.empty((K, d)), np.empty((d, d))
     if ridge is None:
-        check(lib.mlhip_em_finalize_statistics_tied(d, K, dptr(st), dptr(T), dptr(shift), C.c_double(total_weight), dptr(pi), dptr(mu), dptr(S)))
+        check(lib.mlhip_em_finalize_statistics_tied(d, K, dptr(st), dptr(T), dptr(shift), total_weight, dptr(pi), dptr(mu), dptr(S)))
     else:
-        check(lib.mlhip_em_finalize_statistics_tied_ridge(d, K, dptr(st), dptr(T), dptr(shift), float(total_weight), float(ridge), dptr(pi),
-                                                          dptr(mu), dptr(S)))
+        check(lib.mlhip_em_finalize_statistics_tied_ridge(d, K, dptr(st), dptr(T), dptr(shift), total_weight, ridge, dptr(pi), dptr(mu), dptr(S)))
     return pi, mu, S
 
 
@@ -851,10 +906,10 @@ def cholesky_lower(cov):
     """The lower Cholesky factor the sampler uses (mlhip_cholesky_lower, no GPU): L with L @ L.T == cov up to rounding, upper
     triangle zero. ValueError when cov is not positive definite."""
     cov = np.ascontiguousarray(cov, dtype=np.float64)
-    d = cov.shape[0]
-    assert cov.shape == (d, d)
+    d = len(cov)
+    _require_shape("cov", cov, d, d)
     L = np.empty((d, d), order="F")
-    check(lib.mlhip_cholesky_lower(C.c_uint32(d), dptr(cov), dptr(L)))
+    check(lib.mlhip_cholesky_lower(d, dptr(cov), dptr(L)))
     return np.ascontiguousarray(L)
 
 
@@ -863,22 +918,17 @@ def em_condition(means, covs, observed, diagonal=False, tied=False):
     covs_observed K x dO x dO, maps K x dM x dO, means_missing K x dM), the missing coordinates in ascending order. means: K x d;
     covs: K x d x d (K x d variances with diagonal=True, the one d x d matrix with tied=True). ValueError for bad coordinates or an
     observed block that is not positive definite."""
-    means = np.ascontiguousarray(means, dtype=np.float64)
-    covs = np.ascontiguousarray(covs, dtype=np.float64)
-    assert not (diagonal and tied) and means.ndim == 2
-    K, d = means.shape
-    assert covs.shape == ((d, d) if tied else (K, d) if diagonal else (K, d, d))
+    K, d, mode, _, means, covs = mixture_arguments(None, means, covs, diagonal, tied)
     observed = np.ascontiguousarray(observed, dtype=np.uint32).ravel()
     dO = len(observed)
     dM = max(d - dO, 0)
     mu_o, S_oo, A, mu_m = np.empty((K, dO)), np.empty((K, dO, dO)), np.empty((K, dM, dO)), np.empty((K, dM))
-    check(lib.mlhip_em_condition(C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(means), dptr(covs), u32ptr(observed),
-                                 C.c_uint32(dO), dptr(mu_o), dptr(S_oo), dptr(A), dptr(mu_m)))
+    check(lib.mlhip_em_condition(d, K, mode, dptr(means), dptr(covs), u32ptr(observed), dO, dptr(mu_o), dptr(S_oo), dptr(A), dptr(mu_m)))
     return mu_o, S_oo, A, mu_m
 
 
 def _impute_block(x, d=None):
-    if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.ndim == 2 and x.flags.c_contiguous):
+    if not _is_block(x):
         raise TypeError("x must be a C-contiguous float64 N x d numpy array")
     if d is not None and x.shape[1] != d:
         raise ValueError(f"x must have one column per coordinate of the model ({d})")
@@ -892,22 +942,14 @@ def em_impute(ctx, mixing, means, covs, x, diagonal=False, tied=False, log_densi
     marginal mixture and the N x K marginal responsibilities (C-contiguous), in that order. ctx: a Context or a device group (every
     shard imputes its own rows). means: K x d; covs as for Data.em_score. TypeError / ValueError before any device work; ValueError
     where the observed block of a covariance is not positive definite for some row's pattern (nothing is returned)."""
-    mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-    means = np.ascontiguousarray(means, dtype=np.float64)
-    covs = np.ascontiguousarray(covs, dtype=np.float64)
-    assert not (diagonal and tied) and mixing.ndim == 1 and means.ndim == 2
-    K, d = means.shape
-    assert mixing.shape == (K,) and covs.shape == ((d, d) if tied else (K, d) if diagonal else (K, d, d))
+    K, d, mode, mixing, means, covs = mixture_arguments(mixing, means, covs, diagonal, tied)
     x = _impute_block(x, d)
     n = x.shape[0]
     out = np.empty((n, d))
     dens = np.empty(n) if log_density else None
     resp = np.empty((n, K)) if responsibilities else None
-    check(lib.mlhip_em_impute(ctx.handle, C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(mixing), dptr(means),
-                              dptr(covs), dptr(x), C.c_uint64(n), dptr(out), dptr(dens) if log_density else None,
-                              dptr(resp) if responsibilities else None))
-    extra = tuple(v for v in (dens, resp) if v is not None)
-    return (out,) + extra if extra else out
+    check(lib.mlhip_em_impute(ctx.handle, d, K, mode, dptr(mixing), dptr(means), dptr(covs), dptr(x), n, dptr(out), dptr(dens), dptr(resp)))
+    return _with_optional(out, dens, resp)
 
 
 def em_impute_plan(x):
@@ -918,7 +960,7 @@ def em_impute_plan(x):
     n, d = x.shape
     order, bounds, n_obs = np.empty(n, dtype=np.uint32), np.empty(n + 1, dtype=np.uint32), np.empty(n, dtype=np.uint32)
     p = C.c_uint32()
-    check(lib.mlhip_em_impute_plan(dptr(x), C.c_uint64(n), C.c_uint32(d), C.byref(p), u32ptr(order), u32ptr(bounds), u32ptr(n_obs)))
+    check(lib.mlhip_em_impute_plan(dptr(x), n, d, C.byref(p), u32ptr(order), u32ptr(bounds), u32ptr(n_obs)))
     return order, bounds[:p.value + 1].copy(), n_obs[:p.value].copy()
 
 
@@ -926,13 +968,12 @@ def em_impute_route(d, K, x=None):
     """The route mlhip_em_impute takes for a d-dimensional model of K components under the switches as they are set now
     (mlhip_em_impute_route, no GPU, nothing is launched): 'composed' | 'kernel' -- with a block x a pair of it and the kernel launches
     the call makes for that block."""
-    route, launches = C.c_int(), C.c_uint64()
     if x is None:
-        check(lib.mlhip_em_impute_route(C.c_uint32(d), C.c_uint32(K), None, C.c_uint64(0), C.byref(route), None))
-        return ("composed", "kernel")[route.value]
+        return _route_name(lib.mlhip_em_impute_route, ("composed", "kernel"), d, K, None, 0, after=(None,))
     x = _impute_block(x, d)
-    check(lib.mlhip_em_impute_route(C.c_uint32(d), C.c_uint32(K), dptr(x), C.c_uint64(x.shape[0]), C.byref(route), C.byref(launches)))
-    return ("composed", "kernel")[route.value], launches.value
+    launches = C.c_uint64()
+    route = _route_name(lib.mlhip_em_impute_route, ("composed", "kernel"), d, K, dptr(x), len(x), after=(C.byref(launches),))
+    return route, launches.value
 
 
 def em_impute_condition(ctx, mixing, means, covs, observed, diagonal=False, tied=False):
@@ -940,18 +981,13 @@ def em_impute_condition(ctx, mixing, means, covs, observed, diagonal=False, tied
     `observed` (mlhip_em_impute_condition; d <= 32): (means_observed K x dO, whitening K x dO x dO -- W_k = L^-1, L L^T = Sigma_k,OO --,
     coefficients K -- log pi_k - sum_j log L_jj --, maps K x dM x dO, means_missing K x dM). ValueError for bad coordinates or an
     observed block that is not positive definite."""
-    mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-    means = np.ascontiguousarray(means, dtype=np.float64)
-    covs = np.ascontiguousarray(covs, dtype=np.float64)
-    assert not (diagonal and tied) and means.ndim == 2
-    K, d = means.shape
-    assert mixing.shape == (K,) and covs.shape == ((d, d) if tied else (K, d) if diagonal else (K, d, d))
+    K, d, mode, mixing, means, covs = mixture_arguments(mixing, means, covs, diagonal, tied)
     observed = np.ascontiguousarray(observed, dtype=np.uint32).ravel()
     dO = len(observed)
     dM = max(d - dO, 0)
     mu_o, W, coef, A, mu_m = np.empty((K, dO)), np.empty((K, dO, dO)), np.empty(K), np.empty((K, dM, dO)), np.empty((K, dM))
-    check(lib.mlhip_em_impute_condition(ctx.handle, C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(mixing), dptr(means),
-                                        dptr(covs), u32ptr(observed), C.c_uint32(dO), dptr(mu_o), dptr(W), dptr(coef), dptr(A), dptr(mu_m)))
+    check(lib.mlhip_em_impute_condition(ctx.handle, d, K, mode, dptr(mixing), dptr(means), dptr(covs), u32ptr(observed), dO, dptr(mu_o),
+                                        dptr(W), dptr(coef), dptr(A), dptr(mu_m)))
     return mu_o, W, coef, A, mu_m
 
 
@@ -961,18 +997,17 @@ def em_condition_covariances(covs, observed, diagonal=False, tied=False, K=None)
     missing coordinates in ascending order. covs as for em_condition (tied=True: the one d x d matrix, and K components). ValueError for
     bad coordinates or a block that is not positive definite."""
     covs = np.ascontiguousarray(covs, dtype=np.float64)
-    assert not (diagonal and tied)
-    if tied:
-        assert covs.ndim == 2 and covs.shape[0] == covs.shape[1] and K is not None
-        d = covs.shape[0]
-    else:
-        assert covs.ndim == (2 if diagonal else 3) and (diagonal or covs.shape[1] == covs.shape[2])
-        K, d = covs.shape[0], covs.shape[1]
+    if tied and K is None:
+        raise ValueError("tied=True needs K, the number of components")
+    if covs.ndim < 2:
+        raise ValueError(f"covs has shape {covs.shape}: not the covariances of a mixture")
+    K, d = (K, covs.shape[0]) if tied else covs.shape[:2]
+    _require_shape("covs", covs, *_covariance_shape(K, d, diagonal, tied))
     observed = np.ascontiguousarray(observed, dtype=np.uint32).ravel()
     dM = max(d - len(observed), 0)
     C_m, G = np.empty((K, dM, dM)), np.empty((K, dM, dM))
-    check(lib.mlhip_em_condition_covariances(C.c_uint32(d), C.c_uint32(K), 2 if tied else int(bool(diagonal)), dptr(covs), u32ptr(observed),
-                                             C.c_uint32(len(observed)), dptr(C_m), dptr(G)))
+    check(lib.mlhip_em_condition_covariances(d, K, 2 if tied else int(bool(diagonal)), dptr(covs), u32ptr(observed), len(observed), dptr(C_m),
+                                             dptr(G)))
     return C_m, G
 
 
@@ -983,32 +1018,19 @@ def em_conditional_variances(data, mixing, means_observed, covs_observed, maps, 
     means=True and / or log_density=True a tuple of it, E[x_M | x_O] (n x dM) and the n log-densities of the rows under the marginal
     mixture, in that order -- the bits of Data.em_conditional_means. covs_missing: K x dM x dM, the other parameters as for
     Data.em_conditional_means. A function of the module, not a method of Data; nothing the handle holds is changed."""
-    mixing = np.ascontiguousarray(mixing, dtype=np.float64)
-    means_observed = np.ascontiguousarray(means_observed, dtype=np.float64)
-    covs_observed = np.ascontiguousarray(covs_observed, dtype=np.float64)
-    maps = np.ascontiguousarray(maps, dtype=np.float64)
-    means_missing = np.ascontiguousarray(means_missing, dtype=np.float64)
-    covs_missing = np.ascontiguousarray(covs_missing, dtype=np.float64)
-    K, dM = means_missing.shape
-    assert mixing.shape == (K,) and means_observed.shape == (K, data.d) and covs_observed.shape == (K, data.d, data.d)
-    assert maps.shape == (K, dM, data.d) and covs_missing.shape == (K, dM, dM)
+    K, dM, arrays = conditioned_arguments(data.d, mixing, means_observed, covs_observed, maps, means_missing, covs_missing=covs_missing)
     out = np.empty((data.n, dM, dM) if full else (data.n, dM))
     y = np.empty((data.n, dM)) if means else None
     dens = np.empty(data.n) if log_density else None
-    check(lib.mlhip_em_conditional_variances(data.ctx.handle, data._h, C.c_uint32(K), C.c_uint32(dM), dptr(mixing), dptr(means_observed),
-                                             dptr(covs_observed), dptr(maps), dptr(means_missing), dptr(covs_missing), C.c_int(int(bool(full))),
-                                             dptr(out), C.c_int64(dM * dM if full else dM), dptr(y) if means else None, C.c_int64(dM),
-                                             dptr(dens) if log_density else None))
-    extra = ([y] if means else []) + ([dens] if log_density else [])
-    return (out, *extra) if extra else out
+    check(lib.mlhip_em_conditional_variances(data.ctx.handle, data._h, K, dM, *map(dptr, arrays), bool(full), dptr(out),
+                                             dM * dM if full else dM, dptr(y), dM, dptr(dens)))
+    return _with_optional(out, y, dens)
 
 
 def em_condition_variance_route(data, K, dM, full=False):
     """The kernel mlhip_em_conditional_variances runs for dM missing coordinates on the Data block `data` in the form asked for, under
     the switches as they are set now (mlhip_em_condition_variance_route): 'registers' | 'plain'."""
-    k = C.c_int()
-    check(lib.mlhip_em_condition_variance_route(data._h, C.c_uint32(K), C.c_uint32(dM), C.c_int(int(bool(full))), C.byref(k)))
-    return ("registers", "plain")[k.value]
+    return _route_name(lib.mlhip_em_condition_variance_route, ("registers", "plain"), data._h, K, dM, bool(full))
 
 
 def normal_cdf(a):
@@ -1016,7 +1038,7 @@ def normal_cdf(a):
     host; no GPU), elementwise: float64, the shape of `a`."""
     a = np.ascontiguousarray(a, dtype=np.float64)
     out = np.empty_like(a)
-    check(lib.mlhip_normal_cdf(dptr(a), C.c_uint64(a.size), dptr(out)))
+    check(lib.mlhip_normal_cdf(dptr(a), a.size, dptr(out)))
     return out
 
 
@@ -1025,7 +1047,7 @@ def normal_quantile(p):
     strictly inside (0, 1)."""
     p = np.ascontiguousarray(p, dtype=np.float64)
     out = np.empty_like(p)
-    check(lib.mlhip_normal_quantile(dptr(p), C.c_uint64(p.size), dptr(out)))
+    check(lib.mlhip_normal_quantile(dptr(p), p.size, dptr(out)))
     return out
 
 
@@ -1036,19 +1058,12 @@ def em_condition_scales(covs_missing):
     """(scales, inverse_scales), K x dM each: s_kj = sqrt(C_k[j][j]) and w_kj = 1.0 / s_kj from the K x dM x dM conditioned covariances
     of em_condition_covariances (mlhip_em_condition_scales, no GPU). ValueError where a C_k[j][j] is <= 0 or not finite."""
     covs_missing = np.ascontiguousarray(covs_missing, dtype=np.float64)
-    assert covs_missing.ndim == 3 and covs_missing.shape[1] == covs_missing.shape[2]
+    if covs_missing.ndim != 3 or covs_missing.shape[1] != covs_missing.shape[2]:
+        raise ValueError(f"covs_missing has shape {covs_missing.shape}, expected (K, dM, dM)")
     K, dM = covs_missing.shape[:2]
     s, w = np.empty((K, dM)), np.empty((K, dM))
-    check(lib.mlhip_em_condition_scales(C.c_uint32(K), C.c_uint32(dM), dptr(covs_missing), dptr(s), dptr(w)))
+    check(lib.mlhip_em_condition_scales(K, dM, dptr(covs_missing), dptr(s), dptr(w)))
     return s, w
-
-
-def _conditioned_arguments(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales):
-    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales)]
-    K, dM = arrays[4].shape
-    assert arrays[0].shape == (K,) and arrays[1].shape == (K, data.d) and arrays[2].shape == (K, data.d, data.d)
-    assert arrays[3].shape == (K, dM, data.d) and arrays[5].shape == (K, dM) and arrays[6].shape == (K, dM)
-    return K, dM, arrays
 
 
 def em_conditional_cdfs(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales, values, means=False,
@@ -1058,17 +1073,16 @@ def em_conditional_cdfs(data, mixing, means_observed, covs_observed, maps, means
     float64. With means=True and / or log_density=True a tuple of it, E[x_M | x_O] (n x dM) and the n log-densities of the rows under
     the marginal mixture, in that order -- the bits of Data.em_conditional_means. A function of the module, not a method of Data;
     nothing the handle holds is changed."""
-    K, dM, arrays = _conditioned_arguments(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales)
+    K, dM, arrays = conditioned_arguments(data.d, mixing, means_observed, covs_observed, maps, means_missing, scales=scales,
+                                          inverse_scales=inverse_scales)
     values = np.ascontiguousarray(values, dtype=np.float64)
-    assert values.shape == (data.n, dM)
+    _require_shape("values", values, data.n, dM)
     out = np.empty((data.n, dM))
     y = np.empty((data.n, dM)) if means else None
     dens = np.empty(data.n) if log_density else None
-    check(lib.mlhip_em_conditional_cdfs(data.ctx.handle, data._h, C.c_uint32(K), C.c_uint32(dM), *[dptr(a) for a in arrays], dptr(values),
-                                        C.c_int64(dM), dptr(out), C.c_int64(dM), dptr(y) if means else None, C.c_int64(dM),
-                                        dptr(dens) if log_density else None))
-    extra = ([y] if means else []) + ([dens] if log_density else [])
-    return (out, *extra) if extra else out
+    check(lib.mlhip_em_conditional_cdfs(data.ctx.handle, data._h, K, dM, *map(dptr, arrays), dptr(values), dM, dptr(out), dM, dptr(y), dM,
+                                        dptr(dens)))
+    return _with_optional(out, y, dens)
 
 
 def em_conditional_quantiles(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales, probabilities,
@@ -1077,36 +1091,32 @@ def em_conditional_quantiles(data, mixing, means_observed, covs_observed, maps, 
     (mlhip_em_conditional_quantiles): P x n x dM C-contiguous float64, probability-major. With iterations=True, means=True and / or
     log_density=True a tuple of it, the trips every output took (P x n x dM uint32), E[x_M | x_O] and the log-densities, in that
     order. Arguments as for em_conditional_cdfs. ValueError for a bad probability, before any device work."""
-    K, dM, arrays = _conditioned_arguments(data, mixing, means_observed, covs_observed, maps, means_missing, scales, inverse_scales)
+    K, dM, arrays = conditioned_arguments(data.d, mixing, means_observed, covs_observed, maps, means_missing, scales=scales,
+                                          inverse_scales=inverse_scales)
     probabilities = np.ascontiguousarray(probabilities, dtype=np.float64)
-    assert probabilities.ndim == 1
+    if probabilities.ndim != 1:
+        raise ValueError(f"probabilities has shape {probabilities.shape}, expected (P,)")
     P = len(probabilities)
     out = np.empty((P, data.n, dM))
     trips = np.zeros((P, data.n, dM), dtype=np.uint32) if iterations else None
     y = np.empty((data.n, dM)) if means else None
     dens = np.empty(data.n) if log_density else None
-    check(lib.mlhip_em_conditional_quantiles(data.ctx.handle, data._h, C.c_uint32(K), C.c_uint32(dM), *[dptr(a) for a in arrays],
-                                             dptr(probabilities), C.c_uint32(P), dptr(out), C.c_int64(dM), dptr(y) if means else None,
-                                             C.c_int64(dM), dptr(dens) if log_density else None, u32ptr(trips) if iterations else None))
-    extra = ([trips] if iterations else []) + ([y] if means else []) + ([dens] if log_density else [])
-    return (out, *extra) if extra else out
+    check(lib.mlhip_em_conditional_quantiles(data.ctx.handle, data._h, K, dM, *map(dptr, arrays), dptr(probabilities), P, dptr(out), dM,
+                                             dptr(y), dM, dptr(dens), u32ptr(trips)))
+    return _with_optional(out, trips, y, dens)
 
 
 def em_condition_quantile_route(data, K, dM, quantile=True):
     """The kernel mlhip_em_conditional_quantiles (quantile=True) or mlhip_em_conditional_cdfs (quantile=False) runs for dM missing
     coordinates on the Data block `data`, under the switches as they are set now (mlhip_em_condition_quantile_route): 'registers' |
     'plain'."""
-    k = C.c_int()
-    check(lib.mlhip_em_condition_quantile_route(data._h, C.c_uint32(K), C.c_uint32(dM), C.c_int(int(bool(quantile))), C.byref(k)))
-    return ("registers", "plain")[k.value]
+    return _route_name(lib.mlhip_em_condition_quantile_route, ("registers", "plain"), data._h, K, dM, bool(quantile))
 
 
 def em_sample_route(d, K):
     """The kernel the sampling calls run for K components in d dimensions under the switches as they are set now
     (mlhip_em_sample_route): 'lds_table' | 'global_table' | 'plain'."""
-    k = C.c_int()
-    check(lib.mlhip_em_sample_route(C.c_uint32(d), C.c_uint32(K), C.byref(k)))
-    return ("lds_table", "global_table", "plain")[k.value]
+    return _route_name(lib.mlhip_em_sample_route, ("lds_table", "global_table", "plain"), d, K)
 
 
 def process_covariance(cov):

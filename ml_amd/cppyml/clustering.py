@@ -24,10 +24,11 @@ from .. import _lib
 _l = _lib.lib
 _check = _lib.check
 _dp = _lib.dptr
+_get = _lib._get
 
 
 def _require_data(data):
-    if not (isinstance(data, np.ndarray) and data.dtype == np.float64 and data.ndim == 2 and data.flags.c_contiguous):
+    if not _lib._is_block(data):
         raise TypeError("fit(): incompatible function arguments. data must be a C-contiguous float64 array of shape (N, d)")
     return data
 
@@ -36,35 +37,45 @@ def _vector(x):
     return np.ascontiguousarray(x, dtype=np.float64).ravel()
 
 
+def _created(create, *args):
+    """The handle create(*args, &handle) makes."""
+    h = C.c_void_p()
+    _check(create(*args, C.byref(h)))
+    return h
+
+
+def _deleter(destroy):
+    """A __del__ that frees self._h with the library's `destroy`, once."""
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            destroy(h)
+            self._h = None
+    return __del__
+
+
 class CentroidsInitialiser:
     """Abstract centroids initialiser."""
 
     def __init__(self, *args, **kwargs):
         raise TypeError(f"{type(self).__module__}.{type(self).__qualname__}: No constructor defined!")
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            _l.mlpp_centroids_initialiser_destroy(h)
-            self._h = None
+    __del__ = _deleter(_l.mlpp_centroids_initialiser_destroy)
 
     def _run(self, data, number_components, seed=None):
         """Test hook: runs the initialiser on N x d data, returns K x d centroids."""
         data = _require_data(data)
         n, d = data.shape
         out = np.empty((number_components, d))
-        _check(_l.mlpp_centroids_initialiser_run(self._h, _dp(data), C.c_uint64(n), d, number_components,
-                                                 int(seed is not None), C.c_uint32(seed or 0), _dp(out)))
+        _check(_l.mlpp_centroids_initialiser_run(self._h, _dp(data), n, d, number_components, seed is not None, seed or 0, _dp(out)))
         return out
-
 
     def _run_on_device(self, data, number_components, seed=None):
         """Test hook: the same through the path `fit` takes (data uploaded, the O(N) passes on the GPU)."""
         data = _require_data(data)
         n, d = data.shape
         out = np.empty((number_components, d))
-        _check(_l.mlpp_centroids_initialiser_run_on_device(self._h, _dp(data), C.c_uint64(n), d, number_components,
-                                                           int(seed is not None), C.c_uint32(seed or 0), _dp(out)))
+        _check(_l.mlpp_centroids_initialiser_run_on_device(self._h, _dp(data), n, d, number_components, seed is not None, seed or 0, _dp(out)))
         return out
 
 
@@ -74,18 +85,13 @@ class ResponsibilitiesInitialiser:
     def __init__(self, *args, **kwargs):
         raise TypeError(f"{type(self).__module__}.{type(self).__qualname__}: No constructor defined!")
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            _l.mlpp_responsibilities_initialiser_destroy(h)
-            self._h = None
+    __del__ = _deleter(_l.mlpp_responsibilities_initialiser_destroy)
 
     def _run(self, data, number_components, seed=None):
         data = _require_data(data)
         n, d = data.shape
         out = np.empty((n, number_components), order="F")
-        _check(_l.mlpp_responsibilities_initialiser_run(self._h, _dp(data), C.c_uint64(n), d, number_components,
-                                                        int(seed is not None), C.c_uint32(seed or 0), _dp(out)))
+        _check(_l.mlpp_responsibilities_initialiser_run(self._h, _dp(data), n, d, number_components, seed is not None, seed or 0, _dp(out)))
         return out
 
 
@@ -93,24 +99,21 @@ class Forgy(CentroidsInitialiser):
     """Forgy initialisation algorithm."""
 
     def __init__(self):
-        self._h = C.c_void_p()
-        _check(_l.mlpp_forgy_create(C.byref(self._h)))
+        self._h = _created(_l.mlpp_forgy_create)
 
 
 class RandomPartition(CentroidsInitialiser):
     """Random Partition initialisation algorithm."""
 
     def __init__(self):
-        self._h = C.c_void_p()
-        _check(_l.mlpp_random_partition_create(C.byref(self._h)))
+        self._h = _created(_l.mlpp_random_partition_create)
 
 
 class KPP(CentroidsInitialiser):
     """KMeans++ initialisation algorithm."""
 
     def __init__(self):
-        self._h = C.c_void_p()
-        _check(_l.mlpp_kpp_create(C.byref(self._h)))
+        self._h = _created(_l.mlpp_kpp_create)
 
 
 class FixedPointKPP(CentroidsInitialiser):
@@ -118,8 +121,7 @@ class FixedPointKPP(CentroidsInitialiser):
     reproduces the reference's draws bit for bit); on the GPU every draw stays on the device, whatever the sample size."""
 
     def __init__(self):
-        self._h = C.c_void_p()
-        _check(_l.mlpp_fixed_point_kpp_create(C.byref(self._h)))
+        self._h = _created(_l.mlpp_fixed_point_kpp_create)
 
 
 class FixedCentroids(CentroidsInitialiser):
@@ -129,8 +131,7 @@ class FixedCentroids(CentroidsInitialiser):
         c = np.ascontiguousarray(centroids, dtype=np.float64)
         if c.ndim != 2:
             raise ValueError("centroids must be K x d")
-        self._h = C.c_void_p()
-        _check(_l.mlpp_fixed_centroids_create(_dp(c), c.shape[0], c.shape[1], C.byref(self._h)))
+        self._h = _created(_l.mlpp_fixed_centroids_create, _dp(c), c.shape[0], c.shape[1])
 
 
 class ClosestCentroid(ResponsibilitiesInitialiser):
@@ -140,40 +141,33 @@ class ClosestCentroid(ResponsibilitiesInitialiser):
         if centroids_initialiser is not None and not isinstance(centroids_initialiser, CentroidsInitialiser):
             raise TypeError("centroids_initialiser must be a CentroidsInitialiser")
         self._ci = centroids_initialiser
-        self._h = C.c_void_p()
-        _check(_l.mlpp_closest_centroid_create(centroids_initialiser._h if centroids_initialiser is not None else None,
-                                               C.byref(self._h)))
+        self._h = _created(_l.mlpp_closest_centroid_create, centroids_initialiser._h if centroids_initialiser is not None else None)
 
 
 class EM:
     """Gaussian Expectation-Maximisation algorithm."""
 
     def __init__(self, number_components):
-        self._h = C.c_void_p()
-        _check(_l.mlpp_em_create(int(number_components), C.byref(self._h)))
+        self._h = _created(_l.mlpp_em_create, int(number_components))
         self._keep = []
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            _l.mlpp_em_destroy(h)
-            self._h = None
+    __del__ = _deleter(_l.mlpp_em_destroy)
 
     def set_seed(self, seed):
         """Sets PRNG seed."""
-        _check(_l.mlpp_em_set_seed(self._h, C.c_uint32(seed)))
+        _check(_l.mlpp_em_set_seed(self._h, seed))
 
     def set_absolute_tolerance(self, absolute_tolerance):
         """Sets absolute tolerance."""
-        _check(_l.mlpp_em_set_absolute_tolerance(self._h, C.c_double(absolute_tolerance)))
+        _check(_l.mlpp_em_set_absolute_tolerance(self._h, absolute_tolerance))
 
     def set_relative_tolerance(self, relative_tolerance):
         """Sets relative tolerance."""
-        _check(_l.mlpp_em_set_relative_tolerance(self._h, C.c_double(relative_tolerance)))
+        _check(_l.mlpp_em_set_relative_tolerance(self._h, relative_tolerance))
 
     def set_maximum_steps(self, maximum_steps):
         """Sets maximum number of iterations."""
-        _check(_l.mlpp_em_set_maximum_steps(self._h, C.c_uint32(maximum_steps)))
+        _check(_l.mlpp_em_set_maximum_steps(self._h, maximum_steps))
 
     def set_means_initialiser(self, means_initialiser):
         """Sets the algorithm to initialise component means."""
@@ -188,11 +182,11 @@ class EM:
 
     def set_verbose(self, verbose):
         """Turns on/off the verbose mode."""
-        _check(_l.mlpp_em_set_verbose(self._h, int(bool(verbose))))
+        _check(_l.mlpp_em_set_verbose(self._h, bool(verbose)))
 
     def set_maximise_first(self, maximise_first):
         """Turns on/off doing an initial maximisation step before the E-M iterations."""
-        _check(_l.mlpp_em_set_maximise_first(self._h, int(bool(maximise_first))))
+        _check(_l.mlpp_em_set_maximise_first(self._h, bool(maximise_first)))
 
     def set_covariance_type(self, covariance_type):
         """Extension (not in the reference surface): "full" (default, the reference's only mode), "diag" -- every
@@ -208,39 +202,33 @@ class EM:
         """Extension (scikit-learn's `reg_covar`): the value every M-step of the next fit adds to the diagonal of each covariance
         it forms ("full": every component's; "diag": every variance; "tied": the one covariance, once). Default 1e-15, the
         reference's constant; 0 is allowed. ValueError for a negative or non-finite value (the model keeps its value)."""
-        _check(_l.mlpp_em_set_covariance_regularisation(self._h, float(covariance_regularisation)))
+        _check(_l.mlpp_em_set_covariance_regularisation(self._h, covariance_regularisation))
 
     @property
     def covariance_regularisation(self):
         """Extension: the value set by `set_covariance_regularisation` (1e-15 unless set)."""
-        v = C.c_double()
-        _check(_l.mlpp_em_covariance_regularisation(self._h, C.byref(v)))
-        return v.value
+        return _get(_l.mlpp_em_covariance_regularisation, self._h, C.c_double)
 
     def set_number_initialisations(self, number_initialisations):
         """Extension (scikit-learn's `n_init`; the reference's EM has no restarts): `fit` runs this many EM loops on the one
         uploaded sample and keeps the best. Start r is what a solo fit would begin from, drawn from the seeded PRNG in order -- the
         starts of that many consecutive `fit` calls on one object after one `set_seed`. Among the loops that converged the greatest
         log-likelihood wins, the first of equals; if none converged, the same over all. Default 1. ValueError for 0."""
-        _check(_l.mlpp_em_set_number_initialisations(self._h, C.c_uint32(number_initialisations)))
+        _check(_l.mlpp_em_set_number_initialisations(self._h, number_initialisations))
 
     @property
     def number_initialisations(self):
         """Extension: the value set by `set_number_initialisations` (1 unless set)."""
-        v = C.c_uint32()
-        _check(_l.mlpp_em_number_initialisations(self._h, C.byref(v)))
-        return v.value
+        return _get(_l.mlpp_em_number_initialisations, self._h, C.c_uint32)
 
     @property
     def best_initialisation(self):
         """Extension: the initialisation the fitted state (parameters, log-likelihood, labels, responsibilities) belongs to."""
-        v = C.c_uint32()
-        _check(_l.mlpp_em_best_initialisation(self._h, C.byref(v)))
-        return v.value
+        return _get(_l.mlpp_em_best_initialisation, self._h, C.c_uint32)
 
     def _per_initialisation(self, getter, dtype, ctype):
         count = C.c_uint32()
-        _check(getter(self._h, None, C.c_uint32(0), C.byref(count)))
+        _check(getter(self._h, None, 0, C.byref(count)))
         out = np.empty(count.value, dtype=dtype)
         if count.value:
             _check(getter(self._h, out.ctypes.data_as(C.POINTER(ctype)), count, C.byref(count)))
@@ -272,10 +260,10 @@ class EM:
         n, d = data.shape
         conv = C.c_int()
         if sample_weight is None:
-            _check(_l.mlpp_em_fit(self._h, _dp(data), C.c_uint64(n), d, C.byref(conv)))
+            _check(_l.mlpp_em_fit(self._h, _dp(data), n, d, C.byref(conv)))
         else:
             w = _lib.require_weights(sample_weight, n)
-            _check(_l.mlpp_em_fit_weighted(self._h, _dp(data), _dp(w), C.c_uint64(n), d, C.byref(conv)))
+            _check(_l.mlpp_em_fit_weighted(self._h, _dp(data), _dp(w), n, d, C.byref(conv)))
         return bool(conv.value)
 
     def _dims(self):
@@ -286,9 +274,7 @@ class EM:
     @property
     def number_components(self):
         """Number of Gaussian components."""
-        k = C.c_uint32()
-        _check(_l.mlpp_em_number_components(self._h, C.byref(k)))
-        return k.value
+        return _get(_l.mlpp_em_number_components, self._h, C.c_uint32)
 
     @property
     def means(self):
@@ -310,15 +296,13 @@ class EM:
         """Extension: rows [first_row, first_row + number_rows) of `responsibilities` without fetching the whole N x K block
         from the device (5 GB at N=10M, K=64)."""
         out = np.empty((int(number_rows), self.number_components), order="F")
-        _check(_l.mlpp_em_responsibilities_rows(self._h, C.c_uint64(int(first_row)), C.c_uint64(int(number_rows)), _dp(out)))
+        _check(_l.mlpp_em_responsibilities_rows(self._h, int(first_row), int(number_rows), _dp(out)))
         return out
 
     @property
     def log_likelihood(self):
         """Maximised log-likelihood."""
-        v = C.c_double()
-        _check(_l.mlpp_em_log_likelihood(self._h, C.byref(v)))
-        return v.value
+        return _get(_l.mlpp_em_log_likelihood, self._h, C.c_double)
 
     @property
     def mixing_probabilities(self):
@@ -347,7 +331,7 @@ class EM:
         X = _require_data(X)
         n, d = X.shape
         out = np.empty(n)
-        _check(_l.mlpp_em_score_samples(self._h, _dp(X), C.c_uint64(n), d, _dp(out)))
+        _check(_l.mlpp_em_score_samples(self._h, _dp(X), n, d, _dp(out)))
         return out
 
     def score(self, X):
@@ -366,7 +350,7 @@ class EM:
         X = _require_data(X)
         n, d = X.shape
         out = np.empty(n, dtype=np.uint32)
-        _check(_l.mlpp_em_predict(self._h, _dp(X), C.c_uint64(n), d, _lib.u32ptr(out)))
+        _check(_l.mlpp_em_predict(self._h, _dp(X), n, d, _lib.u32ptr(out)))
         return out
 
     def predict_proba(self, X):
@@ -374,7 +358,7 @@ class EM:
         X = _require_data(X)
         n, d = X.shape
         out = np.empty((n, self.number_components), order="F")
-        _check(_l.mlpp_em_predict_proba(self._h, _dp(X), C.c_uint64(n), d, _dp(out)))
+        _check(_l.mlpp_em_predict_proba(self._h, _dp(X), n, d, _dp(out)))
         return out
 
     def sample(self, n_samples, seed=0):
@@ -387,7 +371,7 @@ class EM:
             raise ValueError("sample(): n_samples must not be negative")
         d, _ = self._dims()
         X, labels = np.empty((n, d)), np.empty(n, dtype=np.uint32)
-        _check(_l.mlpp_em_sample(self._h, C.c_uint64(n), C.c_uint64(int(seed)), _dp(X), _lib.u32ptr(labels)))
+        _check(_l.mlpp_em_sample(self._h, n, int(seed), _dp(X), _lib.u32ptr(labels)))
         return X, labels
 
     def _observed(self, observed, name):
@@ -423,9 +407,8 @@ class EM:
         index = np.array(coordinates, dtype=np.uint32)
         out = np.empty((n, d - len(coordinates)))
         dens = np.empty(n) if return_log_density else None
-        _check(_l.mlpp_em_conditional_means(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n), _dp(out),
-                                            _dp(dens) if return_log_density else None))
-        return (out, dens) if return_log_density else out
+        _check(_l.mlpp_em_conditional_means(self._h, _lib.u32ptr(index), len(index), _dp(X), n, _dp(out), _dp(dens)))
+        return _lib._with_optional(out, dens)
 
     def impute(self, X, return_log_density=False, return_responsibilities=False):
         """Extension (imputation of a table with gaps): a copy of X (N x d, C-contiguous float64 like what `fit` takes) in which every
@@ -445,10 +428,8 @@ class EM:
         out = np.empty((n, d))
         dens = np.empty(n) if return_log_density else None
         resp = np.empty((n, self.number_components)) if return_responsibilities else None
-        _check(_l.mlpp_em_impute(self._h, _dp(X), C.c_uint64(n), C.c_uint32(d), _dp(out), _dp(dens) if return_log_density else None,
-                                 _dp(resp) if return_responsibilities else None))
-        extra = tuple(v for v in (dens, resp) if v is not None)
-        return (out,) + extra if extra else out
+        _check(_l.mlpp_em_impute(self._h, _dp(X), n, d, _dp(out), _dp(dens), _dp(resp)))
+        return _lib._with_optional(out, dens, resp)
 
     def conditional_variance(self, X_observed, observed, covariance=False, return_mean=False):
         """Extension (error bars on an imputed value, heteroscedastic regression bands): the predictive variance Var[x_M | x_O] under
@@ -466,9 +447,8 @@ class EM:
         dM = d - len(coordinates)
         out = np.empty((n, dM, dM) if covariance else (n, dM))
         mean = np.empty((n, dM)) if return_mean else None
-        _check(_l.mlpp_em_conditional_variances(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n),
-                                                C.c_int(int(bool(covariance))), _dp(out), _dp(mean) if return_mean else None))
-        return (out, mean) if return_mean else out
+        _check(_l.mlpp_em_conditional_variances(self._h, _lib.u32ptr(index), len(index), _dp(X), n, bool(covariance), _dp(out), _dp(mean)))
+        return _lib._with_optional(out, mean)
 
     def conditional_cdf(self, X_observed, observed, values):
         """Extension (exceedance probabilities, the probability integral transform, p-values of an observed value): the predictive
@@ -488,7 +468,7 @@ class EM:
             raise ValueError("conditional_cdf(): values must have one row per row of X_observed and one column per missing coordinate")
         index = np.array(coordinates, dtype=np.uint32)
         out = np.empty((n, dM))
-        _check(_l.mlpp_em_conditional_cdfs(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n), _dp(values), _dp(out)))
+        _check(_l.mlpp_em_conditional_cdfs(self._h, _lib.u32ptr(index), len(index), _dp(X), n, _dp(values), _dp(out)))
         return out
 
     def conditional_quantile(self, X_observed, observed, probabilities):
@@ -511,8 +491,7 @@ class EM:
             raise ValueError("conditional_quantile(): every probability must lie strictly inside (0, 1)")
         index = np.array(coordinates, dtype=np.uint32)
         out = np.empty((len(p), n, d - len(coordinates)))
-        _check(_l.mlpp_em_conditional_quantiles(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n), _dp(p),
-                                                C.c_uint64(len(p)), _dp(out)))
+        _check(_l.mlpp_em_conditional_quantiles(self._h, _lib.u32ptr(index), len(index), _dp(X), n, _dp(p), len(p), _dp(out)))
         return out
 
     def conditional_covariances(self, observed):
@@ -522,7 +501,7 @@ class EM:
         index = np.array(coordinates, dtype=np.uint32)
         dM = d - len(coordinates)
         out = np.empty((self.number_components, dM, dM))
-        _check(_l.mlpp_em_conditional_covariances(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(out)))
+        _check(_l.mlpp_em_conditional_covariances(self._h, _lib.u32ptr(index), len(index), _dp(out)))
         return out
 
     def conditional_sample(self, X_observed, observed, n_draws=1, seed=0, return_labels=False):
@@ -548,10 +527,9 @@ class EM:
         index = np.array(coordinates, dtype=np.uint32)
         out = np.empty((int(n_draws), n, d - len(coordinates)))
         labels = np.empty((int(n_draws), n), dtype=np.uint32) if return_labels else None
-        _check(_l.mlpp_em_conditional_samples(self._h, _lib.u32ptr(index), C.c_uint32(len(index)), _dp(X), C.c_uint64(n),
-                                              C.c_uint64(int(n_draws)), C.c_uint64(int(seed)), _dp(out),
-                                              _lib.u32ptr(labels) if return_labels else None))
-        return (out, labels) if return_labels else out
+        _check(_l.mlpp_em_conditional_samples(self._h, _lib.u32ptr(index), len(index), _dp(X), n, int(n_draws), int(seed), _dp(out),
+                                              _lib.u32ptr(labels)))
+        return _lib._with_optional(out, labels)
 
     @property
     def labels(self):
@@ -562,24 +540,18 @@ class EM:
 
     @property
     def converged(self):
-        v = C.c_int()
-        _check(_l.mlpp_em_converged(self._h, C.byref(v)))
-        return bool(v.value)
+        return bool(_get(_l.mlpp_em_converged, self._h, C.c_int))
 
     @property
     def steps_done(self):
-        v = C.c_uint32()
-        _check(_l.mlpp_em_steps_done(self._h, C.byref(v)))
-        return v.value
+        return _get(_l.mlpp_em_steps_done, self._h, C.c_uint32)
 
     @property
     def number_parameters(self):
         """Extension (model selection; scikit-learn's `_n_parameters`): the free parameters of the fitted mixture in the covariance
         mode it was fitted in -- full K d (d + 1) / 2, diag K d, tied d (d + 1) / 2, each plus K d + K - 1. No GPU needed.
         ValueError for a model that was not fitted."""
-        v = C.c_uint64()
-        _check(_l.mlpp_em_number_parameters(self._h, C.byref(v)))
-        return v.value
+        return _get(_l.mlpp_em_number_parameters, self._h, C.c_uint64)
 
     def bic(self, X):
         """Extension: the Bayesian information criterion of the fitted model on X (N x d, what `fit` takes), as scikit-learn defines
@@ -609,9 +581,8 @@ def silhouette_samples(X, labels, rows=None):
     n, d = X.shape
     labels, K, rows = _lib.silhouette_arguments(n, labels, rows)
     out = np.empty(n if rows is None else len(rows))
-    _check(_l.mlpp_silhouette_samples(_dp(X), C.c_uint64(n), C.c_uint32(d), _lib.u32ptr(labels), C.c_uint32(K),
-                                      None if rows is None else rows.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      C.c_uint64(0 if rows is None else len(rows)), _dp(out)))
+    _check(_l.mlpp_silhouette_samples(_dp(X), n, d, _lib.u32ptr(labels), K, None if rows is None else rows.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      0 if rows is None else len(rows), _dp(out)))
     return out
 
 
@@ -640,27 +611,22 @@ class KMeans:
     """Naive K-Means algorithm."""
 
     def __init__(self, number_clusters):
-        self._h = C.c_void_p()
-        _check(_l.mlpp_kmeans_create(int(number_clusters), C.byref(self._h)))
+        self._h = _created(_l.mlpp_kmeans_create, int(number_clusters))
         self._keep = []
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            _l.mlpp_kmeans_destroy(h)
-            self._h = None
+    __del__ = _deleter(_l.mlpp_kmeans_destroy)
 
     def set_seed(self, seed):
         """Sets the PRNG seed."""
-        _check(_l.mlpp_kmeans_set_seed(self._h, C.c_uint32(seed)))
+        _check(_l.mlpp_kmeans_set_seed(self._h, seed))
 
     def set_absolute_tolerance(self, absolute_tolerance):
         """Sets absolute tolerance."""
-        _check(_l.mlpp_kmeans_set_absolute_tolerance(self._h, C.c_double(absolute_tolerance)))
+        _check(_l.mlpp_kmeans_set_absolute_tolerance(self._h, absolute_tolerance))
 
     def set_maximum_steps(self, maximum_steps):
         """Sets maximum number of iterations."""
-        _check(_l.mlpp_kmeans_set_maximum_steps(self._h, C.c_uint32(maximum_steps)))
+        _check(_l.mlpp_kmeans_set_maximum_steps(self._h, maximum_steps))
 
     def set_centroids_initialiser(self, centroids_initialiser):
         """Sets the algorithm to initialise cluster centroids."""
@@ -671,11 +637,11 @@ class KMeans:
     def set_number_initialisations(self, centroids_initialiser):
         """Sets number of initialisations to try, to find the clusters with lowest inertia.
         (The keyword really is `centroids_initialiser` in the reference: cppyml/clustering.cpp:159.)"""
-        _check(_l.mlpp_kmeans_set_number_initialisations(self._h, C.c_uint32(centroids_initialiser)))
+        _check(_l.mlpp_kmeans_set_number_initialisations(self._h, centroids_initialiser))
 
     def set_verbose(self, verbose):
         """Turns on/off the verbose mode."""
-        _check(_l.mlpp_kmeans_set_verbose(self._h, int(bool(verbose))))
+        _check(_l.mlpp_kmeans_set_verbose(self._h, bool(verbose)))
 
     def fit(self, data, sample_weight=None):
         """Fits the clusters to the data (2D array with data points in rows). Returns True if the algorithm converged.
@@ -689,10 +655,10 @@ class KMeans:
         n, d = data.shape
         conv = C.c_int()
         if sample_weight is None:
-            _check(_l.mlpp_kmeans_fit(self._h, _dp(data), C.c_uint64(n), d, C.byref(conv)))
+            _check(_l.mlpp_kmeans_fit(self._h, _dp(data), n, d, C.byref(conv)))
         else:
             w = _lib.require_weights(sample_weight, n)
-            _check(_l.mlpp_kmeans_fit_weighted(self._h, _dp(data), _dp(w), C.c_uint64(n), d, C.byref(conv)))
+            _check(_l.mlpp_kmeans_fit_weighted(self._h, _dp(data), _dp(w), n, d, C.byref(conv)))
         return bool(conv.value)
 
     def _dims(self):
@@ -703,9 +669,7 @@ class KMeans:
     @property
     def number_clusters(self):
         """Number of clusters."""
-        k = C.c_uint32()
-        _check(_l.mlpp_kmeans_number_clusters(self._h, C.byref(k)))
-        return k.value
+        return _get(_l.mlpp_kmeans_number_clusters, self._h, C.c_uint32)
 
     @property
     def centroids(self):
@@ -735,9 +699,7 @@ class KMeans:
     @property
     def inertia(self):
         """Minimised inertia."""
-        v = C.c_double()
-        _check(_l.mlpp_kmeans_inertia(self._h, C.byref(v)))
-        return v.value
+        return _get(_l.mlpp_kmeans_inertia, self._h, C.c_double)
 
     def assign_label(self, x):
         """Given a data point x, assigns it to the closest cluster: (label, squared distance)."""
@@ -754,17 +716,13 @@ class KMeans:
         n, d = X.shape
         labels = np.empty(n, dtype=np.uint32)
         dist = np.empty(n) if return_distances else None
-        _check(_l.mlpp_kmeans_predict(self._h, _dp(X), C.c_uint64(n), d, _lib.u32ptr(labels), _dp(dist) if return_distances else None))
-        return (labels, dist) if return_distances else labels
+        _check(_l.mlpp_kmeans_predict(self._h, _dp(X), n, d, _lib.u32ptr(labels), _dp(dist)))
+        return _lib._with_optional(labels, dist)
 
     @property
     def converged(self):
-        v = C.c_int()
-        _check(_l.mlpp_kmeans_converged(self._h, C.byref(v)))
-        return bool(v.value)
+        return bool(_get(_l.mlpp_kmeans_converged, self._h, C.c_int))
 
     @property
     def steps_done(self):
-        v = C.c_uint32()
-        _check(_l.mlpp_kmeans_steps_done(self._h, C.byref(v)))
-        return v.value
+        return _get(_l.mlpp_kmeans_steps_done, self._h, C.c_uint32)

@@ -86,10 +86,7 @@ def test_entry_points_check_their_arguments_without_a_device():
     assert lib.mlhip_em_restarts_route(None, 3, 0, 2, C.byref(route), C.byref(per_launch)) == bad
     steps = (C.c_uint32 * 2)()
     x = (C.c_double * 64)()
-    lib.mlhip_em_iterate_restarts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32] + [C.c_void_p] * 3 + \
-        [C.c_uint32, C.c_double, C.c_double] + [C.c_void_p] * 5
     assert lib.mlhip_em_iterate_restarts(None, None, 3, 0, 2, x, x, x, 5, 0.0, 0.0, steps, conv, ll, None, C.byref(best)) == bad
-    lib.mlhip_em_iterate_restarts.argtypes = None
     count, value = C.c_uint32(), C.c_uint32()
     assert lib.mlpp_em_set_number_initialisations(None, 2) == bad
     assert lib.mlpp_em_number_initialisations(None, C.byref(value)) == bad

@@ -476,3 +476,28 @@ def test_kmeans_refuses_non_finite_data(ctx):
     with pytest.raises(ValueError):
         dt.kmeans_step(np.zeros((3, 4)))
     dt.close()
+
+
+def test_wrong_shapes_are_refused_and_leave_the_handle_usable(ctx):
+    """Every wrapper checks its arrays against the block before the library reads them: a wrong shape is a ValueError from the
+    binding, and the handle goes on giving the bits it gave before."""
+    rng = np.random.default_rng(5)
+    X = rng.standard_normal((64, 3))
+    X[:32] += 3.0
+    K = 2
+    pi, mu, S = np.full(K, 0.5), X[[0, 40]].copy(), np.stack([np.eye(3)] * K)
+    dt = _data(ctx, X)
+    want = dt.em_step(pi, mu, S)
+    bad_calls = [
+        lambda: dt.em_step(pi, mu, np.ones((2, 3))),
+        lambda: dt.em_expectation(pi, np.zeros((2, 2)), S),
+        lambda: dt.em_score(pi, mu, S, tied=True),
+        lambda: dt.kmeans_step(np.zeros((2, 2))),
+        lambda: dt.em_maximisation_from_labels(np.zeros(63, dtype=np.uint32), K),
+    ]
+    for call in bad_calls:
+        with pytest.raises(ValueError):
+            call()
+        got = dt.em_step(pi, mu, S)
+        assert got[0] == want[0] and all(np.array_equal(a, b) for a, b in zip(got[1:], want[1:]))
+    dt.close()
